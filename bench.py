@@ -17,6 +17,12 @@ fixed); `value_survey_count` is SURVEY.md 8(d)'s algorithmic count of the same s
 
 `--gpus N` without a launcher (WORLD_SIZE unset): this process starts N ranks of itself -- before anything touches the GPU -- and
 waits for them; under torchrun (WORLD_SIZE set) it must equal the world size.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, runs W untimed and N timed steps, writes the last step's outputs if
+`--dump-outputs DIR` is given, and prints the line: the headline and what the timed steps themselves give.  Everything else the line can
+carry -- the kernel roofline and its PMC passes, the launch-path comparison, the pp-ladder / CR-(T) / AO->MO / whole-calculation legs, the
+CPU baseline and the other workloads of the same run -- is measured only with `--full` (`--no-cpu-baseline`, `--no-extra`,
+`--steps-only` and `--no-live-pmc` thin out a `--full` run).
 """
 import argparse
 import ctypes
@@ -355,6 +361,23 @@ def real_molecule(name, rank, world, local, dist, cdev, torch, backend, jobdir):
 
 
 DEFAULT_SCALE = {"cfg5": 0.005}     # magnitude of the hashed integrals: keeps the first iterates of every workload finite
+T2_DUMP_MAX = 1 << 21               # --dump-outputs: T2 elements written (16 MB of float64); a larger T2 is sampled
+
+
+def dump_outputs(dirpath, eng, cc, e_t):
+    """`--dump-outputs DIR`: what a caller of the timed path holds after its last step, as float64 .npy files -- the energy and
+    residual norm afesp_ccsd_iterate returned (`ccsd_energy_residual`), E[T] and E(T) summed over the ranks (`t_energies`), and the
+    amplitudes the next step starts from: `t1` (o, v) whole, `t2` flattened in the engine's column-major (i, j, a, b) order -- whole up
+    to T2_DUMP_MAX elements, past that at T2_DUMP_MAX positions drawn with a fixed seed (sorted; config 5's T2 is 128 MB).  The
+    inputs are seeded, so the files of two builds compare element by element."""
+    os.makedirs(dirpath, exist_ok=True)
+    t1, t2 = eng.amplitudes()
+    t2 = t2.ravel(order="F")
+    if t2.size > T2_DUMP_MAX:
+        t2 = t2[np.sort(np.random.default_rng(20251016).integers(0, t2.size, T2_DUMP_MAX))]
+    out = {"ccsd_energy_residual": np.array(cc[:2]), "t_energies": np.asarray(e_t), "t1": t1, "t2": t2}
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 class Reducer:
@@ -525,7 +548,8 @@ def latest_profile(pattern):
     return files[-1] if files else None
 
 
-def measure(args, workload, steps, warmup, rank, world, local, dist, cdev, torch, jobdir, with_roofline=True, with_cpu=True):
+def measure(args, workload, steps, warmup, rank, world, local, dist, cdev, torch, jobdir, with_roofline=True, with_cpu=True,
+            dump_dir=None):
     """Run `warmup` untimed + `steps` timed steps of one workload; returns the result dictionary (rank 0) or None."""
     from afesp_amd.capi import Engine
     o, v = WORKLOADS[workload]
@@ -580,11 +604,11 @@ def measure(args, workload, steps, warmup, rank, world, local, dist, cdev, torch
     elif world > 1:
         split_check = "not attempted (launch-bound system, no product communicator, or AFESP_CC_SHARD=0)"
 
-    acc = {"iter": 0.0, "trip": 0.0, "shard": 0.0, "allred": 0.0, "last": None}
+    acc = {"iter": 0.0, "trip": 0.0, "shard": 0.0, "allred": 0.0, "last": None, "cc": None}
 
     def step(timed):
         t0 = time.perf_counter()
-        eng.ccsd_iterate()
+        acc["cc"] = eng.ccsd_iterate()
         eng.ccsd_diis()
         t1 = time.perf_counter()
         # the benchmark configurations are CCSD(T)_spatial: E[T] and E(T) (the renormalised types' y / D sums are extra)
@@ -608,6 +632,8 @@ def measure(args, workload, steps, warmup, rank, world, local, dist, cdev, torch
     barrier()
     elapsed = time.perf_counter() - t0
     prof = eng.profile(False)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, eng, acc["cc"], acc["last"])
     # per rank, for the record of an N > 1 run: this rank's CCSD iteration, its (T) shard and the all-reduce behind it
     mine = [acc["iter"] / steps * 1e3, acc["shard"] / steps * 1e3, acc["allred"] / steps * 1e6, float(hi - lo)]
     per_rank = None
@@ -825,7 +851,8 @@ def dry_ranks(n, argv):
     a key is missing.  At most 6 ranks: a GPU box admits six processes on its card."""
     if not 2 <= n <= 6:
         raise SystemExit("bench.py --dry-ranks: 2 ... 6 ranks (one GPU admits six processes)")
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mid_large", "--steps", "2", "--warmup", "1", "--no-live-pmc"]
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mid_large", "--steps", "2", "--warmup", "1", "--no-live-pmc",
+            "--full"]
     lines = {}
     for tag, extra in (("one_rank", ["--gpus", "1"]), ("n_ranks", ["--gpus", str(n), "--backend", "gloo"])):
         r = subprocess.run(base + extra, capture_output=True, text=True, env=dict(os.environ, AFESP_CC_SHARD=os.environ.get("AFESP_CC_SHARD", "1")))
@@ -864,7 +891,15 @@ def main():
     ap.add_argument("--dry-ranks", type=int, default=0,
                     help="rehearse the N-rank control flow on one GPU (host transport, mid-size system) and check the emitted line's keys "
                          "against a one-rank run: see dry_ranks()")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline steps: roofline (with its live PMC passes), launch-path comparison, "
+                         "pp-ladder / CR-(T) / AO->MO / whole-calculation legs, CPU baseline, and the same-run workloads that "
+                         "--no-extra leaves out; without it a run is set-up, warm-up, timed steps and the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64): see dump_outputs()")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.dry_ranks:
         sys.exit(dry_ranks(args.dry_ranks, sys.argv[1:]))
@@ -894,9 +929,10 @@ def main():
         torch.cuda.set_device(local)
     cdev = "cpu" if (world > 1 and args.backend == "gloo") else f"cuda:{local}"   # where torch's collectives run
 
-    res = measure(args, args.workload, args.steps, args.warmup, rank, world, local, dist, cdev, torch, jobdir, with_roofline=args.legs)
+    res = measure(args, args.workload, args.steps, args.warmup, rank, world, local, dist, cdev, torch, jobdir,
+                  with_roofline=args.full and args.legs, with_cpu=args.full, dump_dir=args.dump_outputs)
     others = {}
-    if args.extra:
+    if args.full and args.extra:
         if args.workload != "h2o_tz":
             # BASELINE config 2 shape: a step is ~0.6 ms, latency-bound (no roofline meaning): 50 steps, after enough warm-up
             # for the engine to have captured the iteration's graph (it waits for 40 calls: a real solve is shorter)

@@ -119,7 +119,7 @@ def test_bench_two_gpus_over_rccl():
     if _gpus() < 2:
         pytest.skip(f"needs 2 GPUs (this box has {_gpus()})")
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "n2", "--steps", "3", "--warmup", "1",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=1500)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stdout + res.stderr
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2
@@ -186,7 +186,7 @@ def test_bench_gpus_flag_spawns_ranks(tmp_path):
     """`python bench.py --gpus 2 --backend gloo` on a one-GPU box: the parent starts two ranks before touching the GPU; the line
     says n_gpus 2 and the ranks counted by the all-reduce of ones are 2."""
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "n2",
-                          "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                          "--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout + res.stderr
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2
@@ -197,7 +197,7 @@ def test_bench_gpus_flag_spawns_ranks(tmp_path):
     assert line["t_shard_ms_min"] <= line["t_shard_ms_max"] and sum(line["per_rank"]["t_shard_triples"]) == line["config"]["triples"]
     assert line["ccsd_split"] is False and "launch-bound" in line["ccsd_split_check"]
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "n2", "--steps", "3", "--warmup", "1", "--no-extra",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900)
     assert one.returncode == 0, one.stdout + one.stderr
     ref = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][-1])
     assert ref["n_gpus"] == 1 and np.max(np.abs(np.array(ref["e_t"]) - np.array(line["e_t"]))) < 1e-12

@@ -3,6 +3,7 @@ import os
 import re
 import shutil
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -119,6 +120,49 @@ def test_bench_flop_counts_match_the_survey_table():
     assert abs(bench.flops_t_sym(20, 200) - 3.25e13) < 2e-3 * 3.25e13
     # the two cheaper evaluations of the ladder are counted as what they execute
     assert bench.flops_iter(20, 200) < ref_iter(20, 200)
+
+
+def test_bench_dump_outputs_are_float64_bounded_and_repeatable(tmp_path):
+    """`bench.py --dump-outputs DIR`: float64 .npy files, at most 64 MB in all at config 5 (its T2 alone is 128 MB: sampled at fixed
+    seeded positions), the same positions every time, and a T2 small enough written whole in the engine's column-major order."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class FakeEngine:
+        def __init__(self, o, v):
+            rng = np.random.default_rng(o * 1000 + v)
+            self.t1 = rng.standard_normal((o, v))
+            self.t2 = np.asfortranarray(rng.standard_normal((o, o, v, v)))
+
+        def amplitudes(self):
+            return self.t1, self.t2
+
+    big = FakeEngine(20, 200)
+    files = {}
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), big, (-0.5, 1e-3, False), np.array([-1e-3, -2e-3]))
+        files[run] = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    assert sorted(files["a"]) == ["ccsd_energy_residual.npy", "t1.npy", "t2.npy", "t_energies.npy"]
+    for f, arr in files["a"].items():
+        assert arr.dtype == np.float64 and np.array_equal(arr, files["b"][f]), f
+    assert files["a"]["t2.npy"].size == bench.T2_DUMP_MAX
+    assert np.isin(files["a"]["t2.npy"], big.t2).all()
+    assert np.array_equal(files["a"]["t1.npy"], big.t1) and list(files["a"]["ccsd_energy_residual.npy"]) == [-0.5, 1e-3]
+    small = FakeEngine(7, 21)
+    bench.dump_outputs(str(tmp_path / "s"), small, (0.0, 0.0, True), np.zeros(2))
+    assert np.array_equal(np.load(tmp_path / "s" / "t2.npy"), small.t2.ravel(order="F"))
+
+
+def test_bench_options_for_plain_and_full_runs():
+    """The plain run and its extras: `--full` and `--dump-outputs` are accepted, `--steps` below one is refused before any GPU work."""
+    helptext = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert helptext.returncode == 0 and "--full" in helptext.stdout and "--dump-outputs" in helptext.stdout
+    bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert bad.returncode != 0 and "--steps" in bad.stderr
 
 
 def test_multi_rank_launcher_ends_the_job_when_a_rank_fails(tmp_path):

@@ -3,7 +3,7 @@
 # (rocm-smi read-only queries): is the fp64 MFMA peak of the data sheet (2.4 GHz) the clock the (T) launches actually run at?
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 OUT="$(realpath -m "$1")"
-python3 "$HERE/bench.py" --steps 12 --warmup 2 --no-cpu-baseline --no-extra --no-live-pmc > /tmp/clock_bench.json 2> /tmp/clock_bench.err &
+python3 "$HERE/bench.py" --full --steps 12 --warmup 2 --no-cpu-baseline --no-extra --no-live-pmc > /tmp/clock_bench.json 2> /tmp/clock_bench.err &
 BP=$!
 : > "$OUT"
 for i in $(seq 1 60); do
