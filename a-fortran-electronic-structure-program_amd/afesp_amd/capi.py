@@ -30,6 +30,7 @@ EXPORTS = [
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
+    "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -104,6 +105,9 @@ def load_library():
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
     L.afesp_set_eri.argtypes = [C.c_void_p, i64, _dp]
     L.afesp_build_fock.argtypes = [C.c_void_p, i64, _dp, _dp, _dp]
+    L.afesp_build_fock_uhf.argtypes = [C.c_void_p, i64, _dp, _dp, _dp, _dp, _dp]
+    L.afesp_ao2mo_ump2.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, _dp, _opt, _opt, _opt, _opt, C.POINTER(dbl)]
+    L.afesp_ccsd_uso_init.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.c_int]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -339,6 +343,38 @@ class Engine:
         out = np.zeros(nbasis * nbasis)
         self._chk(self.L.afesp_build_fock(self.h, nbasis, _f(density), _f(core_hamil), out))
         return out.reshape((nbasis, nbasis), order="F")
+
+    def build_fock_uhf(self, nbasis, dens_a, dens_b, core_hamil):
+        """F_s = H + J[Da + Db] - K[D_s] (s = alpha, beta) on the device-resident packed AO integrals -> (F_alpha, F_beta)."""
+        fa, fb = np.zeros(nbasis * nbasis), np.zeros(nbasis * nbasis)
+        self._chk(self.L.afesp_build_fock_uhf(self.h, nbasis, _f(dens_a), _f(dens_b), _f(core_hamil), fa, fb))
+        return fa.reshape((nbasis, nbasis), order="F"), fb.reshape((nbasis, nbasis), order="F")
+
+    def do_ump2(self, nbasis, nalpha, nbeta, coeff_a, coeff_b, levels_a, levels_b, eri_packed=None, want_eri_mo=True):
+        """-> (E(UMP2), (aa|aa) packed, (aa|bb) as [npair, npair] (row: alpha pair), (bb|bb) packed); the three blocks stay on
+        the device for init_cc_uspinorb.  eri_packed None: the AO integrals set_eri / read_eri_text left there."""
+        e2 = dbl(0.0)
+        npr = nbasis * (nbasis + 1) // 2
+        aa = np.zeros(self.L.afesp_neri(nbasis)) if want_eri_mo else None
+        bb = np.zeros(self.L.afesp_neri(nbasis)) if want_eri_mo else None
+        ab = np.zeros(npr * npr) if want_eri_mo else None
+        src = None
+        if eri_packed is not None:
+            eri_packed = np.ascontiguousarray(eri_packed, dtype=np.float64)
+            src = eri_packed.ctypes.data_as(C.c_void_p)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.L.afesp_ao2mo_ump2(self.h, nbasis, nalpha, nbeta, _f(coeff_a), _f(coeff_b),
+                                          np.ascontiguousarray(levels_a, dtype=np.float64), np.ascontiguousarray(levels_b, dtype=np.float64),
+                                          src, ptr(aa), ptr(ab), ptr(bb), C.byref(e2)))
+        return e2.value, aa, (ab.reshape((npr, npr)) if ab is not None else None), bb
+
+    def init_cc_uspinorb(self, nbasis, nalpha, nbeta, levels_a, levels_b, diis_nerr=8):
+        """The spin-orbital state from the blocks do_ump2 left; then the so_* methods drive it (occupied: alpha then beta,
+        virtual: alpha then beta)."""
+        self.so_o = int(nalpha + nbeta)
+        self.so_v = int(2 * nbasis - self.so_o)
+        self._chk(self.L.afesp_ccsd_uso_init(self.h, nbasis, nalpha, nbeta, np.ascontiguousarray(levels_a, dtype=np.float64),
+                                             np.ascontiguousarray(levels_b, dtype=np.float64), diis_nerr))
 
     def write_fcidump(self, path, nbasis):
         n = i64()

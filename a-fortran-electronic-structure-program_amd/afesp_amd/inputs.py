@@ -32,6 +32,8 @@ class SystemIn:
     write_fcidump: bool = False
     scf_read_guess: bool = False
     scf_write_guess: bool = False
+    charge: int = 0                 # open-shell types only (UHF_scf, UMP2, UCCSD, UCCSD(T))
+    multiplicity: int = 1           # 2S + 1
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -55,7 +57,13 @@ _CALC_TYPES = {
     "RCCSD[T]_spatial": ("CCSD(T)", True, False, True, False),
     "CRCCSD(T)_spatial": ("CCSD(T)", True, True, False, True),
     "CRCCSD[T]_spatial": ("CCSD(T)", True, False, False, True),
+    # open-shell types on canonical UHF orbitals (no counterpart in the reference, whose "UHF" runs RHF)
+    "UHF_scf": ("UHF", False, False, False, False),
+    "UMP2": ("UMP2", False, False, False, False),
+    "UCCSD": ("UCCSD", False, False, False, False),
+    "UCCSD(T)": ("UCCSD(T)", False, False, False, False),
 }
+OPEN_SHELL_TYPES = ("UHF_scf", "UMP2", "UCCSD", "UCCSD(T)")
 
 
 def _parse_value(text: str):
@@ -89,7 +97,24 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("Unrecognised calculation type!")   # system.f90:163
     (sysin.level, sysin.restricted, sysin.ccsd_t_paren, sysin.ccsd_t_renorm,
      sysin.ccsd_t_comp_renorm) = _CALC_TYPES[sysin.calc_type]
+    if not isinstance(sysin.charge, int) or isinstance(sysin.charge, bool) or not isinstance(sysin.multiplicity, int) \
+            or isinstance(sysin.multiplicity, bool) or sysin.multiplicity < 1:
+        raise ValueError("invalid input file format!")
+    if (sysin.charge, sysin.multiplicity) != (0, 1) and sysin.calc_type not in OPEN_SHELL_TYPES:
+        raise ValueError("charge and multiplicity need an open-shell calculation type!")
     return sysin
+
+
+def spin_counts(sysin: SystemIn, nuclear_charge: int, nbasis: int) -> tuple[int, int]:
+    """(n_alpha, n_beta) of nel = sum Z - charge electrons at multiplicity 2S + 1."""
+    nel = nuclear_charge - sysin.charge
+    twice_a = nel + sysin.multiplicity - 1
+    if nel < 0 or twice_a % 2:
+        raise ValueError("charge and multiplicity do not fit the electron count!")
+    na, nb = twice_a // 2, (nel - sysin.multiplicity + 1) // 2
+    if nb < 0 or na > nbasis:
+        raise ValueError("charge and multiplicity do not fit the electron count!")
+    return na, nb
 
 
 def eri_index(i, j, k, l):
@@ -181,6 +206,11 @@ _ENERGY_LINES = {
     "T1 diagnostic": "t1_diag",
     "D[T]": "d_bt",
     "D(T)": "d_pt",
+    "UHF energy": "uhf_total",
+    "<S^2>": "s2",
+    "UMP2 correlation energy": "ump2_corr",
+    "UCCSD correlation energy": "uccsd_corr",
+    "UCCSD(T) correlation energy": "uccsd_pt_corr",
     "Nuclear repulsion": "e_nuc",
     "Total energy": "total",
 }

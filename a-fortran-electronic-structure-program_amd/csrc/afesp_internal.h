@@ -280,12 +280,20 @@ void k_square_transpose(Context& cx, double* out, const double* in, int64_t n); 
 void k_pair_square_packed(Context& cx, double* out, const double* g, int n, int64_t c_begin, int64_t c_end);   // out(k,l,P) = g(P, tri(k,l))
 void k_tri_pack(Context& cx, double* g, const double* half, int n, int64_t k_begin, int64_t k_end);           // g(PQ,K) = half(q,p,K)
 void k_pack_pairs(Context& cx, double* packed, const double* full, int n, int64_t p_begin = 0, int64_t p_end = -1, int ld = 0);
+void k_pack_cols(Context& cx, double* cols, const double* full, int n);   // cols[PQ np + RS] = full(s,r,PQ), every RS
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);
 // Fock matrix from the half-unpacked integrals u(x,y,P) (k_unpack_half); work holds k_build_fock_work(n) doubles
 void k_build_fock(Context& cx, double* fock, const double* hcore, const double* dens, const double* u, double* work, int n, int ld = 0);
 int64_t k_build_fock_work(int n);
+// the unrestricted pair F_s = H + J[Da + Db] - K[D_s] on the same integrals; work holds k_build_fock_uhf_work(n) doubles
+void k_build_fock_uhf(Context& cx, double* fa, double* fb, const double* hcore, const double* da, const double* db, const double* u,
+                      double* work, int n, int ld = 0);
+int64_t k_build_fock_uhf_work(int n);
+// E(UMP2) from the resident alpha-alpha / beta-beta packed and alpha-beta full blocks (afesp_ao2mo_ump2), one launch, on the host
+double k_ump2(Context& cx, const double* aa, const double* bb, const double* ab, const double* ea_dev, const double* eb_dev, int n, int na,
+              int nb);
 double* host_scalars(Context& cx, int n);
 double* host_scalars_slot(Context& cx, double* seq);          // a kernel of the caller publishes itself (contract.hip); nullptr: use host_scalars
 double* host_scalars_wait(Context& cx, int n, double seq);     // polls for that sequence number, returns the n values on the host
@@ -299,6 +307,7 @@ void preload_contract();
 void preload_kernels();
 void preload_small_path_kernels();   // kernels.hip: per-kernel first-use resolution of what a small system launches
 void preload_ccsd_so();
+void preload_uhf_kernels();   // kernels.hip: the open-shell Fock build, the mixed-spin transform and UMP2
 void preload_fused();
 void preload_triples();   // copies cx.scal[0..n) to pinned host memory and synchronises
 

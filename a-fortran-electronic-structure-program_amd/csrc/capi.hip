@@ -60,6 +60,10 @@ struct afesp_ctx {
     const double *pad_a = nullptr, *pad_b = nullptr;
     int64_t pad_n = 0, pad_ld = 0, pad_epoch = -1;
     int64_t half_n = 0, half_ld = 0, half_epoch = -1;   // scratch "ao2mo_a" holds the half-unpacked AO integrals of this basis size / leading dimension / epoch
+    // the UHF MO integrals left by afesp_ao2mo_ump2 for afesp_ccsd_uso_init: alpha-alpha and beta-beta packed, alpha-beta full
+    // (kept apart from eri_mo_dev: the RHF calls never see them, nor they the RHF ones)
+    double *uhf_aa = nullptr, *uhf_bb = nullptr, *uhf_ab = nullptr;
+    int64_t uhf_n = 0;
 };
 
 namespace {
@@ -315,6 +319,7 @@ int afesp_ctx_create(int device, afesp_ctx** out)
                 timed("small path", preload_small_path_kernels);
                 timed("triples", preload_triples);
                 timed("ccsd_so", preload_ccsd_so);
+                timed("uhf", preload_uhf_kernels);
                 if (knobs().preload_gett) timed("gett", preload_gett);
             });
         }
@@ -548,6 +553,11 @@ int afesp_ao2mo_mp2(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, const double* 
             throw Error(1, "afesp_ao2mo_mp2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
         // upload buffer, then the packed MO integrals; a transform of the same basis size overwrites the previous result
         cx.drop_scratch("t_");   // the (T) pool of a previous system holds the blocks the two temporaries below were
+        if (ctx->uhf_aa) {       // an RHF transform ends the open-shell calculation: its integral blocks go back to the arena
+            cx.release(ctx->uhf_aa); cx.release(ctx->uhf_bb); cx.release(ctx->uhf_ab);
+            ctx->uhf_aa = ctx->uhf_bb = ctx->uhf_ab = nullptr;
+            ctx->uhf_n = 0;
+        }
         double* packed = ctx->eri_mo_dev;
         if (ctx->cc.eri_src == packed) ctx->cc.eri_src = nullptr;   // a solver state initialised from them can no longer form <ef|ab>
         if (!packed || ctx->eri_mo_n != n) {
@@ -1274,6 +1284,161 @@ int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t)
         AFESP_HIP(hipSetDevice(ctx->cx.device));
         const double e = so_triples(ctx->cx, ctx->so, t_begin, t_end);
         if (e_t) *e_t = e;
+    });
+}
+
+// ---------------------------------------------------------------- open-shell (UHF-based) path
+int afesp_build_fock_uhf(afesp_ctx* ctx, int64_t nbasis, const double* dens_a, const double* dens_b, const double* core_hamil,
+                         double* fock_a, double* fock_b)
+{
+    return guarded(ctx, [&] {
+        Context& cx = ctx->cx;
+        AFESP_HIP(hipSetDevice(cx.device));
+        if (!ctx->eri_ao_dev || ctx->eri_ao_n != nbasis || !dens_a || !dens_b || !core_hamil || !fock_a || !fock_b)
+            throw Error(1, "afesp_build_fock_uhf: no AO integrals resident for this basis size (afesp_read_eri_text / afesp_set_eri)");
+        const int64_t n2 = nbasis * nbasis;
+        double* buf = cx.scratch("fock_uio", 5 * n2);   // [ Da | Db | H | Fa | Fb ]
+        AFESP_HIP(hipMemcpyAsync(buf, dens_a, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(buf + n2, dens_b, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(buf + 2 * n2, core_hamil, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        // the half-unpacked integrals afesp_build_fock keeps (same buffer, same validity)
+        const int64_t np = nbasis * (nbasis + 1) / 2, L = ao2mo_ld(nbasis);
+        double* u = cx.scratch("ao2mo_a", L * nbasis * np + 16);
+        if (ctx->half_n != nbasis || ctx->half_ld != L || ctx->half_epoch != cx.scratch_epoch) {
+            if (ctx->pad_n != nbasis || ctx->pad_ld != L) ctx->pad_n = 0;
+            k_unpack_half(cx, u, ctx->eri_ao_dev, (int)nbasis, 0, -1, (int)L);
+            ctx->half_n = nbasis;
+            ctx->half_ld = L;
+            ctx->half_epoch = cx.scratch_epoch;
+        }
+        double* work = cx.scratch("fock_uwork", k_build_fock_uhf_work((int)nbasis));
+        ctx->half_epoch = cx.scratch_epoch;   // (growing the work buffer moves the epoch, not u)
+        k_build_fock_uhf(cx, buf + 3 * n2, buf + 4 * n2, buf + 2 * n2, buf, buf + n2, u, work, (int)nbasis, (int)L);
+        AFESP_HIP(hipMemcpyAsync(fock_a, buf + 3 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(fock_b, buf + 4 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    });
+}
+
+// (aa|aa), (bb|bb) and (aa|bb) from one set of AO integrals: the first pair of quarter transforms with C_a is shared by the first and
+// the third block, the second pair runs with C_a (packed, RS <= PQ) and with C_b (every RS: no 8-fold symmetry is left), then the whole
+// transform once more with C_b.
+int afesp_ao2mo_ump2(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* coeff_a, const double* coeff_b,
+                     const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab,
+                     double* eri_bb, double* e_ump2)
+{
+    return guarded(ctx, [&] {
+        Context& cx = ctx->cx;
+        AFESP_HIP(hipSetDevice(cx.device));
+        const int64_t n = nbasis, na = nalpha, nb = nbeta;
+        if (n <= 0 || n > 1024 || na < 0 || nb < 0 || na > n || nb > n || na + nb <= 0 || !coeff_a || !coeff_b || !levels_a || !levels_b)
+            throw Error(1, "afesp_ao2mo_ump2: bad extents");
+        if (ao2mo_blocked(n))
+            throw Error(1, "afesp_ao2mo_ump2: basis too large (only the slab-blocked transform fits, and it has no open-shell form)");
+        if (!eri_packed && (!ctx->eri_ao_dev || ctx->eri_ao_n != n))
+            throw Error(1, "afesp_ao2mo_ump2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
+        cx.drop_scratch("t_");
+        cx.drop_scratch("ao2mo_");   // (the temporaries are sized below; what they held goes back to the arena)
+        const int64_t ne = neri_of(n), np = n * (n + 1) / 2;
+        // device memory: the temporaries (two npair^2 for the pair form, three n^2 npair for the gather-GEMM form) and, for a new
+        // basis size, the three result blocks, against what the device has free plus what the context's arena holds idle
+        {
+            const double tmp = n <= 64 ? 2.0 * np * np : 3.0 * n * n * np;
+            const double blocks = (ctx->uhf_n == n && ctx->uhf_aa) ? 0.0 : 2.0 * ne + (double)np * np;
+            if (ctx->uhf_n != n && ctx->uhf_aa) {   // (blocks of another basis size: returned before their successors are sized)
+                cx.release(ctx->uhf_aa); cx.release(ctx->uhf_bb); cx.release(ctx->uhf_ab);
+                ctx->uhf_aa = ctx->uhf_bb = ctx->uhf_ab = nullptr;
+                ctx->uhf_n = 0;
+            }
+            size_t free_b = 0, total_b = 0;
+            AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+            if (8.0 * (tmp + blocks + 4.0 * n * n) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+                throw Error(1, "afesp_ao2mo_ump2: the open-shell transform of this basis does not fit the free device memory");
+        }
+        if (ctx->uhf_n != n || !ctx->uhf_aa) {
+            cx.release(ctx->uhf_aa); cx.release(ctx->uhf_bb); cx.release(ctx->uhf_ab);
+            ctx->uhf_aa = ctx->uhf_bb = ctx->uhf_ab = nullptr;
+            ctx->uhf_n = 0;
+            ctx->uhf_aa = cx.alloc_raw(ne);
+            ctx->uhf_bb = cx.alloc_raw(ne);
+            ctx->uhf_ab = cx.alloc_raw(np * np);
+            ctx->uhf_n = n;
+        }
+        double *aa = ctx->uhf_aa, *bb = ctx->uhf_bb, *ab = ctx->uhf_ab;
+        const double* ao = ctx->eri_ao_dev;
+        if (eri_packed) {   // (into the beta-beta block: every read of the AO integrals precedes its one write)
+            AFESP_HIP(hipMemcpyAsync(bb, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+            ao = bb;
+        }
+        Tensor Ca = view(cx.scratch("ao2mo_c", n * n), {n, n}), Cb = view(cx.scratch("ao2mo_cb", n * n), {n, n});
+        AFESP_HIP(hipMemcpyAsync(Ca.d, coeff_a, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(Cb.d, coeff_b, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+        // the temporaries are the RHF transform's (dense columns of n): whatever the Fock build or an LDS-DMA transform left there is gone
+        ctx->half_n = 0;
+        ctx->pad_n = 0;
+        Tensor Ta = view(cx.scratch("ao2mo_a", n * n * np + 16), {n, n, np}), Tb = view(cx.scratch("ao2mo_b", n * n * np + 16), {n, n, np});
+        if (n <= 64) {
+            k_pair_xform(cx, Tb.d, ao, Ca.d, (int)n, np, 1);        // (ij|K) -> g(PQ, K), C_a
+            k_square_transpose(cx, Ta.d, Tb.d, np);                 // g(K, PQ)
+            k_pair_xform(cx, aa, Ta.d, Ca.d, (int)n, np, 2);        // (rs|PQ), RS <= PQ, C_a
+            k_pair_xform(cx, ab, Ta.d, Cb.d, (int)n, np, 3);        // (rs|PQ), every RS, C_b
+            k_pair_xform(cx, Tb.d, ao, Cb.d, (int)n, np, 1);        // and the beta-beta block
+            k_square_transpose(cx, Ta.d, Tb.d, np);
+            k_pair_xform(cx, bb, Ta.d, Cb.d, (int)n, np, 2);
+        } else {
+            Tensor Tc = view(cx.scratch("ao2mo_c3", n * n * np), {n, n, np});
+            k_unpack_half(cx, Ta.d, ao, (int)n);
+            contract(cx, 1.0, Ca, "pi", Ta, "ijK", 0.0, Tb, "pjK");
+            contract(cx, 1.0, Ca, "qj", Tb, "pjK", 0.0, Ta, "pqK");
+            k_pair_transpose(cx, Tb.d, Ta.d, (int)n);                // (kl|PQ), alpha PQ
+            contract(cx, 1.0, Ca, "rk", Tb, "klP", 0.0, Ta, "rlP");
+            contract(cx, 1.0, Ca, "sl", Ta, "rlP", 0.0, Tc, "rsP");
+            k_pack_pairs(cx, aa, Tc.d, (int)n);
+            contract(cx, 1.0, Cb, "rk", Tb, "klP", 0.0, Ta, "rlP");
+            contract(cx, 1.0, Cb, "sl", Ta, "rlP", 0.0, Tc, "rsP");
+            k_pack_cols(cx, ab, Tc.d, (int)n);
+            k_unpack_half(cx, Ta.d, ao, (int)n);
+            contract(cx, 1.0, Cb, "pi", Ta, "ijK", 0.0, Tb, "pjK");
+            contract(cx, 1.0, Cb, "qj", Tb, "pjK", 0.0, Ta, "pqK");
+            k_pair_transpose(cx, Tb.d, Ta.d, (int)n);
+            contract(cx, 1.0, Cb, "rk", Tb, "klP", 0.0, Ta, "rlP");
+            contract(cx, 1.0, Cb, "sl", Ta, "rlP", 0.0, Tc, "rsP");
+            k_pack_pairs(cx, bb, Tc.d, (int)n);
+        }
+        double* ea = cx.scratch("ao2mo_ea", 2 * n);
+        AFESP_HIP(hipMemcpyAsync(ea, levels_a, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(ea + n, levels_b, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+        const double e2 = k_ump2(cx, aa, bb, ab, ea, ea + n, (int)n, (int)na, (int)nb);
+        if (e_ump2) *e_ump2 = e2;
+        if (eri_aa) AFESP_HIP(hipMemcpyAsync(eri_aa, aa, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+        if (eri_bb) AFESP_HIP(hipMemcpyAsync(eri_bb, bb, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+        if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    });
+}
+
+int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* levels_a, const double* levels_b,
+                        int diis_n_errmat)
+{
+    return guarded(ctx, [&] {
+        Context& cx = ctx->cx;
+        AFESP_HIP(hipSetDevice(cx.device));
+        if (nbasis <= 0 || nbasis > 512 || nalpha < 0 || nbeta < 0 || nalpha > nbasis || nbeta > nbasis || nalpha + nbeta <= 0 ||
+            nalpha + nbeta >= 2 * nbasis || !levels_a || !levels_b)
+            throw Error(1, "afesp_ccsd_uso_init: bad extents");
+        if (!ctx->uhf_aa || ctx->uhf_n != nbasis)
+            throw Error(1, "afesp_ccsd_uso_init: no UHF MO integrals resident for this basis size (call afesp_ao2mo_ump2 first)");
+        const int64_t o = nalpha + nbeta, v = 2 * nbasis - o;
+        cx.drop_scratch("ao2mo_");   // the AO->MO temporaries
+        ctx->so_programs_reset();
+        so_free(cx, ctx->so);        // (a previous state's memory counts as available)
+        // against the free device memory plus the context's idle blocks: the resident UHF (and RHF) integral blocks are in use
+        size_t free_b = 0, total_b = 0;
+        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (so_state_bytes(o, v, diis_n_errmat) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+            throw Error(1, "afesp_ccsd_uso_init: the dense spin-orbital state of this system does not fit the free device memory");
+        so_init_uhf(cx, ctx->so, (int)nbasis, (int)nalpha, (int)nbeta, ctx->uhf_aa, ctx->uhf_bb, ctx->uhf_ab, levels_a, levels_b, diis_n_errmat);
+        ctx->so.amp_epoch = ++cx.amp_clock;
     });
 }
 

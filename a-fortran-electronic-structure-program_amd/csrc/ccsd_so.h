@@ -11,7 +11,8 @@ struct SOState : DiisRing {
     int o = 0, v = 0, n = 0;
     bool ready = false;
     bool foo_as_published = false;   // see so_build_F
-    double* e = nullptr;             // spatial orbital energies on device, length n
+    double* e = nullptr;             // spatial orbital energies on device, length n (the RHF-fed state)
+    double* lev = nullptr;           // ... or the level of every spin orbital, length o + v (the UHF-fed state, so_init_uhf)
     // antisymmetrised slices <pq||rs> (ccsd.f90:193-207)
     Tensor oooo, ooov, ovoo, oovo, oovv, ovvo, ovvv, vovv, vvvv;
     Tensor D1, D2, t1, t2, t2_old, r1, r2;
@@ -30,6 +31,14 @@ struct SOState : DiisRing {
 // eri_mo_dev: packed chemist MO integrals on the device (length neri(nbasis)); e_host: spatial orbital energies (host)
 void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_dev, const double* e_host, int diis_nerr,
              bool foo_as_published);
+// The same state from canonical UHF orbitals (n spatial functions, na alpha and nb beta electrons).  Spin-orbital order: occupied =
+// alpha occupied (na), then beta occupied (nb); virtual = alpha virtual (n - na), then beta virtual (n - nb) -- o = na + nb, v = 2n - o.
+// aa / bb: packed (8-fold) alpha-alpha / beta-beta MO integrals on the device; ab: ab[tri(p,q) npair + tri(r,s)] = (p q | r s),
+// pq alpha, rs beta.  ea / eb: the n alpha / beta orbital energies (host).  F_mi always takes Stanton's published order.
+void so_init_uhf(Context& cx, SOState& s, int nbasis, int na, int nb, const double* aa, const double* bb, const double* ab,
+                 const double* ea_host, const double* eb_host, int diis_nerr);
+// device bytes the dense spin-orbital state of o occupied and v virtual spin orbitals needs (iteration and (T) working set)
+double so_state_bytes(int64_t o, int64_t v, int diis_nerr);
 void so_free(Context& cx, SOState& s);
 void so_intermediates(Context& cx, SOState& s);   // build_tau, build_F, build_W
 void so_amplitudes(Context& cx, SOState& s);      // update_amplitudes

@@ -35,11 +35,52 @@ __global__ void slice_asym_kernel(double* out, const double* packed, int d0, int
     }
 }
 
+// The same slices from the UHF blocks: spin orbital x is spatial orbital tab[x] / 2 of spin tab[x] & 1 (0 alpha, 1 beta; so_init_uhf),
+// <pq|rs> = (PR|QS)_{sp sq} [sp = sr][sq = ss] read from aa (both alpha), bb (both beta) or ab (alpha-beta; beta-alpha transposed)
+__device__ __forceinline__ double uhf_chem(const double* aa, const double* bb, const double* ab, int64_t np, int sl, int P, int R, int sr,
+                                           int Q, int S)
+{
+    const int64_t pr = tri(P, R), qs = tri(Q, S);
+    if (sl == sr) return (sl ? bb : aa)[tri(pr, qs)];
+    return sl == 0 ? ab[pr * np + qs] : ab[qs * np + pr];
+}
+__global__ void slice_asym_uhf_kernel(double* out, const double* aa, const double* bb, const double* ab, const int* tab, int64_t np, int d0,
+                                      int d1, int d2, int d3, int b0, int b1, int b2, int b3)
+{
+    const int64_t n = (int64_t)d0 * d1 * d2 * d3;
+    SO_STRIDE(x, n)
+    {
+        const int p = tab[(int)(x % d0) + b0];
+        int64_t y = x / d0;
+        const int q = tab[(int)(y % d1) + b1];
+        y /= d1;
+        const int r = tab[(int)(y % d2) + b2], s = tab[(int)(y / d2) + b3];
+        const int sp = p & 1, sq = q & 1, sr = r & 1, ss = s & 1;
+        double val = 0.0;
+        if (sp == sr && sq == ss) val += uhf_chem(aa, bb, ab, np, sp, p >> 1, r >> 1, sq, q >> 1, s >> 1);
+        if (sp == ss && sq == sr) val -= uhf_chem(aa, bb, ab, np, sp, p >> 1, s >> 1, sq, q >> 1, r >> 1);
+        out[x] = val;
+    }
+}
+// D from the level of every spin orbital (lev: occupied first)
+__global__ void so_denominators_lev_kernel(double* D1, double* D2, const double* lev, int o, int v)
+{
+    const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
+    SO_STRIDE(x, n2)
+    {
+        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        D2[x] = lev[i] + lev[j] - lev[o + a] - lev[o + b];
+        if (x < n1) D1[x] = lev[(int)(x % o)] - lev[o + (int)(x / o)];
+    }
+}
+
 // ccsd.f90:437-448
 }  // namespace
 void preload_ccsd_so()
 {
     first_use_touch(reinterpret_cast<const void*>(slice_asym_kernel));
+    first_use_touch(reinterpret_cast<const void*>(slice_asym_uhf_kernel));
+    first_use_touch(reinterpret_cast<const void*>(so_denominators_lev_kernel));
     (void)hipGetLastError();
 }
 namespace {
@@ -235,6 +276,8 @@ typedef std::vector<FusedRange> Ranges;
 
 }  // namespace
 
+static void so_init_tail(Context& cx, SOState& s, int diis_nerr);
+
 void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_dev, const double* e_host, int diis_nerr,
              bool foo_as_published)
 {
@@ -244,7 +287,7 @@ void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_
     const int o = nel, v = 2 * nbasis - nel;
     s.o = o; s.v = v; s.n = nbasis;
     s.foo_as_published = foo_as_published;
-    const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
+    const int64_t O = o, V = v, o2v2 = O * O * V * V;
     s.e = cx.alloc(nbasis);
     AFESP_HIP(hipMemcpyAsync(s.e, e_host, sizeof(double) * nbasis, hipMemcpyHostToDevice, cx.stream));
     cx.sync();
@@ -259,6 +302,14 @@ void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_
     slice(s.vvvv, o, o, o, o);
     s.D1 = cx.tensor({O, V}); s.D2 = cx.tensor({O, O, V, V});
     SO_LAUNCH(so_denominators_kernel, o2v2, s.D1.d, s.D2.d, s.e, o, v);
+    so_init_tail(cx, s, diis_nerr);
+}
+
+// what follows the integrals and the denominators, for either source
+static void so_init_tail(Context& cx, SOState& s, int diis_nerr)
+{
+    const int o = s.o, v = s.v;
+    const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
     s.nvec = ov + o2v2;
     s.amp = cx.alloc(s.nvec);
     s.t1 = view(s.amp, {O, V}); s.t2 = view(s.amp + ov, {O, O, V, V});
@@ -295,10 +346,62 @@ void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_
     cx.sync();
 }
 
+void so_init_uhf(Context& cx, SOState& s, int nbasis, int na, int nb, const double* aa, const double* bb, const double* ab,
+                 const double* ea_host, const double* eb_host, int diis_nerr)
+{
+    if (nbasis <= 0 || na < 0 || nb < 0 || na > nbasis || nb > nbasis || na + nb <= 0 || na + nb >= 2 * nbasis)
+        throw Error(1, "ccsd_uso_init: need 0 <= nalpha, nbeta <= nbasis with at least one occupied and one virtual spin orbital");
+    so_free(cx, s);
+    const int n = nbasis, o = na + nb, v = 2 * nbasis - o;
+    s.o = o; s.v = v; s.n = nbasis;
+    s.foo_as_published = true;
+    const int64_t O = o, V = v, o2v2 = O * O * V * V, np = (int64_t)n * (n + 1) / 2;
+    // spin-orbital table (2 orbital + spin) and levels, in the order of the header
+    std::vector<int> tab((size_t)(o + v));
+    std::vector<double> lev((size_t)(o + v));
+    for (int x = 0; x < o + v; ++x) {
+        int orb, sp;
+        if (x < na) { orb = x; sp = 0; }
+        else if (x < o) { orb = x - na; sp = 1; }
+        else if (x < o + n - na) { orb = na + (x - o); sp = 0; }
+        else { orb = nb + (x - o - (n - na)); sp = 1; }
+        tab[(size_t)x] = 2 * orb + sp;
+        lev[(size_t)x] = sp ? eb_host[orb] : ea_host[orb];
+    }
+    s.lev = cx.alloc(O + V);
+    AFESP_HIP(hipMemcpyAsync(s.lev, lev.data(), sizeof(double) * (O + V), hipMemcpyHostToDevice, cx.stream));
+    int* tab_dev = (int*)cx.scratch("so_uhf_tab", (O + V + 1) / 2 + 1);
+    AFESP_HIP(hipMemcpyAsync(tab_dev, tab.data(), sizeof(int) * (O + V), hipMemcpyHostToDevice, cx.stream));
+    s.oooo = cx.tensor({O, O, O, O}); s.ooov = cx.tensor({O, O, O, V}); s.ovoo = cx.tensor({O, V, O, O});
+    s.oovo = cx.tensor({O, O, V, O}); s.oovv = cx.tensor({O, O, V, V}); s.ovvo = cx.tensor({O, V, V, O});
+    s.ovvv = cx.tensor({O, V, V, V}); s.vovv = cx.tensor({V, O, V, V}); s.vvvv = cx.tensor({V, V, V, V});
+    auto slice = [&](const Tensor& t, int b0, int b1, int b2, int b3) {
+        SO_LAUNCH(slice_asym_uhf_kernel, t.size(), t.d, aa, bb, ab, tab_dev, np, (int)t.dim[0], (int)t.dim[1], (int)t.dim[2], (int)t.dim[3],
+                  b0, b1, b2, b3);
+    };
+    slice(s.oooo, 0, 0, 0, 0); slice(s.ooov, 0, 0, 0, o); slice(s.ovoo, 0, o, 0, 0); slice(s.oovo, 0, 0, o, 0);
+    slice(s.oovv, 0, 0, o, o); slice(s.ovvo, 0, o, o, 0); slice(s.ovvv, 0, o, o, o); slice(s.vovv, o, 0, o, o);
+    slice(s.vvvv, o, o, o, o);
+    s.D1 = cx.tensor({O, V}); s.D2 = cx.tensor({O, O, V, V});
+    SO_LAUNCH(so_denominators_lev_kernel, o2v2, s.D1.d, s.D2.d, s.lev, o, v);
+    cx.sync();   // (the host images of the table and the levels)
+    so_init_tail(cx, s, diis_nerr);
+}
+
+double so_state_bytes(int64_t o, int64_t v, int diis_nerr)
+{
+    const double O = (double)o, V = (double)v, npv = V * (V - 1) / 2;
+    // slices, the W_abef pair operand va, the o^2 v^2 tensors of the state and the iteration's scratch, the DIIS history, and the
+    // (T) operands (vt / tt / vs)
+    const double doubles = V * V * V * V + 2 * O * V * V * V + O * O * O * O + 4 * O * O * O * V + npv * npv + (16.0 + 2.0 * diis_nerr) * O * O * V * V +
+                           (V + O + 16) * (V * V * O + V * O * O) + O * O * O * V;
+    return 8.0 * doubles;
+}
+
 void so_free(Context& cx, SOState& s)
 {
     if (!s.o) return;
-    double* bufs[] = {s.e, s.oooo.d, s.ooov.d, s.ovoo.d, s.oovo.d, s.oovv.d, s.ovvo.d, s.ovvv.d, s.vovv.d, s.vvvv.d, s.D1.d,
+    double* bufs[] = {s.e, s.lev, s.oooo.d, s.ooov.d, s.ovoo.d, s.oovo.d, s.oovv.d, s.ovvo.d, s.ovvv.d, s.vovv.d, s.vvvv.d, s.D1.d,
                       s.D2.d, s.amp, s.r1.d, s.t2_old.d, s.F_vv.d, s.F_oo.d, s.F_ov.d, s.W_oooo.d, s.W_vvvv.d, s.W_ovvo.d,
                       s.tau.d, s.tau_t.d, s.amp_s, s.hist_t, s.hist_e, s.coef, s.bmat, s.va, s.ta, s.pa, (double*)s.lad_tab, s.t1_w.d};
     for (double* b : bufs) cx.release(b);

@@ -387,6 +387,130 @@ __global__ void fock_reduce_kernel(double* fock, const double* hcore, const doub
         fock[xa] = hcore[xa] + 2.0 * j - k;
     }
 }
+// The unrestricted Fock matrices  F_s = H + J[Da + Db] - K[D_s]  (s = a, b) on the same half-unpacked integrals: J is one pass of
+// fock_j_kernel with dv of the total density; the exchange kernel carries both spins' density columns, so every slab is read
+// once for the two of them.  With Da = Db = D every partial sum is twice (J) or exactly (K) the one of k_build_fock, so the
+// result is the RHF Fock matrix bit for bit.
+__global__ void fock_dv_uhf_kernel(double* dv, const double* da, const double* db, int n)
+{
+    const int64_t np = (int64_t)n * (n + 1) / 2;
+    GRID_STRIDE(p, np)
+    {
+        int b, a;
+        unpair(p, b, a);
+        const int64_t ab = a + (int64_t)n * b, ba = b + (int64_t)n * a;
+        dv[p] = a == b ? da[ab] + db[ab] : (da[ab] + db[ab]) + (da[ba] + db[ba]);
+    }
+}
+// kp[s][0]: sum_y u(x,y,P) D_s(y,b), kp[s][1]: sum_y u(x,y,P) D_s(y,a) -- each in fock_k_kernel's order
+__global__ __launch_bounds__(256) void fock_k_uhf_kernel(double* kp1a, double* kp2a, double* kp1b, double* kp2b, const double* u,
+                                                         const double* da, const double* db, int n, int ld)
+{
+    extern __shared__ double dcol[];   // Da(:,b), Da(:,a), Db(:,b), Db(:,a)
+    const int64_t n2 = (int64_t)ld * n, p = blockIdx.x;
+    int b, a;
+    unpair(p, b, a);
+    for (int y = threadIdx.x; y < n; y += 256) {
+        dcol[y] = da[y + (int64_t)n * b];
+        dcol[n + y] = da[y + (int64_t)n * a];
+        dcol[2 * n + y] = db[y + (int64_t)n * b];
+        dcol[3 * n + y] = db[y + (int64_t)n * a];
+    }
+    __syncthreads();
+    const double* m = u + n2 * p;
+    for (int x = threadIdx.x; x < n; x += 256) {
+        double w1 = 0.0, w2 = 0.0, w3 = 0.0, w4 = 0.0;
+#pragma unroll 8
+        for (int y = 0; y < n; ++y) {
+            const double v = m[x + (int64_t)ld * y];
+            w1 += v * dcol[y];
+            w2 += v * dcol[n + y];
+            w3 += v * dcol[2 * n + y];
+            w4 += v * dcol[3 * n + y];
+        }
+        kp1a[p * n + x] = w1;
+        kp2a[p * n + x] = w2;
+        kp1b[p * n + x] = w3;
+        kp2b[p * n + x] = w4;
+    }
+}
+__global__ void fock_reduce_uhf_kernel(double* fa, double* fb, const double* hcore, const double* jpart, const double* kp1a,
+                                       const double* kp2a, const double* kp1b, const double* kp2b, int n)
+{
+    const int64_t n2 = (int64_t)n * n;
+    GRID_STRIDE(xa, n2)
+    {
+        const int x = (int)(xa % n), a = (int)(xa / n);
+        double j = 0.0, ka = 0.0, kb = 0.0;
+        for (int c = 0; c < FOCK_CHUNKS; ++c) j += jpart[(int64_t)c * n2 + xa];
+        for (int b = 0; b <= a; ++b) {
+            const int64_t at = ((int64_t)a * (a + 1) / 2 + b) * n + x;
+            ka += kp1a[at];
+            kb += kp1b[at];
+        }
+        for (int b = a + 1; b < n; ++b) {
+            const int64_t at = ((int64_t)b * (b + 1) / 2 + a) * n + x;
+            ka += kp2a[at];
+            kb += kp2b[at];
+        }
+        fa[xa] = hcore[xa] + j - ka;
+        fb[xa] = hcore[xa] + j - kb;
+    }
+}
+// UMP2 straight from the three resident blocks of afesp_ao2mo_ump2 (the analogue of mp2_packed_kernel, same last-block reduction):
+//   E = 1/4 sum_{ijab in a} [(ia|jb) - (ib|ja)]^2 / D  +  the same in b  +  sum_{ia in a, jb in b} (ia|jb)^2 / D
+// aa / bb: 8-fold packed (spatial MO index: occupied first), ab: ab[tri(p,q) np + tri(r,s)] = (pq|rs), pq alpha, rs beta
+__global__ __launch_bounds__(TB) void ump2_kernel(double* partial, unsigned* counter, double* scal, const double* __restrict__ aa,
+                                                  const double* __restrict__ bb, const double* __restrict__ ab,
+                                                  const double* __restrict__ ea, const double* __restrict__ eb, int n, int na, int nb)
+{
+    __shared__ double sm[4];
+    __shared__ bool last;
+    auto tri2 = [](int64_t p, int64_t q) { return p >= q ? p * (p + 1) / 2 + q : q * (q + 1) / 2 + p; };
+    const int va = n - na, vb = n - nb;
+    const int64_t np = (int64_t)n * (n + 1) / 2;
+    const int64_t naa = (int64_t)na * na * va * va, nbb = (int64_t)nb * nb * vb * vb, nab = (int64_t)na * nb * va * vb;
+    double acc[1] = {0.0};
+    GRID_STRIDE(x, naa + nbb + nab)
+    {
+        if (x < naa + nbb) {
+            const bool beta = x >= naa;
+            const int o = beta ? nb : na, v = beta ? vb : va;
+            const double* P = beta ? bb : aa;
+            const double* e = beta ? eb : ea;
+            int64_t r = beta ? x - naa : x;
+            const int i = (int)(r % o);
+            r /= o;
+            const int j = (int)(r % o);
+            r /= o;
+            const int a = (int)(r % v), b = (int)(r / v);
+            const double d = P[tri2(tri2(o + a, i), tri2(o + b, j))] - P[tri2(tri2(o + b, i), tri2(o + a, j))];
+            acc[0] += 0.25 * d * d / (e[i] + e[j] - e[o + a] - e[o + b]);
+        } else {
+            int64_t r = x - naa - nbb;
+            const int i = (int)(r % na);
+            r /= na;
+            const int a = (int)(r % va);
+            r /= va;
+            const int j = (int)(r % nb), b = (int)(r / nb);
+            const double g = ab[tri2(na + a, i) * np + tri2(nb + b, j)];
+            acc[0] += g * g / (ea[i] + eb[j] - ea[na + a] - eb[nb + b]);
+        }
+    }
+    block_sum<1>(acc, sm);
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = acc[0];
+        __threadfence();
+        last = atomicInc(counter, gridDim.x - 1) == gridDim.x - 1;   // (wraps to zero: ready for the next call)
+    }
+    __syncthreads();
+    if (!last) return;
+    __threadfence();
+    double tot[1] = {0.0};
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += blockDim.x) tot[0] += __builtin_nontemporal_load(&partial[b]);
+    block_sum<1>(tot, sm);
+    if (threadIdx.x == 0) scal[0] = tot[0];
+}
 }  // namespace
 
 #define LAUNCH(kernel, grid, ...)                                               \
@@ -1146,6 +1270,18 @@ __global__ void pack_pairs_kernel(double* packed, const double* full, int n, int
         packed[pq * (pq + 1) / 2 + rs] = full[s_ + L * r_ + L * N * (pq - p_begin)];
     }
 }
+// cols[PQ np + RS] = full(s,r,PQ) for every RS = tri(r,s) (the full column: afesp_ao2mo_ump2's alpha-beta block)
+__global__ void pack_cols_kernel(double* cols, const double* full, int n)
+{
+    const int64_t N = n, np = N * (N + 1) / 2;
+    GRID_STRIDE(x, np * np)
+    {
+        const int64_t rs = x % np, pq = x / np;
+        int s_, r_;
+        unpair(rs, s_, r_);
+        cols[x] = full[s_ + N * r_ + N * N * pq];
+    }
+}
 // g(PQ, K) = half(q, p, K - k_begin), PQ = tri(p,q) over p >= q, K in [k_begin, k_end): the half-transformed integrals of a slab
 // of (kl) pairs, pair-packed in (pq), into the [np x np] array the second pair of transforms gathers from
 __global__ void tri_pack_kernel(double* g, const double* half, int n, int64_t k_begin, int64_t k_end)
@@ -1192,6 +1328,8 @@ constexpr int PX = 64, PXS = 66;   // padded extent, LDS row stride
 // MODE 0: in = u(a, b, S) squares (n x n per pair), out = squares            (the transform between the layout kernels)
 // MODE 1: in = the 8-fold packed AO integrals, block S gathered through the packed index; out = pair columns g(PQ, S), p >= q
 // MODE 2: in = pair columns h(KL, S);  out = the packed MO integrals, run S: packed[S (S + 1) / 2 + RS], RS <= S
+// MODE 3: in as MODE 2;  out = the full column of S: out[np S + RS] for every RS (afesp_ao2mo_ump2: (ab|ab) with C of the other
+//         spin in the second pair, where the 8-fold symmetry is gone)
 // -- with modes 1 and 2 and one transposition of the npair x npair matrix between them the whole AO->MO transform of a small basis
 // is three launches and moves 8 (2 neri + 4 npair^2) bytes: no squared-up copy of the integrals exists at any point.
 template <int MODE>
@@ -1282,7 +1420,7 @@ __global__ __launch_bounds__(256, 2) void pair_xform_kernel(double* __restrict__
                 const int q = 32 * wn + 16 * j + lm;
                 if (MODE == 0) {
                     if (p < n && q < n) out[nn * blk + q + (int64_t)n * p] = acc[i][j][r];
-                } else if (MODE == 1) {
+                } else if (MODE == 1 || MODE == 3) {
                     if (p < n && q <= p) out[np * blk + (int64_t)p * (p + 1) / 2 + q] = acc[i][j][r];
                 } else {
                     const int64_t rs = (int64_t)p * (p + 1) / 2 + q;
@@ -1315,7 +1453,8 @@ void k_pair_xform(Context& cx, double* out, const double* in, const double* C, i
     if (npairs <= 0) return;
     if (mode == 0) AFESP_KLAUNCH(pair_xform_kernel<0>, dim3((unsigned)npairs), dim3(256), 0, cx.stream, out, in, C, n);
     else if (mode == 1) AFESP_KLAUNCH(pair_xform_kernel<1>, dim3((unsigned)npairs), dim3(256), 0, cx.stream, out, in, C, n);
-    else AFESP_KLAUNCH(pair_xform_kernel<2>, dim3((unsigned)npairs), dim3(256), 0, cx.stream, out, in, C, n);
+    else if (mode == 2) AFESP_KLAUNCH(pair_xform_kernel<2>, dim3((unsigned)npairs), dim3(256), 0, cx.stream, out, in, C, n);
+    else AFESP_KLAUNCH(pair_xform_kernel<3>, dim3((unsigned)npairs), dim3(256), 0, cx.stream, out, in, C, n);
     AFESP_HIP(hipGetLastError());
 }
 void k_square_transpose(Context& cx, double* out, const double* in, int64_t n)
@@ -1343,6 +1482,11 @@ void k_pack_pairs(Context& cx, double* packed, const double* full, int n, int64_
     if (p_end < 0) p_end = np;
     if (p_end > p_begin) LAUNCH(pack_pairs_kernel, dim3(grid_for(np * (p_end - p_begin), 65536)), packed, full, n, p_begin, p_end, ld > 0 ? ld : n);
 }
+void k_pack_cols(Context& cx, double* cols, const double* full, int n)
+{
+    const int64_t np = (int64_t)n * (n + 1) / 2;
+    LAUNCH(pack_cols_kernel, dim3(grid_for(np * np, 65536)), cols, full, n);
+}
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {
     int64_t n = (int64_t)d0 * d1 * d2 * d3;
@@ -1360,6 +1504,36 @@ void k_build_fock(Context& cx, double* fock, const double* hcore, const double* 
     AFESP_KLAUNCH(fock_k_kernel, dim3((unsigned)np), dim3(256), 2 * n * sizeof(double), cx.stream, kp1, kp2, u, dens, n, ld);
     AFESP_HIP(hipGetLastError());
     LAUNCH(fock_reduce_kernel, dim3(grid_for(n2)), fock, hcore, jpart, kp1, kp2, n);
+}
+void k_build_fock_uhf(Context& cx, double* fa, double* fb, const double* hcore, const double* da, const double* db, const double* u,
+                      double* work, int n, int ld)
+{
+    if (ld <= 0) ld = n;
+    // work: [ dv (npair) | jpart (FOCK_CHUNKS n^2) | kp1a, kp2a, kp1b, kp2b (npair n each) ]
+    const int64_t n2 = (int64_t)n * n, np = (int64_t)n * (n + 1) / 2;
+    double *dv = work, *jpart = dv + np, *kp = jpart + FOCK_CHUNKS * n2;
+    LAUNCH(fock_dv_uhf_kernel, dim3(grid_for(np)), dv, da, db, n);
+    LAUNCH(fock_j_kernel, dim3((unsigned)((n2 + 255) / 256), FOCK_CHUNKS), jpart, u, dv, n, ld);
+    AFESP_KLAUNCH(fock_k_uhf_kernel, dim3((unsigned)np), dim3(256), 4 * n * sizeof(double), cx.stream, kp, kp + np * n, kp + 2 * np * n,
+                  kp + 3 * np * n, u, da, db, n, ld);
+    AFESP_HIP(hipGetLastError());
+    LAUNCH(fock_reduce_uhf_kernel, dim3(grid_for(n2)), fa, fb, hcore, jpart, kp, kp + np * n, kp + 2 * np * n, kp + 3 * np * n, n);
+}
+int64_t k_build_fock_uhf_work(int n)
+{
+    const int64_t n2 = (int64_t)n * n, np = (int64_t)n * (n + 1) / 2;
+    return np + FOCK_CHUNKS * n2 + 4 * np * n;
+}
+double k_ump2(Context& cx, const double* aa, const double* bb, const double* ab, const double* ea_dev, const double* eb_dev, int n, int na,
+              int nb)
+{
+    unsigned* counter = reinterpret_cast<unsigned*>(cx.scal + 56);   // (shared with mp2_packed_kernel: zero between launches)
+    const int64_t va = n - na, vb = n - nb;
+    const int64_t tot = (int64_t)na * na * va * va + (int64_t)nb * nb * vb * vb + (int64_t)na * nb * va * vb;
+    if (tot == 0) return 0.0;
+    const int nblk = (int)grid_for(tot, RED_BLOCKS);
+    LAUNCH(ump2_kernel, dim3(nblk), partials(cx), counter, cx.scal, aa, bb, ab, ea_dev, eb_dev, n, na, nb);
+    return host_scalars(cx, 1)[0];
 }
 int64_t k_build_fock_work(int n)
 {
@@ -1385,5 +1559,13 @@ void preload_small_path_kernels()
                          reinterpret_cast<const void*>(pair_expand_add_kernel), reinterpret_cast<const void*>(pair_xform_kernel<1>),
                          reinterpret_cast<const void*>(pair_xform_kernel<2>), reinterpret_cast<const void*>(square_transpose_kernel)};
     for (const void* f : fns) first_use_touch(f);   // (each under the process-wide first-use lock, first_use.h)
+}
+// ... and of the open-shell set-up (afesp_build_fock_uhf, afesp_ao2mo_ump2)
+void preload_uhf_kernels()
+{
+    const void* fns[] = {reinterpret_cast<const void*>(fock_dv_uhf_kernel), reinterpret_cast<const void*>(fock_k_uhf_kernel),
+                         reinterpret_cast<const void*>(fock_reduce_uhf_kernel), reinterpret_cast<const void*>(ump2_kernel),
+                         reinterpret_cast<const void*>(pair_xform_kernel<3>), reinterpret_cast<const void*>(pack_cols_kernel)};
+    for (const void* f : fns) first_use_touch(f);
 }
 }  // namespace afesp

@@ -1135,15 +1135,17 @@ double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
     permute_add(cx, 1.0, s.t2, "qraf", 0.0, sub(tt, 0, V), "farq");
     permute_add(cx, -1.0, s.ovoo, "maqr", 0.0, sub(tt, V, O), "marq");
     permute_add(cx, 1.0, s.oovv, "pqxy", 0.0, vs, "xypq");
-    AFESP_KLAUNCH(so_levels_kernel, dim3((unsigned)((O + V + 255) / 256)), dim3(256), 0, cx.stream, e_so, s.e, (int)(O + V));
-    AFESP_HIP(hipGetLastError());
+    if (!s.lev) {   // (a UHF-fed state carries its spin-orbital levels itself)
+        AFESP_KLAUNCH(so_levels_kernel, dim3((unsigned)((O + V + 255) / 256)), dim3(256), 0, cx.stream, e_so, s.e, (int)(O + V));
+        AFESP_HIP(hipGetLastError());
+    }
     }
     cx.t_ops_owner = (const void*)&s;
     cx.t_ops_amp = s.amp_epoch;
     cx.t_ops_scratch = cx.scratch_epoch;
     cx.t_ops_ts = false;
     cx.t_ops_cr = -1;
-    TriplesIn in{e_so, s.t1.d, vs.d, nullptr, s.t2.d, o, v};
+    TriplesIn in{s.lev ? s.lev : e_so, s.t1.d, vs.d, nullptr, s.t2.d, o, v};
     double* Xpool = cx.scratch("t_xpool", 3 * p->nb * vp3);
     double* partial = cx.scratch("t_partial", std::max<int64_t>((int64_t)p->norb * p->nb, 512));
     for (const TriplesPlan::Chunk& ch : p->chunks) {

@@ -10,6 +10,7 @@ module afesp_capi
              afesp_ccsd_so_energy, afesp_ccsd_so_iterate, afesp_ccsd_so_diis, afesp_ccsd_so_t, afesp_ccsd_so_t_ntriples, &
              afesp_read_eri_text, afesp_write_fcidump, afesp_build_fock, afesp_ccsd_t_plain, afesp_device_count, &
              afesp_comm_init, afesp_comm_destroy, afesp_allreduce_sum, afesp_ccsd_t_shard_bounds, afesp_ccsd_t_block_size, &
+             afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -141,6 +142,37 @@ module afesp_capi
          integer(c_int64_t), value :: nbasis
          real(c_double), intent(in) :: density(*), core_hamil(*)
          real(c_double), intent(out) :: fock(*)
+         integer(c_int) :: rc
+      end function
+      !> open-shell path (include/afesp.h): F_s = H + J[Da + Db] - K[D_s] for both spins
+      function afesp_build_fock_uhf(ctx, nbasis, dens_a, dens_b, core_hamil, fock_a, fock_b) &
+         bind(C, name='afesp_build_fock_uhf') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis
+         real(c_double), intent(in) :: dens_a(*), dens_b(*), core_hamil(*)
+         real(c_double), intent(out) :: fock_a(*), fock_b(*)
+         integer(c_int) :: rc
+      end function
+      !> the alpha-alpha, alpha-beta and beta-beta MO integrals (left on the device) and E(UMP2)
+      function afesp_ao2mo_ump2(ctx, nbasis, nalpha, nbeta, coeff_a, coeff_b, levels_a, levels_b, eri_packed, eri_aa, eri_ab, &
+                                eri_bb, e_ump2) bind(C, name='afesp_ao2mo_ump2') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         real(c_double), intent(in) :: coeff_a(*), coeff_b(*), levels_a(*), levels_b(*)
+         type(c_ptr), value :: eri_packed, eri_aa, eri_ab, eri_bb
+         real(c_double), intent(out) :: e_ump2
+         integer(c_int) :: rc
+      end function
+      !> the spin-orbital CCSD state from those blocks; afesp_ccsd_so_* drive it afterwards
+      function afesp_ccsd_uso_init(ctx, nbasis, nalpha, nbeta, levels_a, levels_b, diis_n_errmat) &
+         bind(C, name='afesp_ccsd_uso_init') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         real(c_double), intent(in) :: levels_a(*), levels_b(*)
+         integer(c_int), value :: diis_n_errmat
          integer(c_int) :: rc
       end function
       !> replaces write_fcidump (reference src/mp2.f90:451-487)

@@ -38,6 +38,8 @@ module host_config
       integer :: level = LEVEL_CCSD_T
       logical :: paren = .false., renorm = .false., comp_renorm = .false.
       logical :: spinorb = .false.   ! the _spinorb calculation types (reference src/system.f90:117-137)
+      logical :: uhf = .false.       ! the open-shell types UHF_scf, UMP2, UCCSD, UCCSD(T) (canonical UHF orbitals)
+      integer :: charge = 0, multiplicity = 1
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -45,15 +47,16 @@ contains
       type(run_config), intent(out) :: cfg
       character(40) :: calc_type
       real(dp) :: scf_e_tol, scf_d_tol, ccsd_e_tol, ccsd_t_tol
-      integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios
+      integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
-         ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess
+         ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
       scf_maxiter = d%scf_maxiter; ccsd_maxiter = d%ccsd_maxiter; write_fcidump = d%write_fcidump
       scf_read_guess = d%scf_read_guess; scf_write_guess = d%scf_write_guess
+      charge = d%charge; multiplicity = d%multiplicity
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -64,6 +67,7 @@ contains
       cfg%ccsd_t_tol = ccsd_t_tol; cfg%scf_diis_n_errmat = scf_diis_n_errmat; cfg%ccsd_diis_n_errmat = ccsd_diis_n_errmat
       cfg%scf_maxiter = scf_maxiter; cfg%ccsd_maxiter = ccsd_maxiter; cfg%write_fcidump = write_fcidump
       cfg%scf_read_guess = scf_read_guess; cfg%scf_write_guess = scf_write_guess
+      cfg%charge = charge; cfg%multiplicity = multiplicity
       select case (trim(calc_type))
       case ('RHF');              cfg%level = LEVEL_RHF
       case ('MP2_spatial');      cfg%level = LEVEL_MP2
@@ -79,9 +83,17 @@ contains
       case ('MP2_spinorb');      cfg%level = LEVEL_MP2; cfg%spinorb = .true.
       case ('CCSD_spinorb');     cfg%level = LEVEL_CCSD; cfg%spinorb = .true.
       case ('CCSD(T)_spinorb');  cfg%level = LEVEL_CCSD_T; cfg%spinorb = .true.
+      ! open-shell types: unrestricted SCF, then the spin-orbital path on its orbitals
+      case ('UHF_scf');          cfg%level = LEVEL_RHF; cfg%uhf = .true.
+      case ('UMP2');             cfg%level = LEVEL_MP2; cfg%uhf = .true.
+      case ('UCCSD');            cfg%level = LEVEL_CCSD; cfg%uhf = .true.
+      case ('UCCSD(T)');         cfg%level = LEVEL_CCSD_T; cfg%uhf = .true.
       case default
          call fail('system::read_system_in', 'Unrecognised calculation type!')
       end select
+      if (multiplicity < 1) call fail('system::read_system_in', 'invalid input file format!')
+      if (.not. cfg%uhf .and. (charge /= 0 .or. multiplicity /= 1)) &
+         call fail('system::read_system_in', 'charge and multiplicity need an open-shell calculation type!')
    end subroutine
 end module host_config
 
@@ -379,6 +391,136 @@ contains
          write (out, '(1X, A)') 'Convergence not reached, please increase maxiter.'
       end if
    end subroutine
+
+   !> Unrestricted Hartree-Fock, the rhf iteration above for two spins (afesp_amd/uhf.py is the same algorithm): both Fock
+   !> matrices start from H_core or guess_in.dat, D_s = C_s,occ^T C_s,occ, E = 1/2 sum [(Da + Db) H + Da Fa + Db Fb], the rms change
+   !> is the mean of the two spins' squared changes, and DIIS takes one set of coefficients for the concatenated error vectors.
+   !> on_device: F_s = H + J[Da + Db] - K[D_s] by afesp_build_fock_uhf.  Returns <S^2> with the orbitals.
+   subroutine uhf(cfg, mol, na, nb, e_hf, ca, cb, la, lb, s2, converged, ctx, on_device)
+      type(run_config), intent(in) :: cfg
+      type(molecule), intent(in) :: mol
+      integer, intent(in) :: na, nb
+      type(c_ptr), intent(in) :: ctx
+      logical, intent(in) :: on_device
+      real(dp), intent(out) :: e_hf, s2
+      real(dp), allocatable, intent(out) :: ca(:, :), cb(:, :), la(:), lb(:)
+      logical, intent(out) :: converged
+      integer :: n, iter, i, j, k, l, slot, nact, m, unit, ios, info
+      real(dp), allocatable :: x(:, :), fa(:, :), fb(:, :), vec(:, :), da(:, :), db(:, :), daold(:, :), dbold(:, :), sv(:), u(:, :)
+      real(dp), allocatable :: fhist(:, :, :, :), ehist(:, :, :, :), bmat(:, :), rhs(:), ov(:, :)
+      real(dp) :: energy, eold, rms, val, jv, t0, t1, sz
+      n = mol%nbasis
+      write (out, '(1X, 25("-"))'); write (out, '(1X, A)') 'Unrestricted Hartree-Fock'; write (out, '(1X, 25("-"))')
+      write (out, '(1X, A, 1X, I0, 1X, I0)') 'Alpha and beta electrons:', na, nb
+      allocate (x(n, n), fa(n, n), fb(n, n), vec(n, n), da(n, n), db(n, n), daold(n, n), dbold(n, n), sv(n), u(n, n))
+      allocate (ca(n, n), cb(n, n), la(n), lb(n))
+      call sym_eig(mol%ovlp, sv, u)
+      do j = 1, n; vec(:, j) = u(:, j)/sqrt(sv(j)); end do
+      x = matmul(vec, transpose(u))                       ! S^-1/2
+      fa = mol%hcore
+      if (cfg%scf_read_guess) then
+         write (out, *) 'Reading previous AO Fock matrix as guess...'
+         open (newunit=unit, file='guess_in.dat', status='old', action='read')
+         do
+            read (unit, *, iostat=ios) i, j, val
+            if (ios /= 0) exit
+            fa(i, j) = val
+         end do
+         close (unit)
+      end if
+      fb = fa
+      m = cfg%scf_diis_n_errmat
+      if (m >= 2) then
+         allocate (fhist(n, n, 2, m), ehist(n, n, 2, m)); fhist = 0.0_dp; ehist = 0.0_dp
+      end if
+      slot = 0; nact = 0; energy = 0.0_dp; daold = 0.0_dp; dbold = 0.0_dp; converged = .false.
+      write (out, '(75("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Iteration', '     Energy    ', '    deltaE     ', '   delta RMS D ', '  Time  '
+      write (out, '(75("-"))')
+      t0 = seconds()
+      do iter = 1, cfg%scf_maxiter
+         call sym_eig(matmul(transpose(x), matmul(fa, x)), la, vec)
+         ca = transpose(matmul(x, vec))
+         call sym_eig(matmul(transpose(x), matmul(fb, x)), lb, vec)
+         cb = transpose(matmul(x, vec))
+         da = matmul(transpose(ca(1:na, :)), ca(1:na, :))
+         db = matmul(transpose(cb(1:nb, :)), cb(1:nb, :))
+         eold = energy
+         energy = 0.5_dp*(sum(da*(mol%hcore + fa)) + sum(db*(mol%hcore + fb)))
+         rms = sqrt(0.5_dp*(sum((da - daold)**2) + sum((db - dbold)**2)))
+         daold = da; dbold = db
+         t1 = seconds()
+         write (out, '(1X, I9, 3X, F15.10, 3X, F15.10, 3X, F15.10, 3X, F8.6)') iter, energy, energy - eold, rms, t1 - t0
+         t0 = t1
+         if (rms < cfg%scf_d_tol .and. abs(energy - eold) < cfg%scf_e_tol) then
+            converged = .true.
+            exit
+         end if
+         if (on_device) then
+            if (afesp_build_fock_uhf(ctx, int(n, c_int64_t), da, db, mol%hcore, fa, fb) /= 0) &
+               call fail('hf::build_fock_uhf', afesp_error_text(ctx))
+         else
+         do j = 1, n
+            do i = 1, n
+               jv = mol%hcore(i, j)
+               do l = 1, n
+                  do k = 1, n
+                     jv = jv + (da(k, l) + db(k, l))*mol%eri(eri_slot(i, j, k, l))
+                  end do
+               end do
+               fa(i, j) = jv; fb(i, j) = jv
+               do l = 1, n
+                  do k = 1, n
+                     val = mol%eri(eri_slot(i, k, j, l))
+                     fa(i, j) = fa(i, j) - da(k, l)*val
+                     fb(i, j) = fb(i, j) - db(k, l)*val
+                  end do
+               end do
+            end do
+         end do
+         end if
+         if (m >= 2) then
+            slot = slot + 1; if (slot > m) slot = slot - m
+            if (nact < m) nact = nact + 1
+            fhist(:, :, 1, slot) = fa; fhist(:, :, 2, slot) = fb
+            ehist(:, :, 1, slot) = matmul(fa, matmul(da, mol%ovlp)) - matmul(mol%ovlp, matmul(da, fa))
+            ehist(:, :, 2, slot) = matmul(fb, matmul(db, mol%ovlp)) - matmul(mol%ovlp, matmul(db, fb))
+            if (nact > 1) then
+               allocate (bmat(nact + 1, nact + 1), rhs(nact + 1))
+               bmat = -1.0_dp; bmat(nact + 1, nact + 1) = 0.0_dp; rhs = 0.0_dp; rhs(nact + 1) = -1.0_dp
+               do i = 1, nact
+                  do j = 1, nact
+                     bmat(i, j) = sum(ehist(:, :, :, i)*ehist(:, :, :, j))
+                  end do
+               end do
+               call solve(bmat, rhs, info)
+               if (info /= 0) call fail('hf::update_diis', 'Linear solve failed!')
+               fa = 0.0_dp; fb = 0.0_dp
+               do i = 1, nact
+                  fa = fa + rhs(i)*fhist(:, :, 1, i); fb = fb + rhs(i)*fhist(:, :, 2, i)
+               end do
+               deallocate (bmat, rhs)
+            end if
+         end if
+      end do
+      e_hf = energy
+      ! <S^2> = Sz (Sz + 1) + n_beta - sum_ij |<i_alpha|j_beta>|^2 over the occupied orbitals
+      sz = 0.5_dp*(na - nb)
+      ov = matmul(ca(1:na, :), matmul(mol%ovlp, transpose(cb(1:nb, :))))
+      s2 = sz*(sz + 1.0_dp) + nb - sum(ov*ov)
+      if (converged) then
+         write (out, '(75("-"))')
+         write (out, '(1X, A)') 'Convergence reached within tolerance.'
+         write (out, '(1X, A, 1X, F15.8)') 'Final SCF Energy (Hartree):', energy
+         write (out, '(1X, A, 1X, F10.6)') '<S^2>:', s2
+         write (out, '(1X, A)') 'Alpha orbital energies (Hartree):'
+         do i = n, 1, -1; write (out, '(1X, I3, 1X, F15.8)') i, la(i); end do
+         write (out, '(1X, A)') 'Beta orbital energies (Hartree):'
+         do i = n, 1, -1; write (out, '(1X, I3, 1X, F15.8)') i, lb(i); end do
+      else
+         write (out, '(1X, A)') 'Convergence not reached, please increase maxiter.'
+      end if
+   end subroutine
 end module host_scf
 
 program els_amd
@@ -393,6 +535,9 @@ program els_amd
    type(molecule) :: mol
    type(c_ptr) :: ctx
    real(dp), allocatable :: coeff(:, :), levels(:), t1(:, :)
+   real(dp), allocatable :: cb(:, :), lb(:)     ! beta orbitals of the open-shell types (alpha: coeff / levels)
+   real(dp) :: s2
+   integer :: na, nb
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
    integer(c_int) :: rc, conv
@@ -454,9 +599,22 @@ program els_amd
       write (out, *) 'Done reading integrals!'
    end if
    write (out, '(1X, 20("-"))'); write (out, '(1X, A)') 'System information'; write (out, '(1X, 20("-"))')
+   if (cfg%uhf) then   ! nel = sum Z - charge, n_alpha - n_beta = multiplicity - 1
+      mol%nel = mol%nel - cfg%charge
+      if (mol%nel < 0 .or. mod(mol%nel + cfg%multiplicity - 1, 2) /= 0) &
+         call fail('system::read_system_in', 'charge and multiplicity do not fit the electron count!')
+      na = (mol%nel + cfg%multiplicity - 1)/2; nb = (mol%nel - cfg%multiplicity + 1)/2
+      if (nb < 0 .or. na > mol%nbasis) call fail('system::read_system_in', 'charge and multiplicity do not fit the electron count!')
+      if (cfg%level >= LEVEL_MP2 .and. na + nb >= 2*mol%nbasis) &
+         call fail('system::read_system_in', 'no virtual spin orbital for a correlated calculation!')
+   end if
    write (out, '(1X, A, 1X, I0)') 'Number of electrons:', mol%nel
    write (out, '(1X, A, 1X, I0)') 'Number of basis functions:', mol%nbasis
-   if (cfg%spinorb) then   ! spin-orbital counts, reference src/geometry.f90:44-45
+   if (cfg%uhf) then
+      write (out, '(1X, A, 1X, I0, 1X, I0)') 'Charge and multiplicity:', cfg%charge, cfg%multiplicity
+      write (out, '(1X, A, 1X, I0)') 'Number of occupied orbitals:', na + nb
+      write (out, '(1X, A, 1X, I0)') 'Number of virtual orbitals:', 2*mol%nbasis - na - nb
+   else if (cfg%spinorb) then   ! spin-orbital counts, reference src/geometry.f90:44-45
       write (out, '(1X, A, 1X, I0)') 'Number of occupied orbitals:', mol%nel
       write (out, '(1X, A, 1X, I0)') 'Number of virtual orbitals:', 2*mol%nbasis - mol%nel
    else
@@ -467,13 +625,83 @@ program els_amd
    write (out, '(1X, A, 1X, A)') 'calc_type:', trim(cfg%calc_type)
 
    t0 = seconds()
-   call rhf(cfg, mol, e_hf, coeff, levels, scf_ok, ctx, have_ctx)
-   t1s = seconds()
-   write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for restricted Hartree-Fock:', t1s - t0, 's'
+   if (cfg%uhf) then
+      call uhf(cfg, mol, na, nb, e_hf, coeff, cb, levels, lb, s2, scf_ok, ctx, have_ctx)
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted Hartree-Fock:', seconds() - t0, 's'
+   else
+      call rhf(cfg, mol, e_hf, coeff, levels, scf_ok, ctx, have_ctx)
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for restricted Hartree-Fock:', seconds() - t0, 's'
+   end if
    e_highest = 0.0_dp; e_mp2 = 0.0_dp; e_ccsd = 0.0_dp; t1diag = 0.0_dp; tq = 0.0_dp; cc_ok = .false.
    e_bt = 0.0_dp; e_pt = 0.0_dp; e_rbt = 0.0_dp; e_rpt = 0.0_dp; e_crbt = 0.0_dp; e_crpt = 0.0_dp
 
-   if (cfg%level >= LEVEL_MP2 .and. scf_ok) then
+   if (cfg%uhf .and. cfg%level >= LEVEL_MP2 .and. scf_ok) then
+      ! ---------------- open shells: UMP2 from the three spin blocks, then the spin-orbital CCSD / (T) on them
+      t0 = seconds()
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'UMP2'; write (out, '(1X, 10("-"))')
+      write (out, '(1X, A)') 'Performing AO to MO ERI transformation (alpha-alpha, alpha-beta, beta-beta)...'
+      rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
+                            c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
+      if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
+      write (out, '(1X, A, 1X, F15.8)') 'UMP2 correlation energy (Hartree):', e_mp2
+      e_highest = e_mp2
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UMP2:', seconds() - t0, 's'
+      if (cfg%level >= LEVEL_CCSD) then
+         t0 = seconds()
+         write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD'; write (out, '(1X, 10("-"))')
+         write (out, '(1X, A)') 'Forming slices of antisymmetrised spinorbital ERIs from the UHF blocks...'
+         rc = afesp_ccsd_uso_init(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), levels, lb, &
+                                  int(cfg%ccsd_diis_n_errmat, c_int))
+         if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
+         rc = afesp_ccsd_so_energy(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, energy, rms, conv)
+         if (rc /= 0) call fail('ccsd::update_cc_energy', afesp_error_text(ctx))
+         write (out, '(75("-"))')
+         write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Iteration', '     Energy    ', '    deltaE     ', '  delta RMS T2 ', '  Time  '
+         write (out, '(75("-"))')
+         write (out, '(1X, A9, 3X, F15.12, 3X, F15.12, 3X, F15.12)') 'MP1', energy, energy, rms
+         t1s = seconds()
+         do iter = 1, cfg%ccsd_maxiter
+            eold = energy
+            rc = afesp_ccsd_so_iterate(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, energy, rms, conv)
+            if (rc /= 0) call fail('ccsd::update_amplitudes', afesp_error_text(ctx))
+            write (out, '(1X, I9, 3X, F15.12, 3X, F15.12, 3X, F15.12, 3X, F8.6)') iter, energy, energy - eold, rms, seconds() - t1s
+            t1s = seconds()
+            if (conv /= 0) then
+               cc_ok = .true.
+               exit
+            end if
+            rc = afesp_ccsd_so_diis(ctx)
+            if (rc /= 0) call fail('ccsd::update_diis_cc', 'Linear solve failed!')
+         end do
+         if (cc_ok) then
+            write (out, '(75("-"))')
+            write (out, '(1X, A)') 'Convergence reached within tolerance.'
+            write (out, '(1X, A, 1X, F15.12)') 'Final UCCSD Energy (Hartree):', energy
+            e_ccsd = energy; e_highest = e_ccsd
+         end if
+         write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UCCSD:', seconds() - t0, 's'
+         if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
+            t0 = seconds()
+            write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
+            t_hi = afesp_ccsd_so_t_ntriples(int(na + nb, c_int64_t))     ! i<j<k triples, an even split over the ranks
+            t_lo = (int(rank, c_int64_t)*t_hi)/world; t_hi = (int(rank + 1, c_int64_t)*t_hi)/world
+            rc = afesp_ccsd_so_t(ctx, t_lo, t_hi, tq(1))
+            if (world > 1) then   ! (every rank enters the sum, a failed shard as a flag: as in the spin-orbital branch below)
+               rc_mine = rc; my_error = ''
+               if (rc_mine /= 0) then; my_error = afesp_error_text(ctx); tq(1) = 0.0_dp; end if
+               tq(2) = merge(1.0_dp, 0.0_dp, rc_mine /= 0)
+               rc = afesp_allreduce_sum(ctx, tq, 2_c_int64_t)
+               if (rc_mine /= 0) call fail('ccsd::do_ccsd_t_spinorb', trim(my_error))
+               if (rc == 0 .and. tq(2) > 0.5_dp) call fail('ccsd::do_ccsd_t_spinorb', 'the (T) shard of another rank failed')
+            end if
+            if (rc /= 0) call fail('ccsd::do_ccsd_t_spinorb', afesp_error_text(ctx))
+            e_pt = e_ccsd + tq(1)
+            e_highest = e_pt
+            write (out, '(1X, A, 1X, F15.9)') 'UCCSD(T) correlation energy (Hartree):', e_pt
+            write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UCCSD(T):', seconds() - t0, 's'
+         end if
+      end if
+   else if (cfg%level >= LEVEL_MP2 .and. scf_ok) then
       ! ---------------- MP2: AO->MO transform + energy on the device (reference do_mp2_spatial)
       t0 = seconds()
       write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'MP2'; write (out, '(1X, 10("-"))')
@@ -683,6 +911,22 @@ program els_amd
    ! ---------------- final table: same labels and formats as the reference (src/main.F90:123-175)
    write (out, '(1X, 64("="))')
    write (out, '(1X, A)') 'Final energy breakdown'
+   if (cfg%uhf) then
+   write (out, '(1X, A, 1X, F15.10)') 'UHF energy:                    ', e_hf + mol%e_nuc
+   write (out, '(1X, A, 1X, F15.10)') '<S^2>:                         ', s2
+   if (cfg%level >= LEVEL_MP2) then
+      write (out, '(1X, A, 1X, F15.10)') 'UMP2 correlation energy:       ', e_mp2
+      write (out, '(1X, A, 1X, F15.10)') 'UMP2 energy:                   ', e_mp2 + e_hf + mol%e_nuc
+   end if
+   if (cfg%level >= LEVEL_CCSD) then
+      write (out, '(1X, A, 1X, F15.10)') 'UCCSD correlation energy:      ', e_ccsd
+      write (out, '(1X, A, 1X, F15.10)') 'UCCSD energy:                  ', e_ccsd + e_hf + mol%e_nuc
+   end if
+   if (cfg%level == LEVEL_CCSD_T) then
+      write (out, '(1X, A, 1X, F15.10)') 'UCCSD(T) correlation energy:   ', e_pt
+      write (out, '(1X, A, 1X, F15.10)') 'UCCSD(T) energy:               ', e_pt + e_hf + mol%e_nuc
+   end if
+   else
    write (out, '(1X, A, 1X, F15.10)') 'RHF energy:                    ', e_hf + mol%e_nuc
    if (cfg%level >= LEVEL_MP2) then
       write (out, '(1X, A, 1X, F15.10)') 'MP2 correlation energy:        ', e_mp2
@@ -726,6 +970,7 @@ program els_amd
    if (cfg%renorm .or. cfg%comp_renorm) then
       write (out, '(1X, A, 1X, F15.10)') 'D[T]:                          ', tq(3)
       if (cfg%paren) write (out, '(1X, A, 1X, F15.10)') 'D(T):                          ', tq(4)
+   end if
    end if
    write (out, '(1X, 47("-"))')
    write (out, '(1X, A, 1X, F15.10)') 'Total electronic energy:       ', e_hf + e_highest

@@ -167,6 +167,31 @@ int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int6
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc);
 int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t);
 
+/* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
+ * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
+ *   afesp_build_fock_uhf = fock_s = core_hamil + J[dens_a + dens_b] - K[dens_s] for s = a, b on the resident packed AO integrals
+ *                          (afesp_set_eri / afesp_read_eri_text), dens_s = C_s,occ^T C_s,occ; n x n column-major host arrays.
+ *                          With dens_a = dens_b it returns afesp_build_fock's matrix bit for bit.
+ *   afesp_ao2mo_ump2     = the alpha-alpha and beta-beta MO integrals (8-fold packed, as afesp_ao2mo_mp2 writes them), the
+ *                          alpha-beta block as a full npair x npair matrix eri_ab[tri(p,q) npair + tri(r,s)] = (pq|rs), pq alpha,
+ *                          rs beta (npair = n(n+1)/2), and E(UMP2).  coeff_s: MO x AO column-major, as canon_coeff; levels_s: n
+ *                          entries.  eri_packed NULL: the resident AO integrals.  Each output array may be NULL; the three blocks
+ *                          stay on the device (apart from the RHF path's MO integrals) for afesp_ccsd_uso_init.  Bases of up to
+ *                          64 functions take the LDS-resident pair transform, larger ones the gather-GEMM form; a basis whose
+ *                          temporaries need the slab-blocked form is refused (status 1).
+ *   afesp_ccsd_uso_init  = the spin-orbital state from those blocks.  Spin-orbital order: occupied = alpha occupied (nalpha),
+ *                          then beta occupied (nbeta); virtual = alpha virtual (n - nalpha), then beta virtual (n - nbeta):
+ *                          nocc = nalpha + nbeta, nvirt = 2n - nocc.  F_mi takes Stanton's published order.  A state that would
+ *                          not fit the device is refused (status 1).  Afterwards afesp_ccsd_so_energy / _iterate / _diis /
+ *                          _get_amplitudes / _set_amplitudes / _get_tensor / _t (with afesp_ccsd_so_t_ntriples(nocc)) drive it. */
+int afesp_build_fock_uhf(afesp_ctx* ctx, int64_t nbasis, const double* dens_a, const double* dens_b, const double* core_hamil,
+                         double* fock_a, double* fock_b);
+int afesp_ao2mo_ump2(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* coeff_a, const double* coeff_b,
+                     const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab,
+                     double* eri_bb, double* e_ump2);
+int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* levels_a, const double* levels_b,
+                        int diis_n_errmat);
+
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
  * every rank evaluates its shard [bounds[r], bounds[r+1]) of the triple list (afesp_ccsd_t_shard_bounds) and that
