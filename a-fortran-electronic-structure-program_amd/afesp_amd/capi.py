@@ -30,7 +30,7 @@ EXPORTS = [
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
-    "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init",
+    "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init", "afesp_mo_window", "afesp_umo_window",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -108,6 +108,8 @@ def load_library():
     L.afesp_build_fock_uhf.argtypes = [C.c_void_p, i64, _dp, _dp, _dp, _dp, _dp]
     L.afesp_ao2mo_ump2.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, _dp, _opt, _opt, _opt, _opt, C.POINTER(dbl)]
     L.afesp_ccsd_uso_init.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.c_int]
+    L.afesp_mo_window.argtypes = [C.c_void_p, i64, i64, i64, i64, _dp, _opt, _opt, C.POINTER(dbl)]
+    L.afesp_umo_window.argtypes = [C.c_void_p, i64, i64, i64, i64, i64, _dp, _dp, _opt, _opt, _opt, C.POINTER(dbl)]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -375,6 +377,37 @@ class Engine:
         self.so_v = int(2 * nbasis - self.so_o)
         self._chk(self.L.afesp_ccsd_uso_init(self.h, nbasis, nalpha, nbeta, np.ascontiguousarray(levels_a, dtype=np.float64),
                                              np.ascontiguousarray(levels_b, dtype=np.float64), diis_nerr))
+
+    # ---- frozen core / frozen virtuals: the active orbital window [nfc, nbasis - nfv)
+    def mo_window(self, nbasis, nocc, nfc, nfv, canon_levels, eri_mo=None, want_eri=True):
+        """-> (packed MO integrals over the n_act = nbasis - nfc - nfv active orbitals or None, frozen-core E(MP2)).  eri_mo None: the
+        integrals do_mp2_spatial left on the device.  The window stays resident as do_mp2_spatial leaves a basis of n_act functions:
+        ccsd_init(nocc - nfc, nvirt - nfv, canon_levels[nfc:nbasis - nfv]) / init_cc_spinorb(n_act, nel - 2 nfc, ...) follow."""
+        e2 = dbl(0.0)
+        n_act = int(nbasis) - int(nfc) - int(nfv)
+        out = np.zeros(self.L.afesp_neri(n_act)) if want_eri and 0 < n_act <= nbasis else None
+        src = None
+        if eri_mo is not None:
+            eri_mo = np.ascontiguousarray(eri_mo, dtype=np.float64)
+            src = eri_mo.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.afesp_mo_window(self.h, nbasis, nocc, nfc, nfv, np.ascontiguousarray(canon_levels, dtype=np.float64), src,
+                                         out.ctypes.data_as(C.c_void_p) if out is not None else None, C.byref(e2)))
+        return out, e2.value
+
+    def umo_window(self, nbasis, nalpha, nbeta, nfc, nfv, levels_a, levels_b, want_eri=True):
+        """The same for the three blocks do_ump2 left -> ((aa|aa) packed, (aa|bb) as [npair_act, npair_act], (bb|bb) packed -- or
+        Nones --, frozen-core E(UMP2)); init_cc_uspinorb(n_act, nalpha - nfc, nbeta - nfc, levels_a[nfc:], levels_b[nfc:]) follows."""
+        e2 = dbl(0.0)
+        n_act = int(nbasis) - int(nfc) - int(nfv)
+        ok = want_eri and 0 < n_act <= nbasis
+        npr = n_act * (n_act + 1) // 2
+        aa = np.zeros(self.L.afesp_neri(n_act)) if ok else None
+        bb = np.zeros(self.L.afesp_neri(n_act)) if ok else None
+        ab = np.zeros(npr * npr) if ok else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.L.afesp_umo_window(self.h, nbasis, nalpha, nbeta, nfc, nfv, np.ascontiguousarray(levels_a, dtype=np.float64),
+                                          np.ascontiguousarray(levels_b, dtype=np.float64), ptr(aa), ptr(ab), ptr(bb), C.byref(e2)))
+        return aa, (ab.reshape((npr, npr)) if ab is not None else None), bb, e2.value
 
     def write_fcidump(self, path, nbasis):
         n = i64()

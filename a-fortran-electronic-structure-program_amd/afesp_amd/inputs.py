@@ -34,6 +34,10 @@ class SystemIn:
     scf_write_guess: bool = False
     charge: int = 0                 # open-shell types only (UHF_scf, UMP2, UCCSD, UCCSD(T))
     multiplicity: int = 1           # 2S + 1
+    # active orbital window of the correlated steps (no counterpart in the reference): all three absent = every orbital correlated
+    frozen_core: bool = False       # freeze the noble-gas cores counted from geom.dat (frozen_core_count)
+    n_frozen_core: int = -1         # explicit number of lowest MOs to freeze; -1 = not given; wins over frozen_core
+    n_frozen_virt: int = 0          # highest MOs dropped
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -102,7 +106,39 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("invalid input file format!")
     if (sysin.charge, sysin.multiplicity) != (0, 1) and sysin.calc_type not in OPEN_SHELL_TYPES:
         raise ValueError("charge and multiplicity need an open-shell calculation type!")
+    if not isinstance(sysin.frozen_core, bool):
+        raise ValueError("invalid input file format!")
+    for key in ("n_frozen_core", "n_frozen_virt"):
+        val = getattr(sysin, key)
+        if not isinstance(val, int) or isinstance(val, bool) or val < -1:
+            raise ValueError(f"{key} must be a non-negative integer!")
     return sysin
+
+
+def frozen_core_count(z_list) -> int:
+    """Number of doubly occupied core orbitals of the atoms with these nuclear charges: the noble-gas core below each atom's valence
+    shell (Z <= 2: 0, <= 10: 1 (He), <= 18: 5 (Ne), <= 36: 9 (Ar)); heavier atoms are refused."""
+    total = 0
+    for z in z_list:
+        z = int(z)
+        if z < 1 or z > 36:
+            raise ValueError("frozen_core: no core count for atoms beyond Kr!")
+        total += 0 if z <= 2 else 1 if z <= 10 else 5 if z <= 18 else 9
+    return total
+
+
+def frozen_window(sysin: SystemIn, z_list) -> tuple[int, int]:
+    """(nfc, nfv) an input asks for: n_frozen_core where given, else the counted cores if frozen_core, else 0; -1 for n_frozen_virt
+    reads as its default."""
+    nfc = sysin.n_frozen_core if sysin.n_frozen_core >= 0 else (frozen_core_count(z_list) if sysin.frozen_core else 0)
+    return nfc, max(sysin.n_frozen_virt, 0)
+
+
+def read_nuclear_charges(path: str) -> list[int]:
+    """The nuclear charges of geom.dat (src/geometry.f90:23-46), in file order."""
+    with open(path) as fh:
+        natoms = int(fh.readline().split()[0])
+        return [int(float(fh.readline().split()[0])) for _ in range(natoms)]
 
 
 def spin_counts(sysin: SystemIn, nuclear_charge: int, nbasis: int) -> tuple[int, int]:

@@ -281,6 +281,9 @@ void k_pair_square_packed(Context& cx, double* out, const double* g, int n, int6
 void k_tri_pack(Context& cx, double* g, const double* half, int n, int64_t k_begin, int64_t k_end);           // g(PQ,K) = half(q,p,K)
 void k_pack_pairs(Context& cx, double* packed, const double* full, int n, int64_t p_begin = 0, int64_t p_end = -1, int ld = 0);
 void k_pack_cols(Context& cx, double* cols, const double* full, int n);   // cols[PQ np + RS] = full(s,r,PQ), every RS
+// the active orbital window [lo, lo + n_act): packed over n -> packed over n_act; the [npair x npair] alpha-beta block likewise
+void k_window_pack(Context& cx, double* dst, const double* src, int n_act, int lo);
+void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int n, int lo);
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);

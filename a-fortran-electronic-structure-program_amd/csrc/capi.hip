@@ -537,6 +537,24 @@ static void ao2mo_tg_xform(Context& cx, Ao2moTg& t, const double* in, double* ou
     const int bm = (knobs().ao2mo_mixed && M % TG_BM != 0 && M % TG_BM <= 96) ? TG_BM : 0;
     AFESP_HIP(tgemm_launch(p, dev, ng, tile, mx, cx.stream, cx.tg, bm));
 }
+// MP2 energy on the <ij|ab> slice of packed MO integrals over o + v orbitals (mp2.f90:418-440); levels: their o + v orbital energies (host)
+double mp2_of_packed(Context& cx, const double* packed, const double* levels, int64_t o, int64_t v)
+{
+    const int64_t n = o + v;
+    if (o * o * v * v <= ((int64_t)1 << 22) && knobs().mp2_packed) {   // (AFESP_MP2_PACKED=0: the five-launch form at every size, A/B runs)
+        // small systems: one launch, straight from the packed array (the slice and the denominators are formed on the fly)
+        return k_mp2_packed(cx, packed, levels, (int)o, (int)v);
+    }
+    double* e_dev = cx.scratch("ao2mo_e", n);
+    AFESP_HIP(hipMemcpyAsync(e_dev, levels, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    Tensor voovv = view(cx.scratch("ao2mo_v", o * o * v * v), {o, o, v, v}), D1 = view(cx.scratch("ao2mo_d1", o * v), {o, v}),
+           D2 = view(cx.scratch("ao2mo_d2", o * o * v * v), {o, o, v, v});
+    k_slice_phys(cx, voovv.d, packed, (int)o, (int)o, (int)v, (int)v, 0, 0, (int)o, (int)o);
+    k_denominators(cx, D1.d, D2.d, e_dev, (int)o, (int)v);
+    k_mp2_energy(cx, cx.scal, voovv.d, D2.d, (int)o, (int)v);
+    return host_scalars(cx, 1)[0];
+}
+
 }  // namespace
 
 // src/mp2.f90:261-449.  Four quarter transforms as MFMA GEMMs; each pass contracts the leading AO index with C(MO,AO) and
@@ -677,24 +695,62 @@ int afesp_ao2mo_mp2(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, const double* 
         }
         ctx->eri_mo_dev = packed;
         ctx->eri_mo_n = n;
-        // MP2 energy on the <ij|ab> slice (mp2.f90:418-440)
-        double emp2 = 0.0;
-        if (o * o * v * v <= ((int64_t)1 << 22) && knobs().mp2_packed) {   // (AFESP_MP2_PACKED=0: the five-launch form at every size, A/B runs)
-            // small systems: one launch, straight from the packed array (the slice and the denominators are formed on the fly)
-            emp2 = k_mp2_packed(cx, packed, canon_levels, (int)o, (int)v);
-        } else {
-            double* e_dev = cx.scratch("ao2mo_e", n);
-            AFESP_HIP(hipMemcpyAsync(e_dev, canon_levels, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
-            Tensor voovv = view(cx.scratch("ao2mo_v", o * o * v * v), {o, o, v, v}), D1 = view(cx.scratch("ao2mo_d1", o * v), {o, v}),
-                   D2 = view(cx.scratch("ao2mo_d2", o * o * v * v), {o, o, v, v});
-            k_slice_phys(cx, voovv.d, packed, (int)o, (int)o, (int)v, (int)v, 0, 0, (int)o, (int)o);
-            k_denominators(cx, D1.d, D2.d, e_dev, (int)o, (int)v);
-            k_mp2_energy(cx, cx.scal, voovv.d, D2.d, (int)o, (int)v);
-            emp2 = host_scalars(cx, 1)[0];
-        }
+        const double emp2 = mp2_of_packed(cx, packed, canon_levels, o, v);
         if (e_mp2) *e_mp2 = emp2;
         if (eri_mo_packed) {
             AFESP_HIP(hipMemcpyAsync(eri_mo_packed, packed, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+            cx.sync();
+        }
+    });
+}
+
+// The active orbital window [nfc, n - nfv) of the resident (or handed-in) packed MO integrals: a gather after the full transform
+// (DESIGN.md), left resident as afesp_ao2mo_mp2 leaves a basis of n_act functions; the full array goes back to the arena here.
+int afesp_mo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_frozen_core, int64_t n_frozen_virt,
+                    const double* canon_levels, const double* eri_mo_packed, double* eri_act, double* e_mp2)
+{
+    return guarded(ctx, [&] {
+        Context& cx = ctx->cx;
+        AFESP_HIP(hipSetDevice(cx.device));
+        const int64_t n = nbasis, nfc = n_frozen_core, nfv = n_frozen_virt;
+        if (n <= 0 || n > 1024 || nocc <= 0 || nocc >= n || !canon_levels) throw Error(1, "afesp_mo_window: bad extents");
+        if (nfc < 0 || nfv < 0) throw Error(1, "afesp_mo_window: negative number of frozen orbitals");
+        if (nfc >= nocc) throw Error(1, "afesp_mo_window: no active occupied orbital left");
+        if (nfv >= n - nocc) throw Error(1, "afesp_mo_window: no active virtual orbital left");
+        if (!eri_mo_packed && (!ctx->eri_mo_dev || ctx->eri_mo_n != n))
+            throw Error(1, "afesp_mo_window: eri_mo_packed is NULL and no MO integrals are resident for this basis size "
+                           "(call afesp_ao2mo_mp2 first; a window is taken once)");
+        const int64_t na = n - nfc - nfv, o = nocc - nfc, v = na - o, ne = neri_of(n), nea = neri_of(na);
+        double* full = ctx->eri_mo_dev;
+        if (eri_mo_packed) {   // from the host: whatever was resident is replaced, as a transform would replace it
+            if (ctx->cc.eri_src == full) ctx->cc.eri_src = nullptr;
+            ctx->eri_mo_dev = nullptr;
+            ctx->eri_mo_n = 0;
+            if (full) cx.release(full);
+            full = cx.alloc_raw(ne);
+            AFESP_HIP(hipMemcpyAsync(full, eri_mo_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+        }
+        double* act = full;
+        if (na != n) {   // (the whole basis: the array stays where it is, bit for bit)
+            try {
+                act = cx.alloc_raw(nea);
+                k_window_pack(cx, act, full, (int)na, (int)nfc);
+            } catch (...) {
+                if (act != full) cx.release(act);
+                if (eri_mo_packed) cx.release(full);   // (resident integrals stay as they were)
+                throw;
+            }
+            if (ctx->cc.eri_src == full) ctx->cc.eri_src = nullptr;   // a solver state initialised from them can no longer form <ef|ab>
+            ctx->eri_mo_dev = nullptr;
+            ctx->eri_mo_n = 0;
+            cx.release(full);   // (waits for the gather) a context never keeps two packed arrays past the call
+        }
+        ctx->eri_mo_dev = act;
+        ctx->eri_mo_n = na;
+        const double emp2 = mp2_of_packed(cx, act, canon_levels + nfc, o, v);
+        if (e_mp2) *e_mp2 = emp2;
+        if (eri_act) {
+            AFESP_HIP(hipMemcpyAsync(eri_act, act, sizeof(double) * nea, hipMemcpyDeviceToHost, cx.stream));
             cx.sync();
         }
     });
@@ -1413,6 +1469,55 @@ int afesp_ao2mo_ump2(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbe
         if (eri_aa) AFESP_HIP(hipMemcpyAsync(eri_aa, aa, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
         if (eri_bb) AFESP_HIP(hipMemcpyAsync(eri_bb, bb, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
         if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    });
+}
+
+// The same window of the three blocks afesp_ao2mo_ump2 left: block by block, each full block back to the arena before the next
+// window is asked for.
+int afesp_umo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, int64_t n_frozen_virt,
+                     const double* levels_a, const double* levels_b, double* eri_aa, double* eri_ab, double* eri_bb, double* e_ump2)
+{
+    return guarded(ctx, [&] {
+        Context& cx = ctx->cx;
+        AFESP_HIP(hipSetDevice(cx.device));
+        const int64_t n = nbasis, nfc = n_frozen_core, nfv = n_frozen_virt;
+        if (n <= 0 || n > 1024 || nalpha < 0 || nbeta < 0 || nalpha > n || nbeta > n || !levels_a || !levels_b)
+            throw Error(1, "afesp_umo_window: bad extents");
+        if (nfc < 0 || nfv < 0) throw Error(1, "afesp_umo_window: negative number of frozen orbitals");
+        // what afesp_ccsd_uso_init accepts for the active extents: a spin may be left without occupied (or without virtual) orbitals,
+        // the two spins together keep at least one of each
+        const int64_t na = n - nfc - nfv, oa = nalpha - nfc, ob = nbeta - nfc;
+        if (na <= 0 || oa < 0 || ob < 0 || oa + ob <= 0) throw Error(1, "afesp_umo_window: no active occupied orbital left");
+        if (oa > na || ob > na || oa + ob >= 2 * na) throw Error(1, "afesp_umo_window: no active virtual orbital left");
+        if (!ctx->uhf_aa || ctx->uhf_n != n)
+            throw Error(1, "afesp_umo_window: no UHF MO integrals resident for this basis size (call afesp_ao2mo_ump2 first; a window is "
+                           "taken once)");
+        const int64_t nea = neri_of(na), npa = na * (na + 1) / 2;
+        if (na != n) {
+            double* w = cx.alloc_raw(nea);
+            k_window_pack(cx, w, ctx->uhf_aa, (int)na, (int)nfc);
+            cx.release(ctx->uhf_aa);
+            ctx->uhf_aa = w;
+            ctx->uhf_n = 0;   // (from here on the blocks are of mixed extents until all three are done)
+            w = cx.alloc_raw(nea);
+            k_window_pack(cx, w, ctx->uhf_bb, (int)na, (int)nfc);
+            cx.release(ctx->uhf_bb);
+            ctx->uhf_bb = w;
+            w = cx.alloc_raw(npa * npa);
+            k_window_pairs(cx, w, ctx->uhf_ab, (int)na, (int)n, (int)nfc);
+            cx.release(ctx->uhf_ab);
+            ctx->uhf_ab = w;
+            ctx->uhf_n = na;
+        }
+        double* ea = cx.scratch("ao2mo_ea", 2 * na);
+        AFESP_HIP(hipMemcpyAsync(ea, levels_a + nfc, sizeof(double) * na, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(ea + na, levels_b + nfc, sizeof(double) * na, hipMemcpyHostToDevice, cx.stream));
+        const double e2 = k_ump2(cx, ctx->uhf_aa, ctx->uhf_bb, ctx->uhf_ab, ea, ea + na, (int)na, (int)oa, (int)ob);
+        if (e_ump2) *e_ump2 = e2;
+        if (eri_aa) AFESP_HIP(hipMemcpyAsync(eri_aa, ctx->uhf_aa, sizeof(double) * nea, hipMemcpyDeviceToHost, cx.stream));
+        if (eri_bb) AFESP_HIP(hipMemcpyAsync(eri_bb, ctx->uhf_bb, sizeof(double) * nea, hipMemcpyDeviceToHost, cx.stream));
+        if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, ctx->uhf_ab, sizeof(double) * npa * npa, hipMemcpyDeviceToHost, cx.stream));
         cx.sync();
     });
 }

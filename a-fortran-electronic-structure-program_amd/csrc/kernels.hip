@@ -1295,6 +1295,40 @@ __global__ void tri_pack_kernel(double* g, const double* half, int n, int64_t k_
         g[pq + np * (k_begin + k)] = half[q + N * p + N * N * k];
     }
 }
+// Active orbital window [lo, lo + n_act) of the packed MO integrals (afesp_mo_window): dst[ijkl(p,q,r,s)] = src[ijkl(p+lo,q+lo,r+lo,s+lo)],
+// dst packed over n_act orbitals, src over n.  Shifting all four indices by lo keeps p >= q, r >= s and PQ >= RS, so every element is
+// read where it lies: a pure gather, one destination element per thread (contiguous writes; reads are runs along s).  64-bit flat
+// indices throughout (neri(220) = 2.96e8, neri(1024) = 1.4e11).
+__global__ void window_pack_kernel(double* __restrict__ dst, const double* __restrict__ src, int lo, int64_t total)
+{
+    GRID_STRIDE(x, total)
+    {
+        // x = PQ(PQ+1)/2 + RS, RS <= PQ: the same triangular inverse, on 64-bit pair indices
+        int64_t pq = (int64_t)((sqrt(8.0 * (double)x + 1.0) - 1.0) * 0.5);
+        while (pq * (pq + 1) / 2 > x) --pq;
+        while ((pq + 1) * (pq + 2) / 2 <= x) ++pq;
+        const int64_t rs = x - pq * (pq + 1) / 2;
+        int q, p, s, r;
+        unpair(pq, q, p);
+        unpair(rs, s, r);
+        const int64_t PQ = tri(p + lo, q + lo), RS = tri(r + lo, s + lo);
+        dst[x] = src[PQ * (PQ + 1) / 2 + RS];
+    }
+}
+// The same for the alpha-beta block of the open-shell path, a full [npair x npair] matrix (afesp_umo_window):
+// dst[tri(p,q) np_act + tri(r,s)] = src[tri(p+lo,q+lo) np + tri(r+lo,s+lo)]
+__global__ void window_pairs_kernel(double* __restrict__ dst, const double* __restrict__ src, int n_act, int n, int lo)
+{
+    const int64_t npa = (int64_t)n_act * (n_act + 1) / 2, np = (int64_t)n * (n + 1) / 2;
+    GRID_STRIDE(x, npa * npa)
+    {
+        const int64_t rs = x % npa, pq = x / npa;
+        int q, p, s, r;
+        unpair(pq, q, p);
+        unpair(rs, s, r);
+        dst[x] = src[tri(p + lo, q + lo) * np + tri(r + lo, s + lo)];
+    }
+}
 static unsigned pair_square_grid(int n, int64_t c_begin, int64_t c_end)
 {
     const int64_t nb = (n + 15) / 16;
@@ -1486,6 +1520,16 @@ void k_pack_cols(Context& cx, double* cols, const double* full, int n)
 {
     const int64_t np = (int64_t)n * (n + 1) / 2;
     LAUNCH(pack_cols_kernel, dim3(grid_for(np * np, 65536)), cols, full, n);
+}
+void k_window_pack(Context& cx, double* dst, const double* src, int n_act, int lo)
+{
+    const int64_t npa = (int64_t)n_act * (n_act + 1) / 2, total = npa * (npa + 1) / 2;
+    if (total > 0) LAUNCH(window_pack_kernel, dim3(grid_for(total, 65536)), dst, src, lo, total);
+}
+void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int n, int lo)
+{
+    const int64_t npa = (int64_t)n_act * (n_act + 1) / 2;
+    if (npa > 0) LAUNCH(window_pairs_kernel, dim3(grid_for(npa * npa, 65536)), dst, src, n_act, n, lo);
 }
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {

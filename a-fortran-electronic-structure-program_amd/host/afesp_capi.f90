@@ -10,7 +10,7 @@ module afesp_capi
              afesp_ccsd_so_energy, afesp_ccsd_so_iterate, afesp_ccsd_so_diis, afesp_ccsd_so_t, afesp_ccsd_so_t_ntriples, &
              afesp_read_eri_text, afesp_write_fcidump, afesp_build_fock, afesp_ccsd_t_plain, afesp_device_count, &
              afesp_comm_init, afesp_comm_destroy, afesp_allreduce_sum, afesp_ccsd_t_shard_bounds, afesp_ccsd_t_block_size, &
-             afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, &
+             afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, afesp_mo_window, afesp_umo_window, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -173,6 +173,29 @@ module afesp_capi
          integer(c_int64_t), value :: nbasis, nalpha, nbeta
          real(c_double), intent(in) :: levels_a(*), levels_b(*)
          integer(c_int), value :: diis_n_errmat
+         integer(c_int) :: rc
+      end function
+      !> the active orbital window [nfc, nbasis - nfv) of the resident MO integrals (frozen core / frozen virtuals): afterwards
+      !> afesp_ccsd_init / afesp_ccsd_so_init / the (T) calls take the active extents and canon_levels(nfc + 1:)
+      function afesp_mo_window(ctx, nbasis, nocc, n_frozen_core, n_frozen_virt, canon_levels, eri_mo_packed, eri_act, e_mp2) &
+         bind(C, name='afesp_mo_window') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nocc, n_frozen_core, n_frozen_virt
+         real(c_double), intent(in) :: canon_levels(*)
+         type(c_ptr), value :: eri_mo_packed, eri_act
+         real(c_double), intent(out) :: e_mp2
+         integer(c_int) :: rc
+      end function
+      !> the same for the three blocks afesp_ao2mo_ump2 left; afterwards afesp_ccsd_uso_init with the active extents
+      function afesp_umo_window(ctx, nbasis, nalpha, nbeta, n_frozen_core, n_frozen_virt, levels_a, levels_b, eri_aa, eri_ab, &
+                                eri_bb, e_ump2) bind(C, name='afesp_umo_window') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta, n_frozen_core, n_frozen_virt
+         real(c_double), intent(in) :: levels_a(*), levels_b(*)
+         type(c_ptr), value :: eri_aa, eri_ab, eri_bb
+         real(c_double), intent(out) :: e_ump2
          integer(c_int) :: rc
       end function
       !> replaces write_fcidump (reference src/mp2.f90:451-487)

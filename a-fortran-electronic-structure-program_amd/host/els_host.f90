@@ -40,6 +40,10 @@ module host_config
       logical :: spinorb = .false.   ! the _spinorb calculation types (reference src/system.f90:117-137)
       logical :: uhf = .false.       ! the open-shell types UHF_scf, UMP2, UCCSD, UCCSD(T) (canonical UHF orbitals)
       integer :: charge = 0, multiplicity = 1
+      ! active orbital window of the correlated steps (no counterpart in the reference); all three absent: every orbital correlated
+      logical :: frozen_core = .false.   ! freeze the noble-gas cores counted from geom.dat
+      integer :: n_frozen_core = -1      ! explicit number of lowest MOs to freeze (-1: not given); wins over frozen_core
+      integer :: n_frozen_virt = 0       ! highest MOs dropped
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -48,15 +52,18 @@ contains
       character(40) :: calc_type
       real(dp) :: scf_e_tol, scf_d_tol, ccsd_e_tol, ccsd_t_tol
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
-      logical :: write_fcidump, scf_read_guess, scf_write_guess, there
+      integer :: n_frozen_core, n_frozen_virt
+      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
-         ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity
+         ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
+         frozen_core, n_frozen_core, n_frozen_virt
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
       scf_maxiter = d%scf_maxiter; ccsd_maxiter = d%ccsd_maxiter; write_fcidump = d%write_fcidump
       scf_read_guess = d%scf_read_guess; scf_write_guess = d%scf_write_guess
       charge = d%charge; multiplicity = d%multiplicity
+      frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -68,6 +75,9 @@ contains
       cfg%scf_maxiter = scf_maxiter; cfg%ccsd_maxiter = ccsd_maxiter; cfg%write_fcidump = write_fcidump
       cfg%scf_read_guess = scf_read_guess; cfg%scf_write_guess = scf_write_guess
       cfg%charge = charge; cfg%multiplicity = multiplicity
+      cfg%frozen_core = frozen_core; cfg%n_frozen_core = n_frozen_core; cfg%n_frozen_virt = max(n_frozen_virt, 0)
+      if (n_frozen_core < -1 .or. n_frozen_virt < -1) &
+         call fail('system::read_system_in', 'n_frozen_core and n_frozen_virt must be non-negative integers!')
       select case (trim(calc_type))
       case ('RHF');              cfg%level = LEVEL_RHF
       case ('MP2_spatial');      cfg%level = LEVEL_MP2
@@ -102,6 +112,7 @@ module host_inputs
    implicit none
    type molecule
       integer :: nbasis = 0, natoms = 0, nel = 0, nocc = 0, nvirt = 0
+      integer :: ncore = 0   ! doubly occupied noble-gas core orbitals of the atoms (-1: an atom beyond Kr, no count)
       real(dp) :: e_nuc = 0.0_dp
       real(dp), allocatable :: ovlp(:, :), hcore(:, :), eri(:)
    end type
@@ -182,6 +193,18 @@ contains
       end do
       close (unit)
       mol%nel = sum(z); mol%nocc = mol%nel/2; mol%nvirt = mol%nbasis - mol%nocc
+      mol%ncore = 0      ! the core below each atom's valence shell: He for Z <= 10, Ne for Z <= 18, Ar for Z <= 36
+      do a = 1, mol%natoms
+         if (z(a) > 36 .or. mol%ncore < 0) then
+            mol%ncore = -1
+         else if (z(a) > 18) then
+            mol%ncore = mol%ncore + 9
+         else if (z(a) > 10) then
+            mol%ncore = mol%ncore + 5
+         else if (z(a) > 2) then
+            mol%ncore = mol%ncore + 1
+         end if
+      end do
       mol%e_nuc = 0.0_dp
       do j = 2, mol%natoms
          do i = 1, j - 1
@@ -538,6 +561,9 @@ program els_amd
    real(dp), allocatable :: cb(:, :), lb(:)     ! beta orbitals of the open-shell types (alpha: coeff / levels)
    real(dp) :: s2
    integer :: na, nb
+   ! the active orbital window [nfc, nbasis - nfv): active basis size, occupied / virtual counts, electrons and spin counts
+   integer :: nfc, nfv, n_act, o_act, v_act, nel_act, na_act, nb_act
+   logical :: windowed
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
    integer(c_int) :: rc, conv
@@ -621,6 +647,37 @@ program els_amd
       write (out, '(1X, A, 1X, I0)') 'Number of occupied orbitals:', mol%nocc
       write (out, '(1X, A, 1X, I0)') 'Number of virtual orbitals:', mol%nvirt
    end if
+   ! the active orbital window of the correlated steps
+   nfc = 0; nfv = 0
+   if (cfg%level >= LEVEL_MP2) then
+      nfv = cfg%n_frozen_virt
+      if (cfg%n_frozen_core >= 0) then
+         nfc = cfg%n_frozen_core
+      else if (cfg%frozen_core) then
+         if (mol%ncore < 0) call fail('system::read_system_in', 'frozen_core: no core count for atoms beyond Kr, give n_frozen_core')
+         nfc = mol%ncore
+      end if
+   end if
+   windowed = nfc > 0 .or. nfv > 0
+   n_act = mol%nbasis - nfc - nfv; o_act = mol%nocc - nfc; v_act = mol%nvirt - nfv; nel_act = mol%nel - 2*nfc
+   if (cfg%uhf) then
+      na_act = na - nfc; nb_act = nb - nfc
+   else
+      na_act = o_act; nb_act = o_act
+   end if
+   if (windowed) then
+      write (out, '(1X, A, 1X, I0)') 'Number of frozen core orbitals:', nfc
+      write (out, '(1X, A, 1X, I0)') 'Number of frozen virtual orbitals:', nfv
+      if (cfg%uhf) then   ! (what afesp_ccsd_uso_init accepts: a spin may keep no occupied orbital)
+         if (n_act <= 0 .or. na_act < 0 .or. nb_act < 0 .or. na_act + nb_act <= 0) &
+            call fail('system::read_system_in', 'the frozen core leaves no active occupied orbital')
+         if (na_act > n_act .or. na_act + nb_act >= 2*n_act) &
+            call fail('system::read_system_in', 'the frozen virtual orbitals leave no active virtual orbital')
+      else
+         if (o_act <= 0) call fail('system::read_system_in', 'the frozen core leaves no active occupied orbital')
+         if (v_act <= 0) call fail('system::read_system_in', 'the frozen virtual orbitals leave no active virtual orbital')
+      end if
+   end if
    write (out, '(1X, A, 1X, ES15.8)') 'E_nuc:', mol%e_nuc
    write (out, '(1X, A, 1X, A)') 'calc_type:', trim(cfg%calc_type)
 
@@ -643,6 +700,11 @@ program els_amd
       rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
       if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
+      if (windowed) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
+         rc = afesp_umo_window(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), &
+                               int(nfv, c_int64_t), levels, lb, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
+         if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
+      end if
       write (out, '(1X, A, 1X, F15.8)') 'UMP2 correlation energy (Hartree):', e_mp2
       e_highest = e_mp2
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UMP2:', seconds() - t0, 's'
@@ -650,8 +712,8 @@ program els_amd
          t0 = seconds()
          write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD'; write (out, '(1X, 10("-"))')
          write (out, '(1X, A)') 'Forming slices of antisymmetrised spinorbital ERIs from the UHF blocks...'
-         rc = afesp_ccsd_uso_init(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), levels, lb, &
-                                  int(cfg%ccsd_diis_n_errmat, c_int))
+         rc = afesp_ccsd_uso_init(ctx, int(n_act, c_int64_t), int(na_act, c_int64_t), int(nb_act, c_int64_t), levels(nfc + 1:), &
+                                  lb(nfc + 1:), int(cfg%ccsd_diis_n_errmat, c_int))
          if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
          rc = afesp_ccsd_so_energy(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, energy, rms, conv)
          if (rc /= 0) call fail('ccsd::update_cc_energy', afesp_error_text(ctx))
@@ -683,7 +745,7 @@ program els_amd
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
-            t_hi = afesp_ccsd_so_t_ntriples(int(na + nb, c_int64_t))     ! i<j<k triples, an even split over the ranks
+            t_hi = afesp_ccsd_so_t_ntriples(int(na_act + nb_act, c_int64_t))     ! i<j<k triples, an even split over the ranks
             t_lo = (int(rank, c_int64_t)*t_hi)/world; t_hi = (int(rank + 1, c_int64_t)*t_hi)/world
             rc = afesp_ccsd_so_t(ctx, t_lo, t_hi, tq(1))
             if (world > 1) then   ! (every rank enters the sum, a failed shard as a flag: as in the spin-orbital branch below)
@@ -708,15 +770,18 @@ program els_amd
       write (out, '(1X, A)') 'Performing AO to MO ERI transformation...'
       rc = afesp_ao2mo_mp2(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), coeff, levels, c_null_ptr, c_null_ptr, e_mp2)
       if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
+      if (windowed) then
+         ! frozen orbitals: the FCIDUMP (if asked for) is of the full integrals; then the window over the active orbitals replaces
+         ! them on the device, and the MP2 energy is the frozen-core one
+         if (cfg%write_fcidump) call dump_integrals()
+         rc = afesp_mo_window(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), int(nfc, c_int64_t), int(nfv, c_int64_t), &
+                              levels, c_null_ptr, c_null_ptr, e_mp2)
+         if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
+      end if
       write (out, '(1X, A)') 'Calculating MP2 energy...'
       write (out, '(1X, A, 1X, F15.8)') 'MP2 correlation energy (Hartree):', e_mp2
       e_highest = e_mp2
-      if (cfg%write_fcidump) then        ! reference src/mp2.f90:445-447
-         write (out, '(1X, A)') 'Writing FCIDUMP file...'
-         rc = afesp_write_fcidump(ctx, 'FCIDUMP'//c_null_char, int(mol%nbasis, c_int64_t), nlines)
-         if (rc /= 0) call fail('mp2::write_fcidump', afesp_error_text(ctx))
-         write (out, '(1X, A)') 'Done writing FCIDUMP file!'
-      end if
+      if (cfg%write_fcidump .and. .not. windowed) call dump_integrals()        ! reference src/mp2.f90:445-447
       t1s = seconds()
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for restricted MP2:', t1s - t0, 's'
 
@@ -730,7 +795,7 @@ program els_amd
          ! AFESP_SO_FOO_AS_PUBLISHED=1: tau~ term of F_mi in Stanton's index order (what the reference's shipped
          ! ref_out was computed with); default: as src/ccsd.f90:789-794 accumulates it today
          call get_environment_variable('AFESP_SO_FOO_AS_PUBLISHED', envval)
-         rc = afesp_ccsd_so_init(ctx, int(mol%nbasis, c_int64_t), int(mol%nel, c_int64_t), c_null_ptr, levels, &
+         rc = afesp_ccsd_so_init(ctx, int(n_act, c_int64_t), int(nel_act, c_int64_t), c_null_ptr, levels(nfc + 1:), &
                                  int(cfg%ccsd_diis_n_errmat, c_int), merge(1_c_int, 0_c_int, trim(envval) == '1'))
          if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
          write (out, '(1X, A, 1X, F8.6, A)') 'Time taken:', seconds() - t0, ' s'
@@ -767,7 +832,7 @@ program els_amd
             ! ---------------- spin-orbital (T) (reference do_ccsd_t_spinorb, src/ccsd.f90:1812-1922)
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
-            t_hi = afesp_ccsd_so_t_ntriples(int(mol%nel, c_int64_t))     ! i<j<k triples, an even split over the ranks
+            t_hi = afesp_ccsd_so_t_ntriples(int(nel_act, c_int64_t))     ! i<j<k triples, an even split over the ranks
             t_lo = (int(rank, c_int64_t)*t_hi)/world; t_hi = (int(rank + 1, c_int64_t)*t_hi)/world
             rc = afesp_ccsd_so_t(ctx, t_lo, t_hi, tq(1))
             if (world > 1) then
@@ -791,7 +856,7 @@ program els_amd
          t0 = seconds()
          write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD'; write (out, '(1X, 10("-"))')
          write (out, '(1X, A)') 'Initialise CC intermediate tensors and DIIS auxilliary arrays...'
-         rc = afesp_ccsd_init(ctx, int(mol%nocc, c_int64_t), int(mol%nvirt, c_int64_t), c_null_ptr, levels, &
+         rc = afesp_ccsd_init(ctx, int(o_act, c_int64_t), int(v_act, c_int64_t), c_null_ptr, levels(nfc + 1:), &
                               int(cfg%ccsd_diis_n_errmat, c_int))
          if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
          write (out, '(1X, A, 1X, F8.6, A)') 'Time taken:', seconds() - t0, ' s'
@@ -818,13 +883,13 @@ program els_amd
             if (rc /= 0) call fail('ccsd::update_diis_cc', 'Linear solve failed!')
          end do
          if (cc_ok) then
-            allocate (t1(mol%nocc, mol%nvirt))
+            allocate (t1(o_act, v_act))
             block
                real(dp), allocatable :: t2(:)
-               allocate (t2(int(mol%nocc, i8)**2*int(mol%nvirt, i8)**2))
+               allocate (t2(int(o_act, i8)**2*int(v_act, i8)**2))
                rc = afesp_ccsd_get_amplitudes(ctx, t1, t2)
             end block
-            t1diag = sqrt(sum(t1**2))/sqrt(real(mol%nel, dp))
+            t1diag = sqrt(sum(t1**2))/sqrt(real(nel_act, dp))   ! (the correlated electrons)
             write (out, '(75("-"))')
             write (out, '(1X, A)') 'Convergence reached within tolerance.'
             write (out, '(1X, A, 1X, F15.12)') 'Final CCSD Energy (Hartree):', energy
@@ -845,7 +910,7 @@ program els_amd
             ! this rank's shard of the (i<=j<=k) list (the whole list for one rank); the ranks must enumerate the triples in
             ! the same order, i.e. agree on the occupied block size: it rides along in the all-reduce
             allocate (bounds(world + 1))
-            rc = afesp_ccsd_t_shard_bounds(ctx, int(mol%nocc, c_int64_t), int(mol%nvirt, c_int64_t), &
+            rc = afesp_ccsd_t_shard_bounds(ctx, int(o_act, c_int64_t), int(v_act, c_int64_t), &
                                            merge(1_c_int, 0_c_int, cfg%comp_renorm), int(world, c_int), bounds)
             if (rc /= 0) call fail('ccsd::do_ccsd_t_spatial', afesp_error_text(ctx))
             t_lo = bounds(rank + 1); t_hi = bounds(rank + 2)
@@ -862,7 +927,7 @@ program els_amd
                rc_mine = rc; my_error = ''
                if (rc_mine /= 0) then; my_error = afesp_error_text(ctx); tq = 0.0_dp; end if
                sb = 0
-               if (rc_mine == 0) rc_mine = afesp_ccsd_t_block_size(ctx, int(mol%nocc, c_int64_t), int(mol%nvirt, c_int64_t), &
+               if (rc_mine == 0) rc_mine = afesp_ccsd_t_block_size(ctx, int(o_act, c_int64_t), int(v_act, c_int64_t), &
                                                                    merge(1_c_int, 0_c_int, cfg%comp_renorm), sb)
                if (rc_mine /= 0 .and. len_trim(my_error) == 0) my_error = afesp_error_text(ctx)
                red(1:6) = tq; red(7) = real(sb, dp); red(8) = real(sb, dp)**2; red(9) = merge(1.0_dp, 0.0_dp, rc_mine /= 0)
@@ -978,4 +1043,12 @@ program els_amd
    write (out, '(1X, A, 1X, F15.10)') 'Total energy:                  ', e_hf + e_highest + mol%e_nuc
    write (out, '(1X, 64("="))')
    write (out, '(1X, A, 1X, F16.8)') 'Total execution time:', seconds() - tstart
+contains
+   !> FCIDUMP of the MO integrals resident after the AO->MO transform (reference src/mp2.f90:445-447)
+   subroutine dump_integrals()
+      write (out, '(1X, A)') 'Writing FCIDUMP file...'
+      rc = afesp_write_fcidump(ctx, 'FCIDUMP'//c_null_char, int(mol%nbasis, c_int64_t), nlines)
+      if (rc /= 0) call fail('mp2::write_fcidump', afesp_error_text(ctx))
+      write (out, '(1X, A)') 'Done writing FCIDUMP file!'
+   end subroutine
 end program els_amd

@@ -59,6 +59,21 @@ int64_t afesp_neri(int64_t nbasis); /* packed length, src/integrals.f90:175-176 
 int afesp_ao2mo_mp2(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, const double* canon_coeff, const double* canon_levels,
                     const double* eri_packed, double* eri_mo_packed, double* e_mp2);
 
+/* Active orbital window [n_frozen_core, nbasis - n_frozen_virt) (frozen core / frozen virtuals; the reference has neither).  Replaces
+ * the MO integrals resident after afesp_ao2mo_mp2 (eri_mo_packed == NULL) -- or takes them from the host -- by their window over
+ * n_act = nbasis - n_frozen_core - n_frozen_virt orbitals, left resident exactly as afesp_ao2mo_mp2 leaves a basis of n_act functions:
+ * afesp_ccsd_init(nocc - nfc, nvirt - nfv, NULL, canon_levels + nfc, ...), afesp_ccsd_so_init(n_act, nel - 2 nfc, NULL,
+ * canon_levels + nfc, ...), the (T) calls, shard bounds and afesp_write_fcidump(n_act) then act on the window (with canonical orbitals
+ * the active Fock matrix is diagonal with the same levels: no new equations).  *e_mp2 = frozen-core MP2 energy (mp2.f90:418-440 over
+ * the active occupied / virtual orbitals).  eri_act (may be NULL) receives the packed window, neri(n_act) doubles.
+ * A gather on the device after the full transform; the full array goes back to the context's arena inside the call, and a CCSD
+ * state initialised from it can no longer form v_vvvv on request (as after a new afesp_ao2mo_mp2).  n_frozen_core = n_frozen_virt = 0
+ * is legal and leaves the resident array as it is.
+ * Status 1, with the resident integrals untouched: a negative count; no active occupied (nfc >= nocc) or no active virtual
+ * (nfv >= nbasis - nocc) orbital left; NULL source with nothing resident for nbasis (so also a second window on a windowed context). */
+int afesp_mo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_frozen_core, int64_t n_frozen_virt,
+                    const double* canon_levels, const double* eri_mo_packed, double* eri_act, double* e_mp2);
+
 /* Replaces init_cc + init_diis_cc_t (src/ccsd.f90:313-316, :404-615).
  *   eri_mo_packed: packed MO integrals from the host, or NULL to use the ones afesp_ao2mo_mp2 left on the device.
  *   diis_n_errmat: sys%ccsd_diis_n_errmat (<2 switches DIIS off, src/ccsd.f90:593-595). */
@@ -191,6 +206,13 @@ int afesp_ao2mo_ump2(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbe
                      double* eri_bb, double* e_ump2);
 int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* levels_a, const double* levels_b,
                         int diis_n_errmat);
+/* afesp_mo_window for the three blocks afesp_ao2mo_ump2 left resident: the same number of lowest orbitals is frozen for both spins and
+ * the same number of highest ones dropped; afterwards afesp_ccsd_uso_init(n_act, nalpha - nfc, nbeta - nfc, levels_a + nfc,
+ * levels_b + nfc, ...).  The active extents must be ones afesp_ccsd_uso_init accepts (a spin may keep no occupied orbital, the two
+ * together keep at least one occupied and one virtual spin orbital); otherwise, for a negative count, or with no blocks resident for
+ * nbasis: status 1, blocks untouched.  eri_aa / eri_bb (neri(n_act)) and eri_ab (npair_act^2) may be NULL.  *e_ump2 = frozen-core UMP2. */
+int afesp_umo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, int64_t n_frozen_virt,
+                     const double* levels_a, const double* levels_b, double* eri_aa, double* eri_ab, double* eri_bb, double* e_ump2);
 
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
