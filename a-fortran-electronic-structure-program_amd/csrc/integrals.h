@@ -1,0 +1,76 @@
+// integrals.h -- the integral layer: everything between "AO integrals arrive" and "packed MO integrals are resident" (integrals.hip).
+#pragma once
+#include "ccsd.h"
+
+namespace afesp {
+
+inline int64_t npair_of(int64_t n) { return n * (n + 1) / 2; }
+inline int64_t neri_of(int64_t n) { return npair_of(npair_of(n)); }
+
+// Which form a transform of basis size n takes, and the leading dimension of the squared-up temporaries that goes with it (the
+// half-unpacked AO integrals a Fock build leaves for it included) -- decided ONCE per call, from one snapshot of the knob table: the
+// transforms on the LDS-DMA GEMM keep columns of 16 ceil(n / 16) doubles -- every column then starts on a 128-byte line, for the GEMM's
+// K steps and for the layout kernels' runs alike (n = 220: 39.2 -> 36 ms per transform; n = 224 ran FASTER than n = 220 before,
+// profiles/r06_ao2mo_alignment_scan.txt) -- every other form keeps n.
+struct Ao2moForm {
+    bool blocked;   // slab by slab (AFESP_AO2MO_BLOCKED=0 / 1; default: where the n^2 npair temporaries pass 2^31 doubles)
+    bool use_tg;    // the LDS-DMA GEMM: even n, and from n = 96 on (its tile has 128 rows: below that most of a tile is padding and the
+                    // transform is launch-bound anyway); AFESP_AO2MO_TG=0 / 1: never / for every even n >= 16 (tests, A/B runs)
+    bool pair;      // up to 64 basis functions: the LDS-resident pair transform (AFESP_AO2MO_PAIR=0: the gather-GEMM form)
+    int64_t ld;
+    // open_shell: afesp_ao2mo_ump2's forms -- no LDS-DMA one, dense columns, the pair transform up to n = 64 whatever the knobs say
+    explicit Ao2moForm(int64_t n, bool open_shell = false);
+};
+
+// The integrals resident in a context.  The member functions are the only code that writes these fields.
+struct Integrals {
+    double* ao = nullptr;   // packed AO integrals (afesp_read_eri_text / afesp_set_eri / afesp_synthetic_ao)
+    int64_t ao_n = 0;       // nbasis they belong to
+    double* mo = nullptr;   // packed MO integrals left by afesp_ao2mo_mp2 / afesp_mo_window
+    int64_t mo_n = 0;
+    // the UHF MO integrals left by afesp_ao2mo_ump2 for afesp_ccsd_uso_init: alpha-alpha and beta-beta packed, alpha-beta full
+    // (kept apart from mo: the RHF calls never see them, nor they the RHF ones)
+    double *uhf_aa = nullptr, *uhf_bb = nullptr, *uhf_ab = nullptr;
+    int64_t uhf_n = 0;
+    // scratch "ao2mo_a" holds the half-unpacked AO integrals (ij|KL) of this basis size / leading dimension / scratch epoch
+    int64_t half_n = 0, half_ld = 0, half_epoch = -1;
+    // the LDS-DMA transforms' temporaries whose padding rows are known to be zero: buffers, extents, scratch epoch
+    const double *pad_a = nullptr, *pad_b = nullptr;
+    int64_t pad_n = 0, pad_ld = 0, pad_epoch = -1;
+
+    // doubles of a squared-up temporary, the same for a Fock build and the transform after it, which so finds the build's very buffer (16 of
+    // slack: the LDS-DMA GEMM reads whole 16-element K steps, i.e. up to Kc - n elements past a column's end -- the next column's, finite,
+    // times the zero padding of C -- and past the tensor's end behind the last one)
+    static int64_t temp_size(int64_t n, int64_t ld) { return ld * n * npair_of(n) + 16; }
+
+    double* adopt_ao(Context& cx, int64_t n);   // a fresh device array to fill; the old one is released, the half-unpacked copy stale
+    void upload_ao(Context& cx, int64_t n, const double* host);
+    bool half_valid(const Context& cx, int64_t n, int64_t ld) const { return half_n == n && half_ld == ld && half_epoch == cx.scratch_epoch; }
+    // (ij|KL) in scratch "ao2mo_a", columns of `ld` doubles as the transform will want them: built by the first Fock build of an SCF
+    const double* half_unpacked(Context& cx, int64_t n, int64_t& ld);
+    void half_restamp(const Context& cx) { half_epoch = cx.scratch_epoch; }   // (growing a Fock work buffer moves the epoch, not u)
+    void half_overwritten() { half_n = 0; }
+    void padding_overwritten() { pad_n = 0; }   // (a form that writes the temporaries densely: zeroed padding rows are data now)
+    void zero_padding(Context& cx, double* a, double* b, int64_t n, int64_t ld);
+    void release_uhf(Context& cx);
+    void adopt_uhf(Context& cx, int64_t n);            // the three blocks for basis size n (kept where they are of that size)
+    void window_uhf(Context& cx, int64_t n_act, int64_t lo);   // the orbitals [lo, lo + n_act) of the three blocks, as afesp_mo_window's of mo
+    void drop_mo(Context& cx, CCState& cc);            // back to the arena; a solver state initialised from them can no longer form <ef|ab>
+    double* replace_mo(Context& cx, CCState& cc, int64_t n);   // the array a transform writes: the resident one if it has the size
+    void set_mo(double* packed, int64_t n) { mo = packed; mo_n = n; }
+};
+
+// the bodies of the entry points of the same names (capi.hip checks the arguments); each returns the energy / the count it reports
+double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, const double* coeff, const double* levels,
+                 const double* eri_packed, double* eri_mo_packed);
+double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
+                  const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab, double* eri_bb);
+double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
+                 const double* eri_mo_packed, double* eri_act);
+// E(UMP2) of the three resident blocks (levels on the host, for their basis size), and the blocks themselves for whoever asks
+double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, const double* levels_b, int64_t oa, int64_t ob, double* eri_aa,
+                      double* eri_ab, double* eri_bb);
+int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
+int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
+
+}  // namespace afesp

@@ -1,0 +1,657 @@
+// integrals.hip -- the integral layer (integrals.h): the resident AO / MO integrals and their validity records, the AO->MO transform in
+// its forms (pair kernels, gather GEMM, LDS-DMA GEMM, slab-blocked), the orbital windows, the text reader and the FCIDUMP writer.
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "integrals.h"
+#include "tgemm.h"
+
+using namespace afesp;
+
+extern "C" {   // (the names these kernels have in profiles: plain, as the entry points' own)
+// ---- a quarter transform on the LDS-DMA GEMM (tgemm.h): out(x2, m, S) = sum_x1 C(m, x1) in(x1, x2, S)
+// The transformed index is the fastest one of `in`, so every column (x2, S) of the product is a contiguous run of n doubles: both
+// operands are contiguous along the summation index (C goes in as a zero-padded transpose), which is all that kernel asks for.
+// The result comes out with x2 fastest and the new index second -- the layout the NEXT quarter transform wants for its input
+// (and the one the old path produced after two of them: (p,q,K), (r,s,P)).  Needs an even n (16-byte chunks, pairs of columns).
+__global__ __launch_bounds__(256) void ao2mo_ct_kernel(double* ct, const double* c, int n, int Kc)
+{
+    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < n * Kc; x += gridDim.x * blockDim.x) {
+        const int m = x / Kc, k = x % Kc;
+        ct[x] = k < n ? c[m + n * k] : 0.0;
+    }
+}
+// rowA[m] = byte offset of row m of the padded transpose; colB[c] = byte offset of column c = x2 + n Sloc of a slab of `in`;
+// offCm[m] = ld m; offCn[c] = x2 + ld n Sloc (elements); the pads behind them (tgemm.h) are zero.
+// ld: the temporaries' columns are ld doubles long (n of them data, the rest zero): ld = Kc puts every column on a 128-byte line
+__global__ __launch_bounds__(256) void ao2mo_tables_kernel(uint32_t* rowA, uint32_t* colB, int64_t* offCm, int64_t* offCn, int n, int Kc, int64_t ncol, int64_t ld)
+{
+    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < ncol + 256; x += (int64_t)gridDim.x * blockDim.x) {
+        if (x < n + 256) rowA[x] = x < n ? (uint32_t)(8 * Kc * x) : 0u;
+        if (x < n + 128) offCm[x] = x < n ? ld * x : 0;
+        colB[x] = x < ncol ? (uint32_t)(8 * ld * x) : 0u;
+        if (x < ncol + 128) offCn[x] = x < ncol ? (x % n) + ld * n * (x / n) : 0;
+    }
+}
+
+// The second pair of transforms is only needed where the packed result has an entry: (rs|PQ) for RS <= PQ, i.e. r <= p(PQ).  The
+// last transform therefore runs over the columns (r, PQ) with r <= p only -- p + 1 of them per pair PQ = tri(p, q), rounded up to
+// an even count (pairs of columns are stored together) -- about half of all: colB / offCn list them pair by pair, relative to
+// the pair's slab (cstart[PQ] = first column of the pair).
+__global__ __launch_bounds__(256) void ao2mo_tables_tri_kernel(uint32_t* colB, int64_t* offCn, const int64_t* cstart, int n, int64_t np, int64_t sl, int64_t ld)
+{
+    for (int64_t P = blockIdx.x; P < np; P += gridDim.x) {
+        const int64_t c0 = cstart[P], cnt = cstart[P + 1] - c0, rel = P % sl;
+        for (int64_t r = threadIdx.x; r < cnt; r += blockDim.x) {
+            colB[c0 + r] = (uint32_t)(8 * ld * (r + (int64_t)n * rel));
+            offCn[c0 + r] = r + ld * n * rel;
+        }
+    }
+}
+
+// columns (x2, S) with x2 < TG_BM only (the pair transposition behind the second transform reads its result (x2, m, S) for
+// x2 <= m only: the rows m < 128 are needed for these columns only), relative to a slab: column c = x2 + 128 Sloc
+__global__ __launch_bounds__(256) void ao2mo_tables_lo_kernel(uint32_t* colB, int64_t* offCn, int n, int cnt, int64_t ncol, int64_t ld)
+{
+    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < ncol + 256; x += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t x2 = x % cnt, sloc = x / cnt;
+        colB[x] = x < ncol ? (uint32_t)(8 * ld * (x2 + (int64_t)n * sloc)) : 0u;
+        if (x < ncol + 128) offCn[x] = x < ncol ? x2 + ld * n * sloc : 0;
+    }
+}
+}  // extern "C"
+
+namespace {
+struct Ao2moTg {
+    int64_t n = 0, Kc = 0, sl = 0;   // basis size, padded summation length, (S) pairs per slab (one TgGroup each)
+    int64_t ld = 0;                  // leading dimension of the temporaries: Kc (ao2mo_ld), or n
+    double* ct = nullptr;
+    uint32_t *rowA = nullptr, *colB = nullptr;
+    int64_t *offCm = nullptr, *offCn = nullptr;
+    TgGroup* groups = nullptr;       // room for the descriptors of every transform of one call (no host synchronisation between them)
+    int64_t groups_cap = 0, groups_used = 0;
+    std::vector<std::vector<TgGroup>> host;   // ... whose host copies live until the call's final synchronisation
+    // columns (r, PQ), r <= p(PQ) only (ao2mo_tables_tri_kernel)
+    uint32_t* colB_tri = nullptr;
+    int64_t* offCn_tri = nullptr;
+    std::vector<int64_t> cstart;     // [np + 1], host copy
+    int64_t p_split = 0;             // first pair PQ with p >= TG_BM (the pairs below it need the first 128 rows only)
+    uint32_t* colB_lo = nullptr;     // columns x2 < TG_BM (ao2mo_tables_lo_kernel)
+    int64_t* offCn_lo = nullptr;
+};
+
+// tables and the padded transpose of the coefficient matrix for basis size n (cached scratch: rebuilt per call, microseconds)
+static Ao2moTg ao2mo_tg_prepare(Context& cx, const double* Cm, int64_t n, int64_t np, int64_t ld)
+{
+    Ao2moTg t;
+    t.n = n;
+    t.ld = ld;
+    t.Kc = (n + 15) / 16 * 16;
+    // a slab's columns are addressed with 32-bit byte offsets: n * sl columns of n doubles each below 4 GiB
+    t.sl = std::min<int64_t>(np, std::min<int64_t>(8192, (((int64_t)1 << 32) - 4096) / (8 * t.ld * n)));
+    const int64_t ncol = n * t.sl;
+    t.ct = cx.scratch("ao2mo_ct", n * t.Kc);
+    t.rowA = (uint32_t*)cx.scratch("ao2mo_t32", (n + 256 + ncol + 256) / 2 + 2);
+    t.colB = t.rowA + n + 256;
+    t.offCm = (int64_t*)cx.scratch("ao2mo_t64", n + 128 + ncol + 128 + 2);
+    t.offCn = t.offCm + n + 128;
+    AFESP_KLAUNCH(ao2mo_ct_kernel, dim3((unsigned)((n * t.Kc + 255) / 256)), dim3(256), 0, cx.stream, t.ct, Cm, (int)n, (int)t.Kc);
+    AFESP_HIP(hipGetLastError());
+    AFESP_KLAUNCH(ao2mo_tables_kernel, dim3((unsigned)std::min<int64_t>((ncol + 256 + 255) / 256, 65536)), dim3(256), 0, cx.stream, t.rowA,
+                       t.colB, t.offCm, t.offCn, (int)n, (int)t.Kc, ncol, t.ld);
+    AFESP_HIP(hipGetLastError());
+    const int64_t ng = (np + t.sl - 1) / t.sl;
+    t.groups_cap = 8 * (ng + 2);
+    t.groups = (TgGroup*)cx.scratch("ao2mo_tg", (int64_t)(t.groups_cap * sizeof(TgGroup) / sizeof(double) + 1));
+    // the triangular column list of the last transform
+    t.cstart.assign((size_t)np + 1, 0);
+    for (int64_t pp = 0, P = 0; pp < n; ++pp)
+        for (int64_t q = 0; q <= pp; ++q, ++P) t.cstart[(size_t)P + 1] = t.cstart[(size_t)P] + ((pp + 2) & ~(int64_t)1);
+    t.p_split = std::min<int64_t>(np, (int64_t)TG_BM * (TG_BM + 1) / 2);
+    const int64_t ctot = t.cstart[(size_t)np];
+    t.colB_tri = (uint32_t*)cx.scratch("ao2mo_t32t", (ctot + 256) / 2 + 2);
+    t.offCn_tri = (int64_t*)cx.scratch("ao2mo_t64t", ctot + 128 + 2);
+    int64_t* cs_dev = (int64_t*)cx.scratch("ao2mo_cs", np + 2);
+    AFESP_HIP(hipMemcpyAsync(cs_dev, t.cstart.data(), (size_t)(np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemsetAsync(t.colB_tri + ctot, 0, 256 * sizeof(uint32_t), cx.stream));
+    AFESP_HIP(hipMemsetAsync(t.offCn_tri + ctot, 0, 128 * sizeof(int64_t), cx.stream));
+    AFESP_KLAUNCH(ao2mo_tables_tri_kernel, dim3((unsigned)std::min<int64_t>(np, 65536)), dim3(256), 0, cx.stream, t.colB_tri, t.offCn_tri,
+                       cs_dev, (int)n, np, t.sl, t.ld);
+    AFESP_HIP(hipGetLastError());
+    if (n > TG_BM) {
+        const int64_t nlo = (int64_t)TG_BM * t.sl;
+        t.colB_lo = (uint32_t*)cx.scratch("ao2mo_t32h", (nlo + 256) / 2 + 2);
+        t.offCn_lo = (int64_t*)cx.scratch("ao2mo_t64h", nlo + 128 + 2);
+        AFESP_KLAUNCH(ao2mo_tables_lo_kernel, dim3((unsigned)std::min<int64_t>((nlo + 256 + 255) / 256, 65536)), dim3(256), 0, cx.stream,
+                           t.colB_lo, t.offCn_lo, (int)n, (int)TG_BM, nlo, t.ld);
+        AFESP_HIP(hipGetLastError());
+    }
+    return t;
+}
+
+// one quarter transform over the pairs S in [s_begin, s_end) of `in` (n x n x np), rows row0 <= m < row0 + M of the result only;
+// cols: 0 every column (x2, S), 1 only x2 <= p(S), 2 only x2 < 128 (the rest of `out` is left untouched)
+static void ao2mo_tg_xform(Context& cx, Ao2moTg& t, const double* in, double* out, int64_t s_begin, int64_t s_end, int64_t M, int cols,
+                    int64_t row0 = 0)
+{
+    if (s_end <= s_begin || M <= 0) return;
+    const bool tri = cols == 1, lo = cols == 2;
+    const int64_t nlo = TG_BM;
+    const int64_t n = t.n, g_lo = s_begin / t.sl, g_hi = (s_end - 1) / t.sl;
+    const int mt = (int)((M + TG_BM - 1) / TG_BM);
+    t.host.emplace_back();
+    std::vector<TgGroup>& hv = t.host.back();
+    int mx = 0, tile = 0;
+    auto ncols = [&](int64_t s0, int64_t s1) { return tri ? t.cstart[(size_t)s1] - t.cstart[(size_t)s0] : (lo ? nlo : n) * (s1 - s0); };
+    for (int64_t g = g_lo; g <= g_hi; ++g) {
+        const int64_t s0 = std::max(s_begin, g * t.sl), s1 = std::min(s_end, (g + 1) * t.sl);
+        mx = std::max(mx, (int)((ncols(s0, s1) + TG_BN - 1) / TG_BN));
+    }
+    const int gm = tgemm_group_m((int)M, mx);
+    for (int64_t g = g_lo; g <= g_hi; ++g) {
+        const int64_t s0 = std::max(s_begin, g * t.sl), s1 = std::min(s_end, (g + 1) * t.sl);
+        TgGroup d{};
+        d.a1 = d.a2 = 0;
+        d.b1 = d.b2 = t.ld * n * g * t.sl;       // (the tables are relative to the slab's first pair; columns are ld doubles long)
+        d.c0 = t.ld * n * g * t.sl;
+        d.colB = tri ? t.colB_tri + t.cstart[(size_t)s0] : lo ? t.colB_lo + nlo * (s0 - g * t.sl) : t.colB + n * (s0 - g * t.sl);
+        d.offCn = tri ? t.offCn_tri + t.cstart[(size_t)s0] : lo ? t.offCn_lo + nlo * (s0 - g * t.sl) : t.offCn + n * (s0 - g * t.sl);
+        d.N = (int)ncols(s0, s1);
+        d.ntiles = (d.N + TG_BN - 1) / TG_BN;
+        d.tile_start = tile;
+        d.nk1 = d.nk = (int)(t.Kc / TG_BK);
+        d.inv_width = tgemm_inverse(gm * d.ntiles);
+        if ((int64_t)mt * d.ntiles * gm * d.ntiles >= ((int64_t)1 << 32)) throw Error(2, "ao2mo: tile walk out of range");
+        tile += mt * d.ntiles;
+        hv.push_back(d);
+    }
+    TgGroup end{};
+    end.tile_start = tile;
+    hv.push_back(end);
+    const int ng = (int)hv.size() - 1;
+    if (t.groups_used + (int64_t)hv.size() > t.groups_cap) throw Error(2, "ao2mo: descriptor buffer too small");
+    TgGroup* dev = t.groups + t.groups_used;
+    t.groups_used += (int64_t)hv.size();
+    AFESP_HIP(hipMemcpyAsync(dev, hv.data(), hv.size() * sizeof(TgGroup), hipMemcpyHostToDevice, cx.stream));
+    TgProblem p{t.ct, in, out, t.rowA + row0, t.offCm + row0, (int)M, true, (int)((n - (t.Kc - TG_BK) + 3) / 4)};
+    p.tag = 2;
+    // (rows that end at most 96 past a multiple of 128 -- n = 220: 92 -- take a 96-row last tile: three quarters of its MFMAs, tgemm.h)
+    const int bm = (knobs().ao2mo_mixed && M % TG_BM != 0 && M % TG_BM <= 96) ? TG_BM : 0;
+    AFESP_HIP(tgemm_launch(p, dev, ng, tile, mx, cx.stream, cx.tg, bm));
+}
+// MP2 energy on the <ij|ab> slice of packed MO integrals over o + v orbitals (mp2.f90:418-440); levels: their o + v orbital energies (host)
+double mp2_of_packed(Context& cx, const double* packed, const double* levels, int64_t o, int64_t v)
+{
+    const int64_t n = o + v;
+    // small systems: one launch, straight from the packed array (the slice and the denominators are formed on the fly)
+    // (AFESP_MP2_PACKED=0: the five-launch form at every size, A/B runs)
+    if (o * o * v * v <= ((int64_t)1 << 22) && knobs().mp2_packed) return k_mp2_packed(cx, packed, levels, (int)o, (int)v);
+    double* e_dev = cx.scratch("ao2mo_e", n);
+    AFESP_HIP(hipMemcpyAsync(e_dev, levels, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    Tensor voovv = view(cx.scratch("ao2mo_v", o * o * v * v), {o, o, v, v}), D1 = view(cx.scratch("ao2mo_d1", o * v), {o, v}),
+           D2 = view(cx.scratch("ao2mo_d2", o * o * v * v), {o, o, v, v});
+    k_slice_phys(cx, voovv.d, packed, (int)o, (int)o, (int)v, (int)v, 0, 0, (int)o, (int)o);
+    k_denominators(cx, D1.d, D2.d, e_dev, (int)o, (int)v);
+    k_mp2_energy(cx, cx.scal, voovv.d, D2.d, (int)o, (int)v);
+    return host_scalars(cx, 1)[0];
+}
+
+// ---- the steps of a transform (src/mp2.f90:261-449), each written once.  Four quarter transforms as MFMA GEMMs; each pass contracts the
+// leading AO index with C(MO,AO) and the planner writes the result with the new MO index in place: (ij|K) in a -> (pq|K) in a, by way of b
+void first_pair(Context& cx, const Tensor& C, const Tensor& a, const Tensor& b)
+{
+    contract(cx, 1.0, C, "pi", a, "ijK", 0.0, b, "pjK");   // mp2.f90:321-333
+    contract(cx, 1.0, C, "qj", b, "pjK", 0.0, a, "pqK");   // mp2.f90:338-348
+}
+// gather-GEMM, second pair: (kl|P) in `in` -> (rs|P) in `out`, by way of tmp
+void second_pair(Context& cx, const Tensor& C, const Tensor& in, const Tensor& tmp, const Tensor& out)
+{
+    contract(cx, 1.0, C, "rk", in, "klP", 0.0, tmp, "rlP");    // mp2.f90:357-367
+    contract(cx, 1.0, C, "sl", tmp, "rlP", 0.0, out, "rsP");   // mp2.f90:375-385
+}
+// pair kernels (both quarter transforms of a pair index in one kernel with the n x n block resident in LDS), first pair: straight from the
+// packed AO integrals to pair columns, one transposition -- g(K, PQ) in a (a / b hold the two npair^2 matrices, no squared-up copy)
+void pair_half(Context& cx, const double* ao, const Tensor& C, const Tensor& a, const Tensor& b)
+{
+    const int64_t n = C.dim[0], np = npair_of(n);
+    k_pair_xform(cx, b.d, ao, C.d, (int)n, np, 1);   // (ij|K) -> g(PQ, K)       mp2.f90:321-348
+    k_square_transpose(cx, a.d, b.d, np);            // g(K, PQ)
+}
+
+// Small bases: the whole tensor at once.  The two temporaries are cached scratch: a second transform in the same context reuses them,
+// the next afesp_ccsd_init / afesp_ccsd_so_init gives them back.
+void transform_dense(Context& cx, Integrals& in, const Ao2moForm& form, double* packed, const double* ao, const Tensor& Cm, bool have_u)
+{
+    const int64_t n = Cm.dim[0], np = npair_of(n), L = form.ld;
+    Tensor Ta = view(cx.scratch("ao2mo_a", Integrals::temp_size(n, L)), {n, n, np}),
+           Tb = view(cx.scratch("ao2mo_b", Integrals::temp_size(n, L)), {n, n, np});
+    if (!have_u && !form.pair) k_unpack_half(cx, Ta.d, ao, (int)n, 0, -1, (int)L);   // (ij|KL), ij squared up
+    in.half_overwritten();
+    if (form.use_tg) {
+        AFESP_HIP(hipMemsetAsync(Ta.d + L * n * np, 0, 16 * sizeof(double), cx.stream));
+        AFESP_HIP(hipMemsetAsync(Tb.d + L * n * np, 0, 16 * sizeof(double), cx.stream));
+        in.zero_padding(cx, Ta.d, Tb.d, n, L);
+        Ao2moTg tg = ao2mo_tg_prepare(cx, Cm.d, n, np, L);
+        ao2mo_tg_xform(cx, tg, Ta.d, Tb.d, 0, np, n, 0);         // (ij|K) -> (j p|K)        mp2.f90:321-333
+        // (jp|K) -> (x2 m|K), mp2.f90:338-348: the transposition below reads x2 <= m only -- the rows m < 128 are computed
+        // for the columns x2 < 128 only
+        if (n > TG_BM) {
+            ao2mo_tg_xform(cx, tg, Tb.d, Ta.d, 0, np, n - TG_BM, 0, TG_BM);
+            ao2mo_tg_xform(cx, tg, Tb.d, Ta.d, 0, np, TG_BM, 2);
+        } else {
+            ao2mo_tg_xform(cx, tg, Tb.d, Ta.d, 0, np, n, 0);
+        }
+        k_pair_transpose(cx, Tb.d, Ta.d, (int)n, (int)L);       // (kl|PQ), kl squared up, p >= q
+        // Second pair: only (rs|PQ) with RS <= PQ is packed (mp2.f90:388-410), i.e. r <= p and s <= r.  Rows beyond the
+        // first 128 are therefore skipped for the pairs with p < 128, and the last transform runs over the columns
+        // (r, PQ) with r <= p only -- 2.6 n^5 flop in 128-row tiles instead of 4 (the reference: 8).
+        const int64_t ps = tg.p_split, m_lo = std::min<int64_t>(n, TG_BM);
+        ao2mo_tg_xform(cx, tg, Tb.d, Ta.d, 0, ps, m_lo, 0);      // (kl|P) -> (l r|P)        mp2.f90:357-367
+        ao2mo_tg_xform(cx, tg, Tb.d, Ta.d, ps, np, n, 0);
+        ao2mo_tg_xform(cx, tg, Ta.d, Tb.d, 0, ps, m_lo, 1);      // (lr|P) -> (r s|P)        mp2.f90:375-385
+        ao2mo_tg_xform(cx, tg, Ta.d, Tb.d, ps, np, n, 1);
+        k_pack_pairs(cx, packed, Tb.d, (int)n, 0, -1, (int)L);   // mp2.f90:388-410
+        cx.sync();                                               // (the descriptors' host copies die with tg)
+        return;
+    }
+    in.padding_overwritten();
+    if (form.pair) {   // every bundled input, the H2O/cc-pVTZ shape: three launches
+        pair_half(cx, ao, Cm, Ta, Tb);
+        k_pair_xform(cx, packed, Ta.d, Cm.d, (int)n, np, 2);   // (kl|P) -> (rs|P), RS <= P  mp2.f90:357-410
+    } else {
+        first_pair(cx, Cm, Ta, Tb);
+        k_pair_transpose(cx, Tb.d, Ta.d, (int)n);   // (kl|PQ), kl squared up, p >= q
+        second_pair(cx, Cm, Tb, Ta, Tb);
+        k_pack_pairs(cx, packed, Tb.d, (int)n);     // mp2.f90:388-410
+    }
+}
+
+// Large bases: slab by slab.  The first pair of transforms acts on every (kl) pair separately and the second on every (pq) pair, so only
+// the half-transformed integrals have to exist as a whole -- pair-packed, g(PQ,K), np^2 doubles (4.7 GB at n = 220) -- and the n^2 npair
+// temporaries (2 x 9.4 GB) shrink to two slabs of S pairs.  S is chosen so that a slab's column tiles fill whole rounds of the persistent
+// GEMM grid.  From temporaries of 16 GiB each (n >= 256): at n = 220 this form is 5 % slower (58.9 against 55.8 ms: one more pass over
+// the half-transformed integrals) for 12.5 GB less -- it is there for the sizes where 2 n^2 npair doubles no longer fit beside the rest
+// (n = 400: 2 x 103 GB)
+void transform_blocked(Context& cx, Integrals& in, double* packed, const double* ao, const Tensor& Cm, bool have_u)
+{
+    const int64_t n = Cm.dim[0], np = npair_of(n);
+    in.padding_overwritten();
+    int64_t S = std::max<int64_t>(16, ((int64_t)256 * 128 * 14 / n) / 16 * 16);
+    if (S > np) S = (np + 15) / 16 * 16;
+    double* g = cx.scratch("ao2mo_g", np * np);
+    double* sa = have_u ? nullptr : cx.scratch("ao2mo_a", n * n * S);   // (with (ij|KL) left by the Fock build: its slabs, in place)
+    double* sb = cx.scratch("ao2mo_b", n * n * S);
+    double* u = have_u ? cx.scratch("ao2mo_a", n * n * np) : nullptr;
+    in.half_overwritten();
+    for (int64_t k0 = 0; k0 < np; k0 += S) {
+        const int64_t k1 = std::min(np, k0 + S), len = k1 - k0;
+        double* a_s = have_u ? u + n * n * k0 : sa;
+        if (!have_u) k_unpack_half(cx, a_s, ao, (int)n, k0, k1);   // (ij|K), ij squared up, K in the slab
+        first_pair(cx, Cm, view(a_s, {n, n, len}), view(sb, {n, n, len}));
+        k_tri_pack(cx, g, a_s, (int)n, k0, k1);                    // g(PQ,K), p >= q
+    }
+    if (have_u) sa = u;   // (dead now: its first slab serves the second pair)
+    for (int64_t p0 = 0; p0 < np; p0 += S) {
+        const int64_t p1 = std::min(np, p0 + S), len = p1 - p0;
+        k_pair_square_packed(cx, sb, g, (int)n, p0, p1);           // (kl|P), kl squared up, P in the slab
+        Tensor Ta = view(sa, {n, n, len}), Tb = view(sb, {n, n, len});
+        second_pair(cx, Cm, Tb, Ta, Tb);
+        k_pack_pairs(cx, packed, sb, (int)n, p0, p1);              // mp2.f90:388-410
+    }
+}
+
+// read_integrals_in, two-body part (src/integrals.f90:146-161): lines "i j a b value", 1-based, any blank separation, in
+// any order; a later line for the same packed slot overwrites an earlier one; slots never mentioned stay 0.
+int64_t parse_eri_text(FILE* f, int64_t nbasis, std::vector<double>& host)
+{
+    std::vector<char> buf((size_t)(8 << 20) + 1);
+    size_t keep = 0;
+    int64_t lines = 0;
+    auto tri = [](int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; };
+    for (;;) {
+        const size_t got = fread(buf.data() + keep, 1, buf.size() - 1 - keep, f);
+        const size_t have = keep + got;
+        if (have == 0) break;
+        buf[have] = 0;
+        // parse whole lines only; the tail (an incomplete line) is carried into the next block
+        size_t end = have;
+        if (got > 0) {
+            while (end > 0 && buf[end - 1] != '\n') --end;
+            if (end == 0 && have == buf.size() - 1) return -1;   // a "line" longer than the buffer
+        }
+        const size_t stop = got > 0 ? end : have;
+        char* p = buf.data();
+        char* const lim = buf.data() + stop;
+        const char saved = *lim;
+        *lim = 0;
+        while (p < lim) {
+            while (p < lim && (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n')) ++p;
+            if (p >= lim) break;
+            // list-directed input (src/integrals.f90:150 `read (ir, *) i, j, a, b, val`): fields are separated by blanks
+            // and/or one comma, a real may carry a Fortran D exponent ("1.0D-05"); whatever follows the fifth field on
+            // the record is ignored, as the reference's read does
+            auto sep = [&](char*& c) {
+                while (c < lim && (*c == ' ' || *c == '\t' || *c == '\r')) ++c;
+                if (c < lim && *c == ',') ++c;
+                while (c < lim && (*c == ' ' || *c == '\t' || *c == '\r')) ++c;
+            };
+            char* q;
+            long idx[4];
+            bool ok = true;
+            for (int k = 0; k < 4 && ok; ++k) {
+                if (*p == '\n') { ok = false; break; }
+                idx[k] = strtol(p, &q, 10);
+                ok = (q != p) && (q >= lim || *q == ' ' || *q == '\t' || *q == ',' || *q == '\r') && idx[k] >= 1 && idx[k] <= nbasis;
+                p = q;
+                if (ok) sep(p);
+            }
+            if (!ok || *p == '\n') return -1;
+            char tok[64];
+            size_t len = 0;
+            while (p + len < lim && len < sizeof(tok) - 1 && p[len] != ' ' && p[len] != '\t' && p[len] != ',' && p[len] != '\r' &&
+                   p[len] != '\n') {
+                const char ch = p[len];
+                tok[len] = (ch == 'D' || ch == 'd') ? 'E' : ch;
+                ++len;
+            }
+            tok[len] = 0;
+            char* tq = nullptr;
+            const double val = strtod(tok, &tq);
+            if (len == 0 || tq != tok + len) return -1;   // the whole token is the number
+            p += len;
+            host[(size_t)tri(tri(idx[0] - 1, idx[1] - 1), tri(idx[2] - 1, idx[3] - 1))] = val;
+            ++lines;
+            while (p < lim && *p != '\n') ++p;   // ignore anything else on the line
+        }
+        *lim = saved;
+        if (got == 0) break;
+        keep = have - stop;
+        memmove(buf.data(), buf.data() + stop, keep);
+    }
+    return lines;
+}
+
+}  // namespace
+
+namespace afesp {
+
+Ao2moForm::Ao2moForm(int64_t n, bool open_shell)
+{
+    const Knobs& k = knobs();
+    blocked = k.ao2mo_blocked >= 0 ? k.ao2mo_blocked == 1 : n * n * npair_of(n) >= ((int64_t)1 << 31);
+    use_tg = !open_shell && !blocked && n % 2 == 0 && n >= 16 && (k.ao2mo_tg >= 0 ? k.ao2mo_tg == 1 : n >= 96);
+    pair = !blocked && !use_tg && n <= 64 && (open_shell || k.ao2mo_pair);
+    ld = use_tg && k.ao2mo_pad ? (n + 15) / 16 * 16 : n;
+}
+
+double* Integrals::adopt_ao(Context& cx, int64_t n)
+{
+    if (ao) cx.release(ao);
+    ao = nullptr;
+    half_n = 0;
+    ao = cx.alloc(neri_of(n));
+    ao_n = n;
+    return ao;
+}
+
+void Integrals::upload_ao(Context& cx, int64_t n, const double* host)
+{
+    AFESP_HIP(hipMemcpyAsync(adopt_ao(cx, n), host, sizeof(double) * neri_of(n), hipMemcpyHostToDevice, cx.stream));
+    cx.sync();
+}
+
+const double* Integrals::half_unpacked(Context& cx, int64_t n, int64_t& ld)
+{
+    ld = Ao2moForm(n).ld;
+    double* u = cx.scratch("ao2mo_a", temp_size(n, ld));
+    if (!half_valid(cx, n, ld)) {
+        if (pad_n != n || pad_ld != ld) pad_n = 0;   // (another layout lands in the buffer the transforms share)
+        k_unpack_half(cx, u, ao, (int)n, 0, -1, (int)ld);
+        half_n = n; half_ld = ld; half_epoch = cx.scratch_epoch;
+    }
+    return u;
+}
+
+// (rows n .. ld - 1 of every column are K padding of the products -- read, times the zero padding of C: finite, so zero.  No kernel of
+// the LDS-DMA form or of the Fock builds writes them, so they are zeroed once per (buffers, n, ld): 0.2 ms each)
+void Integrals::zero_padding(Context& cx, double* a, double* b, int64_t n, int64_t ld)
+{
+    if (pad_a == a && pad_b == b && pad_n == n && pad_ld == ld && pad_epoch == cx.scratch_epoch) return;
+    k_pad_rows_zero(cx, a, (int)n, (int)ld, n * npair_of(n));
+    k_pad_rows_zero(cx, b, (int)n, (int)ld, n * npair_of(n));
+    pad_a = a; pad_b = b; pad_n = n; pad_ld = ld; pad_epoch = cx.scratch_epoch;
+}
+
+void Integrals::release_uhf(Context& cx)
+{
+    cx.release(uhf_aa); cx.release(uhf_bb); cx.release(uhf_ab);
+    uhf_aa = uhf_bb = uhf_ab = nullptr;
+    uhf_n = 0;
+}
+
+void Integrals::adopt_uhf(Context& cx, int64_t n)
+{
+    if (uhf_n == n && uhf_aa) return;
+    release_uhf(cx);
+    uhf_aa = cx.alloc_raw(neri_of(n));
+    uhf_bb = cx.alloc_raw(neri_of(n));
+    uhf_ab = cx.alloc_raw(npair_of(n) * npair_of(n));
+    uhf_n = n;
+}
+
+// the orbitals [lo, lo + n_act) of the three blocks: block by block, each full block back to the arena before the next window is asked for
+void Integrals::window_uhf(Context& cx, int64_t n_act, int64_t lo)
+{
+    const int64_t n = uhf_n, nea = neri_of(n_act), npa = npair_of(n_act);
+    for (double** blk : {&uhf_aa, &uhf_bb, &uhf_ab}) {
+        double* w = cx.alloc_raw(blk == &uhf_ab ? npa * npa : nea);
+        if (blk == &uhf_ab) k_window_pairs(cx, w, uhf_ab, (int)n_act, (int)n, (int)lo);
+        else k_window_pack(cx, w, *blk, (int)n_act, (int)lo);
+        cx.release(*blk);
+        *blk = w;
+        uhf_n = 0;   // (from here on the blocks are of mixed extents until all three are done)
+    }
+    uhf_n = n_act;
+}
+
+void Integrals::drop_mo(Context& cx, CCState& cc)
+{
+    if (cc.eri_src == mo) cc.eri_src = nullptr;
+    if (mo) cx.release(mo);
+    set_mo(nullptr, 0);
+}
+
+double* Integrals::replace_mo(Context& cx, CCState& cc, int64_t n)
+{
+    if (mo && mo_n == n) {   // a transform of the same basis size overwrites the previous result
+        if (cc.eri_src == mo) cc.eri_src = nullptr;
+        return mo;
+    }
+    drop_mo(cx, cc);
+    return cx.alloc_raw(neri_of(n));
+}
+
+double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, const double* coeff, const double* levels,
+                 const double* eri_packed, double* eri_mo_packed)
+{
+    const int64_t ne = neri_of(n);
+    if (!eri_packed && (!in.ao || in.ao_n != n))
+        throw Error(1, "afesp_ao2mo_mp2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
+    cx.drop_scratch("t_");   // the (T) pool of a previous system holds the blocks the two temporaries below were
+    in.release_uhf(cx);      // an RHF transform ends the open-shell calculation: its integral blocks go back to the arena
+    double* packed = in.replace_mo(cx, cc, n);
+    const double* ao = in.ao;   // NULL source: transformed where afesp_read_eri_text / afesp_set_eri left them
+    if (eri_packed) {           // upload buffer, then the packed MO integrals
+        AFESP_HIP(hipMemcpyAsync(packed, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+        ao = packed;
+    }
+    Tensor Cm = view(cx.scratch("ao2mo_c", n * n), {n, n});
+    AFESP_HIP(hipMemcpyAsync(Cm.d, coeff, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    // Pair symmetry: (ij|kl) is transformed for the n(n+1)/2 pairs k >= l only, the half-transformed (pq|kl) kept for
+    // p >= q only -- 4 n^5 flop and two buffers of n^2 x npair instead of 8 n^5 and two of n^4.
+    const Ao2moForm form(n);
+    const bool have_u = ao == in.ao && in.half_valid(cx, n, form.ld);   // a Fock build left (ij|KL)
+    if (form.blocked) transform_blocked(cx, in, packed, ao, Cm, have_u);
+    else transform_dense(cx, in, form, packed, ao, Cm, have_u);
+    in.set_mo(packed, n);
+    const double emp2 = mp2_of_packed(cx, packed, levels, o, n - o);
+    if (eri_mo_packed) {
+        AFESP_HIP(hipMemcpyAsync(eri_mo_packed, packed, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    }
+    return emp2;
+}
+
+// (aa|aa), (bb|bb) and (aa|bb) from one set of AO integrals: the first pair of quarter transforms with C_a is shared by the first and
+// the third block, the second pair runs with C_a (packed, RS <= PQ) and with C_b (every RS: no 8-fold symmetry is left), then the whole
+// transform once more with C_b.
+double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
+                  const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab, double* eri_bb)
+{
+    const Ao2moForm form(n, true);
+    if (form.blocked)
+        throw Error(1, "afesp_ao2mo_ump2: basis too large (only the slab-blocked transform fits, and it has no open-shell form)");
+    if (!eri_packed && (!in.ao || in.ao_n != n))
+        throw Error(1, "afesp_ao2mo_ump2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
+    cx.drop_scratch("t_");
+    cx.drop_scratch("ao2mo_");   // (the temporaries are sized below; what they held goes back to the arena)
+    const int64_t ne = neri_of(n), np = npair_of(n);
+    // device memory: the temporaries (two npair^2 for the pair form, three n^2 npair for the gather-GEMM form) and, for a new
+    // basis size, the three result blocks, against what the device has free plus what the context's arena holds idle
+    const double tmp = form.pair ? 2.0 * np * np : 3.0 * n * n * np;
+    const double blocks = (in.uhf_n == n && in.uhf_aa) ? 0.0 : 2.0 * ne + (double)np * np;
+    if (in.uhf_n != n) in.release_uhf(cx);   // (blocks of another basis size: returned before their successors are sized)
+    size_t free_b = 0, total_b = 0;
+    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (8.0 * (tmp + blocks + 4.0 * n * n) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+        throw Error(1, "afesp_ao2mo_ump2: the open-shell transform of this basis does not fit the free device memory");
+    in.adopt_uhf(cx, n);
+    double *aa = in.uhf_aa, *bb = in.uhf_bb, *ab = in.uhf_ab;
+    const double* ao = in.ao;
+    if (eri_packed) {   // (into the beta-beta block: every read of the AO integrals precedes its one write)
+        AFESP_HIP(hipMemcpyAsync(bb, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+        ao = bb;
+    }
+    Tensor Ca = view(cx.scratch("ao2mo_c", n * n), {n, n}), Cb = view(cx.scratch("ao2mo_cb", n * n), {n, n});
+    AFESP_HIP(hipMemcpyAsync(Ca.d, coeff_a, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(Cb.d, coeff_b, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    // the temporaries are the RHF transform's (dense columns of n): whatever the Fock build or an LDS-DMA transform left there is gone
+    in.half_overwritten();
+    in.padding_overwritten();
+    Tensor Ta = view(cx.scratch("ao2mo_a", Integrals::temp_size(n, form.ld)), {n, n, np}),
+           Tb = view(cx.scratch("ao2mo_b", Integrals::temp_size(n, form.ld)), {n, n, np});
+    if (form.pair) {
+        pair_half(cx, ao, Ca, Ta, Tb);                          // g(K, PQ), C_a
+        k_pair_xform(cx, aa, Ta.d, Ca.d, (int)n, np, 2);        // (rs|PQ), RS <= PQ, C_a
+        k_pair_xform(cx, ab, Ta.d, Cb.d, (int)n, np, 3);        // (rs|PQ), every RS, C_b
+        pair_half(cx, ao, Cb, Ta, Tb);                          // and the beta-beta block
+        k_pair_xform(cx, bb, Ta.d, Cb.d, (int)n, np, 2);
+    } else {
+        Tensor Tc = view(cx.scratch("ao2mo_c3", n * n * np), {n, n, np});
+        k_unpack_half(cx, Ta.d, ao, (int)n);
+        first_pair(cx, Ca, Ta, Tb);
+        k_pair_transpose(cx, Tb.d, Ta.d, (int)n);                // (kl|PQ), alpha PQ
+        second_pair(cx, Ca, Tb, Ta, Tc);
+        k_pack_pairs(cx, aa, Tc.d, (int)n);
+        second_pair(cx, Cb, Tb, Ta, Tc);
+        k_pack_cols(cx, ab, Tc.d, (int)n);
+        k_unpack_half(cx, Ta.d, ao, (int)n);
+        first_pair(cx, Cb, Ta, Tb);
+        k_pair_transpose(cx, Tb.d, Ta.d, (int)n);
+        second_pair(cx, Cb, Tb, Ta, Tc);
+        k_pack_pairs(cx, bb, Tc.d, (int)n);
+    }
+    return ump2_of_blocks(cx, in, levels_a, levels_b, na, nb, eri_aa, eri_ab, eri_bb);
+}
+
+// E(UMP2) of the three resident blocks (levels on the host, for their basis size) and the blocks themselves for whoever asks
+double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, const double* levels_b, int64_t oa, int64_t ob, double* eri_aa,
+                      double* eri_ab, double* eri_bb)
+{
+    const int64_t n = in.uhf_n, ne = neri_of(n), np = npair_of(n);
+    double* ea = cx.scratch("ao2mo_ea", 2 * n);
+    AFESP_HIP(hipMemcpyAsync(ea, levels_a, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(ea + n, levels_b, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    const double e2 = k_ump2(cx, in.uhf_aa, in.uhf_bb, in.uhf_ab, ea, ea + n, (int)n, (int)oa, (int)ob);
+    if (eri_aa) AFESP_HIP(hipMemcpyAsync(eri_aa, in.uhf_aa, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (eri_bb) AFESP_HIP(hipMemcpyAsync(eri_bb, in.uhf_bb, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, in.uhf_ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    return e2;
+}
+
+// The active orbital window [nfc, n - nfv) of the resident (or handed-in) packed MO integrals: a gather after the full transform
+// (DESIGN.md), left resident as afesp_ao2mo_mp2 leaves a basis of n_act functions; the full array goes back to the arena here.
+double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
+                 const double* eri_mo_packed, double* eri_act)
+{
+    const int64_t na = n - nfc - nfv, o = nocc - nfc, v = na - o, ne = neri_of(n), nea = neri_of(na);
+    double* full = in.mo;
+    if (eri_mo_packed) {   // from the host: whatever was resident is replaced, as a transform would replace it
+        in.drop_mo(cx, cc);
+        full = cx.alloc_raw(ne);
+        AFESP_HIP(hipMemcpyAsync(full, eri_mo_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+    }
+    double* act = full;
+    if (na != n) {   // (the whole basis: the array stays where it is, bit for bit)
+        try {
+            act = cx.alloc_raw(nea);
+            k_window_pack(cx, act, full, (int)na, (int)nfc);
+        } catch (...) {
+            if (act != full) cx.release(act);
+            if (eri_mo_packed) cx.release(full);   // (resident integrals stay as they were)
+            throw;
+        }
+        if (eri_mo_packed) cx.release(full);   // (waits for the gather) a context never keeps two packed arrays past the call
+        else in.drop_mo(cx, cc);
+    }
+    in.set_mo(act, na);
+    const double emp2 = mp2_of_packed(cx, act, levels + nfc, o, v);
+    if (eri_act) {
+        AFESP_HIP(hipMemcpyAsync(eri_act, act, sizeof(double) * nea, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    }
+    return emp2;
+}
+
+int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed)
+{
+    FILE* f = fopen(path, "rb");
+    if (!f) throw Error(2, std::string("afesp_read_eri_text: cannot open ") + path);
+    std::vector<double> host((size_t)neri_of(nbasis), 0.0);
+    const int64_t lines = parse_eri_text(f, nbasis, host);
+    fclose(f);
+    if (lines < 0) throw Error(2, std::string("afesp_read_eri_text: malformed line or index outside 1..nbasis in ") + path);
+    in.upload_ao(cx, nbasis, host.data());
+    if (eri_packed) memcpy(eri_packed, host.data(), sizeof(double) * host.size());
+    return lines;
+}
+
+// write_fcidump (src/mp2.f90:451-487): the packed MO integrals in canonical order, one line "p q r s value" in format
+// (I3,I3,I3,I3,ES17.9) for every |value| > 1e-7 (no header, no one-electron part -- as the reference writes it).
+int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis)
+{
+    std::vector<double> host((size_t)neri_of(nbasis));
+    AFESP_HIP(hipMemcpyAsync(host.data(), in.mo, sizeof(double) * host.size(), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    FILE* f = fopen(path, "w");
+    if (!f) throw Error(2, std::string("afesp_write_fcidump: cannot open ") + path);
+    int64_t pqrs = 0, lines = 0;
+    for (int64_t p = 1; p <= nbasis; ++p)
+        for (int64_t q = 1; q <= p; ++q)
+            for (int64_t r = 1; r <= p; ++r) {
+                const int64_t s_up = (p == r) ? q : r;
+                for (int64_t s = 1; s <= s_up; ++s) {
+                    const double x = host[(size_t)pqrs++];
+                    if (std::fabs(x) > 1e-7) {
+                        fprintf(f, "%3d%3d%3d%3d%17.9E\n", (int)p, (int)q, (int)r, (int)s, x);
+                        ++lines;
+                    }
+                }
+            }
+    fclose(f);
+    return lines;
+}
+
+}  // namespace afesp

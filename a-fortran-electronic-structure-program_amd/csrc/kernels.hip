@@ -1191,7 +1191,7 @@ void k_lincomb(Context& cx, double* out, const double* xbase, int64_t xstride, c
 {
     if (n > 0) LAUNCH(lincomb_kernel, dim3(grid_for(n)), out, xbase, xstride, coef_dev, nx, n);
 }
-// ---- pair-symmetric AO->MO (capi.hip, afesp_ao2mo_mp2): the three layout steps between the quarter transforms
+// ---- pair-symmetric AO->MO (integrals.hip, ao2mo_mp2): the three layout steps between the quarter transforms
 // Both steps have the shape  out(x,y,C) = src(C, tri(x,y)):  a pair index is squared up into the two leading (fastest)
 // indices of the result while the other pair index C moves from fastest (in src) to slowest.  A workgroup stages a
 // 16 x 16 x 16 tile through LDS so that both the reads (16 consecutive C, or 16 consecutive members of the packed pair)

@@ -2,7 +2,7 @@
 //
 // Until round 5 the variables were read where they were used: some per call, some once per process through function-local statics
 // (a test that needed the other value had to start a process of its own).  Now: knobs_refresh() -- called at the top of every C-ABI
-// entry point that takes a context (capi.hip, guarded) and lazily by the first knobs() of a process -- looks at the environment's
+// entry point that takes a context (capi.hip, entry) and lazily by the first knobs() of a process -- looks at the environment's
 // AFESP_ entries, and when they differ from what it saw last it parses ALL of them into a fresh table; knobs() hands out that table.
 // So every knob, whatever it selects, follows the environment at the granularity of one C-ABI call, and none changes in the middle of
 // one.  A table that has been handed out is never modified (two tables, swapped), so a thread of another context reading beside a
