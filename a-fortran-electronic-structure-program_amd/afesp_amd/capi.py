@@ -31,6 +31,7 @@ EXPORTS = [
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
     "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init", "afesp_mo_window", "afesp_umo_window",
+    "afesp_mp2_vv_density", "afesp_ump2_vv_density",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -110,6 +111,8 @@ def load_library():
     L.afesp_ccsd_uso_init.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.c_int]
     L.afesp_mo_window.argtypes = [C.c_void_p, i64, i64, i64, i64, _dp, _opt, _opt, C.POINTER(dbl)]
     L.afesp_umo_window.argtypes = [C.c_void_p, i64, i64, i64, i64, i64, _dp, _dp, _opt, _opt, _opt, C.POINTER(dbl)]
+    L.afesp_mp2_vv_density.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.POINTER(dbl)]
+    L.afesp_ump2_vv_density.argtypes = [C.c_void_p, i64, i64, i64, i64, _dp, _dp, _dp, _dp, C.POINTER(dbl)]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -408,6 +411,63 @@ class Engine:
         self._chk(self.L.afesp_umo_window(self.h, nbasis, nalpha, nbeta, nfc, nfv, np.ascontiguousarray(levels_a, dtype=np.float64),
                                           np.ascontiguousarray(levels_b, dtype=np.float64), ptr(aa), ptr(ab), ptr(bb), C.byref(e2)))
         return aa, (ab.reshape((npr, npr)) if ab is not None else None), bb, e2.value
+
+    # ---- frozen natural orbitals (afesp_amd/fno.py does the host algebra)
+    def mp2_vv_density(self, nbasis, nocc, nfc, canon_levels):
+        """-> (D[v, v], frozen-core E(MP2) of the full virtual space) from the MO integrals do_mp2_spatial left on the device, before any
+        window: D(a,b) = sum_ijc [2 t(ijac) - t(ijca)] t(ijbc) over the active occupied orbitals, symmetric to the bit."""
+        e2 = dbl(0.0)
+        v = max(int(nbasis) - int(nocc), 0)
+        d = np.zeros(v * v)
+        self._chk(self.L.afesp_mp2_vv_density(self.h, nbasis, nocc, nfc, np.ascontiguousarray(canon_levels, dtype=np.float64), d,
+                                              C.byref(e2)))
+        return d.reshape((v, v), order="F"), e2.value
+
+    def ump2_vv_density(self, nbasis, nalpha, nbeta, nfc, levels_a, levels_b):
+        """-> (D_alpha[va, va], D_beta[vb, vb], frozen-core E(UMP2)) from the three blocks do_ump2 left on the device."""
+        e2 = dbl(0.0)
+        va, vb = max(int(nbasis) - int(nalpha), 0), max(int(nbasis) - int(nbeta), 0)
+        da, db = np.zeros(va * va), np.zeros(vb * vb)
+        self._chk(self.L.afesp_ump2_vv_density(self.h, nbasis, nalpha, nbeta, nfc, np.ascontiguousarray(levels_a, dtype=np.float64),
+                                               np.ascontiguousarray(levels_b, dtype=np.float64), da, db, C.byref(e2)))
+        return da.reshape((va, va), order="F"), db.reshape((vb, vb), order="F"), e2.value
+
+    def fno_window(self, nbasis, nocc, nfc, canon_coeff, canon_levels, eri_packed=None, n_keep=None, occ_tol=0.0, report=print):
+        """The whole frozen-natural-orbital set-up of a closed shell: transform with the canonical orbitals, the MP2 virtual density, the
+        natural virtuals (fno.natural_virtuals), a second transform with the rotated coefficients on the AO integrals resident on the
+        device, and the window (nfc, v - n_keep).  -> (n_keep, occupations, levels_act, E(MP2) in the FNO space, Delta MP2); afterwards
+        ccsd_init(nocc - nfc, n_keep, levels_act) / init_cc_spinorb(nocc - nfc + n_keep, 2 (nocc - nfc), levels_act).  The rotated
+        orbitals stay in self.fno_coeff / self.fno_levels.  eri_packed None: the AO integrals set_eri / read_eri_text left there."""
+        from . import fno
+        if eri_packed is not None:
+            self.set_eri(nbasis, eri_packed)
+        self.do_mp2_spatial(nbasis, nocc, canon_coeff, canon_levels, None, want_eri_mo=False)
+        d, e_full = self.mp2_vv_density(nbasis, nocc, nfc, canon_levels)
+        kept, occ, c2, l2 = fno.natural_virtuals(d, canon_coeff, canon_levels, nocc, n_keep, occ_tol, report)
+        self.fno_coeff, self.fno_levels = c2, l2
+        nfv = nbasis - nocc - kept
+        self.do_mp2_spatial(nbasis, nocc, c2, l2, None, want_eri_mo=False)   # (its own E(MP2) is not meaningful: Fock is not diagonal)
+        _, e_fno = self.mo_window(nbasis, nocc, nfc, nfv, l2, want_eri=False)
+        return kept, occ, np.ascontiguousarray(l2[nfc:nbasis - nfv]), e_fno, e_full - e_fno
+
+    def ufno_window(self, nbasis, nalpha, nbeta, nfc, coeff_a, coeff_b, levels_a, levels_b, eri_packed=None, n_keep=None, occ_tol=0.0,
+                    report=print):
+        """The open-shell twin -> (n_keep, (occ_a, occ_b), (levels_act_a, levels_act_b), E(UMP2) in the FNO space, Delta MP2); n_keep
+        counts the natural virtuals kept in the smaller virtual space, the same number min(va, vb) - n_keep is dropped from both spins.
+        Afterwards init_cc_uspinorb(nbasis - nfc - n_drop, nalpha - nfc, nbeta - nfc, *levels_act)."""
+        from . import fno
+        if eri_packed is not None:
+            self.set_eri(nbasis, eri_packed)
+        self.do_ump2(nbasis, nalpha, nbeta, coeff_a, coeff_b, levels_a, levels_b, None, want_eri_mo=False)
+        da, db, e_full = self.ump2_vv_density(nbasis, nalpha, nbeta, nfc, levels_a, levels_b)
+        kept, occ, ca, cb, la, lb = fno.natural_virtuals_uhf(da, db, coeff_a, coeff_b, levels_a, levels_b, nalpha, nbeta, n_keep, occ_tol,
+                                                             report)
+        self.fno_coeff, self.fno_levels = (ca, cb), (la, lb)
+        nfv = nbasis - max(nalpha, nbeta) - kept
+        self.do_ump2(nbasis, nalpha, nbeta, ca, cb, la, lb, None, want_eri_mo=False)
+        *_, e_fno = self.umo_window(nbasis, nalpha, nbeta, nfc, nfv, la, lb, want_eri=False)
+        hi = nbasis - nfv
+        return kept, occ, (np.ascontiguousarray(la[nfc:hi]), np.ascontiguousarray(lb[nfc:hi])), e_fno, e_full - e_fno
 
     def write_fcidump(self, path, nbasis):
         n = i64()

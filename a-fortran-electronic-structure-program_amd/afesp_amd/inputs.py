@@ -38,6 +38,9 @@ class SystemIn:
     frozen_core: bool = False       # freeze the noble-gas cores counted from geom.dat (frozen_core_count)
     n_frozen_core: int = -1         # explicit number of lowest MOs to freeze; -1 = not given; wins over frozen_core
     n_frozen_virt: int = 0          # highest MOs dropped
+    # frozen natural orbitals: the virtual space truncated in the basis of the MP2 natural virtuals (afesp_amd/fno.py); at most one of the two
+    fno_n_virt: int = -1            # number of natural virtuals kept; -1 = off
+    fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -112,7 +115,29 @@ def read_els_in(path: str) -> SystemIn:
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < -1:
             raise ValueError(f"{key} must be a non-negative integer!")
+    if not isinstance(sysin.fno_n_virt, int) or isinstance(sysin.fno_n_virt, bool) or sysin.fno_n_virt < -1:
+        raise ValueError("fno_n_virt must be a non-negative integer!")
+    if isinstance(sysin.fno_occ_tol, bool) or not isinstance(sysin.fno_occ_tol, (int, float)) or sysin.fno_occ_tol < 0.0:
+        raise ValueError("fno_occ_tol must be a non-negative number!")
+    sysin.fno_occ_tol = float(sysin.fno_occ_tol)
+    if sysin.fno_n_virt >= 0 and sysin.fno_occ_tol > 0.0:
+        raise ValueError("fno_n_virt and fno_occ_tol exclude each other!")
+    if fno_requested(sysin) and sysin.n_frozen_virt > 0:
+        raise ValueError("frozen natural orbitals and n_frozen_virt exclude each other!")
+    if sysin.fno_n_virt == 0:
+        raise ValueError("fno_n_virt leaves no active virtual orbital!")
     return sysin
+
+
+def fno_requested(sysin: SystemIn) -> bool:
+    """True if the input asks for frozen natural orbitals (either key)."""
+    return sysin.fno_n_virt >= 0 or sysin.fno_occ_tol > 0.0
+
+
+def check_fno_count(sysin: SystemIn, nvirt: int) -> None:
+    """fno_n_virt against the number of virtuals of the system (the smaller of the two spins' for an open shell): 1 ... nvirt."""
+    if sysin.fno_n_virt >= 0 and not 1 <= sysin.fno_n_virt <= nvirt:
+        raise ValueError("fno_n_virt leaves no active virtual orbital or exceeds the number of virtual orbitals!")
 
 
 def frozen_core_count(z_list) -> int:

@@ -284,6 +284,16 @@ void k_pack_cols(Context& cx, double* cols, const double* full, int n);   // col
 // the active orbital window [lo, lo + n_act): packed over n -> packed over n_act; the [npair x npair] alpha-beta block likewise
 void k_window_pack(Context& cx, double* dst, const double* src, int n_act, int lo);
 void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int n, int lo);
+// MP1 amplitude operands of the virtual-virtual MP2 density (afesp_mp2_vv_density / afesp_ump2_vv_density), gathered out of the resident
+// MO integrals with the contraction index fastest; o active occupied orbitals from orbital nfc on, v virtuals from orbital nfc + o on,
+// e_dev: the levels of the whole basis.  Each call leaves its share of the MP2 energy in cx.scal[slot].
+//   k_fno_amps:    T(j,i,c; a) = (ia|jc) / D, Tt = 2 T - T with i and j exchanged (closed shell); Tt == nullptr: T = [(ia|jc) - (ic|ja)] / D
+//                  alone, the same-spin amplitudes of one spin
+//   k_fno_amps_ab: the opposite-spin amplitudes (ia|JB) / D out of the npair x npair alpha-beta block, beta_cols = false: T(J,B,i; a)
+//                  (rows for D alpha), true: T(J,i,a; B) (rows for D beta)
+void k_fno_amps(Context& cx, double* T, double* Tt, const double* packed, const double* e_dev, int nfc, int o, int v, int slot);
+void k_fno_amps_ab(Context& cx, double* T, const double* ab, const double* ea_dev, const double* eb_dev, int n, int nfc, int oa, int ob, int va,
+                   int vb, bool beta_cols, int slot);
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);

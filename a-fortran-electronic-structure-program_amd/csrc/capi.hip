@@ -376,6 +376,22 @@ int afesp_mo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_froz
     });
 }
 
+int afesp_mp2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_frozen_core, const double* canon_levels, double* d_vv,
+                         double* e_mp2)
+{
+    return entry(ctx, [&](Context& cx) {
+        const int64_t n = nbasis, nfc = n_frozen_core;
+        if (n <= 0 || n > 1024 || nocc <= 0 || nocc >= n || !canon_levels || !d_vv) throw Error(1, "afesp_mp2_vv_density: bad extents");
+        if (nfc < 0) throw Error(1, "afesp_mp2_vv_density: negative number of frozen orbitals");
+        if (nfc >= nocc) throw Error(1, "afesp_mp2_vv_density: no active occupied orbital left");
+        if (!ctx->in.mo || ctx->in.mo_n != n)
+            throw Error(1, "afesp_mp2_vv_density: no MO integrals are resident for this basis size (call afesp_ao2mo_mp2 first, and "
+                           "afesp_mo_window afterwards)");
+        const double emp2 = mp2_vv_density(cx, ctx->in, n, nocc, nfc, canon_levels, d_vv);
+        if (e_mp2) *e_mp2 = emp2;
+    });
+}
+
 int afesp_ccsd_init(afesp_ctx* ctx, int64_t nocc, int64_t nvirt, const double* eri_mo_packed, const double* canon_levels,
                     int diis_n_errmat)
 {
@@ -844,6 +860,24 @@ int afesp_umo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbe
                            "taken once)");
         if (na != n) ctx->in.window_uhf(cx, na, nfc);
         const double e2 = ump2_of_blocks(cx, ctx->in, levels_a + nfc, levels_b + nfc, oa, ob, eri_aa, eri_ab, eri_bb);
+        if (e_ump2) *e_ump2 = e2;
+    });
+}
+
+int afesp_ump2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, const double* levels_a,
+                          const double* levels_b, double* d_a, double* d_b, double* e_ump2)
+{
+    return entry(ctx, [&](Context& cx) {
+        const int64_t n = nbasis, nfc = n_frozen_core;
+        if (n <= 0 || n > 1024 || nalpha < 0 || nbeta < 0 || nalpha > n || nbeta > n || !levels_a || !levels_b || !d_a || !d_b)
+            throw Error(1, "afesp_ump2_vv_density: bad extents");
+        if (nfc < 0) throw Error(1, "afesp_ump2_vv_density: negative number of frozen orbitals");
+        if (nalpha - nfc < 0 || nbeta - nfc < 0 || nalpha + nbeta - 2 * nfc <= 0)
+            throw Error(1, "afesp_ump2_vv_density: no active occupied orbital left");
+        if (!ctx->in.uhf_aa || ctx->in.uhf_n != n)
+            throw Error(1, "afesp_ump2_vv_density: no UHF MO integrals resident for this basis size (call afesp_ao2mo_ump2 first, and "
+                           "afesp_umo_window afterwards)");
+        const double e2 = ump2_vv_density(cx, ctx->in, n, nalpha, nbeta, nfc, levels_a, levels_b, d_a, d_b);
         if (e_ump2) *e_ump2 = e2;
     });
 }

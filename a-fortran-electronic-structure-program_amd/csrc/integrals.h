@@ -70,6 +70,12 @@ double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t noc
 // E(UMP2) of the three resident blocks (levels on the host, for their basis size), and the blocks themselves for whoever asks
 double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, const double* levels_b, int64_t oa, int64_t ob, double* eri_aa,
                       double* eri_ab, double* eri_bb);
+// The virtual-virtual block of the MP2 one-particle density from the resident MO integrals (frozen natural orbitals): the
+// MP1 amplitude operands are gathered into scratch that goes back to the arena inside the call, D = T~^T T runs through contract(); d_vv
+// (v x v, host) comes back symmetric to the bit; returns the frozen-core MP2 energy.  Nothing resident is written.
+double mp2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t nocc, int64_t nfc, const double* levels, double* d_vv);
+double ump2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, int64_t nfc, const double* levels_a,
+                       const double* levels_b, double* d_a, double* d_b);
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
 int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
 

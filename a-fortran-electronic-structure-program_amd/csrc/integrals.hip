@@ -615,6 +615,94 @@ double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t noc
     return emp2;
 }
 
+// ---- the virtual-virtual block of the MP2 one-particle density (frozen natural orbitals)
+namespace {
+inline int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }   // (every piece of the scratch block starts on a 128-byte line)
+// One block from the arena for the amplitude operands, D and the levels: refused (status 1) where it does not fit what the device has free
+// plus what the arena holds idle -- as afesp_ao2mo_ump2 refuses -- and given back when the call ends, on every path.
+struct FnoScratch {
+    Context& cx;
+    double* base = nullptr;
+    FnoScratch(Context& c, int64_t ndoubles, const char* who) : cx(c)
+    {
+        size_t free_b = 0, total_b = 0;
+        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (8.0 * (double)ndoubles > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+            throw Error(1, std::string(who) + ": the amplitude operands of this system do not fit the free device memory");
+        base = cx.alloc_raw(ndoubles);
+    }
+    ~FnoScratch()
+    {
+        try {
+            cx.release(base);   // (waits for the stream)
+        } catch (...) {
+        }
+    }
+};
+// D (+)= alpha A^T B over the rows: A, B dense (K x v), the contraction index fastest in both; the planner picks the kernel for the shape
+void fno_product(Context& cx, double alpha, double* A, double* B, double* D, int64_t K, int64_t v)
+{
+    if (K <= 0 || v <= 0) return;
+    contract(cx, alpha, view(A, {K, v}), "ka", view(B, {K, v}), "kb", 1.0, view(D, {v, v}), "ab");
+}
+// D -> host, symmetrised there (v^2 numbers): 1/2 (D(a,b) + D(b,a)) is the same number for both orders
+void fno_fetch_symmetric(Context& cx, const double* D, int64_t v, double* host)
+{
+    if (v <= 0) return;
+    AFESP_HIP(hipMemcpyAsync(host, D, sizeof(double) * v * v, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    for (int64_t b = 0; b < v; ++b)
+        for (int64_t a = 0; a < b; ++a) host[a + v * b] = host[b + v * a] = 0.5 * (host[a + v * b] + host[b + v * a]);
+}
+}  // namespace
+
+double mp2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t nocc, int64_t nfc, const double* levels, double* d_vv)
+{
+    const int64_t o = nocc - nfc, v = n - nocc, sz = up16(o * o * v * v), K = o * o * v;
+    FnoScratch s(cx, 2 * sz + up16(v * v) + up16(n), "afesp_mp2_vv_density");
+    double *T = s.base, *Tt = T + sz, *D = Tt + sz, *e_dev = D + up16(v * v);
+    AFESP_HIP(hipMemcpyAsync(e_dev, levels, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemsetAsync(D, 0, sizeof(double) * v * v, cx.stream));
+    k_fno_amps(cx, T, Tt, in.mo, e_dev, (int)nfc, (int)o, (int)v, 0);
+    const double e2 = host_scalars(cx, 1)[0];
+    fno_product(cx, 1.0, Tt, T, D, K, v);
+    fno_fetch_symmetric(cx, D, v, d_vv);
+    return e2;
+}
+
+double ump2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, int64_t nfc, const double* levels_a,
+                       const double* levels_b, double* d_a, double* d_b)
+{
+    const int64_t oa = na - nfc, ob = nb - nfc, va = n - na, vb = n - nb;
+    const int64_t saa = up16(oa * oa * va * va), sbb = up16(ob * ob * vb * vb), sab = up16(oa * ob * va * vb), sss = std::max(saa, sbb);
+    const int64_t vmax = std::max(va, vb);
+    // one spin after the other in the same two operands: same-spin amplitudes, opposite-spin amplitudes
+    FnoScratch s(cx, sss + sab + up16(vmax * vmax) + up16(2 * n), "afesp_ump2_vv_density");
+    double *Tss = s.base, *Tos = Tss + sss, *D = Tos + sab, *ea = D + up16(vmax * vmax), *eb = ea + n;
+    AFESP_HIP(hipMemcpyAsync(ea, levels_a, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(eb, levels_b, sizeof(double) * n, hipMemcpyHostToDevice, cx.stream));
+    double e2 = 0.0;
+    for (int beta = 0; beta < 2; ++beta) {
+        const int64_t o = beta ? ob : oa, v = beta ? vb : va, Kss = o * o * v, Kos = beta ? oa * ob * va : oa * ob * vb;
+        if (v <= 0) continue;
+        AFESP_HIP(hipMemsetAsync(D, 0, sizeof(double) * v * v, cx.stream));
+        if (Kss > 0) {
+            k_fno_amps(cx, Tss, nullptr, beta ? in.uhf_bb : in.uhf_aa, beta ? eb : ea, (int)nfc, (int)o, (int)v, 0);
+            e2 += host_scalars(cx, 1)[0];
+            fno_product(cx, 0.5, Tss, Tss, D, Kss, v);
+        }
+        if (Kos > 0) {
+            k_fno_amps_ab(cx, Tos, in.uhf_ab, ea, eb, (int)n, (int)nfc, (int)oa, (int)ob, (int)va, (int)vb, beta != 0, 0);
+            if (!beta) e2 += host_scalars(cx, 1)[0];   // (the opposite-spin energy once)
+            fno_product(cx, 1.0, Tos, Tos, D, Kos, v);
+        }
+        fno_fetch_symmetric(cx, D, v, beta ? d_b : d_a);
+    }
+    // (a spin without virtuals contributes its opposite-spin energy through the other spin's pass; without virtuals in alpha that pass is
+    // skipped above and the opposite-spin energy is zero anyway: no alpha virtual, no (ia|JB))
+    return e2;
+}
+
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed)
 {
     FILE* f = fopen(path, "rb");

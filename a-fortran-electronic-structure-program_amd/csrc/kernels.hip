@@ -1531,6 +1531,96 @@ void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int 
     const int64_t npa = (int64_t)n_act * (n_act + 1) / 2;
     if (npa > 0) LAUNCH(window_pairs_kernel, dim3(grid_for(npa * npa, 65536)), dst, src, n_act, n, lo);
 }
+// ---- MP1 amplitude operands of the virtual-virtual MP2 density (afesp_mp2_vv_density / afesp_ump2_vv_density)
+// One destination element per thread, x = j + o (i + o (c + v a)): the contraction index (j,i,c) of D = T~^T T runs fastest in the
+// operand (contiguous writes, both operands K-contiguous for the GEMM), and j fastest of all, because (ia|jc) lies at
+// tri(tri(A,I), tri(C,J)) in the 8-fold packed array -- for PQ >= RS a run along j (window_pack_kernel's argument; the exchange partner
+// (ic|ja) and the PQ < RS half are gathers).  Orbitals: I = nfc + i, A = nfc + o + a.  64-bit flat indices (o^2 v^2 = 3.2e7 at n = 220,
+// 8.5e9 at o = 100, v = 924).  Tt != nullptr (closed shell): T = t(i,j,a,c) = (ia|jc) / D, Tt = 2 t(i,j,a,c) - t(i,j,c,a), the block's
+// share of sum (ia|jc) Tt = E(MP2); Tt == nullptr (one spin of an open shell): T = [(ia|jc) - (ic|ja)] / D, share of 1/4 sum d T.
+// Fixed grid of RED_BLOCKS blocks, per-block partials, ordered final sum (final_sum_kernel): deterministic.
+__global__ __launch_bounds__(TB) void fno_amps_kernel(double* partial, double* __restrict__ T, double* __restrict__ Tt,
+                                                      const double* __restrict__ packed, const double* __restrict__ e, int nfc, int o, int v)
+{
+    __shared__ double sm[4];
+    const int64_t total = (int64_t)o * o * v * v;
+    const int no = nfc + o;
+    double acc[1] = {0.0};
+    GRID_STRIDE(x, total)
+    {
+        const int j = (int)(x % o);
+        int64_t r = x / o;
+        const int i = (int)(r % o);
+        r /= o;
+        const int c = (int)(r % v), a = (int)(r / v);
+        const int64_t I = nfc + i, J = nfc + j, A = no + a, Cc = no + c;
+        const double g = packed[tri(tri(A, I), tri(Cc, J))], gx = packed[tri(tri(Cc, I), tri(A, J))];
+        const double den = e[I] + e[J] - e[A] - e[Cc];
+        if (Tt) {
+            const double t = g / den, tt = 2.0 * t - gx / den;
+            T[x] = t;
+            Tt[x] = tt;
+            acc[0] += g * tt;
+        } else {
+            const double d = g - gx, t = d / den;
+            T[x] = t;
+            acc[0] += 0.25 * d * t;
+        }
+    }
+    block_sum<1>(acc, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
+}
+// The opposite-spin amplitudes t(i,J,a,B) = (ia|JB) / D out of the alpha-beta block ab[tri(A,I) np + tri(B,J)] (alpha pair: row).  J runs
+// fastest on both sides -- tri(B,J) is a run along J in the block's fastest index --
+//   BETA_COLS = false: x = J + ob (B + vb (i + oa a)), rows (J,B,i) of column a: the operand of D alpha
+//   BETA_COLS = true:  x = J + ob (i + oa (a + va B)), rows (J,i,a) of column B: the operand of D beta
+// and the block's share of sum (ia|JB) t, the opposite-spin part of E(UMP2).
+template <bool BETA_COLS>
+__global__ __launch_bounds__(TB) void fno_amps_ab_kernel(double* partial, double* __restrict__ T, const double* __restrict__ ab,
+                                                         const double* __restrict__ ea, const double* __restrict__ eb, int n, int nfc, int oa,
+                                                         int ob, int va, int vb)
+{
+    __shared__ double sm[4];
+    const int64_t total = (int64_t)oa * ob * va * vb, np = (int64_t)n * (n + 1) / 2;
+    const int na = nfc + oa, nb = nfc + ob;
+    double acc[1] = {0.0};
+    GRID_STRIDE(x, total)
+    {
+        const int j = (int)(x % ob);
+        int64_t r = x / ob;
+        int i, a, b;
+        if (BETA_COLS) {
+            i = (int)(r % oa);
+            r /= oa;
+            a = (int)(r % va);
+            b = (int)(r / va);
+        } else {
+            b = (int)(r % vb);
+            r /= vb;
+            i = (int)(r % oa);
+            a = (int)(r / oa);
+        }
+        const int64_t I = nfc + i, J = nfc + j, A = na + a, B = nb + b;
+        const double g = ab[tri(A, I) * np + tri(B, J)];
+        const double t = g / (ea[I] + eb[J] - ea[A] - eb[B]);
+        T[x] = t;
+        acc[0] += g * t;
+    }
+    block_sum<1>(acc, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
+}
+void k_fno_amps(Context& cx, double* T, double* Tt, const double* packed, const double* e_dev, int nfc, int o, int v, int slot)
+{
+    LAUNCH(fno_amps_kernel, dim3(RED_BLOCKS), partials(cx), T, Tt, packed, e_dev, nfc, o, v);
+    LAUNCH(final_sum_kernel, dim3(1), cx.scal + slot, partials(cx), RED_BLOCKS, 1, 0);
+}
+void k_fno_amps_ab(Context& cx, double* T, const double* ab, const double* ea_dev, const double* eb_dev, int n, int nfc, int oa, int ob, int va,
+                   int vb, bool beta_cols, int slot)
+{
+    if (beta_cols) LAUNCH(fno_amps_ab_kernel<true>, dim3(RED_BLOCKS), partials(cx), T, ab, ea_dev, eb_dev, n, nfc, oa, ob, va, vb);
+    else LAUNCH(fno_amps_ab_kernel<false>, dim3(RED_BLOCKS), partials(cx), T, ab, ea_dev, eb_dev, n, nfc, oa, ob, va, vb);
+    LAUNCH(final_sum_kernel, dim3(1), cx.scal + slot, partials(cx), RED_BLOCKS, 1, 0);
+}
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {
     int64_t n = (int64_t)d0 * d1 * d2 * d3;

@@ -11,6 +11,7 @@ module afesp_capi
              afesp_read_eri_text, afesp_write_fcidump, afesp_build_fock, afesp_ccsd_t_plain, afesp_device_count, &
              afesp_comm_init, afesp_comm_destroy, afesp_allreduce_sum, afesp_ccsd_t_shard_bounds, afesp_ccsd_t_block_size, &
              afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, afesp_mo_window, afesp_umo_window, &
+             afesp_mp2_vv_density, afesp_ump2_vv_density, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -195,6 +196,29 @@ module afesp_capi
          integer(c_int64_t), value :: nbasis, nalpha, nbeta, n_frozen_core, n_frozen_virt
          real(c_double), intent(in) :: levels_a(*), levels_b(*)
          type(c_ptr), value :: eri_aa, eri_ab, eri_bb
+         real(c_double), intent(out) :: e_ump2
+         integer(c_int) :: rc
+      end function
+      !> frozen natural orbitals: the virtual-virtual block of the MP2 one-particle density from the resident MO integrals, before any
+      !> window (include/afesp.h); d_vv is v x v, symmetric to the bit; e_mp2 = the frozen-core MP2 energy of the full virtual space
+      function afesp_mp2_vv_density(ctx, nbasis, nocc, n_frozen_core, canon_levels, d_vv, e_mp2) &
+         bind(C, name='afesp_mp2_vv_density') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nocc, n_frozen_core
+         real(c_double), intent(in) :: canon_levels(*)
+         real(c_double), intent(out) :: d_vv(*)
+         real(c_double), intent(out) :: e_mp2
+         integer(c_int) :: rc
+      end function
+      !> the same for the three blocks afesp_ao2mo_ump2 left: d_a (va x va), d_b (vb x vb)
+      function afesp_ump2_vv_density(ctx, nbasis, nalpha, nbeta, n_frozen_core, levels_a, levels_b, d_a, d_b, e_ump2) &
+         bind(C, name='afesp_ump2_vv_density') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta, n_frozen_core
+         real(c_double), intent(in) :: levels_a(*), levels_b(*)
+         real(c_double), intent(out) :: d_a(*), d_b(*)
          real(c_double), intent(out) :: e_ump2
          integer(c_int) :: rc
       end function

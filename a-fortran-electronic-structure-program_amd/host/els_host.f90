@@ -44,6 +44,9 @@ module host_config
       logical :: frozen_core = .false.   ! freeze the noble-gas cores counted from geom.dat
       integer :: n_frozen_core = -1      ! explicit number of lowest MOs to freeze (-1: not given); wins over frozen_core
       integer :: n_frozen_virt = 0       ! highest MOs dropped
+      ! frozen natural orbitals: the virtual space truncated in the basis of the MP2 natural virtuals; at most one of the two keys
+      integer :: fno_n_virt = -1         ! number of natural virtuals kept (-1: off)
+      real(dp) :: fno_occ_tol = 0.0_dp   ! keep every natural virtual whose occupation is at least this (0: off)
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -52,11 +55,12 @@ contains
       character(40) :: calc_type
       real(dp) :: scf_e_tol, scf_d_tol, ccsd_e_tol, ccsd_t_tol
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
-      integer :: n_frozen_core, n_frozen_virt
+      integer :: n_frozen_core, n_frozen_virt, fno_n_virt
+      real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
-         frozen_core, n_frozen_core, n_frozen_virt
+         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -64,6 +68,7 @@ contains
       scf_read_guess = d%scf_read_guess; scf_write_guess = d%scf_write_guess
       charge = d%charge; multiplicity = d%multiplicity
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
+      fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -78,6 +83,13 @@ contains
       cfg%frozen_core = frozen_core; cfg%n_frozen_core = n_frozen_core; cfg%n_frozen_virt = max(n_frozen_virt, 0)
       if (n_frozen_core < -1 .or. n_frozen_virt < -1) &
          call fail('system::read_system_in', 'n_frozen_core and n_frozen_virt must be non-negative integers!')
+      cfg%fno_n_virt = fno_n_virt; cfg%fno_occ_tol = fno_occ_tol
+      if (fno_n_virt < -1) call fail('system::read_system_in', 'fno_n_virt must be a non-negative integer!')
+      if (fno_occ_tol < 0.0_dp) call fail('system::read_system_in', 'fno_occ_tol must be a non-negative number!')
+      if (fno_n_virt >= 0 .and. fno_occ_tol > 0.0_dp) &
+         call fail('system::read_system_in', 'fno_n_virt and fno_occ_tol exclude each other!')
+      if ((fno_n_virt >= 0 .or. fno_occ_tol > 0.0_dp) .and. n_frozen_virt > 0) &
+         call fail('system::read_system_in', 'frozen natural orbitals and n_frozen_virt exclude each other!')
       select case (trim(calc_type))
       case ('RHF');              cfg%level = LEVEL_RHF
       case ('MP2_spatial');      cfg%level = LEVEL_MP2
@@ -290,6 +302,68 @@ contains
       end do
    end subroutine
 end module host_linalg
+
+!> Frozen natural orbitals, host side (afesp_amd/fno.py is the same algebra in numpy): eigenvectors of the virtual-virtual MP2 density the
+!> engine returns, the cut, and the rotation of the virtual block of the coefficients with the kept and the discarded natural virtuals
+!> made canonical among themselves.  v x v work: the Jacobi solver of host_linalg serves.
+module host_fno
+   use host_support
+   use host_linalg
+   implicit none
+   real(dp), parameter :: fno_degenerate_rtol = 1e-8_dp
+contains
+   !> D = U diag(occ) U^T, occupations in descending order
+   subroutine fno_occupations(d, occ, u)
+      real(dp), intent(in) :: d(:, :)
+      real(dp), allocatable, intent(out) :: occ(:), u(:, :)
+      real(dp), allocatable :: w(:), vec(:, :)
+      integer :: v, k
+      v = size(d, 1)
+      allocate (occ(v), u(v, v), w(v), vec(v, v))
+      if (v == 0) return
+      call sym_eig(d, w, vec)
+      do k = 1, v
+         occ(k) = w(v + 1 - k); u(:, k) = vec(:, v + 1 - k)
+      end do
+   end subroutine
+   !> the smallest count >= n_keep that does not split a set of occupations agreeing to a relative 1e-8
+   pure function fno_widen(occ, n_keep) result(k)
+      real(dp), intent(in) :: occ(:)
+      integer, intent(in) :: n_keep
+      integer :: k
+      k = n_keep
+      do while (k > 0 .and. k < size(occ))
+         if (abs(occ(k) - occ(k + 1)) > fno_degenerate_rtol*max(abs(occ(k)), abs(occ(k + 1)))) exit
+         k = k + 1
+      end do
+   end function
+   !> the virtual rows of coeff (MO x AO) become [kept ; discarded] natural virtuals, each block canonical within itself: the projection
+   !> of the (diagonal) virtual Fock matrix on the block is diagonalised, which gives the block's levels and a rotation
+   subroutine fno_rotate(coeff, levels, nocc, u, n_keep)
+      real(dp), intent(inout) :: coeff(:, :), levels(:)
+      integer, intent(in) :: nocc, n_keep
+      real(dp), intent(in) :: u(:, :)
+      real(dp), allocatable :: cv(:, :), ev(:), ub(:, :), x(:, :), f(:, :), e(:), r(:, :)
+      integer :: n, v, blk, lo, hi, m, k
+      n = size(coeff, 1); v = size(u, 1)
+      allocate (cv(v, size(coeff, 2)), ev(v))
+      cv = coeff(nocc + 1:n, :); ev = levels(nocc + 1:n)
+      do blk = 1, 2
+         lo = merge(1, n_keep + 1, blk == 1); hi = merge(n_keep, v, blk == 1)
+         m = hi - lo + 1
+         if (m <= 0) cycle
+         allocate (ub(v, m), x(v, m), f(m, m), e(m), r(m, m))
+         ub = u(:, lo:hi)
+         do k = 1, m; x(:, k) = ev*ub(:, k); end do
+         f = matmul(transpose(ub), x)
+         f = 0.5_dp*(f + transpose(f))
+         call sym_eig(f, e, r)
+         coeff(nocc + lo:nocc + hi, :) = matmul(transpose(matmul(ub, r)), cv)
+         levels(nocc + lo:nocc + hi) = e
+         deallocate (ub, x, f, e, r)
+      end do
+   end subroutine
+end module host_fno
 
 module host_scf
    use, intrinsic :: iso_c_binding
@@ -552,6 +626,7 @@ program els_amd
    use host_config
    use host_inputs
    use host_scf
+   use host_fno
    use afesp_capi
    implicit none
    type(run_config) :: cfg
@@ -564,6 +639,10 @@ program els_amd
    ! the active orbital window [nfc, nbasis - nfv): active basis size, occupied / virtual counts, electrons and spin counts
    integer :: nfc, nfv, n_act, o_act, v_act, nel_act, na_act, nb_act
    logical :: windowed
+   ! frozen natural orbitals: asked for, natural virtuals kept, MP2 in the full virtual space, the Delta MP2 correction
+   logical :: fno
+   integer :: fno_kept, vmin
+   real(dp) :: e_mp2_full, delta_mp2
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
    integer(c_int) :: rc, conv
@@ -678,6 +757,14 @@ program els_amd
          if (v_act <= 0) call fail('system::read_system_in', 'the frozen virtual orbitals leave no active virtual orbital')
       end if
    end if
+   fno = cfg%level >= LEVEL_MP2 .and. (cfg%fno_n_virt >= 0 .or. cfg%fno_occ_tol > 0.0_dp)
+   fno_kept = 0; e_mp2_full = 0.0_dp; delta_mp2 = 0.0_dp
+   if (fno .and. cfg%fno_n_virt >= 0) then   ! (an open shell counts in the smaller of its two virtual spaces)
+      vmin = mol%nvirt
+      if (cfg%uhf) vmin = mol%nbasis - max(na, nb)
+      if (cfg%fno_n_virt < 1 .or. cfg%fno_n_virt > vmin) call fail('system::read_system_in', &
+         'fno_n_virt leaves no active virtual orbital or exceeds the number of virtual orbitals')
+   end if
    write (out, '(1X, A, 1X, ES15.8)') 'E_nuc:', mol%e_nuc
    write (out, '(1X, A, 1X, A)') 'calc_type:', trim(cfg%calc_type)
 
@@ -700,12 +787,14 @@ program els_amd
       rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
       if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
-      if (windowed) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
+      if (fno) call open_shell_fno()   ! natural virtuals of both spins, second transform; sets nfv and the active extents
+      if (windowed .or. fno) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
          rc = afesp_umo_window(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), &
                                int(nfv, c_int64_t), levels, lb, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
       end if
       write (out, '(1X, A, 1X, F15.8)') 'UMP2 correlation energy (Hartree):', e_mp2
+      if (fno) call print_fno_energies('UMP2')
       e_highest = e_mp2
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UMP2:', seconds() - t0, 's'
       if (cfg%level >= LEVEL_CCSD) then
@@ -770,18 +859,23 @@ program els_amd
       write (out, '(1X, A)') 'Performing AO to MO ERI transformation...'
       rc = afesp_ao2mo_mp2(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), coeff, levels, c_null_ptr, c_null_ptr, e_mp2)
       if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
-      if (windowed) then
+      if (fno) then   ! the FCIDUMP (if asked for) is of the canonical integrals; then natural virtuals and the second transform
+         if (cfg%write_fcidump) call dump_integrals()
+         call closed_shell_fno()
+      end if
+      if (windowed .or. fno) then
          ! frozen orbitals: the FCIDUMP (if asked for) is of the full integrals; then the window over the active orbitals replaces
          ! them on the device, and the MP2 energy is the frozen-core one
-         if (cfg%write_fcidump) call dump_integrals()
+         if (cfg%write_fcidump .and. .not. fno) call dump_integrals()
          rc = afesp_mo_window(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), int(nfc, c_int64_t), int(nfv, c_int64_t), &
                               levels, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
       end if
       write (out, '(1X, A)') 'Calculating MP2 energy...'
       write (out, '(1X, A, 1X, F15.8)') 'MP2 correlation energy (Hartree):', e_mp2
+      if (fno) call print_fno_energies('MP2')
       e_highest = e_mp2
-      if (cfg%write_fcidump .and. .not. windowed) call dump_integrals()        ! reference src/mp2.f90:445-447
+      if (cfg%write_fcidump .and. .not. windowed .and. .not. fno) call dump_integrals()        ! reference src/mp2.f90:445-447
       t1s = seconds()
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for restricted MP2:', t1s - t0, 's'
 
@@ -1037,6 +1131,12 @@ program els_amd
       if (cfg%paren) write (out, '(1X, A, 1X, F15.10)') 'D(T):                          ', tq(4)
    end if
    end if
+   if (fno .and. cfg%level >= LEVEL_CCSD) then   ! the truncated virtual space corrected by what MP2 lost in it
+      write (out, '(1X, 47("-"))')
+      write (out, '(1X, A, 1X, F15.10)') 'Delta MP2 (full - FNO space):  ', delta_mp2
+      write (out, '(1X, A, 1X, F15.10)') 'CCSD + Delta MP2 correlation:  ', e_ccsd + delta_mp2
+      if (cfg%level == LEVEL_CCSD_T) write (out, '(1X, A, 1X, F15.10)') 'Final + Delta MP2 correlation: ', e_highest + delta_mp2
+   end if
    write (out, '(1X, 47("-"))')
    write (out, '(1X, A, 1X, F15.10)') 'Total electronic energy:       ', e_hf + e_highest
    write (out, '(1X, A, 1X, F15.10)') 'Nuclear repulsion:             ', mol%e_nuc
@@ -1044,6 +1144,101 @@ program els_amd
    write (out, '(1X, 64("="))')
    write (out, '(1X, A, 1X, F16.8)') 'Total execution time:', seconds() - tstart
 contains
+   !> the cut in one spin's occupations: the count asked for, or every occupation >= fno_occ_tol
+   function fno_count(occ) result(k)
+      real(dp), intent(in) :: occ(:)
+      integer :: k
+      if (cfg%fno_n_virt >= 0) then
+         k = cfg%fno_n_virt
+      else
+         k = count(occ >= cfg%fno_occ_tol)
+      end if
+   end function
+   subroutine print_fno_cut(asked, kept_occ, dropped_occ, any_dropped)
+      integer, intent(in) :: asked
+      real(dp), intent(in) :: kept_occ, dropped_occ
+      logical, intent(in) :: any_dropped
+      if (fno_kept == asked) then
+         write (out, '(1X, A, 1X, I0)') 'Number of natural virtuals kept:', fno_kept
+      else
+         write (out, '(1X, A, 1X, I0, A, I0, A)') 'Number of natural virtuals kept:', fno_kept, ' (asked for ', asked, &
+            ': degenerate occupations are kept together)'
+      end if
+      write (out, '(1X, A, 1X, ES15.8)') 'Smallest kept occupation:', kept_occ
+      if (any_dropped) write (out, '(1X, A, 1X, ES15.8)') 'Largest discarded occupation:', dropped_occ
+   end subroutine
+   !> after the window: e_mp2 is the MP2 energy in the FNO space
+   subroutine print_fno_energies(what)
+      character(*), intent(in) :: what
+      delta_mp2 = e_mp2_full - e_mp2
+      write (out, '(1X, A, 1X, F15.10)') what//' correlation energy, all virtuals (Hartree):', e_mp2_full
+      write (out, '(1X, A, 1X, F15.10)') what//' correlation energy, natural virtuals (Hartree):', e_mp2
+      write (out, '(1X, A, 1X, F15.10)') 'Delta MP2 (Hartree):', delta_mp2
+   end subroutine
+   !> closed shell: the MP2 virtual density of the canonical integrals just transformed, its natural virtuals, the cut, the rotated
+   !> coefficients and levels in place of the canonical ones, and the second transform on the AO integrals resident on the device
+   !> (its own MP2 energy is not meaningful: Fock is not diagonal between the kept and the discarded block).  Every rank does the
+   !> same algebra on the same D: no collective.
+   subroutine closed_shell_fno()
+      real(dp), allocatable :: d(:, :), occ(:), u(:, :)
+      integer :: asked
+      real(dp) :: dummy
+      write (out, '(1X, A)') 'Forming the MP2 natural virtual orbitals...'
+      allocate (d(mol%nvirt, mol%nvirt))
+      rc = afesp_mp2_vv_density(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), int(nfc, c_int64_t), levels, d, e_mp2_full)
+      if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+      call fno_occupations(d, occ, u)
+      asked = fno_count(occ)
+      if (asked < 1) call fail('mp2::natural_virtuals', 'fno_occ_tol leaves no natural virtual orbital')
+      fno_kept = fno_widen(occ, asked)
+      call print_fno_cut(asked, occ(fno_kept), occ(min(fno_kept + 1, mol%nvirt)), fno_kept < mol%nvirt)
+      call fno_rotate(coeff, levels, mol%nocc, u, fno_kept)
+      nfv = mol%nvirt - fno_kept
+      n_act = mol%nbasis - nfc - nfv; v_act = fno_kept
+      rc = afesp_ao2mo_mp2(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), coeff, levels, c_null_ptr, c_null_ptr, dummy)
+      if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+   end subroutine
+   !> open shell: both spins' densities and natural virtuals; the window drops the same number of orbitals from both spins, so the count
+   !> is taken in the smaller virtual space (a threshold: the larger of the two spins' counts, i.e. the smaller number dropped), and a
+   !> degenerate set in either spin moves the cut of both
+   subroutine open_shell_fno()
+      real(dp), allocatable :: da(:, :), db(:, :), occa(:), occb(:), ua(:, :), ub(:, :)
+      integer :: va, vb, asked, drop, new
+      real(dp) :: dummy
+      write (out, '(1X, A)') 'Forming the MP2 natural virtual orbitals...'
+      va = mol%nbasis - na; vb = mol%nbasis - nb; vmin = min(va, vb)
+      allocate (da(va, va), db(vb, vb))
+      rc = afesp_ump2_vv_density(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), levels, lb, &
+                                 da, db, e_mp2_full)
+      if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+      call fno_occupations(da, occa, ua)
+      call fno_occupations(db, occb, ub)
+      if (cfg%fno_n_virt >= 0) then
+         asked = cfg%fno_n_virt
+      else
+         asked = vmin - min(va - fno_count(occa), vb - fno_count(occb))
+      end if
+      if (asked < 1) call fail('mp2::natural_virtuals', 'fno_occ_tol leaves no natural virtual orbital')
+      drop = vmin - asked
+      do
+         new = min(va - fno_widen(occa, va - drop), vb - fno_widen(occb, vb - drop))
+         if (new == drop) exit
+         drop = new
+      end do
+      fno_kept = vmin - drop
+      if (va <= vb) then
+         call print_fno_cut(asked, occa(va - drop), occa(min(va - drop + 1, va)), drop > 0)
+      else
+         call print_fno_cut(asked, occb(vb - drop), occb(min(vb - drop + 1, vb)), drop > 0)
+      end if
+      call fno_rotate(coeff, levels, na, ua, va - drop)
+      call fno_rotate(cb, lb, nb, ub, vb - drop)
+      nfv = drop
+      n_act = mol%nbasis - nfc - nfv
+      rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
+                            c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, dummy)
+      if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+   end subroutine
    !> FCIDUMP of the MO integrals resident after the AO->MO transform (reference src/mp2.f90:445-447)
    subroutine dump_integrals()
       write (out, '(1X, A)') 'Writing FCIDUMP file...'

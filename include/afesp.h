@@ -214,6 +214,27 @@ int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t 
 int afesp_umo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, int64_t n_frozen_virt,
                      const double* levels_a, const double* levels_b, double* eri_aa, double* eri_ab, double* eri_bb, double* e_ump2);
 
+/* Frozen natural orbitals (the reference has none): the virtual-virtual block of the MP2 one-particle density, from the
+ * MO integrals a transform left resident and BEFORE any window.  i, j run over the active occupied orbitals (the n_frozen_core lowest
+ * excluded), a, b, c over all virtuals.
+ *   closed shell, t(i,j,a,b) = (ia|jb) / (e_i + e_j - e_a - e_b):   D(a,b) = sum_ijc [2 t(i,j,a,c) - t(i,j,c,a)] t(i,j,b,c)
+ *   open shell,   t_ss(i,j,a,b) = [(ia|jb) - (ib|ja)] / D,  t_ab(i,J,a,B) = (ia|JB) / D:
+ *                 D_a(a,b) = 1/2 sum_{ijc in alpha} t_aa(ijac) t_aa(ijbc) + sum_{i in alpha; J, C in beta} t_ab(iJaC) t_ab(iJbC);  D_b: the mirror image
+ * (trace D = the number of electron pairs promoted per spin; nalpha = nbeta with equal orbitals gives D_a = D_b = D).
+ *   in : the levels of the whole basis;   out: d_vv[v*v] (v = nbasis - nocc), d_a[va*va], d_b[vb*vb]: column-major, symmetric to the bit;
+ *        *e_mp2 / *e_ump2 (may be NULL) = the frozen-core MP2 energy of the full virtual space, what afesp_mo_window / afesp_umo_window
+ *        report for (n_frozen_core, 0) -- the "full space" term of the Delta-MP2 correction of a truncated virtual space.
+ * HIP builder kernels gather the MP1 amplitudes out of the packed arrays into two scratch operands (o^2 v^2 doubles each) with the
+ * contraction index (i,j,c) fastest; the products D = T~^T T (M = N = v, K = o^2 v) run through the GEMM layer; the scratch goes back to the
+ * context's arena inside the call.  Every resident array is left untouched: the host diagonalises D, rotates the virtual block of the
+ * coefficients, calls afesp_ao2mo_mp2 / afesp_ao2mo_ump2 again on the resident AO integrals (eri_packed = NULL) and takes the window.
+ * Status 1, nothing touched: a negative count, no active occupied orbital (n_frozen_core >= nocc), NULL levels or output, nothing resident
+ * for nbasis (so also after a window), scratch that does not fit the free device memory. */
+int afesp_mp2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_frozen_core, const double* canon_levels, double* d_vv,
+                         double* e_mp2);
+int afesp_ump2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, const double* levels_a,
+                          const double* levels_b, double* d_a, double* d_b, double* e_ump2);
+
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
  * every rank evaluates its shard [bounds[r], bounds[r+1]) of the triple list (afesp_ccsd_t_shard_bounds) and that
