@@ -32,6 +32,7 @@ EXPORTS = [
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
     "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init", "afesp_mo_window", "afesp_umo_window",
     "afesp_mp2_vv_density", "afesp_ump2_vv_density",
+    "afesp_core_operator", "afesp_ucore_operator", "afesp_write_fcidump_active", "afesp_write_fcidump_uactive",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -113,6 +114,10 @@ def load_library():
     L.afesp_umo_window.argtypes = [C.c_void_p, i64, i64, i64, i64, i64, _dp, _dp, _opt, _opt, _opt, C.POINTER(dbl)]
     L.afesp_mp2_vv_density.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.POINTER(dbl)]
     L.afesp_ump2_vv_density.argtypes = [C.c_void_p, i64, i64, i64, i64, _dp, _dp, _dp, _dp, C.POINTER(dbl)]
+    L.afesp_core_operator.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, C.POINTER(dbl)]
+    L.afesp_ucore_operator.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, _dp, _dp, C.POINTER(dbl)]
+    L.afesp_write_fcidump_active.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64, _dp, dbl, dbl, C.POINTER(i64)]
+    L.afesp_write_fcidump_uactive.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64, _dp, _dp, dbl, dbl, C.POINTER(i64)]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -472,6 +477,40 @@ class Engine:
     def write_fcidump(self, path, nbasis):
         n = i64()
         self._chk(self.L.afesp_write_fcidump(self.h, str(path).encode(), nbasis, C.byref(n)))
+        return n.value
+
+    # ---- the active space as a standard FCIDUMP (afesp_amd/fcidump.py reads it back)
+    def core_operator(self, nbasis, nfc, nfv, canon_coeff, core_hamil):
+        """-> (h_act[n_act, n_act], e_core) of the window [nfc, nbasis - nfv) from the full MO integrals do_mp2_spatial left on the
+        device, BEFORE mo_window: h_act = h_mo + sum_c [2 (pq|cc) - (pc|qc)], e_core = 2 sum_c h_cc + sum_cd [2 (cc|dd) - (cd|cd)]
+        (electronic; the caller adds the nuclear repulsion).  h_act is symmetric to the bit."""
+        e = dbl(0.0)
+        na = max(int(nbasis) - int(nfc) - int(nfv), 0)
+        h = np.zeros(na * na)
+        self._chk(self.L.afesp_core_operator(self.h, nbasis, nfc, nfv, _f(canon_coeff), _f(core_hamil), h, C.byref(e)))
+        return h.reshape((na, na), order="F"), e.value
+
+    def ucore_operator(self, nbasis, nfc, nfv, coeff_a, coeff_b, core_hamil):
+        """The open-shell twin on the three blocks do_ump2 left, before umo_window -> (h_act_alpha, h_act_beta, e_core)."""
+        e = dbl(0.0)
+        na = max(int(nbasis) - int(nfc) - int(nfv), 0)
+        ha, hb = np.zeros(na * na), np.zeros(na * na)
+        self._chk(self.L.afesp_ucore_operator(self.h, nbasis, nfc, nfv, _f(coeff_a), _f(coeff_b), _f(core_hamil), ha, hb, C.byref(e)))
+        return ha.reshape((na, na), order="F"), hb.reshape((na, na), order="F"), e.value
+
+    def write_fcidump_active(self, path, n_act, nelec_act, ms2, h_act, e_core_total, threshold=1e-12):
+        """The integrals resident for n_act orbitals (the window after mo_window, else the full basis), h_act and e_core_total (core
+        energy plus nuclear repulsion) as a standard FCIDUMP -> number of lines after the header."""
+        n = i64()
+        self._chk(self.L.afesp_write_fcidump_active(self.h, str(path).encode(), n_act, nelec_act, ms2, _f(h_act), e_core_total, threshold,
+                                                    C.byref(n)))
+        return n.value
+
+    def write_fcidump_uactive(self, path, n_act, nalpha_act, nbeta_act, h_act_a, h_act_b, e_core_total, threshold=1e-12):
+        """The same for the three blocks resident after do_ump2 / umo_window: UHF=.TRUE., 2 n_act interleaved spin orbitals."""
+        n = i64()
+        self._chk(self.L.afesp_write_fcidump_uactive(self.h, str(path).encode(), n_act, nalpha_act, nbeta_act, _f(h_act_a), _f(h_act_b),
+                                                     e_core_total, threshold, C.byref(n)))
         return n.value
 
     # ---- spin-orbital path: do_ccsd_spinorb (src/ccsd.f90:71-277), do_ccsd_t_spinorb (:1812-1922)

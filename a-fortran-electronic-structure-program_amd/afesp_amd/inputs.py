@@ -30,6 +30,7 @@ class SystemIn:
     scf_maxiter: int = 50
     ccsd_maxiter: int = 50
     write_fcidump: bool = False
+    fcidump_active: bool = False    # the active space as a standard FCIDUMP (afesp_amd/fcidump.py); excludes write_fcidump (same file name)
     scf_read_guess: bool = False
     scf_write_guess: bool = False
     charge: int = 0                 # open-shell types only (UHF_scf, UMP2, UCCSD, UCCSD(T))
@@ -109,8 +110,10 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("invalid input file format!")
     if (sysin.charge, sysin.multiplicity) != (0, 1) and sysin.calc_type not in OPEN_SHELL_TYPES:
         raise ValueError("charge and multiplicity need an open-shell calculation type!")
-    if not isinstance(sysin.frozen_core, bool):
+    if not isinstance(sysin.frozen_core, bool) or not isinstance(sysin.fcidump_active, bool):
         raise ValueError("invalid input file format!")
+    if sysin.fcidump_active and sysin.write_fcidump:
+        raise ValueError("write_fcidump and fcidump_active both write FCIDUMP: choose one!")
     for key in ("n_frozen_core", "n_frozen_virt"):
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < -1:

@@ -294,6 +294,18 @@ void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int 
 void k_fno_amps(Context& cx, double* T, double* Tt, const double* packed, const double* e_dev, int nfc, int o, int v, int slot);
 void k_fno_amps_ab(Context& cx, double* T, const double* ab, const double* ea_dev, const double* eb_dev, int n, int nfc, int oa, int ob, int va,
                    int vb, bool beta_cols, int slot);
+// The field of the nfc frozen orbitals on the active window [nfc, nfc + n_act) (afesp_core_operator / afesp_ucore_operator): h_act (n_act x
+// n_act, symmetric to the bit) = window of hmo (n x n) + the core's Coulomb and exchange out of the packed array over n orbitals, and
+// *e_core = the core's own energy.  one_spin: the same-spin weights of an open shell (J - K, half the pair sum) instead of 2 J - K.
+//   k_core_fold_ab: adds the opposite-spin Coulomb terms of the npair x npair alpha-beta block to both h_a and h_b; *e_core = sum_cD (cc|DD)
+void k_core_fold(Context& cx, double* h_act, double* e_core, const double* hmo, const double* packed, int n, int nfc, int n_act, bool one_spin);
+void k_core_fold_ab(Context& cx, double* h_a, double* h_b, double* e_core, const double* ab, int n, int nfc, int n_act);
+// Order-preserving stream compaction: the elements of x[0, total) with |x| > thr as (flat index, value) pairs in rising index order.
+//   k_compact_count:   counts[0 .. k_compact_chunks(total)] = exclusive prefix sums of the per-chunk survivor counts, the last = their number
+//   k_compact_scatter: the pairs, into arrays of that many elements
+int64_t k_compact_chunks(int64_t total);
+void k_compact_count(Context& cx, int64_t* counts, const double* x, int64_t total, double thr);
+void k_compact_scatter(Context& cx, int64_t* out_idx, double* out_val, const int64_t* prefix, const double* x, int64_t total, double thr);
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);

@@ -688,6 +688,67 @@ int afesp_write_fcidump(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_
     });
 }
 
+// ---------------------------------------------------------------- the active space as a Hamiltonian on disk
+int afesp_core_operator(afesp_ctx* ctx, int64_t nbasis, int64_t n_frozen_core, int64_t n_frozen_virt, const double* canon_coeff,
+                        const double* core_hamil_ao, double* h_act, double* e_core)
+{
+    return entry(ctx, [&](Context& cx) {
+        const int64_t n = nbasis, nfc = n_frozen_core, nfv = n_frozen_virt;
+        if (n <= 0 || n > 1024 || !canon_coeff || !core_hamil_ao || !h_act || !e_core) throw Error(1, "afesp_core_operator: bad extents");
+        if (nfc < 0 || nfv < 0) throw Error(1, "afesp_core_operator: negative number of frozen orbitals");
+        if (nfc + nfv >= n) throw Error(1, "afesp_core_operator: no active orbital left");
+        if (!ctx->in.mo || ctx->in.mo_n != n)
+            throw Error(1, "afesp_core_operator: no MO integrals are resident for this basis size (call afesp_ao2mo_mp2 first, and "
+                           "afesp_mo_window afterwards)");
+        core_operator(cx, ctx->in, n, nfc, nfv, canon_coeff, core_hamil_ao, h_act, e_core);
+    });
+}
+
+int afesp_ucore_operator(afesp_ctx* ctx, int64_t nbasis, int64_t n_frozen_core, int64_t n_frozen_virt, const double* coeff_a,
+                         const double* coeff_b, const double* core_hamil_ao, double* h_act_a, double* h_act_b, double* e_core)
+{
+    return entry(ctx, [&](Context& cx) {
+        const int64_t n = nbasis, nfc = n_frozen_core, nfv = n_frozen_virt;
+        if (n <= 0 || n > 1024 || !coeff_a || !coeff_b || !core_hamil_ao || !h_act_a || !h_act_b || !e_core)
+            throw Error(1, "afesp_ucore_operator: bad extents");
+        if (nfc < 0 || nfv < 0) throw Error(1, "afesp_ucore_operator: negative number of frozen orbitals");
+        if (nfc + nfv >= n) throw Error(1, "afesp_ucore_operator: no active orbital left");
+        if (!ctx->in.uhf_aa || ctx->in.uhf_n != n)
+            throw Error(1, "afesp_ucore_operator: no UHF MO integrals resident for this basis size (call afesp_ao2mo_ump2 first, and "
+                           "afesp_umo_window afterwards)");
+        ucore_operator(cx, ctx->in, n, nfc, nfv, coeff_a, coeff_b, core_hamil_ao, h_act_a, h_act_b, e_core);
+    });
+}
+
+int afesp_write_fcidump_active(afesp_ctx* ctx, const char* path, int64_t n_act, int64_t nelec_act, int64_t ms2, const double* h_act,
+                               double e_core_total, double threshold, int64_t* nwritten)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (!path || !h_act || n_act <= 0 || nelec_act < 0 || nelec_act > 2 * n_act || !(threshold >= 0.0))
+            throw Error(1, "afesp_write_fcidump_active: bad arguments");
+        if (!ctx->in.mo || ctx->in.mo_n != n_act)
+            throw Error(1, "afesp_write_fcidump_active: no MO integrals resident for this number of orbitals (afesp_ao2mo_mp2 / "
+                           "afesp_mo_window first)");
+        const int64_t lines = write_fcidump_active(cx, ctx->in, path, n_act, nelec_act, ms2, h_act, e_core_total, threshold);
+        if (nwritten) *nwritten = lines;
+    });
+}
+
+int afesp_write_fcidump_uactive(afesp_ctx* ctx, const char* path, int64_t n_act, int64_t nalpha_act, int64_t nbeta_act, const double* h_act_a,
+                                const double* h_act_b, double e_core_total, double threshold, int64_t* nwritten)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (!path || !h_act_a || !h_act_b || n_act <= 0 || nalpha_act < 0 || nbeta_act < 0 || nalpha_act > n_act || nbeta_act > n_act ||
+            !(threshold >= 0.0))
+            throw Error(1, "afesp_write_fcidump_uactive: bad arguments");
+        if (!ctx->in.uhf_aa || ctx->in.uhf_n != n_act)
+            throw Error(1, "afesp_write_fcidump_uactive: no UHF MO integrals resident for this number of orbitals (afesp_ao2mo_ump2 / "
+                           "afesp_umo_window first)");
+        const int64_t lines = write_fcidump_uactive(cx, ctx->in, path, n_act, nalpha_act, nbeta_act, h_act_a, h_act_b, e_core_total, threshold);
+        if (nwritten) *nwritten = lines;
+    });
+}
+
 // ---------------------------------------------------------------- spin-orbital path
 int afesp_ccsd_so_init(afesp_ctx* ctx, int64_t nbasis, int64_t nel, const double* eri_mo_packed, const double* canon_levels,
                        int diis_n_errmat, int flags)

@@ -76,6 +76,19 @@ double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, 
 double mp2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t nocc, int64_t nfc, const double* levels, double* d_vv);
 double ump2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, int64_t nfc, const double* levels_a,
                        const double* levels_b, double* d_a, double* d_b);
+// The frozen-core operator of the active window [nfc, n - nfv) and the core energy from the full MO integrals a transform
+// left resident: h_mo = C h_ao C^T through contract(), the core's field gathered by k_core_fold; h_act (n_act x n_act, host) symmetric to
+// the bit, *e_core electronic.  Nothing resident is written; the scratch goes back to the arena inside the call.
+void core_operator(Context& cx, const Integrals& in, int64_t n, int64_t nfc, int64_t nfv, const double* coeff, const double* h_ao, double* h_act,
+                   double* e_core);
+void ucore_operator(Context& cx, const Integrals& in, int64_t n, int64_t nfc, int64_t nfv, const double* coeff_a, const double* coeff_b,
+                    const double* h_ao, double* h_act_a, double* h_act_b, double* e_core);
+// The resident integrals over n_act orbitals as a standard FCIDUMP (fcidump_format.h): compacted on the device, formatted on the host;
+// return the number of lines after the header
+int64_t write_fcidump_active(Context& cx, const Integrals& in, const char* path, int64_t n_act, int64_t nelec, int64_t ms2, const double* h_act,
+                             double e_core_total, double threshold);
+int64_t write_fcidump_uactive(Context& cx, const Integrals& in, const char* path, int64_t n_act, int64_t nalpha, int64_t nbeta,
+                              const double* h_act_a, const double* h_act_b, double e_core_total, double threshold);
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
 int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
 

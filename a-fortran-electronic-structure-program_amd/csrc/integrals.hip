@@ -1,9 +1,10 @@
 // integrals.hip -- the integral layer (integrals.h): the resident AO / MO integrals and their validity records, the AO->MO transform in
-// its forms (pair kernels, gather GEMM, LDS-DMA GEMM, slab-blocked), the orbital windows, the text reader and the FCIDUMP writer.
+// its forms (pair kernels, gather GEMM, LDS-DMA GEMM, slab-blocked), the orbital windows, the frozen-core operator, the text reader and the FCIDUMP writers.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
+#include "fcidump_format.h"
 #include "integrals.h"
 #include "tgemm.h"
 
@@ -623,12 +624,12 @@ inline int64_t up16(int64_t x) { return (x + 15) / 16 * 16; }   // (every piece 
 struct FnoScratch {
     Context& cx;
     double* base = nullptr;
-    FnoScratch(Context& c, int64_t ndoubles, const char* who) : cx(c)
+    FnoScratch(Context& c, int64_t ndoubles, const char* who, const char* what = "the amplitude operands of this system") : cx(c)
     {
         size_t free_b = 0, total_b = 0;
         AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
         if (8.0 * (double)ndoubles > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
-            throw Error(1, std::string(who) + ": the amplitude operands of this system do not fit the free device memory");
+            throw Error(1, std::string(who) + ": " + what + " do not fit the free device memory");
         base = cx.alloc_raw(ndoubles);
     }
     ~FnoScratch()
@@ -701,6 +702,122 @@ double ump2_vv_density(Context& cx, const Integrals& in, int64_t n, int64_t na, 
     // (a spin without virtuals contributes its opposite-spin energy through the other spin's pass; without virtuals in alpha that pass is
     // skipped above and the opposite-spin energy is zero anyway: no alpha virtual, no (ia|JB))
     return e2;
+}
+
+// ---- the frozen-core operator of the active window and the core energy
+namespace {
+// h_mo = C h_ao C^T on the device: C is (MO, AO), so h_mo(p,q) = sum_ab C(p,a) h(a,b) C(q,b); hao and tmp are n x n scratch
+void core_h_mo(Context& cx, const double* coeff_host, double* Cm, double* hao, double* tmp, double* hmo, int64_t n)
+{
+    AFESP_HIP(hipMemcpyAsync(Cm, coeff_host, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    contract(cx, 1.0, view(Cm, {n, n}), "pa", view(hao, {n, n}), "ab", 0.0, view(tmp, {n, n}), "pb");
+    contract(cx, 1.0, view(Cm, {n, n}), "qb", view(tmp, {n, n}), "pb", 0.0, view(hmo, {n, n}), "pq");
+}
+}  // namespace
+
+void core_operator(Context& cx, const Integrals& in, int64_t n, int64_t nfc, int64_t nfv, const double* coeff, const double* h_ao, double* h_act,
+                   double* e_core)
+{
+    const int64_t na = n - nfc - nfv, n2 = up16(n * n);
+    FnoScratch s(cx, 4 * n2 + up16(na * na) + 16, "afesp_core_operator", "the one-electron matrices of this system");
+    double *Cm = s.base, *hao = Cm + n2, *tmp = hao + n2, *hmo = tmp + n2, *hact = hmo + n2, *e_dev = hact + up16(na * na);
+    AFESP_HIP(hipMemcpyAsync(hao, h_ao, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    core_h_mo(cx, coeff, Cm, hao, tmp, hmo, n);
+    k_core_fold(cx, hact, e_dev, hmo, in.mo, (int)n, (int)nfc, (int)na, false);
+    AFESP_HIP(hipMemcpyAsync(h_act, hact, sizeof(double) * na * na, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(e_core, e_dev, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+void ucore_operator(Context& cx, const Integrals& in, int64_t n, int64_t nfc, int64_t nfv, const double* coeff_a, const double* coeff_b,
+                    const double* h_ao, double* h_act_a, double* h_act_b, double* e_core)
+{
+    const int64_t na = n - nfc - nfv, n2 = up16(n * n), a2 = up16(na * na);
+    FnoScratch s(cx, 4 * n2 + 2 * a2 + 16, "afesp_ucore_operator", "the one-electron matrices of this system");
+    double *Cm = s.base, *hao = Cm + n2, *tmp = hao + n2, *hmo = tmp + n2, *ha = hmo + n2, *hb = ha + a2, *e_dev = hb + a2;
+    AFESP_HIP(hipMemcpyAsync(hao, h_ao, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+    core_h_mo(cx, coeff_a, Cm, hao, tmp, hmo, n);
+    k_core_fold(cx, ha, e_dev, hmo, in.uhf_aa, (int)n, (int)nfc, (int)na, true);
+    core_h_mo(cx, coeff_b, Cm, hao, tmp, hmo, n);
+    k_core_fold(cx, hb, e_dev + 1, hmo, in.uhf_bb, (int)n, (int)nfc, (int)na, true);
+    k_core_fold_ab(cx, ha, hb, e_dev + 2, in.uhf_ab, (int)n, (int)nfc, (int)na);
+    double e[3] = {0.0, 0.0, 0.0};
+    AFESP_HIP(hipMemcpyAsync(h_act_a, ha, sizeof(double) * na * na, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(h_act_b, hb, sizeof(double) * na * na, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(e, e_dev, 3 * sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    *e_core = (e[0] + e[1]) + e[2];
+}
+
+// ---- the standard FCIDUMP of the resident integrals
+namespace {
+struct File {
+    FILE* f;
+    explicit File(FILE* g) : f(g) {}
+    ~File() { if (f) fclose(f); }
+};
+// the survivors |x| > threshold of a device array, compacted there (kernels.hip) and written as two-electron lines; returns their number
+int64_t dump_block(Context& cx, FILE* f, const char* who, const double* x, int64_t total, double threshold, fcidump::Block b, int64_t np)
+{
+    const int64_t nchunks = k_compact_chunks(total);
+    FnoScratch counts(cx, nchunks + 1, who, "the compaction counters");
+    int64_t* prefix = reinterpret_cast<int64_t*>(counts.base);
+    k_compact_count(cx, prefix, x, total, threshold);
+    int64_t kept = 0;
+    AFESP_HIP(hipMemcpyAsync(&kept, prefix + nchunks, sizeof(int64_t), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    if (kept == 0) return 0;
+    FnoScratch pairs(cx, 2 * kept, who, "the compacted integrals");
+    int64_t* idx_dev = reinterpret_cast<int64_t*>(pairs.base);
+    double* val_dev = pairs.base + kept;
+    k_compact_scatter(cx, idx_dev, val_dev, prefix, x, total, threshold);
+    std::vector<int64_t> idx((size_t)kept);
+    std::vector<double> val((size_t)kept);
+    AFESP_HIP(hipMemcpyAsync(idx.data(), idx_dev, sizeof(int64_t) * kept, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(val.data(), val_dev, sizeof(double) * kept, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    if (!fcidump::write_two_electron(f, b, np, idx.data(), val.data(), kept, fcidump::thread_count(kept)))
+        throw Error(2, std::string(who) + ": write failed");
+    return kept;
+}
+}  // namespace
+
+int64_t write_fcidump_active(Context& cx, const Integrals& in, const char* path, int64_t n_act, int64_t nelec, int64_t ms2, const double* h_act,
+                             double e_core_total, double threshold)
+{
+    const char* who = "afesp_write_fcidump_active";
+    File out(fopen(path, "w"));
+    if (!out.f) throw Error(2, std::string(who) + ": cannot open " + path);
+    if (!fcidump::write_header(out.f, n_act, nelec, ms2, false)) throw Error(2, std::string(who) + ": write failed");
+    int64_t lines = dump_block(cx, out.f, who, in.mo, neri_of(n_act), threshold, fcidump::SPATIAL, 0);
+    const int64_t one = fcidump::write_one_electron(out.f, h_act, n_act, threshold, false, false);
+    if (one < 0 || !fcidump::write_core_energy(out.f, e_core_total)) throw Error(2, std::string(who) + ": write failed");
+    lines += one + 1;
+    FILE* f = out.f;
+    out.f = nullptr;
+    if (fclose(f) != 0) throw Error(2, std::string(who) + ": write failed");
+    return lines;
+}
+
+int64_t write_fcidump_uactive(Context& cx, const Integrals& in, const char* path, int64_t n_act, int64_t nalpha, int64_t nbeta,
+                              const double* h_act_a, const double* h_act_b, double e_core_total, double threshold)
+{
+    const char* who = "afesp_write_fcidump_uactive";
+    const int64_t np = npair_of(n_act);
+    File out(fopen(path, "w"));
+    if (!out.f) throw Error(2, std::string(who) + ": cannot open " + path);
+    if (!fcidump::write_header(out.f, 2 * n_act, nalpha + nbeta, nalpha - nbeta, true)) throw Error(2, std::string(who) + ": write failed");
+    int64_t lines = dump_block(cx, out.f, who, in.uhf_aa, neri_of(n_act), threshold, fcidump::ALPHA_ALPHA, 0);
+    lines += dump_block(cx, out.f, who, in.uhf_bb, neri_of(n_act), threshold, fcidump::BETA_BETA, 0);
+    lines += dump_block(cx, out.f, who, in.uhf_ab, np * np, threshold, fcidump::ALPHA_BETA, np);
+    const int64_t one_a = fcidump::write_one_electron(out.f, h_act_a, n_act, threshold, true, false);
+    const int64_t one_b = one_a < 0 ? -1 : fcidump::write_one_electron(out.f, h_act_b, n_act, threshold, true, true);
+    if (one_b < 0 || !fcidump::write_core_energy(out.f, e_core_total)) throw Error(2, std::string(who) + ": write failed");
+    lines += one_a + one_b + 1;
+    FILE* f = out.f;
+    out.f = nullptr;
+    if (fclose(f) != 0) throw Error(2, std::string(who) + ": write failed");
+    return lines;
 }
 
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed)

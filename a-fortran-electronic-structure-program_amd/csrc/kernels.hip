@@ -294,6 +294,8 @@ __global__ void lincomb_kernel(double* out, const double* xbase, int64_t xstride
 }
 
 __device__ __forceinline__ int64_t tri(int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
+// where (pq|rs) lies in the 8-fold packed array, for the four indices in any order (the one place that canonicalises them)
+__device__ __forceinline__ int64_t packed_index(int64_t p, int64_t q, int64_t r, int64_t s) { return tri(tri(p, q), tri(r, s)); }
 // pair index of x <= y: y(y+1)/2 + x; inverse of it
 __device__ __forceinline__ void unpair(int64_t p, int& lo, int& hi)
 {
@@ -1311,8 +1313,7 @@ __global__ void window_pack_kernel(double* __restrict__ dst, const double* __res
         int q, p, s, r;
         unpair(pq, q, p);
         unpair(rs, s, r);
-        const int64_t PQ = tri(p + lo, q + lo), RS = tri(r + lo, s + lo);
-        dst[x] = src[PQ * (PQ + 1) / 2 + RS];
+        dst[x] = src[packed_index(p + lo, q + lo, r + lo, s + lo)];
     }
 }
 // The same for the alpha-beta block of the open-shell path, a full [npair x npair] matrix (afesp_umo_window):
@@ -1554,7 +1555,7 @@ __global__ __launch_bounds__(TB) void fno_amps_kernel(double* partial, double* _
         r /= o;
         const int c = (int)(r % v), a = (int)(r / v);
         const int64_t I = nfc + i, J = nfc + j, A = no + a, Cc = no + c;
-        const double g = packed[tri(tri(A, I), tri(Cc, J))], gx = packed[tri(tri(Cc, I), tri(A, J))];
+        const double g = packed[packed_index(A, I, Cc, J)], gx = packed[packed_index(Cc, I, A, J)];
         const double den = e[I] + e[J] - e[A] - e[Cc];
         if (Tt) {
             const double t = g / den, tt = 2.0 * t - gx / den;
@@ -1621,6 +1622,178 @@ void k_fno_amps_ab(Context& cx, double* T, const double* ab, const double* ea_de
     else LAUNCH(fno_amps_ab_kernel<false>, dim3(RED_BLOCKS), partials(cx), T, ab, ea_dev, eb_dev, n, nfc, oa, ob, va, vb);
     LAUNCH(final_sum_kernel, dim3(1), cx.scal + slot, partials(cx), RED_BLOCKS, 1, 0);
 }
+// ---- the field of the frozen core on the active window (afesp_core_operator / afesp_ucore_operator)
+// One wave per active pair (p >= q), P = nfc + p, Q = nfc + q: h_act(p,q) = h_mo(P,Q) + sum_c [wj (PQ|cc) - (Pc|Qc)] over the nfc frozen
+// orbitals -- lane l takes c = l, l + 64, ... in rising order and the 64 partial sums are added in wave_sum's fixed order, so the result
+// does not depend on the launch -- written to both triangles from one register (symmetric to the bit; h_mo enters as the mean of its two
+// triangles, which the GEMMs leave equal only to rounding).  The wave after the last pair forms the core energy
+// e_core = eh sum_c h_mo(c,c) + e2 sum_cd [wj (cc|dd) - (cd|cd)].  Closed shell: wj = 2, eh = 2, e2 = 1; one spin of an open shell:
+// wj = 1, eh = 1, e2 = 1/2.  64-bit flat indices (packed_index).
+__global__ __launch_bounds__(TB) void core_fold_kernel(double* __restrict__ h_act, double* __restrict__ e_core, const double* __restrict__ hmo,
+                                                       const double* __restrict__ packed, int n, int nfc, int n_act, double wj, double eh,
+                                                       double e2)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t npa = (int64_t)n_act * (n_act + 1) / 2, w = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (w > npa) return;   // (whole waves leave)
+    double acc = 0.0;
+    if (w < npa) {
+        int q, p;
+        unpair(w, q, p);
+        const int64_t P = p + nfc, Q = q + nfc;
+        for (int64_t c = lane; c < nfc; c += 64) acc += wj * packed[packed_index(P, Q, c, c)] - packed[packed_index(P, c, Q, c)];
+        acc = wave_sum(acc);
+        if (lane == 0) {
+            const double val = 0.5 * (hmo[P + (int64_t)n * Q] + hmo[Q + (int64_t)n * P]) + acc;
+            h_act[p + (int64_t)n_act * q] = val;
+            h_act[q + (int64_t)n_act * p] = val;
+        }
+    } else {
+        double one = 0.0;
+        for (int64_t x = lane; x < (int64_t)nfc * nfc; x += 64) {
+            const int64_t c = x % nfc, d = x / nfc;
+            acc += wj * packed[packed_index(c, c, d, d)] - packed[packed_index(c, d, c, d)];
+        }
+        for (int64_t c = lane; c < nfc; c += 64) one += hmo[c + (int64_t)n * c];
+        acc = wave_sum(acc);
+        one = wave_sum(one);
+        if (lane == 0) *e_core = eh * one + e2 * acc;
+    }
+}
+// The opposite-spin share out of the alpha-beta block ab[tri(p,q) np + tri(r,s)] (alpha pair: row), added to what core_fold_kernel wrote:
+// h_a(p,q) += sum_C (PQ|CC), h_b(p,q) += sum_c (cc|PQ); the last wave: e_core = sum_cD (cc|DD).
+__global__ __launch_bounds__(TB) void core_fold_ab_kernel(double* __restrict__ h_a, double* __restrict__ h_b, double* __restrict__ e_core,
+                                                          const double* __restrict__ ab, int n, int nfc, int n_act)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t npa = (int64_t)n_act * (n_act + 1) / 2, np = (int64_t)n * (n + 1) / 2;
+    const int64_t w = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (w > npa) return;
+    if (w < npa) {
+        int q, p;
+        unpair(w, q, p);
+        const int64_t PQ = tri(p + nfc, q + nfc);
+        double fa = 0.0, fb = 0.0;
+        for (int64_t c = lane; c < nfc; c += 64) {
+            fa += ab[PQ * np + tri(c, c)];
+            fb += ab[tri(c, c) * np + PQ];
+        }
+        fa = wave_sum(fa);
+        fb = wave_sum(fb);
+        if (lane == 0) {
+            const int64_t lo = p + (int64_t)n_act * q, up = q + (int64_t)n_act * p;
+            const double va = h_a[lo] + fa, vb = h_b[lo] + fb;
+            h_a[lo] = va; h_a[up] = va;
+            h_b[lo] = vb; h_b[up] = vb;
+        }
+    } else {
+        double acc = 0.0;
+        for (int64_t x = lane; x < (int64_t)nfc * nfc; x += 64) acc += ab[tri(x % nfc, x % nfc) * np + tri(x / nfc, x / nfc)];
+        acc = wave_sum(acc);
+        if (lane == 0) *e_core = acc;
+    }
+}
+void k_core_fold(Context& cx, double* h_act, double* e_core, const double* hmo, const double* packed, int n, int nfc, int n_act, bool one_spin)
+{
+    const int64_t waves = (int64_t)n_act * (n_act + 1) / 2 + 1;
+    LAUNCH(core_fold_kernel, dim3((unsigned)((waves + TB / 64 - 1) / (TB / 64))), h_act, e_core, hmo, packed, n, nfc, n_act,
+           one_spin ? 1.0 : 2.0, one_spin ? 1.0 : 2.0, one_spin ? 0.5 : 1.0);
+}
+void k_core_fold_ab(Context& cx, double* h_a, double* h_b, double* e_core, const double* ab, int n, int nfc, int n_act)
+{
+    const int64_t waves = (int64_t)n_act * (n_act + 1) / 2 + 1;
+    LAUNCH(core_fold_ab_kernel, dim3((unsigned)((waves + TB / 64 - 1) / (TB / 64))), h_a, h_b, e_core, ab, n, nfc, n_act);
+}
+
+// ---- order-preserving stream compaction of an integral array (afesp_write_fcidump_active / _uactive): the elements with
+// |x| > thr as (flat index, value) pairs in rising index order, so that only they cross to the host.  A wave owns a run of
+// COMPACT_CHUNK = 64 x 32 consecutive elements (chunk c = [c CHUNK, (c + 1) CHUNK): the owner of a chunk depends on its number alone,
+// not on the grid) and walks it 64 elements at a time -- one coalesced 512-byte load per step.
+//   count:   counts[c] = sum over the steps of popcount(ballot(|x| > thr))
+//   scan:    counts -> exclusive prefix sums in place, counts[nchunks] = number of survivors (one workgroup: 1.4e5 chunks at n = 220)
+//   scatter: the same walk; a survivor's slot = prefix[c] + survivors of the earlier steps + lanes below it in this step's ballot (mbcnt)
+// A threshold of 0 keeps everything except exact zeros (and NaNs, which no comparison keeps).
+constexpr int COMPACT_ITEMS = 32;
+constexpr int64_t COMPACT_CHUNK = 64 * COMPACT_ITEMS;
+__global__ __launch_bounds__(TB) void compact_count_kernel(int64_t* __restrict__ counts, const double* __restrict__ x, int64_t total,
+                                                           int64_t nchunks, double thr)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t c = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6); c < nchunks; c += (int64_t)gridDim.x * (TB / 64)) {
+        const int64_t base = c * COMPACT_CHUNK;
+        int64_t cnt = 0;
+#pragma unroll 4
+        for (int it = 0; it < COMPACT_ITEMS; ++it) {
+            const int64_t i = base + 64 * it + lane;
+            const bool keep = i < total && fabs(x[i]) > thr;
+            cnt += __popcll(__ballot(keep));
+        }
+        if (lane == 0) counts[c] = cnt;
+    }
+}
+__global__ __launch_bounds__(TB) void compact_scan_kernel(int64_t* counts, int64_t nchunks)
+{
+    __shared__ int64_t part[TB];
+    const int64_t seg = (nchunks + TB - 1) / TB;   // thread t scans chunks [t seg, (t + 1) seg)
+    const int64_t lo = seg * threadIdx.x < nchunks ? seg * threadIdx.x : nchunks, hi = lo + seg < nchunks ? lo + seg : nchunks;
+    int64_t s = 0;
+    for (int64_t i = lo; i < hi; ++i) s += counts[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t run = 0;
+        for (int t = 0; t < TB; ++t) {
+            const int64_t v = part[t];
+            part[t] = run;
+            run += v;
+        }
+        counts[nchunks] = run;
+    }
+    __syncthreads();
+    int64_t run = part[threadIdx.x];
+    for (int64_t i = lo; i < hi; ++i) {
+        const int64_t v = counts[i];
+        counts[i] = run;
+        run += v;
+    }
+}
+__global__ __launch_bounds__(TB) void compact_scatter_kernel(int64_t* __restrict__ out_idx, double* __restrict__ out_val,
+                                                             const int64_t* __restrict__ prefix, const double* __restrict__ x, int64_t total,
+                                                             int64_t nchunks, double thr)
+{
+    const int lane = threadIdx.x & 63;
+    for (int64_t c = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6); c < nchunks; c += (int64_t)gridDim.x * (TB / 64)) {
+        const int64_t base = c * COMPACT_CHUNK;
+        int64_t off = prefix[c];
+        if (prefix[c + 1] == off) continue;   // (nothing survives in this chunk: wave-uniform)
+#pragma unroll 4
+        for (int it = 0; it < COMPACT_ITEMS; ++it) {
+            const int64_t i = base + 64 * it + lane;
+            const double v = i < total ? x[i] : 0.0;
+            const bool keep = i < total && fabs(v) > thr;
+            const unsigned long long m = __ballot(keep);
+            const int below = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+            if (keep) {
+                out_idx[off + below] = i;
+                out_val[off + below] = v;
+            }
+            off += __popcll(m);
+        }
+    }
+}
+int64_t k_compact_chunks(int64_t total) { return (total + COMPACT_CHUNK - 1) / COMPACT_CHUNK; }
+void k_compact_count(Context& cx, int64_t* counts, const double* x, int64_t total, double thr)
+{
+    const int64_t nchunks = k_compact_chunks(total);
+    if (nchunks > 0) LAUNCH(compact_count_kernel, dim3(grid_for(nchunks * 64, 65536)), counts, x, total, nchunks, thr);
+    LAUNCH(compact_scan_kernel, dim3(1), counts, nchunks);
+}
+void k_compact_scatter(Context& cx, int64_t* out_idx, double* out_val, const int64_t* prefix, const double* x, int64_t total, double thr)
+{
+    const int64_t nchunks = k_compact_chunks(total);
+    if (nchunks > 0) LAUNCH(compact_scatter_kernel, dim3(grid_for(nchunks * 64, 65536)), out_idx, out_val, prefix, x, total, nchunks, thr);
+}
+
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {
     int64_t n = (int64_t)d0 * d1 * d2 * d3;

@@ -12,6 +12,7 @@ module afesp_capi
              afesp_comm_init, afesp_comm_destroy, afesp_allreduce_sum, afesp_ccsd_t_shard_bounds, afesp_ccsd_t_block_size, &
              afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, afesp_mo_window, afesp_umo_window, &
              afesp_mp2_vv_density, afesp_ump2_vv_density, &
+             afesp_core_operator, afesp_ucore_operator, afesp_write_fcidump_active, afesp_write_fcidump_uactive, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -220,6 +221,51 @@ module afesp_capi
          real(c_double), intent(in) :: levels_a(*), levels_b(*)
          real(c_double), intent(out) :: d_a(*), d_b(*)
          real(c_double), intent(out) :: e_ump2
+         integer(c_int) :: rc
+      end function
+      !> the frozen-core operator of the window [nfc, nbasis - nfv) and the core energy from the full resident MO integrals, BEFORE the
+      !> window (include/afesp.h): h_act is n_act x n_act, symmetric to the bit; e_core is electronic
+      function afesp_core_operator(ctx, nbasis, n_frozen_core, n_frozen_virt, canon_coeff, core_hamil_ao, h_act, e_core) &
+         bind(C, name='afesp_core_operator') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, n_frozen_core, n_frozen_virt
+         real(c_double), intent(in) :: canon_coeff(*), core_hamil_ao(*)
+         real(c_double), intent(out) :: h_act(*)
+         real(c_double), intent(out) :: e_core
+         integer(c_int) :: rc
+      end function
+      function afesp_ucore_operator(ctx, nbasis, n_frozen_core, n_frozen_virt, coeff_a, coeff_b, core_hamil_ao, h_act_a, h_act_b, &
+                                    e_core) bind(C, name='afesp_ucore_operator') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, n_frozen_core, n_frozen_virt
+         real(c_double), intent(in) :: coeff_a(*), coeff_b(*), core_hamil_ao(*)
+         real(c_double), intent(out) :: h_act_a(*), h_act_b(*)
+         real(c_double), intent(out) :: e_core
+         integer(c_int) :: rc
+      end function
+      !> the integrals resident for n_act orbitals as a standard FCIDUMP (header, two-electron, one-electron, core energy: include/afesp.h)
+      function afesp_write_fcidump_active(ctx, path, n_act, nelec_act, ms2, h_act, e_core_total, threshold, nwritten) &
+         bind(C, name='afesp_write_fcidump_active') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), value :: n_act, nelec_act, ms2
+         real(c_double), intent(in) :: h_act(*)
+         real(c_double), value :: e_core_total, threshold
+         integer(c_int64_t), intent(out) :: nwritten
+         integer(c_int) :: rc
+      end function
+      function afesp_write_fcidump_uactive(ctx, path, n_act, nalpha_act, nbeta_act, h_act_a, h_act_b, e_core_total, threshold, &
+                                           nwritten) bind(C, name='afesp_write_fcidump_uactive') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), value :: n_act, nalpha_act, nbeta_act
+         real(c_double), intent(in) :: h_act_a(*), h_act_b(*)
+         real(c_double), value :: e_core_total, threshold
+         integer(c_int64_t), intent(out) :: nwritten
          integer(c_int) :: rc
       end function
       !> replaces write_fcidump (reference src/mp2.f90:451-487)

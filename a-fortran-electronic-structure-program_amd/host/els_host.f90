@@ -35,6 +35,7 @@ module host_config
       real(dp) :: scf_e_tol = 1e-6_dp, scf_d_tol = 1e-6_dp, ccsd_e_tol = 1e-6_dp, ccsd_t_tol = 1e-6_dp
       integer :: scf_diis_n_errmat = 6, ccsd_diis_n_errmat = 8, scf_maxiter = 50, ccsd_maxiter = 50
       logical :: write_fcidump = .false., scf_read_guess = .false., scf_write_guess = .false.
+      logical :: fcidump_active = .false.   ! the space the solvers run in as a standard FCIDUMP (header, frozen-core operator, core energy)
       integer :: level = LEVEL_CCSD_T
       logical :: paren = .false., renorm = .false., comp_renorm = .false.
       logical :: spinorb = .false.   ! the _spinorb calculation types (reference src/system.f90:117-137)
@@ -57,10 +58,10 @@ contains
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt
       real(dp) :: fno_occ_tol
-      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core
+      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
-         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol
+         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -68,7 +69,7 @@ contains
       scf_read_guess = d%scf_read_guess; scf_write_guess = d%scf_write_guess
       charge = d%charge; multiplicity = d%multiplicity
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
-      fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol
+      fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -84,6 +85,9 @@ contains
       if (n_frozen_core < -1 .or. n_frozen_virt < -1) &
          call fail('system::read_system_in', 'n_frozen_core and n_frozen_virt must be non-negative integers!')
       cfg%fno_n_virt = fno_n_virt; cfg%fno_occ_tol = fno_occ_tol
+      cfg%fcidump_active = fcidump_active
+      if (fcidump_active .and. write_fcidump) &
+         call fail('system::read_system_in', 'write_fcidump and fcidump_active both write FCIDUMP: choose one')
       if (fno_n_virt < -1) call fail('system::read_system_in', 'fno_n_virt must be a non-negative integer!')
       if (fno_occ_tol < 0.0_dp) call fail('system::read_system_in', 'fno_occ_tol must be a non-negative number!')
       if (fno_n_virt >= 0 .and. fno_occ_tol > 0.0_dp) &
@@ -643,6 +647,9 @@ program els_amd
    logical :: fno
    integer :: fno_kept, vmin
    real(dp) :: e_mp2_full, delta_mp2
+   ! fcidump_active: the frozen-core operator(s) of the window and the core energy, taken before the window
+   real(dp), allocatable :: h_act(:, :), h_act_b(:, :)
+   real(dp) :: e_core
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
    integer(c_int) :: rc, conv
@@ -657,6 +664,7 @@ program els_amd
    integer(c_int64_t) :: nlines
    character(len=32) :: envval
    character(len=80) :: calcname
+   real(dp), parameter :: fcidump_threshold = 1e-12_dp   ! fcidump_active keeps every integral above this (16 digits are written)
 
    tstart = seconds()
    ! Rank mode (one process per GPU, started by host/els_mgpu.sh or any launcher that sets these): AFESP_RANK / AFESP_WORLD,
@@ -681,7 +689,7 @@ program els_amd
    write (out, '(1X, 64("="))')
    call read_config(cfg)
    if (rank > 0) then   ! every rank runs the replicated stages in the same directory: the files are rank 0's to write
-      cfg%scf_write_guess = .false.; cfg%write_fcidump = .false.
+      cfg%scf_write_guess = .false.; cfg%write_fcidump = .false.; cfg%fcidump_active = .false.
    end if
    ! Post-HF levels: the engine context exists from the start, and the engine reads eri.dat (the packed AO integrals
    ! then stay on the device for the AO->MO transform; the host copy feeds the SCF)
@@ -788,11 +796,13 @@ program els_amd
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
       if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
       if (fno) call open_shell_fno()   ! natural virtuals of both spins, second transform; sets nfv and the active extents
+      if (cfg%fcidump_active) call core_operator_before_window()
       if (windowed .or. fno) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
          rc = afesp_umo_window(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), &
                                int(nfv, c_int64_t), levels, lb, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
       end if
+      if (cfg%fcidump_active) call dump_active_space()
       write (out, '(1X, A, 1X, F15.8)') 'UMP2 correlation energy (Hartree):', e_mp2
       if (fno) call print_fno_energies('UMP2')
       e_highest = e_mp2
@@ -863,6 +873,7 @@ program els_amd
          if (cfg%write_fcidump) call dump_integrals()
          call closed_shell_fno()
       end if
+      if (cfg%fcidump_active) call core_operator_before_window()
       if (windowed .or. fno) then
          ! frozen orbitals: the FCIDUMP (if asked for) is of the full integrals; then the window over the active orbitals replaces
          ! them on the device, and the MP2 energy is the frozen-core one
@@ -871,6 +882,7 @@ program els_amd
                               levels, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
       end if
+      if (cfg%fcidump_active) call dump_active_space()
       write (out, '(1X, A)') 'Calculating MP2 energy...'
       write (out, '(1X, A, 1X, F15.8)') 'MP2 correlation energy (Hartree):', e_mp2
       if (fno) call print_fno_energies('MP2')
@@ -1238,6 +1250,38 @@ contains
       rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, dummy)
       if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+   end subroutine
+   !> fcidump_active, first half: the frozen-core operator of the window and the core energy from the full MO integrals of the (last)
+   !> transform -- before the window, which throws the core orbitals away (with natural virtuals: in the rotated orbitals)
+   subroutine core_operator_before_window()
+      allocate (h_act(n_act, n_act))
+      if (cfg%uhf) then
+         allocate (h_act_b(n_act, n_act))
+         rc = afesp_ucore_operator(ctx, int(mol%nbasis, c_int64_t), int(nfc, c_int64_t), int(nfv, c_int64_t), coeff, cb, mol%hcore, &
+                                   h_act, h_act_b, e_core)
+      else
+         rc = afesp_core_operator(ctx, int(mol%nbasis, c_int64_t), int(nfc, c_int64_t), int(nfv, c_int64_t), coeff, mol%hcore, h_act, &
+                                  e_core)
+      end if
+      if (rc /= 0) call fail('mp2::write_fcidump_active', afesp_error_text(ctx))
+   end subroutine
+   !> second half: the integrals the solvers then run on (the window, or the whole basis), h_act and e_core + E_nuc as a standard FCIDUMP
+   subroutine dump_active_space()
+      write (out, '(1X, A)') 'Writing FCIDUMP file (active space)...'
+      if (cfg%uhf) then
+         rc = afesp_write_fcidump_uactive(ctx, 'FCIDUMP'//c_null_char, int(n_act, c_int64_t), int(na_act, c_int64_t), &
+                                          int(nb_act, c_int64_t), h_act, h_act_b, e_core + mol%e_nuc, fcidump_threshold, nlines)
+         if (rc /= 0) call fail('mp2::write_fcidump_active', afesp_error_text(ctx))
+         write (out, '(1X, A, I0, A, I0, A, I0, A, F18.10)') 'FCIDUMP: NORB ', 2*n_act, ', NELEC ', na_act + nb_act, ', lines ', nlines, &
+            ', core energy ', e_core + mol%e_nuc
+      else
+         rc = afesp_write_fcidump_active(ctx, 'FCIDUMP'//c_null_char, int(n_act, c_int64_t), int(nel_act, c_int64_t), 0_c_int64_t, &
+                                         h_act, e_core + mol%e_nuc, fcidump_threshold, nlines)
+         if (rc /= 0) call fail('mp2::write_fcidump_active', afesp_error_text(ctx))
+         write (out, '(1X, A, I0, A, I0, A, I0, A, F18.10)') 'FCIDUMP: NORB ', n_act, ', NELEC ', nel_act, ', lines ', nlines, &
+            ', core energy ', e_core + mol%e_nuc
+      end if
+      write (out, '(1X, A)') 'Done writing FCIDUMP file!'
    end subroutine
    !> FCIDUMP of the MO integrals resident after the AO->MO transform (reference src/mp2.f90:445-447)
    subroutine dump_integrals()

@@ -235,6 +235,47 @@ int afesp_mp2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n
 int afesp_ump2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, int64_t n_frozen_core, const double* levels_a,
                           const double* levels_b, double* d_a, double* d_b, double* e_ump2);
 
+/* The active space as a Hamiltonian on disk (the reference's write_fcidump has no header, no one-electron part and no
+ * window).  Two steps: the frozen-core operator BEFORE the window (the window throws the core orbitals away), the file AFTER it.
+ *
+ * afesp_core_operator / afesp_ucore_operator act on the full MO integrals a transform left resident.  c, d run over the n_frozen_core
+ * lowest orbitals, p, q over the active window [n_frozen_core, nbasis - n_frozen_virt); h_mo = C h_ao C^T with C (MO, AO) as canon_coeff:
+ *   closed shell:  h_act(p,q) = h_mo(p,q) + sum_c [2 (pq|cc) - (pc|qc)]
+ *                  e_core     = 2 sum_c h_mo(c,c) + sum_cd [2 (cc|dd) - (cd|cd)]
+ *   open shell:    h_act_a(p,q) = h_mo_a(p,q) + sum_{c in alpha} [(pq|cc) - (pc|qc)]_aa + sum_{C in beta} (pq|CC)_ab;  h_act_b: the mirror image
+ *                  e_core = sum_c h_a(c,c) + sum_C h_b(C,C) + 1/2 sum_cd [(cc|dd) - (cd|cd)]_aa + 1/2 sum_CD [...]_bb + sum_cD (cc|DD)_ab
+ *   in : canon_coeff / coeff_a / coeff_b [n*n] (MO, AO), core_hamil_ao [n*n];   out: h_act [n_act*n_act] column-major, symmetric to the
+ *        bit; *e_core electronic (the caller adds the nuclear repulsion).  n_frozen_core = 0 is legal: the window of h_mo, e_core = 0.
+ * h_mo runs through the GEMM layer; one wave per active pair gathers the core's field out of the packed arrays in a fixed order.
+ * Every resident array is left untouched.  Status 1, nothing touched: a negative count, no active orbital left, a NULL argument,
+ * nothing resident for nbasis (so also after a window).
+ *
+ * afesp_write_fcidump_active / _uactive write whatever is resident for n_act orbitals -- the window after afesp_mo_window /
+ * afesp_umo_window, the full basis without one -- as a standard FCIDUMP.  The integrals with |value| > threshold are compacted on the
+ * device in canonical order (threshold = 0: everything except exact zeros), only they cross to the host, which formats them (on up to 16
+ * threads; the file is the same bytes run to run).  *nwritten (may be NULL) = the number of lines after the header.  Format:
+ *    &FCI NORB=<n>,NELEC=<nelec>,MS2=<ms2>,
+ *     ORBSYM=1,1,...,1,
+ *     ISYM=1,
+ *    &END
+ *    <value> <i> <j> <k> <l>
+ * the value as %23.15E, four blank-separated 1-based indices, chemists' notation (ij|kl).  First the two-electron lines in the canonical
+ * order of the packed array (i >= j, k >= l, ij >= kl), then h(i,j) i j 0 0 for i >= j with |h| > threshold, last e_core_total 0 0 0 0
+ * (always written; e_core plus the nuclear repulsion).
+ * Open shell: the header gains the line UHF=.TRUE., ; NORB = 2 n_act spin orbitals, NELEC = nalpha_act + nbeta_act, MS2 their difference;
+ * indices are spin-orbital numbers, interleaved as on the spin-orbital path above: spatial orbital p (1-based) is 2p - 1 for alpha and 2p
+ * for beta.  Blocks in this order: alpha-alpha (8-fold unique), beta-beta (8-fold unique), alpha-beta (every p >= q, r >= s, once, as
+ * (p_a q_a | r_b s_b)), h_alpha, h_beta, the core energy.  Spin-forbidden integrals are never written.
+ * Status 1: a NULL path or matrix, a negative threshold, nothing resident for n_act. */
+int afesp_core_operator(afesp_ctx* ctx, int64_t nbasis, int64_t n_frozen_core, int64_t n_frozen_virt, const double* canon_coeff,
+                        const double* core_hamil_ao, double* h_act, double* e_core);
+int afesp_ucore_operator(afesp_ctx* ctx, int64_t nbasis, int64_t n_frozen_core, int64_t n_frozen_virt, const double* coeff_a,
+                         const double* coeff_b, const double* core_hamil_ao, double* h_act_a, double* h_act_b, double* e_core);
+int afesp_write_fcidump_active(afesp_ctx* ctx, const char* path, int64_t n_act, int64_t nelec_act, int64_t ms2, const double* h_act,
+                               double e_core_total, double threshold, int64_t* nwritten);
+int afesp_write_fcidump_uactive(afesp_ctx* ctx, const char* path, int64_t n_act, int64_t nalpha_act, int64_t nbeta_act, const double* h_act_a,
+                                const double* h_act_b, double e_core_total, double threshold, int64_t* nwritten);
+
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
  * every rank evaluates its shard [bounds[r], bounds[r+1]) of the triple list (afesp_ccsd_t_shard_bounds) and that
