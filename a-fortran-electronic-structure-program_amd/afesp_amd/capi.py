@@ -6,6 +6,7 @@ There is no CPU fallback: if the shared library is missing, or no GPU is visible
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -33,6 +34,7 @@ EXPORTS = [
     "afesp_build_fock_uhf", "afesp_ao2mo_ump2", "afesp_ccsd_uso_init", "afesp_mo_window", "afesp_umo_window",
     "afesp_mp2_vv_density", "afesp_ump2_vv_density",
     "afesp_core_operator", "afesp_ucore_operator", "afesp_write_fcidump_active", "afesp_write_fcidump_uactive",
+    "afesp_fcidump_scan", "afesp_read_fcidump", "afesp_read_fcidump_uhf",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -118,6 +120,10 @@ def load_library():
     L.afesp_ucore_operator.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, _dp, _dp, C.POINTER(dbl)]
     L.afesp_write_fcidump_active.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64, _dp, dbl, dbl, C.POINTER(i64)]
     L.afesp_write_fcidump_uactive.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64, _dp, _dp, dbl, dbl, C.POINTER(i64)]
+    L.afesp_fcidump_scan.argtypes = [C.c_char_p, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_int), C.POINTER(i64)]
+    L.afesp_read_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, i64, _opt, _opt, _opt, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), _opt,
+                                     C.POINTER(i64)]
+    L.afesp_read_fcidump_uhf.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64] + [_opt] * 6 + [C.POINTER(dbl)] * 3 + [_opt] * 3 + [C.POINTER(i64)]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -150,6 +156,63 @@ TENSOR_SHAPES = {
     "I_oooo": "oooo", "I_ovov": "ovov", "I_voov": "voov", "I_vovv_p": "vovv", "I_ooov_p": "ooov", "r1": "ov",
     "r2": "oovv", "D1": "ov", "D2": "oovv", "t1": "ov", "t2": "oovv",
 }
+
+
+@dataclasses.dataclass
+class FcidumpHeader:
+    norb: int       # as the header says: spatial orbitals, or spin orbitals with uhf
+    nelec: int
+    ms2: int
+    uhf: bool
+    nlines: int     # non-blank lines after the header
+
+
+@dataclasses.dataclass
+class FcidumpIn:
+    """What Engine.read_fcidump returns.  Closed shell: h / fock / levels; open shell: the _a / _b pairs.  Matrices are [n, n] over the
+    n spatial orbitals of the file and symmetric to the bit; the eri_* arrays are there with want_eri=True."""
+    norb: int
+    nelec: int
+    ms2: int
+    uhf: bool
+    e_core: float
+    e_ref: float
+    fock_offdiag: float
+    nread: int
+    h: np.ndarray | None = None
+    fock: np.ndarray | None = None
+    levels: np.ndarray | None = None
+    h_a: np.ndarray | None = None
+    h_b: np.ndarray | None = None
+    fock_a: np.ndarray | None = None
+    fock_b: np.ndarray | None = None
+    levels_a: np.ndarray | None = None
+    levels_b: np.ndarray | None = None
+    eri: np.ndarray | None = None
+    eri_aa: np.ndarray | None = None
+    eri_ab: np.ndarray | None = None      # [npair, npair], row: alpha pair
+    eri_bb: np.ndarray | None = None
+
+    @property
+    def nspatial(self) -> int:
+        return self.norb // 2 if self.uhf else self.norb
+
+    @property
+    def nalpha(self) -> int:
+        return (self.nelec + self.ms2) // 2
+
+    @property
+    def nbeta(self) -> int:
+        return (self.nelec - self.ms2) // 2
+
+
+def scan_fcidump(path) -> FcidumpHeader:
+    """The header of a FCIDUMP and the number of lines after it (afesp_fcidump_scan: host only, no GPU context)."""
+    norb, nelec, ms2, uhf, nl = i64(), i64(), i64(), C.c_int(), i64()
+    rc = load_library().afesp_fcidump_scan(str(path).encode(), C.byref(norb), C.byref(nelec), C.byref(ms2), C.byref(uhf), C.byref(nl))
+    if rc != 0:
+        raise AfespError(f"status {rc}: afesp_fcidump_scan: {path} is unreadable or has no &FCI ... &END header with NORB and NELEC")
+    return FcidumpHeader(norb.value, nelec.value, ms2.value, bool(uhf.value), nl.value)
 
 
 def device_count():
@@ -512,6 +575,45 @@ class Engine:
         self._chk(self.L.afesp_write_fcidump_uactive(self.h, str(path).encode(), n_act, nalpha_act, nbeta_act, _f(h_act_a), _f(h_act_b),
                                                      e_core_total, threshold, C.byref(n)))
         return n.value
+
+    # ---- a standard FCIDUMP as input
+    def read_fcidump(self, path, canonical_tol=1e-6, want_eri=False) -> FcidumpIn:
+        """Reads a FCIDUMP onto the device (afesp_read_fcidump, or afesp_read_fcidump_uhf where the header says UHF=.TRUE.): the integrals
+        are then resident as do_mp2_spatial / do_ump2 leave theirs, the orbitals in file order with the first nelec / 2 (nalpha, nbeta)
+        occupied.  Raises AfespError where max |F(p,q)|, p != q, exceeds canonical_tol (the solvers assume canonical orbitals);
+        canonical_tol=None skips that check."""
+        hd = scan_fcidump(path)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        ec, er, fo, nr = dbl(0.0), dbl(0.0), dbl(0.0), i64()
+        if not hd.uhf:
+            if hd.nelec % 2 or hd.ms2 != 0:
+                raise AfespError("status 1: read_fcidump: an open shell without UHF=.TRUE. (restricted open-shell orbitals are not supported)")
+            n, o = hd.norb, hd.nelec // 2
+            h, f, lev = np.zeros(n * n), np.zeros(n * n), np.zeros(n)
+            eri = np.zeros(self.L.afesp_neri(n)) if want_eri else None
+            self._chk(self.L.afesp_read_fcidump(self.h, str(path).encode(), n, o, vp(h), vp(f), vp(lev), C.byref(ec), C.byref(er), C.byref(fo),
+                                                vp(eri) if want_eri else None, C.byref(nr)))
+            out = FcidumpIn(hd.norb, hd.nelec, hd.ms2, False, ec.value, er.value, fo.value, nr.value, h=h.reshape((n, n), order="F"),
+                            fock=f.reshape((n, n), order="F"), levels=lev, eri=eri)
+        else:
+            if hd.norb % 2 or (hd.nelec + hd.ms2) % 2:
+                raise AfespError("status 1: read_fcidump: UHF=.TRUE. with an odd NORB, or NELEC and MS2 of different parity")
+            n, na, nb = hd.norb // 2, (hd.nelec + hd.ms2) // 2, (hd.nelec - hd.ms2) // 2
+            m = [np.zeros(n * n) for _ in range(4)]
+            la, lb = np.zeros(n), np.zeros(n)
+            ne, npair = self.L.afesp_neri(n), n * (n + 1) // 2
+            aa, bb, ab = (np.zeros(ne), np.zeros(ne), np.zeros(npair * npair)) if want_eri else (None, None, None)
+            e = lambda a: vp(a) if want_eri else None
+            self._chk(self.L.afesp_read_fcidump_uhf(self.h, str(path).encode(), n, na, nb, vp(m[0]), vp(m[1]), vp(m[2]), vp(m[3]), vp(la), vp(lb),
+                                                    C.byref(ec), C.byref(er), C.byref(fo), e(aa), e(ab), e(bb), C.byref(nr)))
+            sq = lambda a: a.reshape((n, n), order="F")
+            out = FcidumpIn(hd.norb, hd.nelec, hd.ms2, True, ec.value, er.value, fo.value, nr.value, h_a=sq(m[0]), h_b=sq(m[1]), fock_a=sq(m[2]),
+                            fock_b=sq(m[3]), levels_a=la, levels_b=lb, eri_aa=aa, eri_bb=bb,
+                            eri_ab=ab.reshape((npair, npair)) if want_eri else None)
+        if canonical_tol is not None and not out.fock_offdiag <= canonical_tol:
+            raise AfespError(f"status 1: read_fcidump: the orbitals of {path} are not canonical: max |F(p,q)|, p != q, is "
+                             f"{out.fock_offdiag:.3e}, above {canonical_tol:.1e} (the integrals are resident all the same)")
+        return out
 
     # ---- spin-orbital path: do_ccsd_spinorb (src/ccsd.f90:71-277), do_ccsd_t_spinorb (:1812-1922)
     SO_SHAPES = {"F_vv": "vv", "F_oo": "oo", "F_ov": "ov", "W_oooo": "oooo", "W_vvvv": "vvvv", "W_ovvo": "ovvo", "tau": "oovv",

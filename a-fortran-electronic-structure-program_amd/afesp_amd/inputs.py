@@ -31,6 +31,7 @@ class SystemIn:
     ccsd_maxiter: int = 50
     write_fcidump: bool = False
     fcidump_active: bool = False    # the active space as a standard FCIDUMP (afesp_amd/fcidump.py); excludes write_fcidump (same file name)
+    fcidump_in: bool = False        # MO integrals from ./FCIDUMP (Engine.read_fcidump): no SCF, no transform; excludes what needs AO data
     scf_read_guess: bool = False
     scf_write_guess: bool = False
     charge: int = 0                 # open-shell types only (UHF_scf, UMP2, UCCSD, UCCSD(T))
@@ -114,6 +115,19 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("invalid input file format!")
     if sysin.fcidump_active and sysin.write_fcidump:
         raise ValueError("write_fcidump and fcidump_active both write FCIDUMP: choose one!")
+    if not isinstance(sysin.fcidump_in, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.fcidump_in:
+        if sysin.frozen_core:
+            raise ValueError("fcidump_in: frozen_core counts atoms in geom.dat, which is not read: give n_frozen_core!")
+        if fno_requested(sysin):
+            raise ValueError("fcidump_in: frozen natural orbitals need the AO integrals, which are not read!")
+        if sysin.write_fcidump or sysin.fcidump_active:
+            raise ValueError("fcidump_in reads FCIDUMP: write_fcidump / fcidump_active would overwrite it!")
+        if sysin.scf_read_guess or sysin.scf_write_guess:
+            raise ValueError("fcidump_in runs no SCF: scf_read_guess / scf_write_guess have nothing to act on!")
+        if sysin.level in ("RHF", "UHF"):
+            raise ValueError("fcidump_in runs no SCF: choose a correlated calculation type!")
     for key in ("n_frozen_core", "n_frozen_virt"):
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < -1:

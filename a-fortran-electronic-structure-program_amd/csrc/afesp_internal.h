@@ -306,6 +306,24 @@ void k_core_fold_ab(Context& cx, double* h_a, double* h_b, double* e_core, const
 int64_t k_compact_chunks(int64_t total);
 void k_compact_count(Context& cx, int64_t* counts, const double* x, int64_t total, double thr);
 void k_compact_scatter(Context& cx, int64_t* out_idx, double* out_val, const int64_t* prefix, const double* x, int64_t total, double thr);
+
+// The FCIDUMP reader (afesp_read_fcidump / _uhf).  k_fcidump_scatter: `count` records (device copy of fcidump_parse.h's
+// Record) into the targets, three launches: duplicates of earlier chunks checked against the visited map, stores, read-back; conflicting
+// duplicates are counted in err[0], the smallest offending line number lands in err[1].  k_fock_mo: F = h + sum_{i < nocc} [wj (pq|ii) -
+// (pi|qi)] over all n orbitals, one wave per pair, symmetric to the bit; k_fock_mo_ab adds the opposite-spin Coulomb terms to both spins.
+namespace fcidump { struct Record; }
+struct FcidumpTargets {
+    double* eri[3];              // closed shell: [0] packed; open shell: aa, bb packed, ab npair x npair (row: alpha pair)
+    double* h[2];                // n x n (open shell: alpha, beta)
+    double* ecore;
+    uint32_t* visited;           // one bit per slot
+    unsigned long long* err;     // [0] conflicting duplicates, [1] smallest line number among them
+    int64_t n, np, ne, nslots;   // spatial orbitals, npair, neri, number of slots (the core energy is the last one)
+    int uhf;
+};
+void k_fcidump_scatter(Context& cx, const FcidumpTargets& T, const fcidump::Record* rec, int64_t count);
+void k_fock_mo(Context& cx, double* F, const double* h, const double* packed, int n, int nocc, double wj);
+void k_fock_mo_ab(Context& cx, double* fa, double* fb, const double* ab, int n, int na, int nb);
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);

@@ -749,6 +749,51 @@ int afesp_write_fcidump_uactive(afesp_ctx* ctx, const char* path, int64_t n_act,
     });
 }
 
+// ---------------------------------------------------------------- a standard FCIDUMP as input
+int afesp_fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines)
+{
+    try {
+        return fcidump_scan(path, norb, nelec, ms2, uhf, nlines);
+    } catch (const std::exception&) {
+        return 1;
+    }
+}
+
+int afesp_read_fcidump(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nocc, double* h_mo, double* fock, double* levels,
+                       double* e_core, double* e_ref, double* fock_offdiag, double* eri_mo_packed, int64_t* nread)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (!path) throw Error(1, "afesp_read_fcidump: path is NULL");
+        if (nbasis <= 0 || nbasis > 1024 || nocc < 0 || nocc > nbasis) throw Error(1, "afesp_read_fcidump: bad extents");
+        FcidumpResult r;
+        r.h[0] = h_mo; r.fock[0] = fock; r.levels[0] = levels; r.eri[0] = eri_mo_packed;
+        read_fcidump(cx, ctx->in, ctx->cc, path, nbasis, nocc, r);
+        if (e_core) *e_core = r.e_core;
+        if (e_ref) *e_ref = r.e_ref;
+        if (fock_offdiag) *fock_offdiag = r.fock_offdiag;
+        if (nread) *nread = r.nread;
+    });
+}
+
+int afesp_read_fcidump_uhf(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nalpha, int64_t nbeta, double* h_a, double* h_b,
+                           double* fock_a, double* fock_b, double* levels_a, double* levels_b, double* e_core, double* e_ref,
+                           double* fock_offdiag, double* eri_aa, double* eri_ab, double* eri_bb, int64_t* nread)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (!path) throw Error(1, "afesp_read_fcidump_uhf: path is NULL");
+        if (nbasis <= 0 || nbasis > 1024 || nalpha < 0 || nbeta < 0 || nalpha > nbasis || nbeta > nbasis)
+            throw Error(1, "afesp_read_fcidump_uhf: bad extents");
+        FcidumpResult r;
+        r.h[0] = h_a; r.h[1] = h_b; r.fock[0] = fock_a; r.fock[1] = fock_b; r.levels[0] = levels_a; r.levels[1] = levels_b;
+        r.eri[0] = eri_aa; r.eri[1] = eri_bb; r.eri[2] = eri_ab;
+        read_fcidump_uhf(cx, ctx->in, path, nbasis, nalpha, nbeta, r);
+        if (e_core) *e_core = r.e_core;
+        if (e_ref) *e_ref = r.e_ref;
+        if (fock_offdiag) *fock_offdiag = r.fock_offdiag;
+        if (nread) *nread = r.nread;
+    });
+}
+
 // ---------------------------------------------------------------- spin-orbital path
 int afesp_ccsd_so_init(afesp_ctx* ctx, int64_t nbasis, int64_t nel, const double* eri_mo_packed, const double* canon_levels,
                        int diis_n_errmat, int flags)

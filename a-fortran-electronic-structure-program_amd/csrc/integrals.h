@@ -54,6 +54,7 @@ struct Integrals {
     void zero_padding(Context& cx, double* a, double* b, int64_t n, int64_t ld);
     void release_uhf(Context& cx);
     void adopt_uhf(Context& cx, int64_t n);            // the three blocks for basis size n (kept where they are of that size)
+    void swap_uhf(Context& cx, double* aa, double* bb, double* ab, int64_t n);   // three filled blocks take the resident ones' place (afesp_read_fcidump_uhf)
     void window_uhf(Context& cx, int64_t n_act, int64_t lo);   // the orbitals [lo, lo + n_act) of the three blocks, as afesp_mo_window's of mo
     void drop_mo(Context& cx, CCState& cc);            // back to the arena; a solver state initialised from them can no longer form <ef|ab>
     double* replace_mo(Context& cx, CCState& cc, int64_t n);   // the array a transform writes: the resident one if it has the size
@@ -89,6 +90,19 @@ int64_t write_fcidump_active(Context& cx, const Integrals& in, const char* path,
                              double e_core_total, double threshold);
 int64_t write_fcidump_uactive(Context& cx, const Integrals& in, const char* path, int64_t n_act, int64_t nalpha, int64_t nbeta,
                               const double* h_act_a, const double* h_act_b, double e_core_total, double threshold);
+// A standard FCIDUMP as input: fcidump_scan is host only (the header and the number of non-blank lines after it);
+// read_fcidump / _uhf parse the file chunk by chunk on the host (fcidump_parse.h), scatter the records on the device into NEW arrays and
+// make them resident -- as ao2mo_mp2 / ao2mo_ump2 leave theirs -- only when the whole file was good; every pointer of the result may be
+// null and none is written on failure.  Orbitals in file order, the first nocc (nalpha / nbeta) occupied.
+struct FcidumpResult {
+    double *h[2] = {nullptr, nullptr}, *fock[2] = {nullptr, nullptr}, *levels[2] = {nullptr, nullptr};   // closed shell: [0]; open shell: alpha, beta
+    double* eri[3] = {nullptr, nullptr, nullptr};   // packed | aa, bb, ab
+    double e_core = 0.0, e_ref = 0.0, fock_offdiag = 0.0;
+    int64_t nread = 0;
+};
+int fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines);
+void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r);
+void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
 int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
 

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "fcidump_format.h"
+#include "fcidump_parse.h"
 #include "integrals.h"
 #include "tgemm.h"
 
@@ -456,6 +457,13 @@ void Integrals::window_uhf(Context& cx, int64_t n_act, int64_t lo)
     uhf_n = n_act;
 }
 
+void Integrals::swap_uhf(Context& cx, double* aa, double* bb, double* ab, int64_t n)
+{
+    release_uhf(cx);
+    uhf_aa = aa; uhf_bb = bb; uhf_ab = ab;
+    uhf_n = n;
+}
+
 void Integrals::drop_mo(Context& cx, CCState& cc)
 {
     if (cc.eri_src == mo) cc.eri_src = nullptr;
@@ -818,6 +826,251 @@ int64_t write_fcidump_uactive(Context& cx, const Integrals& in, const char* path
     out.f = nullptr;
     if (fclose(f) != 0) throw Error(2, std::string(who) + ": write failed");
     return lines;
+}
+
+// ---- a standard FCIDUMP as input: text -> records on the host (fcidump_parse.h), records -> slots on the device
+namespace {
+// the header (fcidump_parse.h: read_header); leaves the file positioned at the body
+void fcidump_open_header(FILE* f, const char* who, const char* path, fcidump::Header& h)
+{
+    std::string why;
+    if (!fcidump::read_header(f, h, why)) throw Error(1, std::string(who) + ": " + why + " in " + path);
+}
+// everything a read allocates: back to the arena / the driver on every path, after the stream has drained
+struct ReadScratch {
+    Context& cx;
+    std::vector<void*> dev;
+    void* pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    explicit ReadScratch(Context& c) : cx(c) {}
+    double* get(int64_t ndoubles)
+    {
+        double* p = cx.alloc_raw(ndoubles);
+        dev.push_back(p);
+        return p;
+    }
+    void keep(void* p)   // the caller takes it over
+    {
+        for (void*& q : dev)
+            if (q == p) q = nullptr;
+    }
+    ~ReadScratch()
+    {
+        (void)hipStreamSynchronize(cx.stream);
+        for (void* p : dev) {
+            try {
+                if (p) cx.release(p);
+            } catch (...) {
+            }
+        }
+        for (int b = 0; b < 2; ++b) {
+            if (pinned[b]) (void)hipHostFree(pinned[b]);
+            if (ev[b]) (void)hipEventDestroy(ev[b]);
+        }
+    }
+};
+struct FcidumpRead {
+    double e_core = 0.0;
+    int64_t nread = 0;
+};
+// The body of `f` into the targets (zeroed here).  Throws status 1 with the line number for everything the file can do wrong.
+FcidumpRead fcidump_read_body(Context& cx, ReadScratch& rs, FILE* f, const char* who, const fcidump::Header& h, FcidumpTargets& T)
+{
+    const size_t chunk = (size_t)knobs().fcidump_chunk_kib << 10;
+    const int64_t max_rec = (int64_t)(chunk / 8 + 2);
+    for (int b = 0; b < 2; ++b) {
+        AFESP_HIP(hipHostMalloc(&rs.pinned[b], (size_t)max_rec * sizeof(fcidump::Record), hipHostMallocDefault));
+        AFESP_HIP(hipEventCreateWithFlags(&rs.ev[b], hipEventDisableTiming));
+    }
+    fcidump::Record* rec_dev = reinterpret_cast<fcidump::Record*>(rs.get(max_rec * 4));
+    T.visited = reinterpret_cast<uint32_t*>(rs.get((T.nslots + 63) / 64 + 1));
+    T.err = reinterpret_cast<unsigned long long*>(rs.get(2));
+    AFESP_HIP(hipMemsetAsync(T.visited, 0, (size_t)((T.nslots + 63) / 64 + 1) * 8, cx.stream));
+    const unsigned long long err0[2] = {0ull, ~0ull};
+    AFESP_HIP(hipMemcpyAsync(T.err, err0, sizeof(err0), hipMemcpyHostToDevice, cx.stream));
+    cx.sync();   // (err0 is on this frame)
+    FcidumpRead out;
+    bool used[2] = {false, false};
+    // the chunk loop is fcidump_parse.h's: the host parses round k + 1 into one pinned buffer while the device scatters round k
+    const fcidump::ParseError perr = fcidump::read_body(
+        f, h, chunk, fcidump::reader_threads(),
+        [&](int b) {
+            if (used[b]) AFESP_HIP(hipEventSynchronize(rs.ev[b]));   // the copy out of this buffer two rounds ago
+            return static_cast<fcidump::Record*>(rs.pinned[b]);
+        },
+        [&](const fcidump::Record* rec, int64_t count, int b) {
+            AFESP_HIP(hipMemcpyAsync(rec_dev, rec, (size_t)count * sizeof(fcidump::Record), hipMemcpyHostToDevice, cx.stream));
+            AFESP_HIP(hipEventRecord(rs.ev[b], cx.stream));
+            used[b] = true;
+            k_fcidump_scatter(cx, T, rec_dev, count);
+        },
+        &out.nread);
+    if (perr.line) throw Error(1, std::string(who) + ": line " + std::to_string(perr.line) + ": " + perr.why);
+    if (ferror(f)) throw Error(1, std::string(who) + ": read error");
+    unsigned long long err[2] = {0, 0};
+    AFESP_HIP(hipMemcpyAsync(err, T.err, sizeof(err), hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(&out.e_core, T.ecore, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    if (err[0])
+        throw Error(1, std::string(who) + ": line " + std::to_string(err[1]) + ": a duplicate that disagrees with another line for the same integral (" +
+                           std::to_string(err[0]) + " mismatches)");
+    return out;
+}
+void fcidump_fit(Context& cx, const char* who, double ndoubles)
+{
+    size_t free_b = 0, total_b = 0;
+    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (8.0 * ndoubles > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+        throw Error(1, std::string(who) + ": the integrals of this file do not fit the free device memory");
+}
+double offdiag_max(const double* F, int64_t n)
+{
+    double m = 0.0;
+    for (int64_t q = 0; q < n; ++q)
+        for (int64_t p = 0; p < n; ++p)
+            if (p != q) m = std::max(m, std::fabs(F[p + n * q]));
+    return m;
+}
+}  // namespace
+
+int fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines)
+{
+    if (!path) return 1;
+    File in(fopen(path, "rb"));
+    if (!in.f) return 1;
+    fcidump::Header h;
+    try {
+        fcidump_open_header(in.f, "afesp_fcidump_scan", path, h);
+    } catch (const std::exception&) {
+        return 1;
+    }
+    int64_t lines = 0;
+    std::vector<char> blk(1 << 20);
+    bool ink = false;   // the current line has a non-blank character
+    for (size_t got; (got = fread(blk.data(), 1, blk.size(), in.f)) > 0;)
+        for (size_t i = 0; i < got; ++i) {
+            const char c = blk[i];
+            if (c == '\n') { lines += ink; ink = false; }
+            else if (!fcidump::detail::blank(c)) ink = true;
+        }
+    lines += ink;
+    if (norb) *norb = h.norb;
+    if (nelec) *nelec = h.nelec;
+    if (ms2) *ms2 = h.ms2;
+    if (uhf) *uhf = h.uhf ? 1 : 0;
+    if (nlines) *nlines = lines;
+    return 0;
+}
+
+void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r)
+{
+    const char* who = "afesp_read_fcidump";
+    File file(fopen(path, "rb"));
+    if (!file.f) throw Error(1, std::string(who) + ": cannot open " + path);
+    fcidump::Header h;
+    fcidump_open_header(file.f, who, path, h);
+    if (h.uhf) throw Error(1, std::string(who) + ": the file says UHF=.TRUE. (afesp_read_fcidump_uhf reads it)");
+    if (h.norb != n || h.nelec != 2 * nocc || h.ms2 != 0)
+        throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
+                           std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nocc " + std::to_string(nocc));
+    const int64_t ne = neri_of(n), np = npair_of(n), n2 = up16(n * n);
+    FcidumpTargets T{};
+    T.n = n; T.np = np; T.ne = ne; T.uhf = 0;
+    T.nslots = ne + np + 1;
+    fcidump_fit(cx, who, (double)ne + (double)T.nslots / 64 + 2.0 * n2 + ((double)knobs().fcidump_chunk_kib * 1024 / 2));
+    ReadScratch rs(cx);
+    double* packed = rs.get(ne);
+    double* small = rs.get(2 * n2 + 16);   // h | F | core energy
+    T.eri[0] = packed;
+    T.h[0] = small;
+    T.ecore = small + 2 * n2;
+    AFESP_HIP(hipMemsetAsync(packed, 0, sizeof(double) * ne, cx.stream));
+    AFESP_HIP(hipMemsetAsync(small, 0, sizeof(double) * (2 * n2 + 16), cx.stream));
+    const FcidumpRead got = fcidump_read_body(cx, rs, file.f, who, h, T);
+    double* F = small + n2;
+    k_fock_mo(cx, F, T.h[0], packed, (int)n, (int)nocc, 2.0);
+    std::vector<double> hh((size_t)(n * n)), ff((size_t)(n * n));
+    AFESP_HIP(hipMemcpyAsync(hh.data(), T.h[0], sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(ff.data(), F, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+    if (r.eri[0]) AFESP_HIP(hipMemcpyAsync(r.eri[0], packed, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    // from here on nothing fails: the new array takes the place of the resident one, as a transform's result would
+    cx.drop_scratch("t_");
+    in.release_uhf(cx);
+    in.drop_mo(cx, cc);
+    rs.keep(packed);
+    in.set_mo(packed, n);
+    double e = got.e_core;
+    for (int64_t i = 0; i < nocc; ++i) e += hh[(size_t)(i + n * i)] + ff[(size_t)(i + n * i)];
+    if (r.h[0]) memcpy(r.h[0], hh.data(), sizeof(double) * n * n);
+    if (r.fock[0]) memcpy(r.fock[0], ff.data(), sizeof(double) * n * n);
+    if (r.levels[0])
+        for (int64_t p = 0; p < n; ++p) r.levels[0][p] = ff[(size_t)(p + n * p)];
+    r.e_core = got.e_core;
+    r.e_ref = e;
+    r.fock_offdiag = offdiag_max(ff.data(), n);
+    r.nread = got.nread;
+}
+
+void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)
+{
+    const char* who = "afesp_read_fcidump_uhf";
+    File file(fopen(path, "rb"));
+    if (!file.f) throw Error(1, std::string(who) + ": cannot open " + path);
+    fcidump::Header h;
+    fcidump_open_header(file.f, who, path, h);
+    if (!h.uhf) throw Error(1, std::string(who) + ": the file does not say UHF=.TRUE. (afesp_read_fcidump reads it)");
+    if (h.norb != 2 * n || h.nelec != na + nb || h.ms2 != na - nb)
+        throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
+                           std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nalpha " + std::to_string(na) + ", nbeta " +
+                           std::to_string(nb));
+    const int64_t ne = neri_of(n), np = npair_of(n), n2 = up16(n * n);
+    FcidumpTargets T{};
+    T.n = n; T.np = np; T.ne = ne; T.uhf = 1;
+    T.nslots = 2 * ne + np * np + 2 * np + 1;
+    fcidump_fit(cx, who, 2.0 * ne + (double)np * np + (double)T.nslots / 64 + 4.0 * n2 + ((double)knobs().fcidump_chunk_kib * 1024 / 2));
+    ReadScratch rs(cx);
+    double *aa = rs.get(ne), *bb = rs.get(ne), *ab = rs.get(np * np);
+    double* small = rs.get(4 * n2 + 16);   // h_a | h_b | F_a | F_b | core energy
+    T.eri[0] = aa; T.eri[1] = bb; T.eri[2] = ab;
+    T.h[0] = small; T.h[1] = small + n2;
+    T.ecore = small + 4 * n2;
+    AFESP_HIP(hipMemsetAsync(aa, 0, sizeof(double) * ne, cx.stream));
+    AFESP_HIP(hipMemsetAsync(bb, 0, sizeof(double) * ne, cx.stream));
+    AFESP_HIP(hipMemsetAsync(ab, 0, sizeof(double) * np * np, cx.stream));
+    AFESP_HIP(hipMemsetAsync(small, 0, sizeof(double) * (4 * n2 + 16), cx.stream));
+    const FcidumpRead got = fcidump_read_body(cx, rs, file.f, who, h, T);
+    double *Fa = small + 2 * n2, *Fb = small + 3 * n2;
+    k_fock_mo(cx, Fa, T.h[0], aa, (int)n, (int)na, 1.0);
+    k_fock_mo(cx, Fb, T.h[1], bb, (int)n, (int)nb, 1.0);
+    k_fock_mo_ab(cx, Fa, Fb, ab, (int)n, (int)na, (int)nb);
+    std::vector<double> hh[2], ff[2];
+    for (int s = 0; s < 2; ++s) {
+        hh[s].resize((size_t)(n * n));
+        ff[s].resize((size_t)(n * n));
+        AFESP_HIP(hipMemcpyAsync(hh[s].data(), T.h[s], sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(ff[s].data(), s ? Fb : Fa, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+    }
+    if (r.eri[0]) AFESP_HIP(hipMemcpyAsync(r.eri[0], aa, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (r.eri[1]) AFESP_HIP(hipMemcpyAsync(r.eri[1], bb, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (r.eri[2]) AFESP_HIP(hipMemcpyAsync(r.eri[2], ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    cx.drop_scratch("t_");
+    rs.keep(aa); rs.keep(bb); rs.keep(ab);
+    in.swap_uhf(cx, aa, bb, ab, n);
+    double ea = 0.0, eb = 0.0;
+    for (int64_t i = 0; i < na; ++i) ea += hh[0][(size_t)(i + n * i)] + ff[0][(size_t)(i + n * i)];
+    for (int64_t i = 0; i < nb; ++i) eb += hh[1][(size_t)(i + n * i)] + ff[1][(size_t)(i + n * i)];
+    for (int s = 0; s < 2; ++s) {
+        if (r.h[s]) memcpy(r.h[s], hh[s].data(), sizeof(double) * n * n);
+        if (r.fock[s]) memcpy(r.fock[s], ff[s].data(), sizeof(double) * n * n);
+        if (r.levels[s])
+            for (int64_t p = 0; p < n; ++p) r.levels[s][p] = ff[s][(size_t)(p + n * p)];
+    }
+    r.e_core = got.e_core;
+    r.e_ref = got.e_core + 0.5 * ea + 0.5 * eb;
+    r.fock_offdiag = std::max(offdiag_max(ff[0].data(), n), offdiag_max(ff[1].data(), n));
+    r.nread = got.nread;
 }
 
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed)

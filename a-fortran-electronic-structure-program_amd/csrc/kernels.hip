@@ -3,6 +3,7 @@
 #include <algorithm>
 
 #include "afesp_internal.h"
+#include "fcidump_parse.h"
 #include "fused.h"
 
 namespace afesp {
@@ -1703,6 +1704,162 @@ void k_core_fold_ab(Context& cx, double* h_a, double* h_b, double* e_core, const
 {
     const int64_t waves = (int64_t)n_act * (n_act + 1) / 2 + 1;
     LAUNCH(core_fold_ab_kernel, dim3((unsigned)((waves + TB / 64 - 1) / (TB / 64))), h_a, h_b, e_core, ab, n, nfc, n_act);
+}
+
+// ---- the FCIDUMP reader (afesp_read_fcidump / _uhf): records -> slots, and the Fock operator of the file's determinant
+// One record per lane: canonicalise (packed_index / tri do), route, act.  Targets and the bit of the visited map (one bit per slot):
+//   closed shell: packed [0, ne) | h, bit ne + tri(i,j) | core energy
+//   open shell:   aa [0, ne) | bb | ab, row = alpha pair, the (bb|aa) form transposed | h_a | h_b | core energy
+// (odd spin-orbital numbers are alpha, spatial orbital (x + 1) / 2 - 1).  The host has checked every record (fcidump_parse.h: classify);
+// a record that fails here nevertheless is counted as an error and never dereferenced.
+namespace {
+struct FcSlot {
+    double *a, *mirror;
+    int64_t bit;
+};
+__device__ __forceinline__ bool fc_route(const FcidumpTargets& T, const fcidump::Record& r, FcSlot& s)
+{
+    const int64_t norb = T.uhf ? 2 * T.n : T.n;
+    const int64_t i = r.idx[0], j = r.idx[1], k = r.idx[2], l = r.idx[3];
+    s.mirror = nullptr;
+    if (i < 0 || j < 0 || k < 0 || l < 0 || i > norb || j > norb || k > norb || l > norb) return false;
+    if (i == 0 || j == 0) {
+        if (i | j | k | l) return false;
+        s.a = T.ecore;
+        s.bit = T.nslots - 1;
+        return true;
+    }
+    if ((k == 0) != (l == 0)) return false;
+    if (!T.uhf) {
+        if (k == 0) {
+            s.a = T.h[0] + (i - 1) + T.n * (j - 1);
+            s.mirror = T.h[0] + (j - 1) + T.n * (i - 1);
+            s.bit = T.ne + tri(i - 1, j - 1);
+        } else {
+            s.bit = packed_index(i - 1, j - 1, k - 1, l - 1);
+            s.a = T.eri[0] + s.bit;
+        }
+        return true;
+    }
+    const int64_t p = (i + 1) / 2 - 1, q = (j + 1) / 2 - 1;
+    const int b1 = !(i & 1);
+    if (((i ^ j) & 1) || ((k ^ l) & 1)) return false;
+    if (k == 0) {
+        s.a = T.h[b1] + p + T.n * q;
+        s.mirror = T.h[b1] + q + T.n * p;
+        s.bit = 2 * T.ne + T.np * T.np + b1 * T.np + tri(p, q);
+        return true;
+    }
+    const int64_t t = (k + 1) / 2 - 1, u = (l + 1) / 2 - 1;
+    const int b2 = !(k & 1);
+    if (b1 == b2) {
+        const int64_t x = packed_index(p, q, t, u);
+        s.a = T.eri[b1] + x;
+        s.bit = b1 * T.ne + x;
+    } else {
+        const int64_t x = b1 ? tri(t, u) * T.np + tri(p, q) : tri(p, q) * T.np + tri(t, u);
+        s.a = T.eri[2] + x;
+        s.bit = 2 * T.ne + x;
+    }
+    return true;
+}
+__device__ __forceinline__ void fc_flag(const FcidumpTargets& T, int64_t line)
+{
+    atomicAdd(T.err, 1ull);
+    atomicMin(T.err + 1, (unsigned long long)line);
+}
+// PASS 0: a record whose slot an EARLIER chunk visited compares its bits with the resident value.  PASS 1: store, mark visited.
+// PASS 2: every record reads its slot back (a one-electron record both triangles): of two records of this chunk that disagree, at
+// least one finds the other's bits in a location it stored to.
+template <int PASS>
+__global__ __launch_bounds__(TB) void fcidump_scatter_kernel(FcidumpTargets T, const fcidump::Record* __restrict__ rec, int64_t count)
+{
+    GRID_STRIDE(x, count)
+    {
+        const fcidump::Record r = rec[x];
+        FcSlot s;
+        if (!fc_route(T, r, s) || s.bit < 0 || s.bit >= T.nslots) {
+            if (PASS == 0) fc_flag(T, r.line);
+            continue;
+        }
+        uint32_t* word = T.visited + (s.bit >> 5);
+        const uint32_t mask = 1u << (s.bit & 31);
+        if (PASS == 0) {
+            if ((*word & mask) && (__double_as_longlong(*s.a) != __double_as_longlong(r.value) ||
+                                   (s.mirror && __double_as_longlong(*s.mirror) != __double_as_longlong(r.value))))
+                fc_flag(T, r.line);
+        } else if (PASS == 1) {
+            *s.a = r.value;
+            if (s.mirror) *s.mirror = r.value;
+            atomicOr(word, mask);
+        } else {   // (a one-electron record stored both triangles: both are read back, whichever order the stores landed in)
+            if (__double_as_longlong(*s.a) != __double_as_longlong(r.value) ||
+                (s.mirror && __double_as_longlong(*s.mirror) != __double_as_longlong(r.value)))
+                fc_flag(T, r.line);
+        }
+    }
+}
+// The Fock operator of the determinant that fills the first nocc orbitals, over ALL n orbitals (the all-orbital analogue of
+// core_fold_kernel): one wave per pair p >= q, F(p,q) = h(p,q) + sum_{i < nocc} [wj (pq|ii) - (pi|qi)] -- lane l takes i = l, l + 64, ...
+// in rising order, wave_sum adds the 64 partial sums in its fixed order, both triangles are written from one register.  wj = 2 closed
+// shell, 1 for one spin of an open shell.
+__global__ __launch_bounds__(TB) void fock_mo_kernel(double* __restrict__ F, const double* __restrict__ h, const double* __restrict__ packed, int n,
+                                                     int nocc, double wj)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t np = (int64_t)n * (n + 1) / 2, w = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (w >= np) return;   // (whole waves leave)
+    int q, p;
+    unpair(w, q, p);
+    double acc = 0.0;
+    for (int64_t i = lane; i < nocc; i += 64) acc += wj * packed[packed_index(p, q, i, i)] - packed[packed_index(p, i, q, i)];
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        const double val = h[p + (int64_t)n * q] + acc;
+        F[p + (int64_t)n * q] = val;
+        F[q + (int64_t)n * p] = val;
+    }
+}
+// ... and the opposite-spin Coulomb terms out of ab[tri(p,q) np + tri(r,s)] (alpha pair: row), added to what fock_mo_kernel wrote:
+// F_a(p,q) += sum_{I < nb} (pq|II), F_b(p,q) += sum_{i < na} (ii|pq)
+__global__ __launch_bounds__(TB) void fock_mo_ab_kernel(double* __restrict__ fa, double* __restrict__ fb, const double* __restrict__ ab, int n,
+                                                        int na, int nb)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t np = (int64_t)n * (n + 1) / 2, w = (int64_t)blockIdx.x * (TB / 64) + (threadIdx.x >> 6);
+    if (w >= np) return;
+    int q, p;
+    unpair(w, q, p);
+    double ja = 0.0, jb = 0.0;
+    for (int64_t i = lane; i < nb; i += 64) ja += ab[w * np + tri(i, i)];
+    for (int64_t i = lane; i < na; i += 64) jb += ab[tri(i, i) * np + w];
+    ja = wave_sum(ja);
+    jb = wave_sum(jb);
+    if (lane == 0) {
+        const int64_t lo = p + (int64_t)n * q, up = q + (int64_t)n * p;
+        const double va = fa[lo] + ja, vb = fb[lo] + jb;
+        fa[lo] = va; fa[up] = va;
+        fb[lo] = vb; fb[up] = vb;
+    }
+}
+}  // namespace
+void k_fcidump_scatter(Context& cx, const FcidumpTargets& T, const fcidump::Record* rec, int64_t count)
+{
+    if (count <= 0) return;
+    const dim3 grid(grid_for(count, 65536));
+    LAUNCH(fcidump_scatter_kernel<0>, grid, T, rec, count);
+    LAUNCH(fcidump_scatter_kernel<1>, grid, T, rec, count);
+    LAUNCH(fcidump_scatter_kernel<2>, grid, T, rec, count);
+}
+void k_fock_mo(Context& cx, double* F, const double* h, const double* packed, int n, int nocc, double wj)
+{
+    const int64_t waves = (int64_t)n * (n + 1) / 2;
+    LAUNCH(fock_mo_kernel, dim3((unsigned)((waves + TB / 64 - 1) / (TB / 64))), F, h, packed, n, nocc, wj);
+}
+void k_fock_mo_ab(Context& cx, double* fa, double* fb, const double* ab, int n, int na, int nb)
+{
+    const int64_t waves = (int64_t)n * (n + 1) / 2;
+    LAUNCH(fock_mo_ab_kernel, dim3((unsigned)((waves + TB / 64 - 1) / (TB / 64))), fa, fb, ab, n, na, nb);
 }
 
 // ---- order-preserving stream compaction of an integral array (afesp_write_fcidump_active / _uactive): the elements with

@@ -78,6 +78,7 @@ struct Knobs {
     int t_block = 0;                        // AFESP_T_BLOCK        occupied block size of the (T) enumeration (0: chosen)
     int64_t t_pool_gib = -1;                // AFESP_T_POOL_GIB     (T) block pool budget (-1: a quarter of the device, <= 64 GiB)
     int64_t t_split_tiles = 1024;           // AFESP_T_SPLIT_TILES
+    int64_t fcidump_chunk_kib = 4096;       // AFESP_FCIDUMP_CHUNK_KIB  text the FCIDUMP reader parses per round (1 .. 1048576; not tuned)
     // ---------------------------------------------------------------------------------------------------------- DIAGNOSTIC
     int tg_dbg = 0;                         // AFESP_TG_DBG=1       measurement: no C stores
     bool graph_debug = false, preload_debug = false, fused_debug = false, fused_per_op = false, gett_debug = false, t_debug = false;
@@ -145,6 +146,7 @@ inline void parse(Knobs& k)
     if ((e = get("AFESP_T_BLOCK"))) k.t_block = atoi(e);
     if ((e = get("AFESP_T_POOL_GIB"))) k.t_pool_gib = (int64_t)atoll(e);
     if ((e = get("AFESP_T_SPLIT_TILES"))) k.t_split_tiles = (int64_t)atoll(e);
+    if ((e = get("AFESP_FCIDUMP_CHUNK_KIB"))) k.fcidump_chunk_kib = atoll(e) < 1 ? 1 : atoll(e) > (1 << 20) ? (1 << 20) : (int64_t)atoll(e);
     if ((e = get("AFESP_TG_DBG"))) k.tg_dbg = atoi(e);
     k.graph_debug = get("AFESP_GRAPH_DEBUG") != nullptr;
     k.preload_debug = get("AFESP_PRELOAD_DEBUG") != nullptr;

@@ -13,6 +13,7 @@ module afesp_capi
              afesp_build_fock_uhf, afesp_ao2mo_ump2, afesp_ccsd_uso_init, afesp_mo_window, afesp_umo_window, &
              afesp_mp2_vv_density, afesp_ump2_vv_density, &
              afesp_core_operator, afesp_ucore_operator, afesp_write_fcidump_active, afesp_write_fcidump_uactive, &
+             afesp_fcidump_scan, afesp_read_fcidump, afesp_read_fcidump_uhf, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -266,6 +267,39 @@ module afesp_capi
          real(c_double), intent(in) :: h_act_a(*), h_act_b(*)
          real(c_double), value :: e_core_total, threshold
          integer(c_int64_t), intent(out) :: nwritten
+         integer(c_int) :: rc
+      end function
+      !> a standard FCIDUMP as input (include/afesp.h).  afesp_fcidump_scan: host only, the header and the number of lines after it
+      function afesp_fcidump_scan(path, norb, nelec, ms2, uhf, nlines) bind(C, name='afesp_fcidump_scan') result(rc)
+         import :: c_int, c_int64_t, c_char
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), intent(out) :: norb, nelec, ms2, nlines
+         integer(c_int), intent(out) :: uhf
+         integer(c_int) :: rc
+      end function
+      !> the file onto the device, resident as afesp_ao2mo_mp2 leaves its result; h_mo, fock (n x n), levels (n) and eri_mo_packed may be
+      !> c_null_ptr; e_ref = the energy of the determinant of the first nocc orbitals, fock_offdiag = max |F(p,q)|, p /= q
+      function afesp_read_fcidump(ctx, path, nbasis, nocc, h_mo, fock, levels, e_core, e_ref, fock_offdiag, eri_mo_packed, nread) &
+         bind(C, name='afesp_read_fcidump') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), value :: nbasis, nocc
+         type(c_ptr), value :: h_mo, fock, levels, eri_mo_packed
+         real(c_double), intent(out) :: e_core, e_ref, fock_offdiag
+         integer(c_int64_t), intent(out) :: nread
+         integer(c_int) :: rc
+      end function
+      !> the same for a UHF=.TRUE. file: the three blocks resident as afesp_ao2mo_ump2 leaves them
+      function afesp_read_fcidump_uhf(ctx, path, nbasis, nalpha, nbeta, h_a, h_b, fock_a, fock_b, levels_a, levels_b, e_core, e_ref, &
+                                      fock_offdiag, eri_aa, eri_ab, eri_bb, nread) bind(C, name='afesp_read_fcidump_uhf') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         type(c_ptr), value :: h_a, h_b, fock_a, fock_b, levels_a, levels_b, eri_aa, eri_ab, eri_bb
+         real(c_double), intent(out) :: e_core, e_ref, fock_offdiag
+         integer(c_int64_t), intent(out) :: nread
          integer(c_int) :: rc
       end function
       !> replaces write_fcidump (reference src/mp2.f90:451-487)

@@ -36,6 +36,7 @@ module host_config
       integer :: scf_diis_n_errmat = 6, ccsd_diis_n_errmat = 8, scf_maxiter = 50, ccsd_maxiter = 50
       logical :: write_fcidump = .false., scf_read_guess = .false., scf_write_guess = .false.
       logical :: fcidump_active = .false.   ! the space the solvers run in as a standard FCIDUMP (header, frozen-core operator, core energy)
+      logical :: fcidump_in = .false.       ! MO integrals from ./FCIDUMP: no s.dat / t.dat / v.dat / eri.dat / geom.dat, no SCF, no transform
       integer :: level = LEVEL_CCSD_T
       logical :: paren = .false., renorm = .false., comp_renorm = .false.
       logical :: spinorb = .false.   ! the _spinorb calculation types (reference src/system.f90:117-137)
@@ -58,10 +59,10 @@ contains
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt
       real(dp) :: fno_occ_tol
-      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active
+      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
-         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active
+         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -70,6 +71,7 @@ contains
       charge = d%charge; multiplicity = d%multiplicity
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
+      fcidump_in = d%fcidump_in
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -118,6 +120,18 @@ contains
          call fail('system::read_system_in', 'Unrecognised calculation type!')
       end select
       if (multiplicity < 1) call fail('system::read_system_in', 'invalid input file format!')
+      cfg%fcidump_in = fcidump_in
+      if (fcidump_in) then   ! the file replaces everything up to the MO integrals: what needs AO data or writes the same file is refused
+         if (frozen_core) call fail('system::read_system_in', &
+            'fcidump_in: frozen_core counts atoms in geom.dat, which is not read: give n_frozen_core!')
+         if (fno_n_virt >= 0 .or. fno_occ_tol > 0.0_dp) call fail('system::read_system_in', &
+            'fcidump_in: frozen natural orbitals need the AO integrals, which are not read!')
+         if (write_fcidump .or. fcidump_active) call fail('system::read_system_in', &
+            'fcidump_in reads FCIDUMP: write_fcidump / fcidump_active would overwrite it!')
+         if (scf_read_guess .or. scf_write_guess) call fail('system::read_system_in', &
+            'fcidump_in runs no SCF: scf_read_guess / scf_write_guess have nothing to act on!')
+         if (cfg%level == LEVEL_RHF) call fail('system::read_system_in', 'fcidump_in runs no SCF: choose a correlated calculation type!')
+      end if
       if (.not. cfg%uhf .and. (charge /= 0 .or. multiplicity /= 1)) &
          call fail('system::read_system_in', 'charge and multiplicity need an open-shell calculation type!')
    end subroutine
@@ -694,7 +708,11 @@ program els_amd
    ! Post-HF levels: the engine context exists from the start, and the engine reads eri.dat (the packed AO integrals
    ! then stay on the device for the AO->MO transform; the host copy feeds the SCF)
    have_ctx = cfg%level >= LEVEL_MP2
-   call read_molecule(mol, have_ctx)
+   if (cfg%fcidump_in) then
+      call scan_input_file()   ! extents and electron counts from the header of ./FCIDUMP
+   else
+      call read_molecule(mol, have_ctx)
+   end if
    if (have_ctx) then
       device = 0
       if (world > 1 .and. afesp_device_count() > 0) device = mod(rank, int(afesp_device_count()))   ! one GPU per rank
@@ -707,12 +725,14 @@ program els_amd
          if (rc /= 0) call fail('main', afesp_error_text(ctx))
          write (out, '(1X, A, I0, A, A)') 'Ranks: ', world, ', transport ', merge('host', 'rccl', transport == AFESP_COMM_HOST)
       end if
-      rc = afesp_read_eri_text(ctx, 'eri.dat'//c_null_char, int(mol%nbasis, c_int64_t), mol%eri, nlines)
-      if (rc /= 0) call fail('integrals::read_integrals_in', afesp_error_text(ctx))
-      write (out, *) 'Done reading integrals!'
+      if (.not. cfg%fcidump_in) then
+         rc = afesp_read_eri_text(ctx, 'eri.dat'//c_null_char, int(mol%nbasis, c_int64_t), mol%eri, nlines)
+         if (rc /= 0) call fail('integrals::read_integrals_in', afesp_error_text(ctx))
+         write (out, *) 'Done reading integrals!'
+      end if
    end if
    write (out, '(1X, 20("-"))'); write (out, '(1X, A)') 'System information'; write (out, '(1X, 20("-"))')
-   if (cfg%uhf) then   ! nel = sum Z - charge, n_alpha - n_beta = multiplicity - 1
+   if (cfg%uhf .and. .not. cfg%fcidump_in) then   ! nel = sum Z - charge, n_alpha - n_beta = multiplicity - 1
       mol%nel = mol%nel - cfg%charge
       if (mol%nel < 0 .or. mod(mol%nel + cfg%multiplicity - 1, 2) /= 0) &
          call fail('system::read_system_in', 'charge and multiplicity do not fit the electron count!')
@@ -724,7 +744,8 @@ program els_amd
    write (out, '(1X, A, 1X, I0)') 'Number of electrons:', mol%nel
    write (out, '(1X, A, 1X, I0)') 'Number of basis functions:', mol%nbasis
    if (cfg%uhf) then
-      write (out, '(1X, A, 1X, I0, 1X, I0)') 'Charge and multiplicity:', cfg%charge, cfg%multiplicity
+      if (.not. cfg%fcidump_in) write (out, '(1X, A, 1X, I0, 1X, I0)') 'Charge and multiplicity:', cfg%charge, cfg%multiplicity
+      if (cfg%fcidump_in) write (out, '(1X, A, 1X, I0, 1X, I0)') 'Alpha and beta electrons (NELEC, MS2 of the file):', na, nb
       write (out, '(1X, A, 1X, I0)') 'Number of occupied orbitals:', na + nb
       write (out, '(1X, A, 1X, I0)') 'Number of virtual orbitals:', 2*mol%nbasis - na - nb
    else if (cfg%spinorb) then   ! spin-orbital counts, reference src/geometry.f90:44-45
@@ -777,7 +798,9 @@ program els_amd
    write (out, '(1X, A, 1X, A)') 'calc_type:', trim(cfg%calc_type)
 
    t0 = seconds()
-   if (cfg%uhf) then
+   if (cfg%fcidump_in) then
+      call read_input_file()   ! the integrals onto the device, levels and the reference determinant's energy from them
+   else if (cfg%uhf) then
       call uhf(cfg, mol, na, nb, e_hf, coeff, cb, levels, lb, s2, scf_ok, ctx, have_ctx)
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted Hartree-Fock:', seconds() - t0, 's'
    else
@@ -791,13 +814,16 @@ program els_amd
       ! ---------------- open shells: UMP2 from the three spin blocks, then the spin-orbital CCSD / (T) on them
       t0 = seconds()
       write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'UMP2'; write (out, '(1X, 10("-"))')
-      write (out, '(1X, A)') 'Performing AO to MO ERI transformation (alpha-alpha, alpha-beta, beta-beta)...'
-      rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
-                            c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
-      if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
+      if (.not. cfg%fcidump_in) then
+         write (out, '(1X, A)') 'Performing AO to MO ERI transformation (alpha-alpha, alpha-beta, beta-beta)...'
+         rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
+                               c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
+         if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
+      end if
       if (fno) call open_shell_fno()   ! natural virtuals of both spins, second transform; sets nfv and the active extents
       if (cfg%fcidump_active) call core_operator_before_window()
-      if (windowed .or. fno) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
+      if (windowed .or. fno .or. cfg%fcidump_in) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
+         ! (integrals read from a file: this call, with nothing frozen too, is the one that reports the UMP2 energy)
          rc = afesp_umo_window(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), &
                                int(nfv, c_int64_t), levels, lb, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
@@ -866,15 +892,17 @@ program els_amd
       ! ---------------- MP2: AO->MO transform + energy on the device (reference do_mp2_spatial)
       t0 = seconds()
       write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'MP2'; write (out, '(1X, 10("-"))')
-      write (out, '(1X, A)') 'Performing AO to MO ERI transformation...'
-      rc = afesp_ao2mo_mp2(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), coeff, levels, c_null_ptr, c_null_ptr, e_mp2)
-      if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
+      if (.not. cfg%fcidump_in) then
+         write (out, '(1X, A)') 'Performing AO to MO ERI transformation...'
+         rc = afesp_ao2mo_mp2(ctx, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), coeff, levels, c_null_ptr, c_null_ptr, e_mp2)
+         if (rc /= 0) call fail('mp2::do_mp2_spatial', afesp_error_text(ctx))
+      end if
       if (fno) then   ! the FCIDUMP (if asked for) is of the canonical integrals; then natural virtuals and the second transform
          if (cfg%write_fcidump) call dump_integrals()
          call closed_shell_fno()
       end if
       if (cfg%fcidump_active) call core_operator_before_window()
-      if (windowed .or. fno) then
+      if (windowed .or. fno .or. cfg%fcidump_in) then   ! (integrals read from a file: the MP2 energy comes from this call in any case)
          ! frozen orbitals: the FCIDUMP (if asked for) is of the full integrals; then the window over the active orbitals replaces
          ! them on the device, and the MP2 energy is the frozen-core one
          if (cfg%write_fcidump .and. .not. fno) call dump_integrals()
@@ -1084,7 +1112,7 @@ program els_amd
    write (out, '(1X, A)') 'Final energy breakdown'
    if (cfg%uhf) then
    write (out, '(1X, A, 1X, F15.10)') 'UHF energy:                    ', e_hf + mol%e_nuc
-   write (out, '(1X, A, 1X, F15.10)') '<S^2>:                         ', s2
+   if (.not. cfg%fcidump_in) write (out, '(1X, A, 1X, F15.10)') '<S^2>:                         ', s2
    if (cfg%level >= LEVEL_MP2) then
       write (out, '(1X, A, 1X, F15.10)') 'UMP2 correlation energy:       ', e_mp2
       write (out, '(1X, A, 1X, F15.10)') 'UMP2 energy:                   ', e_mp2 + e_hf + mol%e_nuc
@@ -1250,6 +1278,73 @@ contains
       rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
                             c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, dummy)
       if (rc /= 0) call fail('mp2::natural_virtuals', afesp_error_text(ctx))
+   end subroutine
+   !> fcidump_in, first half (no device): the header of ./FCIDUMP gives the extents and the electron counts; the calculation type must
+   !> match the kind of file.  The core energy of the file holds the nuclear repulsion: e_nuc stays 0 and e_hf is the total energy.
+   subroutine scan_input_file()
+      integer(c_int64_t) :: norb, nelec, ms2, nl
+      integer(c_int) :: file_uhf
+      rc = afesp_fcidump_scan('FCIDUMP'//c_null_char, norb, nelec, ms2, file_uhf, nl)
+      if (rc /= 0) call fail('integrals::read_fcidump', 'fcidump_in: FCIDUMP is missing, unreadable or has no &FCI ... &END header')
+      write (out, '(1X, A, I0, A, I0, A, I0, A, L1, A, I0)') 'FCIDUMP header: NORB ', norb, ', NELEC ', nelec, ', MS2 ', ms2, ', UHF ', &
+         file_uhf /= 0, ', lines ', nl
+      if (file_uhf /= 0 .and. .not. cfg%uhf) call fail('integrals::read_fcidump', &
+         'fcidump_in: the file says UHF=.TRUE.: it takes UMP2, UCCSD or UCCSD(T), not '//trim(cfg%calc_type))
+      if (file_uhf == 0 .and. cfg%uhf) call fail('integrals::read_fcidump', &
+         'fcidump_in: a closed-shell file takes the _spatial and _spinorb types, not '//trim(cfg%calc_type))
+      mol%e_nuc = 0.0_dp; mol%natoms = 0; mol%ncore = -1
+      mol%nel = int(nelec)
+      if (cfg%uhf) then
+         if (mod(norb, 2_c_int64_t) /= 0 .or. mod(nelec + ms2, 2_c_int64_t) /= 0) call fail('integrals::read_fcidump', &
+            'fcidump_in: UHF=.TRUE. with an odd NORB, or NELEC and MS2 of different parity')
+         mol%nbasis = int(norb/2)
+         na = int((nelec + ms2)/2); nb = int((nelec - ms2)/2)
+         if (na < 0 .or. nb < 0 .or. na > mol%nbasis .or. nb > mol%nbasis .or. na + nb >= 2*mol%nbasis) &
+            call fail('integrals::read_fcidump', 'fcidump_in: NELEC and MS2 do not fit NORB, or leave no virtual spin orbital')
+         mol%nocc = nb; mol%nvirt = mol%nbasis - na
+      else
+         if (ms2 /= 0 .or. mod(nelec, 2_c_int64_t) /= 0) call fail('integrals::read_fcidump', &
+            'fcidump_in: an open shell without UHF=.TRUE. (restricted open-shell orbitals are not supported)')
+         mol%nbasis = int(norb); mol%nocc = int(nelec/2); mol%nvirt = mol%nbasis - mol%nocc
+         if (mol%nocc <= 0 .or. mol%nvirt <= 0) call fail('integrals::read_fcidump', 'fcidump_in: no occupied or no virtual orbital')
+      end if
+   end subroutine
+   !> second half, where the SCF would run: the integrals onto the device (resident as a transform leaves them), the levels = the
+   !> diagonal of the Fock operator of the file's determinant, e_hf = that determinant's energy.  The solvers assume canonical
+   !> orbitals: the largest off-diagonal Fock element is printed in every run and refused above 1e-6 (a policy value: a file from a
+   !> converged SCF lies orders of magnitude below it).
+   subroutine read_input_file()
+      real(dp), parameter :: canonical_tol = 1e-6_dp
+      real(dp) :: e_core_file, offdiag
+      real(dp), allocatable, target :: la_t(:), lb_t(:)
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'FCIDUMP'; write (out, '(1X, 10("-"))')
+      write (out, '(1X, A)') 'Reading MO integrals from FCIDUMP (no SCF, no AO to MO transformation)...'
+      allocate (la_t(mol%nbasis), lb_t(mol%nbasis))
+      if (cfg%uhf) then
+         rc = afesp_read_fcidump_uhf(ctx, 'FCIDUMP'//c_null_char, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), &
+                                     c_null_ptr, c_null_ptr, c_null_ptr, c_null_ptr, c_loc(la_t), c_loc(lb_t), e_core_file, e_hf, &
+                                     offdiag, c_null_ptr, c_null_ptr, c_null_ptr, nlines)
+      else
+         rc = afesp_read_fcidump(ctx, 'FCIDUMP'//c_null_char, int(mol%nbasis, c_int64_t), int(mol%nocc, c_int64_t), c_null_ptr, &
+                                 c_null_ptr, c_loc(la_t), e_core_file, e_hf, offdiag, c_null_ptr, nlines)
+      end if
+      if (rc /= 0) call fail('integrals::read_fcidump', afesp_error_text(ctx))
+      allocate (levels(mol%nbasis)); levels = la_t
+      if (cfg%uhf) then
+         allocate (lb(mol%nbasis)); lb = lb_t
+      end if
+      s2 = 0.0_dp
+      write (out, '(1X, A, I0)') 'Lines read: ', nlines
+      write (out, '(1X, A, 1X, F18.10)') 'Core energy of the file (Hartree):', e_core_file
+      write (out, '(1X, A, 1X, F18.10)') 'Reference determinant energy (Hartree):', e_hf
+      write (out, '(1X, A, 1X, ES10.3)') 'Largest off-diagonal Fock element:', offdiag
+      if (.not. offdiag <= canonical_tol) then
+         write (my_error, '(A, ES10.3, A, ES8.1, A)') 'fcidump_in: the orbitals of the file are not canonical: max |F(p,q)|, p /= q, is ', &
+            offdiag, ', above ', canonical_tol, ' (the solvers assume canonical orbitals)'
+         call fail('integrals::read_fcidump', trim(my_error))
+      end if
+      scf_ok = .true.
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for reading the FCIDUMP:', seconds() - t0, 's'
    end subroutine
    !> fcidump_active, first half: the frozen-core operator of the window and the core energy from the full MO integrals of the (last)
    !> transform -- before the window, which throws the core orbitals away (with natural virtuals: in the rotated orbitals)

@@ -30,7 +30,7 @@
  *   tuning (tile / slice / pool sizes, scheduling):  AFESP_PP_SPLIT, AFESP_PP_TILES, AFESP_REPACK_MIN, AFESP_PLAN_DEVICE_FROM,
  *     AFESP_FUSED_BIG_FLOP, AFESP_FUSED_ITEMS, AFESP_FUSED_MIN_STEPS, AFESP_FUSED_MAX_MFMA, AFESP_FUSED_NB, AFESP_SPLIT_BELOW,
  *     AFESP_SPLIT_MIN_STEPS, AFESP_TG_PATCH, AFESP_TG_GRID, AFESP_TG_PRIO_SHIFT, AFESP_TG_DYNAMIC, AFESP_T_BLOCK, AFESP_T_POOL_GIB,
- *     AFESP_T_SPLIT_TILES
+ *     AFESP_T_SPLIT_TILES, AFESP_FCIDUMP_CHUNK_KIB
  *   diagnostics (printing, measurement; no effect on results):  AFESP_TG_DBG, AFESP_GRAPH_DEBUG, AFESP_PRELOAD_DEBUG,
  *     AFESP_FUSED_DEBUG, AFESP_FUSED_PER_OP, AFESP_GETT_DEBUG, AFESP_T_DEBUG, AFESP_CONTRACT_TRACE, AFESP_STAMPS_GROUPED
  */
@@ -275,6 +275,49 @@ int afesp_write_fcidump_active(afesp_ctx* ctx, const char* path, int64_t n_act, 
                                double e_core_total, double threshold, int64_t* nwritten);
 int afesp_write_fcidump_uactive(afesp_ctx* ctx, const char* path, int64_t n_act, int64_t nalpha_act, int64_t nbeta_act, const double* h_act_a,
                                 const double* h_act_b, double e_core_total, double threshold, int64_t* nwritten);
+
+/* A standard FCIDUMP as input: the way in for MO integrals that another program -- or afesp_write_fcidump_active --
+ * wrote.  No SCF and no transform: the file's orbitals are taken in file order and the FIRST nocc (nalpha / nbeta) of them are occupied.
+ *
+ * Format: the one documented at afesp_write_fcidump_active above, read liberally.  The namelist may be closed by &END or by / ; keys in any
+ * letter case, over any number of lines, in any order; ORBSYM, ISYM and unknown keys are ignored (no point-group handling); a missing MS2
+ * is 0; UHF=.TRUE. selects the writer's spin-orbital numbering (spatial orbital p is 2p - 1 for alpha, 2p for beta).  Body lines
+ * "value i j k l": fields separated by blanks and/or one comma, reals with E or D exponents (strtod: correctly rounded), blank lines and
+ * \r tolerated, lines in any order, the four indices of a two-electron line in any of the 8 equivalent arrangements, the alpha-beta
+ * integral as (aa|bb) or (bb|aa).  Integrals not mentioned are zero, a missing core-energy line means e_core = 0.
+ * Duplicates: several lines may name one slot (files that list symmetry partners do); they must agree to the bit.  A duplicate that
+ * disagrees is an error wherever in the file the two lines are -- never "the last one wins".
+ *
+ * afesp_fcidump_scan: host only, no context, no device: the header and *nlines = the non-blank lines after it.  Non-zero: NULL or
+ *   unreadable path, no &FCI, no terminator, no NORB / NELEC.
+ * afesp_read_fcidump (closed shell: NORB = nbasis, NELEC = 2 nocc, MS2 = 0, no UHF flag) and afesp_read_fcidump_uhf (UHF=.TRUE.,
+ *   NORB = 2 nbasis, NELEC = nalpha + nbeta, MS2 = nalpha - nbeta) read the file in chunks of AFESP_FCIDUMP_CHUNK_KIB KiB: the host parses
+ *   a chunk on up to 16 threads into 32-byte records while the device scatters the previous one -- the host never holds the integrals.
+ *   On success the packed array is resident exactly as afesp_ao2mo_mp2 leaves the MO integrals of nbasis functions (the three blocks: as
+ *   afesp_ao2mo_ump2 leaves them), so everything that accepts eri_mo_packed = NULL works on it: afesp_ccsd_init, afesp_ccsd_so_init,
+ *   afesp_ccsd_uso_init, afesp_mo_window / afesp_umo_window (a (0, 0) window reports the MP2 energy), afesp_mp2_vv_density,
+ *   afesp_write_fcidump*.  Resident AO integrals are left alone.
+ *   out (each may be NULL; matrices column-major, symmetric to the bit):
+ *     h_mo [n*n]      the one-electron matrix of the file
+ *     fock [n*n]      closed shell: F(p,q) = h(p,q) + sum_{i < nocc} [2 (pq|ii) - (pi|qi)]
+ *                     open shell:   F_a = h_a + sum_{i in alpha occ} [(pq|ii) - (pi|qi)]_aa + sum_{I in beta occ} (pq|II)_ab; F_b the mirror image
+ *     levels [n]      the diagonal of fock
+ *     *e_core         the value on the 0 0 0 0 line
+ *     *e_ref          the energy of the determinant: e_core + sum_i [h(i,i) + F(i,i)]   (open shell: e_core + 1/2 sum_{i in alpha} [h_a + F_a](i,i)
+ *                     + 1/2 sum_{I in beta} [h_b + F_b](I,I))
+ *     *fock_offdiag   max_{p != q} |F(p,q)| over both spins.  The library reports it and does not judge it: the solvers assume canonical
+ *                     orbitals, the caller decides what it accepts (els_amd and Engine.read_fcidump refuse above 1e-6)
+ *     eri_*           host copies of the packed arrays;  *nread = lines after the header
+ *   Status 1, everything resident untouched, no output written, afesp_last_error with the line number where there is one: a NULL path or
+ *   an unreadable file; no &FCI or no terminator; a header that disagrees with the arguments; a malformed line; an index outside
+ *   0..NORB; a line that is neither a two-electron, a one-electron nor the core-energy line; a spin-forbidden element in a UHF file; more
+ *   than one core-energy line; a duplicate that disagrees; arrays that do not fit the device. */
+int afesp_fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines);
+int afesp_read_fcidump(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nocc, double* h_mo, double* fock, double* levels,
+                       double* e_core, double* e_ref, double* fock_offdiag, double* eri_mo_packed, int64_t* nread);
+int afesp_read_fcidump_uhf(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nalpha, int64_t nbeta, double* h_a, double* h_b,
+                           double* fock_a, double* fock_b, double* levels_a, double* levels_b, double* e_core, double* e_ref,
+                           double* fock_offdiag, double* eri_aa, double* eri_ab, double* eri_bb, int64_t* nread);
 
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
