@@ -35,6 +35,7 @@ EXPORTS = [
     "afesp_mp2_vv_density", "afesp_ump2_vv_density",
     "afesp_core_operator", "afesp_ucore_operator", "afesp_write_fcidump_active", "afesp_write_fcidump_uactive",
     "afesp_fcidump_scan", "afesp_read_fcidump", "afesp_read_fcidump_uhf",
+    "afesp_mo_fock_ro", "afesp_read_fcidump_rohf", "afesp_mo_rotate_uhf", "afesp_ccsd_uso_init_fock",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
@@ -124,6 +125,11 @@ def load_library():
     L.afesp_read_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, i64, _opt, _opt, _opt, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl), _opt,
                                      C.POINTER(i64)]
     L.afesp_read_fcidump_uhf.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64] + [_opt] * 6 + [C.POINTER(dbl)] * 3 + [_opt] * 3 + [C.POINTER(i64)]
+    L.afesp_mo_fock_ro.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, _dp, C.POINTER(dbl)]
+    L.afesp_read_fcidump_rohf.argtypes = [C.c_void_p, C.c_char_p, i64, i64, i64, _opt, _opt, _opt, C.POINTER(dbl), C.POINTER(dbl), _opt, _opt,
+                                          C.POINTER(i64)]
+    L.afesp_mo_rotate_uhf.argtypes = [C.c_void_p, i64, _dp, _dp, _opt, _opt, _opt]
+    L.afesp_ccsd_uso_init_fock.argtypes = [C.c_void_p, i64, i64, i64, _dp, _dp, C.c_int, C.POINTER(dbl)]
     L.afesp_device_count.argtypes = []
     L.afesp_comm_unique_id.argtypes = [C.c_char_p]
     L.afesp_comm_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_char_p]
@@ -192,6 +198,9 @@ class FcidumpIn:
     eri_aa: np.ndarray | None = None
     eri_ab: np.ndarray | None = None      # [npair, npair], row: alpha pair
     eri_bb: np.ndarray | None = None
+    # a restricted open-shell file (Engine.read_fcidump_rohf): h, fock_a / fock_b, eri, and max |F| over both spins of the occupied-occupied
+    # off-diagonal, the virtual-virtual off-diagonal and the occupied-virtual elements
+    fock_offdiag3: tuple | None = None
 
     @property
     def nspatial(self) -> int:
@@ -615,9 +624,58 @@ class Engine:
                              f"{out.fock_offdiag:.3e}, above {canonical_tol:.1e} (the integrals are resident all the same)")
         return out
 
+    # ---- restricted open-shell references (afesp_amd/rohf.py strings these together)
+    def mo_fock_ro(self, nbasis, nalpha, nbeta, h_mo):
+        """-> (F_alpha[n, n], F_beta[n, n], electronic reference energy) of the restricted determinant that fills the first nalpha / nbeta
+        orbitals of the packed MO array resident for nbasis (do_mp2_spatial, read_fcidump, read_fcidump_rohf); symmetric to the bit."""
+        n = int(nbasis)
+        fa, fb, e = np.zeros(n * n), np.zeros(n * n), dbl(0.0)
+        self._chk(self.L.afesp_mo_fock_ro(self.h, n, nalpha, nbeta, _f(h_mo), fa, fb, C.byref(e)))
+        return fa.reshape((n, n), order="F"), fb.reshape((n, n), order="F"), e.value
+
+    def read_fcidump_rohf(self, path, want_eri=False) -> FcidumpIn:
+        """Reads a restricted FCIDUMP with MS2 >= 0 (no UHF flag) onto the device (afesp_read_fcidump_rohf): the packed array is resident as
+        read_fcidump leaves it; fock_a / fock_b are the two spin Fock operators of the determinant, fock_offdiag3 their largest
+        off-diagonal elements by block (reported, not judged: the orbitals of such a file are not canonical)."""
+        hd = scan_fcidump(path)
+        if hd.uhf or hd.ms2 < 0 or (hd.nelec + hd.ms2) % 2:
+            raise AfespError("status 1: read_fcidump_rohf: needs a restricted file (no UHF=.TRUE.) with MS2 >= 0 of the parity of NELEC")
+        n, na, nb = hd.norb, (hd.nelec + hd.ms2) // 2, (hd.nelec - hd.ms2) // 2
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        ec, er, nr = dbl(0.0), dbl(0.0), i64()
+        h, fa, fb, fo = np.zeros(n * n), np.zeros(n * n), np.zeros(n * n), np.zeros(3)
+        eri = np.zeros(self.L.afesp_neri(n)) if want_eri else None
+        self._chk(self.L.afesp_read_fcidump_rohf(self.h, str(path).encode(), n, na, nb, vp(h), vp(fa), vp(fb), C.byref(ec), C.byref(er), vp(fo),
+                                                 vp(eri) if want_eri else None, C.byref(nr)))
+        sq = lambda a: a.reshape((n, n), order="F")
+        return FcidumpIn(hd.norb, hd.nelec, hd.ms2, False, ec.value, er.value, float(fo.max()), nr.value, h=sq(h), fock_a=sq(fa), fock_b=sq(fb),
+                         eri=eri, fock_offdiag3=tuple(float(x) for x in fo))
+
+    def mo_rotate_uhf(self, nbasis, u_a, u_b, want_eri=False):
+        """The resident packed MO integrals rotated with u_a / u_b[new orbital, old orbital] into the three blocks do_ump2 leaves ->
+        ((aa|aa) packed, (aa|bb) as [npair, npair], (bb|bb) packed) or Nones; init_cc_uspinorb / uso_init_fock / umo_window follow."""
+        n = int(nbasis)
+        npr = n * (n + 1) // 2
+        aa = np.zeros(self.L.afesp_neri(n)) if want_eri else None
+        bb = np.zeros(self.L.afesp_neri(n)) if want_eri else None
+        ab = np.zeros(npr * npr) if want_eri else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        self._chk(self.L.afesp_mo_rotate_uhf(self.h, n, _f(u_a), _f(u_b), ptr(aa), ptr(ab), ptr(bb)))
+        return aa, (ab.reshape((npr, npr)) if ab is not None else None), bb
+
+    def uso_init_fock(self, nbasis, nalpha, nbeta, fock_a, fock_b, diis_nerr=8):
+        """The spin-orbital state of init_cc_uspinorb from the resident three blocks with the full spin Fock matrices of the same orbitals
+        (levels: their diagonals; f_ov and the off-diagonal f_oo / f_vv enter the equations) -> sum f_ia^2 / D_ia + 1/4 sum <ij||ab>^2 /
+        D_ijab, in semicanonical orbitals the ROHF-MBPT(2) energy.  The so_* methods drive the state."""
+        self.so_o = int(nalpha + nbeta)
+        self.so_v = int(2 * nbasis - self.so_o)
+        e2 = dbl(0.0)
+        self._chk(self.L.afesp_ccsd_uso_init_fock(self.h, nbasis, nalpha, nbeta, _f(fock_a), _f(fock_b), diis_nerr, C.byref(e2)))
+        return e2.value
+
     # ---- spin-orbital path: do_ccsd_spinorb (src/ccsd.f90:71-277), do_ccsd_t_spinorb (:1812-1922)
     SO_SHAPES = {"F_vv": "vv", "F_oo": "oo", "F_ov": "ov", "W_oooo": "oooo", "W_vvvv": "vvvv", "W_ovvo": "ovvo", "tau": "oovv",
-                 "tau_tilde": "oovv", "oovv": "oovv", "vvvv": "vvvv", "t1": "ov", "t2": "oovv"}
+                 "tau_tilde": "oovv", "oovv": "oovv", "vvvv": "vvvv", "t1": "ov", "t2": "oovv", "f_ov": "ov", "f_oo": "oo", "f_vv": "vv"}
 
     def init_cc_spinorb(self, nbasis, nel, canon_levels, eri_mo=None, diis_nerr=8, foo_as_published=False):
         self.so_o, self.so_v = int(nel), int(2 * nbasis - nel)

@@ -121,6 +121,30 @@ def read(path) -> Fcidump:
     return rec
 
 
+def write(path, h, eri, nelec, ms2=0, ecore=0.0, threshold=0.0) -> int:
+    """A restricted FCIDUMP (no UHF flag; ms2 > 0: a restricted open-shell determinant) from h[n, n] and the 8-fold packed eri, every value
+    with 17 significant digits (a reader gets the doubles back to the bit); elements with |x| <= threshold are left out.  -> lines after
+    the header."""
+    h = np.asarray(h, dtype=np.float64)
+    n = h.shape[0]
+    lines = []
+    p, q = np.tril_indices(n)
+    pq = p * (p + 1) // 2 + q
+    for a in range(len(pq)):
+        for b in range(a + 1):
+            x = eri[pq[a] * (pq[a] + 1) // 2 + pq[b]]
+            if abs(x) > threshold:
+                lines.append(f"{x:24.16E} {p[a] + 1:3d} {q[a] + 1:3d} {p[b] + 1:3d} {q[b] + 1:3d}")
+    for a in range(len(pq)):
+        if abs(h[p[a], q[a]]) > threshold:
+            lines.append(f"{h[p[a], q[a]]:24.16E} {p[a] + 1:3d} {q[a] + 1:3d}   0   0")
+    lines.append(f"{ecore:24.16E}   0   0   0   0")
+    with open(path, "w") as fh:
+        fh.write(f" &FCI NORB={n:3d},NELEC={int(nelec):3d},MS2={int(ms2):2d},\n  ORBSYM=" + "1," * n + "\n  ISYM=1,\n &END\n")
+        fh.write("\n".join(lines) + "\n")
+    return len(lines)
+
+
 def _coulomb_exchange(eri, n):
     """J(p,i) = (pp|ii), K(p,i) = (pi|pi) of a packed array"""
     p, i = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")

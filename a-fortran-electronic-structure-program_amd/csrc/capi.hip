@@ -318,6 +318,7 @@ int afesp_ctx_create(int device, afesp_ctx** out)
                 timed("triples", preload_triples);
                 timed("ccsd_so", preload_ccsd_so);
                 timed("uhf", preload_uhf_kernels);
+                timed("integrals", preload_integrals);
                 if (knobs().preload_gett) timed("gett", preload_gett);
             });
         }
@@ -794,6 +795,47 @@ int afesp_read_fcidump_uhf(afesp_ctx* ctx, const char* path, int64_t nbasis, int
     });
 }
 
+// ---------------------------------------------------------------- restricted open-shell references
+int afesp_mo_fock_ro(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* h_mo, double* fock_a, double* fock_b,
+                     double* e_ref_elec)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (nbasis <= 0 || nbasis > 1024 || nalpha < 0 || nbeta < 0 || nalpha < nbeta || nalpha > nbasis || !h_mo || !fock_a || !fock_b ||
+            !e_ref_elec)
+            throw Error(1, "afesp_mo_fock_ro: bad extents or a NULL argument (need 0 <= nbeta <= nalpha <= nbasis)");
+        if (!ctx->in.mo || ctx->in.mo_n != nbasis)
+            throw Error(1, "afesp_mo_fock_ro: no packed MO integrals resident for this basis size (afesp_ao2mo_mp2 / afesp_read_fcidump / "
+                           "afesp_read_fcidump_rohf)");
+        *e_ref_elec = mo_fock_ro(cx, ctx->in, nbasis, nalpha, nbeta, h_mo, fock_a, fock_b);
+    });
+}
+
+int afesp_read_fcidump_rohf(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nalpha, int64_t nbeta, double* h_mo, double* fock_a,
+                            double* fock_b, double* e_core, double* e_ref, double* fock_offdiag, double* eri_mo_packed, int64_t* nread)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (!path) throw Error(1, "afesp_read_fcidump_rohf: path is NULL");
+        if (nbasis <= 0 || nbasis > 1024 || nalpha < 0 || nbeta < 0 || nalpha < nbeta || nalpha > nbasis)
+            throw Error(1, "afesp_read_fcidump_rohf: bad extents (need 0 <= nbeta <= nalpha <= nbasis)");
+        FcidumpResult r;
+        r.h[0] = h_mo; r.fock[0] = fock_a; r.fock[1] = fock_b; r.eri[0] = eri_mo_packed;
+        read_fcidump_rohf(cx, ctx->in, ctx->cc, path, nbasis, nalpha, nbeta, r);
+        if (e_core) *e_core = r.e_core;
+        if (e_ref) *e_ref = r.e_ref;
+        if (fock_offdiag)
+            for (int k = 0; k < 3; ++k) fock_offdiag[k] = r.fock_offdiag3[k];
+        if (nread) *nread = r.nread;
+    });
+}
+
+int afesp_mo_rotate_uhf(afesp_ctx* ctx, int64_t nbasis, const double* u_a, const double* u_b, double* eri_aa, double* eri_ab, double* eri_bb)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (nbasis <= 0 || nbasis > 1024 || !u_a || !u_b) throw Error(1, "afesp_mo_rotate_uhf: bad extents or a NULL rotation");
+        mo_rotate_uhf(cx, ctx->in, nbasis, u_a, u_b, eri_aa, eri_ab, eri_bb);
+    });
+}
+
 // ---------------------------------------------------------------- spin-orbital path
 int afesp_ccsd_so_init(afesp_ctx* ctx, int64_t nbasis, int64_t nel, const double* eri_mo_packed, const double* canon_levels,
                        int diis_n_errmat, int flags)
@@ -889,9 +931,10 @@ int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int6
         struct { const char* n; const Tensor* t; } tab[] = {
             {"F_vv", &s.F_vv}, {"F_oo", &s.F_oo}, {"F_ov", &s.F_ov}, {"W_oooo", &s.W_oooo}, {"W_vvvv", &s.W_vvvv},
             {"W_ovvo", &s.W_ovvo}, {"tau", &s.tau}, {"tau_tilde", &s.tau_t}, {"oovv", &s.oovv}, {"vvvv", &s.vvvv},
-            {"t1", &s.t1}, {"t2", &s.t2}};
+            {"t1", &s.t1}, {"t2", &s.t2}, {"f_ov", &s.f_ov}, {"f_oo", &s.f_oo}, {"f_vv", &s.f_vv}};
         for (auto& e : tab)
             if (!strcmp(e.n, name)) {
+                if (!e.t->d) throw Error(1, std::string("afesp_ccsd_so_get_tensor: this state holds no ") + name + " (afesp_ccsd_uso_init_fock makes one that does)");
                 if (e.t->size() > capacity) throw Error(1, std::string("afesp_ccsd_so_get_tensor: buffer too small for ") + name);
                 AFESP_HIP(hipMemcpyAsync(out, e.t->d, sizeof(double) * e.t->size(), hipMemcpyDeviceToHost, cx.stream));
                 cx.sync();
@@ -1008,6 +1051,31 @@ int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t 
             throw Error(1, "afesp_ccsd_uso_init: the dense spin-orbital state of this system does not fit the free device memory");
         so_init_uhf(cx, ctx->so, (int)nbasis, (int)nalpha, (int)nbeta, ctx->in.uhf_aa, ctx->in.uhf_bb, ctx->in.uhf_ab, levels_a, levels_b, diis_n_errmat);
         ctx->so.amp_epoch = ++cx.amp_clock;
+    });
+}
+
+int afesp_ccsd_uso_init_fock(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* fock_a, const double* fock_b,
+                             int diis_n_errmat, double* e_mp2)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (nbasis <= 0 || nbasis > 512 || nalpha < 0 || nbeta < 0 || nalpha > nbasis || nbeta > nbasis || nalpha + nbeta <= 0 ||
+            nalpha + nbeta >= 2 * nbasis || !fock_a || !fock_b)
+            throw Error(1, "afesp_ccsd_uso_init_fock: bad extents");
+        if (!ctx->in.uhf_aa || ctx->in.uhf_n != nbasis)
+            throw Error(1, "afesp_ccsd_uso_init_fock: no UHF MO integrals resident for this basis size (call afesp_mo_rotate_uhf or "
+                           "afesp_ao2mo_ump2 first)");
+        const int64_t o = nalpha + nbeta, v = 2 * nbasis - o;
+        cx.drop_scratch("ao2mo_");   // the transform's temporaries
+        ctx->so_programs_reset();
+        so_free(cx, ctx->so);        // (a previous state's memory counts as available)
+        size_t free_b = 0, total_b = 0;
+        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+        if (so_state_bytes(o, v, diis_n_errmat) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+            throw Error(1, "afesp_ccsd_uso_init_fock: the dense spin-orbital state of this system does not fit the free device memory");
+        const double e2 = so_init_fock(cx, ctx->so, (int)nbasis, (int)nalpha, (int)nbeta, ctx->in.uhf_aa, ctx->in.uhf_bb, ctx->in.uhf_ab, fock_a,
+                                       fock_b, diis_n_errmat);
+        ctx->so.amp_epoch = ++cx.amp_clock;
+        if (e_mp2) *e_mp2 = e2;
     });
 }
 

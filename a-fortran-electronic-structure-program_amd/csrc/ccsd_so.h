@@ -26,6 +26,12 @@ struct SOState : DiisRing {
     double *va = nullptr, *ta = nullptr, *pa = nullptr;
     int64_t* lad_tab = nullptr;
     int64_t lad_ka = 0, lad_na = 0;  // even leading dimensions: v(v-1)/2 and o(o-1)/2 rounded up
+    // A state with a full Fock matrix (so_init_fock: a non-HF reference, e.g. a restricted open-shell determinant): the levels are its
+    // diagonal (lev); f_ov(i,a), the off-diagonal f_oo(m,i) and the off-diagonal f_vv(a,e) in the state's spin-orbital order enter
+    // Stanton's Eqs. 1-5 as extra terms.  Null on every other state, whose launches are those of before.
+    bool fock = false;
+    Tensor f_ov, f_oo, f_vv;
+    double f_offdiag = 0.0;          // largest |f_oo|, |f_vv| off-diagonal element: (T) is defined for (semi)canonical orbitals only
 };
 
 // eri_mo_dev: packed chemist MO integrals on the device (length neri(nbasis)); e_host: spatial orbital energies (host)
@@ -37,6 +43,11 @@ void so_init(Context& cx, SOState& s, int nbasis, int nel, const double* eri_mo_
 // pq alpha, rs beta.  ea / eb: the n alpha / beta orbital energies (host).  F_mi always takes Stanton's published order.
 void so_init_uhf(Context& cx, SOState& s, int nbasis, int na, int nb, const double* aa, const double* bb, const double* ab,
                  const double* ea_host, const double* eb_host, int diis_nerr);
+// The UHF-ordered state on orbitals that do not diagonalise the spin Fock operators fa / fb (n x n, host, symmetric): levels from their
+// diagonals, the rest kept as f_ov / f_oo / f_vv; the start amplitudes are t1 = f_ia / D_ia, t2 = <ij||ab> / D_ijab and the return value is
+// sum f_ia^2 / D_ia + 1/4 sum <ij||ab>^2 / D_ijab (in semicanonical orbitals: the ROHF-MBPT(2) energy).
+double so_init_fock(Context& cx, SOState& s, int nbasis, int na, int nb, const double* aa, const double* bb, const double* ab,
+                    const double* fa_host, const double* fb_host, int diis_nerr);
 // device bytes the dense spin-orbital state of o occupied and v virtual spin orbitals needs (iteration and (T) working set)
 double so_state_bytes(int64_t o, int64_t v, int diis_nerr);
 void so_free(Context& cx, SOState& s);

@@ -76,12 +76,14 @@ __global__ void so_denominators_lev_kernel(double* D1, double* D2, const double*
 
 // ccsd.f90:437-448
 }  // namespace
+static void preload_ccsd_so_fock();
 void preload_ccsd_so()
 {
     first_use_touch(reinterpret_cast<const void*>(slice_asym_kernel));
     first_use_touch(reinterpret_cast<const void*>(slice_asym_uhf_kernel));
     first_use_touch(reinterpret_cast<const void*>(so_denominators_lev_kernel));
     (void)hipGetLastError();
+    preload_ccsd_so_fock();
 }
 namespace {
 __global__ void so_denominators_kernel(double* D1, double* D2, const double* e, int o, int v)
@@ -200,6 +202,57 @@ __global__ void so_g_kernel(double* G, const double* F_oo, const double* Y, int 
     }
 }
 
+// ---- the Fock terms of a state with a full Fock matrix (so_init_fock), Stanton et al. Eqs. 3-5: the element-wise parts
+// F_vv(a,e) += f_ae (a != e; the diagonal of f_vv is stored as zero), F_oo(m,i) += f_mi likewise, F_ov(m,e) += f_me
+__global__ void so_fock_f_kernel(double* F_vv, double* F_oo, double* F_ov, const double* f_vv, const double* f_oo, const double* f_ov, int o, int v)
+{
+    const int64_t nvv = (int64_t)v * v, noo = (int64_t)o * o, nov = (int64_t)o * v;
+    SO_STRIDE(x, nvv + noo + nov)
+    {
+        if (x < nvv) F_vv[x] += f_vv[x];
+        else if (x < nvv + noo) F_oo[x - nvv] += f_oo[x - nvv];
+        else F_ov[x - nvv - noo] += f_ov[x - nvv - noo];
+    }
+}
+// y += x (the f_ia of the T1 residual, Eq. 1)
+__global__ void so_add_kernel(double* y, const double* x, int64_t n)
+{
+    SO_STRIDE(i, n) y[i] += x[i];
+}
+// out[0] += sum f_ia t_ia behind so_energy_kernel / so_sum2_kernel: one block, a fixed order
+__global__ void so_energy_fock_kernel(double* out, const double* f_ov, const double* t1, int64_t n)
+{
+    __shared__ double red[TB];
+    double s = 0.0;
+    for (int64_t x = threadIdx.x; x < n; x += TB) s += f_ov[x] * t1[x];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] += red[0];
+}
+// partial[block] = sum f_ia^2 / D_ia (x < o v) + 1/4 sum <ij||ab>^2 / D_ijab over the block's elements; summed by so_sum2_kernel
+__global__ void so_mp2_fock_kernel(double* partial, const double* oovv, const double* D2, const double* f_ov, const double* D1, int o, int v)
+{
+    __shared__ double red[TB];
+    const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
+    double e = 0.0;
+    SO_STRIDE(x, n2)
+    {
+        e += 0.25 * oovv[x] * oovv[x] / D2[x];
+        if (x < n1) e += f_ov[x] * f_ov[x] / D1[x];
+    }
+    red[threadIdx.x] = e;
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
 // pairs x < y are numbered y(y-1)/2 + x
 __device__ __forceinline__ void unpair_lt(int64_t p, int& lo, int& hi)
 {
@@ -250,6 +303,17 @@ __global__ void so_ladder_expand_kernel(double* r2, const double* pa, int o, int
     }
 }
 
+}  // namespace
+// ... and the kernels only a state with a full Fock matrix launches (so_init_fock)
+static void preload_ccsd_so_fock()
+{
+    first_use_touch(reinterpret_cast<const void*>(so_fock_f_kernel));
+    first_use_touch(reinterpret_cast<const void*>(so_add_kernel));
+    first_use_touch(reinterpret_cast<const void*>(so_energy_fock_kernel));
+    first_use_touch(reinterpret_cast<const void*>(so_mp2_fock_kernel));
+    (void)hipGetLastError();
+}
+namespace {
 #define SO_LAUNCH(kernel, n, ...)                                                         \
     do {                                                                                  \
         if ((n) > 0) {                                                                    \
@@ -388,13 +452,90 @@ void so_init_uhf(Context& cx, SOState& s, int nbasis, int na, int nb, const doub
     so_init_tail(cx, s, diis_nerr);
 }
 
+static double so_init_fock_terms(Context& cx, SOState& s, int n, int na, int nb, const double* fa_host, const double* fb_host);
+double so_init_fock(Context& cx, SOState& s, int nbasis, int na, int nb, const double* aa, const double* bb, const double* ab,
+                    const double* fa_host, const double* fb_host, int diis_nerr)
+{
+    const int n = nbasis;
+    std::vector<double> ea((size_t)std::max(n, 1)), eb((size_t)std::max(n, 1));
+    for (int p = 0; p < n; ++p) {
+        ea[(size_t)p] = fa_host[p + (int64_t)n * p];
+        eb[(size_t)p] = fb_host[p + (int64_t)n * p];
+    }
+    so_init_uhf(cx, s, nbasis, na, nb, aa, bb, ab, ea.data(), eb.data(), diis_nerr);   // (checks the extents)
+    // so_init_uhf leaves a ready state WITHOUT the Fock terms: it must not survive a failure of what follows
+    s.ready = false;
+    try {
+        return so_init_fock_terms(cx, s, nbasis, na, nb, fa_host, fb_host);
+    } catch (...) {
+        try { so_free(cx, s); } catch (...) {}
+        throw;
+    }
+}
+
+static double so_init_fock_terms(Context& cx, SOState& s, int n, int na, int nb, const double* fa_host, const double* fb_host)
+{
+    const int o = s.o, v = s.v;
+    const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
+    // spin orbital x of the state: (orbital, spin), in so_init_uhf's order
+    auto orb_of = [&](int x, int& orb, int& sp) {
+        if (x < na) { orb = x; sp = 0; }
+        else if (x < o) { orb = x - na; sp = 1; }
+        else if (x < o + n - na) { orb = na + (x - o); sp = 0; }
+        else { orb = nb + (x - o - (n - na)); sp = 1; }
+    };
+    auto f_of = [&](int x, int y) {
+        int px, sx, py, sy;
+        orb_of(x, px, sx);
+        orb_of(y, py, sy);
+        if (sx != sy) return 0.0;
+        return (sx ? fb_host : fa_host)[px + (int64_t)n * py];
+    };
+    std::vector<double> fov((size_t)ov), foo((size_t)(O * O)), fvv((size_t)(V * V));
+    double off = 0.0;
+    for (int a = 0; a < v; ++a)
+        for (int i = 0; i < o; ++i) fov[(size_t)(i + O * a)] = f_of(i, o + a);
+    for (int i = 0; i < o; ++i)
+        for (int m = 0; m < o; ++m) {
+            const double x = m == i ? 0.0 : f_of(m, i);
+            foo[(size_t)(m + O * i)] = x;
+            off = std::max(off, std::fabs(x));
+        }
+    for (int e = 0; e < v; ++e)
+        for (int a = 0; a < v; ++a) {
+            const double x = a == e ? 0.0 : f_of(o + a, o + e);
+            fvv[(size_t)(a + V * e)] = x;
+            off = std::max(off, std::fabs(x));
+        }
+    s.f_ov = cx.tensor({O, V}); s.f_oo = cx.tensor({O, O}); s.f_vv = cx.tensor({V, V});
+    AFESP_HIP(hipMemcpyAsync(s.f_ov.d, fov.data(), sizeof(double) * ov, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(s.f_oo.d, foo.data(), sizeof(double) * O * O, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(s.f_vv.d, fvv.data(), sizeof(double) * V * V, hipMemcpyHostToDevice, cx.stream));
+    s.fock = true;
+    s.f_offdiag = off;
+    k_div(cx, s.t1.d, s.f_ov.d, s.D1.d, ov);   // t1 = f_ia / D_ia beside so_init_tail's t2 = <ij||ab> / D_ijab
+    const int nblk = (int)std::min<int64_t>((o2v2 + TB - 1) / TB, 1024);
+    double e2 = 0.0;
+    if (o2v2 > 0) {
+        double* partial = cx.scratch("so_energy_partial", 2 * 1024);
+        AFESP_KLAUNCH(so_mp2_fock_kernel, dim3(nblk), dim3(TB), 0, cx.stream, partial, s.oovv.d, s.D2.d, s.f_ov.d, s.D1.d, o, v);
+        AFESP_HIP(hipGetLastError());
+        AFESP_KLAUNCH(so_sum2_kernel, dim3(1), dim3(TB), 0, cx.stream, cx.scal, partial, nblk);
+        AFESP_HIP(hipGetLastError());
+        e2 = host_scalars(cx, 1)[0];
+    }
+    cx.sync();   // (the host images of the Fock blocks)
+    s.ready = true;
+    return e2;
+}
+
 double so_state_bytes(int64_t o, int64_t v, int diis_nerr)
 {
     const double O = (double)o, V = (double)v, npv = V * (V - 1) / 2;
     // slices, the W_abef pair operand va, the o^2 v^2 tensors of the state and the iteration's scratch, the DIIS history, and the
     // (T) operands (vt / tt / vs)
     const double doubles = V * V * V * V + 2 * O * V * V * V + O * O * O * O + 4 * O * O * O * V + npv * npv + (16.0 + 2.0 * diis_nerr) * O * O * V * V +
-                           (V + O + 16) * (V * V * O + V * O * O) + O * O * O * V;
+                           (V + O + 16) * (V * V * O + V * O * O) + O * O * O * V + (V * V + O * O + O * V);   // (last: f_vv, f_oo, f_ov of so_init_fock)
     return 8.0 * doubles;
 }
 
@@ -403,7 +544,8 @@ void so_free(Context& cx, SOState& s)
     if (!s.o) return;
     double* bufs[] = {s.e, s.lev, s.oooo.d, s.ooov.d, s.ovoo.d, s.oovo.d, s.oovv.d, s.ovvo.d, s.ovvv.d, s.vovv.d, s.vvvv.d, s.D1.d,
                       s.D2.d, s.amp, s.r1.d, s.t2_old.d, s.F_vv.d, s.F_oo.d, s.F_ov.d, s.W_oooo.d, s.W_vvvv.d, s.W_ovvo.d,
-                      s.tau.d, s.tau_t.d, s.amp_s, s.hist_t, s.hist_e, s.coef, s.bmat, s.va, s.ta, s.pa, (double*)s.lad_tab, s.t1_w.d};
+                      s.tau.d, s.tau_t.d, s.amp_s, s.hist_t, s.hist_e, s.coef, s.bmat, s.va, s.ta, s.pa, (double*)s.lad_tab, s.t1_w.d,
+                      s.f_ov.d, s.f_oo.d, s.f_vv.d};
     for (double* b : bufs) cx.release(b);
     cx.drop_scratch();
     so_triples_plan_free(s);
@@ -430,6 +572,13 @@ void so_intermediates(Context& cx, SOState& s)
     // Stanton's Eq. 4 order, which is what the reference's shipped ref_out (2022) was computed with.
     C(0.5, s.tau_t, "inef", s.oovv, "mnef", 1.0, s.F_oo, s.foo_as_published ? "mi" : "im");
     C(1.0, s.oovv, "mnef", s.t1, "nf", 0.0, s.F_ov, "me");             // :770-780
+    if (s.fock) {   // Stanton Eqs. 3-5 with f: F_ae += (1 - d_ae) f_ae - 1/2 f_me t_ma, F_mi += (1 - d_mi) f_mi + 1/2 t_ie f_me, F_me += f_me
+        C(-0.5, s.t1, "ma", s.f_ov, "me", 1.0, s.F_vv, "ae");
+        C(0.5, s.f_ov, "me", s.t1, "ie", 1.0, s.F_oo, "mi");
+        SO_KERNEL((Ranges{FR(s.f_vv.d, V * V), FR(s.f_oo.d, O * O), FR(s.f_ov.d, O * V), FR(s.F_vv.d, V * V), FR(s.F_oo.d, O * O), FR(s.F_ov.d, O * V)}),
+                  (Ranges{FR(s.F_vv.d, V * V), FR(s.F_oo.d, O * O), FR(s.F_ov.d, O * V)}), so_fock_f_kernel, V * V + O * O + O * V, s.F_vv.d,
+                  s.F_oo.d, s.F_ov.d, s.f_vv.d, s.f_oo.d, s.f_ov.d, o, v);
+    }
     // ---- build_W, ccsd.f90:799-905
     // Eq. 6, stored W(i,j,m,n) (:842-846)
     Tensor sc = view(cx.scratch("so_sc_oooo", O * O * O * O), {O, O, O, O});
@@ -509,6 +658,8 @@ void so_amplitudes(Context& cx, SOState& s)
     C(1.0, s.t2, "miea", s.F_ov, "me", 1.0, s.r1, "ia");
     C(0.5, s.t2, "mife", s.ovvv, "mafe", 1.0, s.r1, "ia");
     C(-0.5, s.t2, "mnea", s.oovo, "mnei", 1.0, s.r1, "ia");
+    if (s.fock)   // Eq. 1: + f_ia
+        SO_KERNEL((Ranges{FR(s.f_ov.d, O * V), FR(s.r1.d, O * V)}), (Ranges{FR(s.r1.d, O * V)}), so_add_kernel, O * V, s.r1.d, s.f_ov.d, O * V);
     // ---- T2, ccsd.f90:959-1034
     Tensor AB = view(cx.scratch("so_AB", o2v2), {O, O, V, V}), A = view(cx.scratch("so_A", o2v2), {O, O, V, V});
     Tensor Bm = view(cx.scratch("so_B", o2v2), {O, O, V, V});
@@ -547,6 +698,10 @@ int so_energy(Context& cx, SOState& s, double e_tol, double t_tol)
     AFESP_HIP(hipGetLastError());
     AFESP_KLAUNCH(so_sum2_kernel, dim3(2), dim3(TB), 0, cx.stream, cx.scal, partial, nblk);
     AFESP_HIP(hipGetLastError());
+    if (s.fock) {   // + sum f_ia t_ia
+        AFESP_KLAUNCH(so_energy_fock_kernel, dim3(1), dim3(TB), 0, cx.stream, cx.scal, s.f_ov.d, s.t1.d, (int64_t)s.o * s.v);
+        AFESP_HIP(hipGetLastError());
+    }
     double* h = host_scalars(cx, DIIS_FLAG_SLOT + 1);
     diis_check_flag(cx, h);
     s.energy_old = s.energy;

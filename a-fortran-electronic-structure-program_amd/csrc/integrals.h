@@ -98,11 +98,24 @@ struct FcidumpResult {
     double *h[2] = {nullptr, nullptr}, *fock[2] = {nullptr, nullptr}, *levels[2] = {nullptr, nullptr};   // closed shell: [0]; open shell: alpha, beta
     double* eri[3] = {nullptr, nullptr, nullptr};   // packed | aa, bb, ab
     double e_core = 0.0, e_ref = 0.0, fock_offdiag = 0.0;
+    double fock_offdiag3[3] = {0.0, 0.0, 0.0};   // read_fcidump_rohf: occupied-occupied, virtual-virtual (off-diagonal), occupied-virtual
     int64_t nread = 0;
 };
 int fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines);
 void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r);
 void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
+// a restricted open-shell file (no UHF flag, MS2 = na - nb >= 0): read_fcidump's parse, scatter and residency; r.fock[0] / [1] the two spin
+// Fock operators of the determinant (k_fock_ro), r.fock_offdiag3 their largest off-diagonal elements by block
+void read_fcidump_rohf(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
+// The two spin Fock operators of the restricted determinant that fills the first na / nb orbitals, from h (n x n, device) and the packed
+// MO integrals: one wave per pair, fixed summation order, symmetric to the bit (integrals.hip)
+void k_fock_ro(Context& cx, double* fa, double* fb, const double* h, const double* packed, int n, int na, int nb);
+// ... for host matrices on the resident packed MO array (afesp_mo_fock_ro); returns the electronic reference energy
+double mo_fock_ro(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, const double* h_mo, double* fock_a, double* fock_b);
+// The resident packed MO integrals rotated with one orthogonal matrix per spin (new orbital, old orbital) into the three resident blocks
+// of the open-shell path, through ao2mo_ump2's transform forms; the packed array and the AO integrals stay as they are
+void mo_rotate_uhf(Context& cx, Integrals& in, int64_t n, const double* u_a, const double* u_b, double* eri_aa, double* eri_ab, double* eri_bb);
+void preload_integrals();   // first-use resolution of this unit's own kernels of the open-shell path
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
 int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
 

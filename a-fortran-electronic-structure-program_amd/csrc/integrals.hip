@@ -62,6 +62,42 @@ __global__ __launch_bounds__(256) void ao2mo_tables_lo_kernel(uint32_t* colB, in
         if (x < ncol + 128) offCn[x] = x < ncol ? x2 + ld * n * sloc : 0;
     }
 }
+// ---- the two spin Fock operators of a restricted determinant (afesp_mo_fock_ro, afesp_read_fcidump_rohf) out of ONE packed MO array:
+//   F_a(p,q) = h(p,q) + sum_{i < na} [(pq|ii) - (pi|qi)] + sum_{i < nb} (pq|ii),   F_b: na and nb exchanged
+// One wave per pair p >= q, as k_fock_mo: lane l takes i = l, l + 64, ... in rising order -- the Coulomb sum over the doubly occupied
+// orbitals i < nb, the one over the singly occupied ones nb <= i < na and the two exchange sums are kept apart -- the 64 partial sums are
+// added in a fixed butterfly order and both triangles are written from one register: symmetric to the bit, the same on every run.
+__global__ __launch_bounds__(256) void fock_ro_kernel(double* __restrict__ fa, double* __restrict__ fb, const double* __restrict__ h,
+                                                      const double* __restrict__ packed, int n, int na, int nb)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t np = (int64_t)n * (n + 1) / 2, w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= np) return;   // (whole waves leave)
+    int64_t p = (int64_t)((sqrt(8.0 * (double)w + 1.0) - 1.0) * 0.5);
+    while (p * (p + 1) / 2 > w) --p;
+    while ((p + 1) * (p + 2) / 2 <= w) ++p;
+    const int64_t q = w - p * (p + 1) / 2;
+    auto tri = [](int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; };
+    double jd = 0.0, js = 0.0, kd = 0.0, ks = 0.0;   // Coulomb / exchange over the doubly / the singly occupied orbitals
+    for (int64_t i = lane; i < na; i += 64) {
+        const double J = packed[tri(w, tri(i, i))], K = packed[tri(tri(p, i), tri(q, i))];
+        if (i < nb) { jd += J; kd += K; }
+        else { js += J; ks += K; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        jd += __shfl_xor(jd, off, 64);
+        js += __shfl_xor(js, off, 64);
+        kd += __shfl_xor(kd, off, 64);
+        ks += __shfl_xor(ks, off, 64);
+    }
+    if (lane == 0) {
+        const int64_t lo = p + (int64_t)n * q, up = q + (int64_t)n * p;
+        const double h0 = h[lo], jj = (jd + jd) + js;
+        const double va = h0 + (jj - (kd + ks)), vb = h0 + (jj - kd);
+        fa[lo] = va; fa[up] = va;
+        fb[lo] = vb; fb[up] = vb;
+    }
+}
 }  // extern "C"
 
 namespace {
@@ -515,33 +551,14 @@ double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, 
 // (aa|aa), (bb|bb) and (aa|bb) from one set of AO integrals: the first pair of quarter transforms with C_a is shared by the first and
 // the third block, the second pair runs with C_a (packed, RS <= PQ) and with C_b (every RS: no 8-fold symmetry is left), then the whole
 // transform once more with C_b.
-double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
-                  const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab, double* eri_bb)
+// The launches of that transform, for whichever packed source `src` (the AO integrals: afesp_ao2mo_ump2; the resident MO integrals:
+// afesp_mo_rotate_uhf) and coefficient pair on the host; the three blocks are the resident ones
+static void uhf_blocks_from_packed(Context& cx, Integrals& in, const Ao2moForm& form, int64_t n, const double* src, const double* coeff_a,
+                                   const double* coeff_b)
 {
-    const Ao2moForm form(n, true);
-    if (form.blocked)
-        throw Error(1, "afesp_ao2mo_ump2: basis too large (only the slab-blocked transform fits, and it has no open-shell form)");
-    if (!eri_packed && (!in.ao || in.ao_n != n))
-        throw Error(1, "afesp_ao2mo_ump2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
-    cx.drop_scratch("t_");
-    cx.drop_scratch("ao2mo_");   // (the temporaries are sized below; what they held goes back to the arena)
-    const int64_t ne = neri_of(n), np = npair_of(n);
-    // device memory: the temporaries (two npair^2 for the pair form, three n^2 npair for the gather-GEMM form) and, for a new
-    // basis size, the three result blocks, against what the device has free plus what the context's arena holds idle
-    const double tmp = form.pair ? 2.0 * np * np : 3.0 * n * n * np;
-    const double blocks = (in.uhf_n == n && in.uhf_aa) ? 0.0 : 2.0 * ne + (double)np * np;
-    if (in.uhf_n != n) in.release_uhf(cx);   // (blocks of another basis size: returned before their successors are sized)
-    size_t free_b = 0, total_b = 0;
-    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (8.0 * (tmp + blocks + 4.0 * n * n) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
-        throw Error(1, "afesp_ao2mo_ump2: the open-shell transform of this basis does not fit the free device memory");
-    in.adopt_uhf(cx, n);
+    const int64_t np = npair_of(n);
     double *aa = in.uhf_aa, *bb = in.uhf_bb, *ab = in.uhf_ab;
-    const double* ao = in.ao;
-    if (eri_packed) {   // (into the beta-beta block: every read of the AO integrals precedes its one write)
-        AFESP_HIP(hipMemcpyAsync(bb, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
-        ao = bb;
-    }
+    const double* ao = src;
     Tensor Ca = view(cx.scratch("ao2mo_c", n * n), {n, n}), Cb = view(cx.scratch("ao2mo_cb", n * n), {n, n});
     AFESP_HIP(hipMemcpyAsync(Ca.d, coeff_a, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
     AFESP_HIP(hipMemcpyAsync(Cb.d, coeff_b, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
@@ -571,6 +588,40 @@ double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb,
         second_pair(cx, Cb, Tb, Ta, Tc);
         k_pack_pairs(cx, bb, Tc.d, (int)n);
     }
+}
+// device memory of that transform: the temporaries (two npair^2 for the pair form, three n^2 npair for the gather-GEMM form) and, for a
+// new basis size, the three result blocks, against what the device has free plus what the context's arena holds idle
+static void uhf_blocks_fit(Context& cx, Integrals& in, const Ao2moForm& form, int64_t n, const char* who)
+{
+    const int64_t ne = neri_of(n), np = npair_of(n);
+    const double tmp = form.pair ? 2.0 * np * np : 3.0 * n * n * np;
+    const double blocks = (in.uhf_n == n && in.uhf_aa) ? 0.0 : 2.0 * ne + (double)np * np;
+    if (in.uhf_n != n) in.release_uhf(cx);   // (blocks of another basis size: returned before their successors are sized)
+    size_t free_b = 0, total_b = 0;
+    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+    if (8.0 * (tmp + blocks + 4.0 * n * n) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+        throw Error(1, std::string(who) + ": the open-shell transform of this basis does not fit the free device memory");
+}
+
+double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
+                  const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab, double* eri_bb)
+{
+    const Ao2moForm form(n, true);
+    if (form.blocked)
+        throw Error(1, "afesp_ao2mo_ump2: basis too large (only the slab-blocked transform fits, and it has no open-shell form)");
+    if (!eri_packed && (!in.ao || in.ao_n != n))
+        throw Error(1, "afesp_ao2mo_ump2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
+    cx.drop_scratch("t_");
+    cx.drop_scratch("ao2mo_");   // (the temporaries are sized below; what they held goes back to the arena)
+    const int64_t ne = neri_of(n);
+    uhf_blocks_fit(cx, in, form, n, "afesp_ao2mo_ump2");
+    in.adopt_uhf(cx, n);
+    const double* ao = in.ao;
+    if (eri_packed) {   // (into the beta-beta block: every read of the AO integrals precedes its one write)
+        AFESP_HIP(hipMemcpyAsync(in.uhf_bb, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
+        ao = in.uhf_bb;
+    }
+    uhf_blocks_from_packed(cx, in, form, n, ao, coeff_a, coeff_b);
     return ump2_of_blocks(cx, in, levels_a, levels_b, na, nb, eri_aa, eri_ab, eri_bb);
 }
 
@@ -588,6 +639,68 @@ double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, 
     if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, in.uhf_ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
     return e2;
+}
+
+// The resident packed MO integrals in two new orbital sets, one per spin (afesp_mo_rotate_uhf): the mixed-spin transform
+// above with the packed MO array in the place of the AO integrals and u_s (new orbital, old orbital) in the place of the coefficients.
+// The source is only read; the three blocks are left resident as ao2mo_ump2 leaves them.
+void mo_rotate_uhf(Context& cx, Integrals& in, int64_t n, const double* u_a, const double* u_b, double* eri_aa, double* eri_ab, double* eri_bb)
+{
+    const Ao2moForm form(n, true);
+    if (form.blocked)
+        throw Error(1, "afesp_mo_rotate_uhf: basis too large (only the slab-blocked transform fits, and it has no open-shell form)");
+    if (!in.mo || in.mo_n != n)
+        throw Error(1, "afesp_mo_rotate_uhf: no packed MO integrals resident for this basis size (afesp_ao2mo_mp2 / afesp_read_fcidump / "
+                       "afesp_read_fcidump_rohf)");
+    cx.drop_scratch("t_");
+    cx.drop_scratch("ao2mo_");
+    uhf_blocks_fit(cx, in, form, n, "afesp_mo_rotate_uhf");
+    in.adopt_uhf(cx, n);
+    uhf_blocks_from_packed(cx, in, form, n, in.mo, u_a, u_b);
+    const int64_t ne = neri_of(n), np = npair_of(n);
+    if (eri_aa) AFESP_HIP(hipMemcpyAsync(eri_aa, in.uhf_aa, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (eri_bb) AFESP_HIP(hipMemcpyAsync(eri_bb, in.uhf_bb, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    if (eri_ab) AFESP_HIP(hipMemcpyAsync(eri_ab, in.uhf_ab, sizeof(double) * np * np, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+void k_fock_ro(Context& cx, double* fa, double* fb, const double* h, const double* packed, int n, int na, int nb)
+{
+    const int64_t waves = npair_of(n);
+    AFESP_KLAUNCH(fock_ro_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cx.stream, fa, fb, h, packed, n, na, nb);
+    AFESP_HIP(hipGetLastError());
+}
+void preload_integrals()
+{
+    first_use_touch(reinterpret_cast<const void*>(fock_ro_kernel));
+    (void)hipGetLastError();
+}
+// 1/2 sum_{i < na} [h + F_a](i,i) + 1/2 sum_{i < nb} [h + F_b](i,i), host matrices
+static double ro_reference_energy(const double* h, const double* fa, const double* fb, int64_t n, int64_t na, int64_t nb)
+{
+    double ea = 0.0, eb = 0.0;
+    for (int64_t i = 0; i < na; ++i) ea += h[i + n * i] + fa[i + n * i];
+    for (int64_t i = 0; i < nb; ++i) eb += h[i + n * i] + fb[i + n * i];
+    return 0.5 * ea + 0.5 * eb;
+}
+
+double mo_fock_ro(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, const double* h_mo, double* fock_a, double* fock_b)
+{
+    const int64_t n2 = (n * n + 15) / 16 * 16;
+    double* buf = cx.alloc_raw(3 * n2);   // h | F_a | F_b; back to the arena before the call ends, on every path
+    try {
+        AFESP_HIP(hipMemcpyAsync(buf, h_mo, sizeof(double) * n * n, hipMemcpyHostToDevice, cx.stream));
+        k_fock_ro(cx, buf + n2, buf + 2 * n2, buf, in.mo, (int)n, (int)na, (int)nb);
+        AFESP_HIP(hipMemcpyAsync(fock_a, buf + n2, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(fock_b, buf + 2 * n2, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    } catch (...) {
+        (void)hipStreamSynchronize(cx.stream);
+        try { cx.release(buf); } catch (...) {}
+        throw;
+    }
+    cx.release(buf);
+    return ro_reference_energy(h_mo, fock_a, fock_b, n, na, nb);
 }
 
 // The active orbital window [nfc, n - nfv) of the resident (or handed-in) packed MO integrals: a gather after the full transform
@@ -962,6 +1075,73 @@ int fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, 
     return 0;
 }
 
+namespace {
+// What afesp_read_fcidump and afesp_read_fcidump_rohf share once the header has passed their own checks: the body of a restricted file
+// into a new packed array and h, the Fock operator(s) of the determinant that fills the first na (alpha) / nb (beta) orbitals -- ro:
+// the two spin operators (k_fock_ro), else the closed-shell one (na == nb) -- and, only when all of that was good, residency.
+void read_restricted(Context& cx, Integrals& in, CCState& cc, FILE* f, const char* who, const fcidump::Header& h, int64_t n, int64_t na,
+                     int64_t nb, bool ro, FcidumpResult& r)
+{
+    const int64_t ne = neri_of(n), np = npair_of(n), n2 = up16(n * n), nf = ro ? 2 : 1;
+    FcidumpTargets T{};
+    T.n = n; T.np = np; T.ne = ne; T.uhf = 0;
+    T.nslots = ne + np + 1;
+    fcidump_fit(cx, who, (double)ne + (double)T.nslots / 64 + (1.0 + nf) * n2 + ((double)knobs().fcidump_chunk_kib * 1024 / 2));
+    ReadScratch rs(cx);
+    double* packed = rs.get(ne);
+    double* small = rs.get((1 + nf) * n2 + 16);   // h | F (| F_b) | core energy
+    T.eri[0] = packed;
+    T.h[0] = small;
+    T.ecore = small + (1 + nf) * n2;
+    AFESP_HIP(hipMemsetAsync(packed, 0, sizeof(double) * ne, cx.stream));
+    AFESP_HIP(hipMemsetAsync(small, 0, sizeof(double) * ((1 + nf) * n2 + 16), cx.stream));
+    const FcidumpRead got = fcidump_read_body(cx, rs, f, who, h, T);
+    double* F = small + n2;
+    if (ro) k_fock_ro(cx, F, F + n2, T.h[0], packed, (int)n, (int)na, (int)nb);
+    else k_fock_mo(cx, F, T.h[0], packed, (int)n, (int)na, 2.0);
+    std::vector<double> hh((size_t)(n * n)), ff[2];
+    AFESP_HIP(hipMemcpyAsync(hh.data(), T.h[0], sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+    for (int64_t s = 0; s < nf; ++s) {
+        ff[s].resize((size_t)(n * n));
+        AFESP_HIP(hipMemcpyAsync(ff[s].data(), F + s * n2, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
+    }
+    if (r.eri[0]) AFESP_HIP(hipMemcpyAsync(r.eri[0], packed, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    // from here on nothing fails: the new array takes the place of the resident one, as a transform's result would
+    cx.drop_scratch("t_");
+    in.release_uhf(cx);
+    in.drop_mo(cx, cc);
+    rs.keep(packed);
+    in.set_mo(packed, n);
+    if (r.h[0]) memcpy(r.h[0], hh.data(), sizeof(double) * n * n);
+    for (int64_t s = 0; s < nf; ++s)
+        if (r.fock[s]) memcpy(r.fock[s], ff[s].data(), sizeof(double) * n * n);
+    r.e_core = got.e_core;
+    r.nread = got.nread;
+    if (ro) {
+        r.e_ref = got.e_core + ro_reference_energy(hh.data(), ff[0].data(), ff[1].data(), n, na, nb);
+        // largest |F| of either spin among the occupied-occupied off-diagonal, the virtual-virtual off-diagonal and the occupied-virtual elements
+        for (int k = 0; k < 3; ++k) r.fock_offdiag3[k] = 0.0;
+        for (int s = 0; s < 2; ++s) {
+            const int64_t o = s ? nb : na;
+            for (int64_t q = 0; q < n; ++q)
+                for (int64_t p = 0; p < n; ++p) {
+                    if (p == q) continue;
+                    const int k = (p < o && q < o) ? 0 : (p >= o && q >= o) ? 1 : 2;
+                    r.fock_offdiag3[k] = std::max(r.fock_offdiag3[k], std::fabs(ff[s][(size_t)(p + n * q)]));
+                }
+        }
+        return;
+    }
+    double e = got.e_core;
+    for (int64_t i = 0; i < na; ++i) e += hh[(size_t)(i + n * i)] + ff[0][(size_t)(i + n * i)];
+    if (r.levels[0])
+        for (int64_t p = 0; p < n; ++p) r.levels[0][p] = ff[0][(size_t)(p + n * p)];
+    r.e_ref = e;
+    r.fock_offdiag = offdiag_max(ff[0].data(), n);
+}
+}  // namespace
+
 void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r)
 {
     const char* who = "afesp_read_fcidump";
@@ -973,43 +1153,24 @@ void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int
     if (h.norb != n || h.nelec != 2 * nocc || h.ms2 != 0)
         throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
                            std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nocc " + std::to_string(nocc));
-    const int64_t ne = neri_of(n), np = npair_of(n), n2 = up16(n * n);
-    FcidumpTargets T{};
-    T.n = n; T.np = np; T.ne = ne; T.uhf = 0;
-    T.nslots = ne + np + 1;
-    fcidump_fit(cx, who, (double)ne + (double)T.nslots / 64 + 2.0 * n2 + ((double)knobs().fcidump_chunk_kib * 1024 / 2));
-    ReadScratch rs(cx);
-    double* packed = rs.get(ne);
-    double* small = rs.get(2 * n2 + 16);   // h | F | core energy
-    T.eri[0] = packed;
-    T.h[0] = small;
-    T.ecore = small + 2 * n2;
-    AFESP_HIP(hipMemsetAsync(packed, 0, sizeof(double) * ne, cx.stream));
-    AFESP_HIP(hipMemsetAsync(small, 0, sizeof(double) * (2 * n2 + 16), cx.stream));
-    const FcidumpRead got = fcidump_read_body(cx, rs, file.f, who, h, T);
-    double* F = small + n2;
-    k_fock_mo(cx, F, T.h[0], packed, (int)n, (int)nocc, 2.0);
-    std::vector<double> hh((size_t)(n * n)), ff((size_t)(n * n));
-    AFESP_HIP(hipMemcpyAsync(hh.data(), T.h[0], sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
-    AFESP_HIP(hipMemcpyAsync(ff.data(), F, sizeof(double) * n * n, hipMemcpyDeviceToHost, cx.stream));
-    if (r.eri[0]) AFESP_HIP(hipMemcpyAsync(r.eri[0], packed, sizeof(double) * ne, hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
-    // from here on nothing fails: the new array takes the place of the resident one, as a transform's result would
-    cx.drop_scratch("t_");
-    in.release_uhf(cx);
-    in.drop_mo(cx, cc);
-    rs.keep(packed);
-    in.set_mo(packed, n);
-    double e = got.e_core;
-    for (int64_t i = 0; i < nocc; ++i) e += hh[(size_t)(i + n * i)] + ff[(size_t)(i + n * i)];
-    if (r.h[0]) memcpy(r.h[0], hh.data(), sizeof(double) * n * n);
-    if (r.fock[0]) memcpy(r.fock[0], ff.data(), sizeof(double) * n * n);
-    if (r.levels[0])
-        for (int64_t p = 0; p < n; ++p) r.levels[0][p] = ff[(size_t)(p + n * p)];
-    r.e_core = got.e_core;
-    r.e_ref = e;
-    r.fock_offdiag = offdiag_max(ff.data(), n);
-    r.nread = got.nread;
+    read_restricted(cx, in, cc, file.f, who, h, n, nocc, nocc, false, r);
+}
+
+// The restricted open-shell file (no UHF flag, MS2 = nalpha - nbeta >= 0): one set of orbitals and integrals, two spin Fock operators
+void read_fcidump_rohf(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)
+{
+    const char* who = "afesp_read_fcidump_rohf";
+    File file(fopen(path, "rb"));
+    if (!file.f) throw Error(1, std::string(who) + ": cannot open " + path);
+    fcidump::Header h;
+    fcidump_open_header(file.f, who, path, h);
+    if (h.uhf) throw Error(1, std::string(who) + ": the file says UHF=.TRUE. (afesp_read_fcidump_uhf reads it)");
+    if (h.ms2 < 0) throw Error(1, std::string(who) + ": MS2 " + std::to_string(h.ms2) + " is negative (more beta than alpha electrons)");
+    if (h.norb != n || h.nelec != na + nb || h.ms2 != na - nb)
+        throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
+                           std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nalpha " + std::to_string(na) + ", nbeta " +
+                           std::to_string(nb));
+    read_restricted(cx, in, cc, file.f, who, h, n, na, nb, true, r);
 }
 
 void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)

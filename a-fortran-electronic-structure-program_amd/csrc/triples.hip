@@ -1103,6 +1103,10 @@ __global__ void so_levels_kernel(double* e_so, const double* e, int n2)
 double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
 {
     if (!s.ready) throw Error(1, "ccsd_so_triples: no converged spin-orbital CCSD state in this context");
+    // (T) is defined in (semi)canonical orbitals only: a guard, not a tolerance
+    if (s.fock && s.f_offdiag > 1e-8)
+        throw Error(1, "ccsd_so_triples: the occupied-occupied / virtual-virtual Fock blocks of this state are not diagonal (largest off-diagonal "
+                       "element " + std::to_string(s.f_offdiag) + "): (T) needs semicanonical orbitals");
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, v2 = V * V;
     const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;
@@ -1145,7 +1149,7 @@ double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
     cx.t_ops_scratch = cx.scratch_epoch;
     cx.t_ops_ts = false;
     cx.t_ops_cr = -1;
-    TriplesIn in{s.lev ? s.lev : e_so, s.t1.d, vs.d, nullptr, s.t2.d, o, v};
+    TriplesIn in{s.lev ? s.lev : e_so, s.t1.d, vs.d, s.fock ? s.f_ov.d : nullptr, s.t2.d, o, v};   // (f_ov in the slot this path leaves free)
     double* Xpool = cx.scratch("t_xpool", 3 * p->nb * vp3);
     double* partial = cx.scratch("t_partial", std::max<int64_t>((int64_t)p->norb * p->nb, 512));
     for (const TriplesPlan::Chunk& ch : p->chunks) {
@@ -1169,8 +1173,12 @@ double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
             gp.wide = true;   // (as in the spin-free plan: K-contiguous operands, Kc a multiple of 16)
             AFESP_HIP(gett_launch(gp, cx.ws, cx.stream));
         }
-        AFESP_KLAUNCH(triples_so_orbit_kernel, dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
-                           p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
+        if (s.fock)
+            AFESP_KLAUNCH((triples_so_orbit_kernel<true>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+                               p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
+        else
+            AFESP_KLAUNCH((triples_so_orbit_kernel<false>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+                               p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
         AFESP_HIP(hipGetLastError());
         // (two stages, 128 blocks first: one block walking the 67 200 partials of the H2O/cc-pVTZ shape took 0.10 ms of a 2.8 ms evaluation)
         sum_partials(cx, cx.scal, partial, 1, p->norb * ch.nt, cx.scratch("t_sum_tmp", 6 * 128));
@@ -1189,6 +1197,7 @@ void preload_triples()
     first_use_touch(reinterpret_cast<const void*>(triples_orbit_kernel<false, true, false>));
     first_use_touch(reinterpret_cast<const void*>(triples_orbit_kernel<false, true, true>));
     first_use_touch(reinterpret_cast<const void*>(triples_orbit_kernel<true, true, true>));
+    first_use_touch(reinterpret_cast<const void*>(triples_so_orbit_kernel<true>));
     (void)hipGetLastError();
     preload_tgemm();
 }

@@ -360,12 +360,20 @@ __global__ __launch_bounds__(256, CR ? 2 : WANT_D ? 3 : 4) void triples_orbit_ke
 //   t3d = P(a/bc)[t1(i,a)<jk||bc> - t1(j,a)<ik||bc> - t1(k,a)<ji||bc>]     :1873-1874, :1890-1892
 //   E_T += t3c (t3c + t3d) / D / 6      (the reference sums all ordered (i,j,k) with 1/36; the summand is antisymmetric)
 // One workgroup = the orbit of one 8x8x8 cube under index permutation, as in the spin-free kernel.
+// FOCK = true (a state with a full Fock matrix, ccsd_so.h: ROHF-CCSD(T) of Watts, Gauss and Bartlett 1993 in semicanonical orbitals): the
+// disconnected part gains f_ia t_jk^bc under the same permutations,
+//   t3d = P(a/bc)[t1(i,a)<jk||bc> + f(i,a) t2(jk,bc) - (j: ik) - (k: ji)]
+// with f_ov in the slot the spin-free kernel keeps its transposed t2 in (in.t2_s, otherwise unused on this path); the t2 patches are
+// gathered from the natural layout in.t2.  FOCK = false is the kernel every other state launches.
+template <bool FOCK>
 __global__ __launch_bounds__(256, 3) void triples_so_orbit_kernel(double* __restrict__ partial, const double* __restrict__ Xpool,
                                                                  const TripleMeta* __restrict__ meta,
                                                                  const int* __restrict__ orbits, TriplesIn in, int nblk_total)
 {
     __shared__ __attribute__((aligned(16))) double wl[6 * CUBE];   // R on the six cubes of the orbit
     __shared__ double vp[27 * PATCH];                              // <pq||xy> patches for pairs (j,k), (i,k), (i,j)
+    __shared__ double tp[FOCK ? 27 * PATCH : 1];                   // t2(p,q,x,y) patches for the same pairs
+    __shared__ double fr[FOCK ? 72 : 1];                           // fr[occ][slot][l] = f_ov(occ, tile[slot]*8 + l)
     __shared__ double t1r[96];                                     // t1r[occ][slot][l] = t1(occ, tile[slot]*8 + l); then evl
     __shared__ int srcq[6][6];
     __shared__ double red[4];
@@ -410,10 +418,16 @@ __global__ __launch_bounds__(256, 3) void triples_so_orbit_kernel(double* __rest
         const int64_t off = ok ? gx + (int64_t)v * gy + vv * (pairp[pr] + (int64_t)o * pairq[pr]) : 0;
         const double a = in.voovv_s[off];
         vp[el] = ok ? a : 0.0;
+        if (FOCK) {
+            const int64_t offt = ok ? pairp[pr] + (int64_t)o * (pairq[pr] + (int64_t)o * (gx + (int64_t)v * gy)) : 0;
+            const double b = in.t2[offt];
+            tp[el] = ok ? b : 0.0;
+        }
     }
     if (t < 72) {
         const int oc = t / 24, sl = (t / 8) % 3, l = t & 7, g = tile[sl] * TT + l;
         t1r[t] = g < v ? in.t1[occ[oc] + o * g] : 0.0;
+        if (FOCK) fr[t] = g < v ? in.t2_s[occ[oc] + o * g] : 0.0;   // (the free slot carries f_ov)
     } else if (t < 96) {
         const int sl = (t - 72) / 8, l = t & 7, g = tile[sl] * TT + l;
         t1r[t] = in.e[(g < v ? g : 0) + o];
@@ -452,6 +466,25 @@ __global__ __launch_bounds__(256, 3) void triples_so_orbit_kernel(double* __rest
         for (int q = 0; q < 6; ++q) {
             const int s0 = sig(q, 0), s1 = sig(q, 1), s2 = sig(q, 2);
             RAW[q] = t1v[0][s0] * V[0][s1][s2] - t1v[1][s0] * V[1][s1][s2] + t1v[2][s0] * V[2][s1][s2];
+        }
+        if (FOCK) {   // + f(i,x) t2(jk,yz) - f(j,x) t2(ik,yz) + f(k,x) t2(ij,yz)
+            double fv[3][3], T2[3][3][3];
+#pragma unroll
+            for (int oc = 0; oc < 3; ++oc)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) fv[oc][c] = fr[oc * 24 + c * TT + l[c]];
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                for (int cx = 0; cx < 3; ++cx)
+#pragma unroll
+                    for (int cy = 0; cy < 3; ++cy)
+                        if (cx != cy) T2[pr][cx][cy] = tp[(pr * 9 + cx * 3 + cy) * PATCH + l[cx] + TT * l[cy]];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const int s0 = sig(q, 0), s1 = sig(q, 1), s2 = sig(q, 2);
+                RAW[q] += fv[0][s0] * T2[0][s1][s2] - fv[1][s0] * T2[1][s1][s2] + fv[2][s0] * T2[2][s1][s2];
+            }
         }
         double sum = 0.0;
 #pragma unroll

@@ -14,6 +14,7 @@ module afesp_capi
              afesp_mp2_vv_density, afesp_ump2_vv_density, &
              afesp_core_operator, afesp_ucore_operator, afesp_write_fcidump_active, afesp_write_fcidump_uactive, &
              afesp_fcidump_scan, afesp_read_fcidump, afesp_read_fcidump_uhf, &
+             afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -300,6 +301,46 @@ module afesp_capi
          type(c_ptr), value :: h_a, h_b, fock_a, fock_b, levels_a, levels_b, eri_aa, eri_ab, eri_bb
          real(c_double), intent(out) :: e_core, e_ref, fock_offdiag
          integer(c_int64_t), intent(out) :: nread
+         integer(c_int) :: rc
+      end function
+      !> restricted open-shell references (include/afesp.h): the two spin Fock operators of a restricted determinant on the resident packed
+      !> MO array, the reader of a restricted file with MS2 >= 0, the spin-dependent rotation of the resident MO integrals into the three
+      !> blocks of the open-shell path, and the spin-orbital state with the full Fock matrices of those orbitals
+      function afesp_mo_fock_ro(ctx, nbasis, nalpha, nbeta, h_mo, fock_a, fock_b, e_ref_elec) bind(C, name='afesp_mo_fock_ro') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         real(c_double), intent(in) :: h_mo(*)
+         real(c_double), intent(out) :: fock_a(*), fock_b(*), e_ref_elec
+         integer(c_int) :: rc
+      end function
+      function afesp_read_fcidump_rohf(ctx, path, nbasis, nalpha, nbeta, h_mo, fock_a, fock_b, e_core, e_ref, fock_offdiag, &
+                                       eri_mo_packed, nread) bind(C, name='afesp_read_fcidump_rohf') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: path(*)
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         type(c_ptr), value :: h_mo, fock_a, fock_b, eri_mo_packed
+         real(c_double), intent(out) :: e_core, e_ref, fock_offdiag(3)
+         integer(c_int64_t), intent(out) :: nread
+         integer(c_int) :: rc
+      end function
+      function afesp_mo_rotate_uhf(ctx, nbasis, u_a, u_b, eri_aa, eri_ab, eri_bb) bind(C, name='afesp_mo_rotate_uhf') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis
+         real(c_double), intent(in) :: u_a(*), u_b(*)
+         type(c_ptr), value :: eri_aa, eri_ab, eri_bb
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_uso_init_fock(ctx, nbasis, nalpha, nbeta, fock_a, fock_b, diis_n_errmat, e_mp2) &
+         bind(C, name='afesp_ccsd_uso_init_fock') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: nbasis, nalpha, nbeta
+         real(c_double), intent(in) :: fock_a(*), fock_b(*)
+         integer(c_int), value :: diis_n_errmat
+         real(c_double), intent(out) :: e_mp2
          integer(c_int) :: rc
       end function
       !> replaces write_fcidump (reference src/mp2.f90:451-487)

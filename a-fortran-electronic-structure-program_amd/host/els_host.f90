@@ -41,6 +41,8 @@ module host_config
       logical :: paren = .false., renorm = .false., comp_renorm = .false.
       logical :: spinorb = .false.   ! the _spinorb calculation types (reference src/system.f90:117-137)
       logical :: uhf = .false.       ! the open-shell types UHF_scf, UMP2, UCCSD, UCCSD(T) (canonical UHF orbitals)
+      logical :: rohf = .false.      ! ROHF-MP2, ROHF-CCSD, ROHF-CCSD(T): a restricted open-shell determinant from a FCIDUMP (uhf is set too:
+                                     ! semicanonical orbitals differ by spin, the open-shell branch runs them with the full Fock matrices)
       integer :: charge = 0, multiplicity = 1
       ! active orbital window of the correlated steps (no counterpart in the reference); all three absent: every orbital correlated
       logical :: frozen_core = .false.   ! freeze the noble-gas cores counted from geom.dat
@@ -116,11 +118,24 @@ contains
       case ('UMP2');             cfg%level = LEVEL_MP2; cfg%uhf = .true.
       case ('UCCSD');            cfg%level = LEVEL_CCSD; cfg%uhf = .true.
       case ('UCCSD(T)');         cfg%level = LEVEL_CCSD_T; cfg%uhf = .true.
+      ! restricted open-shell references: orbitals from a restricted FCIDUMP with MS2 >= 0, no SCF
+      case ('ROHF-MP2');         cfg%level = LEVEL_MP2; cfg%uhf = .true.; cfg%rohf = .true.
+      case ('ROHF-CCSD');        cfg%level = LEVEL_CCSD; cfg%uhf = .true.; cfg%rohf = .true.
+      case ('ROHF-CCSD(T)');     cfg%level = LEVEL_CCSD_T; cfg%uhf = .true.; cfg%rohf = .true.
       case default
          call fail('system::read_system_in', 'Unrecognised calculation type!')
       end select
       if (multiplicity < 1) call fail('system::read_system_in', 'invalid input file format!')
       cfg%fcidump_in = fcidump_in
+      if (cfg%rohf) then   ! no ROHF SCF here: the orbitals come from a file, and a frozen core reaches this path as an active-space file
+         if (.not. fcidump_in) call fail('system::read_system_in', trim(calc_type)// &
+            ' needs fcidump_in = .true.: there is no ROHF SCF, the restricted open-shell orbitals come from a FCIDUMP!')
+         if (frozen_core .or. n_frozen_core >= 0 .or. n_frozen_virt > 0) call fail('system::read_system_in', trim(calc_type)// &
+            ' takes no frozen_core / n_frozen_core / n_frozen_virt: freeze the core in the file (an active-space FCIDUMP carries the core operator)!')
+         if (fno_n_virt >= 0 .or. fno_occ_tol > 0.0_dp) call fail('system::read_system_in', trim(calc_type)// &
+            ' takes no frozen natural orbitals (fno_n_virt / fno_occ_tol)!')
+         if (fcidump_active) call fail('system::read_system_in', trim(calc_type)//' takes no fcidump_active!')
+      end if
       if (fcidump_in) then   ! the file replaces everything up to the MO integrals: what needs AO data or writes the same file is refused
          if (frozen_core) call fail('system::read_system_in', &
             'fcidump_in: frozen_core counts atoms in geom.dat, which is not read: give n_frozen_core!')
@@ -645,6 +660,7 @@ program els_amd
    use host_inputs
    use host_scf
    use host_fno
+   use host_linalg
    use afesp_capi
    implicit none
    type(run_config) :: cfg
@@ -664,6 +680,9 @@ program els_amd
    ! fcidump_active: the frozen-core operator(s) of the window and the core energy, taken before the window
    real(dp), allocatable :: h_act(:, :), h_act_b(:, :)
    real(dp) :: e_core
+   ! ROHF types: the spin Fock matrices of the file's determinant in semicanonical orbitals
+   real(dp), allocatable :: fock_sa(:, :), fock_sb(:, :)
+   character(len=16) :: mp2name, ccname
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
    integer(c_int) :: rc, conv
@@ -813,7 +832,8 @@ program els_amd
    if (cfg%uhf .and. cfg%level >= LEVEL_MP2 .and. scf_ok) then
       ! ---------------- open shells: UMP2 from the three spin blocks, then the spin-orbital CCSD / (T) on them
       t0 = seconds()
-      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'UMP2'; write (out, '(1X, 10("-"))')
+      mp2name = merge('ROHF-MBPT(2)', 'UMP2        ', cfg%rohf); ccname = merge('ROHF-CCSD', 'UCCSD    ', cfg%rohf)
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') trim(mp2name); write (out, '(1X, 10("-"))')
       if (.not. cfg%fcidump_in) then
          write (out, '(1X, A)') 'Performing AO to MO ERI transformation (alpha-alpha, alpha-beta, beta-beta)...'
          rc = afesp_ao2mo_ump2(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), coeff, cb, levels, lb, &
@@ -822,24 +842,34 @@ program els_amd
       end if
       if (fno) call open_shell_fno()   ! natural virtuals of both spins, second transform; sets nfv and the active extents
       if (cfg%fcidump_active) call core_operator_before_window()
-      if (windowed .or. fno .or. cfg%fcidump_in) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
+      if (cfg%rohf) then   ! the state with the full Fock matrices of the semicanonical orbitals: its start amplitudes give ROHF-MBPT(2)
+         rc = afesp_ccsd_uso_init_fock(ctx, int(n_act, c_int64_t), int(na_act, c_int64_t), int(nb_act, c_int64_t), fock_sa, fock_sb, &
+                                       int(cfg%ccsd_diis_n_errmat, c_int), e_mp2)
+         if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
+      else if (windowed .or. fno .or. cfg%fcidump_in) then   ! the three blocks over the active orbitals, and the frozen-core UMP2 energy
          ! (integrals read from a file: this call, with nothing frozen too, is the one that reports the UMP2 energy)
          rc = afesp_umo_window(ctx, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), int(nfc, c_int64_t), &
                                int(nfv, c_int64_t), levels, lb, c_null_ptr, c_null_ptr, c_null_ptr, e_mp2)
          if (rc /= 0) call fail('mp2::do_ump2', afesp_error_text(ctx))
       end if
       if (cfg%fcidump_active) call dump_active_space()
+      if (cfg%rohf) then
+         write (out, '(1X, A, 1X, F18.12)') 'ROHF-MBPT(2) correlation energy (Hartree):', e_mp2
+      else
       write (out, '(1X, A, 1X, F15.8)') 'UMP2 correlation energy (Hartree):', e_mp2
+      end if
       if (fno) call print_fno_energies('UMP2')
       e_highest = e_mp2
-      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UMP2:', seconds() - t0, 's'
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//trim(mp2name)//':', seconds() - t0, 's'
       if (cfg%level >= LEVEL_CCSD) then
          t0 = seconds()
          write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD'; write (out, '(1X, 10("-"))')
+         if (.not. cfg%rohf) then   ! (a ROHF state exists already: afesp_ccsd_uso_init_fock above)
          write (out, '(1X, A)') 'Forming slices of antisymmetrised spinorbital ERIs from the UHF blocks...'
          rc = afesp_ccsd_uso_init(ctx, int(n_act, c_int64_t), int(na_act, c_int64_t), int(nb_act, c_int64_t), levels(nfc + 1:), &
                                   lb(nfc + 1:), int(cfg%ccsd_diis_n_errmat, c_int))
          if (rc /= 0) call fail('ccsd::init_cc', afesp_error_text(ctx))
+         end if
          rc = afesp_ccsd_so_energy(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, energy, rms, conv)
          if (rc /= 0) call fail('ccsd::update_cc_energy', afesp_error_text(ctx))
          write (out, '(75("-"))')
@@ -863,10 +893,10 @@ program els_amd
          if (cc_ok) then
             write (out, '(75("-"))')
             write (out, '(1X, A)') 'Convergence reached within tolerance.'
-            write (out, '(1X, A, 1X, F15.12)') 'Final UCCSD Energy (Hartree):', energy
+            write (out, '(1X, A, 1X, F15.12)') 'Final '//trim(ccname)//' Energy (Hartree):', energy
             e_ccsd = energy; e_highest = e_ccsd
          end if
-         write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UCCSD:', seconds() - t0, 's'
+         write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//trim(ccname)//':', seconds() - t0, 's'
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
@@ -884,8 +914,12 @@ program els_amd
             if (rc /= 0) call fail('ccsd::do_ccsd_t_spinorb', afesp_error_text(ctx))
             e_pt = e_ccsd + tq(1)
             e_highest = e_pt
+            if (cfg%rohf) then
+               write (out, '(1X, A, 1X, F18.12)') 'ROHF-CCSD(T) correlation energy (Hartree):', e_pt
+            else
             write (out, '(1X, A, 1X, F15.9)') 'UCCSD(T) correlation energy (Hartree):', e_pt
-            write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for UCCSD(T):', seconds() - t0, 's'
+            end if
+            write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//trim(ccname)//'(T):', seconds() - t0, 's'
          end if
       end if
    else if (cfg%level >= LEVEL_MP2 .and. scf_ok) then
@@ -1110,7 +1144,21 @@ program els_amd
    ! ---------------- final table: same labels and formats as the reference (src/main.F90:123-175)
    write (out, '(1X, 64("="))')
    write (out, '(1X, A)') 'Final energy breakdown'
-   if (cfg%uhf) then
+   if (cfg%rohf) then
+   write (out, '(1X, A, 1X, F15.10)') 'ROHF reference energy:         ', e_hf + mol%e_nuc
+   if (cfg%level >= LEVEL_MP2) then
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-MBPT(2) correlation energy:', e_mp2
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-MBPT(2) energy:           ', e_mp2 + e_hf + mol%e_nuc
+   end if
+   if (cfg%level >= LEVEL_CCSD) then
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD correlation energy:  ', e_ccsd
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD energy:              ', e_ccsd + e_hf + mol%e_nuc
+   end if
+   if (cfg%level == LEVEL_CCSD_T) then
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD(T) correlation energy:', e_pt
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD(T) energy:           ', e_pt + e_hf + mol%e_nuc
+   end if
+   else if (cfg%uhf) then
    write (out, '(1X, A, 1X, F15.10)') 'UHF energy:                    ', e_hf + mol%e_nuc
    if (.not. cfg%fcidump_in) write (out, '(1X, A, 1X, F15.10)') '<S^2>:                         ', s2
    if (cfg%level >= LEVEL_MP2) then
@@ -1288,6 +1336,19 @@ contains
       if (rc /= 0) call fail('integrals::read_fcidump', 'fcidump_in: FCIDUMP is missing, unreadable or has no &FCI ... &END header')
       write (out, '(1X, A, I0, A, I0, A, I0, A, L1, A, I0)') 'FCIDUMP header: NORB ', norb, ', NELEC ', nelec, ', MS2 ', ms2, ', UHF ', &
          file_uhf /= 0, ', lines ', nl
+      if (cfg%rohf) then   ! a restricted file with MS2 >= 0 (MS2 = 0: the closed-shell limit)
+         if (file_uhf /= 0) call fail('integrals::read_fcidump', &
+            'fcidump_in: the file says UHF=.TRUE.: it takes UMP2, UCCSD or UCCSD(T), not '//trim(cfg%calc_type))
+         if (ms2 < 0 .or. mod(nelec + ms2, 2_c_int64_t) /= 0) call fail('integrals::read_fcidump', &
+            'fcidump_in: '//trim(cfg%calc_type)//' needs a restricted file with MS2 >= 0 of the parity of NELEC')
+         mol%e_nuc = 0.0_dp; mol%natoms = 0; mol%ncore = -1
+         mol%nel = int(nelec); mol%nbasis = int(norb)
+         na = int((nelec + ms2)/2); nb = int((nelec - ms2)/2)
+         if (nb < 0 .or. na > mol%nbasis .or. na + nb <= 0 .or. na + nb >= 2*mol%nbasis) &
+            call fail('integrals::read_fcidump', 'fcidump_in: NELEC and MS2 do not fit NORB, or leave no virtual spin orbital')
+         mol%nocc = nb; mol%nvirt = mol%nbasis - na
+         return
+      end if
       if (file_uhf /= 0 .and. .not. cfg%uhf) call fail('integrals::read_fcidump', &
          'fcidump_in: the file says UHF=.TRUE.: it takes UMP2, UCCSD or UCCSD(T), not '//trim(cfg%calc_type))
       if (file_uhf == 0 .and. cfg%uhf) call fail('integrals::read_fcidump', &
@@ -1319,6 +1380,10 @@ contains
       real(dp), allocatable, target :: la_t(:), lb_t(:)
       write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'FCIDUMP'; write (out, '(1X, 10("-"))')
       write (out, '(1X, A)') 'Reading MO integrals from FCIDUMP (no SCF, no AO to MO transformation)...'
+      if (cfg%rohf) then
+         call read_rohf_file()
+         return
+      end if
       allocate (la_t(mol%nbasis), lb_t(mol%nbasis))
       if (cfg%uhf) then
          rc = afesp_read_fcidump_uhf(ctx, 'FCIDUMP'//c_null_char, int(mol%nbasis, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), &
@@ -1345,6 +1410,63 @@ contains
       end if
       scf_ok = .true.
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for reading the FCIDUMP:', seconds() - t0, 's'
+   end subroutine
+   !> the ROHF types: the restricted file onto the device, the two spin Fock operators of its determinant, semicanonical orbitals (the
+   !> occupied and the virtual block of each spin diagonalised on the host), and the resident integrals rotated into the three blocks of the
+   !> open-shell path.  The off-diagonal Fock elements of the file are printed and not judged: such orbitals are not canonical.
+   subroutine read_rohf_file()
+      real(dp) :: e_core_file, offd(3)
+      real(dp), allocatable, target :: fa(:, :), fb(:, :)
+      real(dp), allocatable :: ua(:, :), ub(:, :)
+      integer :: n, p
+      n = mol%nbasis
+      allocate (fa(n, n), fb(n, n), ua(n, n), ub(n, n), fock_sa(n, n), fock_sb(n, n))
+      rc = afesp_read_fcidump_rohf(ctx, 'FCIDUMP'//c_null_char, int(n, c_int64_t), int(na, c_int64_t), int(nb, c_int64_t), c_null_ptr, &
+                                   c_loc(fa), c_loc(fb), e_core_file, e_hf, offd, c_null_ptr, nlines)
+      if (rc /= 0) call fail('integrals::read_fcidump', afesp_error_text(ctx))
+      write (out, '(1X, A, I0)') 'Lines read: ', nlines
+      write (out, '(1X, A, 1X, F18.10)') 'Core energy of the file (Hartree):', e_core_file
+      write (out, '(1X, A, 1X, F20.12)') 'Reference determinant energy (Hartree):', e_hf
+      write (out, '(1X, A, 1X, ES10.3)') 'Largest occupied-occupied off-diagonal Fock element:', offd(1)
+      write (out, '(1X, A, 1X, ES10.3)') 'Largest virtual-virtual off-diagonal Fock element:', offd(2)
+      write (out, '(1X, A, 1X, ES10.3)') 'Largest occupied-virtual Fock element:', offd(3)
+      call semicanonical(fa, na, ua, fock_sa)
+      call semicanonical(fb, nb, ub, fock_sb)
+      write (out, '(1X, A)') 'Rotating the MO integrals into semicanonical orbitals (alpha-alpha, alpha-beta, beta-beta)...'
+      rc = afesp_mo_rotate_uhf(ctx, int(n, c_int64_t), ua, ub, c_null_ptr, c_null_ptr, c_null_ptr)
+      if (rc /= 0) call fail('integrals::read_fcidump', afesp_error_text(ctx))
+      allocate (levels(n), lb(n))
+      do p = 1, n
+         levels(p) = fock_sa(p, p); lb(p) = fock_sb(p, p)
+      end do
+      s2 = 0.0_dp
+      scf_ok = .true.
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for reading the FCIDUMP:', seconds() - t0, 's'
+   end subroutine
+   !> u(new, old) diagonalises f(1:o, 1:o) and f(o+1:, o+1:); g = u f u^T, symmetric, those two blocks diagonal to the bit
+   subroutine semicanonical(f, o, u, g)
+      real(dp), intent(in) :: f(:, :)
+      integer, intent(in) :: o
+      real(dp), intent(out) :: u(:, :), g(:, :)
+      real(dp), allocatable :: w(:), v(:, :)
+      integer :: n, lo, hi, m, blk, p, q
+      n = size(f, 1)
+      u = 0.0_dp
+      do blk = 1, 2
+         lo = merge(1, o + 1, blk == 1); hi = merge(o, n, blk == 1); m = hi - lo + 1
+         if (m <= 0) cycle
+         allocate (w(m), v(m, m))
+         call sym_eig(f(lo:hi, lo:hi), w, v)
+         u(lo:hi, lo:hi) = transpose(v)
+         deallocate (w, v)
+      end do
+      g = matmul(u, matmul(f, transpose(u)))
+      g = 0.5_dp*(g + transpose(g))
+      do q = 1, n
+         do p = 1, n
+            if (p /= q .and. ((p <= o) .eqv. (q <= o))) g(p, q) = 0.0_dp
+         end do
+      end do
    end subroutine
    !> fcidump_active, first half: the frozen-core operator of the window and the core energy from the full MO integrals of the (last)
    !> transform -- before the window, which throws the core orbitals away (with natural virtuals: in the rotated orbitals)

@@ -319,6 +319,45 @@ int afesp_read_fcidump_uhf(afesp_ctx* ctx, const char* path, int64_t nbasis, int
                            double* fock_a, double* fock_b, double* levels_a, double* levels_b, double* e_core, double* e_ref,
                            double* fock_offdiag, double* eri_aa, double* eri_ab, double* eri_bb, int64_t* nread);
 
+/* ---- Restricted open-shell (ROHF) references: non-HF CCSD and CCSD(T) on the dense spin-orbital solver.
+ * A restricted open-shell determinant -- one set of orbitals, the first nalpha / nbeta of them occupied, nalpha >= nbeta -- has two spin
+ * Fock operators with f_ia != 0 and non-diagonal occupied and virtual blocks.  The route: one packed MO array (a restricted FCIDUMP, or
+ * afesp_ao2mo_mp2) -> the two operators (afesp_mo_fock_ro / afesp_read_fcidump_rohf) -> the caller diagonalises the occupied and the
+ * virtual block of each spin (semicanonical orbitals; afesp_amd/rohf.py) -> afesp_mo_rotate_uhf -> afesp_ccsd_uso_init_fock ->
+ * afesp_ccsd_so_energy / _iterate / _diis -> afesp_ccsd_so_t.  No ROHF SCF: the orbitals come from a file or from the caller.
+ *
+ * afesp_mo_fock_ro: on the packed MO array resident for nbasis (afesp_ao2mo_mp2, afesp_read_fcidump, afesp_read_fcidump_rohf)
+ *     F_a(p,q) = h(p,q) + sum_{i < nalpha} [(pq|ii) - (pi|qi)] + sum_{i < nbeta} (pq|ii)
+ *     F_b(p,q) = h(p,q) + sum_{i < nbeta}  [(pq|ii) - (pi|qi)] + sum_{i < nalpha} (pq|ii)
+ *     *e_ref_elec = 1/2 sum_{i < nalpha} [h + F_a](i,i) + 1/2 sum_{i < nbeta} [h + F_b](i,i)
+ *   h_mo, fock_a, fock_b [n*n] column-major; the outputs are symmetric to the bit (one wave per orbital pair, fixed summation order).
+ *   Nothing resident is touched.  Status 1: a negative count, nalpha < nbeta, nalpha > nbasis, a NULL argument, nothing resident for nbasis.
+ * afesp_read_fcidump_rohf: afesp_read_fcidump for the file with MS2 = nalpha - nbeta >= 0 and no UHF flag (NORB = nbasis, NELEC = nalpha +
+ *   nbeta): the same parse, scatter, duplicate rule, error list and residency (the packed array is left as afesp_read_fcidump leaves it).
+ *   fock_a / fock_b as above, *e_ref = *e_core + e_ref_elec, fock_offdiag[3] = max |F| over both spins of the occupied-occupied
+ *   off-diagonal, the virtual-virtual off-diagonal and the occupied-virtual elements -- reported, not judged.  Each output may be NULL.
+ * afesp_mo_rotate_uhf: the resident packed MO integrals in the orbitals phi'_p = sum_q u_s(p,q) phi_q of spin s (u_s [n*n] column-major,
+ *   (new orbital, old orbital), like canon_coeff), as the three blocks (aa|aa), (aa|bb), (bb|bb) left resident exactly as afesp_ao2mo_ump2
+ *   leaves them; afesp_umo_window works on them afterwards.  The transform is afesp_ao2mo_ump2's with the packed MO array as its source
+ *   (the LDS-resident pair transform up to 64 functions, the gather-GEMM form above; a size that needs the slab-blocked form is
+ *   refused as there).  The packed array and resident AO integrals stay untouched and valid.  eri_* (host copies) may be NULL.
+ * afesp_ccsd_uso_init_fock: the state of afesp_ccsd_uso_init from the resident three blocks with the full spin Fock matrices fock_a /
+ *   fock_b [n*n] of the SAME orbitals: the levels are their diagonals, f_ov and the off-diagonal f_oo / f_vv (afesp_ccsd_so_get_tensor
+ *   "f_ov", "f_oo", "f_vv"; the state's spin-orbital order) enter Stanton et al. Eqs. 1-5:
+ *     F_ae += (1 - d_ae) f_ae - 1/2 f_me t_ma,  F_mi += (1 - d_mi) f_mi + 1/2 t_ie f_me,  F_me += f_me,  T1 residual += f_ia,
+ *     E += sum f_ia t_ia;  start amplitudes t1 = f_ia / D_ia, t2 = <ij||ab> / D_ijab;
+ *     *e_mp2 = sum f_ia^2 / D_ia + 1/4 sum <ij||ab>^2 / D_ijab  (semicanonical orbitals: the ROHF-MBPT(2) energy).
+ *   Only a state made by this call executes these terms.  afesp_ccsd_so_t on it adds f_ia t_jk^bc to the disconnected triples
+ *   (ROHF-CCSD(T), Watts, Gauss, Bartlett 1993) and returns status 1 if an off-diagonal f_oo or f_vv element exceeds 1e-8 in magnitude:
+ *   (T) is defined in semicanonical orbitals only. */
+int afesp_mo_fock_ro(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* h_mo, double* fock_a, double* fock_b,
+                     double* e_ref_elec);
+int afesp_read_fcidump_rohf(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t nalpha, int64_t nbeta, double* h_mo, double* fock_a,
+                            double* fock_b, double* e_core, double* e_ref, double* fock_offdiag, double* eri_mo_packed, int64_t* nread);
+int afesp_mo_rotate_uhf(afesp_ctx* ctx, int64_t nbasis, const double* u_a, const double* u_b, double* eri_aa, double* eri_ab, double* eri_bb);
+int afesp_ccsd_uso_init_fock(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* fock_a, const double* fock_b,
+                             int diis_n_errmat, double* e_mp2);
+
 /* ---- Multi-GPU: one process per GPU, each with its own context.  The reference has no distributed layer;
  * its (T) loop ends in an OpenMP `reduction(+: ...)` over threads (src/ccsd.f90:2091, entered from src/main.F90:112).  Here
  * every rank evaluates its shard [bounds[r], bounds[r+1]) of the triple list (afesp_ccsd_t_shard_bounds) and that
