@@ -541,6 +541,9 @@ int afesp_ccsd_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2
             ring_invalidate(ctx->cc);
         }
         ctx->cc.amps_touched = true;
+        // (a launch-fused iteration has pushed its own result into the DIIS history already: afesp_ccsd_diis extrapolates the amplitudes
+        // current at the call, so it pushes again -- into the same slot, the tail has advanced no counter)
+        ctx->cc.tail_pending = false;
         if (t2) ctx->cc.hist_plain = ctx->cc.nerr + 1;   // (its error vector may lack the amplitudes' symmetry: full DIIS sums until it has left the history)
         if (t1) AFESP_HIP(hipMemcpyAsync(ctx->cc.t1.d, t1, sizeof(double) * ctx->cc.t1.size(), hipMemcpyHostToDevice, cx.stream));
         if (t2) AFESP_HIP(hipMemcpyAsync(ctx->cc.t2.d, t2, sizeof(double) * ctx->cc.t2.size(), hipMemcpyHostToDevice, cx.stream));

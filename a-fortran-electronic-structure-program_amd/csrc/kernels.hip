@@ -905,11 +905,14 @@ __device__ __forceinline__ bool diis_solve_wave(double* coef, double* bmat, cons
                 for (int i = k + 1; i < DIIS_MAXN; ++i)
                     if (i == p) { col[k] = col[i]; col[i] = t; pivot = colk[i]; colk[i] = colk[k]; }
             }
-            const double rkk = singular ? 0.0 : 1.0 / pivot;
+            // The multiplier is a quotient, as in the host elimination (diis_update) and the reference's: a rank-deficient B -- the
+            // same error vector twice -- then leaves an exact zero behind and is reported.  With colk[i] * (1 / pivot) the
+            // product need not round to 1 (49 * (1 / 49) does not), the pivot came out as ~1e-15 instead of 0, and coefficients
+            // of order 1e14 went into the amplitudes unreported.
 #pragma unroll
             for (int i = k + 1; i < DIIS_MAXN; ++i) {
                 if (i < N) {
-                    const double f = colk[i] * rkk;
+                    const double f = singular ? 0.0 : colk[i] / pivot;
                     col[i] -= f * col[k];
                 }
             }

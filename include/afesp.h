@@ -86,7 +86,8 @@ int afesp_ccsd_init(afesp_ctx* ctx, int64_t nocc, int64_t nvirt, const double* e
 int afesp_ccsd_iterate(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged);
 /* update_cc_energy alone on the current amplitudes (the "MP1" line, src/ccsd.f90:325). */
 int afesp_ccsd_energy(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged);
-/* update_diis_cc (src/ccsd.f90:395, :617-676). */
+/* update_diis_cc (src/ccsd.f90:395, :617-676).  It extrapolates the amplitudes current at the call: a set handed in with
+ * afesp_ccsd_set_amplitudes after the last afesp_ccsd_iterate is what enters the history. */
 int afesp_ccsd_diis(afesp_ctx* ctx);
 /* The whole solver loop src/ccsd.f90:325-396.  iter_energy / iter_rms_sq (length maxiter+1, may be NULL) receive the
  * iteration table incl. entry 0 = "MP1".  *niter = iterations taken, or -1 if not converged within maxiter. */
