@@ -1105,7 +1105,13 @@ int afesp_contract(afesp_ctx* ctx, double alpha, const double* A, const char* la
         AFESP_HIP(hipMemcpyAsync(tA.d, A, sizeof(double) * tA.size(), hipMemcpyHostToDevice, cx.stream));
         AFESP_HIP(hipMemcpyAsync(tB.d, B, sizeof(double) * tB.size(), hipMemcpyHostToDevice, cx.stream));
         AFESP_HIP(hipMemcpyAsync(tC.d, C, sizeof(double) * tC.size(), hipMemcpyHostToDevice, cx.stream));
-        contract(cx, alpha, tA, la, tB, lb, beta, tC, lc, 1, nullptr, nullptr, nullptr, force_split, force_tm, force_tn);
+        try {
+            contract(cx, alpha, tA, la, tB, lb, beta, tC, lc, 1, nullptr, nullptr, nullptr, force_split, force_tm, force_tn);
+        } catch (...) {   // (a refused product: the copies above still read the caller's arrays, and the three blocks go back)
+            (void)hipStreamSynchronize(cx.stream);
+            cx.release(tA.d); cx.release(tB.d); cx.release(tC.d);
+            throw;
+        }
         AFESP_HIP(hipMemcpyAsync(C, tC.d, sizeof(double) * tC.size(), hipMemcpyDeviceToHost, cx.stream));
         cx.sync();
         cx.release(tA.d); cx.release(tB.d); cx.release(tC.d);

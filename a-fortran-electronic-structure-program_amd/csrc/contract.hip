@@ -801,7 +801,16 @@ void contract(Context& cx, double alpha, const Tensor& A0, const char* la0, cons
     // tall x skinny (one extent of C at most 32, K a few hundred: the products of t1 with a four-index array): streamed, tall.h
     const bool tall = !force_split && !force_tm && !force_tn && tall_eligible(g);
     ++(tall ? cx.n_tall : cx.n_gett);
-    auto launch = [&]() { return tall ? tall_launch(g, cx.stream) : gett_launch(g, cx.ws, cx.stream, force_split, force_tm, force_tn); };
+    auto launch = [&]() {
+        if (tall) return tall_launch(g, cx.stream);
+        const hipError_t e = gett_launch(g, cx.ws, cx.stream, force_split, force_tm, force_tn);
+        const int ftm = force_tm ? force_tm : g_force_tm, ftn = force_tn ? force_tn : g_force_tn;
+        if (e == hipErrorInvalidValue && (ftm || ftn))   // (nothing was launched)
+            throw Error(3, "contract: the forced tile code (tm, tn) = (" + std::to_string(ftm) + ", " + std::to_string(ftn) +
+                               ") names no gather-GEMM kernel (0: chosen from the extent); the codes are tm, tn in {1, 2, 4}, (8,8), (8,16), "
+                               "(16,8), (16,7), (16,6): " + std::string(la0) + "," + lb0 + "->" + lc);
+        return e;
+    };
     if (!trace) {
         AFESP_HIP(launch());
         return;

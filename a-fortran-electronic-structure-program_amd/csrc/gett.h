@@ -65,7 +65,12 @@ struct GettWorkspace {
     size_t bytes;
 };
 
-// Returns hipSuccess or the launch error.  `force_split` > 0 overrides the heuristic (tests).
+// The tile codes (tm, tn) that name a kernel: tm, tn in {1, 2, 4} (32, 64, 128 rows / columns; (4,4) is the 8-wave 128 x 128 tile),
+// (8,8) the 4-wave 128 x 128 tile, (16,8) 256 x 128, (8,16) 128 x 256, (16,7) 256 x 112, (16,6) 256 x 96.
+bool gett_tile_code_exists(int tm, int tn);
+
+// Returns hipSuccess or the launch error.  `force_split` > 0 overrides the heuristic (tests).  A forced tile code (here or through
+// g_force_tm / g_force_tn) that names no kernel is hipErrorInvalidValue, returned before anything is queued on the stream.
 hipError_t gett_launch(const GettProblem& p, const GettWorkspace& ws, hipStream_t stream, int force_split = 0,
                        int force_tm = 0, int force_tn = 0);
 

@@ -636,6 +636,8 @@ static void launch_one(const GettKernelArgs& a, dim3 grid, hipStream_t st)
     if (g_dbg & 2) per = 1 << 30;   // measurement only: one tile per workgroup
     if (g_dbg & 4) per = per / 4 > 0 ? per / 4 : 1;   // measurement only: a quarter of the device (tools/burst_probe.py)
     if ((int)grid.x > per) grid.x = (unsigned)per;
+    if (!GRP && knobs().gett_debug)   // (fewer workgroups than tiles: the in-kernel walk, in groups of gm m-tiles)
+        fprintf(stderr, "gett_grid %u workgroups for %d tiles gm %d\n", grid.x, a.mtiles * a.ntiles, a.gm);
     AFESP_KLAUNCH((gett_kernel<WM, WN, TM, TN, AK, BK_, W, GRP, RAG, TS>), grid, dim3(64 * WM * WN), 0, st, a);
 }
 
@@ -679,6 +681,15 @@ static int pick_t(int extent)
     if (extent <= 32) return 1;
     if (extent <= 64) return 2;
     return 4;
+}
+
+// the tile codes gett_launch has a kernel for (its AFESP_CFG list and the 256 x 112 / 256 x 96 tiles)
+bool gett_tile_code_exists(int tm, int tn)
+{
+    if (tm == 1 || tm == 2 || tm == 4) return tn == 1 || tn == 2 || tn == 4;
+    if (tm == 8) return tn == 8 || tn == 16;
+    if (tm == 16) return tn == 8 || tn == 7 || tn == 6;
+    return false;
 }
 
 hipError_t gett_launch(const GettProblem& p, const GettWorkspace& ws, hipStream_t stream, int force_split, int force_tm,
@@ -740,6 +751,9 @@ hipError_t gett_launch(const GettProblem& p, const GettWorkspace& ws, hipStream_
             }
     }
     if (tn == 6 || tn == 7) tm = 16;   // (the narrow tiles exist under 256 rows only)
+    // a code pair without an instantiation (the AFESP_CFG list below and the two narrow tiles) would launch nothing and leave C -- or,
+    // sliced, the workspace the reduce kernel sums -- unwritten: an error before anything is queued
+    if (!gett_tile_code_exists(tm, tn)) return hipErrorInvalidValue;
     const int BM = tm == 16 ? 256 : tm == 8 ? 128 : 32 * tm, BN = tn == 16 ? 256 : tn == 8 ? 128 : tn == 7 ? 112 : tn == 6 ? 96 : 32 * tn;
     a.mtiles = (p.M + BM - 1) / BM;
     a.ntiles = (p.N + BN - 1) / BN;
@@ -812,8 +826,8 @@ hipError_t gett_launch(const GettProblem& p, const GettWorkspace& ws, hipStream_
     }
     const bool gett_debug = knobs().gett_debug;   // every launch: extents, tile codes, K slices
     if (gett_debug)
-        fprintf(stderr, "gett_launch M %d N %d K %d batch %d akc %d bkc %d wide %d -> tm %d tn %d tiles %d x %d split %d (steps per slice %d)\n", p.M, p.N, p.K,
-                p.nbatch, (int)p.a_kcontig, (int)p.b_kcontig, (int)wide, tm, tn, a.mtiles, a.ntiles, a.ksplit, a.kchunk / BK);
+        fprintf(stderr, "gett_launch M %d N %d K %d batch %d akc %d bkc %d wide %d -> tm %d tn %d tiles %d x %d split %d sk %d (steps per slice %d)\n", p.M, p.N, p.K,
+                p.nbatch, (int)p.a_kcontig, (int)p.b_kcontig, (int)wide, tm, tn, a.mtiles, a.ntiles, a.ksplit, (int)sk, a.kchunk / BK);
     // tile code (tm,tn) -> wave grid x per-wave MFMA grid.  (4,4) is the 8-wave 128x128 tile: two waves per SIMD share
     // the matrix pipe, so one wave's gather/LDS phases are covered by the other's MFMAs.
 #define AFESP_CFG(TM_, TN_, WM_, WN_, PM_, PN_) \

@@ -463,7 +463,8 @@ int afesp_bench_contract(afesp_ctx* ctx, const char* la, const int64_t* dimsA, c
  * zero padding its tiles execute, GEMM kernel: 1 LDS-DMA kernel / 0 gather kernel}), clears them and switches the
  * instrumentation on/off for the following afesp_ccsd_t calls. */
 int afesp_profile(afesp_ctx* ctx, int enable, double out[8]);
-/* Process-wide tuning overrides of the GEMM launcher (0 = heuristic): tile-walk group, tile shape (1|2|4), split-K. */
+/* Process-wide tuning overrides of the GEMM launcher (0 = heuristic): tile-walk group, tile code, split-K.  Tile codes (tm, tn): tm, tn in
+ * {1, 2, 4}, (8,8), (8,16), (16,8), (16,7), (16,6); any other forced pair makes the products that reach the launcher fail (status 3). */
 int afesp_set_tuning(int group_m, int force_tm, int force_tn, int force_split);
 
 #ifdef __cplusplus
