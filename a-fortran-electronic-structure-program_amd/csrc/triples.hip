@@ -242,6 +242,11 @@ struct TriplesPlan {
     TgGroup* tgdesc = nullptr;
     uint32_t* tables32 = nullptr;  // [rowA (v^2) | per chunk: colB]  byte offsets
     bool c_pairs = false;          // columns (x, x + 1), x even, of a block are adjacent in the cube-blocked layout: v even (tgemm.h)
+    // fused scheme: the tuning knobs the plan was shaped by (knobs.h: every knob follows the environment per C-ABI call).  The block size
+    // decides WHICH triples a sub-range holds, so a plan of another block size is another plan, not the same one laid out differently.
+    int k_block = 0;
+    int64_t k_pool_gib = -1, k_split_tiles = 0;
+    bool k_one_pool = false;
     double* pool0 = nullptr;       // fused scheme, not completely renormalised: base the block offsets refer to (assemble_pool)
 };
 
@@ -510,7 +515,8 @@ static TriplesPlan* plan_fused(Context& cx, void*& slot, int o, int v, int64_t t
     TriplesPlan* p = (TriplesPlan*)slot;
     const bool use_tg = fused_use_tg(o, v);
     if (p && p->o == o && p->v == v && p->t_begin == t_begin && p->t_end == t_end && p->cr == cr && p->mode == 0 &&
-        p->epoch == cx.scratch_epoch && p->use_tg == use_tg)
+        p->epoch == cx.scratch_epoch && p->use_tg == use_tg && p->k_block == knobs().t_block && p->k_pool_gib == knobs().t_pool_gib &&
+        p->k_split_tiles == knobs().t_split_tiles && p->k_one_pool == knobs().t_one_pool)
         return p;
     delete p;
     p = new TriplesPlan();
@@ -518,6 +524,7 @@ static TriplesPlan* plan_fused(Context& cx, void*& slot, int o, int v, int64_t t
     const int64_t O = o, V = v, v2 = V * V, Kc = (V + O + 15) / 16 * 16;
     const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;
     p->o = o; p->v = v; p->t_begin = t_begin; p->t_end = t_end; p->cr = cr; p->mode = 0; p->use_tg = use_tg;
+    p->k_block = knobs().t_block; p->k_pool_gib = knobs().t_pool_gib; p->k_split_tiles = knobs().t_split_tiles; p->k_one_pool = knobs().t_one_pool;
     // a group's columns are (x, block) with x fastest: column 2k is an even x iff v is even; rows and blocks start at multiples of 8
     p->c_pairs = (v % 2) == 0;
     const int nk1 = (int)(Kc / TG_BK);
