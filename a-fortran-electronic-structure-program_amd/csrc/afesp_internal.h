@@ -156,6 +156,7 @@ struct Context {
     double* alloc_raw(int64_t n);         // uninitialised (large temporaries that are fully overwritten)
     int64_t* alloc_i64(int64_t n);
     void release(void* p);                // early free of an `owned` buffer
+    bool fits(double bytes) const;        // within 0.9 of what the device has free plus what the arena holds idle (a caller refuses otherwise)
     double* scratch(const std::string& name, int64_t ndoubles);   // cached, uninitialised, grows on demand
     void drop_scratch();
     void drop_scratch(const std::string& prefix);   // only the cached buffers whose name starts with `prefix`

@@ -1,5 +1,5 @@
 // capi.hip -- extern "C" boundary (include/afesp.h): argument checks and one call each into the layers behind it (the integral layer:
-// integrals.h), and the synthetic-input generators.
+// integrals.h; the drivers of the two CCSD solvers: solver.h), and the synthetic-input generators.
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -10,46 +10,16 @@
 
 #include "../../include/afesp.h"
 #include "integrals.h"
-#include "ccsd_so.h"
+#include "solver.h"
 #include "comm.h"
-#include "fused.h"
 #include "tall.h"
 
 using namespace afesp;
 
 struct afesp_ctx {
     Context cx;
-    CCState cc;
-    SOState so;
+    Solver sv;      // the two CCSD solver states and their compiled programs (solver.h)
     Integrals in;   // the resident AO / MO integrals (integrals.h)
-    // With the chains of a small-system iteration spread over lanes, issuing ~110 launches from the host (~4 us each) is
-    // what is left; from the second call on the iteration is therefore replayed as a hipGraph (captured across the
-    // lanes).  Only used where lanes are (small systems); AFESP_NO_GRAPH=1 keeps plain launches.
-    struct GraphSlot {
-        hipGraphExec_t exec = nullptr;
-        int64_t epoch = -1;      // Context::scratch_epoch at capture
-        int calls = 0;
-        bool disabled = false;
-        void reset()
-        {
-            if (exec) (void)hipGraphExecDestroy(exec);
-            exec = nullptr;
-            calls = 0;
-            disabled = knobs().no_graph;
-        }
-    } graph_cc;
-    // the launch-fused path of a small system (fused.h): the recorded and levelled call sequences of the spin-free solver --
-    // intermediates alone, amplitudes alone (the term-by-term entry points) and the whole iteration
-    FusedSlot fused_int, fused_amp, fused_iter;
-    FusedSlot fused_so;   // ... and the spin-orbital iteration (build_tau / F / W + update_amplitudes)
-    void cc_programs_reset()
-    {
-        graph_cc.reset();
-        fused_slot_reset(cx, fused_int);
-        fused_slot_reset(cx, fused_amp);
-        fused_slot_reset(cx, fused_iter);
-    }
-    void so_programs_reset() { fused_slot_reset(cx, fused_so); }
 };
 
 namespace {
@@ -136,117 +106,15 @@ __global__ void synth_packed_kernel(double* packed, int64_t n, double scale, uin
         packed[k] = scale * (2.0 * hash_uniform(seed + (uint64_t)k) - 1.0);
 }
 
+// what an energy evaluation or an iteration reports, into the caller's optional outputs
+void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
+{
+    if (energy) *energy = r.energy;
+    if (rms_sq) *rms_sq = r.rms;
+    if (converged) *converged = r.converged;
+}
+
 }  // namespace
-
-// Runs `body` (launches on the context's lanes, no host synchronisation) directly for the first AFESP_GRAPH_AFTER calls,
-// then captures it into a graph once and replays the graph afterwards.  Nothing executes during capture, so a failed
-// capture simply falls back to running the body.
-template <typename Body>
-static void replay(afesp_ctx* ctx, afesp_ctx::GraphSlot& g, bool eligible, Body body)
-{
-    Context& cx = ctx->cx;
-    if (g.exec && g.epoch != cx.scratch_epoch) {   // a scratch buffer the graph refers to may have been freed since
-        (void)hipGraphExecDestroy(g.exec);
-        g.exec = nullptr;
-        g.calls = 0;
-    }
-    if (g.exec) {
-        AFESP_HIP(hipGraphLaunch(g.exec, cx.stream));
-        return;
-    }
-    if (!eligible || g.disabled) {
-        body();
-        return;
-    }
-    // Capturing and instantiating the ~110-node graph costs ~10 ms; a replay saves ~0.1 ms over the laned launches.  A real
-    // molecule converges in 15-30 iterations, so the capture waits until a context has iterated long enough for it to pay
-    // (AFESP_GRAPH_AFTER, default 40 calls).
-    const int graph_after = knobs().graph_after;
-    if (g.calls == 0 || g.epoch != cx.scratch_epoch || g.calls < graph_after) {
-        // first call, or cached scratch buffers were dropped since the last one: whatever the body (re)builds or allocates is
-        // done here, outside any capture
-        body();
-        g.calls = (g.epoch != cx.scratch_epoch) ? 1 : g.calls + 1;
-        g.epoch = cx.scratch_epoch;
-        return;
-    }
-    // The capture is opened on the origin stream (lane 0).  A body that throws half-way leaves another lane selected and
-    // events outstanding: both are put back BEFORE the capture is ended, and the capture is ended on the origin stream --
-    // ending it on a lane's stream would leave lane 0 capturing for ever, and the direct run below would execute nothing.
-    cx.use_lane(0);
-    hipStream_t origin = cx.stream;
-    hipGraph_t graph = nullptr;
-    if (hipStreamBeginCapture(origin, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-        (void)hipGetLastError();
-        g.disabled = true;
-        body();
-        return;
-    }
-    bool ok = true;
-    try {
-        body();
-    } catch (...) {
-        ok = false;
-    }
-    cx.use_lane(0);
-    cx.marks_used = 0;
-    const hipError_t e = hipStreamEndCapture(origin, &graph);
-    if (ok && e == hipSuccess && graph && hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess) {
-        (void)hipGraphDestroy(graph);
-        g.epoch = cx.scratch_epoch;
-        AFESP_HIP(hipGraphLaunch(g.exec, cx.stream));
-        return;
-    }
-    if (knobs().graph_debug) fprintf(stderr, "afesp: graph capture failed (body ok %d, end capture %d)\n", (int)ok, (int)e);
-    (void)hipGetLastError();
-    if (graph) (void)hipGraphDestroy(graph);
-    g.exec = nullptr;
-    g.disabled = true;
-    // a failed capture (e.g. lanes left unjoined by the throw) has been invalidated by EndCapture; make sure of it
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(origin, &st) != hipSuccess || st != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        throw Error(2, "afesp: the stream is still capturing after a failed graph capture");
-    }
-    for (size_t i = 1; i < cx.lanes.size(); ++i) {   // lanes that were pulled into the capture are out of it as well
-        hipStreamCaptureStatus ls = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(cx.lanes[i].stream, &ls) != hipSuccess || ls != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            throw Error(2, "afesp: a lane is still capturing after a failed graph capture");
-        }
-    }
-    body();
-}
-
-// One iteration up to the energy kernels (no host synchronisation): the launch-fused program of a small system (fused.h; recorded
-// from the very calls below on first use), the call-by-call sequence otherwise.
-static bool ccsd_iteration_body(afesp_ctx* ctx)   // true: the launch-fused program ran (read with ccsd_tail_read)
-{
-    if (ccsd_uses_lanes(ctx->cc) &&
-        fused_exec(ctx->cx, ctx->fused_iter, [&] {
-            ccsd_intermediates(ctx->cx, ctx->cc, true);
-            ccsd_amplitudes(ctx->cx, ctx->cc, true);
-            ccsd_tail_launch(ctx->cx, ctx->cc);
-        }))
-        return true;
-    // Large systems (one stream, whole-tensor products): the same two-kernel tail -- P(ia/jb) + division, the energy / rms sums and the
-    // DIIS history push in ONE pass over the residual instead of three (update, energy, push: 26 against 23 passes over o^2 v^2 elements at
-    // eight history vectors, and no host wait between the energy and the push); the <= 17 x 17 system is then solved on the host.
-    // AFESP_LARGE_TAIL=0: the three kernels.
-    if (!ccsd_uses_lanes(ctx->cc) && knobs().large_tail) {
-        ccsd_intermediates(ctx->cx, ctx->cc, true);
-        ccsd_amplitudes(ctx->cx, ctx->cc, true);
-        ccsd_tail_launch(ctx->cx, ctx->cc);
-        return true;
-    }
-    ctx->cc.tail_pending = false;
-    replay(ctx, ctx->graph_cc, ccsd_uses_lanes(ctx->cc), [&] {
-        ccsd_intermediates(ctx->cx, ctx->cc, true);
-        ccsd_amplitudes(ctx->cx, ctx->cc);
-        ccsd_energy_launch(ctx->cx, ctx->cc);
-    });
-    return false;
-}
 
 extern "C" {
 
@@ -338,13 +206,9 @@ void afesp_ctx_destroy(afesp_ctx* ctx)
     first_use_tls_device() = ctx->cx.device;   // (no guard here: the thread would otherwise keep its previous call's device)
     (void)hipSetDevice(ctx->cx.device);
     if (ctx->cx.startup.joinable()) ctx->cx.startup.join();
-    ctx->cc_programs_reset();
-    ctx->so_programs_reset();
+    ctx->sv.destroy(ctx->cx);
     comm_destroy(ctx->cx.comm);
     ctx->cx.comm = nullptr;
-    triples_plan_free(ctx->cc);
-    so_triples_plan_free(ctx->so);
-    ring_free(ctx->cx, ctx->cc);   // (the host-side descriptor of the ring launches; its device blocks go with the context)
     delete ctx;
 }
 
@@ -355,7 +219,7 @@ int afesp_ao2mo_mp2(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, const double* 
 {
     return entry(ctx, [&](Context& cx) {
         if (nbasis <= 0 || nocc <= 0 || nbasis - nocc <= 0 || nbasis > 1024) throw Error(1, "afesp_ao2mo_mp2: bad extents");
-        const double emp2 = ao2mo_mp2(cx, ctx->in, ctx->cc, nbasis, nocc, canon_coeff, canon_levels, eri_packed, eri_mo_packed);
+        const double emp2 = ao2mo_mp2(cx, ctx->in, ctx->sv, nbasis, nocc, canon_coeff, canon_levels, eri_packed, eri_mo_packed);
         if (e_mp2) *e_mp2 = emp2;
     });
 }
@@ -372,7 +236,7 @@ int afesp_mo_window(afesp_ctx* ctx, int64_t nbasis, int64_t nocc, int64_t n_froz
         if (!eri_mo_packed && (!ctx->in.mo || ctx->in.mo_n != n))
             throw Error(1, "afesp_mo_window: eri_mo_packed is NULL and no MO integrals are resident for this basis size "
                            "(call afesp_ao2mo_mp2 first; a window is taken once)");
-        const double emp2 = mo_window(cx, ctx->in, ctx->cc, n, nocc, nfc, nfv, canon_levels, eri_mo_packed, eri_act);
+        const double emp2 = mo_window(cx, ctx->in, ctx->sv, n, nocc, nfc, nfv, canon_levels, eri_mo_packed, eri_act);
         if (e_mp2) *e_mp2 = emp2;
     });
 }
@@ -399,214 +263,61 @@ int afesp_ccsd_init(afesp_ctx* ctx, int64_t nocc, int64_t nvirt, const double* e
     return entry(ctx, [&](Context& cx) {
         const int64_t n = nocc + nvirt;
         if (nocc <= 0 || nvirt <= 0 || n > 1024) throw Error(1, "afesp_ccsd_init: bad extents");
-        const double* src = ctx->in.mo;
-        double* tmp = nullptr;
-        if (eri_mo_packed) {
-            // (a same-shape state is about to be initialised where it lies: the packed integrals it kept for ccsd_need_vvvv go back
-            // to the arena BEFORE their successor is asked for -- a geometry scan never holds two packed arrays)
-            if (ccsd_can_reinit(ctx->cc, (int)nocc, (int)nvirt, diis_n_errmat) && ctx->cc.eri_own) {
-                cx.quiesce();
-                if (ctx->cc.eri_src == ctx->cc.eri_own) ctx->cc.eri_src = nullptr;
-                cx.release(ctx->cc.eri_own);
-                ctx->cc.eri_own = nullptr;
-            }
-            tmp = cx.alloc(neri_of(n));
-            AFESP_HIP(hipMemcpyAsync(tmp, eri_mo_packed, sizeof(double) * neri_of(n), hipMemcpyHostToDevice, cx.stream));
-            src = tmp;
-        } else if (!src || ctx->in.mo_n != n) {
+        if (!eri_mo_packed && (!ctx->in.mo || ctx->in.mo_n != n))
             throw Error(1, "afesp_ccsd_init: no MO integrals resident for this basis size (call afesp_ao2mo_mp2 first)");
-        }
-        // (a state of the same extents is initialised again where it lies: its compiled programs stay)
-        if (!ccsd_can_reinit(ctx->cc, (int)nocc, (int)nvirt, diis_n_errmat)) {
-            ctx->cc_programs_reset();
-            cx.drop_scratch("ao2mo_");   // the AO->MO temporaries
-        } else {
-            ctx->graph_cc.reset();
-        }
-        ccsd_init(cx, ctx->cc, (int)nocc, (int)nvirt, src, canon_levels, diis_n_errmat);
-        if (tmp) {
-            // a large system forms <ef|ab> on request only (ccsd_need_vvvv): its state keeps the device copy of the integrals
-            if (ctx->cc.v_vvvv.d) { cx.release(tmp); ctx->cc.eri_src = nullptr; }
-            else ctx->cc.eri_own = tmp;
-        }
+        ctx->sv.init(cx, (int)nocc, (int)nvirt, eri_mo_packed, ctx->in.mo, false, canon_levels, diis_n_errmat);
     });
 }
 
 int afesp_ccsd_energy(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_energy: call afesp_ccsd_init first");
-        int conv = ccsd_energy(cx, ctx->cc, e_tol, t_tol);
-        if (energy) *energy = ctx->cc.energy;
-        if (rms_sq) *rms_sq = ctx->cc.rms;
-        if (converged) *converged = conv;
+        report(ctx->sv.need_cc("afesp_ccsd_energy: call afesp_ccsd_init first").energy(cx, e_tol, t_tol), energy, rms_sq, converged);
     });
 }
 
 int afesp_ccsd_update_intermediates(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "call afesp_ccsd_init first");
-        ccsd_refresh_sharding(cx, ctx->cc);
-        if (!(ccsd_uses_lanes(ctx->cc) && fused_exec(cx, ctx->fused_int, [&] { ccsd_intermediates(cx, ctx->cc); })))
-            ccsd_intermediates(cx, ctx->cc);
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("call afesp_ccsd_init first").update_intermediates(cx); });
 }
 int afesp_ccsd_update_amplitudes(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) {
-        ctx->cc.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        if (!ctx->cc.ready) throw Error(1, "call afesp_ccsd_init first");
-        ccsd_refresh_sharding(cx, ctx->cc);
-        ctx->cc.tail_pending = false;
-        if (!(ccsd_uses_lanes(ctx->cc) && fused_exec(cx, ctx->fused_amp, [&] { ccsd_amplitudes(cx, ctx->cc); })))
-            ccsd_amplitudes(cx, ctx->cc);
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("call afesp_ccsd_init first").update_amplitudes(cx); });
 }
 
 int afesp_ccsd_iterate(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged)
 {
     return entry(ctx, [&](Context& cx) {
-        ctx->cc.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_iterate: call afesp_ccsd_init first");
-        ccsd_refresh_sharding(cx, ctx->cc);
-        const bool fused = ccsd_iteration_body(ctx);
-        int conv = fused ? ccsd_tail_read(cx, ctx->cc, e_tol, t_tol) : ccsd_energy_read(cx, ctx->cc, e_tol, t_tol);
-        if (energy) *energy = ctx->cc.energy;
-        if (rms_sq) *rms_sq = ctx->cc.rms;
-        if (converged) *converged = conv;
+        report(ctx->sv.need_cc("afesp_ccsd_iterate: call afesp_ccsd_init first").iterate(cx, e_tol, t_tol), energy, rms_sq, converged);
     });
 }
 
 int afesp_ccsd_diis(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) {
-        ctx->cc.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_diis: call afesp_ccsd_init first");
-        ccsd_diis_update(cx, ctx->cc);
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("afesp_ccsd_diis: call afesp_ccsd_init first").diis(cx); });
 }
 
 int afesp_ccsd_solve(afesp_ctx* ctx, int maxiter, double e_tol, double t_tol, double* iter_energy, double* iter_rms_sq, int* niter)
 {
     return entry(ctx, [&](Context& cx) {
-        ctx->cc.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_solve: call afesp_ccsd_init first");
-        CCState& s = ctx->cc;
-        // ccsd.f90:314-315, :325
-        s.energy = s.energy_old = 0.0;
-        k_fill(cx, s.t2_old.d, s.t2_old.size(), 0.0);
-        ccsd_energy(cx, s, e_tol, t_tol);
-        if (iter_energy) iter_energy[0] = s.energy;
-        if (iter_rms_sq) iter_rms_sq[0] = s.rms;
-        int result = -1;
-        ccsd_refresh_sharding(cx, s);
-        for (int it = 1; it <= maxiter; ++it) {
-            const bool fused = ccsd_iteration_body(ctx);
-            int conv = fused ? ccsd_tail_read(cx, s, e_tol, t_tol) : ccsd_energy_read(cx, s, e_tol, t_tol);
-            if (iter_energy) iter_energy[it] = s.energy;
-            if (iter_rms_sq) iter_rms_sq[it] = s.rms;
-            if (conv) {
-                result = it;
-                break;
-            }
-            ccsd_diis_update(cx, s);
-        }
-        if (result < 0 && maxiter > 0) diis_check_flag(cx, host_scalars(cx, DIIS_FLAG_SLOT + 1));   // a solve that failed after the last energy read
+        const int result = ctx->sv.need_cc("afesp_ccsd_solve: call afesp_ccsd_init first").solve(cx, maxiter, e_tol, t_tol, iter_energy, iter_rms_sq);
         if (niter) *niter = result;
     });
 }
 
 int afesp_ccsd_get_amplitudes(afesp_ctx* ctx, double* t1, double* t2)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_get_amplitudes: no CCSD state");
-        if (t1) AFESP_HIP(hipMemcpyAsync(t1, ctx->cc.t1.d, sizeof(double) * ctx->cc.t1.size(), hipMemcpyDeviceToHost, cx.stream));
-        if (t2) AFESP_HIP(hipMemcpyAsync(t2, ctx->cc.t2.d, sizeof(double) * ctx->cc.t2.size(), hipMemcpyDeviceToHost, cx.stream));
-        diis_check_flag(cx, host_scalars(cx, DIIS_FLAG_SLOT + 1));   // afesp_ccsd_diis does not wait for its solve: a failure surfaces here at the latest
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("afesp_ccsd_get_amplitudes: no CCSD state").get_amplitudes(cx, t1, t2); });
 }
 
 int afesp_ccsd_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2)
 {
-    return entry(ctx, [&](Context& cx) {
-        ctx->cc.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_set_amplitudes: no CCSD state");
-        // (a large system holds I_ovov / I_voov and copies of the OLD amplitudes in the layout of its ring launches (ring.hip): an
-        // afesp_ccsd_update_amplitudes that follows without new intermediates reads the reference-layout tensors and the new amplitudes)
-        if (ring_live(ctx->cc)) {
-            ring_tg_materialize(cx, ctx->cc, ctx->cc.I_ovov, ctx->cc.I_voov);
-            ring_invalidate(ctx->cc);
-        }
-        ctx->cc.amps_touched = true;
-        // (a launch-fused iteration has pushed its own result into the DIIS history already: afesp_ccsd_diis extrapolates the amplitudes
-        // current at the call, so it pushes again -- into the same slot, the tail has advanced no counter)
-        ctx->cc.tail_pending = false;
-        if (t2) ctx->cc.hist_plain = ctx->cc.nerr + 1;   // (its error vector may lack the amplitudes' symmetry: full DIIS sums until it has left the history)
-        if (t1) AFESP_HIP(hipMemcpyAsync(ctx->cc.t1.d, t1, sizeof(double) * ctx->cc.t1.size(), hipMemcpyHostToDevice, cx.stream));
-        if (t2) AFESP_HIP(hipMemcpyAsync(ctx->cc.t2.d, t2, sizeof(double) * ctx->cc.t2.size(), hipMemcpyHostToDevice, cx.stream));
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("afesp_ccsd_set_amplitudes: no CCSD state").set_amplitudes(cx, t1, t2); });
 }
 
 int afesp_ccsd_get_tensor(afesp_ctx* ctx, const char* name, double* out, int64_t capacity)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_get_tensor: no CCSD state");
-        CCState& s = ctx->cc;
-        struct { const char* n; const Tensor* t; } tab[] = {
-            {"v_oovv", &s.v_oovv}, {"v_ovov", &s.v_ovov}, {"v_vvov", &s.v_vvov}, {"v_oovo", &s.v_oovo}, {"v_oooo", &s.v_oooo},
-            {"v_vvvv", &s.v_vvvv}, {"I_vo", &s.I_vo}, {"I_vv", &s.I_vv}, {"I_oo_p", &s.I_oo_p}, {"I_oo", &s.I_oo},
-            {"c_oovv", &s.c}, {"asym_t2", &s.asym}, {"x_voov", &s.x_voov}, {"I_oooo", &s.I_oooo}, {"I_ovov", &s.I_ovov},
-            {"I_voov", &s.I_voov}, {"I_ooov_p", &s.I_ooov_p}, {"r1", &s.r1}, {"r2", &s.r2},
-            {"D1", &s.D1}, {"D2", &s.D2}, {"t1", &s.t1}, {"t2", &s.t2}};
-        if (!strcmp(name, "I_vovv_p")) {   // not formed by the iteration (ccsd.hip): built from the current t1 on request
-            const int64_t O = s.o, V = s.v;
-            if (V * O * V * V > capacity) throw Error(1, "afesp_ccsd_get_tensor: buffer too small for I_vovv_p");
-            Tensor t = view(cx.scratch("I_vovv_p", V * O * V * V), {V, O, V, V});
-            ccsd_build_I_vovv_p(cx, s, t);
-            AFESP_HIP(hipMemcpyAsync(out, t.d, sizeof(double) * t.size(), hipMemcpyDeviceToHost, cx.stream));
-            cx.sync();
-            return;
-        }
-        if (!strcmp(name, "v_vvvv")) ccsd_need_vvvv(cx, s);
-        for (auto& e : tab)
-            if (!strcmp(e.n, name)) {
-                if (e.t->size() > capacity) throw Error(1, std::string("afesp_ccsd_get_tensor: buffer too small for ") + name);
-                const double* src = e.t->d;
-                // the residuals of a laned iteration lie in partial buffers that the update kernel adds up (ccsd_amplitudes)
-                // (only what the LAST amplitudes call left there: a launch-fused or large-system call after a laned one has none)
-                auto add_partial = [&](double* dst, const char* buf) {
-                    auto it = cx.cache.find(buf);
-                    if (s.partials_live && it != cx.cache.end()) k_axpby(cx, dst, 1.0, (const double*)it->second.first, 1.0, e.t->size());
-                };
-                if (!strcmp(name, "r2")) {   // the reference's tmp_t2 before P(ia/jb) includes 1/2 pp; it is kept packed here
-                    double* full = cx.scratch("r2_full", e.t->size());
-                    k_r2_full(cx, full, s.r2.d, s.pp, s.o, s.v);
-                    add_partial(full, "r2_lane2");
-                    add_partial(full, "r2_lane3");
-                    if (ring_res_live(s)) k_add_swapped(cx, full, ring_Y(s), s.o, s.v);   // a ring term of a large system's residual (ring.hip)
-                    src = full;
-                } else if (ring_live(s) && (!strcmp(name, "I_ovov") || !strcmp(name, "I_voov"))) {
-                    // a large system's iteration holds these two in the layout its ring products read (ring.hip): turned back on request
-                    const int64_t O = s.o, V = s.v;
-                    Tensor io = view(cx.scratch("ring_I_ovov", e.t->size()), {O, V, O, V}), iv = view(cx.scratch("ring_I_voov", e.t->size()), {V, O, O, V});
-                    ring_tg_materialize(cx, s, io, iv);
-                    src = !strcmp(name, "I_ovov") ? io.d : iv.d;
-                } else if (!strcmp(name, "r1")) {
-                    double* full = cx.scratch("r1_full", e.t->size());
-                    k_copy(cx, full, s.r1.d, e.t->size());
-                    add_partial(full, "r1_lane5");
-                    src = full;
-                }
-                AFESP_HIP(hipMemcpyAsync(out, src, sizeof(double) * e.t->size(), hipMemcpyDeviceToHost, cx.stream));
-                cx.sync();
-                return;
-            }
-        throw Error(1, std::string("afesp_ccsd_get_tensor: unknown tensor ") + name);
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_cc("afesp_ccsd_get_tensor: no CCSD state").fetch_tensor(cx, name, out, capacity); });
 }
 
 int64_t afesp_ccsd_t_ntriples(int64_t nocc) { return triples_count((int)nocc); }
@@ -621,26 +332,22 @@ int afesp_ccsd_t_shard_bounds(afesp_ctx* ctx, int64_t nocc, int64_t nvirt, int c
 
 int afesp_ccsd_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double out[4])
 {
-    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->cc, t_begin, t_end, out); });
+    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->sv.cc, t_begin, t_end, out); });
 }
 
 int afesp_ccsd_t_plain(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double out[2])
 {
-    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->cc, t_begin, t_end, out, false, false); });
+    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->sv.cc, t_begin, t_end, out, false, false); });
 }
 
 int afesp_ccsd_cr_intermediates(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) {
-        ctx->cc.cr_epoch = ++cx.amp_clock;
-        ccsd_cr_intermediates(cx, ctx->cc);
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.cr_intermediates(cx); });
 }
 
 int afesp_ccsd_t_cr(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double out[6])
 {
-    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->cc, t_begin, t_end, out, true); });
+    return entry(ctx, [&](Context& cx) { ccsd_triples(cx, ctx->sv.cc, t_begin, t_end, out, true); });
 }
 
 // ---------------------------------------------------------------- input / output side of the path
@@ -771,7 +478,7 @@ int afesp_read_fcidump(afesp_ctx* ctx, const char* path, int64_t nbasis, int64_t
         if (nbasis <= 0 || nbasis > 1024 || nocc < 0 || nocc > nbasis) throw Error(1, "afesp_read_fcidump: bad extents");
         FcidumpResult r;
         r.h[0] = h_mo; r.fock[0] = fock; r.levels[0] = levels; r.eri[0] = eri_mo_packed;
-        read_fcidump(cx, ctx->in, ctx->cc, path, nbasis, nocc, r);
+        read_fcidump(cx, ctx->in, ctx->sv, path, nbasis, nocc, r);
         if (e_core) *e_core = r.e_core;
         if (e_ref) *e_ref = r.e_ref;
         if (fock_offdiag) *fock_offdiag = r.fock_offdiag;
@@ -822,7 +529,7 @@ int afesp_read_fcidump_rohf(afesp_ctx* ctx, const char* path, int64_t nbasis, in
             throw Error(1, "afesp_read_fcidump_rohf: bad extents (need 0 <= nbeta <= nalpha <= nbasis)");
         FcidumpResult r;
         r.h[0] = h_mo; r.fock[0] = fock_a; r.fock[1] = fock_b; r.eri[0] = eri_mo_packed;
-        read_fcidump_rohf(cx, ctx->in, ctx->cc, path, nbasis, nalpha, nbeta, r);
+        read_fcidump_rohf(cx, ctx->in, ctx->sv, path, nbasis, nalpha, nbeta, r);
         if (e_core) *e_core = r.e_core;
         if (e_ref) *e_ref = r.e_ref;
         if (fock_offdiag)
@@ -845,106 +552,45 @@ int afesp_ccsd_so_init(afesp_ctx* ctx, int64_t nbasis, int64_t nel, const double
 {
     return entry(ctx, [&](Context& cx) {
         if (nbasis <= 0 || nbasis > 512 || nel <= 0 || nel >= 2 * nbasis) throw Error(1, "afesp_ccsd_so_init: bad extents");
-        const double* src = ctx->in.mo;
-        double* tmp = nullptr;
-        if (eri_mo_packed) {
-            tmp = cx.alloc(neri_of(nbasis));
-            AFESP_HIP(hipMemcpyAsync(tmp, eri_mo_packed, sizeof(double) * neri_of(nbasis), hipMemcpyHostToDevice, cx.stream));
-            src = tmp;
-        } else if (!src || ctx->in.mo_n != nbasis) {
+        if (!eri_mo_packed && (!ctx->in.mo || ctx->in.mo_n != nbasis))
             throw Error(1, "afesp_ccsd_so_init: no MO integrals resident for this basis size (call afesp_ao2mo_mp2 first)");
-        }
-        cx.drop_scratch("ao2mo_");   // the AO->MO temporaries
-        ctx->so_programs_reset();
-        so_init(cx, ctx->so, (int)nbasis, (int)nel, src, canon_levels, diis_n_errmat, (flags & AFESP_SO_FOO_AS_PUBLISHED) != 0);
-        ctx->so.amp_epoch = ++cx.amp_clock;
-        if (tmp) cx.release(tmp);
+        ctx->sv.so_init_packed(cx, (int)nbasis, (int)nel, eri_mo_packed, ctx->in.mo, canon_levels, diis_n_errmat,
+                               (flags & AFESP_SO_FOO_AS_PUBLISHED) != 0);
     });
 }
 
 int afesp_ccsd_so_energy(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_energy: call afesp_ccsd_so_init first");
-        int conv = so_energy(cx, ctx->so, e_tol, t_tol);
-        if (energy) *energy = ctx->so.energy;
-        if (rms_sq) *rms_sq = ctx->so.rms;
-        if (converged) *converged = conv;
+        report(ctx->sv.need_so("afesp_ccsd_so_energy: call afesp_ccsd_so_init first").so_energy_step(cx, e_tol, t_tol), energy, rms_sq, converged);
     });
 }
 
 int afesp_ccsd_so_iterate(afesp_ctx* ctx, double e_tol, double t_tol, double* energy, double* rms_sq, int* converged)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_iterate: call afesp_ccsd_so_init first");
-        ctx->so.amp_epoch = ++cx.amp_clock;   // (the amplitudes may change: derived copies go stale)
-        // (the levelled sequence of fused.h where the system is small enough for its products to be launch-bound: the big ones
-        // keep their own kernels inside it)
-        auto body = [&] {
-            diis_save(cx, ctx->so);
-            so_intermediates(cx, ctx->so);
-            so_amplitudes(cx, ctx->so);
-        };
-        if (!(ctx->so.t2.size() <= ((int64_t)1 << 22) && fused_exec(cx, ctx->fused_so, body))) body();
-        int conv = so_energy(cx, ctx->so, e_tol, t_tol);
-        if (energy) *energy = ctx->so.energy;
-        if (rms_sq) *rms_sq = ctx->so.rms;
-        if (converged) *converged = conv;
+        report(ctx->sv.need_so("afesp_ccsd_so_iterate: call afesp_ccsd_so_init first").so_iterate(cx, e_tol, t_tol), energy, rms_sq, converged);
     });
 }
 
 int afesp_ccsd_so_diis(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_diis: call afesp_ccsd_so_init first");
-        ctx->so.amp_epoch = ++cx.amp_clock;
-        diis_update(cx, ctx->so);
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_diis: call afesp_ccsd_so_init first").so_diis(cx); });
 }
 
 int afesp_ccsd_so_get_amplitudes(afesp_ctx* ctx, double* t1, double* t2)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_get_amplitudes: no spin-orbital CCSD state");
-        SOState& s = ctx->so;
-        if (t1) AFESP_HIP(hipMemcpyAsync(t1, s.t1.d, sizeof(double) * s.t1.size(), hipMemcpyDeviceToHost, cx.stream));
-        if (t2) AFESP_HIP(hipMemcpyAsync(t2, s.t2.d, sizeof(double) * s.t2.size(), hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_get_amplitudes: no spin-orbital CCSD state").so_get_amplitudes(cx, t1, t2); });
 }
 
 int afesp_ccsd_so_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_set_amplitudes: no spin-orbital CCSD state");
-        ctx->so.amp_epoch = ++cx.amp_clock;
-        SOState& s = ctx->so;
-        if (t1) AFESP_HIP(hipMemcpyAsync(s.t1.d, t1, sizeof(double) * s.t1.size(), hipMemcpyHostToDevice, cx.stream));
-        if (t2) AFESP_HIP(hipMemcpyAsync(s.t2.d, t2, sizeof(double) * s.t2.size(), hipMemcpyHostToDevice, cx.stream));
-        cx.sync();
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_set_amplitudes: no spin-orbital CCSD state").so_set_amplitudes(cx, t1, t2); });
 }
 
 int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int64_t capacity)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (!ctx->so.ready) throw Error(1, "afesp_ccsd_so_get_tensor: no spin-orbital CCSD state");
-        SOState& s = ctx->so;
-        if (!strcmp(name, "W_vvvv")) so_build_W_vvvv(cx, s);   // not formed by the iteration (so_ladder): built from the current t1 on request
-        struct { const char* n; const Tensor* t; } tab[] = {
-            {"F_vv", &s.F_vv}, {"F_oo", &s.F_oo}, {"F_ov", &s.F_ov}, {"W_oooo", &s.W_oooo}, {"W_vvvv", &s.W_vvvv},
-            {"W_ovvo", &s.W_ovvo}, {"tau", &s.tau}, {"tau_tilde", &s.tau_t}, {"oovv", &s.oovv}, {"vvvv", &s.vvvv},
-            {"t1", &s.t1}, {"t2", &s.t2}, {"f_ov", &s.f_ov}, {"f_oo", &s.f_oo}, {"f_vv", &s.f_vv}};
-        for (auto& e : tab)
-            if (!strcmp(e.n, name)) {
-                if (!e.t->d) throw Error(1, std::string("afesp_ccsd_so_get_tensor: this state holds no ") + name + " (afesp_ccsd_uso_init_fock makes one that does)");
-                if (e.t->size() > capacity) throw Error(1, std::string("afesp_ccsd_so_get_tensor: buffer too small for ") + name);
-                AFESP_HIP(hipMemcpyAsync(out, e.t->d, sizeof(double) * e.t->size(), hipMemcpyDeviceToHost, cx.stream));
-                cx.sync();
-                return;
-            }
-        throw Error(1, std::string("afesp_ccsd_so_get_tensor: unknown tensor ") + name);
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_get_tensor: no spin-orbital CCSD state").so_fetch_tensor(cx, name, out, capacity); });
 }
 
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)nocc); }
@@ -952,7 +598,7 @@ int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)no
 int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t)
 {
     return entry(ctx, [&](Context& cx) {
-        const double e = so_triples(cx, ctx->so, t_begin, t_end);
+        const double e = so_triples(cx, ctx->sv.so, t_begin, t_end);
         if (e_t) *e_t = e;
     });
 }
@@ -1037,47 +683,14 @@ int afesp_ump2_vv_density(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_
 int afesp_ccsd_uso_init(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* levels_a, const double* levels_b,
                         int diis_n_errmat)
 {
-    return entry(ctx, [&](Context& cx) {
-        if (nbasis <= 0 || nbasis > 512 || nalpha < 0 || nbeta < 0 || nalpha > nbasis || nbeta > nbasis || nalpha + nbeta <= 0 ||
-            nalpha + nbeta >= 2 * nbasis || !levels_a || !levels_b)
-            throw Error(1, "afesp_ccsd_uso_init: bad extents");
-        if (!ctx->in.uhf_aa || ctx->in.uhf_n != nbasis)
-            throw Error(1, "afesp_ccsd_uso_init: no UHF MO integrals resident for this basis size (call afesp_ao2mo_ump2 first)");
-        const int64_t o = nalpha + nbeta, v = 2 * nbasis - o;
-        cx.drop_scratch("ao2mo_");   // the AO->MO temporaries
-        ctx->so_programs_reset();
-        so_free(cx, ctx->so);        // (a previous state's memory counts as available)
-        // against the free device memory plus the context's idle blocks: the resident UHF (and RHF) integral blocks are in use
-        size_t free_b = 0, total_b = 0;
-        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (so_state_bytes(o, v, diis_n_errmat) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
-            throw Error(1, "afesp_ccsd_uso_init: the dense spin-orbital state of this system does not fit the free device memory");
-        so_init_uhf(cx, ctx->so, (int)nbasis, (int)nalpha, (int)nbeta, ctx->in.uhf_aa, ctx->in.uhf_bb, ctx->in.uhf_ab, levels_a, levels_b, diis_n_errmat);
-        ctx->so.amp_epoch = ++cx.amp_clock;
-    });
+    return entry(ctx, [&](Context& cx) { ctx->sv.uso_init(cx, ctx->in, nbasis, nalpha, nbeta, levels_a, levels_b, diis_n_errmat); });
 }
 
 int afesp_ccsd_uso_init_fock(afesp_ctx* ctx, int64_t nbasis, int64_t nalpha, int64_t nbeta, const double* fock_a, const double* fock_b,
                              int diis_n_errmat, double* e_mp2)
 {
     return entry(ctx, [&](Context& cx) {
-        if (nbasis <= 0 || nbasis > 512 || nalpha < 0 || nbeta < 0 || nalpha > nbasis || nbeta > nbasis || nalpha + nbeta <= 0 ||
-            nalpha + nbeta >= 2 * nbasis || !fock_a || !fock_b)
-            throw Error(1, "afesp_ccsd_uso_init_fock: bad extents");
-        if (!ctx->in.uhf_aa || ctx->in.uhf_n != nbasis)
-            throw Error(1, "afesp_ccsd_uso_init_fock: no UHF MO integrals resident for this basis size (call afesp_mo_rotate_uhf or "
-                           "afesp_ao2mo_ump2 first)");
-        const int64_t o = nalpha + nbeta, v = 2 * nbasis - o;
-        cx.drop_scratch("ao2mo_");   // the transform's temporaries
-        ctx->so_programs_reset();
-        so_free(cx, ctx->so);        // (a previous state's memory counts as available)
-        size_t free_b = 0, total_b = 0;
-        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (so_state_bytes(o, v, diis_n_errmat) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
-            throw Error(1, "afesp_ccsd_uso_init_fock: the dense spin-orbital state of this system does not fit the free device memory");
-        const double e2 = so_init_fock(cx, ctx->so, (int)nbasis, (int)nalpha, (int)nbeta, ctx->in.uhf_aa, ctx->in.uhf_bb, ctx->in.uhf_ab, fock_a,
-                                       fock_b, diis_n_errmat);
-        ctx->so.amp_epoch = ++cx.amp_clock;
+        const double e2 = ctx->sv.uso_init_fock(cx, ctx->in, nbasis, nalpha, nbeta, fock_a, fock_b, diis_n_errmat);
         if (e_mp2) *e_mp2 = e2;
     });
 }
@@ -1162,11 +775,7 @@ int afesp_synthetic_init(afesp_ctx* ctx, int64_t nocc, int64_t nvirt, double sca
         double* packed = cx.alloc(ne);
         AFESP_KLAUNCH(synth_packed_kernel, dim3(4096), dim3(256), 0, cx.stream, packed, ne, scale, seed);
         AFESP_HIP(hipGetLastError());
-        if (!ccsd_can_reinit(ctx->cc, (int)nocc, (int)nvirt, diis_n_errmat)) ctx->cc_programs_reset();
-        else ctx->graph_cc.reset();
-        ccsd_init(cx, ctx->cc, (int)nocc, (int)nvirt, packed, e.data(), diis_n_errmat);
-        if (ctx->cc.v_vvvv.d) { cx.release(packed); ctx->cc.eri_src = nullptr; }
-        else ctx->cc.eri_own = packed;   // kept for ccsd_need_vvvv
+        ctx->sv.init(cx, (int)nocc, (int)nvirt, nullptr, packed, true, e.data(), diis_n_errmat);   // (`packed` is the state's from here on)
     });
 }
 
@@ -1182,37 +791,20 @@ int afesp_synthetic_ao(afesp_ctx* ctx, int64_t nbasis, double scale, uint64_t se
     });
 }
 
-// Floating-point operations of one particle-particle ladder as this context evaluates it (plain a <= b form or the
-// symmetric/antisymmetric pair form, ccsd.hip)
+// Floating-point operations of one particle-particle ladder / one CCSD iteration as this context evaluates it (solver.hip)
 int afesp_ccsd_pp_ladder_flop(afesp_ctx* ctx, double* flop)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_pp_ladder_flop: no CCSD state");
-        const double O = ctx->cc.o, V = ctx->cc.v, ps = V * (V + 1) / 2, pa = V * (V - 1) / 2;
-        if (flop) *flop = ctx->cc.pp_sym ? 2.0 * (O * (O + 1) / 2 * ps * ps + O * (O - 1) / 2 * pa * pa) : 2.0 * O * O * V * V * ps;
+        const double f = ctx->sv.need_cc("afesp_ccsd_pp_ladder_flop: no CCSD state").pp_ladder_flop();
+        if (flop) *flop = f;
     });
 }
 
-// Floating-point operations of one CCSD iteration as this context evaluates it: SURVEY.md 8(d)'s sum over the contraction sites,
-// with the pp-ladder and the t2 x <ef|ia> product counted in the form they are executed (plain, a <= b, or over pair indices)
 int afesp_ccsd_iteration_flop(afesp_ctx* ctx, double* flop)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_ccsd_iteration_flop: no CCSD state");
-        const double O = ctx->cc.o, V = ctx->cc.v, ps = V * (V + 1) / 2, pa = V * (V - 1) / 2, os = O * (O + 1) / 2, oa = O * (O - 1) / 2;
-        const bool sym = ctx->cc.pp_sym;
-        const double pp = sym ? 2.0 * (os * ps * ps + oa * pa * pa) : 2.0 * O * O * V * V * ps;
-        const double ooov = sym ? 2.0 * O * V * (os * ps + oa * pa) : 2.0 * O * O * O * V * V * V;
-        const double o3v3 = O * O * O * V * V * V;
-        // large-system path (round 5): c <ij|ef> -> I_oooo and the hole-hole ladder over pair indices (the latter inside the pp-ladder's
-        // products), and the bare t(i,e) <ab|ej> term as a copy of x_voov instead of a third o^2 v^3 product
-        const bool large = !ccsd_uses_lanes(ctx->cc);
-        const double oooo = (sym && large) ? 4.0 * (os * os * ps + oa * oa * pa) : 2.0 * O * O * O * O * V * V;
-        // (... and asym(m,i,e,f) <ef|ma> -> r1 as a trace of the pair-form t2 <ef|ia> product: one more o^2 v^3 product that is not executed)
-        const double o2v3 = large ? (sym ? 14.0 : 16.0) : 18.0;
-        if (flop)
-            *flop = pp + ooov + 12.0 * o3v3 + oooo + 2.0 * O * O * O * O * V + o2v3 * O * O * V * V * V +
-                    2.0 * O * V * V * V + 14.0 * O * O * O * V * V;
+        const double f = ctx->sv.need_cc("afesp_ccsd_iteration_flop: no CCSD state").iteration_flop();
+        if (flop) *flop = f;
     });
 }
 
@@ -1273,8 +865,8 @@ int afesp_bench_contract(afesp_ctx* ctx, const char* la, const int64_t* dimsA, c
 int afesp_time_pp_ladder(afesp_ctx* ctx, int reps, double* ms_per_launch)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready) throw Error(1, "afesp_time_pp_ladder: no CCSD state");
-        const double ms = time_on_stream(cx, reps, [&] { ccsd_pp_ladder(cx, ctx->cc); });
+        CCState& cc = ctx->sv.need_cc("afesp_time_pp_ladder: no CCSD state").cc;
+        const double ms = time_on_stream(cx, reps, [&] { ccsd_pp_ladder(cx, cc); });
         if (ms_per_launch) *ms_per_launch = ms;
     });
 }
@@ -1305,7 +897,7 @@ int afesp_comm_init(afesp_ctx* ctx, int rank, int world, int transport, const ch
     return entry(ctx, [&](Context& cx) {
         if (cx.comm) throw Error(1, "afesp_comm_init: this context already has a communicator");
         cx.comm = comm_create(cx, rank, world, transport, bootstrap_path, unique_id);
-        ctx->cc_programs_reset();   // a captured iteration does not contain the rank split
+        ctx->sv.cc_programs_reset(cx);   // a captured iteration does not contain the rank split
     });
 }
 
@@ -1315,7 +907,7 @@ int afesp_comm_destroy(afesp_ctx* ctx)
         cx.sync();
         comm_destroy(cx.comm);
         cx.comm = nullptr;
-        ctx->cc_programs_reset();
+        ctx->sv.cc_programs_reset(cx);
     });
 }
 
@@ -1331,9 +923,8 @@ int afesp_allreduce_sum(afesp_ctx* ctx, double* inout, int64_t n)
 int afesp_ccsd_is_split(afesp_ctx* ctx, int* split)
 {
     return entry(ctx, [&](Context& cx) {
-        if (!ctx->cc.ready || !split) throw Error(1, "afesp_ccsd_is_split: no CCSD state");
-        ccsd_refresh_sharding(cx, ctx->cc);
-        *split = ctx->cc.sharded ? 1 : 0;
+        if (!split) throw Error(1, "afesp_ccsd_is_split: no CCSD state");
+        *split = ctx->sv.need_cc("afesp_ccsd_is_split: no CCSD state").is_split(cx) ? 1 : 0;
     });
 }
 
@@ -1349,7 +940,7 @@ int afesp_ccsd_iteration_launches(afesp_ctx* ctx, int* launches)
 {
     return entry(ctx, [&](Context& cx) {
         if (!launches) throw Error(1, "afesp_ccsd_iteration_launches: null argument");
-        *launches = fused_launches(ctx->fused_iter.prog);
+        *launches = ctx->sv.iteration_launches();
     });
 }
 

@@ -70,11 +70,11 @@ struct CCState : DiisRing {
     const double* eri_src = nullptr;
     double* eri_own = nullptr;
     bool have_cr = false;
-    // bumped by every entry point that may change t1 / t2 (resp. the CR intermediates): what is derived from them -- the (T)
+    // bumped by every solver function that may change t1 / t2 (resp. the CR intermediates; solver.h): what is derived from them -- the (T)
     // operand copies, triples.hip -- is rebuilt only when these have moved on
     int64_t amp_epoch = 0, cr_epoch = 0;
     void* ring = nullptr;       // the ring products' operands and descriptors on the LDS-DMA GEMM (ring.hip), large systems
-    bool partials_live = false; // the last amplitudes call left terms of r2 / r1 in the laned partial buffers (afesp_ccsd_get_tensor)
+    bool partials_live = false; // the last amplitudes call left terms of r2 / r1 in the laned partial buffers (ccsd_residual_full)
     int64_t frozen_id = 0;   // what ccsd_init stamped the immutable integral slices with (contract() keeps re-laid-out copies of those)
 };
 void triples_plan_free(CCState& s);
@@ -110,6 +110,7 @@ int ccsd_tail_read(Context& cx, CCState& s, double e_tol, double t_tol);
 void ccsd_pp_ladder(Context& cx, CCState& s);
 // out = nullptr: into I_ooov_p, all rows; otherwise the rows (i, a) with a in [a0, a1) into out(j,k,i,a) (the split iteration's slice)
 void ccsd_ooov_pair_form(Context& cx, CCState& s, double* out = nullptr, int64_t a0 = 0, int64_t a1 = 0);
+const double* ccsd_residual_full(Context& cx, CCState& s, bool r2);   // r2 / r1 of the last ccsd_amplitudes, laned partials and ring term added
 void ccsd_build_I_vovv_p(Context& cx, CCState& s, const Tensor& out);   // out(c,i,a,b), dense v x o x v x v
 bool pp_sym_pays(int64_t o, int64_t v);   // whether ccsd_init chooses the split form (AFESP_PP_SYM=0/1 overrides)
 // updates s.energy / s.energy_old / s.rms (un-rooted, as ccsd.f90:1806); returns 1 if converged

@@ -622,6 +622,9 @@ void ccsd_ooov_pair_form(Context& cx, CCState& s, double* out, int64_t a0, int64
     }
 }
 
+// the partial residuals of a laned update (scratch names): terms of r2 from lanes 2 and 3, of r1 from lane 5
+static const char *const R2_LANE2 = "r2_lane2", *const R2_LANE3 = "r2_lane3", *const R1_LANE5 = "r1_lane5";
+
 void ccsd_amplitudes(Context& cx, CCState& s, bool defer_update)
 {
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
@@ -645,9 +648,9 @@ void ccsd_amplitudes(Context& cx, CCState& s, bool defer_update)
         AFESP_HIP(hipMemsetAsync(s.pp, 0, sizeof(double) * ((int64_t)s.o * s.o * np + s.r2.size() + s.r1.size()), cx.stream));   // [PP | r2_sh | r1_sh]
     }
     if (par) {
-        r2b.d = cx.scratch("r2_lane2", s.r2.size());
-        r2c.d = cx.scratch("r2_lane3", s.r2.size());
-        r1b.d = cx.scratch("r1_lane5", s.r1.size());
+        r2b.d = cx.scratch(R2_LANE2, s.r2.size());
+        r2c.d = cx.scratch(R2_LANE3, s.r2.size());
+        r1b.d = cx.scratch(R1_LANE5, s.r1.size());
         cx.fork(6);
     }
     lane(0);
@@ -731,6 +734,29 @@ void ccsd_amplitudes(Context& cx, CCState& s, bool defer_update)
                 par ? r1b.d : nullptr, s.D1.d, ring ? ring_Y(s) : nullptr);
 }
 
+// The whole r2 / r1 of the last ccsd_amplitudes in scratch (afesp_ccsd_get_tensor): the residuals of a laned iteration lie in partial
+// buffers that the update kernel adds up -- only what the LAST amplitudes call left there: a launch-fused or large-system call after a
+// laned one has none
+const double* ccsd_residual_full(Context& cx, CCState& s, bool r2)
+{
+    const int64_t n = r2 ? s.r2.size() : s.r1.size();
+    double* full = cx.scratch(r2 ? "r2_full" : "r1_full", n);
+    auto add_partial = [&](const char* buf) {
+        auto it = cx.cache.find(buf);
+        if (s.partials_live && it != cx.cache.end()) k_axpby(cx, full, 1.0, (const double*)it->second.first, 1.0, n);
+    };
+    if (r2) {   // the reference's tmp_t2 before P(ia/jb) includes 1/2 pp; it is kept packed here
+        k_r2_full(cx, full, s.r2.d, s.pp, s.o, s.v);
+        add_partial(R2_LANE2);
+        add_partial(R2_LANE3);
+        if (ring_res_live(s)) k_add_swapped(cx, full, ring_Y(s), s.o, s.v);   // a ring term of a large system's residual (ring.hip)
+    } else {
+        k_copy(cx, full, s.r1.d, n);
+        add_partial(R1_LANE5);
+    }
+    return full;
+}
+
 // The intermediate of ccsd.f90:1255-1272 as a tensor (tests / afesp_ccsd_get_tensor); the iteration never forms it.
 void ccsd_build_I_vovv_p(Context& cx, CCState& s, const Tensor& out)
 {
@@ -812,7 +838,7 @@ int ccsd_tail_read(Context& cx, CCState& s, double e_tol, double t_tol)
     return (std::sqrt(s.rms) < t_tol && std::fabs(s.energy - s.energy_old) < e_tol) ? 1 : 0;   // ccsd.f90:1805
 }
 
-// The energy evaluation in two halves: the launches (part of the replayed iteration, capi.hip) and the host read.
+// The energy evaluation in two halves: the launches (part of the replayed iteration, solver.hip) and the host read.
 void ccsd_energy_launch(Context& cx, CCState& s)
 {
     k_cc_energy(cx, cx.scal, s.v_oovv.d, s.t1.d, s.t2.d, s.t2_old.d, s.o, s.v);

@@ -154,6 +154,13 @@ void Context::release(void* p)
         arena.put(p);
     }
 }
+bool Context::fits(double bytes) const
+{
+    size_t free_b = 0, total_b = 0;
+    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
+    return !(bytes > 0.9 * ((double)free_b + (double)arena.idle_bytes));
+}
+
 int64_t* Context::plan_alloc(size_t n)
 {
     n = (n + 1) & ~(size_t)1;

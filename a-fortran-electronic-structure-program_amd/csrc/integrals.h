@@ -4,6 +4,8 @@
 
 namespace afesp {
 
+struct Solver;   // solver.h: told when a packed array its spin-free state may read goes away
+
 inline int64_t npair_of(int64_t n) { return n * (n + 1) / 2; }
 inline int64_t neri_of(int64_t n) { return npair_of(npair_of(n)); }
 
@@ -56,17 +58,17 @@ struct Integrals {
     void adopt_uhf(Context& cx, int64_t n);            // the three blocks for basis size n (kept where they are of that size)
     void swap_uhf(Context& cx, double* aa, double* bb, double* ab, int64_t n);   // three filled blocks take the resident ones' place (afesp_read_fcidump_uhf)
     void window_uhf(Context& cx, int64_t n_act, int64_t lo);   // the orbitals [lo, lo + n_act) of the three blocks, as afesp_mo_window's of mo
-    void drop_mo(Context& cx, CCState& cc);            // back to the arena; a solver state initialised from them can no longer form <ef|ab>
-    double* replace_mo(Context& cx, CCState& cc, int64_t n);   // the array a transform writes: the resident one if it has the size
+    void drop_mo(Context& cx, Solver& sv);            // back to the arena; a solver state initialised from them can no longer form <ef|ab>
+    double* replace_mo(Context& cx, Solver& sv, int64_t n);   // the array a transform writes: the resident one if it has the size
     void set_mo(double* packed, int64_t n) { mo = packed; mo_n = n; }
 };
 
 // the bodies of the entry points of the same names (capi.hip checks the arguments); each returns the energy / the count it reports
-double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, const double* coeff, const double* levels,
+double ao2mo_mp2(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t o, const double* coeff, const double* levels,
                  const double* eri_packed, double* eri_mo_packed);
 double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
                   const double* levels_a, const double* levels_b, const double* eri_packed, double* eri_aa, double* eri_ab, double* eri_bb);
-double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
+double mo_window(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
                  const double* eri_mo_packed, double* eri_act);
 // E(UMP2) of the three resident blocks (levels on the host, for their basis size), and the blocks themselves for whoever asks
 double ump2_of_blocks(Context& cx, const Integrals& in, const double* levels_a, const double* levels_b, int64_t oa, int64_t ob, double* eri_aa,
@@ -102,11 +104,11 @@ struct FcidumpResult {
     int64_t nread = 0;
 };
 int fcidump_scan(const char* path, int64_t* norb, int64_t* nelec, int64_t* ms2, int* uhf, int64_t* nlines);
-void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r);
+void read_fcidump(Context& cx, Integrals& in, Solver& sv, const char* path, int64_t n, int64_t nocc, FcidumpResult& r);
 void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
 // a restricted open-shell file (no UHF flag, MS2 = na - nb >= 0): read_fcidump's parse, scatter and residency; r.fock[0] / [1] the two spin
 // Fock operators of the determinant (k_fock_ro), r.fock_offdiag3 their largest off-diagonal elements by block
-void read_fcidump_rohf(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
+void read_fcidump_rohf(Context& cx, Integrals& in, Solver& sv, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
 // The two spin Fock operators of the restricted determinant that fills the first na / nb orbitals, from h (n x n, device) and the packed
 // MO integrals: one wave per pair, fixed summation order, symmetric to the bit (integrals.hip)
 void k_fock_ro(Context& cx, double* fa, double* fb, const double* h, const double* packed, int n, int na, int nb);

@@ -7,6 +7,7 @@
 #include "fcidump_format.h"
 #include "fcidump_parse.h"
 #include "integrals.h"
+#include "solver.h"
 #include "tgemm.h"
 
 using namespace afesp;
@@ -500,24 +501,24 @@ void Integrals::swap_uhf(Context& cx, double* aa, double* bb, double* ab, int64_
     uhf_n = n;
 }
 
-void Integrals::drop_mo(Context& cx, CCState& cc)
+void Integrals::drop_mo(Context& cx, Solver& sv)
 {
-    if (cc.eri_src == mo) cc.eri_src = nullptr;
+    sv.eri_gone(mo);
     if (mo) cx.release(mo);
     set_mo(nullptr, 0);
 }
 
-double* Integrals::replace_mo(Context& cx, CCState& cc, int64_t n)
+double* Integrals::replace_mo(Context& cx, Solver& sv, int64_t n)
 {
     if (mo && mo_n == n) {   // a transform of the same basis size overwrites the previous result
-        if (cc.eri_src == mo) cc.eri_src = nullptr;
+        sv.eri_gone(mo);
         return mo;
     }
-    drop_mo(cx, cc);
+    drop_mo(cx, sv);
     return cx.alloc_raw(neri_of(n));
 }
 
-double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, const double* coeff, const double* levels,
+double ao2mo_mp2(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t o, const double* coeff, const double* levels,
                  const double* eri_packed, double* eri_mo_packed)
 {
     const int64_t ne = neri_of(n);
@@ -525,7 +526,7 @@ double ao2mo_mp2(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t o, 
         throw Error(1, "afesp_ao2mo_mp2: eri_packed is NULL and no AO integrals were read onto the device for this basis size");
     cx.drop_scratch("t_");   // the (T) pool of a previous system holds the blocks the two temporaries below were
     in.release_uhf(cx);      // an RHF transform ends the open-shell calculation: its integral blocks go back to the arena
-    double* packed = in.replace_mo(cx, cc, n);
+    double* packed = in.replace_mo(cx, sv, n);
     const double* ao = in.ao;   // NULL source: transformed where afesp_read_eri_text / afesp_set_eri left them
     if (eri_packed) {           // upload buffer, then the packed MO integrals
         AFESP_HIP(hipMemcpyAsync(packed, eri_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
@@ -597,9 +598,7 @@ static void uhf_blocks_fit(Context& cx, Integrals& in, const Ao2moForm& form, in
     const double tmp = form.pair ? 2.0 * np * np : 3.0 * n * n * np;
     const double blocks = (in.uhf_n == n && in.uhf_aa) ? 0.0 : 2.0 * ne + (double)np * np;
     if (in.uhf_n != n) in.release_uhf(cx);   // (blocks of another basis size: returned before their successors are sized)
-    size_t free_b = 0, total_b = 0;
-    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (8.0 * (tmp + blocks + 4.0 * n * n) > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+    if (!cx.fits(8.0 * (tmp + blocks + 4.0 * n * n)))
         throw Error(1, std::string(who) + ": the open-shell transform of this basis does not fit the free device memory");
 }
 
@@ -705,13 +704,13 @@ double mo_fock_ro(Context& cx, const Integrals& in, int64_t n, int64_t na, int64
 
 // The active orbital window [nfc, n - nfv) of the resident (or handed-in) packed MO integrals: a gather after the full transform
 // (DESIGN.md), left resident as afesp_ao2mo_mp2 leaves a basis of n_act functions; the full array goes back to the arena here.
-double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
+double mo_window(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t nocc, int64_t nfc, int64_t nfv, const double* levels,
                  const double* eri_mo_packed, double* eri_act)
 {
     const int64_t na = n - nfc - nfv, o = nocc - nfc, v = na - o, ne = neri_of(n), nea = neri_of(na);
     double* full = in.mo;
     if (eri_mo_packed) {   // from the host: whatever was resident is replaced, as a transform would replace it
-        in.drop_mo(cx, cc);
+        in.drop_mo(cx, sv);
         full = cx.alloc_raw(ne);
         AFESP_HIP(hipMemcpyAsync(full, eri_mo_packed, sizeof(double) * ne, hipMemcpyHostToDevice, cx.stream));
     }
@@ -726,7 +725,7 @@ double mo_window(Context& cx, Integrals& in, CCState& cc, int64_t n, int64_t noc
             throw;
         }
         if (eri_mo_packed) cx.release(full);   // (waits for the gather) a context never keeps two packed arrays past the call
-        else in.drop_mo(cx, cc);
+        else in.drop_mo(cx, sv);
     }
     in.set_mo(act, na);
     const double emp2 = mp2_of_packed(cx, act, levels + nfc, o, v);
@@ -747,9 +746,7 @@ struct FnoScratch {
     double* base = nullptr;
     FnoScratch(Context& c, int64_t ndoubles, const char* who, const char* what = "the amplitude operands of this system") : cx(c)
     {
-        size_t free_b = 0, total_b = 0;
-        AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (8.0 * (double)ndoubles > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+        if (!cx.fits(8.0 * (double)ndoubles))
             throw Error(1, std::string(who) + ": " + what + " do not fit the free device memory");
         base = cx.alloc_raw(ndoubles);
     }
@@ -1031,9 +1028,7 @@ FcidumpRead fcidump_read_body(Context& cx, ReadScratch& rs, FILE* f, const char*
 }
 void fcidump_fit(Context& cx, const char* who, double ndoubles)
 {
-    size_t free_b = 0, total_b = 0;
-    AFESP_HIP(hipMemGetInfo(&free_b, &total_b));
-    if (8.0 * ndoubles > 0.9 * ((double)free_b + (double)cx.arena.idle_bytes))
+    if (!cx.fits(8.0 * ndoubles))
         throw Error(1, std::string(who) + ": the integrals of this file do not fit the free device memory");
 }
 double offdiag_max(const double* F, int64_t n)
@@ -1079,7 +1074,7 @@ namespace {
 // What afesp_read_fcidump and afesp_read_fcidump_rohf share once the header has passed their own checks: the body of a restricted file
 // into a new packed array and h, the Fock operator(s) of the determinant that fills the first na (alpha) / nb (beta) orbitals -- ro:
 // the two spin operators (k_fock_ro), else the closed-shell one (na == nb) -- and, only when all of that was good, residency.
-void read_restricted(Context& cx, Integrals& in, CCState& cc, FILE* f, const char* who, const fcidump::Header& h, int64_t n, int64_t na,
+void read_restricted(Context& cx, Integrals& in, Solver& sv, FILE* f, const char* who, const fcidump::Header& h, int64_t n, int64_t na,
                      int64_t nb, bool ro, FcidumpResult& r)
 {
     const int64_t ne = neri_of(n), np = npair_of(n), n2 = up16(n * n), nf = ro ? 2 : 1;
@@ -1110,7 +1105,7 @@ void read_restricted(Context& cx, Integrals& in, CCState& cc, FILE* f, const cha
     // from here on nothing fails: the new array takes the place of the resident one, as a transform's result would
     cx.drop_scratch("t_");
     in.release_uhf(cx);
-    in.drop_mo(cx, cc);
+    in.drop_mo(cx, sv);
     rs.keep(packed);
     in.set_mo(packed, n);
     if (r.h[0]) memcpy(r.h[0], hh.data(), sizeof(double) * n * n);
@@ -1142,7 +1137,7 @@ void read_restricted(Context& cx, Integrals& in, CCState& cc, FILE* f, const cha
 }
 }  // namespace
 
-void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t nocc, FcidumpResult& r)
+void read_fcidump(Context& cx, Integrals& in, Solver& sv, const char* path, int64_t n, int64_t nocc, FcidumpResult& r)
 {
     const char* who = "afesp_read_fcidump";
     File file(fopen(path, "rb"));
@@ -1153,11 +1148,11 @@ void read_fcidump(Context& cx, Integrals& in, CCState& cc, const char* path, int
     if (h.norb != n || h.nelec != 2 * nocc || h.ms2 != 0)
         throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
                            std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nocc " + std::to_string(nocc));
-    read_restricted(cx, in, cc, file.f, who, h, n, nocc, nocc, false, r);
+    read_restricted(cx, in, sv, file.f, who, h, n, nocc, nocc, false, r);
 }
 
 // The restricted open-shell file (no UHF flag, MS2 = nalpha - nbeta >= 0): one set of orbitals and integrals, two spin Fock operators
-void read_fcidump_rohf(Context& cx, Integrals& in, CCState& cc, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)
+void read_fcidump_rohf(Context& cx, Integrals& in, Solver& sv, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)
 {
     const char* who = "afesp_read_fcidump_rohf";
     File file(fopen(path, "rb"));
@@ -1170,7 +1165,7 @@ void read_fcidump_rohf(Context& cx, Integrals& in, CCState& cc, const char* path
         throw Error(1, std::string(who) + ": the header (NORB " + std::to_string(h.norb) + ", NELEC " + std::to_string(h.nelec) + ", MS2 " +
                            std::to_string(h.ms2) + ") disagrees with nbasis " + std::to_string(n) + ", nalpha " + std::to_string(na) + ", nbeta " +
                            std::to_string(nb));
-    read_restricted(cx, in, cc, file.f, who, h, n, na, nb, true, r);
+    read_restricted(cx, in, sv, file.f, who, h, n, na, nb, true, r);
 }
 
 void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r)

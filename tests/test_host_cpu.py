@@ -224,3 +224,12 @@ def test_every_environment_variable_is_defined_in_one_place_and_listed_in_the_he
     block = header[header.index("Environment variables."):header.index("#ifndef AFESP_H")]
     listed = set(re.findall(r"AFESP_[A-Z0-9_]+", block)) - {"AFESP_H"}
     assert parsed == listed, (sorted(parsed - listed), sorted(listed - parsed))
+
+
+def test_the_c_boundary_holds_none_of_the_solver_protocol():
+    """csrc/capi.hip checks arguments and makes one call each: who owns a state's packed integrals, the DIIS / residual flags of an
+    iteration's form, the amplitude epoch stamps, the launch-fused fallback and graph capture all live behind csrc/solver.h."""
+    src = open(os.path.join(ROOT, "a-fortran-electronic-structure-program_amd", "csrc", "capi.hip")).read()
+    found = [w for w in ("eri_own", "eri_src", "tail_pending", "hist_plain", "partials_live", "amp_epoch", "fused_exec", "hipGraph")
+             if w in src]
+    assert found == [], found
