@@ -28,6 +28,8 @@ EXPORTS = [
     "afesp_contract", "afesp_synthetic_init", "afesp_time_pp_ladder", "afesp_bench_contract", "afesp_set_tuning", "afesp_bench_stream", "afesp_profile", "afesp_ccsd_cr_intermediates", "afesp_ccsd_t_cr",
     "afesp_ccsd_so_init", "afesp_ccsd_so_energy", "afesp_ccsd_so_iterate", "afesp_ccsd_so_diis", "afesp_ccsd_so_get_amplitudes",
     "afesp_ccsd_so_set_amplitudes", "afesp_ccsd_so_get_tensor", "afesp_ccsd_so_t_ntriples", "afesp_ccsd_so_t",
+    "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
+    "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
@@ -106,6 +108,13 @@ def load_library():
     L.afesp_ccsd_so_t_ntriples.argtypes = [i64]
     L.afesp_ccsd_so_t_ntriples.restype = i64
     L.afesp_ccsd_so_t.argtypes = [C.c_void_p, i64, i64, C.POINTER(dbl)]
+    L.afesp_ccsd_so_lambda_init.argtypes = [C.c_void_p, C.c_int]
+    L.afesp_ccsd_so_lambda_iterate.argtypes = [C.c_void_p, dbl, dbl, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_lambda_energy.argtypes = [C.c_void_p, dbl, dbl, C.POINTER(dbl), C.POINTER(dbl), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_lambda_diis.argtypes = [C.c_void_p]
+    L.afesp_ccsd_so_get_lambda.argtypes = [C.c_void_p, _dp, _dp]
+    L.afesp_ccsd_so_set_lambda.argtypes = [C.c_void_p, _dp, _dp]
+    L.afesp_ccsd_so_density.argtypes = [C.c_void_p, _dp, i64]
     L.afesp_read_eri_text.argtypes = [C.c_void_p, C.c_char_p, i64, _opt, C.POINTER(i64)]
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
     L.afesp_set_eri.argtypes = [C.c_void_p, i64, _dp]
@@ -738,6 +747,39 @@ class Engine:
         e = dbl()
         self._chk(self.L.afesp_ccsd_so_t(self.h, t_begin, t_end, C.byref(e)))
         return e.value
+
+    # ---- Lambda and the unrelaxed one-particle density of the spin-orbital state (include/afesp.h; afesp_amd.density drives them)
+    def so_lambda_init(self, diis_nerr=8):
+        """The t-dependent intermediates from the state's current t1 / t2 and l = t.  Whatever changes t1 / t2 afterwards makes the Lambda
+        state stale (status 21)."""
+        self._chk(self.L.afesp_ccsd_so_lambda_init(self.h, diis_nerr))
+
+    def so_lambda_iterate(self, e_tol=1e-6, l_tol=1e-7):
+        """One Jacobi step -> (pseudo energy, sum (l2 - l2_old)^2, converged)"""
+        return self._so_step(self.L.afesp_ccsd_so_lambda_iterate, e_tol, l_tol)
+
+    def so_lambda_energy(self, e_tol=1e-6, l_tol=1e-7):
+        return self._so_step(self.L.afesp_ccsd_so_lambda_energy, e_tol, l_tol)
+
+    def so_lambda_diis(self):
+        self._chk(self.L.afesp_ccsd_so_lambda_diis(self.h))
+
+    def so_lambda(self):
+        o, v = self.so_o, self.so_v
+        l1 = np.zeros(o * v)
+        l2 = np.zeros(o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_get_lambda(self.h, l1, l2))
+        return l1.reshape((o, v), order="F"), l2.reshape((o, o, v, v), order="F")
+
+    def so_set_lambda(self, l1, l2):
+        self._chk(self.L.afesp_ccsd_so_set_lambda(self.h, _f(l1), _f(l2)))
+
+    def so_density(self, capacity=None):
+        """The symmetrised correlation part of the unrelaxed one-particle density, (o+v) x (o+v) in the state's spin-orbital order"""
+        n = self.so_o + self.so_v
+        buf = np.zeros(n * n)
+        self._chk(self.L.afesp_ccsd_so_density(self.h, buf, buf.size if capacity is None else capacity))
+        return buf.reshape((n, n), order="F")
 
     def do_ccsd_t_spatial_plain(self, t_begin=0, t_end=None):
         """E[T], E(T) only: what plain CCSD(T)_spatial / CCSD[T]_spatial need (no y, no D sums)."""

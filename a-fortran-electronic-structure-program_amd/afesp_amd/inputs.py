@@ -43,6 +43,7 @@ class SystemIn:
     # frozen natural orbitals: the virtual space truncated in the basis of the MP2 natural virtuals (afesp_amd/fno.py); at most one of the two
     fno_n_virt: int = -1            # number of natural virtuals kept; -1 = off
     fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
+    cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -73,6 +74,7 @@ _CALC_TYPES = {
     "UCCSD(T)": ("UCCSD(T)", False, False, False, False),
 }
 OPEN_SHELL_TYPES = ("UHF_scf", "UMP2", "UCCSD", "UCCSD(T)")
+CC_DENSITY_TYPES = ("CCSD_spinorb", "CCSD(T)_spinorb", "UCCSD", "UCCSD(T)")   # (the host adds its ROHF-CCSD types)
 
 
 def _parse_value(text: str):
@@ -143,6 +145,13 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("frozen natural orbitals and n_frozen_virt exclude each other!")
     if sysin.fno_n_virt == 0:
         raise ValueError("fno_n_virt leaves no active virtual orbital!")
+    if not isinstance(sysin.cc_density, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.cc_density and sysin.calc_type not in CC_DENSITY_TYPES:
+        raise ValueError(f"{sysin.calc_type} takes no cc_density: the Lambda equations run on the spin-orbital CCSD types!")
+    if sysin.cc_density and sysin.fcidump_in and sysin.calc_type in OPEN_SHELL_TYPES:
+        raise ValueError("cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the "
+                         "spin-summed density needs!")
     return sysin
 
 

@@ -118,7 +118,7 @@ void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
 
 extern "C" {
 
-int afesp_version(void) { return 1; }
+int afesp_version(void) { return 2; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -591,6 +591,47 @@ int afesp_ccsd_so_set_amplitudes(afesp_ctx* ctx, const double* t1, const double*
 int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int64_t capacity)
 {
     return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_get_tensor: no spin-orbital CCSD state").so_fetch_tensor(cx, name, out, capacity); });
+}
+
+// ---- Lambda and the one-particle density (lambda_so.h)
+int afesp_ccsd_so_lambda_init(afesp_ctx* ctx, int diis_n_errmat)
+{
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_lambda_init: no spin-orbital CCSD state").so_lambda_begin(cx, diis_n_errmat); });
+}
+
+int afesp_ccsd_so_lambda_iterate(afesp_ctx* ctx, double e_tol, double l_tol, double* pseudo_energy, double* rms_sq, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        report(ctx->sv.need_so("afesp_ccsd_so_lambda_iterate: no spin-orbital CCSD state").so_lambda_step(cx, e_tol, l_tol), pseudo_energy, rms_sq, converged);
+    });
+}
+
+int afesp_ccsd_so_lambda_energy(afesp_ctx* ctx, double e_tol, double l_tol, double* pseudo_energy, double* rms_sq, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        report(ctx->sv.need_so("afesp_ccsd_so_lambda_energy: no spin-orbital CCSD state").so_lambda_energy_step(cx, e_tol, l_tol), pseudo_energy, rms_sq,
+               converged);
+    });
+}
+
+int afesp_ccsd_so_lambda_diis(afesp_ctx* ctx)
+{
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_lambda_diis: no spin-orbital CCSD state").so_lambda_diis(cx); });
+}
+
+int afesp_ccsd_so_get_lambda(afesp_ctx* ctx, double* l1, double* l2)
+{
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_get_lambda: no spin-orbital CCSD state").so_get_lambda(cx, l1, l2); });
+}
+
+int afesp_ccsd_so_set_lambda(afesp_ctx* ctx, const double* l1, const double* l2)
+{
+    return entry(ctx, [&](Context& cx) { ctx->sv.need_so("afesp_ccsd_so_set_lambda: no spin-orbital CCSD state").so_set_lambda(cx, l1, l2); });
+}
+
+int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity)
+{
+    return entry(ctx, [&](Context& cx) { so_density(cx, ctx->sv.need_so("afesp_ccsd_so_density: no spin-orbital CCSD state").so, d, capacity); });
 }
 
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)nocc); }

@@ -549,6 +549,7 @@ void so_free(Context& cx, SOState& s)
     for (double* b : bufs) cx.release(b);
     cx.drop_scratch();
     so_triples_plan_free(s);
+    so_lambda_free(cx, s);
     s = SOState();
 }
 
@@ -616,14 +617,16 @@ void so_build_W_vvvv(Context& cx, SOState& s)
 //   bare part   sum_{e<f} tau(ijef) <ab||ef> for i < j, a < b only -- tau and the integrals are antisymmetric in each pair -- one
 //               product over pair indices, an eighth of the o^2 v^4 multiply-adds, against va(ef, ab) built once (so_init);
 //   t1 parts    1/2 sum_m [ t(m,b) Z(ijma) - t(m,a) Z(ijmb) ],  Z(ijma) = sum_ef tau(ijef) <ma||ef>  (o^3 v^3 and two K = o products).
-static void so_ladder(Context& cx, SOState& s)
+// the bare part: out(ijab) = sum_{e<f} x(ijef) <ab||ef> for any x antisymmetric in each pair (tau here; lambda_2 in lambda_so.hip, whose
+// 1/2 l_ijef <ef||ab> it is)
+void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out)
 {
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, npv = V * (V - 1) / 2, npo = O * (O - 1) / 2, ka = s.lad_ka, na = s.lad_na;
     if (npv == 0 || npo == 0) {
-        k_fill(cx, s.r2.d, s.r2.size(), 0.0);
+        k_fill(cx, out.d, out.size(), 0.0);
     } else {
-        SO_KERNEL((Ranges{FR(s.tau.d, s.tau.size())}), (Ranges{FR(s.ta, na * ka)}), so_tau_asympack_kernel, npo * npv, s.ta, s.tau.d, o, v, na);
+        SO_KERNEL((Ranges{FR(x.d, x.size())}), (Ranges{FR(s.ta, na * ka)}), so_tau_asympack_kernel, npo * npv, s.ta, x.d, o, v, na);
         const int64_t* t = s.lad_tab;
         const int64_t kn = std::max(ka, na);
         GettProblem gp;
@@ -637,8 +640,14 @@ static void so_ladder(Context& cx, SOState& s)
         gp.M = (int)npv; gp.N = (int)na; gp.K = (int)ka;
         if (cx.rec) cx.rec->product(gp, ka * npv, na * ka, na * npv);
         else AFESP_HIP(gett_launch(gp, cx.ws, cx.stream));
-        SO_KERNEL((Ranges{FR(s.pa, na * npv)}), (Ranges{FR(s.r2.d, s.r2.size())}), so_ladder_expand_kernel, s.r2.size(), s.r2.d, s.pa, o, v, na);
+        SO_KERNEL((Ranges{FR(s.pa, na * npv)}), (Ranges{FR(out.d, out.size())}), so_ladder_expand_kernel, out.size(), out.d, s.pa, o, v, na);
     }
+}
+
+static void so_ladder(Context& cx, SOState& s)
+{
+    const int64_t O = s.o, V = s.v;
+    so_ladder_bare(cx, s, s.tau, s.r2);
     Tensor Z = view(cx.scratch("so_Z", O * O * O * V), {O, O, O, V});
     contract(cx, 1.0, s.tau, "ijef", s.ovvv, "maef", 0.0, Z, "ijma");
     contract(cx, 0.5, Z, "ijma", s.t1, "mb", 1.0, s.r2, "ijab");

@@ -1,0 +1,45 @@
+// lambda_so.h -- the left-hand (Lambda) solution of spin-orbital CCSD and the unrelaxed one-particle density built from it
+// (Gauss and Stanton, J. Chem. Phys. 103, 3561 (1995)).  With R1, R2 the residuals so_amplitudes evaluates before its
+// division and L(t, l) = E(t) + sum l1 R1 + 1/4 sum l2 R2, the Lambda residual is G = dL/dt = X - D l; one iteration is the Jacobi step
+// l <- l + G / D = X / D.  Everything in X that depends on t alone is built once (so_lambda_init) for one amp_epoch of the state.
+#pragma once
+#include "ccsd_so.h"
+
+namespace afesp {
+
+// statuses of the Lambda entry points beside 1 (argument error: no spin-orbital state) and 2 (HIP error)
+constexpr int LAMBDA_ERR_FOO = 20;        // the state keeps the reference's transposed F_mi term: no consistent Lagrangian
+constexpr int LAMBDA_ERR_STALE = 21;      // no Lambda state, or t1 / t2 may have changed since so_lambda_init
+constexpr int LAMBDA_ERR_CAPACITY = 22;   // so_density: the caller's buffer is too small
+
+struct SOLambda : DiisRing {   // amp = [l1 ; l2]
+    int64_t epoch = -1;        // SOState::amp_epoch the intermediates were built for
+    Tensor l1, l2, x1, x2, l2_old;
+    Tensor tau;                // of the t1 / t2 of `epoch` (the state's own tau is that of its last so_intermediates)
+    // lambda-independent H-bar elements; Hoo / Hvv without the diagonal of f (the denominators)
+    Tensor Hov, Hoo, Hvv;      // (m,e) (m,i) (a,e)
+    Tensor Hoooo;              // (m,n,i,j)
+    Tensor Hvovv, Hooov;       // (a,m,e,f) (m,n,i,e)
+    Tensor Hovvo;              // (m,b,e,j)
+    Tensor Hvvvo;              // H_abei stored (i,e,a,b)
+    Tensor Hovoo;              // (m,b,i,j)
+    Tensor Gvv, Goo;           // G_ae = -1/2 t_mnef l_mnaf, G_mi = 1/2 t_mnef l_inef, of the current l2
+    double pseudo = 0.0, pseudo_old = 0.0, rms = 0.0;
+};
+
+// device bytes of the Lambda state and its working set (beside so_state_bytes)
+double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr);
+// Builds the intermediates from the state's current t1 / t2 (converged or not) and sets l = t.  Throws LAMBDA_ERR_FOO on a state whose
+// F_mi term is the reference's transposed one.
+void so_lambda_init(Context& cx, SOState& s, int diis_nerr);
+// the live Lambda state of `s`, or LAMBDA_ERR_STALE in the caller's name
+SOLambda& so_lambda_need(SOState& s, const char* who);
+void so_lambda_iterate(Context& cx, SOState& s);   // diis_save + one Jacobi update; the monitor sums are left for so_lambda_read
+// pseudo energy 1/4 sum <ij||ab> l2 + sum f_ia l1 and sum (l2 - l2_old)^2; l2_old <- l2
+void so_lambda_energy(Context& cx, SOState& s);
+int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol);   // the host read of either and the convergence rule
+// the symmetrised correlation part of the unrelaxed one-particle density, (o+v)^2 column-major in the state's spin-orbital order
+void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity);
+void preload_lambda_so();
+
+}  // namespace afesp

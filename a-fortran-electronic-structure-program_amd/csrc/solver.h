@@ -4,6 +4,7 @@
 // integrals a state keeps for ccsd_need_vvvv, and the epoch stamp of everything that may change the amplitudes (solver.hip).
 #pragma once
 #include "ccsd_so.h"
+#include "lambda_so.h"
 #include "fused.h"
 
 namespace afesp {
@@ -76,8 +77,21 @@ struct Solver {
     void so_get_amplitudes(Context& cx, double* t1, double* t2);
     void so_set_amplitudes(Context& cx, const double* t1, const double* t2);
     void so_fetch_tensor(Context& cx, const char* name, double* out, int64_t capacity);
+    // ---- Lambda and the one-particle density of the spin-orbital state (lambda_so.h).  None of these writes t1 / t2 or stamps amp_epoch: the
+    // Lambda state belongs to the epoch it was built for, and whatever stamps a new one makes it stale
+    void so_lambda_begin(Context& cx, int diis_nerr) { so_lambda_init(cx, so, diis_nerr); }
+    StepResult so_lambda_step(Context& cx, double e_tol, double l_tol) { so_lambda_iterate(cx, so); return so_lambda_result(cx, e_tol, l_tol); }
+    StepResult so_lambda_energy_step(Context& cx, double e_tol, double l_tol) { so_lambda_energy(cx, so); return so_lambda_result(cx, e_tol, l_tol); }
+    void so_lambda_diis(Context& cx) { diis_update(cx, so_lambda_need(so, "afesp_ccsd_so_lambda_diis")); }
+    void so_get_lambda(Context& cx, double* l1, double* l2);
+    void so_set_lambda(Context& cx, const double* l1, const double* l2);
 
 private:
+    StepResult so_lambda_result(Context& cx, double e_tol, double l_tol)
+    {
+        const int conv = so_lambda_read(cx, so, e_tol, l_tol);
+        return {so.lam->pseudo, so.lam->rms, conv};
+    }
     bool iteration_body(Context& cx);                              // true: read with ccsd_tail_read
     StepResult step(Context& cx, double e_tol, double t_tol);      // one iteration and the read that matches its form
     void uso_begin(Context& cx, const Integrals& in, const char* who, const char* hint, int64_t nbasis, int64_t nalpha, int64_t nbeta,

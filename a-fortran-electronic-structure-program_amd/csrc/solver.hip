@@ -29,6 +29,7 @@ void Solver::destroy(Context& cx)
     so_programs_reset(cx);
     triples_plan_free(cc);
     so_triples_plan_free(so);
+    so_lambda_free(cx, so);   // (the host-side object of a Lambda state)
     ring_free(cx, cc);   // (the host-side descriptor of the ring launches; its device blocks go with the context)
 }
 
@@ -402,6 +403,22 @@ void Solver::so_set_amplitudes(Context& cx, const double* t1, const double* t2)
 {
     so.amp_epoch = ++cx.amp_clock;
     amps_from_host(cx, so, t1, t2);
+}
+
+void Solver::so_get_lambda(Context& cx, double* l1, double* l2)
+{
+    SOLambda& L = so_lambda_need(so, "afesp_ccsd_so_get_lambda");
+    if (l1) AFESP_HIP(hipMemcpyAsync(l1, L.l1.d, sizeof(double) * L.l1.size(), hipMemcpyDeviceToHost, cx.stream));
+    if (l2) AFESP_HIP(hipMemcpyAsync(l2, L.l2.d, sizeof(double) * L.l2.size(), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+void Solver::so_set_lambda(Context& cx, const double* l1, const double* l2)
+{
+    SOLambda& L = so_lambda_need(so, "afesp_ccsd_so_set_lambda");
+    if (l1) AFESP_HIP(hipMemcpyAsync(L.l1.d, l1, sizeof(double) * L.l1.size(), hipMemcpyHostToDevice, cx.stream));
+    if (l2) AFESP_HIP(hipMemcpyAsync(L.l2.d, l2, sizeof(double) * L.l2.size(), hipMemcpyHostToDevice, cx.stream));
+    cx.sync();
 }
 
 void Solver::so_fetch_tensor(Context& cx, const char* name, double* out, int64_t capacity)

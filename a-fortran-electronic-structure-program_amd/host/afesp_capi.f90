@@ -15,6 +15,8 @@ module afesp_capi
              afesp_core_operator, afesp_ucore_operator, afesp_write_fcidump_active, afesp_write_fcidump_uactive, &
              afesp_fcidump_scan, afesp_read_fcidump, afesp_read_fcidump_uhf, &
              afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
+             afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
+             afesp_ccsd_so_density, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -385,6 +387,44 @@ module afesp_capi
       function afesp_ccsd_so_diis(ctx) bind(C, name='afesp_ccsd_so_diis') result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: ctx
+         integer(c_int) :: rc
+      end function
+      !> Lambda of the spin-orbital state and its unrelaxed one-particle density (include/afesp.h): init from the current t1 / t2, then
+      !> Jacobi steps with DIIS on the Lambda ring; d is (o+v) x (o+v) in the state's spin-orbital order
+      function afesp_ccsd_so_lambda_init(ctx, diis_n_errmat) bind(C, name='afesp_ccsd_so_lambda_init') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: diis_n_errmat
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_lambda_energy(ctx, e_tol, l_tol, pseudo_energy, rms_sq, converged) &
+         bind(C, name='afesp_ccsd_so_lambda_energy') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: e_tol, l_tol
+         real(c_double), intent(out) :: pseudo_energy, rms_sq
+         integer(c_int), intent(out) :: converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_lambda_iterate(ctx, e_tol, l_tol, pseudo_energy, rms_sq, converged) &
+         bind(C, name='afesp_ccsd_so_lambda_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: e_tol, l_tol
+         real(c_double), intent(out) :: pseudo_energy, rms_sq
+         integer(c_int), intent(out) :: converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_lambda_diis(ctx) bind(C, name='afesp_ccsd_so_lambda_diis') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_density(ctx, d, capacity) bind(C, name='afesp_ccsd_so_density') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), intent(out) :: d(*)
+         integer(c_int64_t), value :: capacity
          integer(c_int) :: rc
       end function
       function afesp_ccsd_so_t_ntriples(nocc) bind(C, name='afesp_ccsd_so_t_ntriples') result(n)

@@ -51,6 +51,8 @@ module host_config
       ! frozen natural orbitals: the virtual space truncated in the basis of the MP2 natural virtuals; at most one of the two keys
       integer :: fno_n_virt = -1         ! number of natural virtuals kept (-1: off)
       real(dp) :: fno_occ_tol = 0.0_dp   ! keep every natural virtual whose occupation is at least this (0: off)
+      ! after a converged spin-orbital CCSD: the Lambda equations and the natural occupation numbers of the unrelaxed one-particle density
+      logical :: cc_density = .false.
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -61,10 +63,11 @@ contains
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt
       real(dp) :: fno_occ_tol
-      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in
+      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
-         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in
+         frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
+         cc_density
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -73,7 +76,7 @@ contains
       charge = d%charge; multiplicity = d%multiplicity
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
-      fcidump_in = d%fcidump_in
+      fcidump_in = d%fcidump_in; cc_density = d%cc_density
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -127,6 +130,11 @@ contains
       end select
       if (multiplicity < 1) call fail('system::read_system_in', 'invalid input file format!')
       cfg%fcidump_in = fcidump_in
+      cfg%cc_density = cc_density
+      if (cc_density .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no cc_density: the Lambda equations run on the spin-orbital CCSD types!')
+      if (cc_density .and. fcidump_in .and. cfg%uhf .and. .not. cfg%rohf) call fail('system::read_system_in', &
+         'cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the spin-summed density needs!')
       if (cfg%rohf) then   ! no ROHF SCF here: the orbitals come from a file, and a frozen core reaches this path as an active-space file
          if (.not. fcidump_in) call fail('system::read_system_in', trim(calc_type)// &
             ' needs fcidump_in = .true.: there is no ROHF SCF, the restricted open-shell orbitals come from a FCIDUMP!')
@@ -682,6 +690,8 @@ program els_amd
    real(dp) :: e_core
    ! ROHF types: the spin Fock matrices of the file's determinant in semicanonical orbitals
    real(dp), allocatable :: fock_sa(:, :), fock_sb(:, :)
+   ! cc_density: <beta orbital b | alpha orbital a> over the whole basis where the two sets differ (UHF: C_b S C_a^T; ROHF: u_b u_a^T)
+   real(dp), allocatable :: ab_overlap(:, :)
    character(len=16) :: mp2name, ccname
    real(dp) :: e_hf, e_mp2, e_ccsd, energy, eold, rms, tq(6), t0, t1s, tstart, t1diag, e_highest
    real(dp) :: e_bt, e_pt, e_rbt, e_rpt, e_crbt, e_crpt
@@ -897,6 +907,10 @@ program els_amd
             e_ccsd = energy; e_highest = e_ccsd
          end if
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//trim(ccname)//':', seconds() - t0, 's'
+         if (cfg%cc_density .and. cc_ok) then
+            if (.not. cfg%rohf) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
+            call lambda_and_occupations(n_act, na_act, nb_act, .false.)
+         end if
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
@@ -996,6 +1010,7 @@ program els_amd
             e_ccsd = energy; e_highest = e_ccsd
          end if
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD:', seconds() - t0, 's'
+         if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             ! ---------------- spin-orbital (T) (reference do_ccsd_t_spinorb, src/ccsd.f90:1812-1922)
             t0 = seconds()
@@ -1242,6 +1257,96 @@ contains
          k = count(occ >= cfg%fno_occ_tol)
       end if
    end function
+   !> cc_density: Lambda of the converged spin-orbital CCSD state (Jacobi steps with DIIS, the CCSD table's format), then the spin-summed
+   !> natural occupation numbers of the unrelaxed one-particle density over the whole basis (frozen core orbitals doubly occupied, dropped
+   !> virtuals empty).  The state's spin-orbital order over its n active orbitals is interleaved (2 P + spin: the RHF-fed state) or blocked
+   !> (occupied alpha, occupied beta, virtual alpha, virtual beta).
+   subroutine lambda_and_occupations(n, nalpha, nbeta, interleaved)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      real(dp), allocatable :: d(:, :), ds(:, :), dsb(:, :), occ(:), u(:, :)
+      integer, allocatable :: orb(:), spin(:)
+      real(dp) :: pe, pe_old, lrms, tl
+      integer(c_int) :: lconv
+      integer :: it, x, y, o, nf
+      logical :: ok
+      tl = seconds()
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD Lambda'; write (out, '(1X, 10("-"))')
+      rc = afesp_ccsd_so_lambda_init(ctx, int(cfg%ccsd_diis_n_errmat, c_int))
+      if (rc /= 0) call fail('ccsd::init_lambda', afesp_error_text(ctx))
+      rc = afesp_ccsd_so_lambda_energy(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, pe, lrms, lconv)
+      if (rc /= 0) call fail('ccsd::update_lambda_energy', afesp_error_text(ctx))
+      write (out, '(75("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Iteration', ' Pseudo energy ', '    deltaE     ', '  delta RMS L2 ', '  Time  '
+      write (out, '(75("-"))')
+      write (out, '(1X, A9, 3X, F15.12, 3X, F15.12, 3X, F15.12)') 'L = T', pe, pe, lrms
+      ok = .false.
+      t1s = seconds()
+      do it = 1, cfg%ccsd_maxiter
+         pe_old = pe
+         rc = afesp_ccsd_so_lambda_iterate(ctx, cfg%ccsd_e_tol, cfg%ccsd_t_tol, pe, lrms, lconv)
+         if (rc /= 0) call fail('ccsd::update_lambda', afesp_error_text(ctx))
+         write (out, '(1X, I9, 3X, F15.12, 3X, F15.12, 3X, F15.12, 3X, F8.6)') it, pe, pe - pe_old, lrms, seconds() - t1s
+         t1s = seconds()
+         if (lconv /= 0) then
+            ok = .true.
+            exit
+         end if
+         rc = afesp_ccsd_so_lambda_diis(ctx)
+         if (rc /= 0) call fail('ccsd::update_diis_cc', 'Linear solve failed!')
+      end do
+      write (out, '(75("-"))')
+      if (.not. ok) call fail('ccsd::do_lambda', 'the Lambda equations did not converge!')
+      write (out, '(1X, A)') 'Convergence reached within tolerance.'
+      nf = mol%nbasis
+      allocate (d(2*n, 2*n), ds(nf, nf), dsb(nf, nf), orb(2*n), spin(2*n))
+      rc = afesp_ccsd_so_density(ctx, d, int(size(d), c_int64_t))
+      if (rc /= 0) call fail('ccsd::density', afesp_error_text(ctx))
+      o = nalpha + nbeta
+      do x = 1, 2*n   ! orbital (within the whole basis: the window starts behind nfc) and spin of every spin orbital of the state
+         if (interleaved) then
+            orb(x) = (x + 1)/2; spin(x) = mod(x + 1, 2)
+         else if (x <= nalpha) then
+            orb(x) = x; spin(x) = 0
+         else if (x <= o) then
+            orb(x) = x - nalpha; spin(x) = 1
+         else if (x <= o + n - nalpha) then
+            orb(x) = nalpha + (x - o); spin(x) = 0
+         else
+            orb(x) = nbeta + (x - o - (n - nalpha)); spin(x) = 1
+         end if
+         orb(x) = orb(x) + nfc
+      end do
+      ! each spin's density in its own orbitals: the frozen core and the reference determinant on the diagonal, then the correlation part
+      ! (which has no element between the spins); the beta one is brought into the alpha orbitals before the two are added
+      ds = 0.0_dp; dsb = 0.0_dp
+      do x = 1, nfc
+         ds(x, x) = 1.0_dp; dsb(x, x) = 1.0_dp
+      end do
+      do y = 1, 2*n
+         do x = 1, 2*n
+            if (spin(x) /= spin(y)) cycle
+            if (spin(x) == 0) then
+               ds(orb(x), orb(y)) = ds(orb(x), orb(y)) + d(x, y)
+            else
+               dsb(orb(x), orb(y)) = dsb(orb(x), orb(y)) + d(x, y)
+            end if
+         end do
+         if (y <= o .and. spin(y) == 0) ds(orb(y), orb(y)) = ds(orb(y), orb(y)) + 1.0_dp
+         if (y <= o .and. spin(y) == 1) dsb(orb(y), orb(y)) = dsb(orb(y), orb(y)) + 1.0_dp
+      end do
+      if (allocated(ab_overlap)) then
+         ds = ds + matmul(transpose(ab_overlap), matmul(dsb, ab_overlap))
+      else
+         ds = ds + dsb
+      end if
+      ds = 0.5_dp*(ds + transpose(ds))
+      call fno_occupations(ds, occ, u)
+      write (out, '(1X, A)') 'Natural occupation numbers (unrelaxed CCSD one-particle density, spin-summed):'
+      write (out, '(5(1X, F14.10))') occ
+      write (out, '(1X, A, 1X, F14.10)') 'Sum of natural occupation numbers:', sum(occ)
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for CCSD Lambda and density:', seconds() - tl, 's'
+   end subroutine
    subroutine print_fno_cut(asked, kept_occ, dropped_occ, any_dropped)
       integer, intent(in) :: asked
       real(dp), intent(in) :: kept_occ, dropped_occ
@@ -1432,6 +1537,7 @@ contains
       write (out, '(1X, A, 1X, ES10.3)') 'Largest occupied-virtual Fock element:', offd(3)
       call semicanonical(fa, na, ua, fock_sa)
       call semicanonical(fb, nb, ub, fock_sb)
+      ab_overlap = matmul(ub, transpose(ua))
       write (out, '(1X, A)') 'Rotating the MO integrals into semicanonical orbitals (alpha-alpha, alpha-beta, beta-beta)...'
       rc = afesp_mo_rotate_uhf(ctx, int(n, c_int64_t), ua, ub, c_null_ptr, c_null_ptr, c_null_ptr)
       if (rc /= 0) call fail('integrals::read_fcidump', afesp_error_text(ctx))

@@ -183,6 +183,39 @@ int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int6
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc);
 int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t);
 
+/* The left-hand (Lambda) solution of spin-orbital CCSD and the unrelaxed one-particle density built from it (since
+ * afesp_version 2).  With R1, R2 the CCSD residuals (Stanton et al. Eqs. 1-2 minus D t, f terms included) and
+ *   L(t, l) = E(t) + sum l_ia R1_ia + 1/4 sum l_ijab R2_ijab
+ * the Lambda residual is G = dL/dt and the Lambda equations are G = 0, linear in l.  Any spin-orbital state takes them (afesp_ccsd_so_init
+ * with AFESP_SO_FOO_AS_PUBLISHED, afesp_ccsd_uso_init, afesp_ccsd_uso_init_fock); l1 [o*v] and l2 [o*o*v*v] are laid out as t1 / t2.
+ *   afesp_ccsd_so_lambda_init    = the t-dependent intermediates from the state's CURRENT t1 / t2 (converged or not: the equations are
+ *                                  defined for any t), l = t, and a DIIS ring of diis_n_errmat vectors (0 .. 15; < 2: none).
+ *   afesp_ccsd_so_lambda_iterate = one Jacobi step l <- l + G / D (D: the denominators of the T iteration); *pseudo_energy = 1/4 sum
+ *                                  <ij||ab> l_ijab + sum f_ia l_ia, *rms_sq = sum (l2 - l2_old)^2, *converged = sqrt(rms_sq) < l_tol and
+ *                                  |pseudo_energy - its previous value| < e_tol, as afesp_ccsd_so_iterate reports its numbers.
+ *   afesp_ccsd_so_lambda_energy  = the same three outputs of the l that is there.
+ *   afesp_ccsd_so_lambda_diis    = update_diis_cc on the Lambda ring.
+ *   afesp_ccsd_so_get_lambda / _set_lambda: either pointer may be NULL.
+ *   afesp_ccsd_so_density        = d [(o+v)^2, column-major, the state's spin-orbital order, occupied first] = 1/2 (dL/df_pq + dL/df_qp)
+ *                                  at the current t and l: the correlation part, symmetrised; the full density adds 1 on the occupied
+ *                                  diagonal.  No orbital relaxation.
+ * Call order: converge CCSD -> _lambda_init -> [_lambda_iterate, _lambda_diis] until converged -> _density.  None of them writes t1 / t2, so
+ * afesp_ccsd_so_t before and after gives the same bits.  Every call that may change t1 / t2 (_iterate, _diis, _set_amplitudes, an init)
+ * makes the Lambda state stale; it is then refused, never recomputed on stale intermediates.
+ * Statuses, each with afesp_last_error: 1 no spin-orbital state (or a bad diis_n_errmat); AFESP_LAMBDA_UNPUBLISHED_FOO a state made by
+ * afesp_ccsd_so_init without AFESP_SO_FOO_AS_PUBLISHED (the reference's transposed F_mi term has no consistent Lagrangian);
+ * AFESP_LAMBDA_STALE no Lambda state or a stale one; AFESP_LAMBDA_CAPACITY capacity < (o+v)^2 (nothing is launched). */
+#define AFESP_LAMBDA_UNPUBLISHED_FOO 20
+#define AFESP_LAMBDA_STALE 21
+#define AFESP_LAMBDA_CAPACITY 22
+int afesp_ccsd_so_lambda_init(afesp_ctx* ctx, int diis_n_errmat);
+int afesp_ccsd_so_lambda_iterate(afesp_ctx* ctx, double e_tol, double l_tol, double* pseudo_energy, double* rms_sq, int* converged);
+int afesp_ccsd_so_lambda_energy(afesp_ctx* ctx, double e_tol, double l_tol, double* pseudo_energy, double* rms_sq, int* converged);
+int afesp_ccsd_so_lambda_diis(afesp_ctx* ctx);
+int afesp_ccsd_so_get_lambda(afesp_ctx* ctx, double* l1, double* l2);
+int afesp_ccsd_so_set_lambda(afesp_ctx* ctx, const double* l1, const double* l2);
+int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity);
+
 /* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
  * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
  *   afesp_build_fock_uhf = fock_s = core_hamil + J[dens_a + dens_b] - K[dens_s] for s = a, b on the resident packed AO integrals
