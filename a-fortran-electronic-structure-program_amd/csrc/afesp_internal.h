@@ -237,13 +237,10 @@ void k_ooov_r1_trace(Context& cx, double* r1x, const double* ps, const double* p
 // out[0] = sum (2 v(ijab) - v(ijba)) (t2 + t1 t1), out[1] = sum (t2 - t2_old)^2 ; then t2_old = t2
 void k_cc_energy(Context& cx, double* out2, const double* v_oovv, const double* t1, const double* t2, double* t2_old,
                  int o, int v);
-void k_mp2_energy(Context& cx, double* out1, const double* v_oovv, const double* D2, int o, int v);
-double k_mp2_packed(Context& cx, const double* eri_packed, const double* e_host, int o, int v);   // the same from the packed MO integrals (device), one launch, result on the host; e_host: the n orbital energies
-void k_dots(Context& cx, double* out, const double* x, const double* ybase, int64_t ystride, int ny, int64_t n,
-            bool accumulate);   // out[j] (+)= <x, ybase + j*ystride>
+// out[q] (+)= the ordered sum of block partials q < nq (device_util.h: partials(cx)): the second launch of a deterministic reduction
+void k_final_sum(Context& cx, double* out, int nq, bool accumulate);
 void k_lincomb(Context& cx, double* out, const double* xbase, int64_t xstride, const double* coef_dev, int nx,
                int64_t n);      // out = sum_j coef[j] * x_j
-void k_sub(Context& cx, double* out, const double* a, const double* b, int64_t n);
 // DIIS extrapolation coefficients on the device: bmat (nerr x nerr) gets row/column `slot` from dots[0..n), coef[0..n) out
 void k_diis_solve(Context& cx, double* coef, double* bmat, double* flag, int n, int nerr, int slot);   // sums k_diis_push's partials itself
 void k_diis_push(Context& cx, double* ht, double* he, const double* amp, const double* amp_s, const double* hist_e, int64_t stride, int ny,
@@ -270,75 +267,10 @@ void k_cc_tail(Context& cx, const CCTail& a);
 void k_lincomb_vals(Context& cx, double* out, const double* xbase, int64_t xstride, const double* coef_host, int nx, int64_t n);
 constexpr int DIIS_FLAG_SLOT = 48;   // cx.scal[48]: set by diis_solve_kernel when the solve fails, read with the energies
 void diis_check_flag(Context& cx, const double* host_scal);   // throws the reference's error (ccsd.f90:666) if it is set
-// pair-symmetric AO->MO: u(i,j,KL) from the packed array; out(k,l,PQ) = in(q,p,tri(k,l)); packed[tri(PQ,RS)] = full(s,r,PQ)
-// (ld: leading dimension of the squared-up arrays, 0 = n; the LDS-DMA transforms pad it to whole K steps -- kernels.hip, pair_square_kernel)
-void k_unpack_half(Context& cx, double* u, const double* packed, int n, int64_t c_begin = 0, int64_t c_end = -1, int ld = 0);   // slab of (kl) pairs
-void k_pair_transpose(Context& cx, double* out, const double* in, int n, int ld = 0);
-void k_pad_rows_zero(Context& cx, double* x, int n, int ld, int64_t ncol);   // x(n .. ld - 1, c) = 0 for every column c
-// out(:,:,S) = C in(:,:,S) C^T for npairs symmetric n x n blocks, n <= 64: both quarter transforms of a pair index in one launch
-void k_pair_xform(Context& cx, double* out, const double* in, const double* C, int n, int64_t npairs, int mode = 0);   // modes: kernels.hip
-void k_square_transpose(Context& cx, double* out, const double* in, int64_t n);                                        // out(y, x) = in(x, y)
-void k_pair_square_packed(Context& cx, double* out, const double* g, int n, int64_t c_begin, int64_t c_end);   // out(k,l,P) = g(P, tri(k,l))
-void k_tri_pack(Context& cx, double* g, const double* half, int n, int64_t k_begin, int64_t k_end);           // g(PQ,K) = half(q,p,K)
-void k_pack_pairs(Context& cx, double* packed, const double* full, int n, int64_t p_begin = 0, int64_t p_end = -1, int ld = 0);
-void k_pack_cols(Context& cx, double* cols, const double* full, int n);   // cols[PQ np + RS] = full(s,r,PQ), every RS
-// the active orbital window [lo, lo + n_act): packed over n -> packed over n_act; the [npair x npair] alpha-beta block likewise
-void k_window_pack(Context& cx, double* dst, const double* src, int n_act, int lo);
-void k_window_pairs(Context& cx, double* dst, const double* src, int n_act, int n, int lo);
-// MP1 amplitude operands of the virtual-virtual MP2 density (afesp_mp2_vv_density / afesp_ump2_vv_density), gathered out of the resident
-// MO integrals with the contraction index fastest; o active occupied orbitals from orbital nfc on, v virtuals from orbital nfc + o on,
-// e_dev: the levels of the whole basis.  Each call leaves its share of the MP2 energy in cx.scal[slot].
-//   k_fno_amps:    T(j,i,c; a) = (ia|jc) / D, Tt = 2 T - T with i and j exchanged (closed shell); Tt == nullptr: T = [(ia|jc) - (ic|ja)] / D
-//                  alone, the same-spin amplitudes of one spin
-//   k_fno_amps_ab: the opposite-spin amplitudes (ia|JB) / D out of the npair x npair alpha-beta block, beta_cols = false: T(J,B,i; a)
-//                  (rows for D alpha), true: T(J,i,a; B) (rows for D beta)
-void k_fno_amps(Context& cx, double* T, double* Tt, const double* packed, const double* e_dev, int nfc, int o, int v, int slot);
-void k_fno_amps_ab(Context& cx, double* T, const double* ab, const double* ea_dev, const double* eb_dev, int n, int nfc, int oa, int ob, int va,
-                   int vb, bool beta_cols, int slot);
-// The field of the nfc frozen orbitals on the active window [nfc, nfc + n_act) (afesp_core_operator / afesp_ucore_operator): h_act (n_act x
-// n_act, symmetric to the bit) = window of hmo (n x n) + the core's Coulomb and exchange out of the packed array over n orbitals, and
-// *e_core = the core's own energy.  one_spin: the same-spin weights of an open shell (J - K, half the pair sum) instead of 2 J - K.
-//   k_core_fold_ab: adds the opposite-spin Coulomb terms of the npair x npair alpha-beta block to both h_a and h_b; *e_core = sum_cD (cc|DD)
-void k_core_fold(Context& cx, double* h_act, double* e_core, const double* hmo, const double* packed, int n, int nfc, int n_act, bool one_spin);
-void k_core_fold_ab(Context& cx, double* h_a, double* h_b, double* e_core, const double* ab, int n, int nfc, int n_act);
-// Order-preserving stream compaction: the elements of x[0, total) with |x| > thr as (flat index, value) pairs in rising index order.
-//   k_compact_count:   counts[0 .. k_compact_chunks(total)] = exclusive prefix sums of the per-chunk survivor counts, the last = their number
-//   k_compact_scatter: the pairs, into arrays of that many elements
-int64_t k_compact_chunks(int64_t total);
-void k_compact_count(Context& cx, int64_t* counts, const double* x, int64_t total, double thr);
-void k_compact_scatter(Context& cx, int64_t* out_idx, double* out_val, const int64_t* prefix, const double* x, int64_t total, double thr);
-
-// The FCIDUMP reader (afesp_read_fcidump / _uhf).  k_fcidump_scatter: `count` records (device copy of fcidump_parse.h's
-// Record) into the targets, three launches: duplicates of earlier chunks checked against the visited map, stores, read-back; conflicting
-// duplicates are counted in err[0], the smallest offending line number lands in err[1].  k_fock_mo: F = h + sum_{i < nocc} [wj (pq|ii) -
-// (pi|qi)] over all n orbitals, one wave per pair, symmetric to the bit; k_fock_mo_ab adds the opposite-spin Coulomb terms to both spins.
-namespace fcidump { struct Record; }
-struct FcidumpTargets {
-    double* eri[3];              // closed shell: [0] packed; open shell: aa, bb packed, ab npair x npair (row: alpha pair)
-    double* h[2];                // n x n (open shell: alpha, beta)
-    double* ecore;
-    uint32_t* visited;           // one bit per slot
-    unsigned long long* err;     // [0] conflicting duplicates, [1] smallest line number among them
-    int64_t n, np, ne, nslots;   // spatial orbitals, npair, neri, number of slots (the core energy is the last one)
-    int uhf;
-};
-void k_fcidump_scatter(Context& cx, const FcidumpTargets& T, const fcidump::Record* rec, int64_t count);
-void k_fock_mo(Context& cx, double* F, const double* h, const double* packed, int n, int nocc, double wj);
-void k_fock_mo_ab(Context& cx, double* fa, double* fb, const double* ab, int n, int na, int nb);
 // out(p,q,r,s) = packed[ index( (p+b0)(r+b2) | (q+b1)(s+b3) ) ]  physicist <pq|rs> from packed chemist (pr|qs)
 void k_slice_phys(Context& cx, double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2,
                   int b3);
-// Fock matrix from the half-unpacked integrals u(x,y,P) (k_unpack_half); work holds k_build_fock_work(n) doubles
-void k_build_fock(Context& cx, double* fock, const double* hcore, const double* dens, const double* u, double* work, int n, int ld = 0);
-int64_t k_build_fock_work(int n);
-// the unrestricted pair F_s = H + J[Da + Db] - K[D_s] on the same integrals; work holds k_build_fock_uhf_work(n) doubles
-void k_build_fock_uhf(Context& cx, double* fa, double* fb, const double* hcore, const double* da, const double* db, const double* u,
-                      double* work, int n, int ld = 0);
-int64_t k_build_fock_uhf_work(int n);
-// E(UMP2) from the resident alpha-alpha / beta-beta packed and alpha-beta full blocks (afesp_ao2mo_ump2), one launch, on the host
-double k_ump2(Context& cx, const double* aa, const double* bb, const double* ab, const double* ea_dev, const double* eb_dev, int n, int na,
-              int nb);
-double* host_scalars(Context& cx, int n);
+double* host_scalars(Context& cx, int n);   // copies cx.scal[0..n) to pinned host memory and synchronises
 double* host_scalars_slot(Context& cx, double* seq);          // a kernel of the caller publishes itself (contract.hip); nullptr: use host_scalars
 double* host_scalars_wait(Context& cx, int n, double seq);     // polls for that sequence number, returns the n values on the host
 
@@ -350,9 +282,9 @@ void preload_gett();
 void preload_contract();
 void preload_kernels();
 void preload_small_path_kernels();   // kernels.hip: per-kernel first-use resolution of what a small system launches
+void preload_integrals();     // integrals_kernels.hip: the small AO->MO transform and MP2, the open-shell set-up, the ROHF Fock operators
 void preload_ccsd_so();
-void preload_uhf_kernels();   // kernels.hip: the open-shell Fock build, the mixed-spin transform and UMP2
 void preload_fused();
-void preload_triples();   // copies cx.scal[0..n) to pinned host memory and synchronises
+void preload_triples();
 
 }  // namespace afesp

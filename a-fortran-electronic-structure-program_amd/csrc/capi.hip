@@ -185,7 +185,6 @@ int afesp_ctx_create(int device, afesp_ctx** out)
                 timed("small path", preload_small_path_kernels);
                 timed("triples", preload_triples);
                 timed("ccsd_so", preload_ccsd_so);
-                timed("uhf", preload_uhf_kernels);
                 timed("integrals", preload_integrals);
                 if (knobs().preload_gett) timed("gett", preload_gett);
             });
@@ -375,17 +374,7 @@ int afesp_build_fock(afesp_ctx* ctx, int64_t nbasis, const double* density, cons
     return entry(ctx, [&](Context& cx) {
         if (!ctx->in.ao || ctx->in.ao_n != nbasis || !density || !core_hamil || !fock)
             throw Error(1, "afesp_build_fock: no AO integrals resident for this basis size (afesp_read_eri_text / afesp_set_eri)");
-        const int64_t n2 = nbasis * nbasis;
-        double* buf = cx.scratch("fock_io", 3 * n2);
-        AFESP_HIP(hipMemcpyAsync(buf, density, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(buf + n2, core_hamil, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        int64_t L = 0;
-        const double* u = ctx->in.half_unpacked(cx, nbasis, L);
-        double* work = cx.scratch("fock_work", k_build_fock_work((int)nbasis));
-        ctx->in.half_restamp(cx);
-        k_build_fock(cx, buf + 2 * n2, buf + n2, buf, u, work, (int)nbasis, (int)L);
-        AFESP_HIP(hipMemcpyAsync(fock, buf + 2 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
+        build_fock(cx, ctx->in, nbasis, density, core_hamil, fock);
     });
 }
 
@@ -651,20 +640,7 @@ int afesp_build_fock_uhf(afesp_ctx* ctx, int64_t nbasis, const double* dens_a, c
     return entry(ctx, [&](Context& cx) {
         if (!ctx->in.ao || ctx->in.ao_n != nbasis || !dens_a || !dens_b || !core_hamil || !fock_a || !fock_b)
             throw Error(1, "afesp_build_fock_uhf: no AO integrals resident for this basis size (afesp_read_eri_text / afesp_set_eri)");
-        const int64_t n2 = nbasis * nbasis;
-        double* buf = cx.scratch("fock_uio", 5 * n2);   // [ Da | Db | H | Fa | Fb ]
-        AFESP_HIP(hipMemcpyAsync(buf, dens_a, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(buf + n2, dens_b, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(buf + 2 * n2, core_hamil, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        // the half-unpacked integrals afesp_build_fock keeps (same buffer, same validity)
-        int64_t L = 0;
-        const double* u = ctx->in.half_unpacked(cx, nbasis, L);
-        double* work = cx.scratch("fock_uwork", k_build_fock_uhf_work((int)nbasis));
-        ctx->in.half_restamp(cx);
-        k_build_fock_uhf(cx, buf + 3 * n2, buf + 4 * n2, buf + 2 * n2, buf, buf + n2, u, work, (int)nbasis, (int)L);
-        AFESP_HIP(hipMemcpyAsync(fock_a, buf + 3 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(fock_b, buf + 4 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
+        build_fock_uhf(cx, ctx->in, nbasis, dens_a, dens_b, core_hamil, fock_a, fock_b);
     });
 }
 

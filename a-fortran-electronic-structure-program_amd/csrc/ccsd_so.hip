@@ -2,6 +2,7 @@
 // Every contraction the reference writes as reshape + dgemm or as a loop nest is one label-driven contract() here;
 // the index letters are the reference's.
 #include "ccsd_so.h"
+#include "device_util.h"
 #include "fused.h"
 
 #include <cmath>
@@ -9,11 +10,8 @@
 namespace afesp {
 namespace {
 
-constexpr int TB = 256;
 inline unsigned blocks_for(int64_t n) { return (unsigned)std::min<int64_t>((n + TB - 1) / TB, 65536); }
 #define SO_STRIDE(X_, N_) for (int64_t X_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; X_ < (N_); X_ += (int64_t)gridDim.x * blockDim.x)
-
-__device__ __forceinline__ int64_t tri(int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 
 // ccsd.f90:108-143,193-207: out(p,q,r,s) = <p+b0 q+b1 || r+b2 s+b3> over spin orbitals x = 2 X + spin, from the packed
 // chemist MO integrals: <pq|rs> = (PR|QS) [sp = sr][sq = ss]

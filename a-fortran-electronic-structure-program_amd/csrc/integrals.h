@@ -64,6 +64,10 @@ struct Integrals {
 };
 
 // the bodies of the entry points of the same names (capi.hip checks the arguments); each returns the energy / the count it reports
+// build_fock (src/hf.f90:349-385) and the unrestricted pair on the resident packed AO integrals of basis size n; host matrices n x n
+void build_fock(Context& cx, Integrals& in, int64_t n, const double* density, const double* hcore, double* fock);
+void build_fock_uhf(Context& cx, Integrals& in, int64_t n, const double* dens_a, const double* dens_b, const double* hcore, double* fock_a,
+                    double* fock_b);
 double ao2mo_mp2(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t o, const double* coeff, const double* levels,
                  const double* eri_packed, double* eri_mo_packed);
 double ao2mo_ump2(Context& cx, Integrals& in, int64_t n, int64_t na, int64_t nb, const double* coeff_a, const double* coeff_b,
@@ -109,15 +113,12 @@ void read_fcidump_uhf(Context& cx, Integrals& in, const char* path, int64_t n, i
 // a restricted open-shell file (no UHF flag, MS2 = na - nb >= 0): read_fcidump's parse, scatter and residency; r.fock[0] / [1] the two spin
 // Fock operators of the determinant (k_fock_ro), r.fock_offdiag3 their largest off-diagonal elements by block
 void read_fcidump_rohf(Context& cx, Integrals& in, Solver& sv, const char* path, int64_t n, int64_t na, int64_t nb, FcidumpResult& r);
-// The two spin Fock operators of the restricted determinant that fills the first na / nb orbitals, from h (n x n, device) and the packed
-// MO integrals: one wave per pair, fixed summation order, symmetric to the bit (integrals.hip)
-void k_fock_ro(Context& cx, double* fa, double* fb, const double* h, const double* packed, int n, int na, int nb);
-// ... for host matrices on the resident packed MO array (afesp_mo_fock_ro); returns the electronic reference energy
+// The two spin Fock operators of the restricted determinant that fills the first na / nb orbitals (k_fock_ro) for host matrices on the
+// resident packed MO array (afesp_mo_fock_ro); returns the electronic reference energy
 double mo_fock_ro(Context& cx, const Integrals& in, int64_t n, int64_t na, int64_t nb, const double* h_mo, double* fock_a, double* fock_b);
 // The resident packed MO integrals rotated with one orthogonal matrix per spin (new orbital, old orbital) into the three resident blocks
 // of the open-shell path, through ao2mo_ump2's transform forms; the packed array and the AO integrals stay as they are
 void mo_rotate_uhf(Context& cx, Integrals& in, int64_t n, const double* u_a, const double* u_b, double* eri_aa, double* eri_ab, double* eri_bb);
-void preload_integrals();   // first-use resolution of this unit's own kernels of the open-shell path
 int64_t read_eri_text(Context& cx, Integrals& in, const char* path, int64_t nbasis, double* eri_packed);
 int64_t write_fcidump(Context& cx, const Integrals& in, const char* path, int64_t nbasis);
 

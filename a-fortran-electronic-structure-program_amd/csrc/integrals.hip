@@ -1,5 +1,6 @@
-// integrals.hip -- the integral layer (integrals.h): the resident AO / MO integrals and their validity records, the AO->MO transform in
-// its forms (pair kernels, gather GEMM, LDS-DMA GEMM, slab-blocked), the orbital windows, the frozen-core operator, the text reader and the FCIDUMP writers.
+// integrals.hip -- the integral layer (integrals.h), host side: the resident AO / MO integrals and their validity records, the Fock builds,
+// the AO->MO transform in its forms (pair kernels, gather GEMM, LDS-DMA GEMM, slab-blocked), the orbital windows, the frozen-core operator,
+// the text reader and the FCIDUMP reader and writers.  No device code: the layer's kernels are integrals_kernels.hip's.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -7,99 +8,11 @@
 #include "fcidump_format.h"
 #include "fcidump_parse.h"
 #include "integrals.h"
+#include "integrals_kernels.h"
 #include "solver.h"
 #include "tgemm.h"
 
 using namespace afesp;
-
-extern "C" {   // (the names these kernels have in profiles: plain, as the entry points' own)
-// ---- a quarter transform on the LDS-DMA GEMM (tgemm.h): out(x2, m, S) = sum_x1 C(m, x1) in(x1, x2, S)
-// The transformed index is the fastest one of `in`, so every column (x2, S) of the product is a contiguous run of n doubles: both
-// operands are contiguous along the summation index (C goes in as a zero-padded transpose), which is all that kernel asks for.
-// The result comes out with x2 fastest and the new index second -- the layout the NEXT quarter transform wants for its input
-// (and the one the old path produced after two of them: (p,q,K), (r,s,P)).  Needs an even n (16-byte chunks, pairs of columns).
-__global__ __launch_bounds__(256) void ao2mo_ct_kernel(double* ct, const double* c, int n, int Kc)
-{
-    for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < n * Kc; x += gridDim.x * blockDim.x) {
-        const int m = x / Kc, k = x % Kc;
-        ct[x] = k < n ? c[m + n * k] : 0.0;
-    }
-}
-// rowA[m] = byte offset of row m of the padded transpose; colB[c] = byte offset of column c = x2 + n Sloc of a slab of `in`;
-// offCm[m] = ld m; offCn[c] = x2 + ld n Sloc (elements); the pads behind them (tgemm.h) are zero.
-// ld: the temporaries' columns are ld doubles long (n of them data, the rest zero): ld = Kc puts every column on a 128-byte line
-__global__ __launch_bounds__(256) void ao2mo_tables_kernel(uint32_t* rowA, uint32_t* colB, int64_t* offCm, int64_t* offCn, int n, int Kc, int64_t ncol, int64_t ld)
-{
-    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < ncol + 256; x += (int64_t)gridDim.x * blockDim.x) {
-        if (x < n + 256) rowA[x] = x < n ? (uint32_t)(8 * Kc * x) : 0u;
-        if (x < n + 128) offCm[x] = x < n ? ld * x : 0;
-        colB[x] = x < ncol ? (uint32_t)(8 * ld * x) : 0u;
-        if (x < ncol + 128) offCn[x] = x < ncol ? (x % n) + ld * n * (x / n) : 0;
-    }
-}
-
-// The second pair of transforms is only needed where the packed result has an entry: (rs|PQ) for RS <= PQ, i.e. r <= p(PQ).  The
-// last transform therefore runs over the columns (r, PQ) with r <= p only -- p + 1 of them per pair PQ = tri(p, q), rounded up to
-// an even count (pairs of columns are stored together) -- about half of all: colB / offCn list them pair by pair, relative to
-// the pair's slab (cstart[PQ] = first column of the pair).
-__global__ __launch_bounds__(256) void ao2mo_tables_tri_kernel(uint32_t* colB, int64_t* offCn, const int64_t* cstart, int n, int64_t np, int64_t sl, int64_t ld)
-{
-    for (int64_t P = blockIdx.x; P < np; P += gridDim.x) {
-        const int64_t c0 = cstart[P], cnt = cstart[P + 1] - c0, rel = P % sl;
-        for (int64_t r = threadIdx.x; r < cnt; r += blockDim.x) {
-            colB[c0 + r] = (uint32_t)(8 * ld * (r + (int64_t)n * rel));
-            offCn[c0 + r] = r + ld * n * rel;
-        }
-    }
-}
-
-// columns (x2, S) with x2 < TG_BM only (the pair transposition behind the second transform reads its result (x2, m, S) for
-// x2 <= m only: the rows m < 128 are needed for these columns only), relative to a slab: column c = x2 + 128 Sloc
-__global__ __launch_bounds__(256) void ao2mo_tables_lo_kernel(uint32_t* colB, int64_t* offCn, int n, int cnt, int64_t ncol, int64_t ld)
-{
-    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < ncol + 256; x += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t x2 = x % cnt, sloc = x / cnt;
-        colB[x] = x < ncol ? (uint32_t)(8 * ld * (x2 + (int64_t)n * sloc)) : 0u;
-        if (x < ncol + 128) offCn[x] = x < ncol ? x2 + ld * n * sloc : 0;
-    }
-}
-// ---- the two spin Fock operators of a restricted determinant (afesp_mo_fock_ro, afesp_read_fcidump_rohf) out of ONE packed MO array:
-//   F_a(p,q) = h(p,q) + sum_{i < na} [(pq|ii) - (pi|qi)] + sum_{i < nb} (pq|ii),   F_b: na and nb exchanged
-// One wave per pair p >= q, as k_fock_mo: lane l takes i = l, l + 64, ... in rising order -- the Coulomb sum over the doubly occupied
-// orbitals i < nb, the one over the singly occupied ones nb <= i < na and the two exchange sums are kept apart -- the 64 partial sums are
-// added in a fixed butterfly order and both triangles are written from one register: symmetric to the bit, the same on every run.
-__global__ __launch_bounds__(256) void fock_ro_kernel(double* __restrict__ fa, double* __restrict__ fb, const double* __restrict__ h,
-                                                      const double* __restrict__ packed, int n, int na, int nb)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t np = (int64_t)n * (n + 1) / 2, w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= np) return;   // (whole waves leave)
-    int64_t p = (int64_t)((sqrt(8.0 * (double)w + 1.0) - 1.0) * 0.5);
-    while (p * (p + 1) / 2 > w) --p;
-    while ((p + 1) * (p + 2) / 2 <= w) ++p;
-    const int64_t q = w - p * (p + 1) / 2;
-    auto tri = [](int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; };
-    double jd = 0.0, js = 0.0, kd = 0.0, ks = 0.0;   // Coulomb / exchange over the doubly / the singly occupied orbitals
-    for (int64_t i = lane; i < na; i += 64) {
-        const double J = packed[tri(w, tri(i, i))], K = packed[tri(tri(p, i), tri(q, i))];
-        if (i < nb) { jd += J; kd += K; }
-        else { js += J; ks += K; }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        jd += __shfl_xor(jd, off, 64);
-        js += __shfl_xor(js, off, 64);
-        kd += __shfl_xor(kd, off, 64);
-        ks += __shfl_xor(ks, off, 64);
-    }
-    if (lane == 0) {
-        const int64_t lo = p + (int64_t)n * q, up = q + (int64_t)n * p;
-        const double h0 = h[lo], jj = (jd + jd) + js;
-        const double va = h0 + (jj - (kd + ks)), vb = h0 + (jj - kd);
-        fa[lo] = va; fa[up] = va;
-        fb[lo] = vb; fb[up] = vb;
-    }
-}
-}  // extern "C"
 
 namespace {
 struct Ao2moTg {
@@ -135,11 +48,8 @@ static Ao2moTg ao2mo_tg_prepare(Context& cx, const double* Cm, int64_t n, int64_
     t.colB = t.rowA + n + 256;
     t.offCm = (int64_t*)cx.scratch("ao2mo_t64", n + 128 + ncol + 128 + 2);
     t.offCn = t.offCm + n + 128;
-    AFESP_KLAUNCH(ao2mo_ct_kernel, dim3((unsigned)((n * t.Kc + 255) / 256)), dim3(256), 0, cx.stream, t.ct, Cm, (int)n, (int)t.Kc);
-    AFESP_HIP(hipGetLastError());
-    AFESP_KLAUNCH(ao2mo_tables_kernel, dim3((unsigned)std::min<int64_t>((ncol + 256 + 255) / 256, 65536)), dim3(256), 0, cx.stream, t.rowA,
-                       t.colB, t.offCm, t.offCn, (int)n, (int)t.Kc, ncol, t.ld);
-    AFESP_HIP(hipGetLastError());
+    k_ao2mo_ct(cx, t.ct, Cm, (int)n, (int)t.Kc);
+    k_ao2mo_tables(cx, t.rowA, t.colB, t.offCm, t.offCn, (int)n, (int)t.Kc, ncol, t.ld);
     const int64_t ng = (np + t.sl - 1) / t.sl;
     t.groups_cap = 8 * (ng + 2);
     t.groups = (TgGroup*)cx.scratch("ao2mo_tg", (int64_t)(t.groups_cap * sizeof(TgGroup) / sizeof(double) + 1));
@@ -155,16 +65,12 @@ static Ao2moTg ao2mo_tg_prepare(Context& cx, const double* Cm, int64_t n, int64_
     AFESP_HIP(hipMemcpyAsync(cs_dev, t.cstart.data(), (size_t)(np + 1) * sizeof(int64_t), hipMemcpyHostToDevice, cx.stream));
     AFESP_HIP(hipMemsetAsync(t.colB_tri + ctot, 0, 256 * sizeof(uint32_t), cx.stream));
     AFESP_HIP(hipMemsetAsync(t.offCn_tri + ctot, 0, 128 * sizeof(int64_t), cx.stream));
-    AFESP_KLAUNCH(ao2mo_tables_tri_kernel, dim3((unsigned)std::min<int64_t>(np, 65536)), dim3(256), 0, cx.stream, t.colB_tri, t.offCn_tri,
-                       cs_dev, (int)n, np, t.sl, t.ld);
-    AFESP_HIP(hipGetLastError());
+    k_ao2mo_tables_tri(cx, t.colB_tri, t.offCn_tri, cs_dev, (int)n, np, t.sl, t.ld);
     if (n > TG_BM) {
         const int64_t nlo = (int64_t)TG_BM * t.sl;
         t.colB_lo = (uint32_t*)cx.scratch("ao2mo_t32h", (nlo + 256) / 2 + 2);
         t.offCn_lo = (int64_t*)cx.scratch("ao2mo_t64h", nlo + 128 + 2);
-        AFESP_KLAUNCH(ao2mo_tables_lo_kernel, dim3((unsigned)std::min<int64_t>((nlo + 256 + 255) / 256, 65536)), dim3(256), 0, cx.stream,
-                           t.colB_lo, t.offCn_lo, (int)n, (int)TG_BM, nlo, t.ld);
-        AFESP_HIP(hipGetLastError());
+        k_ao2mo_tables_lo(cx, t.colB_lo, t.offCn_lo, (int)n, (int)TG_BM, nlo, t.ld);
     }
     return t;
 }
@@ -518,6 +424,41 @@ double* Integrals::replace_mo(Context& cx, Solver& sv, int64_t n)
     return cx.alloc_raw(neri_of(n));
 }
 
+// build_fock (src/hf.f90:349-385) on the resident packed AO integrals
+void build_fock(Context& cx, Integrals& in, int64_t n, const double* density, const double* hcore, double* fock)
+{
+    const int64_t n2 = n * n;
+    double* buf = cx.scratch("fock_io", 3 * n2);
+    AFESP_HIP(hipMemcpyAsync(buf, density, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(buf + n2, hcore, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+    int64_t L = 0;
+    const double* u = in.half_unpacked(cx, n, L);
+    double* work = cx.scratch("fock_work", k_build_fock_work((int)n));
+    in.half_restamp(cx);
+    k_build_fock(cx, buf + 2 * n2, buf + n2, buf, u, work, (int)n, (int)L);
+    AFESP_HIP(hipMemcpyAsync(fock, buf + 2 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+void build_fock_uhf(Context& cx, Integrals& in, int64_t n, const double* dens_a, const double* dens_b, const double* hcore, double* fock_a,
+                    double* fock_b)
+{
+    const int64_t n2 = n * n;
+    double* buf = cx.scratch("fock_uio", 5 * n2);   // [ Da | Db | H | Fa | Fb ]
+    AFESP_HIP(hipMemcpyAsync(buf, dens_a, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(buf + n2, dens_b, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(buf + 2 * n2, hcore, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+    // the half-unpacked integrals build_fock keeps (same buffer, same validity)
+    int64_t L = 0;
+    const double* u = in.half_unpacked(cx, n, L);
+    double* work = cx.scratch("fock_uwork", k_build_fock_uhf_work((int)n));
+    in.half_restamp(cx);
+    k_build_fock_uhf(cx, buf + 3 * n2, buf + 4 * n2, buf + 2 * n2, buf, buf + n2, u, work, (int)n, (int)L);
+    AFESP_HIP(hipMemcpyAsync(fock_a, buf + 3 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(fock_b, buf + 4 * n2, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
 double ao2mo_mp2(Context& cx, Integrals& in, Solver& sv, int64_t n, int64_t o, const double* coeff, const double* levels,
                  const double* eri_packed, double* eri_mo_packed)
 {
@@ -663,17 +604,6 @@ void mo_rotate_uhf(Context& cx, Integrals& in, int64_t n, const double* u_a, con
     cx.sync();
 }
 
-void k_fock_ro(Context& cx, double* fa, double* fb, const double* h, const double* packed, int n, int na, int nb)
-{
-    const int64_t waves = npair_of(n);
-    AFESP_KLAUNCH(fock_ro_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, cx.stream, fa, fb, h, packed, n, na, nb);
-    AFESP_HIP(hipGetLastError());
-}
-void preload_integrals()
-{
-    first_use_touch(reinterpret_cast<const void*>(fock_ro_kernel));
-    (void)hipGetLastError();
-}
 // 1/2 sum_{i < na} [h + F_a](i,i) + 1/2 sum_{i < nb} [h + F_b](i,i), host matrices
 static double ro_reference_energy(const double* h, const double* fa, const double* fb, int64_t n, int64_t na, int64_t nb)
 {
@@ -874,7 +804,7 @@ struct File {
     explicit File(FILE* g) : f(g) {}
     ~File() { if (f) fclose(f); }
 };
-// the survivors |x| > threshold of a device array, compacted there (kernels.hip) and written as two-electron lines; returns their number
+// the survivors |x| > threshold of a device array, compacted there (integrals_kernels.hip) and written as two-electron lines; returns their number
 int64_t dump_block(Context& cx, FILE* f, const char* who, const double* x, int64_t total, double threshold, fcidump::Block b, int64_t np)
 {
     const int64_t nchunks = k_compact_chunks(total);

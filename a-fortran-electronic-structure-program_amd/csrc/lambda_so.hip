@@ -2,6 +2,7 @@
 // Every term is one label-driven contract(), in the letters of Gauss and Stanton (1995) as restated in tests/np_lambda.py
 // (hbar, lambda_rhs_explicit, density_explicit); launches are plain call-by-call ones -- the levelled / recorded path of fused.h is
 // not extended to them.
+#include "device_util.h"
 #include "lambda_so.h"
 
 #include <cmath>
@@ -9,7 +10,6 @@
 namespace afesp {
 namespace {
 
-constexpr int TB = 256;
 constexpr int MAXBLK = 1024;
 inline unsigned blocks_for(int64_t n) { return (unsigned)std::min<int64_t>((n + TB - 1) / TB, 65536); }
 #define LAM_STRIDE(X_, N_) for (int64_t X_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; X_ < (N_); X_ += (int64_t)gridDim.x * blockDim.x)
