@@ -684,7 +684,10 @@ class Engine:
 
     # ---- spin-orbital path: do_ccsd_spinorb (src/ccsd.f90:71-277), do_ccsd_t_spinorb (:1812-1922)
     SO_SHAPES = {"F_vv": "vv", "F_oo": "oo", "F_ov": "ov", "W_oooo": "oooo", "W_vvvv": "vvvv", "W_ovvo": "ovvo", "tau": "oovv",
-                 "tau_tilde": "oovv", "oovv": "oovv", "vvvv": "vvvv", "t1": "ov", "t2": "oovv", "f_ov": "ov", "f_oo": "oo", "f_vv": "vv"}
+                 "tau_tilde": "oovv", "oovv": "oovv", "vvvv": "vvvv", "t1": "ov", "t2": "oovv", "f_ov": "ov", "f_oo": "oo", "f_vv": "vv",
+                 # of a live Lambda state (status 21 otherwise): H_vvvo is H_abei stored (i,e,a,b), H_ovoo is H_mbij stored (m,b,i,j)
+                 "H_ov": "ov", "H_oo": "oo", "H_vv": "vv", "H_oooo": "oooo", "H_vovv": "vovv", "H_ooov": "ooov", "H_ovvo": "ovvo",
+                 "H_vvvo": "ovvv", "H_ovoo": "ovoo", "lam_tau": "oovv", "G_vv": "vv", "G_oo": "oo"}
 
     def init_cc_spinorb(self, nbasis, nel, canon_levels, eri_mo=None, diis_nerr=8, foo_as_published=False):
         self.so_o, self.so_v = int(nel), int(2 * nbasis - nel)

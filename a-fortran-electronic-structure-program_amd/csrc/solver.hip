@@ -429,6 +429,17 @@ void Solver::so_fetch_tensor(Context& cx, const char* name, double* out, int64_t
         {"F_vv", &s.F_vv}, {"F_oo", &s.F_oo}, {"F_ov", &s.F_ov}, {"W_oooo", &s.W_oooo}, {"W_vvvv", &s.W_vvvv},
         {"W_ovvo", &s.W_ovvo}, {"tau", &s.tau}, {"tau_tilde", &s.tau_t}, {"oovv", &s.oovv}, {"vvvv", &s.vvvv},
         {"t1", &s.t1}, {"t2", &s.t2}, {"f_ov", &s.f_ov}, {"f_oo", &s.f_oo}, {"f_vv", &s.f_vv}};
+    // the intermediates of a live Lambda state (lambda_so.h), in its storage; G_vv / G_oo as of the last iteration or density
+    static const char* const lam_names[] = {"H_ov", "H_oo", "H_vv", "H_oooo", "H_vovv", "H_ooov", "H_ovvo", "H_vvvo", "H_ovoo", "lam_tau", "G_vv", "G_oo"};
+    for (size_t q = 0; q < sizeof(lam_names) / sizeof(lam_names[0]); ++q)
+        if (!strcmp(lam_names[q], name)) {
+            SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_get_tensor");
+            const Tensor* lam[] = {&L.Hov, &L.Hoo, &L.Hvv, &L.Hoooo, &L.Hvovv, &L.Hooov, &L.Hovvo, &L.Hvvvo, &L.Hovoo, &L.tau, &L.Gvv, &L.Goo};
+            if (lam[q]->size() > capacity) throw Error(1, std::string("afesp_ccsd_so_get_tensor: buffer too small for ") + name);
+            AFESP_HIP(hipMemcpyAsync(out, lam[q]->d, sizeof(double) * lam[q]->size(), hipMemcpyDeviceToHost, cx.stream));
+            cx.sync();
+            return;
+        }
     for (auto& e : tab)
         if (!strcmp(e.n, name)) {
             if (!e.t->d) throw Error(1, std::string("afesp_ccsd_so_get_tensor: this state holds no ") + name + " (afesp_ccsd_uso_init_fock makes one that does)");

@@ -178,7 +178,10 @@ int afesp_ccsd_so_iterate(afesp_ctx* ctx, double e_tol, double t_tol, double* en
 int afesp_ccsd_so_diis(afesp_ctx* ctx);
 int afesp_ccsd_so_get_amplitudes(afesp_ctx* ctx, double* t1, double* t2);
 int afesp_ccsd_so_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2);
-/* name: F_vv F_oo F_ov W_oooo (stored i,j,m,n) W_vvvv (stored e,f,a,b) W_ovvo tau tau_tilde oovv vvvv t1 t2 */
+/* name: F_vv F_oo F_ov W_oooo (stored i,j,m,n) W_vvvv (stored e,f,a,b) W_ovvo tau tau_tilde oovv vvvv t1 t2.
+ * With a live Lambda state (afesp_ccsd_so_lambda_init; status 21 without one or with a stale one) also its t-fixed intermediates:
+ * H_ov (m,e) H_oo (m,i) H_vv (a,e) H_oooo (m,n,i,j) H_vovv (a,m,e,f) H_ooov (m,n,i,e) H_ovvo (m,b,e,j) H_vvvo (H_abei stored i,e,a,b)
+ * H_ovoo (m,b,i,j) lam_tau (i,j,a,b), and G_vv (a,e) G_oo (m,i) as of the last afesp_ccsd_so_lambda_iterate / afesp_ccsd_so_density */
 int afesp_ccsd_so_get_tensor(afesp_ctx* ctx, const char* name, double* out, int64_t capacity);
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc);
 int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t);

@@ -189,7 +189,7 @@ def density_explicit(cc, t1, t2, l1, l2):
     doo = -E("ia,ma->mi", l1, t1) - Goo                                   # dL/df_mi
     dvv = E("ia,ie->ae", l1, t1) - Gvv                                    # dL/df_ae
     dov = (t1 + l1 + E("ia,imae->me", l1, t2) - E("ia,ie,ma->me", l1, t1, t1) + E("be,mb->me", Gvv, t1) - E("mj,je->me", Goo, t1))
-    d = np.zeros((o + v, o + v))
+    d = np.zeros((o + v, o + v), dov.dtype)
     d[:o, :o] = 0.5 * (doo + doo.T)
     d[o:, o:] = 0.5 * (dvv + dvv.T)
     d[:o, o:] = 0.5 * dov

@@ -49,10 +49,13 @@ _CASES = {}
 
 def _case(name):
     """the numpy side of a shape, made once: integrals, the restatement, and how to feed the engine"""
-    if name in _CASES:
-        return _CASES[name]
-    src, n, na, nb = SHAPES[name]
-    seed = 100 + sorted(SHAPES).index(name)
+    if name not in _CASES:
+        _CASES[name] = _build_case(name, *SHAPES[name], 100 + sorted(SHAPES).index(name))
+    return _CASES[name]
+
+
+def _build_case(name, src, n, na, nb, seed):
+    """(test_gpu_lambda_mid.py builds its shapes with this too)"""
     rng = np.random.default_rng(seed)
     if name == "two_electron":
         h, chem, fa, fb = np_lambda.two_electron_model(n, seed)
@@ -74,7 +77,6 @@ def _case(name):
         f = np_rocc.so_fock(fa, fb, na, nb)
         c.update(cc=np_rocc.ROCC(g, f, o), g=g, f=f, ua=ua, ub=ub, fa=fa, fb=fb)
     c["o"], c["v"] = c["cc"].o, c["cc"].v
-    _CASES[name] = c
     return c
 
 

@@ -45,20 +45,69 @@ def _close(x, ref, what):
     assert err < bound, what
 
 
+def _explicit_against_complex_step(g, f, cc, t1, t2, l1, l2, jac):
+    G1, G2 = np_lambda.lambda_residual(cc, t1, t2, l1, l2, jac)
+    X1, X2 = np_lambda.lambda_residual_explicit(cc, t1, t2, l1, l2)
+    _close(X1, G1, "G1")
+    _close(X2, G2, "G2")
+    _close(np_lambda.density_explicit(cc, t1, t2, l1, l2), np_lambda.density(g, f, cc.o, t1, t2, l1, l2), "density")
+
+
 def test_explicit_forms_equal_the_complex_step_forms(case):
     c, cc = case, case["cc"]
     rng = np.random.default_rng(11)
     o, v = cc.o, cc.v
     points = [(c["t1"], c["t2"], c["l1"], c["l2"], c["jac"]), (*np_lambda.antisym_random(rng, o, v), *np_lambda.antisym_random(rng, o, v), None)]
     for t1, t2, l1, l2, jac in points:
-        G1, G2 = np_lambda.lambda_residual(cc, t1, t2, l1, l2, jac)
-        X1, X2 = np_lambda.lambda_residual_explicit(cc, t1, t2, l1, l2)
-        _close(X1, G1, "G1")
-        _close(X2, G2, "G2")
-        _close(np_lambda.density_explicit(cc, t1, t2, l1, l2), np_lambda.density(c["g"], c["f"], o, t1, t2, l1, l2), "density")
+        _explicit_against_complex_step(c["g"], c["f"], cc, t1, t2, l1, l2, jac)
     # at the converged t and the solved l the residual itself vanishes
     G1, G2 = np_lambda.lambda_residual_explicit(cc, c["t1"], c["t2"], c["l1"], c["l2"])
     assert max(np.max(np.abs(G1)), np.max(np.abs(G2))) < 1e-12
+
+
+def test_explicit_forms_equal_the_complex_step_forms_at_pairwise_distinct_extents():
+    """The random-point comparison alone (nothing is converged) on the non-canonical model n = 6, nalpha = 3, nbeta = 2: o = 5, v = 7,
+    npo = 10 and npv = 21 are pairwise distinct, so an einsum of the restatement with two extents transposed cannot even be evaluated,
+    let alone agree.  245 unique amplitudes: 245 complex residuals for the Jacobian."""
+    g, f, o, _ = np_lambda.model(6, 3, 2, 3, canonical=False)
+    cc = np_rocc.ROCC(g, f, o)
+    v = cc.v
+    assert (o, v) == (5, 7) and len(np_lambda.pack(cc.t1, cc.t2)) == 245
+    assert len({o, v, o * (o - 1) // 2, v * (v - 1) // 2}) == 4 and np.max(np.abs(cc.f_ov)) > 0.05
+    rng = np.random.default_rng(12)
+    t1, t2 = np_lambda.antisym_random(rng, o, v)
+    l1, l2 = np_lambda.antisym_random(rng, o, v)
+    _explicit_against_complex_step(g, f, cc, t1, t2, l1, l2, None)
+
+
+@pytest.mark.parametrize("name,n,na,nb,canonical", [("fock_odd", 11, 5, 4, False), ("rhf_mid", 14, 5, 5, True)])
+def test_float64_explicit_form_is_the_extended_precision_one_to_1e_13(name, n, na, nb, canonical):
+    """The explicit form is the only reference of tests/test_gpu_lambda_mid.py (the complex step is infeasible at those extents), and
+    the bound there is 1e-11 x max(1, max |ref|): here every tensor it supplies, evaluated in float64, stays within 1e-13 x max |ref| of
+    the same formulas in np.longdouble (64-bit mantissa) at O(1) amplitudes -- two orders inside that bound.  Measured: 2.9e-15 (x1 at rhf_mid)."""
+    assert np.finfo(np.longdouble).eps < 1e-18                     # (an extended type, not an alias of float64)
+    g, f, o, _ = np_lambda.model(n, na, nb, 40 + n, canonical=canonical)
+    ld = np.longdouble
+    cc, cx = np_rocc.ROCC(g, f, o), np_rocc.ROCC(g.astype(ld), f.astype(ld), o)
+    v = cc.v
+    rng = np.random.default_rng(13)
+    t1, t2 = np_lambda.antisym_random(rng, o, v)
+    l1, l2 = np_lambda.antisym_random(rng, o, v)
+    amps = (t1, t2, l1, l2)
+
+    def everything(c, a):
+        I = np_lambda.hbar(c, a[0], a[1])
+        x1, x2 = np_lambda.lambda_rhs_explicit(c, *a, I)
+        return dict(I, x1=x1, x2=x2, density=np_lambda.density_explicit(c, *a))
+    got, ref = everything(cc, amps), everything(cx, tuple(x.astype(ld) for x in amps))
+    assert ref["x2"].dtype == ld and ref["Hvvvo"].dtype == ld and ref["density"].dtype == ld
+    worst = 0.0
+    for k in sorted(ref):
+        rel = float(np.max(np.abs(got[k] - ref[k])) / np.max(np.abs(ref[k])))
+        print(name, k, "float64 against longdouble, relative", rel)
+        worst = max(worst, rel)
+        assert rel < 1e-13, k
+    print(name, "worst", worst)
 
 
 def test_density_is_the_derivative_of_the_converged_energy(case):
@@ -155,6 +204,9 @@ def test_library_exports_the_lambda_entry_points():
     for m in ("so_lambda_init", "so_lambda_iterate", "so_lambda_energy", "so_lambda_diis", "so_lambda", "so_set_lambda", "so_density"):
         assert callable(getattr(capi.Engine, m))
     assert lib.afesp_ccsd_so_lambda_init(None, 8) == 1           # a NULL context is an argument error, as everywhere
+    for name in ("H_ov", "H_oo", "H_vv", "H_oooo", "H_vovv", "H_ooov", "H_ovvo", "H_vvvo", "H_ovoo", "lam_tau", "G_vv", "G_oo"):
+        assert len(capi.Engine.SO_SHAPES[name]) in (2, 4), name  # (afesp_ccsd_so_get_tensor serves them from a live Lambda state)
+    assert (capi.Engine.SO_SHAPES["H_vvvo"], capi.Engine.SO_SHAPES["H_ovoo"]) == ("ovvv", "ovoo")   # H_abei as (i,e,a,b), H_mbij as (m,b,i,j)
 
 
 def test_cc_density_key_is_refused_on_the_types_that_run_no_spin_orbital_ccsd(tmp_path):
