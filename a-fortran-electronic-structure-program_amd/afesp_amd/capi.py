@@ -30,6 +30,8 @@ EXPORTS = [
     "afesp_ccsd_so_set_amplitudes", "afesp_ccsd_so_get_tensor", "afesp_ccsd_so_t_ntriples", "afesp_ccsd_so_t",
     "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density",
+    "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
+    "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
@@ -115,6 +117,14 @@ def load_library():
     L.afesp_ccsd_so_get_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_set_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_density.argtypes = [C.c_void_p, _dp, i64]
+    L.afesp_ccsd_so_eom_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.afesp_ccsd_so_eom_sigma.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+    L.afesp_ccsd_so_eom_guess.argtypes = [C.c_void_p]
+    L.afesp_ccsd_so_eom_set_guess.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
+                                            C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_eom_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_eig_general.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp]
     L.afesp_read_eri_text.argtypes = [C.c_void_p, C.c_char_p, i64, _opt, C.POINTER(i64)]
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
     L.afesp_set_eri.argtypes = [C.c_void_p, i64, _dp]
@@ -783,6 +793,53 @@ class Engine:
         buf = np.zeros(n * n)
         self._chk(self.L.afesp_ccsd_so_density(self.h, buf, buf.size if capacity is None else capacity))
         return buf.reshape((n, n), order="F")
+
+    # ---- EOM-EE-CCSD excitation energies of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them).  All need a live Lambda
+    # state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes t1 / t2 or lambda
+    eom_nroots = 0
+
+    def so_eom_init(self, nroots, max_space):
+        self._chk(self.L.afesp_ccsd_so_eom_init(self.h, nroots, max_space))
+        self.eom_nroots = int(nroots)
+
+    def so_eom_sigma(self, r1, r2):
+        """sigma = A r.  r1 (o,v) and r2 (o,o,v,v) for one vector -> (s1, s2); with a leading axis, (k,o,v) and (k,o,o,v,v), k vectors in one
+        call -> the same with that axis."""
+        o, v = self.so_o, self.so_v
+        r1, r2 = np.asarray(r1, dtype=np.float64), np.asarray(r2, dtype=np.float64)
+        single = r1.ndim == 2
+        if single:
+            r1, r2 = r1[None], r2[None]
+        k = r1.shape[0]
+        if r1.shape != (k, o, v) or r2.shape != (k, o, o, v, v):
+            raise ValueError("so_eom_sigma: r1 / r2 do not have the shapes (k,) o v / (k,) o o v v of this state")
+        a1, a2 = np.concatenate([_f(x) for x in r1]), np.concatenate([_f(x) for x in r2])
+        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
+        self._chk(self.L.afesp_ccsd_so_eom_sigma(self.h, k, a1, a2, s1, s2))
+        s1 = np.stack([x.reshape((o, v), order="F") for x in s1.reshape(k, o * v)])
+        s2 = np.stack([x.reshape((o, o, v, v), order="F") for x in s2.reshape(k, o * o * v * v)])
+        return (s1[0], s2[0]) if single else (s1, s2)
+
+    def so_eom_guess(self):
+        self._chk(self.L.afesp_ccsd_so_eom_guess(self.h))
+
+    def so_eom_set_guess(self, k, r1, r2):
+        self._chk(self.L.afesp_ccsd_so_eom_set_guess(self.h, k, _f(r1), _f(r2)))
+
+    def so_eom_iterate(self, tol=1e-8):
+        """One Davidson step -> (omega, resnorm, flags, sigma builds so far, converged); flags: bit 0 converged, bit 1 complex"""
+        n = self.eom_nroots
+        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        ns, cv = C.c_int(), C.c_int()
+        self._chk(self.L.afesp_ccsd_so_eom_iterate(self.h, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
+        return om, rs, fl, ns.value, bool(cv.value)
+
+    def so_eom_vector(self, k):
+        """Ritz vector k of the last step, <x, x> = sum x1^2 + 1/4 sum x2^2 = 1"""
+        o, v = self.so_o, self.so_v
+        r1, r2 = np.zeros(o * v), np.zeros(o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_eom_get_vector(self.h, k, r1, r2))
+        return r1.reshape((o, v), order="F"), r2.reshape((o, o, v, v), order="F")
 
     def do_ccsd_t_spatial_plain(self, t_begin=0, t_end=None):
         """E[T], E(T) only: what plain CCSD(T)_spatial / CCSD[T]_spatial need (no y, no D sums)."""

@@ -44,6 +44,7 @@ class SystemIn:
     fno_n_virt: int = -1            # number of natural virtuals kept; -1 = off
     fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
     cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
+    eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -152,6 +153,10 @@ def read_els_in(path: str) -> SystemIn:
     if sysin.cc_density and sysin.fcidump_in and sysin.calc_type in OPEN_SHELL_TYPES:
         raise ValueError("cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the "
                          "spin-summed density needs!")
+    if not isinstance(sysin.eom_nroots, int) or isinstance(sysin.eom_nroots, bool) or sysin.eom_nroots < 0:
+        raise ValueError("eom_nroots must be a non-negative integer!")
+    if sysin.eom_nroots > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
+        raise ValueError(f"{sysin.calc_type} takes no eom_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!")
     return sysin
 
 

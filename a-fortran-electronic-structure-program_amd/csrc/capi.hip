@@ -11,6 +11,8 @@
 #include "../../include/afesp.h"
 #include "integrals.h"
 #include "solver.h"
+#include "eom_so.h"
+#include "small_eig.h"
 #include "comm.h"
 #include "tall.h"
 
@@ -622,6 +624,53 @@ int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity)
 {
     return entry(ctx, [&](Context& cx) { so_density(cx, ctx->sv.need_so("afesp_ccsd_so_density: no spin-orbital CCSD state").so, d, capacity); });
 }
+
+// ---- EOM-EE-CCSD excitation energies (eom_so.h)
+int afesp_ccsd_so_eom_init(afesp_ctx* ctx, int nroots, int max_space)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_init(cx, ctx->sv.need_so("afesp_ccsd_so_eom_init: no spin-orbital CCSD state").so, nroots, max_space); });
+}
+
+int afesp_ccsd_so_eom_sigma(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_sigma_host(cx, ctx->sv.need_so("afesp_ccsd_so_eom_sigma: no spin-orbital CCSD state").so, nvec, r1, r2, s1, s2);
+    });
+}
+
+int afesp_ccsd_so_eom_guess(afesp_ctx* ctx)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_guess: no spin-orbital CCSD state").so); });
+}
+
+int afesp_ccsd_so_eom_set_guess(afesp_ctx* ctx, int k, const double* r1, const double* r2)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_set_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_set_guess: no spin-orbital CCSD state").so, k, r1, r2); });
+}
+
+int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_iterate: no spin-orbital CCSD state").so;
+        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_iterate: tol must be positive");
+        const int conv = so_eom_iterate(cx, so, tol);
+        const SOEom& E = *so.eom;
+        for (int k = 0; k < E.nroots; ++k) {
+            if (omega) omega[k] = E.omega[k];
+            if (resnorm) resnorm[k] = E.resnorm[k];
+            if (flags) flags[k] = E.flags[k];
+        }
+        if (nsigma) *nsigma = E.nsigma;
+        if (converged) *converged = conv;
+    });
+}
+
+int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_get_vector(cx, ctx->sv.need_so("afesp_ccsd_so_eom_get_vector: no spin-orbital CCSD state").so, k, r1, r2); });
+}
+
+int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr) { return eig_general(n, a, lda, wr, wi, vr); }
 
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)nocc); }
 

@@ -8,6 +8,7 @@
 namespace afesp {
 
 struct SOLambda;   // lambda_so.h
+struct SOEom;      // eom_so.h
 
 struct SOState : DiisRing {
     int o = 0, v = 0, n = 0;
@@ -35,6 +36,7 @@ struct SOState : DiisRing {
     Tensor f_ov, f_oo, f_vv;
     double f_offdiag = 0.0;          // largest |f_oo|, |f_vv| off-diagonal element: (T) is defined for (semi)canonical orbitals only
     SOLambda* lam = nullptr;         // the Lambda state made by so_lambda_init for one amp_epoch (lambda_so.h); released by so_free
+    SOEom* eom = nullptr;            // the EOM state that borrows lam's H-bar elements (eom_so.h); released wherever lam is
 };
 
 // eri_mo_dev: packed chemist MO integrals on the device (length neri(nbasis)); e_host: spatial orbital energies (host)
@@ -60,7 +62,8 @@ void so_build_W_vvvv(Context& cx, SOState& s);    // W_abef itself (ccsd.f90:852
 int so_energy(Context& cx, SOState& s, double e_tol, double t_tol);
 // out(ijab) = sum_{e<f} x(ijef) <ab||ef> over antisymmetric pairs against va (the bare part of so_amplitudes' ladder; x: tau or lambda_2)
 void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out);
-void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip
+void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip (releases the EOM state too: it borrows from the Lambda state)
+void so_eom_free(Context& cx, SOState& s);        // eom_so.hip
 // (T): contribution of the triples i<j<k with flat index in [t_begin, t_end) to E_T (ccsd.f90:1910)
 int64_t so_triples_count(int o);
 double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);

@@ -17,6 +17,8 @@ module afesp_capi
              afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
              afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
              afesp_ccsd_so_density, &
+             afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
+             afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -425,6 +427,56 @@ module afesp_capi
          type(c_ptr), value :: ctx
          real(c_double), intent(out) :: d(*)
          integer(c_int64_t), value :: capacity
+         integer(c_int) :: rc
+      end function
+      ! EOM-EE-CCSD excitation energies on the live Lambda state's H-bar elements (include/afesp.h)
+      function afesp_ccsd_so_eom_init(ctx, nroots, max_space) bind(C, name='afesp_ccsd_so_eom_init') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nroots, max_space
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_sigma(ctx, nvec, r1, r2, s1, s2) bind(C, name='afesp_ccsd_so_eom_sigma') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nvec
+         real(c_double), intent(in) :: r1(*), r2(*)
+         real(c_double), intent(out) :: s1(*), s2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_guess(ctx) bind(C, name='afesp_ccsd_so_eom_guess') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_set_guess(ctx, k, r1, r2) bind(C, name='afesp_ccsd_so_eom_set_guess') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: k
+         real(c_double), intent(in) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_iterate(ctx, tol, omega, resnorm, flags, nsigma, converged) &
+         bind(C, name='afesp_ccsd_so_eom_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: tol
+         real(c_double), intent(out) :: omega(*), resnorm(*)
+         integer(c_int), intent(out) :: flags(*), nsigma, converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_get_vector(ctx, k, r1, r2) bind(C, name='afesp_ccsd_so_eom_get_vector') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: k
+         real(c_double), intent(out) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_eig_general(n, a, lda, wr, wi, vr) bind(C, name='afesp_eig_general') result(rc)
+         import :: c_int, c_double
+         integer(c_int), value :: n, lda
+         real(c_double), intent(in) :: a(*)
+         real(c_double), intent(out) :: wr(*), wi(*), vr(*)
          integer(c_int) :: rc
       end function
       function afesp_ccsd_so_t_ntriples(nocc) bind(C, name='afesp_ccsd_so_t_ntriples') result(n)

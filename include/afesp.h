@@ -219,6 +219,43 @@ int afesp_ccsd_so_get_lambda(afesp_ctx* ctx, double* l1, double* l2);
 int afesp_ccsd_so_set_lambda(afesp_ctx* ctx, const double* l1, const double* l2);
 int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity);
 
+/* EOM-EE-CCSD excitation energies of the spin-orbital state.  The right-hand EOM matrix in the singles and doubles space
+ * is the Jacobian A = dR/dt of the residuals above over the unique amplitudes; sigma(r) = A r for r = [r1 [o*v]; r2 [o*o*v*v]] laid out as
+ * t1 / t2, r2 antisymmetric in i,j and in a,b.  On that storage <x, y> = sum x1 y1 + 1/4 sum x2 y2.  The excitation energies are the lowest
+ * eigenvalues of A at the converged t.  The H-bar elements are those of the live Lambda state (borrowed): afesp_ccsd_so_lambda_init must
+ * have been called for the current t1 / t2 -- Lambda itself need not be converged -- and status 21 (AFESP_LAMBDA_STALE) is returned
+ * without one or with a stale one.  None of these calls writes t1 / t2, lambda or the epoch.
+ *   afesp_ccsd_so_eom_sigma     = s = A r for nvec vectors stored one after the other (host in / out); needs no afesp_ccsd_so_eom_init.
+ *   afesp_ccsd_so_eom_init      = a block Davidson state for the nroots lowest roots with at most max_space basis vectors
+ *                                 (1 <= nroots <= unique dimension, 2 nroots <= max_space <= 4096 -- the projected problem is solved
+ *                                 densely on the host --; status 1 otherwise, or if it does not fit);
+ *                                 released by afesp_ccsd_so_lambda_init, by every init of the state and with the context.
+ *   afesp_ccsd_so_eom_guess     = unit vectors on the nroots smallest -D (the diagonal guess of A) over the unique amplitudes, ties by flat
+ *                                 index; afesp_ccsd_so_eom_set_guess = the caller's vector k (0-based) instead.  _eom_guess starts over, and
+ *                                 so does the first _eom_set_guess after an _eom_init, an _eom_guess or an _eom_iterate; further
+ *                                 _eom_set_guess calls join that block, and a k left out is a zero vector, which is dropped.
+ *   afesp_ccsd_so_eom_iterate   = one Davidson step: the pending vectors are orthonormalised against the basis (dropped below 1e-10),
+ *                                 their sigma built, the projected matrix extended and solved on the host, then x_k, rho_k = A x_k -
+ *                                 omega_k x_k and the corrections rho_k / (omega_k + D) of the roots with |rho_k| >= tol are formed.  When
+ *                                 basis and pending vectors exceed max_space the basis is first collapsed onto the nroots Ritz vectors.
+ *                                 omega, resnorm, flags: nroots entries each (NULL: not wanted); flags[k] bit 0: |rho_k| < tol, bit 1: the
+ *                                 projected root had an imaginary part (the real part of its vector is used).  *nsigma = sigma builds
+ *                                 since the guess, *converged = every root has |rho_k| < tol.
+ *   afesp_ccsd_so_eom_get_vector = Ritz vector k of the last step, <x, x> = 1.
+ *   afesp_eig_general           = the host eigen-solver of the projected matrix (no context, no GPU): eigenvalues wr + i wi of the real
+ *                                 n x n column-major a, ordered by real part (ties: a complex pair stays adjacent, wi > 0 first), and
+ *                                 right eigenvectors vr [n*n]: unit columns; a pair's two columns hold real and imaginary part.
+ *                                 Returns 0, 1 (bad argument) or 2 (no convergence). */
+#define AFESP_EOM_CONVERGED 1
+#define AFESP_EOM_COMPLEX 2
+int afesp_ccsd_so_eom_init(afesp_ctx* ctx, int nroots, int max_space);
+int afesp_ccsd_so_eom_sigma(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* s1, double* s2);
+int afesp_ccsd_so_eom_guess(afesp_ctx* ctx);
+int afesp_ccsd_so_eom_set_guess(afesp_ctx* ctx, int k, const double* r1, const double* r2);
+int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged);
+int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2);
+int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr);
+
 /* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
  * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
  *   afesp_build_fock_uhf = fock_s = core_hamil + J[dens_a + dens_b] - K[dens_s] for s = a, b on the resident packed AO integrals
