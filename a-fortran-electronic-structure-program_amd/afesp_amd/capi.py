@@ -32,6 +32,8 @@ EXPORTS = [
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density",
     "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
     "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
+    "afesp_ccsd_so_eom_ipea_init", "afesp_ccsd_so_eom_ipea_sigma", "afesp_ccsd_so_eom_ipea_guess", "afesp_ccsd_so_eom_ipea_set_guess",
+    "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
@@ -124,6 +126,13 @@ def load_library():
     L.afesp_ccsd_so_eom_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.afesp_ccsd_so_eom_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_ipea_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.afesp_ccsd_so_eom_ipea_sigma.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+    L.afesp_ccsd_so_eom_ipea_guess.argtypes = [C.c_void_p, C.c_int]
+    L.afesp_ccsd_so_eom_ipea_set_guess.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_ipea_iterate.argtypes = [C.c_void_p, C.c_int, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_eom_ipea_get_vector.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     L.afesp_eig_general.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp]
     L.afesp_read_eri_text.argtypes = [C.c_void_p, C.c_char_p, i64, _opt, C.POINTER(i64)]
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
@@ -840,6 +849,57 @@ class Engine:
         r1, r2 = np.zeros(o * v), np.zeros(o * o * v * v)
         self._chk(self.L.afesp_ccsd_so_eom_get_vector(self.h, k, r1, r2))
         return r1.reshape((o, v), order="F"), r2.reshape((o, o, v, v), order="F")
+
+    # ---- EOM-IP-CCSD / EOM-EA-CCSD of the same state (include/afesp.h; afesp_amd.eom drives them).  sector: EOM_IP (1h + 2h1p:
+    # r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)); the rules and statuses are those of the EE calls above
+    EOM_IP, EOM_EA = 1, 2
+    eom_ipea_nroots = {}                                                    # sector -> nroots of its last so_eom_ipea_init
+
+    def so_eom_ipea_shapes(self, sector):
+        o, v = self.so_o, self.so_v
+        return ((o,), (o, o, v)) if sector == self.EOM_IP else ((v,), (o, v, v))
+
+    def so_eom_ipea_init(self, sector, nroots, max_space):
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_init(self.h, sector, nroots, max_space))
+        self.eom_ipea_nroots = {**self.eom_ipea_nroots, sector: int(nroots)}
+
+    def so_eom_ipea_sigma(self, sector, r1, r2):
+        """sigma = A r of the sector for one vector -> (s1, s2); with a leading axis, k vectors in one call -> the same with that axis."""
+        sh1, sh2 = self.so_eom_ipea_shapes(sector)
+        r1, r2 = np.asarray(r1, dtype=np.float64), np.asarray(r2, dtype=np.float64)
+        single = r1.ndim == 1
+        if single:
+            r1, r2 = r1[None], r2[None]
+        k = r1.shape[0]
+        if r1.shape != (k, *sh1) or r2.shape != (k, *sh2):
+            raise ValueError("so_eom_ipea_sigma: r1 / r2 do not have the shapes of this sector and state")
+        a1, a2 = np.concatenate([_f(x) for x in r1]), np.concatenate([_f(x) for x in r2])
+        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_sigma(self.h, sector, k, a1, a2, s1, s2))
+        s1 = s1.reshape(k, *sh1)
+        s2 = np.stack([x.reshape(sh2, order="F") for x in s2.reshape(k, -1)])
+        return (s1[0], s2[0]) if single else (s1, s2)
+
+    def so_eom_ipea_guess(self, sector):
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_guess(self.h, sector))
+
+    def so_eom_ipea_set_guess(self, sector, k, r1, r2):
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_set_guess(self.h, sector, k, _f(r1), _f(r2)))
+
+    def so_eom_ipea_iterate(self, sector, tol=1e-8):
+        """One Davidson step of the sector -> (omega, resnorm, flags, sigma builds so far, converged)"""
+        n = self.eom_ipea_nroots.get(sector, 1)
+        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        ns, cv = C.c_int(), C.c_int()
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_iterate(self.h, sector, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
+        return om, rs, fl, ns.value, bool(cv.value)
+
+    def so_eom_ipea_vector(self, sector, k):
+        """Ritz vector k of the sector's last step, <x, x> = sum x1^2 + 1/2 sum x2^2 = 1"""
+        sh1, sh2 = self.so_eom_ipea_shapes(sector)
+        r1, r2 = np.zeros(int(np.prod(sh1))), np.zeros(int(np.prod(sh2)))
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_get_vector(self.h, sector, k, r1, r2))
+        return r1, r2.reshape(sh2, order="F")
 
     def do_ccsd_t_spatial_plain(self, t_begin=0, t_end=None):
         """E[T], E(T) only: what plain CCSD(T)_spatial / CCSD[T]_spatial need (no y, no D sums)."""

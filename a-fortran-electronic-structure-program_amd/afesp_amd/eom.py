@@ -1,5 +1,6 @@
 """EOM-EE-CCSD excitation energies of a spin-orbital CCSD state: the Davidson driver over Engine.so_eom_* and the labelling of a root
-(host code).
+(host code); EOM-IP-CCSD ionisation potentials and EOM-EA-CCSD electron affinities of the same state over
+Engine.so_eom_ipea_* (so_eom_ip_solve, so_eom_ea_solve, label_ipea_root).
 
 The spin-orbital space holds every Ms component: a triplet appears threefold (Ms = 0 and the two spin-flip components Ms = +-1), a singlet
 once.  The driver reports the degeneracies and filters nothing."""
@@ -68,6 +69,72 @@ def label_root(x1, x2, nbasis, nalpha, nbeta, interleaved):
     return dict(kind="double", occ=(int(orb[i]), int(orb[j])), virt=(int(orb[a]), int(orb[b])), spins_occ=(int(spin[i]), int(spin[j])),
                 spins_virt=(int(spin[a]), int(spin[b])), delta_ms=float(ms(spin[a]) + ms(spin[b]) - ms(spin[i]) - ms(spin[j])),
                 weight=float(x2[i2] ** 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------- EOM-IP / EOM-EA
+SECTOR_IP, SECTOR_EA = 1, 2
+
+
+def ipea_nunique(sector, o, v):
+    """i, then (i < j, a) / a, then (i, a < b)"""
+    return o + (o * (o - 1) // 2) * v if sector == SECTOR_IP else v + o * (v * (v - 1) // 2)
+
+
+def _so_eom_ipea_solve(eng, sector, nroots, tol, max_space, maxiter, guesses):
+    if maxiter < 1:
+        raise ValueError("so_eom_ip_solve / so_eom_ea_solve: maxiter must be at least 1")
+    if max_space is None:
+        max_space = default_max_space(nroots, ipea_nunique(sector, eng.so_o, eng.so_v))
+    eng.so_eom_ipea_init(sector, nroots, max_space)
+    if guesses is None:
+        eng.so_eom_ipea_guess(sector)
+    else:
+        for k, (r1, r2) in enumerate(guesses):
+            eng.so_eom_ipea_set_guess(sector, k, r1, r2)
+    for it in range(1, maxiter + 1):
+        omega, res, flags, nsigma, conv = eng.so_eom_ipea_iterate(sector, tol)
+        if conv:
+            vectors = [eng.so_eom_ipea_vector(sector, k) for k in range(nroots)]
+            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
+                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
+                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
+                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
+            return omega, vectors, info
+    raise AfespError(f"the EOM-CCSD Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+
+
+def so_eom_ip_solve(eng, nroots, tol=1e-8, max_space=None, maxiter=100, guesses=None):
+    """The nroots lowest EOM-IP-CCSD ionisation potentials omega = E(N-1) - E(N) of the engine's spin-orbital state, as so_eom_solve finds
+    excitation energies: a live Lambda state is needed.  Vectors are (x1 (o,), x2 (o,o,v)) with sum x1^2 + 1/2 sum x2^2 = 1; r1_norm2 is the
+    one-hole weight.  The library's guesses carry a small admixture of every unique amplitude, so that a root in another Ms block or irreducible
+    representation than the smallest diagonal elements is found too.  Nothing is filtered: a closed-shell reference shows every doublet twofold (info["degeneracy"])."""
+    return _so_eom_ipea_solve(eng, SECTOR_IP, nroots, tol, max_space, maxiter, guesses)
+
+
+def so_eom_ea_solve(eng, nroots, tol=1e-8, max_space=None, maxiter=100, guesses=None):
+    """The nroots lowest EOM-EA-CCSD electron affinities omega = E(N+1) - E(N); vectors are (x1 (v,), x2 (o,v,v)).  See so_eom_ip_solve."""
+    return _so_eom_ipea_solve(eng, SECTOR_EA, nroots, tol, max_space, maxiter, guesses)
+
+
+def label_ipea_root(sector, x1, x2, nbasis, nalpha, nbeta, interleaved):
+    """The dominant amplitude of an IP or EA root: -> dict(kind "1h" / "2h1p" or "1p" / "2p1h", occ, virt (spatial orbital indices),
+    spins_occ, spins_virt (0 alpha, 1 beta), delta_ms, weight).  delta_ms = Ms(target) - Ms(reference): -+1/2 for the removal or the
+    attachment of an alpha / beta electron where the other amplitudes conserve spin."""
+    orb, spin = so_spin_order(nbasis, nalpha, nbeta, interleaved)
+    o = nalpha + nbeta
+    x1, x2 = np.asarray(x1), np.asarray(x2)
+    ms = lambda s: 0.5 - s
+    i1 = int(np.argmax(np.abs(x1)))
+    i2 = np.unravel_index(np.argmax(np.abs(x2)), x2.shape) if x2.size else None
+    if i2 is None or abs(x1[i1]) >= abs(x2[i2]):
+        occ, virt = ((i1,), ()) if sector == SECTOR_IP else ((), (i1 + o,))
+        kind, weight = ("1h" if sector == SECTOR_IP else "1p"), float(x1[i1] ** 2)
+    else:
+        occ, virt = ((int(i2[0]), int(i2[1])), (int(i2[2]) + o,)) if sector == SECTOR_IP else ((int(i2[0]),), (int(i2[1]) + o, int(i2[2]) + o))
+        kind, weight = ("2h1p" if sector == SECTOR_IP else "2p1h"), float(x2[i2] ** 2)
+    return dict(kind=kind, occ=tuple(int(orb[p]) for p in occ), virt=tuple(int(orb[p]) for p in virt),
+                spins_occ=tuple(int(spin[p]) for p in occ), spins_virt=tuple(int(spin[p]) for p in virt),
+                delta_ms=float(sum(ms(spin[p]) for p in virt) - sum(ms(spin[p]) for p in occ)), weight=weight)
 
 
 def table(omega, info):

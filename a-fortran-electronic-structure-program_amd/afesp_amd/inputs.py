@@ -45,6 +45,8 @@ class SystemIn:
     fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
     cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
+    eom_ip_nroots: int = 0          # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
+    eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -157,6 +159,12 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("eom_nroots must be a non-negative integer!")
     if sysin.eom_nroots > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
         raise ValueError(f"{sysin.calc_type} takes no eom_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!")
+    for key in ("eom_ip_nroots", "eom_ea_nroots"):
+        val = getattr(sysin, key)
+        if not isinstance(val, int) or isinstance(val, bool) or val < 0:
+            raise ValueError(f"{key} must be a non-negative integer!")
+        if val > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
+            raise ValueError(f"{sysin.calc_type} takes no {key}: the EOM-CCSD equations run on the spin-orbital CCSD types!")
     return sysin
 
 

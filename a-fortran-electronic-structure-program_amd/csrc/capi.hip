@@ -12,6 +12,7 @@
 #include "integrals.h"
 #include "solver.h"
 #include "eom_so.h"
+#include "eom_ipea_so.h"
 #include "small_eig.h"
 #include "comm.h"
 #include "tall.h"
@@ -671,6 +672,57 @@ int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2)
 }
 
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr) { return eig_general(n, a, lda, wr, wi, vr); }
+
+// ---- EOM-IP-CCSD and EOM-EA-CCSD (eom_ipea_so.h)
+static SOState& ipea_state(afesp_ctx* ctx, int sector, const char* who)
+{
+    if (!so_eom_sector_ok(sector)) throw Error(1, std::string(who) + ": sector must be AFESP_EOM_IP (1) or AFESP_EOM_EA (2)");
+    return ctx->sv.need_so((std::string(who) + ": no spin-orbital CCSD state").c_str()).so;
+}
+
+int afesp_ccsd_so_eom_ipea_init(afesp_ctx* ctx, int sector, int nroots, int max_space)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_ipea_init(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_init"), sector, nroots, max_space); });
+}
+
+int afesp_ccsd_so_eom_ipea_sigma(afesp_ctx* ctx, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_ipea_sigma_host(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_sigma"), sector, nvec, r1, r2, s1, s2);
+    });
+}
+
+int afesp_ccsd_so_eom_ipea_guess(afesp_ctx* ctx, int sector)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_ipea_guess(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_guess"), sector); });
+}
+
+int afesp_ccsd_so_eom_ipea_set_guess(afesp_ctx* ctx, int sector, int k, const double* r1, const double* r2)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_ipea_set_guess(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_set_guess"), sector, k, r1, r2); });
+}
+
+int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        SOState& so = ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_iterate");
+        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: tol must be positive");
+        const int conv = so_eom_ipea_iterate(cx, so, sector, tol);
+        const SOEomX& E = *so.ipea[sector - 1];
+        for (int k = 0; k < E.nroots; ++k) {
+            if (omega) omega[k] = E.omega[k];
+            if (resnorm) resnorm[k] = E.resnorm[k];
+            if (flags) flags[k] = E.flags[k];
+        }
+        if (nsigma) *nsigma = E.nsigma;
+        if (converged) *converged = conv;
+    });
+}
+
+int afesp_ccsd_so_eom_ipea_get_vector(afesp_ctx* ctx, int sector, int k, double* r1, double* r2)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_ipea_get_vector(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_get_vector"), sector, k, r1, r2); });
+}
 
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)nocc); }
 

@@ -9,6 +9,7 @@ namespace afesp {
 
 struct SOLambda;   // lambda_so.h
 struct SOEom;      // eom_so.h
+struct SOEomX;     // eom_ipea_so.h
 
 struct SOState : DiisRing {
     int o = 0, v = 0, n = 0;
@@ -37,6 +38,7 @@ struct SOState : DiisRing {
     double f_offdiag = 0.0;          // largest |f_oo|, |f_vv| off-diagonal element: (T) is defined for (semi)canonical orbitals only
     SOLambda* lam = nullptr;         // the Lambda state made by so_lambda_init for one amp_epoch (lambda_so.h); released by so_free
     SOEom* eom = nullptr;            // the EOM state that borrows lam's H-bar elements (eom_so.h); released wherever lam is
+    SOEomX* ipea[2] = {nullptr, nullptr};   // ... and those of the EOM-IP and EOM-EA sectors (eom_ipea_so.h), released with it
 };
 
 // eri_mo_dev: packed chemist MO integrals on the device (length neri(nbasis)); e_host: spatial orbital energies (host)
@@ -64,6 +66,7 @@ int so_energy(Context& cx, SOState& s, double e_tol, double t_tol);
 void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out);
 void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip (releases the EOM state too: it borrows from the Lambda state)
 void so_eom_free(Context& cx, SOState& s);        // eom_so.hip
+void so_eom_ipea_free(Context& cx, SOState& s);   // eom_ipea_so.hip
 // (T): contribution of the triples i<j<k with flat index in [t_begin, t_end) to E_T (ccsd.f90:1910)
 int64_t so_triples_count(int o);
 double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);

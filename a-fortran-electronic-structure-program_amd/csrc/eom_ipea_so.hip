@@ -1,0 +1,683 @@
+// eom_ipea_so.hip -- EOM-IP-CCSD and EOM-EA-CCSD on the spin-orbital CCSD state (eom_ipea_so.h): the sigma build of either
+// sector, term by term in the letters of tests/np_eom_ipea.py (ip_sigma_explicit, ea_sigma_explicit) over the H-bar elements of the live
+// Lambda state, and the block Davidson iteration of eom_so.hip on a vector described by (n1, n2, weight 1/2, a resident diagonal).
+// Launches are plain call-by-call ones.  Every reduction is block partials on a grid fixed by the vector length, then an ordered final
+// sum: the same input gives the same bits on every run.
+#include "device_util.h"
+#include "eom_ipea_so.h"
+#include "eom_so.h"
+#include "small_eig.h"
+#include "tall.h"
+
+#include <cmath>
+
+namespace afesp {
+namespace {
+
+constexpr int IPEA_MAXBLK = 128;   // blocks of a reduction (at most TB: ipea_final_kernel sums them in one block)
+constexpr int IPEA_RCHUNK = 8;     // roots one launch of the Ritz pass forms
+constexpr double IPEA_DROP = 1e-10, IPEA_CLAMP = 1e-4, IPEA_W2 = 0.5;
+constexpr double IPEA_SEED = 1e-3;   // weight of the guesses' admixture of every unique amplitude (ipea_unit_kernel)
+
+// the level of spin orbital p (occupied first) of either kind of state: lev of a UHF- or Fock-fed one, the spatial e of an RHF-fed one
+// (interleaved spins: so_denominators_kernel)
+__device__ __forceinline__ double ipea_level(const double* e, const double* lev, int o, int p)
+{
+    return lev ? lev[p] : (p < o ? e[p / 2] : e[(p - o) / 2 + o / 2]);
+}
+
+// The diagonal of a sector's matrix on full storage.  IP: -e_i, then -((e_i + e_j) - e_a); EA: e_a, then (e_a + e_b) - e_i.  The bracketed
+// sum is symmetric in the antisymmetric pair to the bit, so a product with an antisymmetric vector stays antisymmetric to the bit.
+__device__ __forceinline__ double ipea_diag(int sector, const double* e, const double* lev, int o, int v, int64_t x)
+{
+    if (sector == EOM_SECTOR_IP) {
+        if (x < o) return -ipea_level(e, lev, o, (int)x);
+        const int64_t y = x - o;
+        const int i = (int)(y % o), j = (int)((y / o) % o), a = (int)(y / ((int64_t)o * o));
+        return -__dadd_rn(__dadd_rn(ipea_level(e, lev, o, i), ipea_level(e, lev, o, j)), -ipea_level(e, lev, o, o + a));
+    }
+    if (x < v) return ipea_level(e, lev, o, o + (int)x);
+    const int64_t y = x - v;
+    const int i = (int)(y % o), a = (int)((y / o) % v), b = (int)(y / ((int64_t)o * v));
+    return __dadd_rn(__dadd_rn(ipea_level(e, lev, o, o + a), ipea_level(e, lev, o, o + b)), -ipea_level(e, lev, o, i));
+}
+
+__global__ void ipea_diag_kernel(double* diag, int sector, const double* e, const double* lev, int o, int v, int64_t nvec)
+{
+    GRID_STRIDE(x, nvec) diag[x] = ipea_diag(sector, e, lev, o, v, x);
+}
+
+// sigma of a sector from the carriers of its sigma build, one thread per element of [sigma1; sigma2]:
+//   IP   sigma2(i,j,a) = W + P(ij) A + diag r2      EA   sigma2(i,a,b) = W + P(ab) A + diag r2      sigma1 += diag r1
+// W is antisymmetric in the pair as a sum of products only up to rounding.  With c = 1/2 W + A the value is c(pair) - c(pair exchanged):
+// exchanging the pair negates it to the bit and it vanishes on the diagonal; diag is symmetric in the pair to the bit (ipea_diag).
+__global__ void ipea_assemble_kernel(double* s, const double* W, const double* A, const double* r, int sector, const double* e, const double* lev,
+                                     int o, int v)
+{
+    const bool ip = sector == EOM_SECTOR_IP;
+    const int64_t n1 = ip ? o : v, n2 = ip ? (int64_t)o * o * v : (int64_t)o * v * v;
+    GRID_STRIDE(x, n1 + n2)
+    {
+        const double d = ipea_diag(sector, e, lev, o, v, x);
+        if (x < n1) {
+            s[x] = __dadd_rn(s[x], __dmul_rn(d, r[x]));
+            continue;
+        }
+        const int64_t y = x - n1;
+        int64_t z;   // the image with the pair exchanged
+        if (ip) {
+            const int i = (int)(y % o), j = (int)((y / o) % o);
+            z = j + (int64_t)o * (i + (y / ((int64_t)o * o)) * o);
+        } else {
+            const int i = (int)(y % o), a = (int)((y / o) % v), b = (int)(y / ((int64_t)o * v));
+            z = i + (int64_t)o * (b + (int64_t)v * a);
+        }
+        const double cy = __dadd_rn(__dmul_rn(0.5, W[y]), A[y]), cz = __dadd_rn(__dmul_rn(0.5, W[z]), A[z]);
+        s[x] = __dadd_rn(__dadd_rn(cy, -cz), __dmul_rn(d, r[x]));
+    }
+}
+
+// pair index p = f (f - 1) / 2 + e of e < f, inverted
+__device__ __forceinline__ void ipea_unpair_lt(int64_t p, int& lo, int& hi)
+{
+    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
+    while (h * (h - 1) / 2 > p) --h;
+    while ((h + 1) * h / 2 <= p) ++h;
+    hi = (int)h;
+    lo = (int)(p - h * (h - 1) / 2);
+}
+// ra(i, ef) = r(i,e,f) for e < f, leading dimension na; rows o .. oa and pairs npv .. ka are written as zero (the product reads them)
+__global__ void ipea_ea_pack_kernel(double* ra, const double* r2, int o, int v, int64_t na, int64_t oa, int64_t ka)
+{
+    const int64_t npv = (int64_t)v * (v - 1) / 2;
+    GRID_STRIDE(x, oa * ka)
+    {
+        const int64_t i = x % oa, p = x / oa;
+        double val = 0.0;
+        if (i < o && p < npv) {
+            int e, f;
+            ipea_unpair_lt(p, e, f);
+            val = r2[i + (int64_t)o * (e + (int64_t)v * f)];
+        }
+        ra[i + na * p] = val;
+    }
+}
+// W(i,a,b) = +- pa(i, ab): + for a < b, - for b < a, 0 on the diagonal
+__global__ void ipea_ea_expand_kernel(double* W, const double* pa, int o, int v, int64_t na)
+{
+    GRID_STRIDE(x, (int64_t)o * v * v)
+    {
+        const int i = (int)(x % o), a = (int)((x / o) % v), b = (int)(x / ((int64_t)o * v));
+        double val = 0.0;
+        if (a != b) {
+            const int al = min(a, b), ah = max(a, b);
+            const double p = pa[i + na * ((int64_t)ah * (ah - 1) / 2 + al)];
+            val = a < b ? p : -p;
+        }
+        W[x] = val;
+    }
+}
+
+// ---- the Davidson kernels of eom_so.hip on a vector of n1 elements of weight 1 and nvec - n1 of weight IPEA_W2
+// The Gram panel of one vector pair (bq, sq) against ncol stored columns -- block (blk, p):
+//   p < ncol:  <b_p, sq>, <s_p, bq>, <b_p, bq>        p = ncol:  <bq, sq>, the same again, <bq, bq>
+// partial[(q (ncol + 1) + p) nblk + blk], q = 0, 1, 2.  sq null: the overlaps alone (q = 2; the others are written as zero).
+__global__ void ipea_panel_kernel(double* partial, const double* B, const double* S, int64_t stride, int ncol, const double* bq, const double* sq,
+                                  int64_t nvec, int64_t n1)
+{
+    __shared__ double sm[3 * 4];
+    const int p = blockIdx.y, nblk = gridDim.x;
+    const double* bp = p < ncol ? B + stride * p : bq;
+    const double* sp = sq ? (p < ncol ? S + stride * p : sq) : nullptr;
+    double acc[3] = {0.0, 0.0, 0.0};
+    GRID_STRIDE(x, nvec)
+    {
+        const double w = x < n1 ? 1.0 : IPEA_W2, b = bp[x], q = bq[x];
+        if (sp) {
+            acc[0] += w * b * sq[x];
+            acc[1] += w * sp[x] * q;
+        }
+        acc[2] += w * b * q;
+    }
+    block_sum<3>(acc, sm);
+    if (threadIdx.x == 0)
+        for (int q = 0; q < 3; ++q) partial[((int64_t)q * (ncol + 1) + p) * nblk + blockIdx.x] = acc[q];
+}
+
+// out[b] = the sum of partial[b nblk .. (b + 1) nblk) in a fixed order (nblk <= TB)
+__global__ void ipea_final_kernel(double* out, const double* partial, int nblk)
+{
+    __shared__ double red[TB];
+    red[threadIdx.x] = (int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0;
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// one projection pass: x -= sum_p coef[p] b_p, and the companion sx -= sum_p coef[p] s_p where given
+__global__ void ipea_project_kernel(double* x, double* sx, const double* B, const double* S, int64_t stride, int ncol, const double* coef, int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        double a = x[e], sa = sx ? sx[e] : 0.0;
+        for (int p = 0; p < ncol; ++p) {
+            const double c = coef[p];
+            a = __fma_rn(-c, B[stride * p + e], a);
+            if (sx) sa = __fma_rn(-c, S[stride * p + e], sa);
+        }
+        x[e] = a;
+        if (sx) sx[e] = sa;
+    }
+}
+
+__global__ void ipea_scale_kernel(double* dst, const double* src, double* dst2, const double* src2, double scale, int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        dst[e] = __dmul_rn(scale, src[e]);
+        if (src2) dst2[e] = __dmul_rn(scale, src2[e]);
+    }
+}
+
+// A guess: +1 at ip, -1 at im (negative index: none), and on every unique amplitude the admixture IPEA_SEED (frac((q + 1) phi) - 1/2)
+// with q the flat index of its i < j / a < b element and phi the golden ratio's fraction (the image carries the opposite sign, the
+// diagonal zero).  sigma couples neither different Ms nor different irreducible representations and a unit vector lies in one block of
+// each: without the admixture a wanted root in a block that holds none of the smallest diagonal elements -- the Ms = -+3/2 components of
+// a 2h1p quartet, a hole in an orbital of another symmetry -- is never found, or only when rounding noise has grown into it.
+__global__ void ipea_unit_kernel(double* x, int64_t nvec, int64_t ip, int64_t im, int sector, int o, int v)
+{
+    const int64_t n1 = sector == EOM_SECTOR_IP ? o : v;
+    GRID_STRIDE(e, nvec)
+    {
+        int64_t q = e;
+        double sign = 1.0;
+        if (e >= n1) {
+            const int64_t y = e - n1;
+            int64_t z;
+            if (sector == EOM_SECTOR_IP) z = (y / o) % o + (int64_t)o * (y % o + (y / ((int64_t)o * o)) * o);
+            else z = y % o + (int64_t)o * (y / ((int64_t)o * v) + (int64_t)v * ((y / o) % v));
+            sign = z == y ? 0.0 : (y < z ? 1.0 : -1.0);
+            q = n1 + (y < z ? y : z);
+        }
+        const double t = __dmul_rn((double)(q + 1), 0.6180339887498949);
+        const double seed = __dmul_rn(__dmul_rn(IPEA_SEED, sign), __dadd_rn(__dadd_rn(t, -floor(t)), -0.5));
+        x[e] = __dadd_rn(e == ip ? 1.0 : (e == im ? -1.0 : 0.0), seed);
+    }
+}
+
+// The Ritz pass for the roots k0 .. k0 + nr (nr <= IPEA_RCHUNK): every stored b_p and sigma_p is read once and gives
+//   x_k = sum_p y(p,k) b_p,  sx_k = sum_p y(p,k) sigma_p,  rho_k = sx_k - omega_k x_k,  corr_k = rho_k / (omega_k - diag)
+// (|omega_k - diag| clamped below at IPEA_CLAMP, keeping its sign) and the block partials of <rho_k, rho_k> at
+// partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.
+__global__ void ipea_ritz_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride, int nb,
+                                 const double* y, const double* omega, const double* diag, int64_t n1, int64_t nvec, int k0, int nr)
+{
+    __shared__ double sm[IPEA_RCHUNK * 4];
+    double nrm[IPEA_RCHUNK];
+#pragma unroll
+    for (int k = 0; k < IPEA_RCHUNK; ++k) nrm[k] = 0.0;
+    GRID_STRIDE(e, nvec)
+    {
+        double xa[IPEA_RCHUNK], sa[IPEA_RCHUNK];
+#pragma unroll
+        for (int k = 0; k < IPEA_RCHUNK; ++k) xa[k] = sa[k] = 0.0;
+        for (int p = 0; p < nb; ++p) {
+            const double b = B[stride * p + e], s = S[stride * p + e];
+#pragma unroll
+            for (int k = 0; k < IPEA_RCHUNK; ++k)
+                if (k < nr) {
+                    const double c = y[p + (int64_t)nb * (k0 + k)];
+                    xa[k] = __fma_rn(c, b, xa[k]);
+                    sa[k] = __fma_rn(c, s, sa[k]);
+                }
+        }
+        const double D = diag[e], w = e < n1 ? 1.0 : IPEA_W2;
+#pragma unroll
+        for (int k = 0; k < IPEA_RCHUNK; ++k)
+            if (k < nr) {
+                const double om = omega[k0 + k];
+                const double rho = __fma_rn(-om, xa[k], sa[k]);
+                double den = om - D;
+                if (fabs(den) < IPEA_CLAMP) den = den < 0.0 ? -IPEA_CLAMP : IPEA_CLAMP;
+                X[stride * (k0 + k) + e] = xa[k];
+                SX[stride * (k0 + k) + e] = sa[k];
+                corr[stride * (k0 + k) + e] = rho / den;
+                nrm[k] += w * rho * rho;
+            }
+    }
+    block_sum<IPEA_RCHUNK>(nrm, sm);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
+}
+
+const char* sector_name(int sector) { return sector == EOM_SECTOR_IP ? "EOM-IP" : "EOM-EA"; }
+
+void need_plain(Context& cx)
+{
+    if (cx.rec) throw Error(1, "so_eom_ipea: the EOM equations are not part of a recorded (launch-fused) sequence");
+}
+
+void sector_sizes(const SOState& s, int sector, int64_t* n1, int64_t* n2, int64_t* nunique)
+{
+    const int64_t O = s.o, V = s.v;
+    if (sector == EOM_SECTOR_IP) { *n1 = O; *n2 = O * O * V; *nunique = O + (O * (O - 1) / 2) * V; }
+    else { *n1 = V; *n2 = O * V * V; *nunique = V + O * (V * (V - 1) / 2); }
+}
+
+inline int ipea_nblk(int64_t nvec) { return (int)std::max<int64_t>(1, std::min<int64_t>((nvec + TB - 1) / TB, IPEA_MAXBLK)); }
+
+void read_back(Context& cx, double* host, const double* dev, int64_t n)
+{
+    AFESP_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+// the panel of (bq, sq) against the first ncol columns, summed: E.sums[q (ncol + 1) + p]
+void panel(Context& cx, SOEomX& E, int ncol, const double* bq, const double* sq)
+{
+    const int nblk = ipea_nblk(E.nvec);
+    LAUNCH(ipea_panel_kernel, dim3(nblk, ncol + 1), E.partial, E.B, E.S, E.nvec, ncol, bq, sq, E.nvec, E.n1);
+    LAUNCH(ipea_final_kernel, dim3(3 * (ncol + 1)), E.sums, E.partial, nblk);
+}
+
+// Two passes of projection of x (and its companion sx) against the first nb columns through the panel, then x / |x| -> column nb of B
+// (sx / |x| -> column nb of S).  -> false: the norm after projection is below IPEA_DROP, nothing was stored
+bool orthonormalise(Context& cx, SOEomX& E, double* x, double* sx)
+{
+    const int nb = E.nb;
+    if (nb > 0)
+        for (int pass = 0; pass < 2; ++pass) {
+            panel(cx, E, nb, x, nullptr);
+            LAUNCH(ipea_project_kernel, grid_for(E.nvec), x, sx, E.B, E.S, E.nvec, nb, E.sums + 2 * (nb + 1), E.nvec);
+        }
+    panel(cx, E, 0, x, nullptr);
+    double nrm2 = 0.0;
+    read_back(cx, &nrm2, E.sums + 2, 1);
+    const double nrm = std::sqrt(nrm2);
+    if (!(nrm >= IPEA_DROP)) return false;
+    LAUNCH(ipea_scale_kernel, grid_for(E.nvec), E.B + E.nvec * nb, x, sx ? E.S + E.nvec * nb : nullptr, sx, 1.0 / nrm, E.nvec);
+    return true;
+}
+
+// column nb of B and S is there: its row and column of the projected matrix, then nb + 1 columns
+void extend_projected(Context& cx, SOEomX& E)
+{
+    const int q = E.nb, ms = E.max_space;
+    panel(cx, E, q, E.B + E.nvec * q, E.S + E.nvec * q);
+    std::vector<double> h(3 * (q + 1));
+    read_back(cx, h.data(), E.sums, 3 * (q + 1));
+    for (int p = 0; p <= q; ++p) E.G[p + (size_t)ms * q] = h[p];
+    for (int p = 0; p < q; ++p) E.G[q + (size_t)ms * p] = h[(q + 1) + p];
+    E.nb = q + 1;
+}
+
+void free_one(Context& cx, SOState& s, int sector)
+{
+    SOEomX*& E = s.ipea[sector - 1];
+    if (!E) return;
+    double* bufs[] = {E->B, E->S, E->pend, E->x, E->sx, E->corr, E->partial, E->sums, E->coef, E->diag};
+    for (double* b : bufs) cx.release(b);
+    delete E;
+    E = nullptr;
+}
+
+void restart(SOEomX& E)
+{
+    E.nb = 0;
+    E.npend = 0;
+    E.ritz = false;
+    E.user_guess = false;
+    E.nsigma = E.ncollapse = 0;
+    std::fill(E.flags.begin(), E.flags.end(), 0);
+}
+
+// W(i,a,b) = sum_{e<f} <ab||ef> r(i,e,f) = 1/2 sum_ef: the bare ladder over the antisymmetric pair (e,f) against the pair-form va the T
+// iteration built at init, in that iteration's own pair buffers ta / pa and with its offset table -- r is packed as ra(i, ef) on ta's
+// leading dimension, a tall x skinny product M = K = v (v - 1) / 2, N = o.  That needs o <= o (o - 1) / 2, so that r fills rows of ta the T
+// iteration fills too and its zero padding stays zero: o >= 3.  A state with o = 2, or without va (o = 1: the T iteration has no pair of
+// occupied orbitals), contracts against <ab||ef> itself.
+void ea_ladder_bare(Context& cx, SOState& s, const Tensor& r2, const Tensor& W)
+{
+    const int o = s.o, v = s.v;
+    const int64_t V = v, npv = V * (V - 1) / 2, ka = s.lad_ka, na = s.lad_na, oa = (o + 1) & ~1;
+    if (npv == 0) {
+        k_fill(cx, W.d, W.size(), 0.0);
+        return;
+    }
+    if (!s.va || o > (int64_t)o * (o - 1) / 2) {
+        contract(cx, 0.5, r2, "ief", s.vvvv, "abef", 0.0, W, "iab");
+        return;
+    }
+    LAUNCH(ipea_ea_pack_kernel, grid_for(oa * ka), s.ta, r2.d, o, v, na, oa, ka);
+    const int64_t* t = s.lad_tab;
+    const int64_t kn = std::max(ka, na);
+    GettProblem gp;
+    gp.alpha = 1.0; gp.beta = 0.0;
+    gp.nbatch = 1; gp.batchA = gp.batchB = gp.batchC = nullptr;
+    gp.a_kcontig = true; gp.b_kcontig = false;
+    gp.wide = true;
+    gp.A = s.va; gp.B = s.ta; gp.C = s.pa;
+    gp.offAk = t; gp.offBn = gp.offCn = t;
+    gp.offAm = t + kn; gp.offBk = t + kn + npv; gp.offCm = t + kn + npv + ka;
+    gp.M = (int)npv; gp.N = (int)oa; gp.K = (int)ka;
+    const bool tall = tall_eligible(gp);   // the launcher's own choice, as contract() makes it
+    ++(tall ? cx.n_tall : cx.n_gett);
+    AFESP_HIP(tall ? tall_launch(gp, cx.stream) : gett_launch(gp, cx.ws, cx.stream));
+    LAUNCH(ipea_ea_expand_kernel, grid_for(W.size()), W.d, s.pa, o, v, na);
+}
+
+}  // namespace
+
+void preload_eom_ipea_so()
+{
+    first_use_touch(reinterpret_cast<const void*>(ipea_diag_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_panel_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_final_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_project_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_scale_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
+    first_use_touch(reinterpret_cast<const void*>(ipea_ritz_kernel));
+    (void)hipGetLastError();
+}
+
+static void preload_once()
+{
+    static const bool loaded = (preload_eom_ipea_so(), true);
+    (void)loaded;
+}
+
+double so_eom_ipea_bytes(int64_t o, int64_t v, int sector, int nroots, int max_space)
+{
+    const bool ip = sector == EOM_SECTOR_IP;
+    const double O = (double)o, V = (double)v;
+    const double n1 = ip ? O : V, n2 = ip ? O * O * V : O * V * V, nvec = n1 + n2;
+    // b_p and sigma_p; the pending vectors, the Ritz vectors, their sigma and the corrections; the diagonal; the reduction buffers; the
+    // scratch of a sigma build (W and the permutation carrier, y; EA: Z and the o^3 product) and the two staging vectors of the host entry
+    const double scratch = 2.0 * n2 + (ip ? V : O + O * V * O + O * O * O);
+    const double doubles = (2.0 * max_space + 4.0 * nroots + 1.0) * nvec + 3.0 * (max_space + 1.0) * (IPEA_MAXBLK + 1.0) +
+                           (double)nroots * (IPEA_MAXBLK + 2.0) + (double)max_space * nroots + scratch + 2.0 * nvec;
+    return 8.0 * doubles;
+}
+
+void so_eom_ipea_free(Context& cx, SOState& s)
+{
+    free_one(cx, s, EOM_SECTOR_IP);
+    free_one(cx, s, EOM_SECTOR_EA);
+}
+
+SOEomX& so_eom_ipea_need(SOState& s, int sector, const char* who)
+{
+    so_lambda_need(s, who);
+    SOEomX* E = s.ipea[sector - 1];
+    if (!E || E->epoch != s.amp_epoch)
+        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no " + sector_name(sector) +
+                                          " state for the live Lambda state (call afesp_ccsd_so_eom_ipea_init first)");
+    return *E;
+}
+
+void so_eom_ipea_init(Context& cx, SOState& s, int sector, int nroots, int max_space)
+{
+    need_plain(cx);
+    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ipea_init");
+    int64_t n1, n2, nunique;
+    sector_sizes(s, sector, &n1, &n2, &nunique);
+    const int64_t nvec = n1 + n2;
+    if (nroots < 1 || (int64_t)nroots > nunique)
+        throw Error(1, "afesp_ccsd_so_eom_ipea_init: nroots must be in 1 .. " + std::to_string(nunique) + " (the unique amplitudes of the " +
+                           sector_name(sector) + " sector)");
+    if ((int64_t)max_space < 2 * (int64_t)nroots || max_space > 4096)
+        throw Error(1, "afesp_ccsd_so_eom_ipea_init: max_space must be in 2 nroots .. 4096");
+    free_one(cx, s, sector);
+    if (!cx.fits(so_eom_ipea_bytes(s.o, s.v, sector, nroots, max_space)))
+        throw Error(1, std::string("afesp_ccsd_so_eom_ipea_init: the ") + sector_name(sector) + " state of this system (" + std::to_string(max_space) +
+                           " basis vectors) does not fit the free device memory");
+    preload_once();
+    s.ipea[sector - 1] = new SOEomX();
+    SOEomX& E = *s.ipea[sector - 1];
+    try {
+        E.sector = sector;
+        E.nroots = nroots;
+        E.max_space = max_space;
+        E.n1 = n1; E.n2 = n2; E.nvec = nvec;
+        E.B = cx.alloc(nvec * max_space);
+        E.S = cx.alloc(nvec * max_space);
+        E.pend = cx.alloc(nvec * nroots);
+        E.x = cx.alloc(nvec * nroots);
+        E.sx = cx.alloc(nvec * nroots);
+        E.corr = cx.alloc(nvec * nroots);
+        E.partial = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots) * IPEA_MAXBLK);
+        E.sums = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots));
+        E.coef = cx.alloc((int64_t)max_space * nroots + nroots);
+        E.diag = cx.alloc(nvec);
+        LAUNCH(ipea_diag_kernel, grid_for(nvec), E.diag, sector, s.e, s.lev, s.o, s.v, nvec);
+        E.G.assign((size_t)max_space * max_space, 0.0);
+        E.omega.assign(nroots, 0.0);
+        E.resnorm.assign(nroots, 0.0);
+        E.flags.assign(nroots, 0);
+        E.epoch = L.epoch;
+        cx.sync();
+    } catch (...) {
+        try { cx.quiesce(); free_one(cx, s, sector); } catch (...) {}
+        throw;
+    }
+}
+
+void so_eom_ipea_sigma(Context& cx, SOState& s, int sector, const double* r, double* sigma)
+{
+    need_plain(cx);
+    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ipea_sigma");
+    preload_once();
+    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
+                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const int o = s.o, v = s.v;
+    const int64_t O = o, V = v;
+    const Tensor &t1 = s.t1, &t2 = s.t2;
+    double* rr = const_cast<double*>(r);
+    if (sector == EOM_SECTOR_IP) {
+        const int64_t n2 = O * O * V;
+        const Tensor r1 = view(rr, {O}), r2 = view(rr + O, {O, O, V}), s1 = view(sigma, {O});
+        // ---- sigma1: -H_mi r_m - H_me r_ime + 1/2 H_mnie r_mne  (- e_i r_i: the assemble kernel)
+        C(-1.0, L.Hoo, "mi", r1, "m", 0.0, s1, "i");
+        C(-1.0, r2, "ime", L.Hov, "me", 1.0, s1, "i");
+        C(0.5, L.Hooov, "mnie", r2, "mne", 1.0, s1, "i");
+        // ---- y_e = 1/2 <mn||ef> r_mnf
+        Tensor y = view(cx.scratch("ipea_y", V), {V});
+        C(0.5, s.oovv, "mnef", r2, "mnf", 0.0, y, "e");
+        // ---- sigma2: W = 1/2 H_mnij r_mna + H_ae r_ije + H_maij r_m + y_e t_ijae;  P(ij) [ H_maej r_ime - H_mj r_ima ]
+        Tensor W = view(cx.scratch("ipea_W", n2), {O, O, V}), A = view(cx.scratch("ipea_A", n2), {O, O, V});
+        C(0.5, L.Hoooo, "mnij", r2, "mna", 0.0, W, "ija");
+        C(1.0, r2, "ije", L.Hvv, "ae", 1.0, W, "ija");
+        C(1.0, L.Hovoo, "maij", r1, "m", 1.0, W, "ija");
+        C(1.0, t2, "ijae", y, "e", 1.0, W, "ija");
+        C(1.0, r2, "ime", L.Hovvo, "maej", 0.0, A, "ija");
+        C(-1.0, r2, "ima", L.Hoo, "mj", 1.0, A, "ija");
+        LAUNCH(ipea_assemble_kernel, grid_for(O + n2), sigma, W.d, A.d, r, sector, s.e, s.lev, o, v);
+    } else {
+        const int64_t n2 = O * V * V;
+        const Tensor r1 = view(rr, {V}), r2 = view(rr + V, {O, V, V}), s1 = view(sigma, {V});
+        // ---- sigma1: H_ae r_e - H_me r_mae - 1/2 H_amef r_mef  (+ e_a r_a: the assemble kernel)
+        C(1.0, L.Hvv, "ae", r1, "e", 0.0, s1, "a");
+        C(-1.0, r2, "mae", L.Hov, "me", 1.0, s1, "a");
+        C(-0.5, L.Hvovv, "amef", r2, "mef", 1.0, s1, "a");
+        // ---- y_m = 1/2 <mn||ef> r_nef,  Z_iam = 1/2 r_ief <am||ef>,  Q_imn = r_ief <mn||ef>
+        Tensor y = view(cx.scratch("ipea_y", O), {O}), Z = view(cx.scratch("ipea_Z", O * V * O), {O, V, O});
+        Tensor Q = view(cx.scratch("ipea_Q", O * O * O), {O, O, O});
+        C(0.5, s.oovv, "mnef", r2, "nef", 0.0, y, "m");
+        C(0.5, r2, "ief", s.vovv, "amef", 0.0, Z, "iam");
+        C(1.0, r2, "ief", s.oovv, "mnef", 0.0, Q, "imn");
+        // ---- sigma2: W = bare ladder + 1/4 Q_imn tau_mnab + y_m t_imab - H_mi r_mab - H_abei r_e  (H_abei stored (i,e,a,b));
+        //      P(ab) [ -t_mb Z_iam + H_mbei r_mae + H_be r_iae ]
+        Tensor W = view(cx.scratch("ipea_W", n2), {O, V, V}), A = view(cx.scratch("ipea_A", n2), {O, V, V});
+        ea_ladder_bare(cx, s, r2, W);
+        C(0.25, Q, "imn", L.tau, "mnab", 1.0, W, "iab");
+        C(1.0, t2, "imab", y, "m", 1.0, W, "iab");
+        C(-1.0, L.Hoo, "mi", r2, "mab", 1.0, W, "iab");
+        C(-1.0, L.Hvvvo, "ieab", r1, "e", 1.0, W, "iab");
+        C(-1.0, Z, "iam", t1, "mb", 0.0, A, "iab");
+        C(1.0, r2, "mae", L.Hovvo, "mbei", 1.0, A, "iab");
+        C(1.0, r2, "iae", L.Hvv, "be", 1.0, A, "iab");
+        LAUNCH(ipea_assemble_kernel, grid_for(V + n2), sigma, W.d, A.d, r, sector, s.e, s.lev, o, v);
+    }
+}
+
+void so_eom_ipea_sigma_host(Context& cx, SOState& s, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+{
+    need_plain(cx);
+    so_lambda_need(s, "afesp_ccsd_so_eom_ipea_sigma");
+    if (nvec < 1 || !r1 || !r2 || !s1 || !s2) throw Error(1, "afesp_ccsd_so_eom_ipea_sigma: nvec < 1 or a NULL vector");
+    int64_t n1, n2, nunique;
+    sector_sizes(s, sector, &n1, &n2, &nunique);
+    double* r = cx.scratch("ipea_r_stage", n1 + n2);
+    double* sg = cx.scratch("ipea_s_stage", n1 + n2);
+    for (int k = 0; k < nvec; ++k) {
+        AFESP_HIP(hipMemcpyAsync(r, r1 + n1 * k, sizeof(double) * n1, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(r + n1, r2 + n2 * k, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        so_eom_ipea_sigma(cx, s, sector, r, sg);
+        AFESP_HIP(hipMemcpyAsync(s1 + n1 * k, sg, sizeof(double) * n1, hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(s2 + n2 * k, sg + n1, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    }
+}
+
+void so_eom_ipea_guess(Context& cx, SOState& s, int sector)
+{
+    need_plain(cx);
+    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_guess");
+    const int64_t O = s.o, V = s.v, n1 = E.n1;
+    std::vector<double> D(E.nvec);
+    read_back(cx, D.data(), E.diag, E.nvec);
+    // the unique amplitudes by ascending diagonal, ties by flat index
+    std::vector<int64_t> idx;
+    for (int64_t x = 0; x < n1; ++x) idx.push_back(x);
+    if (sector == EOM_SECTOR_IP) {
+        for (int64_t a = 0; a < V; ++a)
+            for (int64_t j = 0; j < O; ++j)
+                for (int64_t i = 0; i < j; ++i) idx.push_back(n1 + i + O * (j + O * a));
+    } else {
+        for (int64_t b = 0; b < V; ++b)
+            for (int64_t a = 0; a < b; ++a)
+                for (int64_t i = 0; i < O; ++i) idx.push_back(n1 + i + O * (a + V * b));
+    }
+    const int nr = E.nroots;
+    std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return D[p] != D[q] ? D[p] < D[q] : p < q; });
+    restart(E);
+    for (int k = 0; k < nr; ++k) {
+        const int64_t ip = idx[k];
+        int64_t im = -1;
+        if (ip >= n1) {
+            const int64_t y = ip - n1;
+            if (sector == EOM_SECTOR_IP) im = n1 + (y / O) % O + O * (y % O + O * (y / (O * O)));
+            else im = n1 + y % O + O * (y / (O * V) + V * ((y / O) % V));
+        }
+        LAUNCH(ipea_unit_kernel, grid_for(E.nvec), E.pend + E.nvec * k, E.nvec, ip, im, sector, s.o, s.v);
+    }
+    E.npend = nr;
+    cx.sync();
+}
+
+void so_eom_ipea_set_guess(Context& cx, SOState& s, int sector, int k, const double* r1, const double* r2)
+{
+    need_plain(cx);
+    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_set_guess");
+    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, "afesp_ccsd_so_eom_ipea_set_guess: k outside 0 .. nroots - 1, or a NULL vector");
+    if (E.nb > 0 || !E.user_guess) {   // the first of a block of the caller's guesses starts over: a running iteration, the unit guesses
+        restart(E);
+        k_fill(cx, E.pend, E.nvec * E.nroots, 0.0);   // (a column the caller leaves out stays zero and is dropped)
+        E.user_guess = true;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k, r1, sizeof(double) * E.n1, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k + E.n1, r2, sizeof(double) * E.n2, hipMemcpyHostToDevice, cx.stream));
+    cx.sync();
+    E.npend = std::max(E.npend, k + 1);
+}
+
+int so_eom_ipea_iterate(Context& cx, SOState& s, int sector, double tol)
+{
+    need_plain(cx);
+    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_iterate");
+    const int64_t nvec = E.nvec;
+    const int ms = E.max_space;
+    if (E.nb == 0 && E.npend == 0)
+        throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: no guess vectors (call afesp_ccsd_so_eom_ipea_guess or afesp_ccsd_so_eom_ipea_set_guess first)");
+    // ---- collapse: restart from the Ritz vectors, their sigma being the same combination of the stored sigma (no new sigma builds)
+    if (E.nb + E.npend > ms) {
+        const int nr = std::min(E.nroots, E.nb);
+        E.nb = 0;
+        for (int k = 0; k < nr; ++k)
+            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k)) extend_projected(cx, E);
+        ++E.ncollapse;
+    }
+    // ---- the pending vectors: orthonormalise, sigma, one more row and column of the projected matrix
+    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
+        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr)) continue;
+        so_eom_ipea_sigma(cx, s, sector, E.B + nvec * E.nb, E.S + nvec * E.nb);
+        ++E.nsigma;
+        extend_projected(cx, E);
+    }
+    E.npend = 0;
+    if (E.nb == 0) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: every guess vector vanished");
+    // ---- the projected problem on the host
+    const int nb = E.nb, nr = std::min(E.nroots, nb);
+    std::vector<double> g((size_t)nb * nb), wr(nb), wi(nb), vr((size_t)nb * nb), up((size_t)nb * nr + nr);
+    for (int q = 0; q < nb; ++q)
+        for (int p = 0; p < nb; ++p) g[p + (size_t)nb * q] = E.G[p + (size_t)ms * q];
+    const int rc = eig_general(nb, g.data(), nb, wr.data(), wi.data(), vr.data());
+    if (rc) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
+    for (int k = 0; k < nr; ++k) {
+        // a root with an imaginary part: the real part of its vector (the column of the pair's root with wi > 0)
+        const double* col = vr.data() + (size_t)nb * (wi[k] < 0.0 && k > 0 ? k - 1 : k);
+        double n2 = 0.0;
+        for (int p = 0; p < nb; ++p) n2 += col[p] * col[p];
+        const double sc = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;   // <x, x> = sum_p y_p^2: the basis is orthonormal
+        for (int p = 0; p < nb; ++p) up[p + (size_t)nb * k] = sc * col[p];
+        up[(size_t)nb * nr + k] = wr[k];
+        E.omega[k] = wr[k];
+        E.flags[k] = wi[k] != 0.0 ? EOM_FLAG_COMPLEX : 0;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
+    // ---- Ritz pass
+    const int nblk = ipea_nblk(nvec);
+    for (int k0 = 0; k0 < nr; k0 += IPEA_RCHUNK)
+        LAUNCH(ipea_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * nr, E.diag, E.n1, nvec, k0,
+               std::min(IPEA_RCHUNK, nr - k0));
+    LAUNCH(ipea_final_kernel, dim3(nr), E.sums, E.partial, nblk);
+    std::vector<double> nrm(nr);
+    read_back(cx, nrm.data(), E.sums, nr);   // (also: `up` is no longer read)
+    E.ritz = true;
+    int all = nr == E.nroots ? 1 : 0;
+    for (int k = 0; k < E.nroots; ++k) {
+        if (k >= nr) {   // fewer basis vectors than roots: not found (yet)
+            E.omega[k] = 0.0;
+            E.resnorm[k] = HUGE_VAL;
+            E.flags[k] = 0;
+            continue;
+        }
+        E.resnorm[k] = std::sqrt(nrm[k]);
+        if (E.resnorm[k] < tol) E.flags[k] |= EOM_FLAG_CONVERGED;
+        else {
+            all = 0;
+            k_copy(cx, E.pend + nvec * E.npend, E.corr + nvec * k, nvec);
+            ++E.npend;
+        }
+    }
+    return all;
+}
+
+void so_eom_ipea_get_vector(Context& cx, SOState& s, int sector, int k, double* r1, double* r2)
+{
+    need_plain(cx);
+    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_get_vector");
+    if (!E.ritz || k < 0 || k >= std::min(E.nroots, E.nb) || !r1 || !r2)
+        throw Error(1, "afesp_ccsd_so_eom_ipea_get_vector: no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
+    AFESP_HIP(hipMemcpyAsync(r1, E.x + E.nvec * k, sizeof(double) * E.n1, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(r2, E.x + E.nvec * k + E.n1, sizeof(double) * E.n2, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+}  // namespace afesp

@@ -195,6 +195,7 @@ double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr)
 void so_lambda_free(Context& cx, SOState& s)
 {
     so_eom_free(cx, s);   // (it borrows this state's H-bar elements)
+    so_eom_ipea_free(cx, s);
     if (!s.lam) return;
     free_buffers(cx, *s.lam);
     delete s.lam;

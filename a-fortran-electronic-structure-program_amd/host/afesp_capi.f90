@@ -19,9 +19,12 @@ module afesp_capi
              afesp_ccsd_so_density, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
              afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
+             afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
+             afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
+   integer(c_int), parameter :: AFESP_EOM_IP = 1, AFESP_EOM_EA = 2   ! the sector of the afesp_ccsd_so_eom_ipea_* calls
 
    interface
       function afesp_ctx_create(device, ctx) bind(C, name='afesp_ctx_create') result(rc)
@@ -469,6 +472,51 @@ module afesp_capi
          import :: c_int, c_double, c_ptr
          type(c_ptr), value :: ctx
          integer(c_int), value :: k
+         real(c_double), intent(out) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      ! EOM-IP-CCSD / EOM-EA-CCSD: the same calls with a sector (AFESP_EOM_IP, AFESP_EOM_EA) behind the context (include/afesp.h)
+      function afesp_ccsd_so_eom_ipea_init(ctx, sector, nroots, max_space) bind(C, name='afesp_ccsd_so_eom_ipea_init') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nroots, max_space
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_sigma(ctx, sector, nvec, r1, r2, s1, s2) bind(C, name='afesp_ccsd_so_eom_ipea_sigma') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nvec
+         real(c_double), intent(in) :: r1(*), r2(*)
+         real(c_double), intent(out) :: s1(*), s2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_guess(ctx, sector) bind(C, name='afesp_ccsd_so_eom_ipea_guess') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_set_guess(ctx, sector, k, r1, r2) bind(C, name='afesp_ccsd_so_eom_ipea_set_guess') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, k
+         real(c_double), intent(in) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_iterate(ctx, sector, tol, omega, resnorm, flags, nsigma, converged) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector
+         real(c_double), value :: tol
+         real(c_double), intent(out) :: omega(*), resnorm(*)
+         integer(c_int), intent(out) :: flags(*), nsigma, converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_get_vector(ctx, sector, k, r1, r2) bind(C, name='afesp_ccsd_so_eom_ipea_get_vector') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, k
          real(c_double), intent(out) :: r1(*), r2(*)
          integer(c_int) :: rc
       end function

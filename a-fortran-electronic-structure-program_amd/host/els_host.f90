@@ -55,6 +55,8 @@ module host_config
       logical :: cc_density = .false.
       ! after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (0: off)
       integer :: eom_nroots = 0
+      ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
+      integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -63,13 +65,13 @@ contains
       character(40) :: calc_type
       real(dp) :: scf_e_tol, scf_d_tol, ccsd_e_tol, ccsd_t_tol
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
-      integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots
+      integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, eom_nroots
+         cc_density, eom_nroots, eom_ip_nroots, eom_ea_nroots
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -79,6 +81,7 @@ contains
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
+      eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -141,6 +144,13 @@ contains
       if (eom_nroots < 0) call fail('system::read_system_in', 'eom_nroots must be a non-negative integer!')
       if (eom_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
          trim(calc_type)//' takes no eom_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
+      cfg%eom_ip_nroots = eom_ip_nroots; cfg%eom_ea_nroots = eom_ea_nroots
+      if (eom_ip_nroots < 0) call fail('system::read_system_in', 'eom_ip_nroots must be a non-negative integer!')
+      if (eom_ea_nroots < 0) call fail('system::read_system_in', 'eom_ea_nroots must be a non-negative integer!')
+      if (eom_ip_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no eom_ip_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
+      if (eom_ea_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no eom_ea_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
       if (cfg%rohf) then   ! no ROHF SCF here: the orbitals come from a file, and a frozen core reaches this path as an active-space file
          if (.not. fcidump_in) call fail('system::read_system_in', trim(calc_type)// &
             ' needs fcidump_in = .true.: there is no ROHF SCF, the restricted open-shell orbitals come from a FCIDUMP!')
@@ -918,6 +928,8 @@ program els_amd
             call lambda_and_occupations(n_act, na_act, nb_act, .false.)
          end if
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
+         if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
+         if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
@@ -1019,6 +1031,8 @@ program els_amd
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD:', seconds() - t0, 's'
          if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
+         if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
+         if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, nel_act, 2*n_act - nel_act)
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             ! ---------------- spin-orbital (T) (reference do_ccsd_t_spinorb, src/ccsd.f90:1812-1922)
             t0 = seconds()
@@ -1411,6 +1425,69 @@ contains
       end do
       write (out, '(75("-"))')
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for EOM-CCSD:', seconds() - te, 's'
+   end subroutine
+   !> eom_ip_nroots / eom_ea_nroots: the lowest EOM-IP-CCSD ionisation potentials (1h + 2h1p) or EOM-EA-CCSD electron affinities (1p + 2p1h) of the
+   !> converged spin-orbital CCSD state, after Lambda and EOM-EE where those were asked for.  The H-bar elements are those of the Lambda
+   !> state they left, else of one made here.  Nothing is filtered: a closed-shell reference shows every doublet twofold.
+   subroutine eom_ipea(sector, nr, o, v)
+      integer(c_int), intent(in) :: sector
+      integer, intent(in) :: nr, o, v
+      real(dp), parameter :: hartree_ev = 27.211386245988_dp, eom_tol = 1.0e-8_dp
+      real(dp), allocatable :: omega(:), res(:), x1(:), x2(:), w1(:)
+      integer(c_int), allocatable :: flags(:)
+      integer(c_int) :: nsig, econv
+      integer :: ms, it, k
+      integer(c_int64_t) :: o8, v8, nunique, n1, n2
+      real(dp) :: te
+      logical :: ok
+      character(6) :: what
+      te = seconds()
+      what = merge('EOM-IP', 'EOM-EA', sector == AFESP_EOM_IP)
+      write (out, '(1X, 11("-"))'); write (out, '(1X, A)') what//'-CCSD'; write (out, '(1X, 11("-"))')
+      o8 = int(o, c_int64_t); v8 = int(v, c_int64_t)
+      if (sector == AFESP_EOM_IP) then
+         n1 = o8; n2 = o8*o8*v8; nunique = o8 + (o8*(o8 - 1)/2)*v8
+      else
+         n1 = v8; n2 = o8*v8*v8; nunique = v8 + o8*(v8*(v8 - 1)/2)
+      end if
+      ms = max(2*nr, int(min(nunique, int(8*nr, c_int64_t))))
+      if (.not. cfg%cc_density .and. cfg%eom_nroots <= 0 .and. .not. (sector == AFESP_EOM_EA .and. cfg%eom_ip_nroots > 0)) then
+         rc = afesp_ccsd_so_lambda_init(ctx, 0_c_int)
+         if (rc /= 0) call fail('eom_ipea::init_hbar', afesp_error_text(ctx))
+      end if
+      rc = afesp_ccsd_so_eom_ipea_init(ctx, sector, int(nr, c_int), int(ms, c_int))
+      if (rc /= 0) call fail('eom_ipea::init_eom', afesp_error_text(ctx))
+      rc = afesp_ccsd_so_eom_ipea_guess(ctx, sector)
+      if (rc /= 0) call fail('eom_ipea::guess', afesp_error_text(ctx))
+      allocate (omega(nr), res(nr), flags(nr), w1(nr), x1(n1), x2(n2))
+      ok = .false.
+      do it = 1, 100
+         rc = afesp_ccsd_so_eom_ipea_iterate(ctx, sector, eom_tol, omega, res, flags, nsig, econv)
+         if (rc /= 0) call fail('eom_ipea::davidson_step', afesp_error_text(ctx))
+         if (econv /= 0) then
+            ok = .true.
+            exit
+         end if
+      end do
+      if (.not. ok) call fail('eom_ipea::do_eom', 'the '//what//'-CCSD Davidson iteration did not converge!')
+      do k = 1, nr
+         rc = afesp_ccsd_so_eom_ipea_get_vector(ctx, sector, int(k - 1, c_int), x1, x2)
+         if (rc /= 0) call fail('eom_ipea::get_vector', afesp_error_text(ctx))
+         w1(k) = sum(x1*x1)
+      end do
+      write (out, '(1X, A, 1X, I0, A, I0, A, I0, A)') 'Davidson steps:', it, ', sigma builds: ', nsig, ', at most ', ms, ' basis vectors'
+      write (out, '(75("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Root', '  omega (Hartree) ', '    omega (eV)    ', '  |r1|^2  ', ' Residual '
+      write (out, '(75("-"))')
+      do k = 1, nr
+         if (iand(flags(k), 2_c_int) /= 0) then
+            write (out, '(1X, I4, 3X, F18.12, 3X, F18.10, 3X, F10.8, 3X, ES10.3, 1X, A)') k, omega(k), omega(k)*hartree_ev, w1(k), res(k), 'complex'
+         else
+            write (out, '(1X, I4, 3X, F18.12, 3X, F18.10, 3X, F10.8, 3X, ES10.3)') k, omega(k), omega(k)*hartree_ev, w1(k), res(k)
+         end if
+      end do
+      write (out, '(75("-"))')
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//what//'-CCSD:', seconds() - te, 's'
    end subroutine
    subroutine print_fno_cut(asked, kept_occ, dropped_occ, any_dropped)
       integer, intent(in) :: asked

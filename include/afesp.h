@@ -256,6 +256,26 @@ int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double*
 int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2);
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr);
 
+/* EOM-IP-CCSD and EOM-EA-CCSD on the same state: ionisation potentials omega = E(N-1) - E(N) in the 1h + 2h1p sector,
+ * r1(nocc), r2(nocc,nocc,nvirt) antisymmetric in its first two indices, and electron affinities omega = E(N+1) - E(N) in the 1p + 2p1h
+ * sector, r1(nvirt), r2(nocc,nvirt,nvirt) antisymmetric in its last two.  <x, y> = sum x1 y1 + 1/2 sum x2 y2; the unique amplitudes are
+ * i, then (i < j, a) / a, then (i, a < b).  `sector` is AFESP_EOM_IP or AFESP_EOM_EA (status 1 otherwise).  The calls are those of the
+ * EE sector above with the same rules and statuses, one Davidson state per sector beside the EE one: status 21 without a live Lambda
+ * state or with a stale one, and from _iterate, _guess, _set_guess and _get_vector without an _init of that sector; _sigma needs the
+ * Lambda state only.  None writes t1 / t2, lambda, the epoch or the EE state.  One rule differs: the vectors of _guess are the unit vectors
+ * on the nroots smallest diagonal elements, each with a fixed 1e-3 admixture of every unique amplitude, because sigma couples neither
+ * different Ms nor different irreducible representations and a wanted root may lie in a block that holds none of those elements.  nroots is at most the number of unique amplitudes (with
+ * one occupied spin orbital the IP sector has no doubles: nocc). */
+#define AFESP_EOM_IP 1
+#define AFESP_EOM_EA 2
+int afesp_ccsd_so_eom_ipea_init(afesp_ctx* ctx, int sector, int nroots, int max_space);
+int afesp_ccsd_so_eom_ipea_sigma(afesp_ctx* ctx, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2);
+int afesp_ccsd_so_eom_ipea_guess(afesp_ctx* ctx, int sector);
+int afesp_ccsd_so_eom_ipea_set_guess(afesp_ctx* ctx, int sector, int k, const double* r1, const double* r2);
+int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma,
+                                   int* converged);
+int afesp_ccsd_so_eom_ipea_get_vector(afesp_ctx* ctx, int sector, int k, double* r1, double* r2);
+
 /* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
  * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
  *   afesp_build_fock_uhf = fock_s = core_hamil + J[dens_a + dens_b] - K[dens_s] for s = a, b on the resident packed AO integrals
