@@ -29,7 +29,7 @@ EXPORTS = [
     "afesp_ccsd_so_init", "afesp_ccsd_so_energy", "afesp_ccsd_so_iterate", "afesp_ccsd_so_diis", "afesp_ccsd_so_get_amplitudes",
     "afesp_ccsd_so_set_amplitudes", "afesp_ccsd_so_get_tensor", "afesp_ccsd_so_t_ntriples", "afesp_ccsd_so_t",
     "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
-    "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density",
+    "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density", "afesp_ccsd_so_lambda_t",
     "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
     "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
     "afesp_ccsd_so_eom_ipea_init", "afesp_ccsd_so_eom_ipea_sigma", "afesp_ccsd_so_eom_ipea_guess", "afesp_ccsd_so_eom_ipea_set_guess",
@@ -119,6 +119,7 @@ def load_library():
     L.afesp_ccsd_so_get_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_set_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_density.argtypes = [C.c_void_p, _dp, i64]
+    L.afesp_ccsd_so_lambda_t.argtypes = [C.c_void_p, i64, i64, C.POINTER(dbl)]
     L.afesp_ccsd_so_eom_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_sigma.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_guess.argtypes = [C.c_void_p]
@@ -802,6 +803,15 @@ class Engine:
         buf = np.zeros(n * n)
         self._chk(self.L.afesp_ccsd_so_density(self.h, buf, buf.size if capacity is None else capacity))
         return buf.reshape((n, n), order="F")
+
+    def so_lambda_t(self, t_begin=0, t_end=None):
+        """Lambda-CCSD(T): the triples [t_begin, t_end) of do_ccsd_t_spinorb's list with l1 / l2 in the left factor, at the current t and l
+        (needs a live Lambda state: status 21 otherwise).  Writes no amplitude of either kind."""
+        if t_end is None:
+            t_end = self.so_ntriples()
+        e = dbl()
+        self._chk(self.L.afesp_ccsd_so_lambda_t(self.h, t_begin, t_end, C.byref(e)))
+        return e.value
 
     # ---- EOM-EE-CCSD excitation energies of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them).  All need a live Lambda
     # state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes t1 / t2 or lambda

@@ -27,6 +27,20 @@ def so_lambda_solve(eng, maxiter=100, e_tol=1e-8, l_tol=1e-8, diis_nerr=8):
     raise AfespError(f"the Lambda equations did not converge in {maxiter} iterations")
 
 
+def so_lambda_t_correction(eng, t_begin=0, t_end=None, maxiter=100, e_tol=1e-8, l_tol=1e-8, diis_nerr=8):
+    """Lambda-CCSD(T) beside (T) for the triples [t_begin, t_end) of the engine's list (default: all) -> (e_lt, e_t).  A live Lambda state
+    of the current amplitudes is used as it stands (the caller converged it, or set it); without one the Lambda equations are solved
+    first (so_lambda_solve with the given limits)."""
+    try:
+        e_lt = eng.so_lambda_t(t_begin, t_end)
+    except AfespError as err:
+        if not str(err).startswith("status 21:"):   # (AFESP_LAMBDA_STALE: no Lambda state, or t1 / t2 changed since its init)
+            raise
+        so_lambda_solve(eng, maxiter, e_tol, l_tol, diis_nerr)
+        e_lt = eng.so_lambda_t(t_begin, t_end)
+    return e_lt, eng.do_ccsd_t_spinorb(t_begin, t_end)
+
+
 def so_spin_order(nbasis, nalpha, nbeta, interleaved):
     """(spatial orbital, spin) of every spin orbital of a state, in its own order"""
     n = int(nbasis)

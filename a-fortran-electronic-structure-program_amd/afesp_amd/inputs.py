@@ -44,6 +44,7 @@ class SystemIn:
     fno_n_virt: int = -1            # number of natural virtuals kept; -1 = off
     fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
     cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
+    cc_lambda_t: bool = False       # after a converged spin-orbital CCSD: Lambda and the Lambda-CCSD(T) correction (density.so_lambda_t_correction)
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
     eom_ip_nroots: int = 0          # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
@@ -155,6 +156,10 @@ def read_els_in(path: str) -> SystemIn:
     if sysin.cc_density and sysin.fcidump_in and sysin.calc_type in OPEN_SHELL_TYPES:
         raise ValueError("cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the "
                          "spin-summed density needs!")
+    if not isinstance(sysin.cc_lambda_t, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.cc_lambda_t and sysin.calc_type not in CC_DENSITY_TYPES:   # (no orbital overlap needed: a UHF FCIDUMP takes it)
+        raise ValueError(f"{sysin.calc_type} takes no cc_lambda_t: the Lambda equations run on the spin-orbital CCSD types!")
     if not isinstance(sysin.eom_nroots, int) or isinstance(sysin.eom_nroots, bool) or sysin.eom_nroots < 0:
         raise ValueError("eom_nroots must be a non-negative integer!")
     if sysin.eom_nroots > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
@@ -311,6 +316,8 @@ _ENERGY_LINES = {
     "UMP2 correlation energy": "ump2_corr",
     "UCCSD correlation energy": "uccsd_corr",
     "UCCSD(T) correlation energy": "uccsd_pt_corr",
+    "ΛCCSD(T) correlation energy": "lambda_ccsd_pt_corr",       # cc_lambda_t (the host's own lines, as the open-shell ones above)
+    "UΛCCSD(T) correlation energy": "lambda_uccsd_pt_corr",
     "Nuclear repulsion": "e_nuc",
     "Total energy": "total",
 }

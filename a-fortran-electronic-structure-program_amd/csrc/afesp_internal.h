@@ -167,6 +167,11 @@ struct Context {
     const void* t_ops_owner = nullptr;
     int64_t t_ops_amp = -1, t_ops_scratch = -1, t_ops_cr = -1;
     bool t_ops_ts = false;
+    // the same record for the Lambda-side operand copies lt_vt / lt_tt of Lambda-(T) (so_lambda_triples): the state, the stamp of the
+    // Lambda amplitudes they were built from (SOLambda::stamp, drawn from lam_clock by every writer of l1 / l2) and the scratch epoch
+    int64_t lam_clock = 0;
+    const void* lt_ops_owner = nullptr;
+    int64_t lt_ops_stamp = -1, lt_ops_scratch = -1;
     Tensor tensor(std::initializer_list<int64_t> dims);
     void sync();
     void quiesce();                       // every lane and the main stream idle (before memory returns to the arena, after an error)

@@ -734,6 +734,14 @@ int afesp_ccsd_so_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_t)
     });
 }
 
+int afesp_ccsd_so_lambda_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_lt)
+{
+    return entry(ctx, [&](Context& cx) {
+        const double e = so_lambda_triples(cx, ctx->sv.so, t_begin, t_end);
+        if (e_lt) *e_lt = e;
+    });
+}
+
 // ---------------------------------------------------------------- open-shell (UHF-based) path
 int afesp_build_fock_uhf(afesp_ctx* ctx, int64_t nbasis, const double* dens_a, const double* dens_b, const double* core_hamil,
                          double* fock_a, double* fock_b)

@@ -14,6 +14,7 @@ constexpr int LAMBDA_ERR_CAPACITY = 22;   // so_density: the caller's buffer is 
 
 struct SOLambda : DiisRing {   // amp = [l1 ; l2]
     int64_t epoch = -1;        // SOState::amp_epoch the intermediates were built for
+    int64_t stamp = -1;        // ++Context::lam_clock by whoever writes l1 / l2 (init, iterate, diis, set_lambda): what copies of them go by
     Tensor l1, l2, x1, x2, l2_old;
     Tensor tau;                // of the t1 / t2 of `epoch` (the state's own tau is that of its last so_intermediates)
     // lambda-independent H-bar elements; Hoo / Hvv without the diagonal of f (the denominators)
@@ -40,6 +41,8 @@ void so_lambda_energy(Context& cx, SOState& s);
 int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol);   // the host read of either and the convergence rule
 // the symmetrised correlation part of the unrelaxed one-particle density, (o+v)^2 column-major in the state's spin-orbital order
 void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity);
+// Lambda-CCSD(T): the triples [t_begin, t_end) of so_triples' own list with l1 / l2 in the left factor (triples.hip)
+double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);
 void preload_lambda_so();
 
 }  // namespace afesp

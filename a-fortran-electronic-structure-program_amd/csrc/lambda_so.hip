@@ -185,10 +185,11 @@ double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr)
 {
     const double O = (double)o, V = (double)v, o2v2 = O * O * V * V, nvec = O * V + o2v2;
     // [l1; l2], X, l2_old, tau, Hovvo and the DIIS ring; the two- and four-index H-bar elements; the scratch of the build and of an
-    // iteration (AB, A, B, q, Zv / ring operand, p1, p2, Lt, two o^4)
+    // iteration (AB, A, B, q, Zv / ring operand, p1, p2, Lt, two o^4); the Lambda-side operand pair of Lambda-(T) (lt_vt / lt_tt, as
+    // so_state_bytes counts vt / tt -- its second block pool is checked where it is allocated, so_lambda_triples)
     const double doubles = (2.0 + (diis_nerr >= 2 ? 1.0 + 2.0 * diis_nerr : 0.0)) * nvec + 3.0 * o2v2 + 2.0 * (O * V + O * O + V * V) +
                            O * O * O * O + 2.0 * O * V * V * V + 2.0 * O * O * O * V + 5.0 * o2v2 + O * V * V * V + 2.0 * O * O * O * V +
-                           2.0 * O * O * O * O;
+                           2.0 * O * O * O * O + (V + O + 16) * (V * V * O + V * O * O);
     return 8.0 * doubles;
 }
 
@@ -316,6 +317,7 @@ void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
         k_copy(cx, L.amp, s.amp, L.nvec);
         L.pseudo = L.pseudo_old = L.rms = 0.0;
         L.epoch = s.amp_epoch;
+        L.stamp = ++cx.lam_clock;
         cx.sync();
     } catch (...) {
         try { cx.quiesce(); so_lambda_free(cx, s); } catch (...) {}
@@ -332,6 +334,7 @@ void so_lambda_iterate(Context& cx, SOState& s)
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
     const Tensor &l1 = L.l1, &l2 = L.l2;
+    L.stamp = ++cx.lam_clock;
     diis_save(cx, L);
     build_G(cx, s, L);
     // ---- l1: H_ia + l_ie H_ea - l_ma H_im + l_me H_ieam + 1/2 l_imef H_efam - 1/2 l_mnae H_iemn - G_ef H_eifa - G_mn H_mina

@@ -82,7 +82,12 @@ struct Solver {
     void so_lambda_begin(Context& cx, int diis_nerr) { so_lambda_init(cx, so, diis_nerr); }
     StepResult so_lambda_step(Context& cx, double e_tol, double l_tol) { so_lambda_iterate(cx, so); return so_lambda_result(cx, e_tol, l_tol); }
     StepResult so_lambda_energy_step(Context& cx, double e_tol, double l_tol) { so_lambda_energy(cx, so); return so_lambda_result(cx, e_tol, l_tol); }
-    void so_lambda_diis(Context& cx) { diis_update(cx, so_lambda_need(so, "afesp_ccsd_so_lambda_diis")); }
+    void so_lambda_diis(Context& cx)
+    {
+        SOLambda& L = so_lambda_need(so, "afesp_ccsd_so_lambda_diis");
+        L.stamp = ++cx.lam_clock;
+        diis_update(cx, L);
+    }
     void so_get_lambda(Context& cx, double* l1, double* l2);
     void so_set_lambda(Context& cx, const double* l1, const double* l2);
 

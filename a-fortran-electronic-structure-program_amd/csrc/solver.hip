@@ -416,6 +416,7 @@ void Solver::so_get_lambda(Context& cx, double* l1, double* l2)
 void Solver::so_set_lambda(Context& cx, const double* l1, const double* l2)
 {
     SOLambda& L = so_lambda_need(so, "afesp_ccsd_so_set_lambda");
+    L.stamp = ++cx.lam_clock;
     if (l1) AFESP_HIP(hipMemcpyAsync(L.l1.d, l1, sizeof(double) * L.l1.size(), hipMemcpyHostToDevice, cx.stream));
     if (l2) AFESP_HIP(hipMemcpyAsync(L.l2.d, l2, sizeof(double) * L.l2.size(), hipMemcpyHostToDevice, cx.stream));
     cx.sync();

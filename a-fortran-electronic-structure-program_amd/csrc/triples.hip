@@ -25,6 +25,7 @@
 
 #include "ccsd.h"
 #include "ccsd_so.h"
+#include "lambda_so.h"
 #include "tgemm.h"
 #include "triples_orbit.h"
 
@@ -300,6 +301,7 @@ static std::vector<int64_t> assemble_pool(Context& cx, int64_t nblocks, int64_t 
 }
 
 static bool fused_use_tg(int o, int v);
+static int64_t device_pool_budget();
 
 // Plan of the spin-orbital (T): i<j<k, three blocks per triple; one tgemm_kernel launch per chunk (or, under AFESP_T_GEMM=gett, one
 // gather-GEMM launch per integral slab and chunk).
@@ -307,13 +309,14 @@ static TriplesPlan* plan_for(Context& cx, void*& slot, int o, int v, int64_t t_b
 {
     TriplesPlan* p = (TriplesPlan*)slot;
     if (p && p->o == o && p->v == v && p->t_begin == t_begin && p->t_end == t_end && p->mode == 1 && p->epoch == cx.scratch_epoch &&
-        p->use_tg == (fused_use_tg(o, v) && (((int64_t)v + o + 15) / 16 * 16) >= 2 * TG_BK))
+        p->use_tg == (fused_use_tg(o, v) && (((int64_t)v + o + 15) / 16 * 16) >= 2 * TG_BK) && p->k_pool_gib == knobs().t_pool_gib)
         return p;
     delete p;
     p = new TriplesPlan();
     slot = p;
     const int64_t O = o, V = v, Kc = (V + O + 15) / 16 * 16;   // padded, see ccsd_triples
     p->o = o; p->v = v; p->t_begin = t_begin; p->t_end = t_end; p->cr = false; p->mode = 1;
+    p->k_pool_gib = knobs().t_pool_gib;
     // the products of this path on the LDS-DMA kernel too (tgemm.h): K-contiguous operands, one run of the summation index per group
     p->use_tg = fused_use_tg(o, v) && Kc >= 2 * TG_BK;
     p->c_pairs = (v % 2) == 0;
@@ -324,10 +327,10 @@ static TriplesPlan* plan_for(Context& cx, void*& slot, int o, int v, int64_t t_b
     const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;   // a block is stored cube by cube, edges padded to 8
     const int64_t per = 3 * vp3 * (int64_t)sizeof(double);
     // pool budget: a quarter of the device memory, at most 64 GiB (MI355X: 288 GB -> 64 GiB, ~165 triples per chunk at
-    // v = 200): the more triples share an integral slab, the wider each GEMM and the smaller its ragged last round
-    size_t mem_free = 0, mem_total = 0;
-    AFESP_HIP(hipMemGetInfo(&mem_free, &mem_total));
-    const int64_t budget = std::min<int64_t>((int64_t)64 << 30, (int64_t)(mem_total / 4));
+    // v = 200): the more triples share an integral slab, the wider each GEMM and the smaller its ragged last round.  The tuning knob
+    // AFESP_T_POOL_GIB replaces the budget here as on the spin-free path (0: a chunk per triple); the chunking moves no triple of the
+    // list.  Lambda-(T) runs this plan with a second pool of the same size: two budgets, at most half the device (so_lambda_triples).
+    const int64_t budget = device_pool_budget();
     int64_t nb = std::max<int64_t>(1, budget / per);
     nb = std::min<int64_t>(nb, 4096);
     nb = std::min<int64_t>(nb, std::max<int64_t>(1, t_end - t_begin));
@@ -1107,13 +1110,164 @@ __global__ void so_levels_kernel(double* e_so, const double* e, int n2)
     if (x < n2) e_so[x] = e[x / 2];
 }
 
-double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
+// afesp_profile on the spin-orbital drivers: three events per chunk (before the products, between them and the orbit pass, after it), read
+// once the call's result is on the host; adds to Context::prof_gemm_ms / prof_orbit_ms as the spin-free driver does.  Nothing without it.
+struct SOStamps {
+    Context& cx;
+    std::vector<hipEvent_t> evs;
+    explicit SOStamps(Context& c) : cx(c) {}
+    void stamp()
+    {
+        if (!cx.prof) return;
+        hipEvent_t e;
+        AFESP_HIP(hipEventCreate(&e));
+        AFESP_HIP(hipEventRecord(e, cx.stream));
+        evs.push_back(e);
+    }
+    void read()
+    {
+        if (!evs.empty()) AFESP_HIP(hipEventSynchronize(evs.back()));
+        for (size_t q = 0; q + 2 < evs.size(); q += 3) {
+            float a = 0.f, b = 0.f;
+            AFESP_HIP(hipEventElapsedTime(&a, evs[q], evs[q + 1]));
+            AFESP_HIP(hipEventElapsedTime(&b, evs[q + 1], evs[q + 2]));
+            cx.prof_gemm_ms += a;
+            cx.prof_orbit_ms += b;
+            cx.prof_gemm_launches += 1;
+            cx.prof_orbit_launches += 1;
+        }
+    }
+    ~SOStamps() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); }
+};
+
+// The t-side operand copies of the spin-orbital (T) in the cached buffers t_vt / t_tt / t_vs / t_eso, rebuilt only when the record
+// Context::t_ops_* does not name this state, its amplitude epoch and the scratch epoch (shared by so_triples and so_lambda_triples).
+struct SOTOperands { Tensor vt, tt, vs; double* e_so; };
+static Tensor rows_of(const Tensor& full, int64_t row0, int64_t nrows)
 {
-    if (!s.ready) throw Error(1, "ccsd_so_triples: no converged spin-orbital CCSD state in this context");
+    Tensor t = full;
+    t.d = full.d + row0;
+    t.dim[0] = nrows;
+    return t;
+}
+static SOTOperands so_t_operands(Context& cx, SOState& s)
+{
+    const int64_t O = s.o, V = s.v, v2 = V * V;
+    const int64_t Kc = (V + O + 15) / 16 * 16;
+    Tensor vt = view(cx.scratch("t_vt", Kc * v2 * O), {Kc, V, V, O}), tt = view(cx.scratch("t_tt", Kc * V * O * O), {Kc, V, O, O});
+    Tensor vs = view(cx.scratch("t_vs", v2 * O * O), {V, V, O, O});    // vs(x,y,p,q) = <pq||xy>
+    double* e_so = cx.scratch("t_eso", O + V);
+    // The operand copies depend on the amplitudes only: a call on unchanged amplitudes -- the next shard of the same (T), a timed
+    // repetition -- finds them in the cached buffers (as the spin-free path does) instead of five permuting passes, two memsets and a
+    // round trip of the orbital energies through the host with two stream synchronisations (round 4: every call).
+    const bool ops_valid = cx.t_ops_owner == (const void*)&s && cx.t_ops_amp == s.amp_epoch && cx.t_ops_scratch == cx.scratch_epoch;
+    if (!ops_valid) {
+        if (Kc != V + O) {
+            AFESP_HIP(hipMemsetAsync(vt.d, 0, sizeof(double) * Kc * v2 * O, cx.stream));
+            AFESP_HIP(hipMemsetAsync(tt.d, 0, sizeof(double) * Kc * V * O * O, cx.stream));
+        }
+        permute_add(cx, 1.0, s.vovv, "fpbc", 0.0, rows_of(vt, 0, V), "fbcp");
+        permute_add(cx, 1.0, s.t2, "mpcb", 0.0, rows_of(vt, V, O), "mbcp");
+        permute_add(cx, 1.0, s.t2, "qraf", 0.0, rows_of(tt, 0, V), "farq");
+        permute_add(cx, -1.0, s.ovoo, "maqr", 0.0, rows_of(tt, V, O), "marq");
+        permute_add(cx, 1.0, s.oovv, "pqxy", 0.0, vs, "xypq");
+        if (!s.lev) {   // (a UHF-fed state carries its spin-orbital levels itself)
+            AFESP_KLAUNCH(so_levels_kernel, dim3((unsigned)((O + V + 255) / 256)), dim3(256), 0, cx.stream, e_so, s.e, (int)(O + V));
+            AFESP_HIP(hipGetLastError());
+        }
+    }
+    cx.t_ops_owner = (const void*)&s;
+    cx.t_ops_amp = s.amp_epoch;
+    cx.t_ops_scratch = cx.scratch_epoch;
+    cx.t_ops_ts = false;
+    cx.t_ops_cr = -1;
+    return {vt, tt, vs, e_so};
+}
+
+// The GEMM launches of one chunk of the spin-orbital plan: X(b,c; a,block) = sum_kappa vt(kappa,b,c,r) tt(kappa,a,q,p) into `pool`
+static void so_chunk_products(Context& cx, const TriplesPlan* p, const TriplesPlan::Chunk& ch, const Tensor& vt, const Tensor& tt, double* pool)
+{
+    const int64_t O = p->o, V = p->v, v2 = V * V, Kc = (V + O + 15) / 16 * 16;
+    const int64_t* tabs = p->tables + ch.tab_off;
+    if (p->use_tg) {
+        TgProblem tp{vt.d, tt.d, pool, p->tables32, p->tables + p->off_Cm, (int)v2, p->c_pairs, (int)((V + O - (Kc - TG_BK) + 3) / 4)};
+        AFESP_HIP(tgemm_launch(tp, p->tgdesc + ch.tg_off, ch.tg_ngroups, ch.tg_tiles, ch.tg_max_ntiles, cx.stream, cx.tg));
+        return;
+    }
+    for (const TriplesPlan::Group& g : ch.groups) {
+        GettProblem gp;
+        gp.A = vt.d + Kc * v2 * g.r;
+        gp.B = tt.d;
+        gp.C = pool;
+        gp.offAm = p->tables + p->off_Am; gp.offAk = p->tables + p->off_k; gp.offBk = p->tables + p->off_k;
+        gp.offBn = tabs + g.start;
+        gp.offCm = p->tables + p->off_Cm; gp.offCn = tabs + ch.ntab + g.start;
+        gp.M = (int)v2; gp.N = (int)g.N; gp.K = (int)Kc;
+        gp.alpha = 1.0; gp.beta = 0.0;
+        gp.nbatch = 1; gp.batchA = gp.batchB = gp.batchC = nullptr;
+        gp.a_kcontig = gp.b_kcontig = true;
+        gp.wide = true;   // (as in the spin-free plan: K-contiguous operands, Kc a multiple of 16)
+        AFESP_HIP(gett_launch(gp, cx.ws, cx.stream));
+    }
+}
+
+static void so_triples_guard(const SOState& s, const char* who)
+{
+    if (!s.ready) throw Error(1, std::string(who) + ": no converged spin-orbital CCSD state in this context");
     // (T) is defined in (semi)canonical orbitals only: a guard, not a tolerance
     if (s.fock && s.f_offdiag > 1e-8)
-        throw Error(1, "ccsd_so_triples: the occupied-occupied / virtual-virtual Fock blocks of this state are not diagonal (largest off-diagonal "
+        throw Error(1, std::string(who) + ": the occupied-occupied / virtual-virtual Fock blocks of this state are not diagonal (largest off-diagonal "
                        "element " + std::to_string(s.f_offdiag) + "): (T) needs semicanonical orbitals");
+}
+
+double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
+{
+    so_triples_guard(s, "ccsd_so_triples");
+    const int o = s.o, v = s.v;
+    const int64_t V = v;
+    const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;
+    t_begin = std::max<int64_t>(0, t_begin);
+    t_end = std::min<int64_t>(so_triples_count(o), t_end);
+    k_fill(cx, cx.scal, 1, 0.0);
+    if (t_end <= t_begin) return 0.0;
+    TriplesPlan* p = plan_for(cx, s.tplan, o, v, t_begin, t_end);
+    const SOTOperands ops = so_t_operands(cx, s);
+    TriplesIn in{s.lev ? s.lev : ops.e_so, s.t1.d, ops.vs.d, s.fock ? s.f_ov.d : nullptr, s.t2.d, o, v};   // (f_ov in the slot this path leaves free)
+    double* Xpool = cx.scratch("t_xpool", 3 * p->nb * vp3);
+    double* partial = cx.scratch("t_partial", std::max<int64_t>((int64_t)p->norb * p->nb, 512));
+    SOStamps prof(cx);
+    for (const TriplesPlan::Chunk& ch : p->chunks) {
+        prof.stamp();
+        so_chunk_products(cx, p, ch, ops.vt, ops.tt, Xpool);
+        prof.stamp();
+        if (s.fock)
+            AFESP_KLAUNCH((triples_so_orbit_kernel<true>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+                               p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
+        else
+            AFESP_KLAUNCH((triples_so_orbit_kernel<false>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+                               p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
+        AFESP_HIP(hipGetLastError());
+        prof.stamp();
+        // (two stages, 128 blocks first: one block walking the 67 200 partials of the H2O/cc-pVTZ shape took 0.10 ms of a 2.8 ms evaluation)
+        sum_partials(cx, cx.scal, partial, 1, p->norb * ch.nt, cx.scratch("t_sum_tmp", 6 * 128));
+    }
+    double* h = host_scalars(cx, 1);
+    prof.read();
+    return h[0];
+}
+
+// Lambda-CCSD(T): so_triples with the left factor of every triple taken from the Lambda state.  The plan, the t-side
+// operands and the first pool are so_triples' own; the Lambda side is a second operand pair under names of its own,
+//   lt_vt(kappa,b,c,p):  kappa<v: vovv(f,p,b,c);   kappa=v+m: l2(m,p,c,b)
+//   lt_tt(kappa,a,r,q):  kappa<v: l2(q,r,a,f);     kappa=v+m: -ovoo(m,a,q,r)
+// kept across calls under Context::lt_ops_* (state, SOLambda::stamp, scratch epoch), and a second pool lt_xpool of the same 3 nb vp3
+// doubles that every chunk's launches fill a second time.  Nothing of the state, of the Lambda state or of cx's other records is written.
+double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
+{
+    if (cx.rec) throw Error(1, "afesp_ccsd_so_lambda_t: Lambda-(T) is not part of a recorded (launch-fused) sequence");
+    if (!s.ready) throw Error(1, "afesp_ccsd_so_lambda_t: no converged spin-orbital CCSD state in this context");
+    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_lambda_t");
+    so_triples_guard(s, "afesp_ccsd_so_lambda_t");
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, v2 = V * V;
     const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;
@@ -1123,74 +1277,58 @@ double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end)
     k_fill(cx, cx.scal, 1, 0.0);
     if (t_end <= t_begin) return 0.0;
     TriplesPlan* p = plan_for(cx, s.tplan, o, v, t_begin, t_end);
-    Tensor vt = view(cx.scratch("t_vt", Kc * v2 * O), {Kc, V, V, O}), tt = view(cx.scratch("t_tt", Kc * V * O * O), {Kc, V, O, O});
-    Tensor vs = view(cx.scratch("t_vs", v2 * O * O), {V, V, O, O});    // vs(x,y,p,q) = <pq||xy>
-    double* e_so = cx.scratch("t_eso", O + V);
-    // The operand copies depend on the amplitudes only: a call on unchanged amplitudes -- the next shard of the same (T), a timed
-    // repetition -- finds them in the cached buffers (as the spin-free path does) instead of five permuting passes, two memsets and a
-    // round trip of the orbital energies through the host with two stream synchronisations (round 4: every call).
-    const bool ops_valid = cx.t_ops_owner == (const void*)&s && cx.t_ops_amp == s.amp_epoch && cx.t_ops_scratch == cx.scratch_epoch;
-    if (!ops_valid) {
-    auto sub = [&](const Tensor& full, int64_t row0, int64_t nrows) {
-        Tensor t = full;
-        t.d = full.d + row0;
-        t.dim[0] = nrows;
-        return t;
-    };
-    if (Kc != V + O) {
-        AFESP_HIP(hipMemsetAsync(vt.d, 0, sizeof(double) * Kc * v2 * O, cx.stream));
-        AFESP_HIP(hipMemsetAsync(tt.d, 0, sizeof(double) * Kc * V * O * O, cx.stream));
+    if (knobs().t_debug)
+        fprintf(stderr, "afesp Lambda-(T): o %d v %d triples %lld per chunk %lld chunks %zu kernel %s\n", o, v, (long long)(t_end - t_begin),
+                (long long)p->nb, p->chunks.size(), p->use_tg ? "tgemm" : "gett");
+    // the second pool is the one allocation of this call that grows with the plan: refuse it rather than fail inside the allocator
+    {
+        auto it = cx.cache.find("lt_xpool");
+        const size_t want = (size_t)(3 * p->nb * vp3) * sizeof(double);
+        if ((it == cx.cache.end() || it->second.second < want) && !cx.fits((double)want))
+            throw Error(1, "afesp_ccsd_so_lambda_t: the second block pool of Lambda-(T) does not fit the free device memory (lower AFESP_T_POOL_GIB)");
     }
-    permute_add(cx, 1.0, s.vovv, "fpbc", 0.0, sub(vt, 0, V), "fbcp");
-    permute_add(cx, 1.0, s.t2, "mpcb", 0.0, sub(vt, V, O), "mbcp");
-    permute_add(cx, 1.0, s.t2, "qraf", 0.0, sub(tt, 0, V), "farq");
-    permute_add(cx, -1.0, s.ovoo, "maqr", 0.0, sub(tt, V, O), "marq");
-    permute_add(cx, 1.0, s.oovv, "pqxy", 0.0, vs, "xypq");
-    if (!s.lev) {   // (a UHF-fed state carries its spin-orbital levels itself)
-        AFESP_KLAUNCH(so_levels_kernel, dim3((unsigned)((O + V + 255) / 256)), dim3(256), 0, cx.stream, e_so, s.e, (int)(O + V));
-        AFESP_HIP(hipGetLastError());
-    }
-    }
-    cx.t_ops_owner = (const void*)&s;
-    cx.t_ops_amp = s.amp_epoch;
-    cx.t_ops_scratch = cx.scratch_epoch;
-    cx.t_ops_ts = false;
-    cx.t_ops_cr = -1;
-    TriplesIn in{s.lev ? s.lev : e_so, s.t1.d, vs.d, s.fock ? s.f_ov.d : nullptr, s.t2.d, o, v};   // (f_ov in the slot this path leaves free)
+    // every cached buffer first: a buffer that grows bumps the scratch epoch, which the two records below are compared with
     double* Xpool = cx.scratch("t_xpool", 3 * p->nb * vp3);
+    double* Lpool = cx.scratch("lt_xpool", 3 * p->nb * vp3);
     double* partial = cx.scratch("t_partial", std::max<int64_t>((int64_t)p->norb * p->nb, 512));
-    for (const TriplesPlan::Chunk& ch : p->chunks) {
-        const int64_t* tabs = p->tables + ch.tab_off;
-        if (p->use_tg) {
-            TgProblem tp{vt.d, tt.d, Xpool, p->tables32, p->tables + p->off_Cm, (int)v2, p->c_pairs, (int)((V + O - (Kc - TG_BK) + 3) / 4)};
-            AFESP_HIP(tgemm_launch(tp, p->tgdesc + ch.tg_off, ch.tg_ngroups, ch.tg_tiles, ch.tg_max_ntiles, cx.stream, cx.tg));
-        } else
-        for (const TriplesPlan::Group& g : ch.groups) {
-            GettProblem gp;
-            gp.A = vt.d + Kc * v2 * g.r;
-            gp.B = tt.d;
-            gp.C = Xpool;
-            gp.offAm = p->tables + p->off_Am; gp.offAk = p->tables + p->off_k; gp.offBk = p->tables + p->off_k;
-            gp.offBn = tabs + g.start;
-            gp.offCm = p->tables + p->off_Cm; gp.offCn = tabs + ch.ntab + g.start;
-            gp.M = (int)v2; gp.N = (int)g.N; gp.K = (int)Kc;
-            gp.alpha = 1.0; gp.beta = 0.0;
-            gp.nbatch = 1; gp.batchA = gp.batchB = gp.batchC = nullptr;
-            gp.a_kcontig = gp.b_kcontig = true;
-            gp.wide = true;   // (as in the spin-free plan: K-contiguous operands, Kc a multiple of 16)
-            AFESP_HIP(gett_launch(gp, cx.ws, cx.stream));
+    double* sum_tmp = cx.scratch("t_sum_tmp", 6 * 128);
+    Tensor lvt = view(cx.scratch("lt_vt", Kc * v2 * O), {Kc, V, V, O}), ltt = view(cx.scratch("lt_tt", Kc * V * O * O), {Kc, V, O, O});
+    p = plan_for(cx, s.tplan, o, v, t_begin, t_end);   // (its tables live in cached buffers too)
+    const SOTOperands ops = so_t_operands(cx, s);
+    const bool l_valid = cx.lt_ops_owner == (const void*)&s && cx.lt_ops_stamp == L.stamp && cx.lt_ops_scratch == cx.scratch_epoch;
+    if (!l_valid) {
+        if (Kc != V + O) {
+            AFESP_HIP(hipMemsetAsync(lvt.d, 0, sizeof(double) * Kc * v2 * O, cx.stream));
+            AFESP_HIP(hipMemsetAsync(ltt.d, 0, sizeof(double) * Kc * V * O * O, cx.stream));
         }
+        permute_add(cx, 1.0, s.vovv, "fpbc", 0.0, rows_of(lvt, 0, V), "fbcp");
+        permute_add(cx, 1.0, L.l2, "mpcb", 0.0, rows_of(lvt, V, O), "mbcp");
+        permute_add(cx, 1.0, L.l2, "qraf", 0.0, rows_of(ltt, 0, V), "farq");
+        permute_add(cx, -1.0, s.ovoo, "maqr", 0.0, rows_of(ltt, V, O), "marq");
+    }
+    cx.lt_ops_owner = (const void*)&s;
+    cx.lt_ops_stamp = L.stamp;
+    cx.lt_ops_scratch = cx.scratch_epoch;
+    // l1 / l2 where the (T) kernel reads t1 / t2 (the right factor is the connected part alone), f_ov in the free slot
+    TriplesIn in{s.lev ? s.lev : ops.e_so, L.l1.d, ops.vs.d, s.fock ? s.f_ov.d : nullptr, L.l2.d, o, v};
+    SOStamps prof(cx);
+    for (const TriplesPlan::Chunk& ch : p->chunks) {
+        prof.stamp();
+        so_chunk_products(cx, p, ch, ops.vt, ops.tt, Xpool);
+        so_chunk_products(cx, p, ch, lvt, ltt, Lpool);
+        prof.stamp();
         if (s.fock)
-            AFESP_KLAUNCH((triples_so_orbit_kernel<true>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+            AFESP_KLAUNCH((triples_so_lambda_orbit_kernel<true>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool, Lpool,
                                p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
         else
-            AFESP_KLAUNCH((triples_so_orbit_kernel<false>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool,
+            AFESP_KLAUNCH((triples_so_lambda_orbit_kernel<false>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Xpool, Lpool,
                                p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt);
         AFESP_HIP(hipGetLastError());
-        // (two stages, 128 blocks first: one block walking the 67 200 partials of the H2O/cc-pVTZ shape took 0.10 ms of a 2.8 ms evaluation)
-        sum_partials(cx, cx.scal, partial, 1, p->norb * ch.nt, cx.scratch("t_sum_tmp", 6 * 128));
+        prof.stamp();
+        sum_partials(cx, cx.scal, partial, 1, p->norb * ch.nt, sum_tmp);
     }
     double* h = host_scalars(cx, 1);
+    prof.read();
     return h[0];
 }
 
@@ -1205,6 +1343,8 @@ void preload_triples()
     first_use_touch(reinterpret_cast<const void*>(triples_orbit_kernel<false, true, true>));
     first_use_touch(reinterpret_cast<const void*>(triples_orbit_kernel<true, true, true>));
     first_use_touch(reinterpret_cast<const void*>(triples_so_orbit_kernel<true>));
+    first_use_touch(reinterpret_cast<const void*>(triples_so_lambda_orbit_kernel<true>));
+    first_use_touch(reinterpret_cast<const void*>(triples_so_lambda_orbit_kernel<false>));
     (void)hipGetLastError();
     preload_tgemm();
 }

@@ -505,4 +505,169 @@ __global__ __launch_bounds__(256, 3) void triples_so_orbit_kernel(double* __rest
     if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) / (6.0 * nH);
 }
 
+// Lambda-CCSD(T) (Kucharski and Bartlett 1998; Crawford and Stanton 1998): the left factor of the spin-orbital (T)
+// taken from the left-hand CCSD state.  Two pools of the same layout: Xpool as above (from t2), Lpool the same three blocks with l2 in
+// place of t2 (triples.hip, so_lambda_triples).  With R_x = Y_x^{i;jk} - Y_x^{j;ik} + Y_x^{k;ij} and
+//   L = R_l + l1(i,a)<jk||bc> - l1(j,a)<ik||bc> + l1(k,a)<ij||bc>  [+ f(i,a) l2(jk,bc) - f(j,a) l2(ik,bc) + f(k,a) l2(ij,bc)]
+//   E_LT += P(L) P(R_t) / D / 6,   P(y) = y(abc) - y(bac) - y(cba).
+// P is self-adjoint over the six images a thread owns and P(R_t) is antisymmetric under every exchange, so P P(R_t) = 3 P(R_t):
+//   sum_q P(L)[q] P(R_t)[q] = 3 sum_q L[q] P(R_t)[q]     -- the left side is never permuted.
+// The LDS of the (T) kernel serves both pools in turn: R_t is staged, every thread keeps P(R_t) at its twelve elements in registers,
+// and after a barrier the same cubes are restaged with R_l (whose loads were issued before the first barrier's readers started).
+// `in` carries l1 and l2 where the (T) kernel has t1 and t2 -- the right factor is the connected part alone and needs neither.
+template <bool FOCK>
+__global__ __launch_bounds__(256, 3) void triples_so_lambda_orbit_kernel(double* __restrict__ partial, const double* __restrict__ Xpool,
+                                                                        const double* __restrict__ Lpool,
+                                                                        const TripleMeta* __restrict__ meta,
+                                                                        const int* __restrict__ orbits, TriplesIn in, int nblk_total)
+{
+    __shared__ __attribute__((aligned(16))) double wl[6 * CUBE];   // R_t, then R_l, on the six cubes of the orbit
+    __shared__ double vp[27 * PATCH];                              // <pq||xy> patches for pairs (j,k), (i,k), (i,j)
+    __shared__ double tp[FOCK ? 27 * PATCH : 1];                   // l2(p,q,x,y) patches for the same pairs
+    __shared__ double fr[FOCK ? 72 : 1];                           // fr[occ][slot][l] = f_ov(occ, tile[slot]*8 + l)
+    __shared__ double t1r[96];                                     // l1 rows as t1r of the (T) kernel; then evl
+    __shared__ int srcq[6][6];
+    __shared__ double red[4];
+    const TripleMeta m = meta[blockIdx.y];
+    const int o = in.o, v = in.v, t = threadIdx.x;
+    const int packed = orbits[blockIdx.x];
+    const int tile[3] = {packed & 1023, (packed >> 10) & 1023, (packed >> 20) & 1023};
+    if (t < 36) {
+        const int s = t / 6, q = t % 6;
+        int want[3];
+        for (int d = 0; d < 3; ++d) want[d] = tile[sig(q, sig(s, d))];
+        int found = 0;
+        for (int r = 5; r >= 0; --r)
+            if (tile[sig(r, 0)] == want[0] && tile[sig(r, 1)] == want[1] && tile[sig(r, 2)] == want[2]) found = r;
+        srcq[s][q] = found;
+    }
+    const int64_t vv = (int64_t)v * v;
+    const int nt8 = (v + TT - 1) / TT;
+    const int p0 = (2 * t) & 7, p1 = (t >> 2) & 7, p2 = t >> 5;
+    const int sbase = (((p0 ^ p1 ^ p2) & 7) & ~1) | (p1 << 3) | (p2 << 6);
+    const bool flip = ((p1 ^ p2) & 1) != 0;
+    typedef double v2d_t __attribute__((ext_vector_type(2)));
+    // R of one pool on cube q, the two elements of this thread's 16-byte piece
+    auto combine = [&](const double* pool, int q) {
+        const int T0 = tile[sig(q, 0)], T1 = tile[sig(q, 1)], T2 = tile[sig(q, 2)];
+        const int64_t off = (int64_t)CUBE * (T0 + (int64_t)nt8 * (T1 + (int64_t)nt8 * T2)) + 2 * t;
+        const v2d_t x0 = *reinterpret_cast<const v2d_t*>(pool + m.xoff[0] + off);
+        const v2d_t x1 = *reinterpret_cast<const v2d_t*>(pool + m.xoff[1] + off);
+        const v2d_t x2 = *reinterpret_cast<const v2d_t*>(pool + m.xoff[2] + off);
+        const int g0 = T0 * TT + p0;
+        const bool rows = (T1 * TT + p1 < v) && (T2 * TT + p2 < v);
+        const double r0 = (rows && g0 < v) ? x0[0] - x1[0] + x2[0] : 0.0;
+        const double r1 = (rows && g0 + 1 < v) ? x0[1] - x1[1] + x2[1] : 0.0;
+        return flip ? (v2d_t){r1, r0} : (v2d_t){r0, r1};
+    };
+#pragma unroll
+    for (int q = 0; q < 6; ++q) *reinterpret_cast<v2d_t*>(&wl[q * CUBE + sbase]) = combine(Xpool, q);
+    const int occ[3] = {m.i, m.j, m.k};
+    const int pairp[3] = {m.j, m.i, m.i}, pairq[3] = {m.k, m.k, m.j};
+    for (int el = t; el < 27 * PATCH; el += 256) {
+        const int pr = el / (9 * PATCH), rest = el % (9 * PATCH), sx = rest / (3 * PATCH), sy = (rest / PATCH) % 3, loc = rest % PATCH;
+        const int gx = tile[sx] * TT + (loc & 7), gy = tile[sy] * TT + (loc >> 3);
+        const bool ok = gx < v && gy < v;
+        const int64_t off = ok ? gx + (int64_t)v * gy + vv * (pairp[pr] + (int64_t)o * pairq[pr]) : 0;
+        const double a = in.voovv_s[off];
+        vp[el] = ok ? a : 0.0;
+        if (FOCK) {
+            const int64_t offt = ok ? pairp[pr] + (int64_t)o * (pairq[pr] + (int64_t)o * (gx + (int64_t)v * gy)) : 0;
+            const double b = in.t2[offt];   // (l2)
+            tp[el] = ok ? b : 0.0;
+        }
+    }
+    if (t < 72) {
+        const int oc = t / 24, sl = (t / 8) % 3, l = t & 7, g = tile[sl] * TT + l;
+        t1r[t] = g < v ? in.t1[occ[oc] + o * g] : 0.0;              // (l1)
+        if (FOCK) fr[t] = g < v ? in.t2_s[occ[oc] + o * g] : 0.0;   // (the free slot carries f_ov)
+    } else if (t < 96) {
+        const int sl = (t - 72) / 8, l = t & 7, g = tile[sl] * TT + l;
+        t1r[t] = in.e[(g < v ? g : 0) + o];
+    }
+    const double* evl = t1r + 72;   // evl[slot][l] = e(o + tile[slot]*8 + l)
+    // the second pool's cubes travel under the first pool's permuted reads
+    v2d_t rl[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) rl[q] = combine(Lpool, q);
+    __syncthreads();
+    const int l0 = t & 7, l1 = (t >> 3) & 7, l2h[2] = {t >> 6, (t >> 6) + 4};
+    double T3[2][6];   // P(R_t) at the six images of the two base elements                      :1894-1896
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int l[3] = {l0, l1, l2h[h]};
+        double R[6];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) R[q] = wl[srcq[0][q] * CUBE + cidx(l[sig(q, 0)], l[sig(q, 1)], l[sig(q, 2)])];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) T3[h][q] = R[q] - R[compose(q, 1)] - R[compose(q, 2)];
+    }
+    __syncthreads();   // every reader of R_t is done with wl
+#pragma unroll
+    for (int q = 0; q < 6; ++q) *reinterpret_cast<v2d_t*>(&wl[q * CUBE + sbase]) = rl[q];
+    __syncthreads();
+    const double eo = in.e[m.i] + in.e[m.j] + in.e[m.k];
+    double acc = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        int l2v = l2h[h];
+        if (h == 1) asm volatile("" : "+v"(l2v) : "v"(acc));   // the second orbit's reads stay behind the first orbit's arithmetic
+        const int l[3] = {l0, l1, l2v};
+        const bool live = tile[0] * TT + l[0] < v && tile[1] * TT + l[1] < v && tile[2] * TT + l[2] < v;
+        const double D = eo - evl[l[0]] - evl[TT + l[1]] - evl[2 * TT + l[2]];
+        const double rD = rcp_nr(D);
+        double L[6], l1v[3][3], V[3][3][3];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) L[q] = wl[srcq[0][q] * CUBE + cidx(l[sig(q, 0)], l[sig(q, 1)], l[sig(q, 2)])];
+#pragma unroll
+        for (int oc = 0; oc < 3; ++oc)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) l1v[oc][c] = t1r[oc * 24 + c * TT + l[c]];
+#pragma unroll
+        for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int cx = 0; cx < 3; ++cx)
+#pragma unroll
+                for (int cy = 0; cy < 3; ++cy)
+                    if (cx != cy) V[pr][cx][cy] = vp[(pr * 9 + cx * 3 + cy) * PATCH + l[cx] + TT * l[cy]];
+        // + l1(i,x)<jk||yz> - l1(j,x)<ik||yz> + l1(k,x)<ij||yz> at the q-th image
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const int s0 = sig(q, 0), s1 = sig(q, 1), s2 = sig(q, 2);
+            L[q] += l1v[0][s0] * V[0][s1][s2] - l1v[1][s0] * V[1][s1][s2] + l1v[2][s0] * V[2][s1][s2];
+        }
+        if (FOCK) {   // + f(i,x) l2(jk,yz) - f(j,x) l2(ik,yz) + f(k,x) l2(ij,yz)
+            double fv[3][3], L2[3][3][3];
+#pragma unroll
+            for (int oc = 0; oc < 3; ++oc)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) fv[oc][c] = fr[oc * 24 + c * TT + l[c]];
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                for (int cx = 0; cx < 3; ++cx)
+#pragma unroll
+                    for (int cy = 0; cy < 3; ++cy)
+                        if (cx != cy) L2[pr][cx][cy] = tp[(pr * 9 + cx * 3 + cy) * PATCH + l[cx] + TT * l[cy]];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const int s0 = sig(q, 0), s1 = sig(q, 1), s2 = sig(q, 2);
+                L[q] += fv[0][s0] * L2[0][s1][s2] - fv[1][s0] * L2[1][s1][s2] + fv[2][s0] * L2[2][s1][s2];
+            }
+        }
+        double sum = 0.0;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) sum += L[q] * T3[h][q];
+        acc += live ? sum * rD : 0.0;
+    }
+    const int nH = (tile[0] == tile[1] && tile[1] == tile[2]) ? 6 : (tile[0] == tile[1] || tile[1] == tile[2] || tile[0] == tile[2]) ? 2 : 1;
+    const int lane = t & 63, wv = t >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if (lane == 0) red[wv] = acc;
+    __syncthreads();
+    // 3 (the identity above) / 6 (i<j<k of the 36 ordered terms) / |H|
+    if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) / (2.0 * nH);
+}
+
 }  // namespace afesp

@@ -16,7 +16,7 @@ module afesp_capi
              afesp_fcidump_scan, afesp_read_fcidump, afesp_read_fcidump_uhf, &
              afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
              afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
-             afesp_ccsd_so_density, &
+             afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
              afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
              afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
@@ -538,6 +538,15 @@ module afesp_capi
          type(c_ptr), value :: ctx
          integer(c_int64_t), value :: t_begin, t_end
          real(c_double), intent(out) :: e_t
+         integer(c_int) :: rc
+      end function
+      !> Lambda-CCSD(T): the triples [t_begin, t_end) of afesp_ccsd_so_t's list with the Lambda amplitudes in the left factor (needs a live
+      !> Lambda state: status 21 otherwise)
+      function afesp_ccsd_so_lambda_t(ctx, t_begin, t_end, e_lt) bind(C, name='afesp_ccsd_so_lambda_t') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int64_t), value :: t_begin, t_end
+         real(c_double), intent(out) :: e_lt
          integer(c_int) :: rc
       end function
       !> ---- multi-GPU: one process per GPU; the OpenMP reduction of the reference's (T) loop (src/ccsd.f90:2091) becomes a

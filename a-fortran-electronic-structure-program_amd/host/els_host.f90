@@ -53,6 +53,8 @@ module host_config
       real(dp) :: fno_occ_tol = 0.0_dp   ! keep every natural virtual whose occupation is at least this (0: off)
       ! after a converged spin-orbital CCSD: the Lambda equations and the natural occupation numbers of the unrelaxed one-particle density
       logical :: cc_density = .false.
+      ! after a converged spin-orbital CCSD: the Lambda equations and the triples correction with the left-hand state in its left factor
+      logical :: cc_lambda_t = .false.
       ! after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (0: off)
       integer :: eom_nroots = 0
       ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
@@ -67,11 +69,11 @@ contains
       integer :: scf_diis_n_errmat, ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, unit, ios, charge, multiplicity
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
-      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density
+      logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, eom_nroots, eom_ip_nroots, eom_ea_nroots
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -81,6 +83,7 @@ contains
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
+      cc_lambda_t = d%cc_lambda_t
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
@@ -140,6 +143,10 @@ contains
          trim(calc_type)//' takes no cc_density: the Lambda equations run on the spin-orbital CCSD types!')
       if (cc_density .and. fcidump_in .and. cfg%uhf .and. .not. cfg%rohf) call fail('system::read_system_in', &
          'cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the spin-summed density needs!')
+      ! (Lambda-(T) needs no overlap of the alpha and beta orbitals: a UHF FCIDUMP takes it)
+      cfg%cc_lambda_t = cc_lambda_t
+      if (cc_lambda_t .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no cc_lambda_t: the Lambda equations run on the spin-orbital CCSD types!')
       cfg%eom_nroots = eom_nroots
       if (eom_nroots < 0) call fail('system::read_system_in', 'eom_nroots must be a non-negative integer!')
       if (eom_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
@@ -720,6 +727,8 @@ program els_amd
    integer :: rc_mine
    character(len=512) :: comm_file
    logical :: scf_ok, cc_ok, compat, have_ctx
+   logical :: lambda_live = .false.   ! lambda_solve has converged Lambda for the CCSD state (cc_density, cc_lambda_t)
+   real(dp) :: e_lt = 0.0_dp          ! the Lambda-CCSD(T) correction (cc_lambda_t)
    integer(c_int64_t) :: nlines
    character(len=32) :: envval
    character(len=80) :: calcname
@@ -927,6 +936,7 @@ program els_amd
             if (.not. cfg%rohf) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
             call lambda_and_occupations(n_act, na_act, nb_act, .false.)
          end if
+         if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
@@ -954,6 +964,8 @@ program els_amd
             end if
             write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//trim(ccname)//'(T):', seconds() - t0, 's'
          end if
+         if (cfg%cc_lambda_t .and. cc_ok .and. cfg%rohf) call lambda_triples(na_act + nb_act, 'ROHF-ΛCCSD(T)')
+         if (cfg%cc_lambda_t .and. cc_ok .and. .not. cfg%rohf) call lambda_triples(na_act + nb_act, 'UΛCCSD(T)')
       end if
    else if (cfg%level >= LEVEL_MP2 .and. scf_ok) then
       ! ---------------- MP2: AO->MO transform + energy on the device (reference do_mp2_spatial)
@@ -1030,6 +1042,7 @@ program els_amd
          end if
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD:', seconds() - t0, 's'
          if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
+         if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, nel_act, 2*n_act - nel_act)
@@ -1056,6 +1069,7 @@ program els_amd
             write (out, '(1X, A, 1X, F15.9)') 'Unrestricted CCSD(T) correlation energy (Hartree):', e_pt
             write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD(T):', seconds() - t0, 's'
          end if
+         if (cfg%cc_lambda_t .and. cc_ok) call lambda_triples(nel_act, 'Unrestricted ΛCCSD(T)')
       else if (cfg%level >= LEVEL_CCSD) then
          ! ---------------- CCSD (reference do_ccsd_spatial): the solver loop stays here, one C call per reference call
          t0 = seconds()
@@ -1195,6 +1209,10 @@ program els_amd
       write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD(T) correlation energy:', e_pt
       write (out, '(1X, A, 1X, F15.10)') 'ROHF-CCSD(T) energy:           ', e_pt + e_hf + mol%e_nuc
    end if
+   if (cfg%cc_lambda_t) then
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-ΛCCSD(T) correlation energy:', e_ccsd + e_lt
+      write (out, '(1X, A, 1X, F15.10)') 'ROHF-ΛCCSD(T) energy:          ', e_ccsd + e_lt + e_hf + mol%e_nuc
+   end if
    else if (cfg%uhf) then
    write (out, '(1X, A, 1X, F15.10)') 'UHF energy:                    ', e_hf + mol%e_nuc
    if (.not. cfg%fcidump_in) write (out, '(1X, A, 1X, F15.10)') '<S^2>:                         ', s2
@@ -1210,6 +1228,10 @@ program els_amd
       write (out, '(1X, A, 1X, F15.10)') 'UCCSD(T) correlation energy:   ', e_pt
       write (out, '(1X, A, 1X, F15.10)') 'UCCSD(T) energy:               ', e_pt + e_hf + mol%e_nuc
    end if
+   if (cfg%cc_lambda_t) then
+      write (out, '(1X, A, 1X, F15.10)') 'UΛCCSD(T) correlation energy:  ', e_ccsd + e_lt
+      write (out, '(1X, A, 1X, F15.10)') 'UΛCCSD(T) energy:              ', e_ccsd + e_lt + e_hf + mol%e_nuc
+   end if
    else
    write (out, '(1X, A, 1X, F15.10)') 'RHF energy:                    ', e_hf + mol%e_nuc
    if (cfg%level >= LEVEL_MP2) then
@@ -1219,6 +1241,10 @@ program els_amd
    if (cfg%level >= LEVEL_CCSD) then
       write (out, '(1X, A, 1X, F15.10)') 'CCSD correlation energy:       ', e_ccsd
       write (out, '(1X, A, 1X, F15.10)') 'CCSD energy:                   ', e_ccsd + e_hf + mol%e_nuc
+   end if
+   if (cfg%cc_lambda_t) then
+      write (out, '(1X, A, 1X, F15.10)') 'ΛCCSD(T) correlation energy:   ', e_ccsd + e_lt
+      write (out, '(1X, A, 1X, F15.10)') 'ΛCCSD(T) energy:               ', e_ccsd + e_lt + e_hf + mol%e_nuc
    end if
    if (cfg%level == LEVEL_CCSD_T .and. cfg%spinorb) then        ! reference src/main.F90:156-158
       write (out, '(1X, A, 1X, F15.10)') 'CCSD(T) correlation energy:    ', e_pt
@@ -1279,20 +1305,13 @@ contains
          k = count(occ >= cfg%fno_occ_tol)
       end if
    end function
-   !> cc_density: Lambda of the converged spin-orbital CCSD state (Jacobi steps with DIIS, the CCSD table's format), then the spin-summed
-   !> natural occupation numbers of the unrelaxed one-particle density over the whole basis (frozen core orbitals doubly occupied, dropped
-   !> virtuals empty).  The state's spin-orbital order over its n active orbitals is interleaved (2 P + spin: the RHF-fed state) or blocked
-   !> (occupied alpha, occupied beta, virtual alpha, virtual beta).
-   subroutine lambda_and_occupations(n, nalpha, nbeta, interleaved)
-      integer, intent(in) :: n, nalpha, nbeta
-      logical, intent(in) :: interleaved
-      real(dp), allocatable :: d(:, :), ds(:, :), dsb(:, :), occ(:), u(:, :)
-      integer, allocatable :: orb(:), spin(:)
-      real(dp) :: pe, pe_old, lrms, tl
+   !> Lambda of the converged spin-orbital CCSD state: Jacobi steps with DIIS, the CCSD table's format.  One solve serves cc_density,
+   !> cc_lambda_t and the EOM sectors (which borrow its H-bar elements).
+   subroutine lambda_solve()
+      real(dp) :: pe, pe_old, lrms
       integer(c_int) :: lconv
-      integer :: it, x, y, o, nf
+      integer :: it
       logical :: ok
-      tl = seconds()
       write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD Lambda'; write (out, '(1X, 10("-"))')
       rc = afesp_ccsd_so_lambda_init(ctx, int(cfg%ccsd_diis_n_errmat, c_int))
       if (rc /= 0) call fail('ccsd::init_lambda', afesp_error_text(ctx))
@@ -1320,6 +1339,55 @@ contains
       write (out, '(75("-"))')
       if (.not. ok) call fail('ccsd::do_lambda', 'the Lambda equations did not converge!')
       write (out, '(1X, A)') 'Convergence reached within tolerance.'
+      lambda_live = .true.
+   end subroutine
+   !> cc_lambda_t: Lambda-CCSD(T) of the converged state and its converged Lambda -- this rank's shard of the i<j<k list, then the flagged
+   !> sum over the ranks of the (T) branches.
+   subroutine lambda_triples(nel_so, label)
+      integer, intent(in) :: nel_so
+      character(*), intent(in) :: label
+      real(dp) :: lq(2), tl
+      integer(c_int64_t) :: l_lo, l_hi
+      integer(c_int) :: lrc_mine
+      character(512) :: l_error
+      tl = seconds()
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'Lambda-CCSD(T)'; write (out, '(1X, 10("-"))')
+      l_hi = afesp_ccsd_so_t_ntriples(int(nel_so, c_int64_t))
+      l_lo = (int(rank, c_int64_t)*l_hi)/world; l_hi = (int(rank + 1, c_int64_t)*l_hi)/world
+      lq = 0.0_dp
+      rc = afesp_ccsd_so_lambda_t(ctx, l_lo, l_hi, lq(1))
+      if (world > 1) then   ! (every rank enters the sum, a failed shard as a flag: as in the (T) branches)
+         lrc_mine = rc; l_error = ''
+         if (lrc_mine /= 0) then; l_error = afesp_error_text(ctx); lq(1) = 0.0_dp; end if
+         lq(2) = merge(1.0_dp, 0.0_dp, lrc_mine /= 0)
+         rc = afesp_allreduce_sum(ctx, lq, 2_c_int64_t)
+         if (lrc_mine /= 0) call fail('ccsd::do_lambda_ccsd_t', trim(l_error))
+         if (rc == 0 .and. lq(2) > 0.5_dp) call fail('ccsd::do_lambda_ccsd_t', 'the Lambda-(T) shard of another rank failed')
+      end if
+      if (rc /= 0) call fail('ccsd::do_lambda_ccsd_t', afesp_error_text(ctx))
+      e_lt = lq(1)
+      if (cfg%rohf) then   ! (the formats of the (T) lines of the same branch)
+         write (out, '(1X, A, 1X, F18.12)') 'E(ΛCCSD(T)) correction (Hartree):', e_lt
+         write (out, '(1X, A, 1X, F18.12)') label//' correlation energy (Hartree):', e_ccsd + e_lt
+      else
+         write (out, '(1X, A, 1X, F15.9)') 'E(ΛCCSD(T)) correction (Hartree):', e_lt
+         write (out, '(1X, A, 1X, F15.9)') label//' correlation energy (Hartree):', e_ccsd + e_lt
+      end if
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for Lambda-CCSD(T):', seconds() - tl, 's'
+   end subroutine
+   !> cc_density: Lambda of the converged spin-orbital CCSD state (Jacobi steps with DIIS, the CCSD table's format), then the spin-summed
+   !> natural occupation numbers of the unrelaxed one-particle density over the whole basis (frozen core orbitals doubly occupied, dropped
+   !> virtuals empty).  The state's spin-orbital order over its n active orbitals is interleaved (2 P + spin: the RHF-fed state) or blocked
+   !> (occupied alpha, occupied beta, virtual alpha, virtual beta).
+   subroutine lambda_and_occupations(n, nalpha, nbeta, interleaved)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      real(dp), allocatable :: d(:, :), ds(:, :), dsb(:, :), occ(:), u(:, :)
+      integer, allocatable :: orb(:), spin(:)
+      real(dp) :: tl
+      integer :: x, y, o, nf
+      tl = seconds()
+      call lambda_solve()
       nf = mol%nbasis
       allocate (d(2*n, 2*n), ds(nf, nf), dsb(nf, nf), orb(2*n), spin(2*n))
       rc = afesp_ccsd_so_density(ctx, d, int(size(d), c_int64_t))
@@ -1388,7 +1456,7 @@ contains
       o8 = int(o, c_int64_t); v8 = int(v, c_int64_t)
       nunique = o8*v8 + (o8*(o8 - 1)/2)*(v8*(v8 - 1)/2)
       ms = max(2*nr, int(min(nunique, int(8*nr, c_int64_t))))
-      if (.not. cfg%cc_density) then
+      if (.not. lambda_live) then
          rc = afesp_ccsd_so_lambda_init(ctx, 0_c_int)
          if (rc /= 0) call fail('eom::init_hbar', afesp_error_text(ctx))
       end if
@@ -1451,7 +1519,7 @@ contains
          n1 = v8; n2 = o8*v8*v8; nunique = v8 + o8*(v8*(v8 - 1)/2)
       end if
       ms = max(2*nr, int(min(nunique, int(8*nr, c_int64_t))))
-      if (.not. cfg%cc_density .and. cfg%eom_nroots <= 0 .and. .not. (sector == AFESP_EOM_EA .and. cfg%eom_ip_nroots > 0)) then
+      if (.not. lambda_live .and. cfg%eom_nroots <= 0 .and. .not. (sector == AFESP_EOM_EA .and. cfg%eom_ip_nroots > 0)) then
          rc = afesp_ccsd_so_lambda_init(ctx, 0_c_int)
          if (rc /= 0) call fail('eom_ipea::init_hbar', afesp_error_text(ctx))
       end if

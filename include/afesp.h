@@ -219,6 +219,20 @@ int afesp_ccsd_so_get_lambda(afesp_ctx* ctx, double* l1, double* l2);
 int afesp_ccsd_so_set_lambda(afesp_ctx* ctx, const double* l1, const double* l2);
 int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity);
 
+/* Lambda-CCSD(T) (Kucharski and Bartlett 1998, Taube and Bartlett 2008; a-CCSD(T) of Crawford and Stanton 1998): the
+ * triples correction with the left factor taken from the left-hand state.  With pp_x, hh_x the particle / hole products of x2 with
+ * <fp||bc> / <ma||qr>, wc_x the connected and wd_x the disconnected numerator of afesp_ccsd_so_t built from x = t or x = l, P(y) = y(abc)
+ * - y(bac) - y(cba) and D = e_i + e_j + e_k - e_a - e_b - e_c,
+ *   afesp_ccsd_so_lambda_t = sum over the triples i<j<k numbered [t_begin, t_end) of afesp_ccsd_so_t_ntriples(nocc), and over a, b, c, of
+ *                            P(wc_l + wd_l) P(wc_t) / D / 6
+ * at the current t and l (converged or not; with l = t it is afesp_ccsd_so_t term for term).  The enumeration is afesp_ccsd_so_t's, so
+ * shards add up; on a state with a full Fock matrix wd_l carries f_ia l_jkbc.  It writes none of t1 / t2, l1 / l2, the epochs, the Lambda
+ * intermediates, the EOM states or the DIIS rings: afesp_ccsd_so_t, the Lambda residual and the density give the same bits before and
+ * after.  Device memory: a second operand pair and a second block pool beside those of afesp_ccsd_so_t (AFESP_T_POOL_GIB sizes one pool).
+ * Statuses: 1 no spin-orbital state, a recording context, a Fock state whose oo / vv blocks are not diagonal (as afesp_ccsd_so_t), or a
+ * second pool that does not fit; AFESP_LAMBDA_STALE no Lambda state or a stale one.  An empty range gives 0. */
+int afesp_ccsd_so_lambda_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_lt);
+
 /* EOM-EE-CCSD excitation energies of the spin-orbital state.  The right-hand EOM matrix in the singles and doubles space
  * is the Jacobian A = dR/dt of the residuals above over the unique amplitudes; sigma(r) = A r for r = [r1 [o*v]; r2 [o*o*v*v]] laid out as
  * t1 / t2, r2 antisymmetric in i,j and in a,b.  On that storage <x, y> = sum x1 y1 + 1/4 sum x2 y2.  The excitation energies are the lowest
