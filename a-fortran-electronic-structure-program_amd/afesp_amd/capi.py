@@ -32,6 +32,8 @@ EXPORTS = [
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density", "afesp_ccsd_so_lambda_t",
     "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
     "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
+    "afesp_ccsd_so_eom_lsigma", "afesp_ccsd_so_eom_left_init", "afesp_ccsd_so_eom_left_guess", "afesp_ccsd_so_eom_left_set_guess",
+    "afesp_ccsd_so_eom_left_iterate", "afesp_ccsd_so_eom_left_get_vector", "afesp_ccsd_so_eom_ref_coupling", "afesp_ccsd_so_eom_density",
     "afesp_ccsd_so_eom_ipea_init", "afesp_ccsd_so_eom_ipea_sigma", "afesp_ccsd_so_eom_ipea_guess", "afesp_ccsd_so_eom_ipea_set_guess",
     "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
@@ -127,6 +129,15 @@ def load_library():
     L.afesp_ccsd_so_eom_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
                                             C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.afesp_ccsd_so_eom_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_lsigma.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
+    L.afesp_ccsd_so_eom_left_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.afesp_ccsd_so_eom_left_guess.argtypes = [C.c_void_p]
+    L.afesp_ccsd_so_eom_left_set_guess.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_left_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
+                                                 C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_eom_left_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_ref_coupling.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    L.afesp_ccsd_so_eom_density.argtypes = [C.c_void_p, dbl, _opt, _opt, dbl, _opt, _opt, _dp, i64]
     L.afesp_ccsd_so_eom_ipea_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_ipea_sigma.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_ipea_guess.argtypes = [C.c_void_p, C.c_int]
@@ -859,6 +870,79 @@ class Engine:
         r1, r2 = np.zeros(o * v), np.zeros(o * o * v * v)
         self._chk(self.L.afesp_ccsd_so_eom_get_vector(self.h, k, r1, r2))
         return r1.reshape((o, v), order="F"), r2.reshape((o, o, v, v), order="F")
+
+    # ---- EOM-EE-CCSD left eigenvectors, reference coupling and the bilinear density (include/afesp.h; afesp_amd.eom drives them).  The
+    # left Davidson state stands beside the right-hand one: no call here touches that, t1 / t2 or lambda
+    eom_left_nroots = 0
+
+    def _so_stack(self, x1, x2, who):
+        """(k,o,v) / (k,o,o,v,v) or one vector -> (k, flat x1, flat x2, single)"""
+        o, v = self.so_o, self.so_v
+        x1, x2 = np.asarray(x1, dtype=np.float64), np.asarray(x2, dtype=np.float64)
+        single = x1.ndim == 2
+        if single:
+            x1, x2 = x1[None], x2[None]
+        k = x1.shape[0]
+        if x1.shape != (k, o, v) or x2.shape != (k, o, o, v, v):
+            raise ValueError(f"{who}: the vectors do not have the shapes (k,) o v / (k,) o o v v of this state")
+        return k, np.concatenate([_f(x) for x in x1]), np.concatenate([_f(x) for x in x2]), single
+
+    def so_eom_lsigma(self, l1, l2):
+        """sigma_L = A^T l.  l1 (o,v) and l2 (o,o,v,v) for one vector -> (s1, s2); with a leading axis, k vectors in one call -> the same
+        with that axis."""
+        o, v = self.so_o, self.so_v
+        k, a1, a2, single = self._so_stack(l1, l2, "so_eom_lsigma")
+        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
+        self._chk(self.L.afesp_ccsd_so_eom_lsigma(self.h, k, a1, a2, s1, s2))
+        s1 = np.stack([x.reshape((o, v), order="F") for x in s1.reshape(k, o * v)])
+        s2 = np.stack([x.reshape((o, o, v, v), order="F") for x in s2.reshape(k, o * o * v * v)])
+        return (s1[0], s2[0]) if single else (s1, s2)
+
+    def so_eom_left_init(self, nroots, max_space):
+        self._chk(self.L.afesp_ccsd_so_eom_left_init(self.h, nroots, max_space))
+        self.eom_left_nroots = int(nroots)
+
+    def so_eom_left_guess(self):
+        self._chk(self.L.afesp_ccsd_so_eom_left_guess(self.h))
+
+    def so_eom_left_set_guess(self, k, l1, l2):
+        self._chk(self.L.afesp_ccsd_so_eom_left_set_guess(self.h, k, _f(l1), _f(l2)))
+
+    def so_eom_left_iterate(self, tol=1e-8):
+        """One Davidson step of the left state -> (omega, resnorm, flags, sigma builds so far, converged)"""
+        n = self.eom_left_nroots
+        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        ns, cv = C.c_int(), C.c_int()
+        self._chk(self.L.afesp_ccsd_so_eom_left_iterate(self.h, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
+        return om, rs, fl, ns.value, bool(cv.value)
+
+    def so_eom_left_vector(self, k):
+        """Left Ritz vector k of the last step, <x, x> = 1 (biorthonormalise it against the right vectors: afesp_amd.eom)"""
+        o, v = self.so_o, self.so_v
+        l1, l2 = np.zeros(o * v), np.zeros(o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_eom_left_get_vector(self.h, k, l1, l2))
+        return l1.reshape((o, v), order="F"), l2.reshape((o, o, v, v), order="F")
+
+    def so_eom_ref_coupling(self, r1, r2):
+        """c = sum H_ia r_ia + 1/4 sum <ij||ab> r_ijab of one right vector (-> float) or of k vectors (-> array); r0 = c / omega"""
+        k, a1, a2, single = self._so_stack(r1, r2, "so_eom_ref_coupling")
+        c = np.zeros(k)
+        self._chk(self.L.afesp_ccsd_so_eom_ref_coupling(self.h, k, a1, a2, c))
+        return float(c[0]) if single else c
+
+    def so_eom_density(self, l0, l, r0, r, capacity=None):
+        """The symmetrised one-particle matrix of <0| (l0 + L) H-bar (r0 + R) |0> over the state's spin orbitals, (o+v) x (o+v).
+        l, r: (x1, x2), or None for a zero vector (not read)."""
+        o, v, n = self.so_o, self.so_v, self.so_o + self.so_v
+        for x in (l, r):
+            if x is not None and (np.shape(x[0]) != (o, v) or np.shape(x[1]) != (o, o, v, v)):
+                raise ValueError("so_eom_density: a vector does not have the shapes o v / o o v v of this state")
+        keep = [None if x is None else (_f(x[0]), _f(x[1])) for x in (l, r)]
+        ptr = [(None, None) if x is None else (x[0].ctypes.data, x[1].ctypes.data) for x in keep]
+        buf = np.zeros(n * n)
+        self._chk(self.L.afesp_ccsd_so_eom_density(self.h, l0, ptr[0][0], ptr[0][1], r0, ptr[1][0], ptr[1][1], buf,
+                                                   buf.size if capacity is None else capacity))
+        return buf.reshape((n, n), order="F")
 
     # ---- EOM-IP-CCSD / EOM-EA-CCSD of the same state (include/afesp.h; afesp_amd.eom drives them).  sector: EOM_IP (1h + 2h1p:
     # r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)); the rules and statuses are those of the EE calls above

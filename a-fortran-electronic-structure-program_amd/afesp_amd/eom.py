@@ -1,6 +1,8 @@
 """EOM-EE-CCSD excitation energies of a spin-orbital CCSD state: the Davidson driver over Engine.so_eom_* and the labelling of a root
 (host code); EOM-IP-CCSD ionisation potentials and EOM-EA-CCSD electron affinities of the same state over
-Engine.so_eom_ipea_* (so_eom_ip_solve, so_eom_ea_solve, label_ipea_root).
+Engine.so_eom_ipea_* (so_eom_ip_solve, so_eom_ea_solve, label_ipea_root); the left eigenvectors of the EE roots, their
+biorthonormalisation against the right ones, excited-state and transition densities and oscillator strengths over Engine.so_eom_left_*,
+so_eom_ref_coupling and so_eom_density (so_eom_left_solve, biorthonormalise, so_eom_properties, oscillator_strengths).
 
 The spin-orbital space holds every Ms component: a triplet appears threefold (Ms = 0 and the two spin-flip components Ms = +-1), a singlet
 once.  The driver reports the degeneracies and filters nothing."""
@@ -69,6 +71,116 @@ def label_root(x1, x2, nbasis, nalpha, nbeta, interleaved):
     return dict(kind="double", occ=(int(orb[i]), int(orb[j])), virt=(int(orb[a]), int(orb[b])), spins_occ=(int(spin[i]), int(spin[j])),
                 spins_virt=(int(spin[a]), int(spin[b])), delta_ms=float(ms(spin[a]) + ms(spin[b]) - ms(spin[i]) - ms(spin[j])),
                 weight=float(x2[i2] ** 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------- left vectors, densities
+def dot(x, y):
+    """<x, y> = sum x1 y1 + 1/4 sum x2 y2 of two vectors (x1, x2), (y1, y2) on full (i,j,a,b) storage"""
+    return float(np.sum(x[0] * y[0]) + 0.25 * np.sum(x[1] * y[1]))
+
+
+def so_eom_left_solve(eng, right_vectors=None, nroots=None, tol=1e-8, max_space=None, maxiter=100):
+    """The left eigenvectors l A = omega l of the nroots lowest EOM-EE-CCSD roots, on a Davidson state of its own beside
+    the right-hand one, which is not touched.  right_vectors: the converged right vectors [(r1, r2)] as the left guess (nroots defaults
+    to their number) -- the library then follows these states: it returns the Ritz pairs nearest to the roots of the guesses, not the lowest
+    ones, so that a lower root the right-hand solve never saw takes no place --; without them the unit vectors of so_eom_solve and the
+    lowest roots.  A live Lambda state is needed, as for so_eom_solve.
+    -> (omega [nroots], [(l1, l2)] with <l, l> = 1, info) like so_eom_solve.  The vectors are not yet biorthonormal to the right ones:
+    see biorthonormalise.  Raises AfespError if maxiter steps do not converge."""
+    if maxiter < 1:
+        raise ValueError("so_eom_left_solve: maxiter must be at least 1")
+    if nroots is None:
+        if right_vectors is None:
+            raise ValueError("so_eom_left_solve: give nroots or right_vectors")
+        nroots = len(right_vectors)
+    o, v = eng.so_o, eng.so_v
+    nunique = o * v + (o * (o - 1) // 2) * (v * (v - 1) // 2)
+    if max_space is None:
+        max_space = default_max_space(nroots, nunique)
+    eng.so_eom_left_init(nroots, max_space)
+    if right_vectors is None:
+        eng.so_eom_left_guess()
+    else:
+        for k, (r1, r2) in enumerate(right_vectors[:nroots]):
+            eng.so_eom_left_set_guess(k, r1, r2)
+    for it in range(1, maxiter + 1):
+        omega, res, flags, nsigma, conv = eng.so_eom_left_iterate(tol)
+        if conv:
+            vectors = [eng.so_eom_left_vector(k) for k in range(nroots)]
+            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
+                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
+                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
+                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
+            return omega, vectors, info
+    raise AfespError(f"the left EOM-CCSD Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+
+
+def clusters(omega, degeneracy_tol=1e-6):
+    """index lists of the roots whose omega lie within degeneracy_tol of their neighbour's (omega ascending or not)"""
+    order = [int(k) for k in np.argsort(omega, kind="stable")]
+    out = []
+    for k in order:
+        if out and abs(omega[k] - omega[out[-1][-1]]) < degeneracy_tol:
+            out[-1].append(k)
+        else:
+            out.append([k])
+    return out
+
+
+def biorthonormalise(omega, L, R, degeneracy_tol=1e-6):
+    """-> new left vectors with <L_j, R_k> = delta_jk inside every cluster of degenerate roots (eigenvectors of different eigenvalues are
+    biorthogonal as they are).  Inside a cluster L is replaced by S^-1 L with S_jk = <L_j, R_k>: the three components of a triplet come
+    out of the two Davidson iterations in two different bases of their space.  Raises ValueError where a cluster's S is singular
+    (condition number above 1e8, with every vector scaled to unit norm): the left and the right solve did not find the same states."""
+    if not (len(omega) == len(L) == len(R)):
+        raise ValueError("biorthonormalise: omega, L and R differ in length")
+    out = [None] * len(L)
+    for cl in clusters(np.asarray(omega), degeneracy_tol):
+        S = np.array([[dot(L[j], R[k]) for k in cl] for j in cl])
+        # (the condition number of the overlaps of the normalised vectors, so that a single root whose two vectors are orthogonal counts)
+        nl, nr = [np.sqrt(dot(L[j], L[j])) for j in cl], [np.sqrt(dot(R[k], R[k])) for k in cl]
+        sv = np.linalg.svd(S / np.outer(nl, nr), compute_uv=False) if min(nl + nr) > 0.0 else np.zeros(1)
+        if not sv[-1] * 1e8 >= max(1.0, sv[0]):
+            raise ValueError(f"biorthonormalise: the overlap of the left and right vectors of the roots {cl} is singular "
+                             f"(singular values {sv}): the two solves found different states")
+        Si = np.linalg.inv(S)
+        for a, j in enumerate(cl):                                           # S^-1 L: (S^-1 S)_jk = delta_jk
+            out[j] = (sum(Si[a, b] * L[m][0] for b, m in enumerate(cl)), sum(Si[a, b] * L[m][1] for b, m in enumerate(cl)))
+    return out
+
+
+def so_eom_properties(eng, omega, L, R, lam):
+    """Per root k, from biorthonormal left vectors L (biorthonormalise), right vectors R and the converged ground-state lam = (l1, l2):
+    -> [dict(r0, density, g0k, gk0)].  r0 = <0| H-bar R_k |0> / omega_k; density is the correlation part of the excited state's
+    one-particle density (afesp_amd.density.spatial_blocks adds the reference), g0k = <0| (1 + Lambda) [p+ q] R_k |0> and gk0 =
+    <0| L_k [p+ q] |0> the two transition densities, all symmetrised, (o+v) x (o+v) in the state's spin-orbital order."""
+    c = eng.so_eom_ref_coupling(np.stack([r[0] for r in R]), np.stack([r[1] for r in R]))
+    out = []
+    for k, w in enumerate(omega):
+        r0 = float(c[k] / w)
+        out.append(dict(r0=r0, density=eng.so_eom_density(0.0, L[k], r0, R[k]), g0k=eng.so_eom_density(1.0, lam, r0, R[k]),
+                        gk0=eng.so_eom_density(0.0, L[k], 1.0, None)))
+    return out
+
+
+def oscillator_strengths(omega, g0k, gk0, dipole_so):
+    """f_k = 2/3 omega_k sum_x (mu^x . gamma^0k)(mu^x . gamma^k0).  dipole_so: the three Cartesian components of the dipole operator as
+    symmetric matrices over the state's spin orbitals, in its order (afesp_amd.density.so_spin_order).  The program reads no dipole
+    integrals: the operator is the caller's, in the same molecular orbitals as the state."""
+    dipole_so = [np.asarray(m, dtype=np.float64) for m in dipole_so]
+    if len(dipole_so) != 3 or any(m.shape != np.shape(g0k[0]) or not np.allclose(m, m.T, rtol=0.0, atol=1e-12 * max(1.0, np.max(np.abs(m))))
+                                  for m in dipole_so):
+        raise ValueError("oscillator_strengths: dipole_so is three symmetric matrices of the densities' shape")
+    return np.array([2.0 / 3.0 * w * sum(float(np.sum(m * a)) * float(np.sum(m * b)) for m in dipole_so) for w, a, b in zip(omega, g0k, gk0)])
+
+
+def left_table(omega_left, omega_right, info):
+    """The lines the Fortran host prints for eom_left: root, omega_left in Eh and eV, |omega_left - omega_right|, residual, sigma builds"""
+    lines = ["  root   omega(left) / Eh   omega(left) / eV   |left-right|     residual"]
+    for k, w in enumerate(omega_left):
+        lines.append(f"  {k + 1:4d}  {w:16.10f}  {w * HARTREE_EV:16.8f}  {abs(w - omega_right[k]):11.3e}  {info['resnorm'][k]:11.3e}")
+    lines.append(f"  left sigma builds: {info['nsigma']}")
+    return "\n".join(lines)
 
 
 # ---------------------------------------------------------------------------------------------------------------- EOM-IP / EOM-EA

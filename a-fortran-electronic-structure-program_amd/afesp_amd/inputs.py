@@ -46,7 +46,8 @@ class SystemIn:
     cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
     cc_lambda_t: bool = False       # after a converged spin-orbital CCSD: Lambda and the Lambda-CCSD(T) correction (density.so_lambda_t_correction)
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
-    eom_ip_nroots: int = 0          # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
+    eom_left: bool = False          # ... and their left eigenvectors, from the right ones as guess (eom.so_eom_left_solve); needs eom_nroots > 0
+    eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
@@ -164,6 +165,10 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("eom_nroots must be a non-negative integer!")
     if sysin.eom_nroots > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
         raise ValueError(f"{sysin.calc_type} takes no eom_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!")
+    if not isinstance(sysin.eom_left, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.eom_left and sysin.eom_nroots == 0:
+        raise ValueError("eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!")
     for key in ("eom_ip_nroots", "eom_ea_nroots"):
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < 0:

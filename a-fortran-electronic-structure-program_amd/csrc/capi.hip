@@ -673,6 +673,72 @@ int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2)
 
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr) { return eig_general(n, a, lda, wr, wi, vr); }
 
+// ---- EOM-EE-CCSD left eigenvectors, reference coupling and the bilinear density (eom_so.h, eom_left_so.hip)
+int afesp_ccsd_so_eom_lsigma(afesp_ctx* ctx, int nvec, const double* l1, const double* l2, double* s1, double* s2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_lsigma_host(cx, ctx->sv.need_so("afesp_ccsd_so_eom_lsigma: no spin-orbital CCSD state").so, nvec, l1, l2, s1, s2);
+    });
+}
+
+int afesp_ccsd_so_eom_left_init(afesp_ctx* ctx, int nroots, int max_space)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_init(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_init: no spin-orbital CCSD state").so, nroots, max_space, true);
+    });
+}
+
+int afesp_ccsd_so_eom_left_guess(afesp_ctx* ctx)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_guess: no spin-orbital CCSD state").so, true); });
+}
+
+int afesp_ccsd_so_eom_left_set_guess(afesp_ctx* ctx, int k, const double* l1, const double* l2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_set_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_set_guess: no spin-orbital CCSD state").so, k, l1, l2, true);
+    });
+}
+
+int afesp_ccsd_so_eom_left_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_left_iterate: no spin-orbital CCSD state").so;
+        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_left_iterate: tol must be positive");
+        const int conv = so_eom_iterate(cx, so, tol, true);
+        const SOEom& E = *so.eom_left;
+        for (int k = 0; k < E.nroots; ++k) {
+            if (omega) omega[k] = E.omega[k];
+            if (resnorm) resnorm[k] = E.resnorm[k];
+            if (flags) flags[k] = E.flags[k];
+        }
+        if (nsigma) *nsigma = E.nsigma;
+        if (converged) *converged = conv;
+    });
+}
+
+int afesp_ccsd_so_eom_left_get_vector(afesp_ctx* ctx, int k, double* l1, double* l2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_get_vector(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_get_vector: no spin-orbital CCSD state").so, k, l1, l2, true);
+    });
+}
+
+int afesp_ccsd_so_eom_ref_coupling(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* c)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_ref_coupling(cx, ctx->sv.need_so("afesp_ccsd_so_eom_ref_coupling: no spin-orbital CCSD state").so, nvec, r1, r2, c);
+    });
+}
+
+int afesp_ccsd_so_eom_density(afesp_ctx* ctx, double l0, const double* l1, const double* l2, double r0, const double* r1, const double* r2,
+                              double* d, int64_t capacity)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_eom_density(cx, ctx->sv.need_so("afesp_ccsd_so_eom_density: no spin-orbital CCSD state").so, l0, l1, l2, r0, r1, r2, d, capacity);
+    });
+}
+
 // ---- EOM-IP-CCSD and EOM-EA-CCSD (eom_ipea_so.h)
 static SOState& ipea_state(afesp_ctx* ctx, int sector, const char* who)
 {

@@ -38,6 +38,7 @@ struct SOState : DiisRing {
     double f_offdiag = 0.0;          // largest |f_oo|, |f_vv| off-diagonal element: (T) is defined for (semi)canonical orbitals only
     SOLambda* lam = nullptr;         // the Lambda state made by so_lambda_init for one amp_epoch (lambda_so.h); released by so_free
     SOEom* eom = nullptr;            // the EOM state that borrows lam's H-bar elements (eom_so.h); released wherever lam is
+    SOEom* eom_left = nullptr;       // the left-hand Davidson state beside it (eigenvectors of A^T); released with it
     SOEomX* ipea[2] = {nullptr, nullptr};   // ... and those of the EOM-IP and EOM-EA sectors (eom_ipea_so.h), released with it
 };
 

@@ -240,6 +240,13 @@ void preload_eom_so()
     (void)hipGetLastError();
 }
 
+int so_eom_reduce_blocks(int64_t nvec) { return eom_nblk(nvec); }
+
+void so_eom_reduce_final(Context& cx, double* out, const double* partial, int nout, int nblk)
+{
+    LAUNCH(eom_final_kernel, dim3(nout), out, partial, nblk);
+}
+
 double so_eom_bytes(int64_t o, int64_t v, int nroots, int max_space)
 {
     const double O = (double)o, V = (double)v, o2v2 = O * O * V * V, nvec = O * V + o2v2;
@@ -250,39 +257,58 @@ double so_eom_bytes(int64_t o, int64_t v, int nroots, int max_space)
     return 8.0 * doubles;
 }
 
+// the right-hand and the left-hand Davidson state are one type and one code: `left` chooses the slot, the sigma build and the names
+static SOEom*& eom_slot(SOState& s, bool left) { return left ? s.eom_left : s.eom; }
+static std::string eom_name(bool left, const char* call) { return std::string(left ? "afesp_ccsd_so_eom_left_" : "afesp_ccsd_so_eom_") + call; }
+
+static void eom_free_one(Context& cx, SOState& s, bool left)
+{
+    SOEom*& e = eom_slot(s, left);
+    if (!e) return;
+    free_buffers(cx, *e);
+    delete e;
+    e = nullptr;
+}
+
 void so_eom_free(Context& cx, SOState& s)
 {
-    if (!s.eom) return;
-    free_buffers(cx, *s.eom);
-    delete s.eom;
-    s.eom = nullptr;
+    eom_free_one(cx, s, false);
+    eom_free_one(cx, s, true);
 }
 
-SOEom& so_eom_need(SOState& s, const char* who)
+SOEom& so_eom_need(SOState& s, const char* who, bool left)
 {
     so_lambda_need(s, who);
-    if (!s.eom || s.eom->epoch != s.amp_epoch)
-        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no EOM state for the live Lambda state (call afesp_ccsd_so_eom_init first)");
-    return *s.eom;
+    SOEom* e = eom_slot(s, left);
+    if (!e || e->epoch != s.amp_epoch)
+        throw Error(LAMBDA_ERR_STALE, std::string(who) + (left ? ": no left EOM state for the live Lambda state (call afesp_ccsd_so_eom_left_init first)"
+                                                               : ": no EOM state for the live Lambda state (call afesp_ccsd_so_eom_init first)"));
+    return *e;
 }
 
-void so_eom_init(Context& cx, SOState& s, int nroots, int max_space)
+void so_eom_init(Context& cx, SOState& s, int nroots, int max_space, bool left)
 {
     need_plain(cx);
-    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_init");
+    const std::string who = eom_name(left, "init");
+    SOLambda& L = so_lambda_need(s, who.c_str());
     const int64_t O = s.o, V = s.v, nvec = O * V + O * O * V * V, nunique = O * V + (O * (O - 1) / 2) * (V * (V - 1) / 2);
     if (nroots < 1 || (int64_t)nroots > nunique)
-        throw Error(1, "afesp_ccsd_so_eom_init: nroots must be in 1 .. " + std::to_string(nunique) + " (the unique singles and doubles)");
+        throw Error(1, who + ": nroots must be in 1 .. " + std::to_string(nunique) + " (the unique singles and doubles)");
     if ((int64_t)max_space < 2 * (int64_t)nroots || max_space > 4096)
-        throw Error(1, "afesp_ccsd_so_eom_init: max_space must be in 2 nroots .. 4096");
-    so_eom_free(cx, s);
-    if (!cx.fits(so_eom_bytes(O, V, nroots, max_space)))
-        throw Error(1, "afesp_ccsd_so_eom_init: the EOM state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
+        throw Error(1, who + ": max_space must be in 2 nroots .. 4096");
+    eom_free_one(cx, s, left);
+    if (!cx.fits(left ? so_eom_left_bytes(O, V, nroots, max_space) : so_eom_bytes(O, V, nroots, max_space)))
+        throw Error(1, who + ": the EOM state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
     static const bool loaded = (preload_eom_so(), true);
     (void)loaded;
-    s.eom = new SOEom();
-    SOEom& E = *s.eom;
+    if (left) {
+        static const bool loaded_left = (preload_eom_left_so(), true);
+        (void)loaded_left;
+    }
+    eom_slot(s, left) = new SOEom();
+    SOEom& E = *eom_slot(s, left);
     try {
+        E.left = left;
         E.nroots = nroots;
         E.max_space = max_space;
         E.nvec = nvec;
@@ -302,7 +328,7 @@ void so_eom_init(Context& cx, SOState& s, int nroots, int max_space)
         E.epoch = L.epoch;
         cx.sync();
     } catch (...) {
-        try { cx.quiesce(); so_eom_free(cx, s); } catch (...) {}
+        try { cx.quiesce(); eom_free_one(cx, s, left); } catch (...) {}
         throw;
     }
 }
@@ -383,14 +409,15 @@ static void eom_restart(SOEom& E)
     E.npend = 0;
     E.ritz = false;
     E.user_guess = false;
+    E.target.clear();
     E.nsigma = E.ncollapse = 0;
     std::fill(E.flags.begin(), E.flags.end(), 0);
 }
 
-void so_eom_guess(Context& cx, SOState& s)
+void so_eom_guess(Context& cx, SOState& s, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, "afesp_ccsd_so_eom_guess");
+    SOEom& E = so_eom_need(s, eom_name(left, "guess").c_str(), left);
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
     std::vector<double> D(ov + o2v2);
     AFESP_HIP(hipMemcpyAsync(D.data(), s.D1.d, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
@@ -421,11 +448,11 @@ void so_eom_guess(Context& cx, SOState& s)
     cx.sync();
 }
 
-void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const double* r2)
+void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const double* r2, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, "afesp_ccsd_so_eom_set_guess");
-    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, "afesp_ccsd_so_eom_set_guess: k outside 0 .. nroots - 1, or a NULL vector");
+    SOEom& E = so_eom_need(s, eom_name(left, "set_guess").c_str(), left);
+    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, eom_name(left, "set_guess") + ": k outside 0 .. nroots - 1, or a NULL vector");
     const int64_t ov = (int64_t)s.o * s.v;
     if (E.nb > 0 || !E.user_guess) {   // the first of a block of the caller's guesses starts over: a running iteration, the unit guesses
         eom_restart(E);
@@ -438,13 +465,15 @@ void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const do
     E.npend = std::max(E.npend, k + 1);
 }
 
-int so_eom_iterate(Context& cx, SOState& s, double tol)
+int so_eom_iterate(Context& cx, SOState& s, double tol, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, "afesp_ccsd_so_eom_iterate");
+    const std::string who = eom_name(left, "iterate");
+    SOEom& E = so_eom_need(s, who.c_str(), left);
     const int64_t n1 = (int64_t)s.o * s.v, nvec = E.nvec;
     const int ms = E.max_space;
-    if (E.nb == 0 && E.npend == 0) throw Error(1, "afesp_ccsd_so_eom_iterate: no guess vectors (call afesp_ccsd_so_eom_guess or afesp_ccsd_so_eom_set_guess first)");
+    if (E.nb == 0 && E.npend == 0) throw Error(1, who + ": no guess vectors (call " + eom_name(left, "guess") + " or " + eom_name(left, "set_guess") + " first)");
+    const bool guess_step = E.nb == 0;
     // ---- collapse: restart from the Ritz vectors, their sigma being the same combination of the stored sigma (no new sigma builds)
     if (E.nb + E.npend > ms) {
         const int nr = std::min(E.nroots, E.nb);
@@ -456,29 +485,52 @@ int so_eom_iterate(Context& cx, SOState& s, double tol)
     // ---- the pending vectors: orthonormalise, sigma, one more row and column of the projected matrix
     for (int k = 0; k < E.npend && E.nb < ms; ++k) {
         if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr, n1)) continue;
-        so_eom_sigma(cx, s, E.B + nvec * E.nb, E.S + nvec * E.nb);
+        if (left) so_eom_lsigma(cx, s, E.B + nvec * E.nb, E.S + nvec * E.nb);   // the projected matrix is then <b_p, sigma_L(b_q)>
+        else so_eom_sigma(cx, s, E.B + nvec * E.nb, E.S + nvec * E.nb);
         ++E.nsigma;
         extend_projected(cx, E, n1);
     }
     E.npend = 0;
-    if (E.nb == 0) throw Error(1, "afesp_ccsd_so_eom_iterate: every guess vector vanished");
+    if (E.nb == 0) throw Error(1, who + ": every guess vector vanished");
     // ---- the projected problem on the host
     const int nb = E.nb, nr = std::min(E.nroots, nb);
     std::vector<double> g((size_t)nb * nb), wr(nb), wi(nb), vr((size_t)nb * nb), up((size_t)nb * nr + nr);
     for (int q = 0; q < nb; ++q)
         for (int p = 0; p < nb; ++p) g[p + (size_t)nb * q] = E.G[p + (size_t)ms * q];
     const int rc = eig_general(nb, g.data(), nb, wr.data(), wi.data(), vr.data());
-    if (rc) throw Error(1, "afesp_ccsd_so_eom_iterate: the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
+    if (rc) throw Error(1, who + ": the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
+    // The roots taken: the lowest nr -- or, for the left state from the caller's guesses, those nearest to the Ritz values of its guess step,
+    // target by target in their order, each root once, then by ascending omega.  A lower root of another symmetry, which only rounding
+    // brings into the basis and the iteration then amplifies, takes no place that way.
+    std::vector<int> sel(nr);
+    std::iota(sel.begin(), sel.end(), 0);
+    if (guess_step && left && E.user_guess) E.target.assign(wr.begin(), wr.begin() + nr);
+    else if (!E.target.empty() && nb > nr) {
+        std::vector<char> used(nb, 0);
+        const int nt = std::min<int>(nr, (int)E.target.size());
+        for (int k = 0; k < nr; ++k) {
+            int best = -1;
+            for (int c = 0; c < nb; ++c) {
+                if (used[c]) continue;
+                // (beyond the targets -- a guess was dropped --: the lowest root not yet taken)
+                if (best < 0 || (k < nt && std::fabs(wr[c] - E.target[k]) < std::fabs(wr[best] - E.target[k]))) best = c;
+            }
+            used[best] = 1;
+            sel[k] = best;
+        }
+        std::sort(sel.begin(), sel.end());
+    }
     for (int k = 0; k < nr; ++k) {
+        const int c = sel[k];
         // a root with an imaginary part: the real part of its vector (the column of the pair's root with wi > 0)
-        const double* col = vr.data() + (size_t)nb * (wi[k] < 0.0 && k > 0 ? k - 1 : k);
+        const double* col = vr.data() + (size_t)nb * (wi[c] < 0.0 && c > 0 ? c - 1 : c);
         double n2 = 0.0;
         for (int p = 0; p < nb; ++p) n2 += col[p] * col[p];
         const double sc = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;   // <x, x> = sum_p y_p^2: the basis is orthonormal
         for (int p = 0; p < nb; ++p) up[p + (size_t)nb * k] = sc * col[p];
-        up[(size_t)nb * nr + k] = wr[k];
-        E.omega[k] = wr[k];
-        E.flags[k] = wi[k] != 0.0 ? EOM_FLAG_COMPLEX : 0;
+        up[(size_t)nb * nr + k] = wr[c];
+        E.omega[k] = wr[c];
+        E.flags[k] = wi[c] != 0.0 ? EOM_FLAG_COMPLEX : 0;
     }
     AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
     // ---- Ritz pass
@@ -509,12 +561,12 @@ int so_eom_iterate(Context& cx, SOState& s, double tol)
     return all;
 }
 
-void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2)
+void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, "afesp_ccsd_so_eom_get_vector");
+    SOEom& E = so_eom_need(s, eom_name(left, "get_vector").c_str(), left);
     if (!E.ritz || k < 0 || k >= std::min(E.nroots, E.nb) || !r1 || !r2)
-        throw Error(1, "afesp_ccsd_so_eom_get_vector: no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
+        throw Error(1, eom_name(left, "get_vector") + ": no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
     const int64_t ov = (int64_t)s.o * s.v;
     AFESP_HIP(hipMemcpyAsync(r1, E.x + E.nvec * k, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
     AFESP_HIP(hipMemcpyAsync(r2, E.x + E.nvec * k + ov, sizeof(double) * (E.nvec - ov), hipMemcpyDeviceToHost, cx.stream));

@@ -19,6 +19,9 @@ module afesp_capi
              afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
              afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
+             afesp_ccsd_so_eom_lsigma, afesp_ccsd_so_eom_left_init, afesp_ccsd_so_eom_left_guess, afesp_ccsd_so_eom_left_set_guess, &
+             afesp_ccsd_so_eom_left_iterate, afesp_ccsd_so_eom_left_get_vector, afesp_ccsd_so_eom_ref_coupling, &
+             afesp_ccsd_so_eom_density, &
              afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
              afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
@@ -473,6 +476,68 @@ module afesp_capi
          type(c_ptr), value :: ctx
          integer(c_int), value :: k
          real(c_double), intent(out) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      ! EOM-EE-CCSD left eigenvectors (the right-hand calls on a second Davidson state, for A^T), the coupling of right vectors to the
+      ! reference and the bilinear one-particle density (include/afesp.h)
+      function afesp_ccsd_so_eom_lsigma(ctx, nvec, l1, l2, s1, s2) bind(C, name='afesp_ccsd_so_eom_lsigma') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nvec
+         real(c_double), intent(in) :: l1(*), l2(*)
+         real(c_double), intent(out) :: s1(*), s2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_left_init(ctx, nroots, max_space) bind(C, name='afesp_ccsd_so_eom_left_init') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nroots, max_space
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_left_guess(ctx) bind(C, name='afesp_ccsd_so_eom_left_guess') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_left_set_guess(ctx, k, l1, l2) bind(C, name='afesp_ccsd_so_eom_left_set_guess') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: k
+         real(c_double), intent(in) :: l1(*), l2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_left_iterate(ctx, tol, omega, resnorm, flags, nsigma, converged) &
+         bind(C, name='afesp_ccsd_so_eom_left_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: tol
+         real(c_double), intent(out) :: omega(*), resnorm(*)
+         integer(c_int), intent(out) :: flags(*), nsigma, converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_left_get_vector(ctx, k, l1, l2) bind(C, name='afesp_ccsd_so_eom_left_get_vector') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: k
+         real(c_double), intent(out) :: l1(*), l2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ref_coupling(ctx, nvec, r1, r2, c) bind(C, name='afesp_ccsd_so_eom_ref_coupling') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nvec
+         real(c_double), intent(in) :: r1(*), r2(*)
+         real(c_double), intent(out) :: c(*)
+         integer(c_int) :: rc
+      end function
+      ! (l1 / l2 and r1 / r2 are C pointers: c_null_ptr for an absent vector, c_loc of the array otherwise)
+      function afesp_ccsd_so_eom_density(ctx, l0, l1, l2, r0, r1, r2, d, capacity) bind(C, name='afesp_ccsd_so_eom_density') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: l0, r0
+         type(c_ptr), value :: l1, l2, r1, r2
+         real(c_double), intent(out) :: d(*)
+         integer(c_int64_t), value :: capacity
          integer(c_int) :: rc
       end function
       ! EOM-IP-CCSD / EOM-EA-CCSD: the same calls with a sector (AFESP_EOM_IP, AFESP_EOM_EA) behind the context (include/afesp.h)

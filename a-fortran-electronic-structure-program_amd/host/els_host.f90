@@ -57,6 +57,8 @@ module host_config
       logical :: cc_lambda_t = .false.
       ! after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (0: off)
       integer :: eom_nroots = 0
+      ! ... and their left eigenvectors, from the right ones as guess (needs eom_nroots > 0)
+      logical :: eom_left = .false.
       ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
       integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
    end type
@@ -70,10 +72,11 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
+      logical :: eom_left
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -84,7 +87,7 @@ contains
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
       cc_lambda_t = d%cc_lambda_t
-      eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots
+      eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -151,6 +154,9 @@ contains
       if (eom_nroots < 0) call fail('system::read_system_in', 'eom_nroots must be a non-negative integer!')
       if (eom_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
          trim(calc_type)//' takes no eom_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
+      cfg%eom_left = eom_left
+      if (eom_left .and. eom_nroots == 0) call fail('system::read_system_in', &
+         'eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!')
       cfg%eom_ip_nroots = eom_ip_nroots; cfg%eom_ea_nroots = eom_ea_nroots
       if (eom_ip_nroots < 0) call fail('system::read_system_in', 'eom_ip_nroots must be a non-negative integer!')
       if (eom_ea_nroots < 0) call fail('system::read_system_in', 'eom_ea_nroots must be a non-negative integer!')
@@ -1443,8 +1449,8 @@ contains
    subroutine eom_excitations(o, v)
       integer, intent(in) :: o, v
       real(dp), parameter :: hartree_ev = 27.211386245988_dp, eom_tol = 1.0e-8_dp
-      real(dp), allocatable :: omega(:), res(:), x1(:), x2(:), w1(:)
-      integer(c_int), allocatable :: flags(:)
+      real(dp), allocatable :: omega(:), res(:), x1(:), x2(:), w1(:), omega_l(:), res_l(:)
+      integer(c_int), allocatable :: flags(:), flags_l(:)
       integer(c_int) :: nsig, econv
       integer :: nr, ms, it, k
       integer(c_int64_t) :: o8, v8, nunique   ! (o^2 v^2 and the pair counts leave 32 bits long before the state leaves the device)
@@ -1492,6 +1498,37 @@ contains
          end if
       end do
       write (out, '(75("-"))')
+      ! eom_left: the left eigenvectors of the same roots on a Davidson state of its own, from the right vectors as guess
+      if (cfg%eom_left) then
+         rc = afesp_ccsd_so_eom_left_init(ctx, int(nr, c_int), int(ms, c_int))
+         if (rc /= 0) call fail('eom::init_left', afesp_error_text(ctx))
+         do k = 1, nr
+            rc = afesp_ccsd_so_eom_get_vector(ctx, int(k - 1, c_int), x1, x2)
+            if (rc /= 0) call fail('eom::get_vector', afesp_error_text(ctx))
+            rc = afesp_ccsd_so_eom_left_set_guess(ctx, int(k - 1, c_int), x1, x2)
+            if (rc /= 0) call fail('eom::left_guess', afesp_error_text(ctx))
+         end do
+         allocate (omega_l(nr), res_l(nr), flags_l(nr))
+         ok = .false.
+         do it = 1, 100
+            rc = afesp_ccsd_so_eom_left_iterate(ctx, eom_tol, omega_l, res_l, flags_l, nsig, econv)
+            if (rc /= 0) call fail('eom::left_davidson_step', afesp_error_text(ctx))
+            if (econv /= 0) then
+               ok = .true.
+               exit
+            end if
+         end do
+         if (.not. ok) call fail('eom::do_eom_left', 'the left EOM-CCSD Davidson iteration did not converge!')
+         write (out, '(1X, A, 1X, I0, A, I0)') 'Left eigenvectors: Davidson steps:', it, ', sigma builds: ', nsig
+         write (out, '(75("-"))')
+         write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Root', 'omega left (Eh)   ', ' omega left (eV)  ', '|left-right|', ' Residual '
+         write (out, '(75("-"))')
+         do k = 1, nr
+            write (out, '(1X, I4, 3X, F18.12, 3X, F18.10, 3X, ES12.3, 3X, ES10.3)') k, omega_l(k), omega_l(k)*hartree_ev, &
+               abs(omega_l(k) - omega(k)), res_l(k)
+         end do
+         write (out, '(75("-"))')
+      end if
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for EOM-CCSD:', seconds() - te, 's'
    end subroutine
    !> eom_ip_nroots / eom_ea_nroots: the lowest EOM-IP-CCSD ionisation potentials (1h + 2h1p) or EOM-EA-CCSD electron affinities (1p + 2p1h) of the

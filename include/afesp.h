@@ -270,6 +270,37 @@ int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double*
 int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2);
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr);
 
+/* EOM-EE-CCSD left eigenvectors, and excited-state and transition densities.  EOM-CC is not Hermitian: a root's left
+ * eigenvector l A = omega l differs from its right one.  Vectors are host arrays laid out as t1 / t2, as above, with the same metric;
+ * every call needs the live Lambda state (status 21 without one or with a stale one, 20 where Lambda is refused) and writes nothing of
+ * t1 / t2, lambda, the Lambda state or the right-hand EOM state.
+ *   afesp_ccsd_so_eom_lsigma       = s = A^T l for nvec vectors stored one after the other; needs no afesp_ccsd_so_eom_left_init.
+ *   afesp_ccsd_so_eom_left_init    = a second block Davidson state, for A^T, beside the right-hand one and with its rules (arguments,
+ *                                    release); _left_guess (the same unit vectors: -D is the diagonal of A^T too), _left_set_guess (the
+ *                                    converged right vectors are the natural guess), _left_iterate and _left_get_vector are the
+ *                                    right-hand calls on that state, with one difference: started by _left_set_guess, the iteration
+ *                                    follows the Ritz values of its first step (the right-hand roots, when the guesses are converged
+ *                                    right vectors) and returns the Ritz pairs nearest to them, not the lowest roots.
+ *   afesp_ccsd_so_eom_ref_coupling = c[k] = sum H_ia r_ia + 1/4 sum <ij||ab> r_ijab of nvec right vectors: the coupling of R to the
+ *                                    reference, r0 = c / omega.
+ *   afesp_ccsd_so_eom_density      = d [(nocc+nvirt)^2, column-major, symmetric, in the state's spin-orbital order]: with
+ *                                      F(f) = <0| (l0 + L) H-bar (r0 + R) |0>
+ *                                           = l0 r0 E + l0 dE.r + r0 <l, R(t)> + <l, A r> + E <l, r> + sum l_ijab r_ia R1_jb,
+ *                                    d_pq = 1/2 (dF/df_pq + dF/df_qp), bilinear in (l0, l) and (r0, r).  l1 / l2 are both NULL (a zero
+ *                                    vector, not read) or both given, and so are r1 / r2 (status 1 otherwise); status 22 if capacity <
+ *                                    (nocc+nvirt)^2.  (1, lambda; 1, 0) is afesp_ccsd_so_density; (0, L_k; r0_k, R_k) with <L_k, R_k> = 1
+ *                                    the correlation part of excited state k's density; (1, lambda; r0_k, R_k) and (0, L_k; 1, 0) the
+ *                                    transition densities gamma^0k and gamma^k0. */
+int afesp_ccsd_so_eom_lsigma(afesp_ctx* ctx, int nvec, const double* l1, const double* l2, double* s1, double* s2);
+int afesp_ccsd_so_eom_left_init(afesp_ctx* ctx, int nroots, int max_space);
+int afesp_ccsd_so_eom_left_guess(afesp_ctx* ctx);
+int afesp_ccsd_so_eom_left_set_guess(afesp_ctx* ctx, int k, const double* l1, const double* l2);
+int afesp_ccsd_so_eom_left_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged);
+int afesp_ccsd_so_eom_left_get_vector(afesp_ctx* ctx, int k, double* l1, double* l2);
+int afesp_ccsd_so_eom_ref_coupling(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* c);
+int afesp_ccsd_so_eom_density(afesp_ctx* ctx, double l0, const double* l1, const double* l2, double r0, const double* r1, const double* r2,
+                              double* d, int64_t capacity);
+
 /* EOM-IP-CCSD and EOM-EA-CCSD on the same state: ionisation potentials omega = E(N-1) - E(N) in the 1h + 2h1p sector,
  * r1(nocc), r2(nocc,nocc,nvirt) antisymmetric in its first two indices, and electron affinities omega = E(N+1) - E(N) in the 1p + 2p1h
  * sector, r1(nvirt), r2(nocc,nvirt,nvirt) antisymmetric in its last two.  <x, y> = sum x1 y1 + 1/2 sum x2 y2; the unique amplitudes are

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Prints the per-product table of tests/test_gpu_eom_mid.py: every product of one so_eom_sigma at the three mid-size shapes with its
 kernel extents, tile code, K slices and staging width, from the launcher's own lines (AFESP_GETT_DEBUG, AFESP_CONTRACT_TRACE), and which
-of them the tall kernel takes once AFESP_TALL_MIN is o^2 v."""
+of them the tall kernel takes once AFESP_TALL_MIN is o^2 v.  With --left the table of tests/test_gpu_eom_left_mid.py: the products of
+one so_eom_lsigma; with --density those of one so_eom_density with both vectors given."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "a-fortran-electronic-structure-program_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -15,7 +16,7 @@ import np_lambda
 from afesp_amd.capi import Engine
 from test_gpu_lambda import _build_case, _feed
 from test_gpu_lambda_mid import MID
-name = sys.argv[1]
+name, what = sys.argv[1], sys.argv[2]
 c = _build_case(name, *MID[name])
 rng = np.random.default_rng(7)
 t = np_lambda.antisym_random(rng, c["o"], c["v"])
@@ -25,10 +26,18 @@ with Engine(0) as eng:
     eng.so_set_amplitudes(*t)
     eng.so_lambda_init(0)
     sys.stderr.write("SIGMA BEGINS\\n"); sys.stderr.flush()
-    eng.so_eom_sigma(*r)
+    if what == "sigma":
+        eng.so_eom_sigma(*r)
+    elif what == "left":
+        eng.so_eom_lsigma(*r)
+    else:
+        eng.so_eom_density(0.7, np_lambda.antisym_random(np.random.default_rng(11), c["o"], c["v"]), -0.4, r)
 """
 LAUNCH = re.compile(r"gett_launch M (\d+) N (\d+) K (\d+) batch \d+ akc \d bkc \d wide (\d) -> tm (\d+) tn (\d+) tiles \d+ x \d+ split (\d+)")
 TRACE = re.compile(r"contract (\S+)\s*,(\S+)\s*>(\S+)\s+M\s+(\d+) N\s+(\d+) K\s+(\d+) akc \d bkc \d wide (\d)[^\n]*?(\(repacked\)|\(tall\))?$")
+
+
+WHAT = "left" if "--left" in sys.argv else ("density" if "--density" in sys.argv else "sigma")
 
 
 def run(name, tall_min=None):
@@ -36,7 +45,7 @@ def run(name, tall_min=None):
     if tall_min is not None:
         env["AFESP_TALL_MIN"] = str(tall_min)
     src = CHILD.format(pkg=os.path.join(ROOT, "a-fortran-electronic-structure-program_amd"), tests=os.path.join(ROOT, "tests"))
-    err = subprocess.run([sys.executable, "-c", src, name], env=env, capture_output=True, text=True, timeout=600, check=True).stderr
+    err = subprocess.run([sys.executable, "-c", src, name, WHAT], env=env, capture_output=True, text=True, timeout=600, check=True).stderr
     rows, last = [], None
     for line in err.split("SIGMA BEGINS\n", 1)[1].splitlines():
         m = LAUNCH.search(line)

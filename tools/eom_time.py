@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """One EOM-CCSD sigma build and one Davidson step next to one Lambda iteration, on the same spin-orbital state at the H2O/cc-pVTZ shape
 (n = 58, 10 electrons -> o = 10, v = 106 spin orbitals; synthetic integrals as tools/so_time.py).  Wall times of the calls, each
-synchronised by its own host read; the median of the repeats after one warm call.  DESIGN.md 4.13 records the numbers."""
+synchronised by its own host read; the median of the repeats after one warm call.  DESIGN.md 4.13 records the numbers.  Beside the
+right-hand sigma build: one left sigma build and one density call with both vectors given."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "a-fortran-electronic-structure-program_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -40,6 +41,12 @@ with Engine(0) as eng:
     s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
     one = lambda: eng._chk(eng.L.afesp_ccsd_so_eom_sigma(eng.h, 1, a1, a2, s1, s2))
     print("sigma, host in/out   median %8.2f ms  (min %.2f, max %.2f): one vector with its two copies of %.1f MB" % (*median_ms(one), a2.nbytes / 1e6))
+    left = lambda: eng._chk(eng.L.afesp_ccsd_so_eom_lsigma(eng.h, 1, a1, a2, s1, s2))
+    print("left sigma, host i/o median %8.2f ms  (min %.2f, max %.2f)" % median_ms(left))
+    l1, l2 = np.ascontiguousarray(a1[::-1]), np.ascontiguousarray(-a2)
+    d = np.zeros((so + sv) ** 2)
+    dens = lambda: eng._chk(eng.L.afesp_ccsd_so_eom_density(eng.h, 0.7, l1.ctypes.data, l2.ctypes.data, -0.4, a1.ctypes.data, a2.ctypes.data, d, d.size))
+    print("density, host in/out median %8.2f ms  (min %.2f, max %.2f): two vectors in, (o+v)^2 out" % median_ms(dens))
     eng.so_eom_init(nroots, 8 * nroots)
     eng.so_eom_guess()
     eng.so_eom_iterate(1e-8)                                               # (the guess step: nroots sigma builds)
