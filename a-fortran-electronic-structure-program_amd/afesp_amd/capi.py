@@ -30,6 +30,7 @@ EXPORTS = [
     "afesp_ccsd_so_set_amplitudes", "afesp_ccsd_so_get_tensor", "afesp_ccsd_so_t_ntriples", "afesp_ccsd_so_t",
     "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density", "afesp_ccsd_so_lambda_t",
+    "afesp_ccsd_so_density2_build", "afesp_ccsd_so_density2_get", "afesp_ccsd_so_density2_energy", "afesp_ccsd_so_density2_expect",
     "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
     "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
     "afesp_ccsd_so_eom_lsigma", "afesp_ccsd_so_eom_left_init", "afesp_ccsd_so_eom_left_guess", "afesp_ccsd_so_eom_left_set_guess",
@@ -122,6 +123,10 @@ def load_library():
     L.afesp_ccsd_so_set_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_density.argtypes = [C.c_void_p, _dp, i64]
     L.afesp_ccsd_so_lambda_t.argtypes = [C.c_void_p, i64, i64, C.POINTER(dbl)]
+    L.afesp_ccsd_so_density2_build.argtypes = [C.c_void_p]
+    L.afesp_ccsd_so_density2_get.argtypes = [C.c_void_p, C.c_char_p, _opt, i64]
+    L.afesp_ccsd_so_density2_energy.argtypes = [C.c_void_p, _opt]
+    L.afesp_ccsd_so_density2_expect.argtypes = [C.c_void_p, _opt, _opt, _opt]
     L.afesp_ccsd_so_eom_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_sigma.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_guess.argtypes = [C.c_void_p]
@@ -823,6 +828,46 @@ class Engine:
         e = dbl()
         self._chk(self.L.afesp_ccsd_so_lambda_t(self.h, t_begin, t_end, C.byref(e)))
         return e.value
+
+    # ---- the two-particle density of the spin-orbital state (include/afesp.h; afesp_amd.density drives them).  All need a
+    # live Lambda state; get / energy / expect need a build of the current t and lambda (status 21 otherwise)
+    def so_density2_build(self):
+        """The correlation part of the two-particle density for the current t and lambda, kept on the device"""
+        self._chk(self.L.afesp_ccsd_so_density2_build(self.h))
+
+    def so_density2_shape(self, name):
+        o, v = self.so_o, self.so_v
+        if name == "vvvv_pairs":
+            return (v * (v - 1) // 2,) * 2
+        if name == "full":
+            return (o + v,) * 4
+        if name not in ("oooo", "ooov", "oovv", "ovov", "ovvv", "vvvv"):
+            raise ValueError(f"so_density2_get: unknown name {name}")
+        return tuple(o if ch == "o" else v for ch in name)
+
+    def so_density2_get(self, name, capacity=None):
+        """A stored block (oooo ooov oovv ovov ovvv), the pair matrix vvvv_pairs, or the host-side expansions vvvv and full"""
+        dims = self.so_density2_shape(name)
+        buf = np.zeros(max(int(np.prod(dims)), 1))
+        n = int(np.prod(dims))
+        self._chk(self.L.afesp_ccsd_so_density2_get(self.h, name.encode(), buf.ctypes.data_as(C.c_void_p), n if capacity is None else capacity))
+        return buf[:n].reshape(dims, order="F")
+
+    def so_density2_energy(self):
+        """[sum f D, the six 1/4 sum g Gamma family contributions (oooo ooov oovv ovov ovvv vvvv), their sum]"""
+        e = np.zeros(8)
+        self._chk(self.L.afesp_ccsd_so_density2_energy(self.h, e.ctypes.data_as(C.c_void_p)))
+        return e
+
+    def so_density2_expect(self, a, b):
+        """sum_pqrs Gamma_pqrs A_pr B_qs for two (o+v) x (o+v) matrices in the state's spin-orbital order"""
+        n = self.so_o + self.so_v
+        a, b = _f(a), _f(b)
+        if a.size != n * n or b.size != n * n:
+            raise ValueError("so_density2_expect: A and B are (o+v) x (o+v)")
+        val = dbl()
+        self._chk(self.L.afesp_ccsd_so_density2_expect(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(val)))
+        return val.value
 
     # ---- EOM-EE-CCSD excitation energies of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them).  All need a live Lambda
     # state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes t1 / t2 or lambda

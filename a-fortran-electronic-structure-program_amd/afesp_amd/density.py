@@ -1,5 +1,6 @@
 """The Lambda solve of a spin-orbital CCSD state and what follows from its unrelaxed one-particle density: the spin blocks, natural
-occupation numbers and one-electron expectation values (host code; the device calls are Engine.so_lambda_* / so_density).
+occupation numbers and one-electron expectation values (host code; the device calls are Engine.so_lambda_* / so_density), and from its
+two-particle density (Engine.so_density2_*): the full two-particle density, <S^2> and the density-side energy.
 
 Spin-orbital orders of the engine's states (include/afesp.h): the RHF-fed state (Engine.init_cc_spinorb) is interleaved -- spin orbital
 2 P + spin over the spatial orbitals P in level order; the UHF- and Fock-fed states (init_cc_uspinorb, uso_init_fock) are block-ordered --
@@ -88,3 +89,62 @@ def expectation(da, db, a_mo_alpha, a_mo_beta=None):
     """<A> of a one-electron operator given in the MO basis of each spin (the beta matrix defaults to the alpha one)"""
     a_mo_beta = a_mo_alpha if a_mo_beta is None else a_mo_beta
     return float(np.sum(da * np.asarray(a_mo_alpha)) + np.sum(db * np.asarray(a_mo_beta)))
+
+
+def total_rdm2(d, gamma, nocc):
+    """<a+_p a+_q a_s a_r> over the spin orbitals from the engine's correlation parts d (so_density) and gamma (so_density2_get("full")): the
+    reference determinant's part, the one-particle parts and gamma.  An (o+v)^4 array: for small cases."""
+    d, gamma = np.asarray(d, dtype=np.float64), np.asarray(gamma, dtype=np.float64)
+    g0 = np.diag((np.arange(d.shape[0]) < nocc).astype(np.float64))
+    ref = np.einsum("pr,qs->pqrs", g0, g0) - np.einsum("ps,qr->pqrs", g0, g0)
+    one = (np.einsum("pr,qs->pqrs", d, g0) + np.einsum("qs,pr->pqrs", d, g0) - np.einsum("ps,qr->pqrs", d, g0)
+           - np.einsum("qr,ps->pqrs", d, g0))
+    return ref + one + gamma
+
+
+def _spin_flip_overlap(nbasis, nalpha, nbeta, interleaved, beta_in_alpha):
+    """(alpha spin orbitals, beta spin orbitals, S[beta spin orbital, alpha spin orbital])"""
+    orb, spin = so_spin_order(nbasis, nalpha, nbeta, interleaved)
+    ia, ib = np.where(spin == 0)[0], np.where(spin == 1)[0]
+    m = np.eye(int(nbasis)) if beta_in_alpha is None else np.asarray(beta_in_alpha, dtype=np.float64)
+    return ia, ib, m[np.ix_(orb[ib], orb[ia])]
+
+
+def _spin_flip_pair(x, y, ia, ib, s):
+    """sum over p, r beta and q, s alpha of (x_pr y_qs - x_ps y_qr) S_ps S_rq"""
+    return float(np.trace(x[np.ix_(ib, ib)] @ s @ y[np.ix_(ia, ia)] @ s.T) - np.sum(x[np.ix_(ib, ia)] * s) * np.sum(y[np.ix_(ia, ib)] * s.T))
+
+
+def s_squared_reference(nbasis, nalpha, nbeta, interleaved, beta_in_alpha=None):
+    """<S^2> of the reference determinant of a state: N/2 + Ms^2 - sum over occupied alpha a and beta b of <b|a>^2"""
+    ia, ib, s = _spin_flip_overlap(nbasis, nalpha, nbeta, interleaved, beta_in_alpha)
+    g0 = np.diag((np.arange(2 * int(nbasis)) < nalpha + nbeta).astype(np.float64))
+    ms = 0.5 * (nalpha - nbeta)
+    return 0.5 * (nalpha + nbeta) + ms * ms - _spin_flip_pair(g0, g0, ia, ib, s)
+
+
+def s_squared(eng, nbasis, nalpha, nbeta, interleaved, beta_in_alpha=None):
+    """<S^2> = N/2 + Ms^2 - sum_PQ Gtot[P beta, Q alpha, Q beta, P alpha] of the engine's CCSD state (unrelaxed; needs a live Lambda state and
+    so_density2_build for the current t and lambda).  The correlation part goes through Engine.so_density2_expect with the spin-flip
+    overlaps as the two matrices, the reference and one-particle parts are one-body algebra here.  beta_in_alpha as natural_occupations
+    takes it: <beta orbital b | alpha orbital a> where the two spins have different orbitals."""
+    ia, ib, s = _spin_flip_overlap(nbasis, nalpha, nbeta, interleaved, beta_in_alpha)
+    n2 = 2 * int(nbasis)
+    d = eng.so_density()
+    g0 = np.diag((np.arange(n2) < nalpha + nbeta).astype(np.float64))
+    a = np.zeros((n2, n2))
+    a[np.ix_(ib, ia)] = s
+    # Gamma_pqrs S_ps S_rq = -Gamma_pqsr S_ps S_rq: A_pr B_qs with A the (beta, alpha) overlap and B its transpose
+    corr = -eng.so_density2_expect(a, a.T)
+    ms = 0.5 * (nalpha - nbeta)
+    flips = _spin_flip_pair(g0, g0, ia, ib, s) + _spin_flip_pair(d, g0, ia, ib, s) + _spin_flip_pair(g0, d, ia, ib, s) + corr
+    return 0.5 * (nalpha + nbeta) + ms * ms - flips
+
+
+def energy_from_densities(eng):
+    """The density-side correlation energy of the engine's state: -> (e, difference), e the eight numbers of Engine.so_density2_energy
+    (sum f D, the six family contributions of 1/4 sum g Gamma, their sum) and difference = e[0] + e[7] - E(CCSD) at the state's current
+    amplitudes: zero at converged t and lambda, where the discarded Lagrangian terms vanish."""
+    e = eng.so_density2_energy()
+    e_cc = eng.so_energy()[0]
+    return e, float(e[0] + e[7] - e_cc)

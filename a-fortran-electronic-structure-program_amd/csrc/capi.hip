@@ -11,6 +11,7 @@
 #include "../../include/afesp.h"
 #include "integrals.h"
 #include "solver.h"
+#include "density2_so.h"
 #include "eom_so.h"
 #include "eom_ipea_so.h"
 #include "small_eig.h"
@@ -672,6 +673,33 @@ int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2)
 }
 
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr) { return eig_general(n, a, lda, wr, wi, vr); }
+
+// ---- the two-particle density of the spin-orbital state (density2_so.h)
+int afesp_ccsd_so_density2_build(afesp_ctx* ctx)
+{
+    return entry(ctx, [&](Context& cx) { so_density2_build(cx, ctx->sv.need_so("afesp_ccsd_so_density2_build: no spin-orbital CCSD state").so); });
+}
+
+int afesp_ccsd_so_density2_get(afesp_ctx* ctx, const char* name, double* out, int64_t capacity)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_density2_get(cx, ctx->sv.need_so("afesp_ccsd_so_density2_get: no spin-orbital CCSD state").so, name, out, capacity);
+    });
+}
+
+int afesp_ccsd_so_density2_energy(afesp_ctx* ctx, double* e)
+{
+    return entry(ctx, [&](Context& cx) { so_density2_energy(cx, ctx->sv.need_so("afesp_ccsd_so_density2_energy: no spin-orbital CCSD state").so, e); });
+}
+
+int afesp_ccsd_so_density2_expect(afesp_ctx* ctx, const double* A, const double* B, double* value)
+{
+    return entry(ctx, [&](Context& cx) {
+        SOState& s = ctx->sv.need_so("afesp_ccsd_so_density2_expect: no spin-orbital CCSD state").so;
+        if (!value) throw Error(1, "afesp_ccsd_so_density2_expect: NULL argument");
+        *value = so_density2_expect(cx, s, A, B);
+    });
+}
 
 // ---- EOM-EE-CCSD left eigenvectors, reference coupling and the bilinear density (eom_so.h, eom_left_so.hip)
 int afesp_ccsd_so_eom_lsigma(afesp_ctx* ctx, int nvec, const double* l1, const double* l2, double* s1, double* s2)

@@ -65,6 +65,8 @@ void so_build_W_vvvv(Context& cx, SOState& s);    // W_abef itself (ccsd.f90:852
 int so_energy(Context& cx, SOState& s, double e_tol, double t_tol);
 // out(ijab) = sum_{e<f} x(ijef) <ab||ef> over antisymmetric pairs against va (the bare part of so_amplitudes' ladder; x: tau or lambda_2)
 void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out);
+// xa(ij, ef) = x(i,j,e,f) for i < j, e < f with leading dimension lad_na: so_ladder_bare's packer, into a buffer of the caller's
+void so_pair_pack(Context& cx, SOState& s, const Tensor& x, double* xa);
 void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip (releases the EOM state too: it borrows from the Lambda state)
 void so_eom_free(Context& cx, SOState& s);        // eom_so.hip
 void so_eom_ipea_free(Context& cx, SOState& s);   // eom_ipea_so.hip

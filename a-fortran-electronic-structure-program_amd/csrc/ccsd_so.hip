@@ -642,6 +642,13 @@ void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out)
     }
 }
 
+// xa(ij, ef) = x(i,j,e,f), i < j, e < f, in the layout of ta (leading dimension lad_na): the ladder's packer on a caller's buffer
+void so_pair_pack(Context& cx, SOState& s, const Tensor& x, double* xa)
+{
+    const int64_t O = s.o, V = s.v, npv = V * (V - 1) / 2, npo = O * (O - 1) / 2;
+    SO_KERNEL((Ranges{FR(x.d, x.size())}), (Ranges{FR(xa, s.lad_na * npv)}), so_tau_asympack_kernel, npo * npv, xa, x.d, s.o, s.v, s.lad_na);
+}
+
 static void so_ladder(Context& cx, SOState& s)
 {
     const int64_t O = s.o, V = s.v;

@@ -7,10 +7,12 @@
 
 namespace afesp {
 
+struct SODensity2;   // density2_so.h
+
 // statuses of the Lambda entry points beside 1 (argument error: no spin-orbital state) and 2 (HIP error)
 constexpr int LAMBDA_ERR_FOO = 20;        // the state keeps the reference's transposed F_mi term: no consistent Lagrangian
 constexpr int LAMBDA_ERR_STALE = 21;      // no Lambda state, or t1 / t2 may have changed since so_lambda_init
-constexpr int LAMBDA_ERR_CAPACITY = 22;   // so_density: the caller's buffer is too small
+constexpr int LAMBDA_ERR_CAPACITY = 22;   // so_density: the caller's buffer is too small (density2_so.h: or the device memory)
 
 struct SOLambda : DiisRing {   // amp = [l1 ; l2]
     int64_t epoch = -1;        // SOState::amp_epoch the intermediates were built for
@@ -26,6 +28,7 @@ struct SOLambda : DiisRing {   // amp = [l1 ; l2]
     Tensor Hovoo;              // (m,b,i,j)
     Tensor Gvv, Goo;           // G_ae = -1/2 t_mnef l_mnaf, G_mi = 1/2 t_mnef l_inef, of the current l2
     double pseudo = 0.0, pseudo_old = 0.0, rms = 0.0;
+    SODensity2* d2 = nullptr;  // the two-particle density built for one (epoch, stamp) (density2_so.h); released wherever this state is
 };
 
 // device bytes of the Lambda state and its working set (beside so_state_bytes)

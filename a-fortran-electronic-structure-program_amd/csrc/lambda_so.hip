@@ -4,6 +4,7 @@
 // not extended to them.
 #include "device_util.h"
 #include "lambda_so.h"
+#include "density2_so.h"
 
 #include <cmath>
 
@@ -198,6 +199,7 @@ void so_lambda_free(Context& cx, SOState& s)
     so_eom_free(cx, s);   // (it borrows this state's H-bar elements)
     so_eom_ipea_free(cx, s);
     if (!s.lam) return;
+    so_density2_free(cx, *s.lam);
     free_buffers(cx, *s.lam);
     delete s.lam;
     s.lam = nullptr;

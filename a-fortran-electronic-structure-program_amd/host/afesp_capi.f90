@@ -17,6 +17,7 @@ module afesp_capi
              afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
              afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
              afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, &
+             afesp_ccsd_so_density2_build, afesp_ccsd_so_density2_get, afesp_ccsd_so_density2_energy, afesp_ccsd_so_density2_expect, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
              afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
              afesp_ccsd_so_eom_lsigma, afesp_ccsd_so_eom_left_init, afesp_ccsd_so_eom_left_guess, afesp_ccsd_so_eom_left_set_guess, &
@@ -433,6 +434,33 @@ module afesp_capi
          type(c_ptr), value :: ctx
          real(c_double), intent(out) :: d(*)
          integer(c_int64_t), value :: capacity
+         integer(c_int) :: rc
+      end function
+      ! the two-particle density of the current t and lambda of a live Lambda state (include/afesp.h)
+      function afesp_ccsd_so_density2_build(ctx) bind(C, name='afesp_ccsd_so_density2_build') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_density2_get(ctx, name, gamma, capacity) bind(C, name='afesp_ccsd_so_density2_get') result(rc)
+         import :: c_int, c_int64_t, c_double, c_char, c_ptr
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: name(*)
+         real(c_double), intent(out) :: gamma(*)
+         integer(c_int64_t), value :: capacity
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_density2_energy(ctx, e) bind(C, name='afesp_ccsd_so_density2_energy') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), intent(out) :: e(8)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_density2_expect(ctx, a, b, val) bind(C, name='afesp_ccsd_so_density2_expect') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), intent(in) :: a(*), b(*)
+         real(c_double), intent(out) :: val
          integer(c_int) :: rc
       end function
       ! EOM-EE-CCSD excitation energies on the live Lambda state's H-bar elements (include/afesp.h)

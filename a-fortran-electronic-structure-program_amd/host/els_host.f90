@@ -55,6 +55,8 @@ module host_config
       logical :: cc_density = .false.
       ! after a converged spin-orbital CCSD: the Lambda equations and the triples correction with the left-hand state in its left factor
       logical :: cc_lambda_t = .false.
+      ! after a converged spin-orbital CCSD: the Lambda equations, the two-particle density, the density-side energy and <S^2>
+      logical :: cc_rdm2 = .false.
       ! after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (0: off)
       integer :: eom_nroots = 0
       ! ... and their left eigenvectors, from the right ones as guess (needs eom_nroots > 0)
@@ -72,11 +74,11 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left
+      logical :: eom_left, cc_rdm2
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -86,7 +88,7 @@ contains
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
-      cc_lambda_t = d%cc_lambda_t
+      cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
@@ -146,6 +148,11 @@ contains
          trim(calc_type)//' takes no cc_density: the Lambda equations run on the spin-orbital CCSD types!')
       if (cc_density .and. fcidump_in .and. cfg%uhf .and. .not. cfg%rohf) call fail('system::read_system_in', &
          'cc_density on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the spin-summed density needs!')
+      cfg%cc_rdm2 = cc_rdm2
+      if (cc_rdm2 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no cc_rdm2: the Lambda equations run on the spin-orbital CCSD types!')
+      if (cc_rdm2 .and. fcidump_in .and. cfg%uhf .and. .not. cfg%rohf) call fail('system::read_system_in', &
+         'cc_rdm2 on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which <S^2> needs!')
       ! (Lambda-(T) needs no overlap of the alpha and beta orbitals: a UHF FCIDUMP takes it)
       cfg%cc_lambda_t = cc_lambda_t
       if (cc_lambda_t .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
@@ -942,6 +949,10 @@ program els_amd
             if (.not. cfg%rohf) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
             call lambda_and_occupations(n_act, na_act, nb_act, .false.)
          end if
+         if (cfg%cc_rdm2 .and. cc_ok) then
+            if (.not. cfg%rohf .and. .not. allocated(ab_overlap)) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
+            call rdm2_energy_and_spin(n_act, na_act, nb_act, .false.)
+         end if
          if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
@@ -1048,6 +1059,7 @@ program els_amd
          end if
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD:', seconds() - t0, 's'
          if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
+         if (cfg%cc_rdm2 .and. cc_ok) call rdm2_energy_and_spin(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
@@ -1381,6 +1393,28 @@ contains
       end if
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for Lambda-CCSD(T):', seconds() - tl, 's'
    end subroutine
+   !> orbital (within the whole basis: the window starts behind nfc) and spin of every spin orbital of a state over n active orbitals
+   subroutine spin_orbital_map(n, nalpha, nbeta, interleaved, orb, spin)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      integer, intent(out) :: orb(:), spin(:)
+      integer :: x, o
+      o = nalpha + nbeta
+      do x = 1, 2*n
+         if (interleaved) then
+            orb(x) = (x + 1)/2; spin(x) = mod(x + 1, 2)
+         else if (x <= nalpha) then
+            orb(x) = x; spin(x) = 0
+         else if (x <= o) then
+            orb(x) = x - nalpha; spin(x) = 1
+         else if (x <= o + n - nalpha) then
+            orb(x) = nalpha + (x - o); spin(x) = 0
+         else
+            orb(x) = nbeta + (x - o - (n - nalpha)); spin(x) = 1
+         end if
+         orb(x) = orb(x) + nfc
+      end do
+   end subroutine
    !> cc_density: Lambda of the converged spin-orbital CCSD state (Jacobi steps with DIIS, the CCSD table's format), then the spin-summed
    !> natural occupation numbers of the unrelaxed one-particle density over the whole basis (frozen core orbitals doubly occupied, dropped
    !> virtuals empty).  The state's spin-orbital order over its n active orbitals is interleaved (2 P + spin: the RHF-fed state) or blocked
@@ -1399,20 +1433,7 @@ contains
       rc = afesp_ccsd_so_density(ctx, d, int(size(d), c_int64_t))
       if (rc /= 0) call fail('ccsd::density', afesp_error_text(ctx))
       o = nalpha + nbeta
-      do x = 1, 2*n   ! orbital (within the whole basis: the window starts behind nfc) and spin of every spin orbital of the state
-         if (interleaved) then
-            orb(x) = (x + 1)/2; spin(x) = mod(x + 1, 2)
-         else if (x <= nalpha) then
-            orb(x) = x; spin(x) = 0
-         else if (x <= o) then
-            orb(x) = x - nalpha; spin(x) = 1
-         else if (x <= o + n - nalpha) then
-            orb(x) = nalpha + (x - o); spin(x) = 0
-         else
-            orb(x) = nbeta + (x - o - (n - nalpha)); spin(x) = 1
-         end if
-         orb(x) = orb(x) + nfc
-      end do
+      call spin_orbital_map(n, nalpha, nbeta, interleaved, orb, spin)
       ! each spin's density in its own orbitals: the frozen core and the reference determinant on the diagonal, then the correlation part
       ! (which has no element between the spins); the beta one is brought into the alpha orbitals before the two are added
       ds = 0.0_dp; dsb = 0.0_dp
@@ -1443,6 +1464,73 @@ contains
       write (out, '(1X, A, 1X, F14.10)') 'Sum of natural occupation numbers:', sum(occ)
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for CCSD Lambda and density:', seconds() - tl, 's'
    end subroutine
+   !> cc_rdm2: the two-particle density of the converged state and its converged Lambda (one solve serves cc_density, cc_lambda_t and the EOM
+   !> sectors too), the density-side correlation energy sum f D + 1/4 sum g Gamma beside E(CCSD), and <S^2> = N/2 + Ms^2 - sum_PQ
+   !> Gtot[P beta, Q alpha, Q beta, P alpha] of the reference determinant and of CCSD (unrelaxed).  The correlation part of the sum is the
+   !> library's expectation value with the spin-flip overlaps as its two matrices; the reference and one-particle parts are one-body algebra
+   !> over the frozen core (doubly occupied, uncorrelated) and the state's spin orbitals.
+   subroutine rdm2_energy_and_spin(n, nalpha, nbeta, interleaved)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      real(dp), allocatable :: d(:, :), dx(:, :), g0(:, :), a(:, :)
+      integer, allocatable :: orb(:), spin(:), orbx(:), spinx(:)
+      real(dp) :: tl, e8(8), corr, flips_ref, flips, ms, nel
+      integer :: x, y, o, m, c2
+      tl = seconds()
+      if (.not. lambda_live) call lambda_solve()
+      rc = afesp_ccsd_so_density2_build(ctx)
+      if (rc /= 0) call fail('ccsd::density2', afesp_error_text(ctx))
+      rc = afesp_ccsd_so_density2_energy(ctx, e8)
+      if (rc /= 0) call fail('ccsd::density2_energy', afesp_error_text(ctx))
+      write (out, '(1X, A, 1X, F15.12)') 'Density-side CCSD correlation energy (Hartree):', e8(1) + e8(8)
+      write (out, '(1X, A, 1X, ES10.3)') 'Difference to E(CCSD) (Hartree):', e8(1) + e8(8) - e_ccsd
+      o = nalpha + nbeta; c2 = 2*nfc; m = c2 + 2*n
+      allocate (d(2*n, 2*n), dx(m, m), g0(m, m), a(m, m), orb(2*n), spin(2*n), orbx(m), spinx(m))
+      rc = afesp_ccsd_so_density(ctx, d, int(size(d), c_int64_t))
+      if (rc /= 0) call fail('ccsd::density', afesp_error_text(ctx))
+      call spin_orbital_map(n, nalpha, nbeta, interleaved, orb, spin)
+      do x = 1, nfc   ! the frozen core in front: alpha, then beta
+         orbx(x) = x; spinx(x) = 0; orbx(nfc + x) = x; spinx(nfc + x) = 1
+      end do
+      orbx(c2 + 1:) = orb; spinx(c2 + 1:) = spin
+      dx = 0.0_dp; g0 = 0.0_dp; a = 0.0_dp
+      dx(c2 + 1:, c2 + 1:) = d
+      do x = 1, c2 + o
+         g0(x, x) = 1.0_dp
+      end do
+      do y = 1, m   ! a(x beta, y alpha) = <beta orbital of x | alpha orbital of y>
+         do x = 1, m
+            if (spinx(x) /= 1 .or. spinx(y) /= 0) cycle
+            if (allocated(ab_overlap)) then
+               a(x, y) = ab_overlap(orbx(x), orbx(y))
+            else if (orbx(x) == orbx(y)) then
+               a(x, y) = 1.0_dp
+            end if
+         end do
+      end do
+      ! Gamma_pqrs S_ps S_rq = -Gamma_pqsr S_ps S_rq: A_pr B_qs with A the (beta, alpha) overlap over the state's spin orbitals, B = A^T
+      rc = afesp_ccsd_so_density2_expect(ctx, a(c2 + 1:, c2 + 1:), transpose(a(c2 + 1:, c2 + 1:)), corr)
+      if (rc /= 0) call fail('ccsd::density2_expect', afesp_error_text(ctx))
+      flips_ref = flip_pair(g0, g0, a)
+      flips = flips_ref + flip_pair(dx, g0, a) + flip_pair(g0, dx, a) - corr
+      nel = real(c2 + o, dp); ms = 0.5_dp*real(nalpha - nbeta, dp)
+      write (out, '(1X, A, 1X, F14.10)') '<S^2> of the reference determinant:', 0.5_dp*nel + ms*ms - flips_ref
+      write (out, '(1X, A, 1X, F14.10)') '<S^2> of CCSD (unrelaxed two-particle density):', 0.5_dp*nel + ms*ms - flips
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the CCSD two-particle density:', seconds() - tl, 's'
+   end subroutine
+   !> sum over p, r beta and q, s alpha of (x_pr y_qs - x_ps y_qr) S_ps S_rq, S the non-zero (beta, alpha) block of a
+   function flip_pair(xm, ym, a) result(val)
+      real(dp), intent(in) :: xm(:, :), ym(:, :), a(:, :)
+      real(dp) :: val
+      real(dp), allocatable :: w(:, :)
+      integer :: p
+      w = matmul(matmul(xm, a), matmul(ym, transpose(a)))
+      val = 0.0_dp
+      do p = 1, size(w, 1)
+         val = val + w(p, p)
+      end do
+      val = val - sum(xm*a)*sum(ym*transpose(a))
+   end function
    !> eom_nroots: the lowest EOM-EE-CCSD excitation energies of the converged spin-orbital CCSD state (o occupied, v virtual spin orbitals) by
    !> the library's block Davidson iteration.  The H-bar elements are those of the Lambda state: the one cc_density left, else one made here
    !> (Lambda itself is not iterated).  The spin-orbital space holds every Ms component: a triplet appears threefold.

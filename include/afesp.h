@@ -219,6 +219,38 @@ int afesp_ccsd_so_get_lambda(afesp_ctx* ctx, double* l1, double* l2);
 int afesp_ccsd_so_set_lambda(afesp_ctx* ctx, const double* l1, const double* l2);
 int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity);
 
+/* The two-particle density of spin-orbital CCSD: the correlation part Gamma of the current t and l of a live Lambda state,
+ * over all o + v spin orbitals in the state's order (occupied first).  Gamma is antisymmetric in p,q and in r,s, Gamma_pqrs = Gamma_rspq (the
+ * symmetry of real integrals), and normalised so that
+ *   L = sum_pq f_pq D_pq + 1/4 sum_pqrs <pq||rs> Gamma_pqrs     for every (f, g), D that of afesp_ccsd_so_density
+ * -- the derivative of L in g with f held fixed: for p<q, r<s and x the perturbation with +-eps on the antisymmetric images of (pq,rs) and
+ * of (rs,pq), [L(g+x) - L(g-x)] / 2 eps is Gamma_pqrs if (pq) = (rs) and 2 Gamma_pqrs otherwise.  With g0 the reference determinant's
+ * occupation matrix the full density <a+_p a+_q a_s a_r> is
+ *   Gtot_pqrs = (g0_pr g0_qs - g0_ps g0_qr) + (D_pr g0_qs + D_qs g0_pr - D_ps g0_qr - D_qr g0_ps) + Gamma_pqrs,
+ * E_elec = sum h gamma + 1/4 sum g Gtot, and <S^2> = N/2 + Ms^2 - sum_PQ Gtot[P beta, Q alpha, Q beta, P alpha] in one common spatial
+ * basis.  At converged t and l, sum f D + 1/4 sum g Gamma is the CCSD correlation energy.  No orbital relaxation.
+ *   afesp_ccsd_so_density2_build  = Gamma for the current t and l: the unique blocks oooo ooov oovv ovov ovvv, and vvvv only over
+ *                                   antisymmetric pairs (no dense v^4 array exists on the device).  Any later writer of t1 / t2 or l1 / l2
+ *                                   makes the build stale; the calls below then return AFESP_LAMBDA_STALE and read nothing.
+ *   afesp_ccsd_so_density2_get    = name: oooo (i,j,k,l) ooov (i,j,k,a) oovv (i,j,a,b) ovov (i,a,j,b) ovvv (i,a,b,c), the stored block, first
+ *                                   index fastest; vvvv_pairs (ab,cd), a<b, c<d, pair index a + b (b - 1) / 2, [v(v-1)/2]^2 column-major; vvvv,
+ *                                   the dense v^4 expansion, and full, the whole (o+v)^4 Gamma, both written on the host for small cases
+ *                                   and tests.  Every block is antisymmetric / pair-symmetric to the bit, with zero diagonals.
+ *   afesp_ccsd_so_density2_energy = e[0] = sum f D with the state's f (levels on the diagonal, f_ov / f_oo / f_vv where it has them);
+ *                                   e[1..6] = 1/4 sum <pq||rs> Gamma_pqrs over the family oooo, ooov, oovv, ovov, ovvv, vvvv with all its
+ *                                   images; e[7] = e[1] + ... + e[6].
+ *   afesp_ccsd_so_density2_expect = *value = sum_pqrs Gamma_pqrs A_pr B_qs; A, B [(o+v)^2, column-major, the state's order].  The
+ *                                   reference and one-particle parts of a two-body expectation value are one-body algebra of the caller.
+ * None of them writes t1 / t2, l1 / l2, the epochs, the Lambda intermediates (G_vv / G_oo are rebuilt for the current l as
+ * afesp_ccsd_so_density does), a (T) plan or an EOM state.  The build is released with the Lambda state.
+ * Statuses: 1 no spin-orbital state, a NULL argument, an unknown name or a recording context; AFESP_LAMBDA_UNPUBLISHED_FOO as
+ * afesp_ccsd_so_lambda_init; AFESP_LAMBDA_STALE no live Lambda state (build) or no live build (get / energy / expect);
+ * AFESP_LAMBDA_CAPACITY capacity too small (nothing is launched) or the build does not fit the device memory. */
+int afesp_ccsd_so_density2_build(afesp_ctx* ctx);
+int afesp_ccsd_so_density2_get(afesp_ctx* ctx, const char* name, double* out, int64_t capacity);
+int afesp_ccsd_so_density2_energy(afesp_ctx* ctx, double* e /* [8] */);
+int afesp_ccsd_so_density2_expect(afesp_ctx* ctx, const double* A, const double* B, double* value);
+
 /* Lambda-CCSD(T) (Kucharski and Bartlett 1998, Taube and Bartlett 2008; a-CCSD(T) of Crawford and Stanton 1998): the
  * triples correction with the left factor taken from the left-hand state.  With pp_x, hh_x the particle / hole products of x2 with
  * <fp||bc> / <ma||qr>, wc_x the connected and wd_x the disconnected numerator of afesp_ccsd_so_t built from x = t or x = l, P(y) = y(abc)
