@@ -31,6 +31,8 @@ EXPORTS = [
     "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density", "afesp_ccsd_so_lambda_t",
     "afesp_ccsd_so_density2_build", "afesp_ccsd_so_density2_get", "afesp_ccsd_so_density2_energy", "afesp_ccsd_so_density2_expect",
+    "afesp_ccsd_so_orbital_gradient", "afesp_ccsd_so_zvector_apply", "afesp_ccsd_so_zvector_solve", "afesp_ccsd_so_relaxed_density",
+    "afesp_ccsd_so_relax_pair_row",
     "afesp_ccsd_so_eom_init", "afesp_ccsd_so_eom_sigma", "afesp_ccsd_so_eom_guess", "afesp_ccsd_so_eom_set_guess",
     "afesp_ccsd_so_eom_iterate", "afesp_ccsd_so_eom_get_vector", "afesp_eig_general",
     "afesp_ccsd_so_eom_lsigma", "afesp_ccsd_so_eom_left_init", "afesp_ccsd_so_eom_left_guess", "afesp_ccsd_so_eom_left_set_guess",
@@ -127,6 +129,11 @@ def load_library():
     L.afesp_ccsd_so_density2_get.argtypes = [C.c_void_p, C.c_char_p, _opt, i64]
     L.afesp_ccsd_so_density2_energy.argtypes = [C.c_void_p, _opt]
     L.afesp_ccsd_so_density2_expect.argtypes = [C.c_void_p, _opt, _opt, _opt]
+    L.afesp_ccsd_so_orbital_gradient.argtypes = [C.c_void_p, C.c_int, _opt, i64]
+    L.afesp_ccsd_so_zvector_apply.argtypes = [C.c_void_p, _opt, _opt]
+    L.afesp_ccsd_so_zvector_solve.argtypes = [C.c_void_p, dbl, C.c_int, _opt, C.POINTER(C.c_int), C.POINTER(dbl)]
+    L.afesp_ccsd_so_relaxed_density.argtypes = [C.c_void_p, _opt, i64]
+    L.afesp_ccsd_so_relax_pair_row.argtypes = [C.c_void_p, C.c_int, _opt, C.c_int, C.POINTER(dbl)]
     L.afesp_ccsd_so_eom_init.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_sigma.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_guess.argtypes = [C.c_void_p]
@@ -868,6 +875,52 @@ class Engine:
         val = dbl()
         self._chk(self.L.afesp_ccsd_so_density2_expect(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), C.byref(val)))
         return val.value
+
+    # ---- orbital relaxation (include/afesp.h; afesp_amd.density.so_relaxed_density_solve drives them).  All need a build of
+    # the two-particle density of the current t and lambda (status 21 otherwise); w, x, y and z are (o, v) arrays laid out as t1
+    def so_orbital_gradient(self, fock_response=True, capacity=None):
+        """w_ai = dL/dkappa_ai of the Lagrangian on the rotated (f, g); fock_response: f follows the occupied space"""
+        o, v = self.so_o, self.so_v
+        buf = np.zeros(max(o * v, 1))
+        self._chk(self.L.afesp_ccsd_so_orbital_gradient(self.h, int(fock_response), buf.ctypes.data_as(C.c_void_p), o * v if capacity is None else capacity))
+        return buf[:o * v].reshape((o, v), order="F")
+
+    def so_zvector_apply(self, x):
+        """y = A x, A_ai,bj = delta (e_a - e_i) + <ab||ij> + <aj||ib>"""
+        o, v = self.so_o, self.so_v
+        x = _f(x)
+        if x.size != o * v:
+            raise ValueError("so_zvector_apply: x is (o, v)")
+        y = np.zeros(max(o * v, 1))
+        self._chk(self.L.afesp_ccsd_so_zvector_apply(self.h, x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p)))
+        return y[:o * v].reshape((o, v), order="F")
+
+    def so_zvector_solve(self, tol=1e-10, maxiter=100):
+        """A z = -w by preconditioned conjugate gradients on the device -> (z, iterations, residual norm).  Status 25 when tol is not
+        reached (self.so_zvector_last then holds the iteration count and the residual), 24 on a state made by uso_init_fock"""
+        o, v = self.so_o, self.so_v
+        z = np.zeros(max(o * v, 1))
+        it, res = C.c_int(0), dbl(0.0)
+        rc = self.L.afesp_ccsd_so_zvector_solve(self.h, tol, maxiter, z.ctypes.data_as(C.c_void_p), C.byref(it), C.byref(res))
+        self.so_zvector_last = (it.value, res.value)
+        self._chk(rc)
+        return z[:o * v].reshape((o, v), order="F"), it.value, res.value
+
+    def so_relaxed_density(self, capacity=None):
+        """The unrelaxed matrix of so_density plus 1/2 z on the ov and vo blocks (needs a converged so_zvector_solve of the current t, lambda)"""
+        n = self.so_o + self.so_v
+        buf = np.zeros(n * n)
+        self._chk(self.L.afesp_ccsd_so_relaxed_density(self.h, buf.ctypes.data_as(C.c_void_p), buf.size if capacity is None else capacity))
+        return buf.reshape((n, n), order="F")
+
+    def so_relax_pair_row(self, which, reps=0):
+        """Diagnostic (tools/relax_time.py and the tests; not part of the supported interface): the o v^4 term `which` of the orbital gradient
+        alone -> (out (o, v), device ms per call over reps calls after a warm one)"""
+        o, v = self.so_o, self.so_v
+        out = np.zeros(max(o * v, 1))
+        ms = dbl(0.0)
+        self._chk(self.L.afesp_ccsd_so_relax_pair_row(self.h, which, out.ctypes.data_as(C.c_void_p), reps, C.byref(ms)))
+        return out[:o * v].reshape((o, v), order="F"), ms.value
 
     # ---- EOM-EE-CCSD excitation energies of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them).  All need a live Lambda
     # state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes t1 / t2 or lambda

@@ -1,6 +1,7 @@
 """The Lambda solve of a spin-orbital CCSD state and what follows from its unrelaxed one-particle density: the spin blocks, natural
 occupation numbers and one-electron expectation values (host code; the device calls are Engine.so_lambda_* / so_density), and from its
-two-particle density (Engine.so_density2_*): the full two-particle density, <S^2> and the density-side energy.
+two-particle density (Engine.so_density2_*): the full two-particle density, <S^2> and the density-side energy; and the orbital-relaxed
+one-particle density (Engine.so_zvector_solve / so_relaxed_density), which the same helpers take as they take the unrelaxed one.
 
 Spin-orbital orders of the engine's states (include/afesp.h): the RHF-fed state (Engine.init_cc_spinorb) is interleaved -- spin orbital
 2 P + spin over the spatial orbitals P in level order; the UHF- and Fock-fed states (init_cc_uspinorb, uso_init_fock) are block-ordered --
@@ -139,6 +140,21 @@ def s_squared(eng, nbasis, nalpha, nbeta, interleaved, beta_in_alpha=None):
     ms = 0.5 * (nalpha - nbeta)
     flips = _spin_flip_pair(g0, g0, ia, ib, s) + _spin_flip_pair(d, g0, ia, ib, s) + _spin_flip_pair(g0, d, ia, ib, s) + corr
     return 0.5 * (nalpha + nbeta) + ms * ms - flips
+
+
+def so_relaxed_density_solve(eng, tol=1e-10, maxiter=100):
+    """The orbital-relaxed correlation density of the engine's CCSD state: builds the two-particle density of the current
+    t and lambda if there is no live build, solves the Z-vector equations on the device and -> (d_rel, z, iterations).  d_rel is laid out
+    as Engine.so_density: spatial_blocks, natural_occupations and expectation take it as they take the unrelaxed matrix.  Needs a live
+    (converged) Lambda state; a state made by uso_init_fock is refused (status 24), a solve that does not converge raises status 25."""
+    try:
+        z, it, _ = eng.so_zvector_solve(tol, maxiter)
+    except AfespError as err:
+        if not str(err).startswith("status 21:"):   # (AFESP_LAMBDA_STALE: no live build -- or no live Lambda state, which the build reports)
+            raise
+        eng.so_density2_build()
+        z, it, _ = eng.so_zvector_solve(tol, maxiter)
+    return eng.so_relaxed_density(), z, it
 
 
 def energy_from_densities(eng):

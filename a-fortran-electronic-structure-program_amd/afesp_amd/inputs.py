@@ -45,6 +45,7 @@ class SystemIn:
     fno_occ_tol: float = 0.0        # keep every natural virtual whose occupation is at least this; 0 = off
     cc_density: bool = False        # after a converged spin-orbital CCSD: Lambda and the natural occupations (afesp_amd/density.py)
     cc_rdm2: bool = False           # ... Lambda, the two-particle density, the density-side energy and <S^2> (density.s_squared)
+    cc_relaxed: bool = False        # ... Lambda, the two-particle density, the Z-vector and the orbital-relaxed density (density.so_relaxed_density_solve)
     cc_lambda_t: bool = False       # after a converged spin-orbital CCSD: Lambda and the Lambda-CCSD(T) correction (density.so_lambda_t_correction)
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
     eom_left: bool = False          # ... and their left eigenvectors, from the right ones as guess (eom.so_eom_left_solve); needs eom_nroots > 0
@@ -164,6 +165,13 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError(f"{sysin.calc_type} takes no cc_rdm2: the Lambda equations run on the spin-orbital CCSD types!")
     if sysin.cc_rdm2 and sysin.fcidump_in and sysin.calc_type in OPEN_SHELL_TYPES:
         raise ValueError("cc_rdm2 on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which <S^2> needs!")
+    if not isinstance(sysin.cc_relaxed, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.cc_relaxed and sysin.calc_type not in CC_DENSITY_TYPES:
+        raise ValueError(f"{sysin.calc_type} takes no cc_relaxed: the Lambda equations run on the spin-orbital CCSD types!")
+    if sysin.cc_relaxed and (sysin.frozen_core or sysin.n_frozen_core > 0 or sysin.n_frozen_virt > 0 or fno_requested(sysin)):
+        raise ValueError("cc_relaxed with a frozen-core / frozen-virtual window or frozen natural orbitals: the windowed state lacks the "
+                         "core-active integrals that orbital relaxation needs!")
     if not isinstance(sysin.cc_lambda_t, bool):
         raise ValueError("invalid input file format!")
     if sysin.cc_lambda_t and sysin.calc_type not in CC_DENSITY_TYPES:   # (no orbital overlap needed: a UHF FCIDUMP takes it)

@@ -12,6 +12,7 @@
 #include "integrals.h"
 #include "solver.h"
 #include "density2_so.h"
+#include "relax_so.h"
 #include "eom_so.h"
 #include "eom_ipea_so.h"
 #include "small_eig.h"
@@ -122,7 +123,7 @@ void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
 
 extern "C" {
 
-int afesp_version(void) { return 2; }
+int afesp_version(void) { return 3; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -698,6 +699,41 @@ int afesp_ccsd_so_density2_expect(afesp_ctx* ctx, const double* A, const double*
         SOState& s = ctx->sv.need_so("afesp_ccsd_so_density2_expect: no spin-orbital CCSD state").so;
         if (!value) throw Error(1, "afesp_ccsd_so_density2_expect: NULL argument");
         *value = so_density2_expect(cx, s, A, B);
+    });
+}
+
+// ---- orbital relaxation of the spin-orbital density (relax_so.h)
+int afesp_ccsd_so_orbital_gradient(afesp_ctx* ctx, int fock_response, double* w, int64_t capacity)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_orbital_gradient(cx, ctx->sv.need_so("afesp_ccsd_so_orbital_gradient: no spin-orbital CCSD state").so, fock_response, w, capacity);
+    });
+}
+
+int afesp_ccsd_so_zvector_apply(afesp_ctx* ctx, const double* x, double* y)
+{
+    return entry(ctx, [&](Context& cx) { so_zvector_apply(cx, ctx->sv.need_so("afesp_ccsd_so_zvector_apply: no spin-orbital CCSD state").so, x, y); });
+}
+
+int afesp_ccsd_so_zvector_solve(afesp_ctx* ctx, double tol, int maxiter, double* z, int* iters, double* resid)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_zvector_solve(cx, ctx->sv.need_so("afesp_ccsd_so_zvector_solve: no spin-orbital CCSD state").so, tol, maxiter, z, iters, resid);
+    });
+}
+
+int afesp_ccsd_so_relaxed_density(afesp_ctx* ctx, double* d, int64_t capacity)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_relaxed_density(cx, ctx->sv.need_so("afesp_ccsd_so_relaxed_density: no spin-orbital CCSD state").so, d, capacity);
+    });
+}
+
+int afesp_ccsd_so_relax_pair_row(afesp_ctx* ctx, int which, double* out, int reps, double* ms)
+{
+    return entry(ctx, [&](Context& cx) {
+        const double t = so_relax_pair_row(cx, ctx->sv.need_so("afesp_ccsd_so_relax_pair_row: no spin-orbital CCSD state").so, which, out, reps);
+        if (ms) *ms = t;
     });
 }
 

@@ -78,6 +78,8 @@ struct Knobs {
     int t_block = 0;                        // AFESP_T_BLOCK        occupied block size of the (T) enumeration (0: chosen)
     int64_t t_pool_gib = -1;                // AFESP_T_POOL_GIB     (T) block pool budget (-1: a quarter of the device, <= 64 GiB)
     int64_t t_split_tiles = 1024;           // AFESP_T_SPLIT_TILES
+    int relax_mcap = 6016;                  // AFESP_RELAX_MCAP     pair-row kernel: doubles of a pair column per LDS segment (1 .. 6016; tests force segments)
+    int relax_qcap = 2048;                  // AFESP_RELAX_QCAP     ... largest padded o v whose (i,b) slice of Q is staged in LDS (0 .. 2048; 0: never)
     int64_t fcidump_chunk_kib = 4096;       // AFESP_FCIDUMP_CHUNK_KIB  text the FCIDUMP reader parses per round (1 .. 1048576; not tuned)
     // ---------------------------------------------------------------------------------------------------------- DIAGNOSTIC
     int tg_dbg = 0;                         // AFESP_TG_DBG=1       measurement: no C stores
@@ -146,6 +148,8 @@ inline void parse(Knobs& k)
     if ((e = get("AFESP_T_BLOCK"))) k.t_block = atoi(e);
     if ((e = get("AFESP_T_POOL_GIB"))) k.t_pool_gib = (int64_t)atoll(e);
     if ((e = get("AFESP_T_SPLIT_TILES"))) k.t_split_tiles = (int64_t)atoll(e);
+    if ((e = get("AFESP_RELAX_MCAP"))) k.relax_mcap = atoi(e) < 1 ? 1 : atoi(e) > 6016 ? 6016 : atoi(e);
+    if ((e = get("AFESP_RELAX_QCAP"))) k.relax_qcap = atoi(e) < 0 ? 0 : atoi(e) > 2048 ? 2048 : atoi(e);
     if ((e = get("AFESP_FCIDUMP_CHUNK_KIB"))) k.fcidump_chunk_kib = atoll(e) < 1 ? 1 : atoll(e) > (1 << 20) ? (1 << 20) : (int64_t)atoll(e);
     if ((e = get("AFESP_TG_DBG"))) k.tg_dbg = atoi(e);
     k.graph_debug = get("AFESP_GRAPH_DEBUG") != nullptr;

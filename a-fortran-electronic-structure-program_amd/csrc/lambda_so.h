@@ -8,6 +8,7 @@
 namespace afesp {
 
 struct SODensity2;   // density2_so.h
+struct SORelax;      // relax_so.h
 
 // statuses of the Lambda entry points beside 1 (argument error: no spin-orbital state) and 2 (HIP error)
 constexpr int LAMBDA_ERR_FOO = 20;        // the state keeps the reference's transposed F_mi term: no consistent Lagrangian
@@ -29,6 +30,7 @@ struct SOLambda : DiisRing {   // amp = [l1 ; l2]
     Tensor Gvv, Goo;           // G_ae = -1/2 t_mnef l_mnaf, G_mi = 1/2 t_mnef l_inef, of the current l2
     double pseudo = 0.0, pseudo_old = 0.0, rms = 0.0;
     SODensity2* d2 = nullptr;  // the two-particle density built for one (epoch, stamp) (density2_so.h); released wherever this state is
+    SORelax* rx = nullptr;     // the orbital gradient and Z-vector beside it (relax_so.h); released wherever d2 is
 };
 
 // device bytes of the Lambda state and its working set (beside so_state_bytes)
@@ -44,6 +46,9 @@ void so_lambda_energy(Context& cx, SOState& s);
 int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol);   // the host read of either and the convergence rule
 // the symmetrised correlation part of the unrelaxed one-particle density, (o+v)^2 column-major in the state's spin-orbital order
 void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity);
+// the same matrix left on the device (the cached buffer lam_density, valid until the next call of either)
+double* so_density_device(Context& cx, SOState& s, const char* who);
+void so_relax_free(Context& cx, SOLambda& L);   // relax_so.hip
 // Lambda-CCSD(T): the triples [t_begin, t_end) of so_triples' own list with l1 / l2 in the left factor (triples.hip)
 double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);
 void preload_lambda_so();

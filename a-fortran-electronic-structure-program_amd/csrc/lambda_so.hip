@@ -200,6 +200,7 @@ void so_lambda_free(Context& cx, SOState& s)
     so_eom_ipea_free(cx, s);
     if (!s.lam) return;
     so_density2_free(cx, *s.lam);
+    so_relax_free(cx, *s.lam);
     free_buffers(cx, *s.lam);
     delete s.lam;
     s.lam = nullptr;
@@ -401,15 +402,11 @@ int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol)
     return (std::sqrt(h[1]) < l_tol && std::fabs(L.pseudo - L.pseudo_old) < e_tol) ? 1 : 0;
 }
 
-void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity)
+double* so_density_device(Context& cx, SOState& s, const char* who)
 {
-    need_plain(cx);
-    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_density");
+    SOLambda& L = so_lambda_need(s, who);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V;
-    if (!d_host || capacity < N * N)
-        throw Error(LAMBDA_ERR_CAPACITY, "afesp_ccsd_so_density: the buffer holds " + std::to_string(d_host ? capacity : 0) + " doubles, the density needs (o + v)^2 = " +
-                                             std::to_string(N * N));
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
                  const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
     Tensor doo = view(cx.scratch("lam_doo", O * O), {O, O}), dvv = view(cx.scratch("lam_dvv", V * V), {V, V});
@@ -426,6 +423,18 @@ void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity)
     C(-1.0, s.t1, "mb", dvv, "be", 1.0, dov, "me");
     C(-1.0, L.Goo, "mj", s.t1, "je", 1.0, dov, "me");
     LAM_LAUNCH(lam_density_assemble_kernel, blocks_for(N * N), D, doo.d, dvv.d, dov.d, s.t1.d, L.l1.d, o, v);
+    return D;
+}
+
+void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity)
+{
+    need_plain(cx);
+    so_lambda_need(s, "afesp_ccsd_so_density");
+    const int64_t N = (int64_t)s.o + s.v;
+    if (!d_host || capacity < N * N)
+        throw Error(LAMBDA_ERR_CAPACITY, "afesp_ccsd_so_density: the buffer holds " + std::to_string(d_host ? capacity : 0) + " doubles, the density needs (o + v)^2 = " +
+                                             std::to_string(N * N));
+    const double* D = so_density_device(cx, s, "afesp_ccsd_so_density");
     AFESP_HIP(hipMemcpyAsync(d_host, D, sizeof(double) * N * N, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
 }

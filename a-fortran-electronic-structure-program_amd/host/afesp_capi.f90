@@ -18,6 +18,7 @@ module afesp_capi
              afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
              afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, &
              afesp_ccsd_so_density2_build, afesp_ccsd_so_density2_get, afesp_ccsd_so_density2_energy, afesp_ccsd_so_density2_expect, &
+             afesp_ccsd_so_zvector_solve, afesp_ccsd_so_relaxed_density, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
              afesp_ccsd_so_eom_iterate, afesp_ccsd_so_eom_get_vector, afesp_eig_general, &
              afesp_ccsd_so_eom_lsigma, afesp_ccsd_so_eom_left_init, afesp_ccsd_so_eom_left_guess, afesp_ccsd_so_eom_left_set_guess, &
@@ -461,6 +462,24 @@ module afesp_capi
          type(c_ptr), value :: ctx
          real(c_double), intent(in) :: a(*), b(*)
          real(c_double), intent(out) :: val
+         integer(c_int) :: rc
+      end function
+      ! orbital relaxation: the Z-vector equations and the relaxed one-particle density (include/afesp.h)
+      function afesp_ccsd_so_zvector_solve(ctx, tol, maxiter, z, iters, resid) bind(C, name='afesp_ccsd_so_zvector_solve') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: tol
+         integer(c_int), value :: maxiter
+         real(c_double), intent(out) :: z(*)
+         integer(c_int), intent(out) :: iters
+         real(c_double), intent(out) :: resid
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_relaxed_density(ctx, d, capacity) bind(C, name='afesp_ccsd_so_relaxed_density') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), intent(out) :: d(*)
+         integer(c_int64_t), value :: capacity
          integer(c_int) :: rc
       end function
       ! EOM-EE-CCSD excitation energies on the live Lambda state's H-bar elements (include/afesp.h)

@@ -57,6 +57,8 @@ module host_config
       logical :: cc_lambda_t = .false.
       ! after a converged spin-orbital CCSD: the Lambda equations, the two-particle density, the density-side energy and <S^2>
       logical :: cc_rdm2 = .false.
+      ! ... the Lambda equations, the two-particle density, the Z-vector equations and the orbital-relaxed one-particle density
+      logical :: cc_relaxed = .false.
       ! after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (0: off)
       integer :: eom_nroots = 0
       ! ... and their left eigenvectors, from the right ones as guess (needs eom_nroots > 0)
@@ -74,11 +76,11 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left, cc_rdm2
+      logical :: eom_left, cc_rdm2, cc_relaxed
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2, cc_relaxed
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -88,7 +90,7 @@ contains
       frozen_core = d%frozen_core; n_frozen_core = d%n_frozen_core; n_frozen_virt = d%n_frozen_virt
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
-      cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2
+      cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
@@ -153,6 +155,15 @@ contains
          trim(calc_type)//' takes no cc_rdm2: the Lambda equations run on the spin-orbital CCSD types!')
       if (cc_rdm2 .and. fcidump_in .and. cfg%uhf .and. .not. cfg%rohf) call fail('system::read_system_in', &
          'cc_rdm2 on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which <S^2> needs!')
+      cfg%cc_relaxed = cc_relaxed
+      if (cc_relaxed .and. (cfg%rohf .or. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf)))) &
+         call fail('system::read_system_in', trim(calc_type)//' takes no cc_relaxed: the Z-vector equations run on the spin-orbital CCSD '// &
+                   'types with a Hartree-Fock reference!')
+      if (cc_relaxed .and. fcidump_in .and. cfg%uhf) call fail('system::read_system_in', &
+         'cc_relaxed on a UHF FCIDUMP: the file does not hold the overlap of its alpha and beta orbitals, which the spin-summed density needs!')
+      if (cc_relaxed .and. (frozen_core .or. n_frozen_core > 0 .or. n_frozen_virt > 0 .or. fno_n_virt >= 0 .or. fno_occ_tol > 0.0_dp)) &
+         call fail('system::read_system_in', 'cc_relaxed with a frozen-core / frozen-virtual window or frozen natural orbitals: the windowed '// &
+                   'state lacks the core-active integrals that orbital relaxation needs!')
       ! (Lambda-(T) needs no overlap of the alpha and beta orbitals: a UHF FCIDUMP takes it)
       cfg%cc_lambda_t = cc_lambda_t
       if (cc_lambda_t .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
@@ -204,6 +215,7 @@ module host_inputs
       integer :: ncore = 0   ! doubly occupied noble-gas core orbitals of the atoms (-1: an atom beyond Kr, no count)
       real(dp) :: e_nuc = 0.0_dp
       real(dp), allocatable :: ovlp(:, :), hcore(:, :), eri(:)
+      real(dp), allocatable :: ke(:, :), en(:, :)   ! t.dat and v.dat, the two parts of hcore (absent when the integrals come from a FCIDUMP)
    end type
 contains
    pure function pair(i, j) result(ij)     ! 1-based lower-triangle index
@@ -250,16 +262,16 @@ contains
    subroutine read_molecule(mol, engine_reads_eri)
       type(molecule), intent(out) :: mol
       logical, intent(in) :: engine_reads_eri
-      real(dp), allocatable :: ke(:, :), en(:, :), xyz(:, :)
+      real(dp), allocatable :: xyz(:, :)
       integer, allocatable :: z(:)
       integer :: unit, ios, i, j, k, l, a
       integer(i8) :: npair, neri
       real(dp) :: x, charge
       write (out, '(1X, 16("-"))'); write (out, '(1X, A)') 'Integral read-in'; write (out, '(1X, 16("-"))')
       call read_two_index('s.dat', mol%ovlp, mol%nbasis)
-      call read_two_index('t.dat', ke, mol%nbasis)
-      call read_two_index('v.dat', en, mol%nbasis)
-      allocate (mol%hcore(mol%nbasis, mol%nbasis)); mol%hcore = ke + en
+      call read_two_index('t.dat', mol%ke, mol%nbasis)
+      call read_two_index('v.dat', mol%en, mol%nbasis)
+      allocate (mol%hcore(mol%nbasis, mol%nbasis)); mol%hcore = mol%ke + mol%en
       npair = int(mol%nbasis, i8)*(mol%nbasis + 1)/2
       neri = npair*(npair + 1)/2
       allocate (mol%eri(neri)); mol%eri = 0.0_dp
@@ -953,6 +965,10 @@ program els_amd
             if (.not. cfg%rohf .and. .not. allocated(ab_overlap)) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
             call rdm2_energy_and_spin(n_act, na_act, nb_act, .false.)
          end if
+         if (cfg%cc_relaxed .and. cc_ok) then
+            if (.not. allocated(ab_overlap)) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
+            call relaxed_density_report(n_act, na_act, nb_act, .false.)
+         end if
          if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
@@ -1060,6 +1076,7 @@ program els_amd
          write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for unrestricted CCSD:', seconds() - t0, 's'
          if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%cc_rdm2 .and. cc_ok) call rdm2_energy_and_spin(n_act, nel_act/2, nel_act/2, .true.)
+         if (cfg%cc_relaxed .and. cc_ok) call relaxed_density_report(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
@@ -1517,6 +1534,81 @@ contains
       write (out, '(1X, A, 1X, F14.10)') '<S^2> of the reference determinant:', 0.5_dp*nel + ms*ms - flips_ref
       write (out, '(1X, A, 1X, F14.10)') '<S^2> of CCSD (unrelaxed two-particle density):', 0.5_dp*nel + ms*ms - flips
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the CCSD two-particle density:', seconds() - tl, 's'
+   end subroutine
+   !> cc_relaxed: the orbital-relaxed one-particle density of the converged state (DESIGN.md 4.18).  Shares the one Lambda solve; builds the
+   !> two-particle density of the current t and lambda, solves the Z-vector equations on the device and prints the iteration count, the
+   !> residual and the largest |z|, the natural occupation numbers of the relaxed density and -- when t.dat and v.dat were read -- <T> and
+   !> <V_ne> of the unrelaxed and of the relaxed density.  No orbital window (refused with the key): the state's orbitals are all of them.
+   subroutine relaxed_density_report(n, nalpha, nbeta, interleaved)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      real(dp), allocatable :: d(:, :), z(:), da(:, :), db(:, :), ds(:, :), occ(:), u(:, :), ta(:, :), tb(:, :), va(:, :), vb(:, :)
+      integer, allocatable :: orb(:), spin(:)
+      integer(c_int) :: zit
+      real(dp) :: tl, zres, ex(2, 2)
+      integer :: x, y, o, pass
+      tl = seconds()
+      if (.not. lambda_live) call lambda_solve()
+      rc = afesp_ccsd_so_density2_build(ctx)
+      if (rc /= 0) call fail('ccsd::density2', afesp_error_text(ctx))
+      o = nalpha + nbeta
+      allocate (d(2*n, 2*n), z(o*(2*n - o)), da(n, n), db(n, n), orb(2*n), spin(2*n))
+      rc = afesp_ccsd_so_zvector_solve(ctx, 1.0e-10_dp, 100_c_int, z, zit, zres)
+      if (rc /= 0) call fail('ccsd::zvector', afesp_error_text(ctx))
+      write (out, '(1X, A, 1X, I0)') 'Z-vector iterations:', zit
+      write (out, '(1X, A, 1X, ES10.3)') 'Z-vector residual norm:', zres
+      write (out, '(1X, A, 1X, ES14.7)') 'Largest |z|:', maxval(abs(z))
+      call spin_orbital_map(n, nalpha, nbeta, interleaved, orb, spin)
+      if (allocated(mol%ke)) then
+         ta = matmul(coeff, matmul(mol%ke, transpose(coeff))); va = matmul(coeff, matmul(mol%en, transpose(coeff)))
+         if (cfg%uhf) then
+            tb = matmul(cb, matmul(mol%ke, transpose(cb))); vb = matmul(cb, matmul(mol%en, transpose(cb)))
+         else
+            tb = ta; vb = va
+         end if
+      end if
+      do pass = 1, 2   ! the unrelaxed density, then the relaxed one
+         if (pass == 1) then
+            rc = afesp_ccsd_so_density(ctx, d, int(size(d), c_int64_t))
+         else
+            rc = afesp_ccsd_so_relaxed_density(ctx, d, int(size(d), c_int64_t))
+         end if
+         if (rc /= 0) call fail('ccsd::relaxed_density', afesp_error_text(ctx))
+         da = 0.0_dp; db = 0.0_dp   ! each spin's density in its own orbitals, the reference determinant on the diagonal
+         do y = 1, 2*n
+            do x = 1, 2*n
+               if (spin(x) /= spin(y)) cycle
+               if (spin(x) == 0) then
+                  da(orb(x), orb(y)) = da(orb(x), orb(y)) + d(x, y)
+               else
+                  db(orb(x), orb(y)) = db(orb(x), orb(y)) + d(x, y)
+               end if
+            end do
+            if (y <= o .and. spin(y) == 0) da(orb(y), orb(y)) = da(orb(y), orb(y)) + 1.0_dp
+            if (y <= o .and. spin(y) == 1) db(orb(y), orb(y)) = db(orb(y), orb(y)) + 1.0_dp
+         end do
+         if (allocated(mol%ke)) then
+            ex(1, pass) = sum(da*ta) + sum(db*tb); ex(2, pass) = sum(da*va) + sum(db*vb)
+         end if
+         if (pass == 1) cycle
+         if (allocated(ab_overlap)) then
+            ds = da + matmul(transpose(ab_overlap), matmul(db, ab_overlap))
+         else
+            ds = da + db
+         end if
+         ds = 0.5_dp*(ds + transpose(ds))
+         call fno_occupations(ds, occ, u)
+         write (out, '(1X, A)') 'Natural occupation numbers (relaxed CCSD one-particle density, spin-summed):'
+         write (out, '(5(1X, F14.10))') occ
+         write (out, '(1X, A, 1X, F14.10)') 'Sum of relaxed natural occupation numbers:', sum(occ)
+      end do
+      if (allocated(mol%ke)) then
+         write (out, '(1X, A, 1X, F16.8)') '<T> (unrelaxed CCSD density, Hartree):', ex(1, 1)
+         write (out, '(1X, A, 1X, F16.8)') '<T> (relaxed CCSD density, Hartree):', ex(1, 2)
+         write (out, '(1X, A, 1X, F16.8)') '<V_ne> (unrelaxed CCSD density, Hartree):', ex(2, 1)
+         write (out, '(1X, A, 1X, F16.8)') '<V_ne> (relaxed CCSD density, Hartree):', ex(2, 2)
+      end if
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the relaxed CCSD density:', seconds() - tl, 's'
    end subroutine
    !> sum over p, r beta and q, s alpha of (x_pr y_qs - x_ps y_qr) S_ps S_rq, S the non-zero (beta, alpha) block of a
    function flip_pair(xm, ym, a) result(val)

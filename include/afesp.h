@@ -30,7 +30,7 @@
  *   tuning (tile / slice / pool sizes, scheduling):  AFESP_PP_SPLIT, AFESP_PP_TILES, AFESP_REPACK_MIN, AFESP_PLAN_DEVICE_FROM,
  *     AFESP_FUSED_BIG_FLOP, AFESP_FUSED_ITEMS, AFESP_FUSED_MIN_STEPS, AFESP_FUSED_MAX_MFMA, AFESP_FUSED_NB, AFESP_SPLIT_BELOW,
  *     AFESP_SPLIT_MIN_STEPS, AFESP_TG_PATCH, AFESP_TG_GRID, AFESP_TG_PRIO_SHIFT, AFESP_TG_DYNAMIC, AFESP_T_BLOCK, AFESP_T_POOL_GIB,
- *     AFESP_T_SPLIT_TILES, AFESP_FCIDUMP_CHUNK_KIB
+ *     AFESP_T_SPLIT_TILES, AFESP_RELAX_MCAP, AFESP_RELAX_QCAP, AFESP_FCIDUMP_CHUNK_KIB
  *   diagnostics (printing, measurement; no effect on results):  AFESP_TG_DBG, AFESP_GRAPH_DEBUG, AFESP_PRELOAD_DEBUG,
  *     AFESP_FUSED_DEBUG, AFESP_FUSED_PER_OP, AFESP_GETT_DEBUG, AFESP_T_DEBUG, AFESP_CONTRACT_TRACE, AFESP_STAMPS_GROUPED
  */
@@ -250,6 +250,51 @@ int afesp_ccsd_so_density2_build(afesp_ctx* ctx);
 int afesp_ccsd_so_density2_get(afesp_ctx* ctx, const char* name, double* out, int64_t capacity);
 int afesp_ccsd_so_density2_energy(afesp_ctx* ctx, double* e /* [8] */);
 int afesp_ccsd_so_density2_expect(afesp_ctx* ctx, const double* A, const double* B, double* value);
+
+/* Orbital relaxation of the spin-orbital CCSD density (afesp_version 3).  With L(f, g; t, l) the Lagrangian above as a
+ * functional of the state's (f, g), kappa an antisymmetric matrix over all o + v spin orbitals whose only non-zero elements are
+ * kappa_ai = -kappa_ia, and U = exp(kappa):
+ *   afesp_ccsd_so_orbital_gradient = w[i + o a], laid out as t1.  fock_response = 0: w0_ai = d/dkappa_ai L(U^T f U, g transformed by U on all
+ *                                    four indices) at kappa = 0 with t and l held fixed and f, g rotated as plain tensors
+ *                                    = 2 (X_ai - X_ia), X_pq = sum_r f_pr D_rq + 1/2 sum_rst <pr||st> Gamma_qrst; defined for any t and l.
+ *                                    fock_response = 1: f is h + sum_k <pk||qk>, so rotating the occupied space changes f:
+ *                                    w_ai = w0_ai + 2 sum_pq D_pq <pa||qi>.  Any other flag: status 1.
+ *   afesp_ccsd_so_zvector_apply    = y = A x, both [o v] as t1, A_ai,bj = delta_ab delta_ij (e_a - e_i) + <ab||ij> + <aj||ib> with the
+ *                                    state's levels.
+ *   afesp_ccsd_so_zvector_solve    = A z = -w (fock_response = 1) by conjugate gradients from z = 0, preconditioned with e_a - e_i, until
+ *                                    the residual 2-norm is below tol.  *iters and *resid are written whenever the iteration ran; z (may be
+ *                                    NULL) only on success.  Spin-forbidden elements of z stay exact zeros.  On the interleaved
+ *                                    (RHF-fed) state the two spin-exchange parts (below) share the one budget maxiter, *iters is
+ *                                    their sum, and each part is held to tol / sqrt(2), so that *resid, the norm over both, is
+ *                                    below tol: size maxiter for the two parts together.
+ *   afesp_ccsd_so_relaxed_density  = D_rel [(o+v)^2 as afesp_ccsd_so_density] = D with 1/2 z_ai added to the ov and vo blocks, symmetric to
+ *                                    the bit: for h -> h + eps V with the Hartree-Fock reference re-optimised at every eps,
+ *                                    d(E_ref + E_CCSD)/d eps = sum_pq V_pq (g0 + D_rel)_pq at converged t and l.
+ *   afesp_ccsd_so_relax_pair_row   = DIAGNOSTIC, not part of the supported interface and free to disappear: the o v^4 part alone, for
+ *                                    tools/relax_time.py and the tests: out[i + o a] = sum_b sum_{c<d} P(ab;cd) Q(i,b,c,d) with
+ *                                    (P, Q) = (<ab||cd>, Gamma_ibcd) for which = 0 and (Gamma_abcd, <ib||cd>) for which = 1; *ms = device
+ *                                    milliseconds per call over `reps` calls after a warm one (out and ms may be NULL).
+ * Call order: afesp_ccsd_so_lambda_init ... (Lambda converged) -> afesp_ccsd_so_density2_build -> _orbital_gradient / _zvector_apply /
+ * _zvector_solve -> _relaxed_density.  Every call needs the live build of the current t and l, and _relaxed_density a converged solve of
+ * them: whatever writes t1 / t2 or l1 / l2 makes both stale (AFESP_LAMBDA_STALE, nothing is read).  None of the calls writes t1 / t2,
+ * l1 / l2, the epochs, the Lambda intermediates (G_vv / G_oo are rebuilt for the current l as afesp_ccsd_so_density does), Gamma, a (T)
+ * plan or an EOM state; the vectors are released with the Lambda state.
+ * Statuses: 1 no spin-orbital state, a NULL or bad argument or a recording context; AFESP_LAMBDA_STALE as above; AFESP_LAMBDA_CAPACITY
+ * capacity too small (nothing is launched) or no device memory; AFESP_RELAX_NOT_HF _zvector_solve / _relaxed_density on a state made
+ * by afesp_ccsd_uso_init_fock, whose reference is not stationary in the spin-orbital rotations (_orbital_gradient and _zvector_apply
+ * take every state Lambda takes); AFESP_RELAX_NOT_CONVERGED tol not reached within maxiter, or a breakdown p A p = 0 (a singular orbital
+ * Hessian: an instability threshold of the reference; a nearly singular one stagnates and ends at maxiter) -- the solve is then not
+ * usable.  Negative curvature alone (an unstable but stationary reference, A indefinite) does not stop the iteration: the equations
+ * still have their solution.  On the interleaved (RHF-fed) state, whose operator commutes with the exchange of the two spins, the part of
+ * the right-hand side that is symmetric under the exchange and the antisymmetric one are solved one after the other, each kept in its
+ * part to the bit, so that the rounding noise of a spin-pure right-hand side never reaches a triplet instability of the reference. */
+#define AFESP_RELAX_NOT_HF 24
+#define AFESP_RELAX_NOT_CONVERGED 25
+int afesp_ccsd_so_orbital_gradient(afesp_ctx* ctx, int fock_response, double* w /* [o*v], as t1 */, int64_t capacity);
+int afesp_ccsd_so_zvector_apply(afesp_ctx* ctx, const double* x, double* y);
+int afesp_ccsd_so_zvector_solve(afesp_ctx* ctx, double tol, int maxiter, double* z /* may be NULL */, int* iters, double* resid);
+int afesp_ccsd_so_relaxed_density(afesp_ctx* ctx, double* d /* (o+v)^2 as afesp_ccsd_so_density */, int64_t capacity);
+int afesp_ccsd_so_relax_pair_row(afesp_ctx* ctx, int which, double* out, int reps, double* ms);
 
 /* Lambda-CCSD(T) (Kucharski and Bartlett 1998, Taube and Bartlett 2008; a-CCSD(T) of Crawford and Stanton 1998): the
  * triples correction with the left factor taken from the left-hand state.  With pp_x, hh_x the particle / hole products of x2 with
