@@ -22,6 +22,37 @@ def default_max_space(nroots, nunique):
     return max(2 * nroots, min(int(nunique), 8 * nroots))
 
 
+def _davidson(init, guess, set_guess, iterate, vector, nroots, guesses, tol, maxiter, message):
+    """the solve loop of every Davidson state of the library: init() -> max_space, the library's guesses or the caller's, steps until
+    every root has converged -> (omega, vectors, info); message names the iteration where maxiter steps do not converge"""
+    max_space = init()
+    if guesses is None:
+        guess()
+    else:
+        for k, (r1, r2) in enumerate(guesses):
+            set_guess(k, r1, r2)
+    for it in range(1, maxiter + 1):
+        omega, res, flags, nsigma, conv = iterate(tol)
+        if conv:
+            vectors = [vector(k) for k in range(nroots)]
+            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
+                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
+                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
+                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
+            return omega, vectors, info
+    raise AfespError(f"the {message} Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+
+
+def _ee_init(init, eng, nroots, max_space):
+    """-> the init() of _davidson for an EE state, right or left: max_space defaults by the unique singles and doubles"""
+    def run():
+        o, v = eng.so_o, eng.so_v
+        ms = max_space if max_space is not None else default_max_space(nroots, o * v + (o * (o - 1) // 2) * (v * (v - 1) // 2))
+        init(nroots, ms)
+        return ms
+    return run
+
+
 def so_eom_solve(eng, nroots, tol=1e-8, max_space=None, maxiter=100, guesses=None):
     """The nroots lowest EOM-EE-CCSD excitation energies of the engine's spin-orbital state at its current (converged) amplitudes.
     A live Lambda state is needed for its H-bar elements (eng.so_lambda_init, or density.so_lambda_solve); Lambda need not be converged.
@@ -31,26 +62,8 @@ def so_eom_solve(eng, nroots, tol=1e-8, max_space=None, maxiter=100, guesses=Non
     Raises AfespError if maxiter steps do not converge."""
     if maxiter < 1:
         raise ValueError("so_eom_solve: maxiter must be at least 1")
-    o, v = eng.so_o, eng.so_v
-    nunique = o * v + (o * (o - 1) // 2) * (v * (v - 1) // 2)
-    if max_space is None:
-        max_space = default_max_space(nroots, nunique)
-    eng.so_eom_init(nroots, max_space)
-    if guesses is None:
-        eng.so_eom_guess()
-    else:
-        for k, (r1, r2) in enumerate(guesses):
-            eng.so_eom_set_guess(k, r1, r2)
-    for it in range(1, maxiter + 1):
-        omega, res, flags, nsigma, conv = eng.so_eom_iterate(tol)
-        if conv:
-            vectors = [eng.so_eom_vector(k) for k in range(nroots)]
-            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
-                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
-                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
-                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
-            return omega, vectors, info
-    raise AfespError(f"the EOM-CCSD Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+    return _davidson(_ee_init(eng.so_eom_init, eng, nroots, max_space), eng.so_eom_guess, eng.so_eom_set_guess, eng.so_eom_iterate,
+                     eng.so_eom_vector, nroots, guesses, tol, maxiter, "EOM-CCSD")
 
 
 def label_root(x1, x2, nbasis, nalpha, nbeta, interleaved):
@@ -93,26 +106,9 @@ def so_eom_left_solve(eng, right_vectors=None, nroots=None, tol=1e-8, max_space=
         if right_vectors is None:
             raise ValueError("so_eom_left_solve: give nroots or right_vectors")
         nroots = len(right_vectors)
-    o, v = eng.so_o, eng.so_v
-    nunique = o * v + (o * (o - 1) // 2) * (v * (v - 1) // 2)
-    if max_space is None:
-        max_space = default_max_space(nroots, nunique)
-    eng.so_eom_left_init(nroots, max_space)
-    if right_vectors is None:
-        eng.so_eom_left_guess()
-    else:
-        for k, (r1, r2) in enumerate(right_vectors[:nroots]):
-            eng.so_eom_left_set_guess(k, r1, r2)
-    for it in range(1, maxiter + 1):
-        omega, res, flags, nsigma, conv = eng.so_eom_left_iterate(tol)
-        if conv:
-            vectors = [eng.so_eom_left_vector(k) for k in range(nroots)]
-            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
-                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
-                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
-                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
-            return omega, vectors, info
-    raise AfespError(f"the left EOM-CCSD Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+    return _davidson(_ee_init(eng.so_eom_left_init, eng, nroots, max_space), eng.so_eom_left_guess, eng.so_eom_left_set_guess,
+                     eng.so_eom_left_iterate, eng.so_eom_left_vector, nroots, None if right_vectors is None else right_vectors[:nroots],
+                     tol, maxiter, "left EOM-CCSD")
 
 
 def clusters(omega, degeneracy_tol=1e-6):
@@ -195,24 +191,13 @@ def ipea_nunique(sector, o, v):
 def _so_eom_ipea_solve(eng, sector, nroots, tol, max_space, maxiter, guesses):
     if maxiter < 1:
         raise ValueError("so_eom_ip_solve / so_eom_ea_solve: maxiter must be at least 1")
-    if max_space is None:
-        max_space = default_max_space(nroots, ipea_nunique(sector, eng.so_o, eng.so_v))
-    eng.so_eom_ipea_init(sector, nroots, max_space)
-    if guesses is None:
-        eng.so_eom_ipea_guess(sector)
-    else:
-        for k, (r1, r2) in enumerate(guesses):
-            eng.so_eom_ipea_set_guess(sector, k, r1, r2)
-    for it in range(1, maxiter + 1):
-        omega, res, flags, nsigma, conv = eng.so_eom_ipea_iterate(sector, tol)
-        if conv:
-            vectors = [eng.so_eom_ipea_vector(sector, k) for k in range(nroots)]
-            info = dict(iterations=it, nsigma=nsigma, resnorm=res, flags=flags, max_space=max_space,
-                        r1_norm2=np.array([float(np.sum(x1 * x1)) for x1, _ in vectors]),
-                        complex=[k for k in range(nroots) if flags[k] & FLAG_COMPLEX],
-                        degeneracy=np.array([int(np.sum(np.abs(omega - w) < 1e-6)) for w in omega]))
-            return omega, vectors, info
-    raise AfespError(f"the EOM-CCSD Davidson iteration did not converge in {maxiter} steps (residuals {res})")
+    def init():
+        ms = max_space if max_space is not None else default_max_space(nroots, ipea_nunique(sector, eng.so_o, eng.so_v))
+        eng.so_eom_ipea_init(sector, nroots, ms)
+        return ms
+    return _davidson(init, lambda: eng.so_eom_ipea_guess(sector), lambda k, r1, r2: eng.so_eom_ipea_set_guess(sector, k, r1, r2),
+                     lambda t: eng.so_eom_ipea_iterate(sector, t), lambda k: eng.so_eom_ipea_vector(sector, k), nroots, guesses, tol, maxiter,
+                     "EOM-CCSD")
 
 
 def so_eom_ip_solve(eng, nroots, tol=1e-8, max_space=None, maxiter=100, guesses=None):

@@ -651,20 +651,25 @@ int afesp_ccsd_so_eom_set_guess(afesp_ctx* ctx, int k, const double* r1, const d
     return entry(ctx, [&](Context& cx) { so_eom_set_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_set_guess: no spin-orbital CCSD state").so, k, r1, r2); });
 }
 
+// what a Davidson step reports, for the three iterate entry points
+static void davidson_report(const Davidson& E, int conv, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    for (int k = 0; k < E.nroots; ++k) {
+        if (omega) omega[k] = E.omega[k];
+        if (resnorm) resnorm[k] = E.resnorm[k];
+        if (flags) flags[k] = E.flags[k];
+    }
+    if (nsigma) *nsigma = E.nsigma;
+    if (converged) *converged = conv;
+}
+
 int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
 {
     return entry(ctx, [&](Context& cx) {
         SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_iterate: no spin-orbital CCSD state").so;
         if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_iterate: tol must be positive");
         const int conv = so_eom_iterate(cx, so, tol);
-        const SOEom& E = *so.eom;
-        for (int k = 0; k < E.nroots; ++k) {
-            if (omega) omega[k] = E.omega[k];
-            if (resnorm) resnorm[k] = E.resnorm[k];
-            if (flags) flags[k] = E.flags[k];
-        }
-        if (nsigma) *nsigma = E.nsigma;
-        if (converged) *converged = conv;
+        davidson_report(so.eom->d, conv, omega, resnorm, flags, nsigma, converged);
     });
 }
 
@@ -770,14 +775,7 @@ int afesp_ccsd_so_eom_left_iterate(afesp_ctx* ctx, double tol, double* omega, do
         SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_left_iterate: no spin-orbital CCSD state").so;
         if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_left_iterate: tol must be positive");
         const int conv = so_eom_iterate(cx, so, tol, true);
-        const SOEom& E = *so.eom_left;
-        for (int k = 0; k < E.nroots; ++k) {
-            if (omega) omega[k] = E.omega[k];
-            if (resnorm) resnorm[k] = E.resnorm[k];
-            if (flags) flags[k] = E.flags[k];
-        }
-        if (nsigma) *nsigma = E.nsigma;
-        if (converged) *converged = conv;
+        davidson_report(so.eom_left->d, conv, omega, resnorm, flags, nsigma, converged);
     });
 }
 
@@ -838,14 +836,7 @@ int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, doubl
         SOState& so = ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_iterate");
         if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: tol must be positive");
         const int conv = so_eom_ipea_iterate(cx, so, sector, tol);
-        const SOEomX& E = *so.ipea[sector - 1];
-        for (int k = 0; k < E.nroots; ++k) {
-            if (omega) omega[k] = E.omega[k];
-            if (resnorm) resnorm[k] = E.resnorm[k];
-            if (flags) flags[k] = E.flags[k];
-        }
-        if (nsigma) *nsigma = E.nsigma;
-        if (converged) *converged = conv;
+        davidson_report(so.ipea[sector - 1]->d, conv, omega, resnorm, flags, nsigma, converged);
     });
 }
 

@@ -1,0 +1,64 @@
+// davidson_so.h -- the block Davidson iteration for the lowest (or the followed) eigenvalues of a non-symmetric matrix that is given as a
+// sigma build on device vectors.  A vector has n1 elements of weight 1 and nvec - n1 of weight w2 in the metric
+// <x, y> = sum x1 y1 + w2 sum x2 y2; the vectors never leave the device.  The unit knows nothing of coupled cluster: its users are
+// EOM-EE-CCSD, right and left (eom_so.h), and the EOM-IP and EOM-EA sectors (eom_ipea_so.h).
+#pragma once
+#include "afesp_internal.h"
+
+#include <functional>
+#include <string>
+#include <vector>
+
+namespace afesp {
+
+constexpr int EOM_FLAG_CONVERGED = 1;   // per-root flags of davidson_iterate
+constexpr int EOM_FLAG_COMPLEX = 2;     // the projected root has an imaginary part: the real part of its vector is used
+
+struct Davidson {
+    int64_t epoch = -1;          // the owner's stamp of what the sigma build borrows (SOState::amp_epoch of the Lambda state)
+    int nroots = 0, max_space = 0;
+    int64_t n1 = 0, nvec = 0;    // elements of weight 1; all elements
+    double w2 = 0.0;             // weight of the elements behind the first n1
+    // A following state started from the caller's guesses keeps the states it was given: the Ritz values of its first step -- for
+    // eigenvectors of the transposed matrix as guesses these are the roots themselves, their span being invariant -- and at every later
+    // step the Ritz pairs nearest to them, not the lowest ones.  `target` empty: the lowest roots.
+    bool follow = false;
+    std::vector<double> target;
+    int nb = 0;                  // basis columns b_p and their sigma_p
+    int npend = 0;               // pending vectors (guesses or corrections) in `pend`
+    bool user_guess = false;     // the pending vectors are the caller's: a further one joins them instead of starting over
+    bool ritz = false;           // x / sx / omega are those of the current basis
+    double *B = nullptr, *S = nullptr;        // max_space columns each
+    double *pend = nullptr;                   // nroots columns
+    double *x = nullptr, *sx = nullptr;       // Ritz vectors x_k = sum_p y_pk b_p and sum_p y_pk sigma_p, nroots columns each
+    double *corr = nullptr;                   // the corrections of the last Ritz pass, nroots columns
+    double *partial = nullptr, *sums = nullptr, *coef = nullptr;   // reduction partials, their ordered sums, coefficients (device)
+    double *diag = nullptr;      // the diagonal guess of the matrix, nvec long: corr = rho / (omega - diag)
+    std::vector<double> G;       // projected matrix <b_p, sigma_q>, max_space x max_space column-major (host)
+    std::vector<double> omega, resnorm;
+    std::vector<int> flags;
+    int nsigma = 0, ncollapse = 0;
+};
+
+using DavidsonSigma = std::function<void(const double* r, double* sigma)>;   // sigma = A r on device vectors
+
+// device bytes of a state
+double davidson_bytes(double nvec, int nroots, int max_space);
+// fill_diag writes `diag` once (launches on cx.stream).  A failed allocation leaves what was allocated to the caller's davidson_free.
+void davidson_alloc(Context& cx, Davidson& D, int64_t n1, int64_t nvec, double w2, bool follow, int nroots, int max_space,
+                    const std::function<void(double* diag)>& fill_diag);
+void davidson_free(Context& cx, Davidson& D);
+void davidson_restart(Davidson& D);   // no basis, no pending vectors, no targets
+// Messages carry the caller's names: prefix + "iterate", "guess", "set_guess", "get_vector".
+// The caller's guess k from host halves of n1 and nvec - n1 elements; the first of a block of them starts over
+void davidson_set_pending_from_host(Context& cx, Davidson& D, const std::string& prefix, int k, const double* r1, const double* r2);
+// One step: (collapse if the pending vectors do not fit,) orthonormalise the pending vectors, build their sigma, extend the projected
+// matrix, solve it on the host, Ritz pass.  -> 1 when every root has |rho_k| < tol
+int davidson_iterate(Context& cx, Davidson& D, const std::string& prefix, double tol, const DavidsonSigma& sigma);
+void davidson_get_vector(Context& cx, Davidson& D, const std::string& prefix, int k, double* r1, double* r2);
+// the fixed-order reduction of this unit for others: blocks of a partial-sum grid over nvec elements, and out[b] = the ordered sum of
+// partial[b nblk .. (b + 1) nblk)
+int davidson_reduce_blocks(int64_t nvec);
+void davidson_reduce_final(Context& cx, double* out, const double* partial, int nout, int nblk);
+
+}  // namespace afesp

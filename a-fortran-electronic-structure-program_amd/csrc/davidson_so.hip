@@ -1,0 +1,363 @@
+// davidson_so.hip -- the block Davidson iteration of davidson_so.h.  Launches are plain call-by-call ones.  Every
+// reduction is block partials on a grid fixed by the vector length, then an ordered final sum: the same input gives the same bits on
+// every run.
+#include "davidson_so.h"
+#include "device_util.h"
+#include "small_eig.h"
+
+#include <cmath>
+#include <numeric>
+
+namespace afesp {
+namespace {
+
+constexpr int DAV_MAXBLK = 128;   // blocks of a reduction (at most TB: davidson_final_kernel sums them in one block)
+constexpr int DAV_RCHUNK = 8;     // roots one launch of the Ritz pass forms
+constexpr double DAV_DROP = 1e-10, DAV_CLAMP = 1e-4;
+
+// The Gram panel of one vector pair (bq, sq) against ncol stored columns, in one launch -- block (blk, p):
+//   p < ncol:  <b_p, sq>, <s_p, bq>, <b_p, bq>        p = ncol:  <bq, sq>, the same again, <bq, bq>
+// with the weights 1 on the first n1 elements and w2 behind them; partial[(q (ncol + 1) + p) nblk + blk], q = 0, 1, 2.  sq null: the
+// overlaps alone (q = 2; the others are written as zero).
+__global__ void davidson_panel_kernel(double* partial, const double* B, const double* S, int64_t stride, int ncol, const double* bq,
+                                      const double* sq, int64_t nvec, int64_t n1, double w2)
+{
+    __shared__ double sm[3 * 4];
+    const int p = blockIdx.y, nblk = gridDim.x;
+    const double* bp = p < ncol ? B + stride * p : bq;
+    const double* sp = sq ? (p < ncol ? S + stride * p : sq) : nullptr;
+    double acc[3] = {0.0, 0.0, 0.0};
+    GRID_STRIDE(x, nvec)
+    {
+        const double w = x < n1 ? 1.0 : w2, b = bp[x], q = bq[x];
+        if (sp) {
+            acc[0] += w * b * sq[x];
+            acc[1] += w * sp[x] * q;
+        }
+        acc[2] += w * b * q;
+    }
+    block_sum<3>(acc, sm);
+    if (threadIdx.x == 0)
+        for (int q = 0; q < 3; ++q) partial[((int64_t)q * (ncol + 1) + p) * nblk + blockIdx.x] = acc[q];
+}
+
+// out[b] = the sum of partial[b nblk .. (b + 1) nblk) in a fixed order (nblk <= TB)
+__global__ void davidson_final_kernel(double* out, const double* partial, int nblk)
+{
+    __shared__ double red[TB];
+    red[threadIdx.x] = (int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0;
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+// one projection pass: x -= sum_p coef[p] b_p, and the companion sx -= sum_p coef[p] s_p where given
+__global__ void davidson_project_kernel(double* x, double* sx, const double* B, const double* S, int64_t stride, int ncol, const double* coef,
+                                        int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        double a = x[e], sa = sx ? sx[e] : 0.0;
+        for (int p = 0; p < ncol; ++p) {
+            const double c = coef[p];
+            a = __fma_rn(-c, B[stride * p + e], a);
+            if (sx) sa = __fma_rn(-c, S[stride * p + e], sa);
+        }
+        x[e] = a;
+        if (sx) sx[e] = sa;
+    }
+}
+
+__global__ void davidson_scale_kernel(double* dst, const double* src, double* dst2, const double* src2, double scale, int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        dst[e] = __dmul_rn(scale, src[e]);
+        if (src2) dst2[e] = __dmul_rn(scale, src2[e]);
+    }
+}
+
+// The Ritz pass for the roots k0 .. k0 + nr (nr <= DAV_RCHUNK): every stored b_p and sigma_p is read once and gives
+//   x_k = sum_p y(p,k) b_p,  sx_k = sum_p y(p,k) sigma_p,  rho_k = sx_k - omega_k x_k,  corr_k = rho_k / (omega_k - diag)
+// (|omega_k - diag| clamped below at DAV_CLAMP, keeping its sign) and the block partials of <rho_k, rho_k> at
+// partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.
+__global__ void davidson_ritz_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride, int nb,
+                                     const double* y, const double* omega, const double* diag, int64_t n1, double w2, int64_t nvec, int k0, int nr)
+{
+    __shared__ double sm[DAV_RCHUNK * 4];
+    double nrm[DAV_RCHUNK];
+#pragma unroll
+    for (int k = 0; k < DAV_RCHUNK; ++k) nrm[k] = 0.0;
+    GRID_STRIDE(e, nvec)
+    {
+        double xa[DAV_RCHUNK], sa[DAV_RCHUNK];
+#pragma unroll
+        for (int k = 0; k < DAV_RCHUNK; ++k) xa[k] = sa[k] = 0.0;
+        for (int p = 0; p < nb; ++p) {
+            const double b = B[stride * p + e], s = S[stride * p + e];
+#pragma unroll
+            for (int k = 0; k < DAV_RCHUNK; ++k)
+                if (k < nr) {
+                    const double c = y[p + (int64_t)nb * (k0 + k)];
+                    xa[k] = __fma_rn(c, b, xa[k]);
+                    sa[k] = __fma_rn(c, s, sa[k]);
+                }
+        }
+        const double D = diag[e], w = e < n1 ? 1.0 : w2;
+#pragma unroll
+        for (int k = 0; k < DAV_RCHUNK; ++k)
+            if (k < nr) {
+                const double om = omega[k0 + k];
+                const double rho = __fma_rn(-om, xa[k], sa[k]);
+                double den = om - D;
+                if (fabs(den) < DAV_CLAMP) den = den < 0.0 ? -DAV_CLAMP : DAV_CLAMP;
+                X[stride * (k0 + k) + e] = xa[k];
+                SX[stride * (k0 + k) + e] = sa[k];
+                corr[stride * (k0 + k) + e] = rho / den;
+                nrm[k] += w * rho * rho;
+            }
+    }
+    block_sum<DAV_RCHUNK>(nrm, sm);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
+}
+
+void preload_once()
+{
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(davidson_panel_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_final_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_project_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_scale_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_ritz_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
+}
+
+void read_back(Context& cx, double* host, const double* dev, int64_t n)
+{
+    AFESP_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+// the panel of (bq, sq) against the first ncol columns, summed: E.sums[q (ncol + 1) + p]
+void panel(Context& cx, Davidson& E, int ncol, const double* bq, const double* sq)
+{
+    const int nblk = davidson_reduce_blocks(E.nvec);
+    LAUNCH(davidson_panel_kernel, dim3(nblk, ncol + 1), E.partial, E.B, E.S, E.nvec, ncol, bq, sq, E.nvec, E.n1, E.w2);
+    LAUNCH(davidson_final_kernel, dim3(3 * (ncol + 1)), E.sums, E.partial, nblk);
+}
+
+// Two passes of projection of x (and its companion sx) against the first nb columns through the panel, then x / |x| -> column nb of B
+// (sx / |x| -> column nb of S).  -> false: the norm after projection is below DAV_DROP, nothing was stored
+bool orthonormalise(Context& cx, Davidson& E, double* x, double* sx)
+{
+    const int nb = E.nb;
+    if (nb > 0)
+        for (int pass = 0; pass < 2; ++pass) {
+            panel(cx, E, nb, x, nullptr);
+            LAUNCH(davidson_project_kernel, grid_for(E.nvec), x, sx, E.B, E.S, E.nvec, nb, E.sums + 2 * (nb + 1), E.nvec);
+        }
+    panel(cx, E, 0, x, nullptr);
+    double nrm2 = 0.0;
+    read_back(cx, &nrm2, E.sums + 2, 1);
+    const double nrm = std::sqrt(nrm2);
+    if (!(nrm >= DAV_DROP)) return false;
+    LAUNCH(davidson_scale_kernel, grid_for(E.nvec), E.B + E.nvec * nb, x, sx ? E.S + E.nvec * nb : nullptr, sx, 1.0 / nrm, E.nvec);
+    return true;
+}
+
+// column nb of B and S is there: its row and column of the projected matrix, then nb + 1 columns
+void extend_projected(Context& cx, Davidson& E)
+{
+    const int q = E.nb, ms = E.max_space;
+    panel(cx, E, q, E.B + E.nvec * q, E.S + E.nvec * q);
+    std::vector<double> h(3 * (q + 1));
+    read_back(cx, h.data(), E.sums, 3 * (q + 1));
+    for (int p = 0; p <= q; ++p) E.G[p + (size_t)ms * q] = h[p];
+    for (int p = 0; p < q; ++p) E.G[q + (size_t)ms * p] = h[(q + 1) + p];
+    E.nb = q + 1;
+}
+
+}  // namespace
+
+int davidson_reduce_blocks(int64_t nvec) { return (int)std::max<int64_t>(1, std::min<int64_t>((nvec + TB - 1) / TB, DAV_MAXBLK)); }
+
+void davidson_reduce_final(Context& cx, double* out, const double* partial, int nout, int nblk)
+{
+    LAUNCH(davidson_final_kernel, dim3(nout), out, partial, nblk);
+}
+
+double davidson_bytes(double nvec, int nroots, int max_space)
+{
+    // b_p and sigma_p; the pending vectors, the Ritz vectors, their sigma and the corrections; the diagonal; the reduction buffers
+    return 8.0 * ((2.0 * max_space + 4.0 * nroots + 1.0) * nvec + 3.0 * (max_space + 1.0) * (DAV_MAXBLK + 1.0) +
+                  (double)nroots * (DAV_MAXBLK + 2.0) + (double)max_space * nroots);
+}
+
+void davidson_alloc(Context& cx, Davidson& E, int64_t n1, int64_t nvec, double w2, bool follow, int nroots, int max_space,
+                    const std::function<void(double* diag)>& fill_diag)
+{
+    preload_once();
+    E.nroots = nroots;
+    E.max_space = max_space;
+    E.n1 = n1;
+    E.nvec = nvec;
+    E.w2 = w2;
+    E.follow = follow;
+    E.B = cx.alloc(nvec * max_space);
+    E.S = cx.alloc(nvec * max_space);
+    E.pend = cx.alloc(nvec * nroots);
+    E.x = cx.alloc(nvec * nroots);
+    E.sx = cx.alloc(nvec * nroots);
+    E.corr = cx.alloc(nvec * nroots);
+    E.partial = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots) * DAV_MAXBLK);
+    E.sums = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots));
+    E.coef = cx.alloc((int64_t)max_space * nroots + nroots);
+    E.diag = cx.alloc(nvec);
+    fill_diag(E.diag);
+    E.G.assign((size_t)max_space * max_space, 0.0);
+    E.omega.assign(nroots, 0.0);
+    E.resnorm.assign(nroots, 0.0);
+    E.flags.assign(nroots, 0);
+}
+
+void davidson_free(Context& cx, Davidson& E)
+{
+    double* bufs[] = {E.B, E.S, E.pend, E.x, E.sx, E.corr, E.partial, E.sums, E.coef, E.diag};
+    for (double* b : bufs) cx.release(b);
+}
+
+void davidson_restart(Davidson& E)
+{
+    E.nb = 0;
+    E.npend = 0;
+    E.ritz = false;
+    E.user_guess = false;
+    E.target.clear();
+    E.nsigma = E.ncollapse = 0;
+    std::fill(E.flags.begin(), E.flags.end(), 0);
+}
+
+void davidson_set_pending_from_host(Context& cx, Davidson& E, const std::string& prefix, int k, const double* r1, const double* r2)
+{
+    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, prefix + "set_guess: k outside 0 .. nroots - 1, or a NULL vector");
+    if (E.nb > 0 || !E.user_guess) {   // the first of a block of the caller's guesses starts over: a running iteration, the unit guesses
+        davidson_restart(E);
+        k_fill(cx, E.pend, E.nvec * E.nroots, 0.0);   // (a column the caller leaves out stays zero and is dropped)
+        E.user_guess = true;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k, r1, sizeof(double) * E.n1, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k + E.n1, r2, sizeof(double) * (E.nvec - E.n1), hipMemcpyHostToDevice, cx.stream));
+    cx.sync();
+    E.npend = std::max(E.npend, k + 1);
+}
+
+int davidson_iterate(Context& cx, Davidson& E, const std::string& prefix, double tol, const DavidsonSigma& sigma)
+{
+    const std::string who = prefix + "iterate";
+    const int64_t nvec = E.nvec;
+    const int ms = E.max_space;
+    if (E.nb == 0 && E.npend == 0) throw Error(1, who + ": no guess vectors (call " + prefix + "guess or " + prefix + "set_guess first)");
+    const bool guess_step = E.nb == 0;
+    // ---- collapse: restart from the Ritz vectors, their sigma being the same combination of the stored sigma (no new sigma builds)
+    if (E.nb + E.npend > ms) {
+        const int nr = std::min(E.nroots, E.nb);
+        E.nb = 0;
+        for (int k = 0; k < nr; ++k)
+            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k)) extend_projected(cx, E);
+        ++E.ncollapse;
+    }
+    // ---- the pending vectors: orthonormalise, sigma, one more row and column of the projected matrix <b_p, sigma(b_q)>
+    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
+        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr)) continue;
+        sigma(E.B + nvec * E.nb, E.S + nvec * E.nb);
+        ++E.nsigma;
+        extend_projected(cx, E);
+    }
+    E.npend = 0;
+    if (E.nb == 0) throw Error(1, who + ": every guess vector vanished");
+    // ---- the projected problem on the host
+    const int nb = E.nb, nr = std::min(E.nroots, nb);
+    std::vector<double> g((size_t)nb * nb), wr(nb), wi(nb), vr((size_t)nb * nb), up((size_t)nb * nr + nr);
+    for (int q = 0; q < nb; ++q)
+        for (int p = 0; p < nb; ++p) g[p + (size_t)nb * q] = E.G[p + (size_t)ms * q];
+    const int rc = eig_general(nb, g.data(), nb, wr.data(), wi.data(), vr.data());
+    if (rc) throw Error(1, who + ": the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
+    // The roots taken: the lowest nr -- or, for a following state from the caller's guesses, those nearest to the Ritz values of its guess
+    // step, target by target in their order, each root once, then by ascending omega.  A lower root of another symmetry, which only
+    // rounding brings into the basis and the iteration then amplifies, takes no place that way.
+    std::vector<int> sel(nr);
+    std::iota(sel.begin(), sel.end(), 0);
+    if (guess_step && E.follow && E.user_guess) E.target.assign(wr.begin(), wr.begin() + nr);
+    else if (!E.target.empty() && nb > nr) {
+        std::vector<char> used(nb, 0);
+        const int nt = std::min<int>(nr, (int)E.target.size());
+        for (int k = 0; k < nr; ++k) {
+            int best = -1;
+            for (int c = 0; c < nb; ++c) {
+                if (used[c]) continue;
+                // (beyond the targets -- a guess was dropped --: the lowest root not yet taken)
+                if (best < 0 || (k < nt && std::fabs(wr[c] - E.target[k]) < std::fabs(wr[best] - E.target[k]))) best = c;
+            }
+            used[best] = 1;
+            sel[k] = best;
+        }
+        std::sort(sel.begin(), sel.end());
+    }
+    for (int k = 0; k < nr; ++k) {
+        const int c = sel[k];
+        // a root with an imaginary part: the real part of its vector (the column of the pair's root with wi > 0)
+        const double* col = vr.data() + (size_t)nb * (wi[c] < 0.0 && c > 0 ? c - 1 : c);
+        double n2 = 0.0;
+        for (int p = 0; p < nb; ++p) n2 += col[p] * col[p];
+        const double sc = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;   // <x, x> = sum_p y_p^2: the basis is orthonormal
+        for (int p = 0; p < nb; ++p) up[p + (size_t)nb * k] = sc * col[p];
+        up[(size_t)nb * nr + k] = wr[c];
+        E.omega[k] = wr[c];
+        E.flags[k] = wi[c] != 0.0 ? EOM_FLAG_COMPLEX : 0;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
+    // ---- Ritz pass
+    const int nblk = davidson_reduce_blocks(nvec);
+    for (int k0 = 0; k0 < nr; k0 += DAV_RCHUNK)
+        LAUNCH(davidson_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * nr, E.diag, E.n1, E.w2,
+               nvec, k0, std::min(DAV_RCHUNK, nr - k0));
+    LAUNCH(davidson_final_kernel, dim3(nr), E.sums, E.partial, nblk);
+    std::vector<double> nrm(nr);
+    read_back(cx, nrm.data(), E.sums, nr);   // (also: `up` is no longer read)
+    E.ritz = true;
+    int all = nr == E.nroots ? 1 : 0;
+    for (int k = 0; k < E.nroots; ++k) {
+        if (k >= nr) {   // fewer basis vectors than roots: not found (yet)
+            E.omega[k] = 0.0;
+            E.resnorm[k] = HUGE_VAL;
+            E.flags[k] = 0;
+            continue;
+        }
+        E.resnorm[k] = std::sqrt(nrm[k]);
+        if (E.resnorm[k] < tol) E.flags[k] |= EOM_FLAG_CONVERGED;
+        else {
+            all = 0;
+            k_copy(cx, E.pend + nvec * E.npend, E.corr + nvec * k, nvec);
+            ++E.npend;
+        }
+    }
+    return all;
+}
+
+void davidson_get_vector(Context& cx, Davidson& E, const std::string& prefix, int k, double* r1, double* r2)
+{
+    if (!E.ritz || k < 0 || k >= std::min(E.nroots, E.nb) || !r1 || !r2)
+        throw Error(1, prefix + "get_vector: no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
+    AFESP_HIP(hipMemcpyAsync(r1, E.x + E.nvec * k, sizeof(double) * E.n1, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(r2, E.x + E.nvec * k + E.n1, sizeof(double) * (E.nvec - E.n1), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+}  // namespace afesp

@@ -2,31 +2,18 @@
 // sector, r = [r1(i); r2(i,j,a)] with r2 antisymmetric in i,j, and electron affinities in the 1p + 2p1h sector, r = [r1(a); r2(i,a,b)]
 // with r2 antisymmetric in a,b.  Either sector is EOM-EE (eom_so.h) into a ghost orbital that interacts with nothing, so sigma(r) is
 // contracted from the same H-bar elements of the live SOLambda (borrowed, not copied), and the lowest eigenvalues come from the block
-// Davidson iteration of eom_so.h, rule by rule.  On full storage <x, y> = sum x1 y1 + 1/2 sum x2 y2.
+// Davidson iteration of davidson_so.h.  On full storage <x, y> = sum x1 y1 + 1/2 sum x2 y2.
 #pragma once
+#include "davidson_so.h"
 #include "lambda_so.h"
-
-#include <vector>
 
 namespace afesp {
 
 constexpr int EOM_SECTOR_IP = 1, EOM_SECTOR_EA = 2;
 
 struct SOEomX {
+    Davidson d;                 // IP: n1 = o, n2 = o^2 v; EA: n1 = v, n2 = o v^2; w2 = 1/2; diag = -e_i, -(e_i + e_j - e_a) / e_a, -(e_i - e_a - e_b)
     int sector = 0;
-    int64_t epoch = -1;          // SOState::amp_epoch of the Lambda state whose H-bar elements are borrowed
-    int nroots = 0, max_space = 0;
-    int64_t n1 = 0, n2 = 0, nvec = 0;   // IP: o, o^2 v; EA: v, o v^2; their sum
-    int nb = 0, npend = 0;       // basis columns; pending vectors (guesses or corrections)
-    bool user_guess = false, ritz = false;   // as SOEom's
-    double *B = nullptr, *S = nullptr;        // max_space columns each
-    double *pend = nullptr, *x = nullptr, *sx = nullptr, *corr = nullptr;   // nroots columns each
-    double *partial = nullptr, *sums = nullptr, *coef = nullptr;           // reduction partials, their ordered sums, coefficients
-    double *diag = nullptr;      // the diagonal guess of the sector's matrix (-D), nvec long: -e_i, -(e_i + e_j - e_a) / e_a, -(e_i - e_a - e_b)
-    std::vector<double> G;       // projected matrix, max_space x max_space column-major (host)
-    std::vector<double> omega, resnorm;
-    std::vector<int> flags;      // EOM_FLAG_CONVERGED / EOM_FLAG_COMPLEX (eom_so.h)
-    int nsigma = 0, ncollapse = 0;
 };
 
 inline bool so_eom_sector_ok(int sector) { return sector == EOM_SECTOR_IP || sector == EOM_SECTOR_EA; }

@@ -1,22 +1,14 @@
 // eom_ipea_so.hip -- EOM-IP-CCSD and EOM-EA-CCSD on the spin-orbital CCSD state (eom_ipea_so.h): the sigma build of either
 // sector, term by term in the letters of tests/np_eom_ipea.py (ip_sigma_explicit, ea_sigma_explicit) over the H-bar elements of the live
-// Lambda state, and the block Davidson iteration of eom_so.hip on a vector described by (n1, n2, weight 1/2, a resident diagonal).
-// Launches are plain call-by-call ones.  Every reduction is block partials on a grid fixed by the vector length, then an ordered final
-// sum: the same input gives the same bits on every run.
+// Lambda state, the diagonal and the guesses, for the block Davidson iteration of davidson_so.h on a vector described by (n1, n2, weight
+// 1/2).  Launches are plain call-by-call ones.
 #include "device_util.h"
 #include "eom_ipea_so.h"
-#include "eom_so.h"
-#include "small_eig.h"
 #include "tall.h"
-
-#include <cmath>
 
 namespace afesp {
 namespace {
 
-constexpr int IPEA_MAXBLK = 128;   // blocks of a reduction (at most TB: ipea_final_kernel sums them in one block)
-constexpr int IPEA_RCHUNK = 8;     // roots one launch of the Ritz pass forms
-constexpr double IPEA_DROP = 1e-10, IPEA_CLAMP = 1e-4, IPEA_W2 = 0.5;
 constexpr double IPEA_SEED = 1e-3;   // weight of the guesses' admixture of every unique amplitude (ipea_unit_kernel)
 
 // the level of spin orbital p (occupied first) of either kind of state: lev of a UHF- or Fock-fed one, the spatial e of an RHF-fed one
@@ -118,70 +110,6 @@ __global__ void ipea_ea_expand_kernel(double* W, const double* pa, int o, int v,
     }
 }
 
-// ---- the Davidson kernels of eom_so.hip on a vector of n1 elements of weight 1 and nvec - n1 of weight IPEA_W2
-// The Gram panel of one vector pair (bq, sq) against ncol stored columns -- block (blk, p):
-//   p < ncol:  <b_p, sq>, <s_p, bq>, <b_p, bq>        p = ncol:  <bq, sq>, the same again, <bq, bq>
-// partial[(q (ncol + 1) + p) nblk + blk], q = 0, 1, 2.  sq null: the overlaps alone (q = 2; the others are written as zero).
-__global__ void ipea_panel_kernel(double* partial, const double* B, const double* S, int64_t stride, int ncol, const double* bq, const double* sq,
-                                  int64_t nvec, int64_t n1)
-{
-    __shared__ double sm[3 * 4];
-    const int p = blockIdx.y, nblk = gridDim.x;
-    const double* bp = p < ncol ? B + stride * p : bq;
-    const double* sp = sq ? (p < ncol ? S + stride * p : sq) : nullptr;
-    double acc[3] = {0.0, 0.0, 0.0};
-    GRID_STRIDE(x, nvec)
-    {
-        const double w = x < n1 ? 1.0 : IPEA_W2, b = bp[x], q = bq[x];
-        if (sp) {
-            acc[0] += w * b * sq[x];
-            acc[1] += w * sp[x] * q;
-        }
-        acc[2] += w * b * q;
-    }
-    block_sum<3>(acc, sm);
-    if (threadIdx.x == 0)
-        for (int q = 0; q < 3; ++q) partial[((int64_t)q * (ncol + 1) + p) * nblk + blockIdx.x] = acc[q];
-}
-
-// out[b] = the sum of partial[b nblk .. (b + 1) nblk) in a fixed order (nblk <= TB)
-__global__ void ipea_final_kernel(double* out, const double* partial, int nblk)
-{
-    __shared__ double red[TB];
-    red[threadIdx.x] = (int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
-// one projection pass: x -= sum_p coef[p] b_p, and the companion sx -= sum_p coef[p] s_p where given
-__global__ void ipea_project_kernel(double* x, double* sx, const double* B, const double* S, int64_t stride, int ncol, const double* coef, int64_t nvec)
-{
-    GRID_STRIDE(e, nvec)
-    {
-        double a = x[e], sa = sx ? sx[e] : 0.0;
-        for (int p = 0; p < ncol; ++p) {
-            const double c = coef[p];
-            a = __fma_rn(-c, B[stride * p + e], a);
-            if (sx) sa = __fma_rn(-c, S[stride * p + e], sa);
-        }
-        x[e] = a;
-        if (sx) sx[e] = sa;
-    }
-}
-
-__global__ void ipea_scale_kernel(double* dst, const double* src, double* dst2, const double* src2, double scale, int64_t nvec)
-{
-    GRID_STRIDE(e, nvec)
-    {
-        dst[e] = __dmul_rn(scale, src[e]);
-        if (src2) dst2[e] = __dmul_rn(scale, src2[e]);
-    }
-}
-
 // A guess: +1 at ip, -1 at im (negative index: none), and on every unique amplitude the admixture IPEA_SEED (frac((q + 1) phi) - 1/2)
 // with q the flat index of its i < j / a < b element and phi the golden ratio's fraction (the image carries the opposite sign, the
 // diagonal zero).  sigma couples neither different Ms nor different irreducible representations and a unit vector lies in one block of
@@ -208,51 +136,6 @@ __global__ void ipea_unit_kernel(double* x, int64_t nvec, int64_t ip, int64_t im
     }
 }
 
-// The Ritz pass for the roots k0 .. k0 + nr (nr <= IPEA_RCHUNK): every stored b_p and sigma_p is read once and gives
-//   x_k = sum_p y(p,k) b_p,  sx_k = sum_p y(p,k) sigma_p,  rho_k = sx_k - omega_k x_k,  corr_k = rho_k / (omega_k - diag)
-// (|omega_k - diag| clamped below at IPEA_CLAMP, keeping its sign) and the block partials of <rho_k, rho_k> at
-// partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.
-__global__ void ipea_ritz_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride, int nb,
-                                 const double* y, const double* omega, const double* diag, int64_t n1, int64_t nvec, int k0, int nr)
-{
-    __shared__ double sm[IPEA_RCHUNK * 4];
-    double nrm[IPEA_RCHUNK];
-#pragma unroll
-    for (int k = 0; k < IPEA_RCHUNK; ++k) nrm[k] = 0.0;
-    GRID_STRIDE(e, nvec)
-    {
-        double xa[IPEA_RCHUNK], sa[IPEA_RCHUNK];
-#pragma unroll
-        for (int k = 0; k < IPEA_RCHUNK; ++k) xa[k] = sa[k] = 0.0;
-        for (int p = 0; p < nb; ++p) {
-            const double b = B[stride * p + e], s = S[stride * p + e];
-#pragma unroll
-            for (int k = 0; k < IPEA_RCHUNK; ++k)
-                if (k < nr) {
-                    const double c = y[p + (int64_t)nb * (k0 + k)];
-                    xa[k] = __fma_rn(c, b, xa[k]);
-                    sa[k] = __fma_rn(c, s, sa[k]);
-                }
-        }
-        const double D = diag[e], w = e < n1 ? 1.0 : IPEA_W2;
-#pragma unroll
-        for (int k = 0; k < IPEA_RCHUNK; ++k)
-            if (k < nr) {
-                const double om = omega[k0 + k];
-                const double rho = __fma_rn(-om, xa[k], sa[k]);
-                double den = om - D;
-                if (fabs(den) < IPEA_CLAMP) den = den < 0.0 ? -IPEA_CLAMP : IPEA_CLAMP;
-                X[stride * (k0 + k) + e] = xa[k];
-                SX[stride * (k0 + k) + e] = sa[k];
-                corr[stride * (k0 + k) + e] = rho / den;
-                nrm[k] += w * rho * rho;
-            }
-    }
-    block_sum<IPEA_RCHUNK>(nrm, sm);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
-}
-
 const char* sector_name(int sector) { return sector == EOM_SECTOR_IP ? "EOM-IP" : "EOM-EA"; }
 
 void need_plain(Context& cx)
@@ -267,71 +150,13 @@ void sector_sizes(const SOState& s, int sector, int64_t* n1, int64_t* n2, int64_
     else { *n1 = V; *n2 = O * V * V; *nunique = V + O * (V * (V - 1) / 2); }
 }
 
-inline int ipea_nblk(int64_t nvec) { return (int)std::max<int64_t>(1, std::min<int64_t>((nvec + TB - 1) / TB, IPEA_MAXBLK)); }
-
-void read_back(Context& cx, double* host, const double* dev, int64_t n)
-{
-    AFESP_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
-}
-
-// the panel of (bq, sq) against the first ncol columns, summed: E.sums[q (ncol + 1) + p]
-void panel(Context& cx, SOEomX& E, int ncol, const double* bq, const double* sq)
-{
-    const int nblk = ipea_nblk(E.nvec);
-    LAUNCH(ipea_panel_kernel, dim3(nblk, ncol + 1), E.partial, E.B, E.S, E.nvec, ncol, bq, sq, E.nvec, E.n1);
-    LAUNCH(ipea_final_kernel, dim3(3 * (ncol + 1)), E.sums, E.partial, nblk);
-}
-
-// Two passes of projection of x (and its companion sx) against the first nb columns through the panel, then x / |x| -> column nb of B
-// (sx / |x| -> column nb of S).  -> false: the norm after projection is below IPEA_DROP, nothing was stored
-bool orthonormalise(Context& cx, SOEomX& E, double* x, double* sx)
-{
-    const int nb = E.nb;
-    if (nb > 0)
-        for (int pass = 0; pass < 2; ++pass) {
-            panel(cx, E, nb, x, nullptr);
-            LAUNCH(ipea_project_kernel, grid_for(E.nvec), x, sx, E.B, E.S, E.nvec, nb, E.sums + 2 * (nb + 1), E.nvec);
-        }
-    panel(cx, E, 0, x, nullptr);
-    double nrm2 = 0.0;
-    read_back(cx, &nrm2, E.sums + 2, 1);
-    const double nrm = std::sqrt(nrm2);
-    if (!(nrm >= IPEA_DROP)) return false;
-    LAUNCH(ipea_scale_kernel, grid_for(E.nvec), E.B + E.nvec * nb, x, sx ? E.S + E.nvec * nb : nullptr, sx, 1.0 / nrm, E.nvec);
-    return true;
-}
-
-// column nb of B and S is there: its row and column of the projected matrix, then nb + 1 columns
-void extend_projected(Context& cx, SOEomX& E)
-{
-    const int q = E.nb, ms = E.max_space;
-    panel(cx, E, q, E.B + E.nvec * q, E.S + E.nvec * q);
-    std::vector<double> h(3 * (q + 1));
-    read_back(cx, h.data(), E.sums, 3 * (q + 1));
-    for (int p = 0; p <= q; ++p) E.G[p + (size_t)ms * q] = h[p];
-    for (int p = 0; p < q; ++p) E.G[q + (size_t)ms * p] = h[(q + 1) + p];
-    E.nb = q + 1;
-}
-
 void free_one(Context& cx, SOState& s, int sector)
 {
     SOEomX*& E = s.ipea[sector - 1];
     if (!E) return;
-    double* bufs[] = {E->B, E->S, E->pend, E->x, E->sx, E->corr, E->partial, E->sums, E->coef, E->diag};
-    for (double* b : bufs) cx.release(b);
+    davidson_free(cx, E->d);
     delete E;
     E = nullptr;
-}
-
-void restart(SOEomX& E)
-{
-    E.nb = 0;
-    E.npend = 0;
-    E.ritz = false;
-    E.user_guess = false;
-    E.nsigma = E.ncollapse = 0;
-    std::fill(E.flags.begin(), E.flags.end(), 0);
 }
 
 // W(i,a,b) = sum_{e<f} <ab||ef> r(i,e,f) = 1/2 sum_ef: the bare ladder over the antisymmetric pair (e,f) against the pair-form va the T
@@ -377,12 +202,7 @@ void preload_eom_ipea_so()
     first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
     first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
     first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_panel_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_final_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_project_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_scale_kernel));
     first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_ritz_kernel));
     (void)hipGetLastError();
 }
 
@@ -397,12 +217,10 @@ double so_eom_ipea_bytes(int64_t o, int64_t v, int sector, int nroots, int max_s
     const bool ip = sector == EOM_SECTOR_IP;
     const double O = (double)o, V = (double)v;
     const double n1 = ip ? O : V, n2 = ip ? O * O * V : O * V * V, nvec = n1 + n2;
-    // b_p and sigma_p; the pending vectors, the Ritz vectors, their sigma and the corrections; the diagonal; the reduction buffers; the
-    // scratch of a sigma build (W and the permutation carrier, y; EA: Z and the o^3 product) and the two staging vectors of the host entry
+    // the Davidson state; the scratch of a sigma build (W and the permutation carrier, y; EA: Z and the o^3 product) and the two staging
+    // vectors of the host entry
     const double scratch = 2.0 * n2 + (ip ? V : O + O * V * O + O * O * O);
-    const double doubles = (2.0 * max_space + 4.0 * nroots + 1.0) * nvec + 3.0 * (max_space + 1.0) * (IPEA_MAXBLK + 1.0) +
-                           (double)nroots * (IPEA_MAXBLK + 2.0) + (double)max_space * nroots + scratch + 2.0 * nvec;
-    return 8.0 * doubles;
+    return davidson_bytes(nvec, nroots, max_space) + 8.0 * (scratch + 2.0 * nvec);
 }
 
 void so_eom_ipea_free(Context& cx, SOState& s)
@@ -415,7 +233,7 @@ SOEomX& so_eom_ipea_need(SOState& s, int sector, const char* who)
 {
     so_lambda_need(s, who);
     SOEomX* E = s.ipea[sector - 1];
-    if (!E || E->epoch != s.amp_epoch)
+    if (!E || E->d.epoch != s.amp_epoch)
         throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no " + sector_name(sector) +
                                           " state for the live Lambda state (call afesp_ccsd_so_eom_ipea_init first)");
     return *E;
@@ -442,25 +260,9 @@ void so_eom_ipea_init(Context& cx, SOState& s, int sector, int nroots, int max_s
     SOEomX& E = *s.ipea[sector - 1];
     try {
         E.sector = sector;
-        E.nroots = nroots;
-        E.max_space = max_space;
-        E.n1 = n1; E.n2 = n2; E.nvec = nvec;
-        E.B = cx.alloc(nvec * max_space);
-        E.S = cx.alloc(nvec * max_space);
-        E.pend = cx.alloc(nvec * nroots);
-        E.x = cx.alloc(nvec * nroots);
-        E.sx = cx.alloc(nvec * nroots);
-        E.corr = cx.alloc(nvec * nroots);
-        E.partial = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots) * IPEA_MAXBLK);
-        E.sums = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots));
-        E.coef = cx.alloc((int64_t)max_space * nroots + nroots);
-        E.diag = cx.alloc(nvec);
-        LAUNCH(ipea_diag_kernel, grid_for(nvec), E.diag, sector, s.e, s.lev, s.o, s.v, nvec);
-        E.G.assign((size_t)max_space * max_space, 0.0);
-        E.omega.assign(nroots, 0.0);
-        E.resnorm.assign(nroots, 0.0);
-        E.flags.assign(nroots, 0);
-        E.epoch = L.epoch;
+        davidson_alloc(cx, E.d, n1, nvec, 0.5, false, nroots, max_space,
+                       [&](double* diag) { LAUNCH(ipea_diag_kernel, grid_for(nvec), diag, sector, s.e, s.lev, s.o, s.v, nvec); });
+        E.d.epoch = L.epoch;
         cx.sync();
     } catch (...) {
         try { cx.quiesce(); free_one(cx, s, sector); } catch (...) {}
@@ -548,10 +350,11 @@ void so_eom_ipea_sigma_host(Context& cx, SOState& s, int sector, int nvec, const
 void so_eom_ipea_guess(Context& cx, SOState& s, int sector)
 {
     need_plain(cx);
-    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_guess");
+    Davidson& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_guess").d;
     const int64_t O = s.o, V = s.v, n1 = E.n1;
     std::vector<double> D(E.nvec);
-    read_back(cx, D.data(), E.diag, E.nvec);
+    AFESP_HIP(hipMemcpyAsync(D.data(), E.diag, sizeof(double) * E.nvec, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
     // the unique amplitudes by ascending diagonal, ties by flat index
     std::vector<int64_t> idx;
     for (int64_t x = 0; x < n1; ++x) idx.push_back(x);
@@ -566,7 +369,7 @@ void so_eom_ipea_guess(Context& cx, SOState& s, int sector)
     }
     const int nr = E.nroots;
     std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return D[p] != D[q] ? D[p] < D[q] : p < q; });
-    restart(E);
+    davidson_restart(E);
     for (int k = 0; k < nr; ++k) {
         const int64_t ip = idx[k];
         int64_t im = -1;
@@ -581,103 +384,25 @@ void so_eom_ipea_guess(Context& cx, SOState& s, int sector)
     cx.sync();
 }
 
+static const char* const ipea_prefix ="afesp_ccsd_so_eom_ipea_";
+
 void so_eom_ipea_set_guess(Context& cx, SOState& s, int sector, int k, const double* r1, const double* r2)
 {
     need_plain(cx);
-    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_set_guess");
-    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, "afesp_ccsd_so_eom_ipea_set_guess: k outside 0 .. nroots - 1, or a NULL vector");
-    if (E.nb > 0 || !E.user_guess) {   // the first of a block of the caller's guesses starts over: a running iteration, the unit guesses
-        restart(E);
-        k_fill(cx, E.pend, E.nvec * E.nroots, 0.0);   // (a column the caller leaves out stays zero and is dropped)
-        E.user_guess = true;
-    }
-    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k, r1, sizeof(double) * E.n1, hipMemcpyHostToDevice, cx.stream));
-    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k + E.n1, r2, sizeof(double) * E.n2, hipMemcpyHostToDevice, cx.stream));
-    cx.sync();
-    E.npend = std::max(E.npend, k + 1);
+    davidson_set_pending_from_host(cx, so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_set_guess").d, ipea_prefix, k, r1, r2);
 }
 
 int so_eom_ipea_iterate(Context& cx, SOState& s, int sector, double tol)
 {
     need_plain(cx);
-    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_iterate");
-    const int64_t nvec = E.nvec;
-    const int ms = E.max_space;
-    if (E.nb == 0 && E.npend == 0)
-        throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: no guess vectors (call afesp_ccsd_so_eom_ipea_guess or afesp_ccsd_so_eom_ipea_set_guess first)");
-    // ---- collapse: restart from the Ritz vectors, their sigma being the same combination of the stored sigma (no new sigma builds)
-    if (E.nb + E.npend > ms) {
-        const int nr = std::min(E.nroots, E.nb);
-        E.nb = 0;
-        for (int k = 0; k < nr; ++k)
-            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k)) extend_projected(cx, E);
-        ++E.ncollapse;
-    }
-    // ---- the pending vectors: orthonormalise, sigma, one more row and column of the projected matrix
-    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
-        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr)) continue;
-        so_eom_ipea_sigma(cx, s, sector, E.B + nvec * E.nb, E.S + nvec * E.nb);
-        ++E.nsigma;
-        extend_projected(cx, E);
-    }
-    E.npend = 0;
-    if (E.nb == 0) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: every guess vector vanished");
-    // ---- the projected problem on the host
-    const int nb = E.nb, nr = std::min(E.nroots, nb);
-    std::vector<double> g((size_t)nb * nb), wr(nb), wi(nb), vr((size_t)nb * nb), up((size_t)nb * nr + nr);
-    for (int q = 0; q < nb; ++q)
-        for (int p = 0; p < nb; ++p) g[p + (size_t)nb * q] = E.G[p + (size_t)ms * q];
-    const int rc = eig_general(nb, g.data(), nb, wr.data(), wi.data(), vr.data());
-    if (rc) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
-    for (int k = 0; k < nr; ++k) {
-        // a root with an imaginary part: the real part of its vector (the column of the pair's root with wi > 0)
-        const double* col = vr.data() + (size_t)nb * (wi[k] < 0.0 && k > 0 ? k - 1 : k);
-        double n2 = 0.0;
-        for (int p = 0; p < nb; ++p) n2 += col[p] * col[p];
-        const double sc = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;   // <x, x> = sum_p y_p^2: the basis is orthonormal
-        for (int p = 0; p < nb; ++p) up[p + (size_t)nb * k] = sc * col[p];
-        up[(size_t)nb * nr + k] = wr[k];
-        E.omega[k] = wr[k];
-        E.flags[k] = wi[k] != 0.0 ? EOM_FLAG_COMPLEX : 0;
-    }
-    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
-    // ---- Ritz pass
-    const int nblk = ipea_nblk(nvec);
-    for (int k0 = 0; k0 < nr; k0 += IPEA_RCHUNK)
-        LAUNCH(ipea_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * nr, E.diag, E.n1, nvec, k0,
-               std::min(IPEA_RCHUNK, nr - k0));
-    LAUNCH(ipea_final_kernel, dim3(nr), E.sums, E.partial, nblk);
-    std::vector<double> nrm(nr);
-    read_back(cx, nrm.data(), E.sums, nr);   // (also: `up` is no longer read)
-    E.ritz = true;
-    int all = nr == E.nroots ? 1 : 0;
-    for (int k = 0; k < E.nroots; ++k) {
-        if (k >= nr) {   // fewer basis vectors than roots: not found (yet)
-            E.omega[k] = 0.0;
-            E.resnorm[k] = HUGE_VAL;
-            E.flags[k] = 0;
-            continue;
-        }
-        E.resnorm[k] = std::sqrt(nrm[k]);
-        if (E.resnorm[k] < tol) E.flags[k] |= EOM_FLAG_CONVERGED;
-        else {
-            all = 0;
-            k_copy(cx, E.pend + nvec * E.npend, E.corr + nvec * k, nvec);
-            ++E.npend;
-        }
-    }
-    return all;
+    Davidson& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_iterate").d;
+    return davidson_iterate(cx, E, ipea_prefix, tol, [&](const double* r, double* sigma) { so_eom_ipea_sigma(cx, s, sector, r, sigma); });
 }
 
 void so_eom_ipea_get_vector(Context& cx, SOState& s, int sector, int k, double* r1, double* r2)
 {
     need_plain(cx);
-    SOEomX& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_get_vector");
-    if (!E.ritz || k < 0 || k >= std::min(E.nroots, E.nb) || !r1 || !r2)
-        throw Error(1, "afesp_ccsd_so_eom_ipea_get_vector: no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
-    AFESP_HIP(hipMemcpyAsync(r1, E.x + E.nvec * k, sizeof(double) * E.n1, hipMemcpyDeviceToHost, cx.stream));
-    AFESP_HIP(hipMemcpyAsync(r2, E.x + E.nvec * k + E.n1, sizeof(double) * E.n2, hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
+    davidson_get_vector(cx, so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_get_vector").d, ipea_prefix, k, r1, r2);
 }
 
 }  // namespace afesp

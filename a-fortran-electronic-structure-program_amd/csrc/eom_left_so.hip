@@ -1,8 +1,8 @@
 // eom_left_so.hip -- the left-hand side of EOM-EE-CCSD on the spin-orbital CCSD state (eom_so.h): the left sigma build
 // sigma_L(l) = A^T l, the coupling of right vectors to the reference, and the one-particle density as a bilinear form of a left pair
 // (l0, l) and a right pair (r0, r).  Term by term in the letters of tests/np_eom_left.py (lsigma_explicit, density_explicit) over the
-// H-bar elements of the live Lambda state, which are borrowed and never written.  The left Davidson state is the right-hand one's code
-// with a flag (eom_so.hip).  Launches are plain call-by-call ones; every reduction is block partials, then an ordered final sum.
+// H-bar elements of the live Lambda state, which are borrowed and never written.  The left Davidson state is a second user of
+// davidson_so.h (eom_so.hip).  Launches are plain call-by-call ones; every reduction is block partials, then an ordered final sum.
 #include "device_util.h"
 #include "eom_so.h"
 
@@ -95,10 +95,10 @@ void build_G(Context& cx, const Tensor& x2, const Tensor& l2, const Tensor& Gvv,
 // the ordered sum of eom_wdot_kernel's partials into out[0] (device)
 void wdot(Context& cx, double* out, const double* a1, const double* a2, const double* y, int64_t n1, int64_t n2)
 {
-    const int nblk = so_eom_reduce_blocks(n1 + n2);
+    const int nblk = davidson_reduce_blocks(n1 + n2);
     double* partial = cx.scratch("eoml_partial", nblk);
     LAUNCH(eom_wdot_kernel, dim3(nblk), partial, a1, a2, y, n1, n2);
-    so_eom_reduce_final(cx, out, partial, 1, nblk);
+    davidson_reduce_final(cx, out, partial, 1, nblk);
 }
 
 }  // namespace

@@ -3,37 +3,15 @@
 // from the lambda-independent H-bar elements a live SOLambda keeps resident (borrowed, not copied), and the lowest eigenvalues of A come
 // from a block Davidson iteration whose vectors never leave the device.  On full (i,j,a,b) storage <x, y> = sum x1 y1 + 1/4 sum x2 y2.
 #pragma once
+#include "davidson_so.h"
 #include "lambda_so.h"
-
-#include <vector>
 
 namespace afesp {
 
-constexpr int EOM_FLAG_CONVERGED = 1;   // per-root flags of so_eom_iterate
-constexpr int EOM_FLAG_COMPLEX = 2;     // the projected root has an imaginary part: the real part of its vector is used
-
 struct SOEom {
-    int64_t epoch = -1;          // SOState::amp_epoch of the Lambda state whose H-bar elements are borrowed
-    int nroots = 0, max_space = 0;
-    int64_t nvec = 0;            // o v + o^2 v^2
-    int nb = 0;                  // basis columns b_p and their sigma_p
-    int npend = 0;               // pending vectors (guesses or corrections) in `pend`
-    bool user_guess = false;     // the pending vectors are the caller's (so_eom_set_guess): a further one joins them instead of starting over
-    bool ritz = false;           // x / sx / omega / y are those of the current basis
-    double *B = nullptr, *S = nullptr;        // max_space columns each
-    double *pend = nullptr;                   // nroots columns
-    double *x = nullptr, *sx = nullptr;       // Ritz vectors x_k = sum_p y_pk b_p and sum_p y_pk sigma_p, nroots columns each
-    double *corr = nullptr;                   // the corrections of the last Ritz pass, nroots columns
-    double *partial = nullptr, *sums = nullptr, *coef = nullptr;   // reduction partials, their ordered sums, coefficients (device)
-    std::vector<double> G;       // projected matrix <b_p, sigma_q>, max_space x max_space column-major (host)
-    std::vector<double> omega, resnorm;
-    std::vector<int> flags;
-    int nsigma = 0, ncollapse = 0;
-    // The left state started from the caller's guesses follows the states it was given: the Ritz values of its first step -- for right
-    // eigenvectors as guesses these are the right-hand roots themselves, their span being invariant under A -- and at every later step
-    // the Ritz pairs nearest to them, not the lowest ones.  Empty: the lowest roots (every right-hand state, the unit guesses).
-    std::vector<double> target;
-    bool left = false;          // the left-hand state (SOState::eom_left): its sigma is so_eom_lsigma, A^T in place of A
+    Davidson d;                 // n1 = o v, nvec = o v + o^2 v^2, w2 = 1/4, diag = -D (the a,b-symmetrised mean of D2 behind the singles)
+    bool left = false;          // the left-hand state (SOState::eom_left): its sigma is so_eom_lsigma, A^T in place of A, and it follows the
+                                // states of the caller's guesses
 };
 
 // device bytes of the EOM state and the working set of a sigma build (beside so_state_bytes and so_lambda_bytes)
@@ -50,16 +28,11 @@ void so_eom_sigma_host(Context& cx, SOState& s, int nvec, const double* r1, cons
 // pending vectors: unit vectors on the nroots smallest -D over the unique amplitudes (ties by flat index), or the caller's own
 void so_eom_guess(Context& cx, SOState& s, bool left = false);   // (-D is the diagonal of A^T too: the same unit vectors)
 void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const double* r2, bool left = false);
-// One Davidson step: (collapse if the pending vectors do not fit,) orthonormalise the pending vectors, build their sigma, extend the
-// projected matrix, solve it on the host, Ritz pass.  -> 1 when every root has |rho_k| < tol
+// One Davidson step (davidson_iterate).  -> 1 when every root has |rho_k| < tol
 int so_eom_iterate(Context& cx, SOState& s, double tol, bool left = false);
 void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2, bool left = false);
 SOEom& so_eom_need(SOState& s, const char* who, bool left = false);
 void preload_eom_so();
-// the fixed-order reduction of this unit for its siblings: blocks of a partial-sum grid over nvec elements, and out[b] = the ordered
-// sum of partial[b nblk .. (b + 1) nblk)
-int so_eom_reduce_blocks(int64_t nvec);
-void so_eom_reduce_final(Context& cx, double* out, const double* partial, int nout, int nblk);
 
 // ---- the left-hand side (eom_left_so.hip)
 // device bytes of the left Davidson state and the working set of a left sigma build and of a density call

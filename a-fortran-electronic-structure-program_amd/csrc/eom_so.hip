@@ -1,20 +1,11 @@
 // eom_so.hip -- EOM-EE-CCSD on the spin-orbital CCSD state (eom_so.h): the sigma build sigma(r) = A r, term by term in
-// the letters of tests/np_eom.py (sigma_explicit) over the H-bar elements of the live Lambda state, and a block Davidson iteration for the
-// lowest eigenvalues of the non-symmetric A.  Launches are plain call-by-call ones, as Lambda's.  Every reduction is block partials on a
-// grid fixed by the vector length, then an ordered final sum: the same input gives the same bits on every run.
+// the letters of tests/np_eom.py (sigma_explicit) over the H-bar elements of the live Lambda state, the diagonal and the guesses, for the
+// block Davidson iteration of davidson_so.h on the non-symmetric A.  Launches are plain call-by-call ones, as Lambda's.
 #include "device_util.h"
 #include "eom_so.h"
-#include "small_eig.h"
-
-#include <cmath>
-#include <numeric>
 
 namespace afesp {
 namespace {
-
-constexpr int EOM_MAXBLK = 128;   // blocks of a reduction (at most TB: eom_final_kernel sums them in one block)
-constexpr int EOM_RCHUNK = 8;     // roots one launch of the Ritz pass forms
-constexpr double EOM_DROP = 1e-10, EOM_CLAMP = 1e-4;
 
 // sigma2 from the ladder block and the three permutation carriers, and sigma1's diagonal term (threads x < o v):
 //   sigma2 = lad + P(ij)P(ab) AB + P(ij) A + P(ab) Bm - D2 r2,   sigma1 -= D1 r1.
@@ -43,105 +34,20 @@ __global__ void eom_sigma_assemble_kernel(double* s2, double* s1, const double* 
     }
 }
 
-// The Gram panel of one vector pair (bq, sq) against ncol stored columns, in one launch -- block (blk, p):
-//   p < ncol:  <b_p, sq>, <s_p, bq>, <b_p, bq>        p = ncol:  <bq, sq>, the same again, <bq, bq>
-// with the weights 1 on the first n1 elements and 1/4 behind them; partial[(q (ncol + 1) + p) nblk + blk], q = 0, 1, 2.  sq null: the
-// overlaps alone (q = 2; the others are written as zero).
-__global__ void eom_panel_kernel(double* partial, const double* B, const double* S, int64_t stride, int ncol, const double* bq, const double* sq,
-                                 int64_t nvec, int64_t n1)
-{
-    __shared__ double sm[3 * 4];
-    const int p = blockIdx.y, nblk = gridDim.x;
-    const double* bp = p < ncol ? B + stride * p : bq;
-    const double* sp = sq ? (p < ncol ? S + stride * p : sq) : nullptr;
-    double acc[3] = {0.0, 0.0, 0.0};
-    GRID_STRIDE(x, nvec)
-    {
-        const double w = x < n1 ? 1.0 : 0.25, b = bp[x], q = bq[x];
-        if (sp) {
-            acc[0] += w * b * sq[x];
-            acc[1] += w * sp[x] * q;
-        }
-        acc[2] += w * b * q;
-    }
-    block_sum<3>(acc, sm);
-    if (threadIdx.x == 0)
-        for (int q = 0; q < 3; ++q) partial[((int64_t)q * (ncol + 1) + p) * nblk + blockIdx.x] = acc[q];
-}
-
-// out[b] = the sum of partial[b nblk .. (b + 1) nblk) in a fixed order (nblk <= TB)
-__global__ void eom_final_kernel(double* out, const double* partial, int nblk)
-{
-    __shared__ double red[TB];
-    red[threadIdx.x] = (int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
-// one projection pass: x -= sum_p coef[p] b_p, and the companion sx -= sum_p coef[p] s_p where given
-__global__ void eom_project_kernel(double* x, double* sx, const double* B, const double* S, int64_t stride, int ncol, const double* coef, int64_t nvec)
-{
-    GRID_STRIDE(e, nvec)
-    {
-        double a = x[e], sa = sx ? sx[e] : 0.0;
-        for (int p = 0; p < ncol; ++p) {
-            const double c = coef[p];
-            a = __fma_rn(-c, B[stride * p + e], a);
-            if (sx) sa = __fma_rn(-c, S[stride * p + e], sa);
-        }
-        x[e] = a;
-        if (sx) sx[e] = sa;
-    }
-}
-
-__global__ void eom_scale_kernel(double* dst, const double* src, double* dst2, const double* src2, double scale, int64_t nvec)
-{
-    GRID_STRIDE(e, nvec)
-    {
-        dst[e] = __dmul_rn(scale, src[e]);
-        if (src2) dst2[e] = __dmul_rn(scale, src2[e]);
-    }
-}
-
 // a guess: +1 at i0 and i1, -1 at i2 and i3 (negative index: none) of a vector that is zero otherwise
 __global__ void eom_unit_kernel(double* x, int64_t nvec, int64_t i0, int64_t i1, int64_t i2, int64_t i3)
 {
     GRID_STRIDE(e, nvec) x[e] = (e == i0 || e == i1) ? 1.0 : ((e == i2 || e == i3) ? -1.0 : 0.0);
 }
 
-// The Ritz pass for the roots k0 .. k0 + nr (nr <= EOM_RCHUNK): every stored b_p and sigma_p is read once and gives
-//   x_k = sum_p y(p,k) b_p,  sx_k = sum_p y(p,k) sigma_p,  rho_k = sx_k - omega_k x_k,  corr_k = rho_k / (omega_k + D)
-// (|omega_k + D| clamped below at EOM_CLAMP, keeping its sign; -D is the diagonal guess of A) and the block partials of <rho_k, rho_k>
-// at partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.
-__global__ void eom_ritz_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride, int nb,
-                                const double* y, const double* omega, const double* D1, const double* D2, int o, int v, int64_t nvec, int k0, int nr)
+// The diagonal guess of A as the Davidson unit reads it (corr = rho / (omega - diag)): diag = -D, D = D1 on the singles and the mean of D2
+// and its a,b image behind them.  (D2 is summed as ((e_i + e_j) - e_a) - e_b: symmetric in i,j to the bit, in a,b only with its image -- the
+// corrections stay antisymmetric to the bit as the basis vectors are.)
+__global__ void eom_diag_kernel(double* diag, const double* D1, const double* D2, int o, int v, int64_t nvec)
 {
-    __shared__ double sm[EOM_RCHUNK * 4];
     const int64_t n1 = (int64_t)o * v;
-    double nrm[EOM_RCHUNK];
-#pragma unroll
-    for (int k = 0; k < EOM_RCHUNK; ++k) nrm[k] = 0.0;
     GRID_STRIDE(e, nvec)
     {
-        double xa[EOM_RCHUNK], sa[EOM_RCHUNK];
-#pragma unroll
-        for (int k = 0; k < EOM_RCHUNK; ++k) xa[k] = sa[k] = 0.0;
-        for (int p = 0; p < nb; ++p) {
-            const double b = B[stride * p + e], s = S[stride * p + e];
-#pragma unroll
-            for (int k = 0; k < EOM_RCHUNK; ++k)
-                if (k < nr) {
-                    const double c = y[p + (int64_t)nb * (k0 + k)];
-                    xa[k] = __fma_rn(c, b, xa[k]);
-                    sa[k] = __fma_rn(c, s, sa[k]);
-                }
-        }
-        // (D2 is summed as ((e_i + e_j) - e_a) - e_b: symmetric in i,j to the bit, in a,b only with its image -- the corrections stay
-        // antisymmetric to the bit as the basis vectors are)
         double D;
         if (e < n1) D = D1[e];
         else {
@@ -149,23 +55,8 @@ __global__ void eom_ritz_kernel(double* X, double* SX, double* corr, double* par
             const int a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
             D = __dmul_rn(0.5, __dadd_rn(D2[x], D2[ij + (int64_t)o * o * (b + (int64_t)v * a)]));
         }
-        const double w = e < n1 ? 1.0 : 0.25;
-#pragma unroll
-        for (int k = 0; k < EOM_RCHUNK; ++k)
-            if (k < nr) {
-                const double om = omega[k0 + k];
-                const double rho = __fma_rn(-om, xa[k], sa[k]);
-                double den = om + D;
-                if (fabs(den) < EOM_CLAMP) den = den < 0.0 ? -EOM_CLAMP : EOM_CLAMP;
-                X[stride * (k0 + k) + e] = xa[k];
-                SX[stride * (k0 + k) + e] = sa[k];
-                corr[stride * (k0 + k) + e] = rho / den;
-                nrm[k] += w * rho * rho;
-            }
+        diag[e] = -D;
     }
-    block_sum<EOM_RCHUNK>(nrm, sm);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
 }
 
 void need_plain(Context& cx)
@@ -173,99 +64,33 @@ void need_plain(Context& cx)
     if (cx.rec) throw Error(1, "so_eom: the EOM equations are not part of a recorded (launch-fused) sequence");
 }
 
-inline int eom_nblk(int64_t nvec) { return (int)std::max<int64_t>(1, std::min<int64_t>((nvec + TB - 1) / TB, EOM_MAXBLK)); }
-
-void read_back(Context& cx, double* host, const double* dev, int64_t n)
-{
-    AFESP_HIP(hipMemcpyAsync(host, dev, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
-}
-
-// the panel of (bq, sq) against the first ncol columns, summed: E.sums[q (ncol + 1) + p]
-void panel(Context& cx, SOEom& E, int ncol, const double* bq, const double* sq, int64_t n1)
-{
-    const int nblk = eom_nblk(E.nvec);
-    LAUNCH(eom_panel_kernel, dim3(nblk, ncol + 1), E.partial, E.B, E.S, E.nvec, ncol, bq, sq, E.nvec, n1);
-    LAUNCH(eom_final_kernel, dim3(3 * (ncol + 1)), E.sums, E.partial, nblk);
-}
-
-// Two passes of projection of x (and its companion sx) against the first nb columns through the panel, then x / |x| -> column nb of B
-// (sx / |x| -> column nb of S).  -> false: the norm after projection is below EOM_DROP, nothing was stored
-bool orthonormalise(Context& cx, SOEom& E, double* x, double* sx, int64_t n1)
-{
-    const int nb = E.nb;
-    if (nb > 0)
-        for (int pass = 0; pass < 2; ++pass) {
-            panel(cx, E, nb, x, nullptr, n1);
-            LAUNCH(eom_project_kernel, grid_for(E.nvec), x, sx, E.B, E.S, E.nvec, nb, E.sums + 2 * (nb + 1), E.nvec);
-        }
-    panel(cx, E, 0, x, nullptr, n1);
-    double nrm2 = 0.0;
-    read_back(cx, &nrm2, E.sums + 2, 1);
-    const double nrm = std::sqrt(nrm2);
-    if (!(nrm >= EOM_DROP)) return false;
-    LAUNCH(eom_scale_kernel, grid_for(E.nvec), E.B + E.nvec * nb, x, sx ? E.S + E.nvec * nb : nullptr, sx, 1.0 / nrm, E.nvec);
-    return true;
-}
-
-// column nb of B and S is there: its row and column of the projected matrix, then nb + 1 columns
-void extend_projected(Context& cx, SOEom& E, int64_t n1)
-{
-    const int q = E.nb, ms = E.max_space;
-    panel(cx, E, q, E.B + E.nvec * q, E.S + E.nvec * q, n1);
-    std::vector<double> h(3 * (q + 1));
-    read_back(cx, h.data(), E.sums, 3 * (q + 1));
-    for (int p = 0; p <= q; ++p) E.G[p + (size_t)ms * q] = h[p];
-    for (int p = 0; p < q; ++p) E.G[q + (size_t)ms * p] = h[(q + 1) + p];
-    E.nb = q + 1;
-}
-
-void free_buffers(Context& cx, SOEom& E)
-{
-    double* bufs[] = {E.B, E.S, E.pend, E.x, E.sx, E.corr, E.partial, E.sums, E.coef};
-    for (double* b : bufs) cx.release(b);
-}
-
 }  // namespace
 
 void preload_eom_so()
 {
     first_use_touch(reinterpret_cast<const void*>(eom_sigma_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_panel_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_final_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_project_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_scale_kernel));
     first_use_touch(reinterpret_cast<const void*>(eom_unit_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_ritz_kernel));
+    first_use_touch(reinterpret_cast<const void*>(eom_diag_kernel));
     (void)hipGetLastError();
-}
-
-int so_eom_reduce_blocks(int64_t nvec) { return eom_nblk(nvec); }
-
-void so_eom_reduce_final(Context& cx, double* out, const double* partial, int nout, int nblk)
-{
-    LAUNCH(eom_final_kernel, dim3(nout), out, partial, nblk);
 }
 
 double so_eom_bytes(int64_t o, int64_t v, int nroots, int max_space)
 {
     const double O = (double)o, V = (double)v, o2v2 = O * O * V * V, nvec = O * V + o2v2;
-    // b_p and sigma_p; the pending vectors, the Ritz vectors, their sigma and the corrections; the reduction buffers; the scratch of a
-    // sigma build (lad, AB, A, B, Z, the o^4 product, Y_vv, Y_oo) and the two staging vectors of the host entry
-    const double doubles = (2.0 * max_space + 4.0 * nroots) * nvec + 3.0 * (max_space + 1.0) * (EOM_MAXBLK + 1.0) + (double)nroots * (EOM_MAXBLK + 2.0) +
-                           (double)max_space * nroots + 4.0 * o2v2 + O * O * O * V + O * O * O * O + V * V + O * O + 2.0 * nvec;
-    return 8.0 * doubles;
+    // the Davidson state; the scratch of a sigma build (lad, AB, A, B, Z, the o^4 product, Y_vv, Y_oo) and the two staging vectors of the
+    // host entry
+    return davidson_bytes(nvec, nroots, max_space) + 8.0 * (4.0 * o2v2 + O * O * O * V + O * O * O * O + V * V + O * O + 2.0 * nvec);
 }
 
 // the right-hand and the left-hand Davidson state are one type and one code: `left` chooses the slot, the sigma build and the names
 static SOEom*& eom_slot(SOState& s, bool left) { return left ? s.eom_left : s.eom; }
-static std::string eom_name(bool left, const char* call) { return std::string(left ? "afesp_ccsd_so_eom_left_" : "afesp_ccsd_so_eom_") + call; }
+static std::string eom_name(bool left, const char* call = "") { return std::string(left ? "afesp_ccsd_so_eom_left_" : "afesp_ccsd_so_eom_") + call; }
 
 static void eom_free_one(Context& cx, SOState& s, bool left)
 {
     SOEom*& e = eom_slot(s, left);
     if (!e) return;
-    free_buffers(cx, *e);
+    davidson_free(cx, e->d);
     delete e;
     e = nullptr;
 }
@@ -280,7 +105,7 @@ SOEom& so_eom_need(SOState& s, const char* who, bool left)
 {
     so_lambda_need(s, who);
     SOEom* e = eom_slot(s, left);
-    if (!e || e->epoch != s.amp_epoch)
+    if (!e || e->d.epoch != s.amp_epoch)
         throw Error(LAMBDA_ERR_STALE, std::string(who) + (left ? ": no left EOM state for the live Lambda state (call afesp_ccsd_so_eom_left_init first)"
                                                                : ": no EOM state for the live Lambda state (call afesp_ccsd_so_eom_init first)"));
     return *e;
@@ -309,23 +134,9 @@ void so_eom_init(Context& cx, SOState& s, int nroots, int max_space, bool left)
     SOEom& E = *eom_slot(s, left);
     try {
         E.left = left;
-        E.nroots = nroots;
-        E.max_space = max_space;
-        E.nvec = nvec;
-        E.B = cx.alloc(nvec * max_space);
-        E.S = cx.alloc(nvec * max_space);
-        E.pend = cx.alloc(nvec * nroots);
-        E.x = cx.alloc(nvec * nroots);
-        E.sx = cx.alloc(nvec * nroots);
-        E.corr = cx.alloc(nvec * nroots);
-        E.partial = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots) * EOM_MAXBLK);
-        E.sums = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots));
-        E.coef = cx.alloc((int64_t)max_space * nroots + nroots);
-        E.G.assign((size_t)max_space * max_space, 0.0);
-        E.omega.assign(nroots, 0.0);
-        E.resnorm.assign(nroots, 0.0);
-        E.flags.assign(nroots, 0);
-        E.epoch = L.epoch;
+        davidson_alloc(cx, E.d, O * V, nvec, 0.25, left, nroots, max_space,
+                       [&](double* diag) { LAUNCH(eom_diag_kernel, grid_for(nvec), diag, s.D1.d, s.D2.d, s.o, s.v, nvec); });
+        E.d.epoch = L.epoch;
         cx.sync();
     } catch (...) {
         try { cx.quiesce(); eom_free_one(cx, s, left); } catch (...) {}
@@ -403,22 +214,12 @@ void so_eom_sigma_host(Context& cx, SOState& s, int nvec, const double* r1, cons
     }
 }
 
-static void eom_restart(SOEom& E)
-{
-    E.nb = 0;
-    E.npend = 0;
-    E.ritz = false;
-    E.user_guess = false;
-    E.target.clear();
-    E.nsigma = E.ncollapse = 0;
-    std::fill(E.flags.begin(), E.flags.end(), 0);
-}
-
 void so_eom_guess(Context& cx, SOState& s, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, eom_name(left, "guess").c_str(), left);
+    Davidson& E = so_eom_need(s, eom_name(left, "guess").c_str(), left).d;
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
+    // (the raw D1 / D2, not the unit's symmetrised diagonal: the two can differ in the last bit, and a tie broken differently is another guess set)
     std::vector<double> D(ov + o2v2);
     AFESP_HIP(hipMemcpyAsync(D.data(), s.D1.d, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
     AFESP_HIP(hipMemcpyAsync(D.data() + ov, s.D2.d, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
@@ -433,7 +234,7 @@ void so_eom_guess(Context& cx, SOState& s, bool left)
                 for (int64_t i = 0; i < j; ++i) idx.push_back(ov + i + O * (j + O * (a + V * b)));
     const int nr = E.nroots;
     std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return -D[p] != -D[q] ? -D[p] < -D[q] : p < q; });
-    eom_restart(E);
+    davidson_restart(E);
     for (int k = 0; k < nr; ++k) {
         int64_t i0 = idx[k], i1 = -1, i2 = -1, i3 = -1;
         if (i0 >= ov) {
@@ -451,126 +252,23 @@ void so_eom_guess(Context& cx, SOState& s, bool left)
 void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const double* r2, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, eom_name(left, "set_guess").c_str(), left);
-    if (k < 0 || k >= E.nroots || !r1 || !r2) throw Error(1, eom_name(left, "set_guess") + ": k outside 0 .. nroots - 1, or a NULL vector");
-    const int64_t ov = (int64_t)s.o * s.v;
-    if (E.nb > 0 || !E.user_guess) {   // the first of a block of the caller's guesses starts over: a running iteration, the unit guesses
-        eom_restart(E);
-        k_fill(cx, E.pend, E.nvec * E.nroots, 0.0);   // (a column the caller leaves out stays zero and is dropped)
-        E.user_guess = true;
-    }
-    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k, r1, sizeof(double) * ov, hipMemcpyHostToDevice, cx.stream));
-    AFESP_HIP(hipMemcpyAsync(E.pend + E.nvec * k + ov, r2, sizeof(double) * (E.nvec - ov), hipMemcpyHostToDevice, cx.stream));
-    cx.sync();
-    E.npend = std::max(E.npend, k + 1);
+    davidson_set_pending_from_host(cx, so_eom_need(s, eom_name(left, "set_guess").c_str(), left).d, eom_name(left), k, r1, r2);
 }
 
 int so_eom_iterate(Context& cx, SOState& s, double tol, bool left)
 {
     need_plain(cx);
-    const std::string who = eom_name(left, "iterate");
-    SOEom& E = so_eom_need(s, who.c_str(), left);
-    const int64_t n1 = (int64_t)s.o * s.v, nvec = E.nvec;
-    const int ms = E.max_space;
-    if (E.nb == 0 && E.npend == 0) throw Error(1, who + ": no guess vectors (call " + eom_name(left, "guess") + " or " + eom_name(left, "set_guess") + " first)");
-    const bool guess_step = E.nb == 0;
-    // ---- collapse: restart from the Ritz vectors, their sigma being the same combination of the stored sigma (no new sigma builds)
-    if (E.nb + E.npend > ms) {
-        const int nr = std::min(E.nroots, E.nb);
-        E.nb = 0;
-        for (int k = 0; k < nr; ++k)
-            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k, n1)) extend_projected(cx, E, n1);
-        ++E.ncollapse;
-    }
-    // ---- the pending vectors: orthonormalise, sigma, one more row and column of the projected matrix
-    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
-        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr, n1)) continue;
-        if (left) so_eom_lsigma(cx, s, E.B + nvec * E.nb, E.S + nvec * E.nb);   // the projected matrix is then <b_p, sigma_L(b_q)>
-        else so_eom_sigma(cx, s, E.B + nvec * E.nb, E.S + nvec * E.nb);
-        ++E.nsigma;
-        extend_projected(cx, E, n1);
-    }
-    E.npend = 0;
-    if (E.nb == 0) throw Error(1, who + ": every guess vector vanished");
-    // ---- the projected problem on the host
-    const int nb = E.nb, nr = std::min(E.nroots, nb);
-    std::vector<double> g((size_t)nb * nb), wr(nb), wi(nb), vr((size_t)nb * nb), up((size_t)nb * nr + nr);
-    for (int q = 0; q < nb; ++q)
-        for (int p = 0; p < nb; ++p) g[p + (size_t)nb * q] = E.G[p + (size_t)ms * q];
-    const int rc = eig_general(nb, g.data(), nb, wr.data(), wi.data(), vr.data());
-    if (rc) throw Error(1, who + ": the eigenvalues of the projected matrix were not found (status " + std::to_string(rc) + ")");
-    // The roots taken: the lowest nr -- or, for the left state from the caller's guesses, those nearest to the Ritz values of its guess step,
-    // target by target in their order, each root once, then by ascending omega.  A lower root of another symmetry, which only rounding
-    // brings into the basis and the iteration then amplifies, takes no place that way.
-    std::vector<int> sel(nr);
-    std::iota(sel.begin(), sel.end(), 0);
-    if (guess_step && left && E.user_guess) E.target.assign(wr.begin(), wr.begin() + nr);
-    else if (!E.target.empty() && nb > nr) {
-        std::vector<char> used(nb, 0);
-        const int nt = std::min<int>(nr, (int)E.target.size());
-        for (int k = 0; k < nr; ++k) {
-            int best = -1;
-            for (int c = 0; c < nb; ++c) {
-                if (used[c]) continue;
-                // (beyond the targets -- a guess was dropped --: the lowest root not yet taken)
-                if (best < 0 || (k < nt && std::fabs(wr[c] - E.target[k]) < std::fabs(wr[best] - E.target[k]))) best = c;
-            }
-            used[best] = 1;
-            sel[k] = best;
-        }
-        std::sort(sel.begin(), sel.end());
-    }
-    for (int k = 0; k < nr; ++k) {
-        const int c = sel[k];
-        // a root with an imaginary part: the real part of its vector (the column of the pair's root with wi > 0)
-        const double* col = vr.data() + (size_t)nb * (wi[c] < 0.0 && c > 0 ? c - 1 : c);
-        double n2 = 0.0;
-        for (int p = 0; p < nb; ++p) n2 += col[p] * col[p];
-        const double sc = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;   // <x, x> = sum_p y_p^2: the basis is orthonormal
-        for (int p = 0; p < nb; ++p) up[p + (size_t)nb * k] = sc * col[p];
-        up[(size_t)nb * nr + k] = wr[c];
-        E.omega[k] = wr[c];
-        E.flags[k] = wi[c] != 0.0 ? EOM_FLAG_COMPLEX : 0;
-    }
-    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
-    // ---- Ritz pass
-    const int nblk = eom_nblk(nvec);
-    for (int k0 = 0; k0 < nr; k0 += EOM_RCHUNK)
-        LAUNCH(eom_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * nr, s.D1.d, s.D2.d, s.o, s.v,
-               nvec, k0, std::min(EOM_RCHUNK, nr - k0));
-    LAUNCH(eom_final_kernel, dim3(nr), E.sums, E.partial, nblk);
-    std::vector<double> nrm(nr);
-    read_back(cx, nrm.data(), E.sums, nr);   // (also: `up` is no longer read)
-    E.ritz = true;
-    int all = nr == E.nroots ? 1 : 0;
-    for (int k = 0; k < E.nroots; ++k) {
-        if (k >= nr) {   // fewer basis vectors than roots: not found (yet)
-            E.omega[k] = 0.0;
-            E.resnorm[k] = HUGE_VAL;
-            E.flags[k] = 0;
-            continue;
-        }
-        E.resnorm[k] = std::sqrt(nrm[k]);
-        if (E.resnorm[k] < tol) E.flags[k] |= EOM_FLAG_CONVERGED;
-        else {
-            all = 0;
-            k_copy(cx, E.pend + nvec * E.npend, E.corr + nvec * k, nvec);
-            ++E.npend;
-        }
-    }
-    return all;
+    Davidson& E = so_eom_need(s, eom_name(left, "iterate").c_str(), left).d;
+    return davidson_iterate(cx, E, eom_name(left), tol, [&](const double* r, double* sigma) {
+        if (left) so_eom_lsigma(cx, s, r, sigma);   // the projected matrix is then <b_p, sigma_L(b_q)>
+        else so_eom_sigma(cx, s, r, sigma);
+    });
 }
 
 void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2, bool left)
 {
     need_plain(cx);
-    SOEom& E = so_eom_need(s, eom_name(left, "get_vector").c_str(), left);
-    if (!E.ritz || k < 0 || k >= std::min(E.nroots, E.nb) || !r1 || !r2)
-        throw Error(1, eom_name(left, "get_vector") + ": no Ritz vector k (iterate first; k in 0 .. nroots - 1), or a NULL vector");
-    const int64_t ov = (int64_t)s.o * s.v;
-    AFESP_HIP(hipMemcpyAsync(r1, E.x + E.nvec * k, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
-    AFESP_HIP(hipMemcpyAsync(r2, E.x + E.nvec * k + ov, sizeof(double) * (E.nvec - ov), hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
+    davidson_get_vector(cx, so_eom_need(s, eom_name(left, "get_vector").c_str(), left).d, eom_name(left), k, r1, r2);
 }
 
 }  // namespace afesp
