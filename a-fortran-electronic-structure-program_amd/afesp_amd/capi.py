@@ -39,6 +39,8 @@ EXPORTS = [
     "afesp_ccsd_so_eom_left_iterate", "afesp_ccsd_so_eom_left_get_vector", "afesp_ccsd_so_eom_ref_coupling", "afesp_ccsd_so_eom_density",
     "afesp_ccsd_so_eom_ipea_init", "afesp_ccsd_so_eom_ipea_sigma", "afesp_ccsd_so_eom_ipea_guess", "afesp_ccsd_so_eom_ipea_set_guess",
     "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
+    "afesp_ccsd_so_response_xi", "afesp_ccsd_so_response_init", "afesp_ccsd_so_response_iterate", "afesp_ccsd_so_response_get_vector",
+    "afesp_ccsd_so_response_function", "afesp_lu_solve",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
@@ -150,6 +152,12 @@ def load_library():
     L.afesp_ccsd_so_eom_left_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     L.afesp_ccsd_so_eom_ref_coupling.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_density.argtypes = [C.c_void_p, dbl, _opt, _opt, dbl, _opt, _opt, _dp, i64]
+    L.afesp_ccsd_so_response_xi.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
+    L.afesp_ccsd_so_response_init.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int, _dp, C.c_int]
+    L.afesp_ccsd_so_response_iterate.argtypes = [C.c_void_p, dbl, _dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.afesp_ccsd_so_response_get_vector.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_response_function.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_lu_solve.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, dbl]
     L.afesp_ccsd_so_eom_ipea_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_ipea_sigma.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_ipea_guess.argtypes = [C.c_void_p, C.c_int]
@@ -1041,6 +1049,62 @@ class Engine:
         self._chk(self.L.afesp_ccsd_so_eom_density(self.h, l0, ptr[0][0], ptr[0][1], r0, ptr[1][0], ptr[1][1], buf,
                                                    buf.size if capacity is None else capacity))
         return buf.reshape((n, n), order="F")
+
+    # ---- EOM-CCSD linear response of the spin-orbital state (include/afesp.h; afesp_amd.response drives them).  The response state has a
+    # basis of its own: no call here touches t1 / t2, lambda or an EOM state
+    RESPONSE_POLE, RESPONSE_NOT_CONVERGED = 26, 27
+    response_shape = (0, 0)                                                 # (nop, signed frequencies) of the last so_response_init
+
+    def _so_operators(self, x, who):
+        n = self.so_o + self.so_v
+        x = np.asarray(x, dtype=np.float64)
+        single = x.ndim == 2
+        if single:
+            x = x[None]
+        if x.ndim != 3 or x.shape[1:] != (n, n):
+            raise ValueError(f"{who}: the operators are (k,) o+v x o+v matrices over the spin orbitals of this state")
+        return x.shape[0], np.concatenate([_f(m) for m in x]) if x.shape[0] else np.zeros(0), single
+
+    def so_response_xi(self, x):
+        """xi^X = <mu| X-bar |0> of one symmetric operator x (o+v, o+v) -> (xi1 (o,v), xi2 (o,o,v,v)); with a leading axis, k operators in
+        one launch -> the same with that axis."""
+        o, v = self.so_o, self.so_v
+        k, flat, single = self._so_operators(x, "so_response_xi")
+        x1, x2 = np.zeros(max(k, 1) * o * v), np.zeros(max(k, 1) * o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_response_xi(self.h, k, flat if k else np.zeros(1), x1, x2))
+        x1 = np.stack([m.reshape((o, v), order="F") for m in x1.reshape(k, o * v)])
+        x2 = np.stack([m.reshape((o, o, v, v), order="F") for m in x2.reshape(k, o * o * v * v)])
+        return (x1[0], x2[0]) if single else (x1, x2)
+
+    def so_response_init(self, x, omega_signed, max_space):
+        """The response state of the operators x (k, o+v, o+v) for the signed frequencies omega_signed, on one basis of max_space vectors"""
+        k, flat, _ = self._so_operators(x, "so_response_init")
+        om = np.ascontiguousarray(np.atleast_1d(omega_signed), dtype=np.float64)
+        self._chk(self.L.afesp_ccsd_so_response_init(self.h, k, flat if k else np.zeros(1), om.size, om if om.size else np.zeros(1), max_space))
+        self.response_shape = (k, om.size)
+
+    def so_response_iterate(self, tol=1e-8):
+        """One step -> (resnorm [signed frequencies, nop], sigma builds so far, converged)"""
+        nop, nf = self.response_shape
+        rs = np.zeros(max(nop * nf, 1))
+        ns, cv = C.c_int(), C.c_int()
+        self._chk(self.L.afesp_ccsd_so_response_iterate(self.h, tol, rs, C.byref(ns), C.byref(cv)))
+        return rs[:nop * nf].reshape(nf, nop), ns.value, bool(cv.value)
+
+    def so_response_vector(self, iop, ifreq):
+        """R^X_iop(omega_signed[ifreq]) of the last step -> (r1, r2)"""
+        o, v = self.so_o, self.so_v
+        r1, r2 = np.zeros(o * v), np.zeros(o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_response_get_vector(self.h, iop, ifreq, r1, r2))
+        return r1.reshape((o, v), order="F"), r2.reshape((o, o, v, v), order="F")
+
+    def so_response_function(self, omegas):
+        """<<X_a;X_b>>_omega for every omega of omegas whose +omega and -omega solutions are converged in the state -> (nfreq, nop, nop)"""
+        nop = self.response_shape[0]
+        om = np.ascontiguousarray(np.atleast_1d(omegas), dtype=np.float64)
+        out = np.zeros(max(om.size * nop * nop, 1))
+        self._chk(self.L.afesp_ccsd_so_response_function(self.h, om.size, om if om.size else np.zeros(1), out))
+        return out[:om.size * nop * nop].reshape(om.size, nop, nop)
 
     # ---- EOM-IP-CCSD / EOM-EA-CCSD of the same state (include/afesp.h; afesp_amd.eom drives them).  sector: EOM_IP (1h + 2h1p:
     # r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)); the rules and statuses are those of the EE calls above

@@ -48,6 +48,8 @@ class SystemIn:
     cc_relaxed: bool = False        # ... Lambda, the two-particle density, the Z-vector and the orbital-relaxed density (density.so_relaxed_density_solve)
     cc_lambda_t: bool = False       # after a converged spin-orbital CCSD: Lambda and the Lambda-CCSD(T) correction (density.so_lambda_t_correction)
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
+    cc_polar: bool = False          # ... the EOM-CCSD polarisability alpha(omega) from dipx.dat / dipy.dat / dipz.dat (afesp_amd/response.py)
+    polar_omega: list = dataclasses.field(default_factory=lambda: [0.0])   # ... at these real frequencies / Eh (up to 8)
     eom_left: bool = False          # ... and their left eigenvectors, from the right ones as guess (eom.so_eom_left_solve); needs eom_nroots > 0
     eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
@@ -111,6 +113,12 @@ def read_els_in(path: str) -> SystemIn:
         if not hasattr(sysin, key):
             raise ValueError("invalid input file format!")
         setattr(sysin, key, _parse_value(val))
+    # polar_omega is the one list-valued key: every number behind it, comma-separated (the loop above kept the first alone)
+    pm = re.search(r"\bpolar_omega\s*=\s*((?:\s*[-+]?(?:\d+\.?\d*|\.\d+)(?:[eEdD][-+]?\d+)?\s*,?)+)", m.group(1), re.I)
+    if pm:
+        sysin.polar_omega = [float(x.lower().replace("d", "e")) for x in pm.group(1).replace(",", " ").split()]
+    elif not isinstance(sysin.polar_omega, list):
+        raise ValueError("invalid input file format!")
     if sysin.calc_type not in _CALC_TYPES:
         raise ValueError("Unrecognised calculation type!")   # system.f90:163
     (sysin.level, sysin.restricted, sysin.ccsd_t_paren, sysin.ccsd_t_renorm,
@@ -184,6 +192,15 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("invalid input file format!")
     if sysin.eom_left and sysin.eom_nroots == 0:
         raise ValueError("eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!")
+    if not isinstance(sysin.cc_polar, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.cc_polar and sysin.calc_type not in CC_DENSITY_TYPES:
+        raise ValueError(f"{sysin.calc_type} takes no cc_polar: the response equations run on the spin-orbital CCSD types!")
+    if sysin.cc_polar and sysin.fcidump_in:
+        raise ValueError("cc_polar with fcidump_in: the operator files dipx.dat / dipy.dat / dipz.dat are in the AO basis, which a FCIDUMP "
+                         "run does not have!")
+    if not 1 <= len(sysin.polar_omega) <= 8:
+        raise ValueError("polar_omega takes at most 8 frequencies!")
     for key in ("eom_ip_nroots", "eom_ea_nroots"):
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < 0:

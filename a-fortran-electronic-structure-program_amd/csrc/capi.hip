@@ -15,6 +15,7 @@
 #include "relax_so.h"
 #include "eom_so.h"
 #include "eom_ipea_so.h"
+#include "response_so.h"
 #include "small_eig.h"
 #include "comm.h"
 #include "tall.h"
@@ -123,7 +124,7 @@ void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
 
 extern "C" {
 
-int afesp_version(void) { return 3; }
+int afesp_version(void) { return 4; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -800,6 +801,47 @@ int afesp_ccsd_so_eom_density(afesp_ctx* ctx, double l0, const double* l1, const
         so_eom_density(cx, ctx->sv.need_so("afesp_ccsd_so_eom_density: no spin-orbital CCSD state").so, l0, l1, l2, r0, r1, r2, d, capacity);
     });
 }
+
+// ---- EOM-CCSD linear response (response_so.h)
+int afesp_ccsd_so_response_xi(afesp_ctx* ctx, int nop, const double* x, double* xi1, double* xi2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_xi_host(cx, ctx->sv.need_so("afesp_ccsd_so_response_xi: no spin-orbital CCSD state").so, nop, x, xi1, xi2);
+    });
+}
+
+int afesp_ccsd_so_response_init(afesp_ctx* ctx, int nop, const double* x, int nfreq_signed, const double* omega, int max_space)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_init(cx, ctx->sv.need_so("afesp_ccsd_so_response_init: no spin-orbital CCSD state").so, nop, x, nfreq_signed, omega, max_space);
+    });
+}
+
+int afesp_ccsd_so_response_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* nsigma, int* converged)
+{
+    return entry(ctx, [&](Context& cx) {
+        SOState& so = ctx->sv.need_so("afesp_ccsd_so_response_iterate: no spin-orbital CCSD state").so;
+        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_response_iterate: tol must be positive");
+        const int conv = so_response_iterate(cx, so, tol);
+        davidson_report(so.resp->d, conv, nullptr, resnorm, nullptr, nsigma, converged);
+    });
+}
+
+int afesp_ccsd_so_response_get_vector(afesp_ctx* ctx, int iop, int ifreq, double* r1, double* r2)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_get_vector(cx, ctx->sv.need_so("afesp_ccsd_so_response_get_vector: no spin-orbital CCSD state").so, iop, ifreq, r1, r2);
+    });
+}
+
+int afesp_ccsd_so_response_function(afesp_ctx* ctx, int nfreq, const double* omega, double* out)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_function(cx, ctx->sv.need_so("afesp_ccsd_so_response_function: no spin-orbital CCSD state").so, nfreq, omega, out);
+    });
+}
+
+int afesp_lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor) { return lu_solve(n, a, lda, nrhs, b, ldb, floor); }
 
 // ---- EOM-IP-CCSD and EOM-EA-CCSD (eom_ipea_so.h)
 static SOState& ipea_state(afesp_ctx* ctx, int sector, const char* who)

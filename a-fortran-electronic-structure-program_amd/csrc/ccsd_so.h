@@ -10,6 +10,7 @@ namespace afesp {
 struct SOLambda;   // lambda_so.h
 struct SOEom;      // eom_so.h
 struct SOEomX;     // eom_ipea_so.h
+struct SOResponse; // response_so.h
 
 struct SOState : DiisRing {
     int o = 0, v = 0, n = 0;
@@ -40,6 +41,7 @@ struct SOState : DiisRing {
     SOEom* eom = nullptr;            // the EOM state that borrows lam's H-bar elements (eom_so.h); released wherever lam is
     SOEom* eom_left = nullptr;       // the left-hand Davidson state beside it (eigenvectors of A^T); released with it
     SOEomX* ipea[2] = {nullptr, nullptr};   // ... and those of the EOM-IP and EOM-EA sectors (eom_ipea_so.h), released with it
+    SOResponse* resp = nullptr;      // the linear-response state beside them (response_so.h), released with it
 };
 
 // eri_mo_dev: packed chemist MO integrals on the device (length neri(nbasis)); e_host: spatial orbital energies (host)
@@ -70,6 +72,7 @@ void so_pair_pack(Context& cx, SOState& s, const Tensor& x, double* xa);
 void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip (releases the EOM state too: it borrows from the Lambda state)
 void so_eom_free(Context& cx, SOState& s);        // eom_so.hip
 void so_eom_ipea_free(Context& cx, SOState& s);   // eom_ipea_so.hip
+void so_response_free(Context& cx, SOState& s);   // response_so.hip
 // (T): contribution of the triples i<j<k with flat index in [t_begin, t_end) to E_T (ccsd.f90:1910)
 int64_t so_triples_count(int o);
 double so_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);

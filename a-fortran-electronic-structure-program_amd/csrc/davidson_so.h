@@ -2,6 +2,10 @@
 // sigma build on device vectors.  A vector has n1 elements of weight 1 and nvec - n1 of weight w2 in the metric
 // <x, y> = sum x1 y1 + w2 sum x2 y2; the vectors never leave the device.  The unit knows nothing of coupled cluster: its users are
 // EOM-EE-CCSD, right and left (eom_so.h), and the EOM-IP and EOM-EA sectors (eom_ipea_so.h).
+//
+// Linear mode (davidson_linear_*; its user is response_so.h): the same basis, sigma storage, orthonormalisation, Gram panel
+// collapse and fused pass solve (A - shift_j) x_j = -rhs_j for `nroots` systems at once on ONE basis -- every pending correction costs one sigma build
+// that serves every system.  The eigenvalue entry points above are untouched by it.
 #pragma once
 #include "afesp_internal.h"
 
@@ -38,7 +42,14 @@ struct Davidson {
     std::vector<double> omega, resnorm;
     std::vector<int> flags;
     int nsigma = 0, ncollapse = 0;
+    // linear mode: system j has the shift `shift[j]` and the right-hand side column j % nrhs of `rhs` (device, nvec apart, borrowed);
+    // prhs[p + max_space a] = <b_p, rhs_a> (host)
+    const double* rhs = nullptr;
+    int nrhs = 0;
+    std::vector<double> shift, prhs;
 };
+
+constexpr int DAVIDSON_ERR_POLE = 26;   // davidson_linear_iterate: a shift is at a root of the projected matrix
 
 using DavidsonSigma = std::function<void(const double* r, double* sigma)>;   // sigma = A r on device vectors
 
@@ -56,6 +67,17 @@ void davidson_set_pending_from_host(Context& cx, Davidson& D, const std::string&
 // matrix, solve it on the host, Ritz pass.  -> 1 when every root has |rho_k| < tol
 int davidson_iterate(Context& cx, Davidson& D, const std::string& prefix, double tol, const DavidsonSigma& sigma);
 void davidson_get_vector(Context& cx, Davidson& D, const std::string& prefix, int k, double* r1, double* r2);
+// ---- linear mode.  Start: no basis, and the pending vectors are the preconditioned right-hand sides rhs_j / (shift_j - diag) (the
+// denominator guarded as the Ritz pass guards it).  nrhs columns in rhs, nroots shifts.
+void davidson_linear_start(Context& cx, Davidson& D, const double* rhs, int nrhs, const double* shifts);
+// One step: (collapse onto the current x_j if the pending vectors do not fit,) orthonormalise the pending vectors, build their sigma,
+// extend the projected matrix and the projected right-hand sides, solve (G - shift_j) y_j = -B^T rhs_j on the host by LU, then one fused
+// pass: x_j = B y_j, rho_j = rhs_j + (S - shift_j B) y_j, |rho_j| and the corrections rho_j / (shift_j - diag) of the systems with
+// |rho_j| >= tol, which become the pending vectors scaled by 1 / |rho_j| (the drop threshold of the orthonormalisation is absolute).
+// D.x holds the solutions, D.resnorm their residual norms, D.flags bit 0 |rho_j| < tol.  -> 1 when every system has converged.
+// Throws DAVIDSON_ERR_POLE when a pivot of a projected system is below 1e-10 max(|G|_max, |shift_j|): the basis has been extended and
+// the sigma builds counted by then, no pending vector is left, and a repeated call only solves the same systems and throws again.
+int davidson_linear_iterate(Context& cx, Davidson& D, const std::string& prefix, double tol, const DavidsonSigma& sigma);
 // the fixed-order reduction of this unit for others: blocks of a partial-sum grid over nvec elements, and out[b] = the ordered sum of
 // partial[b nblk .. (b + 1) nblk)
 int davidson_reduce_blocks(int64_t nvec);

@@ -14,6 +14,7 @@ namespace {
 constexpr int DAV_MAXBLK = 128;   // blocks of a reduction (at most TB: davidson_final_kernel sums them in one block)
 constexpr int DAV_RCHUNK = 8;     // roots one launch of the Ritz pass forms
 constexpr double DAV_DROP = 1e-10, DAV_CLAMP = 1e-4;
+constexpr double DAV_POLE = 1e-10;   // linear mode: a pivot below this times max(|G|_max, |shift|) is a pole
 
 // The Gram panel of one vector pair (bq, sq) against ncol stored columns, in one launch -- block (blk, p):
 //   p < ncol:  <b_p, sq>, <s_p, bq>, <b_p, bq>        p = ncol:  <bq, sq>, the same again, <bq, bq>
@@ -83,9 +84,11 @@ __global__ void davidson_scale_kernel(double* dst, const double* src, double* ds
 // The Ritz pass for the roots k0 .. k0 + nr (nr <= DAV_RCHUNK): every stored b_p and sigma_p is read once and gives
 //   x_k = sum_p y(p,k) b_p,  sx_k = sum_p y(p,k) sigma_p,  rho_k = sx_k - omega_k x_k,  corr_k = rho_k / (omega_k - diag)
 // (|omega_k - diag| clamped below at DAV_CLAMP, keeping its sign) and the block partials of <rho_k, rho_k> at
-// partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.
+// partial[(k0 + k) nblk + blk].  y: nb x nroots column-major.  rhs non-null: the fused pass of the linear mode -- omega holds the shifts
+// and rho_k = rhs_(k % nrhs) + (sx_k - omega_k x_k); rhs null is the Ritz pass, with the arithmetic it always had.
 __global__ void davidson_ritz_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride, int nb,
-                                     const double* y, const double* omega, const double* diag, int64_t n1, double w2, int64_t nvec, int k0, int nr)
+                                     const double* y, const double* omega, const double* diag, int64_t n1, double w2, int64_t nvec, int k0, int nr,
+                                     const double* rhs, int nrhs)
 {
     __shared__ double sm[DAV_RCHUNK * 4];
     double nrm[DAV_RCHUNK];
@@ -111,7 +114,8 @@ __global__ void davidson_ritz_kernel(double* X, double* SX, double* corr, double
         for (int k = 0; k < DAV_RCHUNK; ++k)
             if (k < nr) {
                 const double om = omega[k0 + k];
-                const double rho = __fma_rn(-om, xa[k], sa[k]);
+                double rho = __fma_rn(-om, xa[k], sa[k]);
+                if (rhs) rho = __dadd_rn(rhs[stride * ((k0 + k) % nrhs) + e], rho);
                 double den = om - D;
                 if (fabs(den) < DAV_CLAMP) den = den < 0.0 ? -DAV_CLAMP : DAV_CLAMP;
                 X[stride * (k0 + k) + e] = xa[k];
@@ -125,6 +129,21 @@ __global__ void davidson_ritz_kernel(double* X, double* SX, double* corr, double
         for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
 }
 
+// pend_j = rhs_(j % nrhs) / (shift_j - diag), j < nsys: the first pending vectors of the linear mode
+__global__ void davidson_precondition_kernel(double* pend, const double* rhs, int nrhs, const double* shift, const double* diag, int64_t stride,
+                                             int nsys, int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        const double D = diag[e];
+        for (int j = 0; j < nsys; ++j) {
+            double den = shift[j] - D;
+            if (fabs(den) < DAV_CLAMP) den = den < 0.0 ? -DAV_CLAMP : DAV_CLAMP;
+            pend[stride * j + e] = rhs[stride * (j % nrhs) + e] / den;
+        }
+    }
+}
+
 void preload_once()
 {
     static const bool loaded = [] {
@@ -133,6 +152,7 @@ void preload_once()
         first_use_touch(reinterpret_cast<const void*>(davidson_project_kernel));
         first_use_touch(reinterpret_cast<const void*>(davidson_scale_kernel));
         first_use_touch(reinterpret_cast<const void*>(davidson_ritz_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_precondition_kernel));
         (void)hipGetLastError();
         return true;
     }();
@@ -182,6 +202,21 @@ void extend_projected(Context& cx, Davidson& E)
     for (int p = 0; p <= q; ++p) E.G[p + (size_t)ms * q] = h[p];
     for (int p = 0; p < q; ++p) E.G[q + (size_t)ms * p] = h[(q + 1) + p];
     E.nb = q + 1;
+}
+
+// linear mode: extend_projected, and row q of the projected right-hand sides <b_q, rhs_a> through the same panel kernel (the right-hand
+// sides in the place of the stored columns, overlaps alone)
+void extend_linear(Context& cx, Davidson& E)
+{
+    const int q = E.nb, ms = E.max_space, nr = E.nrhs;
+    extend_projected(cx, E);
+    const int nblk = davidson_reduce_blocks(E.nvec);
+    LAUNCH(davidson_panel_kernel, dim3(nblk, nr + 1), E.partial, E.rhs, (const double*)nullptr, E.nvec, nr, E.B + E.nvec * q, (const double*)nullptr,
+           E.nvec, E.n1, E.w2);
+    LAUNCH(davidson_final_kernel, dim3(3 * (nr + 1)), E.sums, E.partial, nblk);
+    std::vector<double> h(nr);
+    read_back(cx, h.data(), E.sums + 2 * (nr + 1), nr);
+    for (int a = 0; a < nr; ++a) E.prhs[q + (size_t)ms * a] = h[a];
 }
 
 }  // namespace
@@ -327,7 +362,7 @@ int davidson_iterate(Context& cx, Davidson& E, const std::string& prefix, double
     const int nblk = davidson_reduce_blocks(nvec);
     for (int k0 = 0; k0 < nr; k0 += DAV_RCHUNK)
         LAUNCH(davidson_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * nr, E.diag, E.n1, E.w2,
-               nvec, k0, std::min(DAV_RCHUNK, nr - k0));
+               nvec, k0, std::min(DAV_RCHUNK, nr - k0), (const double*)nullptr, 1);
     LAUNCH(davidson_final_kernel, dim3(nr), E.sums, E.partial, nblk);
     std::vector<double> nrm(nr);
     read_back(cx, nrm.data(), E.sums, nr);   // (also: `up` is no longer read)
@@ -347,6 +382,88 @@ int davidson_iterate(Context& cx, Davidson& E, const std::string& prefix, double
             k_copy(cx, E.pend + nvec * E.npend, E.corr + nvec * k, nvec);
             ++E.npend;
         }
+    }
+    return all;
+}
+
+void davidson_linear_start(Context& cx, Davidson& E, const double* rhs, int nrhs, const double* shifts)
+{
+    if (!rhs || nrhs < 1 || nrhs > E.nroots || !shifts) throw Error(1, "davidson_linear_start: no right-hand sides or shifts");
+    davidson_restart(E);
+    E.rhs = rhs;
+    E.nrhs = nrhs;
+    E.shift.assign(shifts, shifts + E.nroots);
+    E.prhs.assign((size_t)E.max_space * nrhs, 0.0);
+    std::fill(E.resnorm.begin(), E.resnorm.end(), HUGE_VAL);
+    AFESP_HIP(hipMemcpyAsync(E.coef, E.shift.data(), sizeof(double) * E.nroots, hipMemcpyHostToDevice, cx.stream));
+    LAUNCH(davidson_precondition_kernel, grid_for(E.nvec), E.pend, rhs, nrhs, E.coef, E.diag, E.nvec, E.nroots, E.nvec);
+    cx.sync();   // (E.coef is written again by the first step)
+    E.npend = E.nroots;
+}
+
+int davidson_linear_iterate(Context& cx, Davidson& E, const std::string& prefix, double tol, const DavidsonSigma& sigma)
+{
+    const std::string who = prefix + "iterate";
+    const int64_t nvec = E.nvec;
+    const int ms = E.max_space, ns = E.nroots;
+    if (!E.rhs || (E.nb == 0 && E.npend == 0)) throw Error(1, who + ": no right-hand sides (call " + prefix + "init first)");
+    // ---- collapse onto the current solutions, their sigma being the same combination of the stored sigma (no new sigma builds)
+    if (E.nb + E.npend > ms) {
+        E.nb = 0;
+        for (int k = 0; k < ns; ++k)
+            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k)) extend_linear(cx, E);
+        ++E.ncollapse;
+    }
+    // ---- the pending vectors: orthonormalise, ONE sigma build each for all systems, the projected matrix and right-hand sides
+    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
+        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr)) continue;
+        sigma(E.B + nvec * E.nb, E.S + nvec * E.nb);
+        ++E.nsigma;
+        extend_linear(cx, E);
+    }
+    E.npend = 0;
+    if (E.nb == 0) throw Error(1, who + ": every right-hand side vanished");
+    // ---- (G - shift_j) y_j = -B^T rhs_j on the host
+    const int nb = E.nb;
+    double gmax = 0.0;
+    for (int q = 0; q < nb; ++q)
+        for (int p = 0; p < nb; ++p) gmax = std::max(gmax, std::fabs(E.G[p + (size_t)ms * q]));
+    std::vector<double> m((size_t)nb * nb), up((size_t)nb * ns + ns);
+    for (int j = 0; j < ns; ++j) {
+        const double om = E.shift[j];
+        for (int q = 0; q < nb; ++q)
+            for (int p = 0; p < nb; ++p) m[p + (size_t)nb * q] = E.G[p + (size_t)ms * q] - (p == q ? om : 0.0);
+        double* y = up.data() + (size_t)nb * j;
+        for (int p = 0; p < nb; ++p) y[p] = -E.prhs[p + (size_t)ms * (j % E.nrhs)];
+        const int rc = lu_solve(nb, m.data(), nb, 1, y, nb, DAV_POLE * std::max(gmax, std::fabs(om)));
+        if (rc == 2)
+            throw Error(DAVIDSON_ERR_POLE, who + ": frequency at a pole: system " + std::to_string(j) + " (shift " + std::to_string(om) +
+                                               ") is singular in the projected space of " + std::to_string(nb) + " vectors");
+        if (rc) throw Error(1, who + ": the projected system was not solved (status " + std::to_string(rc) + ")");
+        up[(size_t)nb * ns + j] = om;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
+    // ---- the fused pass: the Ritz kernel with the right-hand sides
+    const int nblk = davidson_reduce_blocks(nvec);
+    for (int k0 = 0; k0 < ns; k0 += DAV_RCHUNK)
+        LAUNCH(davidson_ritz_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, E.coef, E.coef + (size_t)nb * ns, E.diag, E.n1,
+               E.w2, nvec, k0, std::min(DAV_RCHUNK, ns - k0), E.rhs, E.nrhs);
+    LAUNCH(davidson_final_kernel, dim3(ns), E.sums, E.partial, nblk);
+    std::vector<double> nrm(ns);
+    read_back(cx, nrm.data(), E.sums, ns);   // (also: `up` is no longer read)
+    E.ritz = true;
+    int all = 1;
+    for (int j = 0; j < ns; ++j) {
+        E.omega[j] = E.shift[j];
+        E.resnorm[j] = std::sqrt(nrm[j]);
+        E.flags[j] = E.resnorm[j] < tol ? EOM_FLAG_CONVERGED : 0;
+        if (E.flags[j]) continue;
+        all = 0;
+        // (scaled by 1 / |rho_j|: the drop threshold of the orthonormalisation is absolute, and a correction of a nearly converged system
+        // is as small as its residual)
+        LAUNCH(davidson_scale_kernel, grid_for(nvec), E.pend + nvec * E.npend, E.corr + nvec * j, (double*)nullptr, (const double*)nullptr,
+               1.0 / E.resnorm[j], nvec);
+        ++E.npend;
     }
     return all;
 }

@@ -32,6 +32,8 @@ void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const do
 int so_eom_iterate(Context& cx, SOState& s, double tol, bool left = false);
 void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2, bool left = false);
 SOEom& so_eom_need(SOState& s, const char* who, bool left = false);
+// the diagonal guess of A as the Davidson unit reads it, -D, into a vector of o v + o^2 v^2 (the EE states' and the response state's)
+void so_eom_fill_diag(Context& cx, SOState& s, double* diag);
 void preload_eom_so();
 
 // ---- the left-hand side (eom_left_so.hip)

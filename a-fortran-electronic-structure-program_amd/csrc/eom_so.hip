@@ -101,6 +101,12 @@ void so_eom_free(Context& cx, SOState& s)
     eom_free_one(cx, s, true);
 }
 
+void so_eom_fill_diag(Context& cx, SOState& s, double* diag)
+{
+    const int64_t nvec = (int64_t)s.o * s.v + (int64_t)s.o * s.o * s.v * s.v;
+    LAUNCH(eom_diag_kernel, grid_for(nvec), diag, s.D1.d, s.D2.d, s.o, s.v, nvec);
+}
+
 SOEom& so_eom_need(SOState& s, const char* who, bool left)
 {
     so_lambda_need(s, who);
@@ -135,7 +141,7 @@ void so_eom_init(Context& cx, SOState& s, int nroots, int max_space, bool left)
     try {
         E.left = left;
         davidson_alloc(cx, E.d, O * V, nvec, 0.25, left, nroots, max_space,
-                       [&](double* diag) { LAUNCH(eom_diag_kernel, grid_for(nvec), diag, s.D1.d, s.D2.d, s.o, s.v, nvec); });
+                       [&](double* diag) { so_eom_fill_diag(cx, s, diag); });
         E.d.epoch = L.epoch;
         cx.sync();
     } catch (...) {

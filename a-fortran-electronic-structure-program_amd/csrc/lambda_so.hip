@@ -198,6 +198,7 @@ void so_lambda_free(Context& cx, SOState& s)
 {
     so_eom_free(cx, s);   // (it borrows this state's H-bar elements)
     so_eom_ipea_free(cx, s);
+    so_response_free(cx, s);
     if (!s.lam) return;
     so_density2_free(cx, *s.lam);
     so_relax_free(cx, *s.lam);

@@ -1,8 +1,8 @@
 // small_eig.h -- eigenvalues and right eigenvectors of a small real general matrix on the host (the projected matrix of the EOM
 // Davidson iteration, eom_so.h: n is at most a few hundred).  Householder reduction to Hessenberg form, the shifted double-step QR
 // iteration on it with the transformations accumulated, and back-substitution for the vectors of the quasi-triangular form (the
-// classical orthes / hqr2 pair: Wilkinson and Reinsch, Handbook for Automatic Computation II, 1971).  Host code only; the library links
-// no LAPACK.
+// classical orthes / hqr2 pair: Wilkinson and Reinsch, Handbook for Automatic Computation II, 1971), and the partial-pivot LU solve of
+// the projected linear systems of its linear mode (davidson_so.h).  Host code only; the library links no LAPACK.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -401,6 +401,39 @@ inline int eig_general(int n, const double* a, int lda, double* wr, double* wi, 
         s = s > 0.0 ? 1.0 / std::sqrt(s) : 0.0;
         for (int i = 0; i < n; ++i) vr[i + (size_t)n * k] = w.V(i, c) * s;
     }
+    return 0;
+}
+
+// a x = b for nrhs right-hand sides by LU with partial pivoting, in place: a (n x n, column-major, leading dimension lda) is overwritten
+// by its factors and b (n x nrhs, leading dimension ldb) by the solutions.  -> 0, 1 on a bad argument, 2 when a pivot is not above
+// `floor` in magnitude (floor = 0: an exactly singular matrix) -- a and b then hold a partial elimination.
+inline int lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor)
+{
+    if (n < 1 || nrhs < 0 || !a || lda < n || (nrhs > 0 && (!b || ldb < n)) || !(floor >= 0.0)) return 1;
+    for (int k = 0; k < n; ++k) {
+        int p = k;
+        for (int i = k + 1; i < n; ++i)
+            if (std::fabs(a[i + (size_t)lda * k]) > std::fabs(a[p + (size_t)lda * k])) p = i;
+        if (!(std::fabs(a[p + (size_t)lda * k]) > floor)) return 2;
+        if (p != k) {
+            for (int j = 0; j < n; ++j) std::swap(a[k + (size_t)lda * j], a[p + (size_t)lda * j]);
+            for (int j = 0; j < nrhs; ++j) std::swap(b[k + (size_t)ldb * j], b[p + (size_t)ldb * j]);
+        }
+        const double piv = a[k + (size_t)lda * k];
+        for (int i = k + 1; i < n; ++i) {
+            const double l = a[i + (size_t)lda * k] / piv;
+            if (l == 0.0) continue;
+            a[i + (size_t)lda * k] = l;
+            for (int j = k + 1; j < n; ++j) a[i + (size_t)lda * j] -= l * a[k + (size_t)lda * j];
+            for (int j = 0; j < nrhs; ++j) b[i + (size_t)ldb * j] -= l * b[k + (size_t)ldb * j];
+        }
+    }
+    for (int j = 0; j < nrhs; ++j)
+        for (int k = n - 1; k >= 0; --k) {
+            double x = b[k + (size_t)ldb * j];
+            for (int i = k + 1; i < n; ++i) x -= a[k + (size_t)lda * i] * b[i + (size_t)ldb * j];
+            b[k + (size_t)ldb * j] = x / a[k + (size_t)lda * k];
+        }
     return 0;
 }
 

@@ -26,6 +26,7 @@ module afesp_capi
              afesp_ccsd_so_eom_density, &
              afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
              afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
+             afesp_ccsd_so_response_init, afesp_ccsd_so_response_iterate, afesp_ccsd_so_response_function, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -585,6 +586,30 @@ module afesp_capi
          type(c_ptr), value :: l1, l2, r1, r2
          real(c_double), intent(out) :: d(*)
          integer(c_int64_t), value :: capacity
+         integer(c_int) :: rc
+      end function
+      ! EOM-CCSD linear response (include/afesp.h): x holds nop operators of (o+v)^2 each, omega the signed frequencies
+      function afesp_ccsd_so_response_init(ctx, nop, x, nfreq_signed, omega, max_space) bind(C, name='afesp_ccsd_so_response_init') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nop, nfreq_signed, max_space
+         real(c_double), intent(in) :: x(*), omega(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_response_iterate(ctx, tol, resnorm, nsigma, converged) bind(C, name='afesp_ccsd_so_response_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         real(c_double), value :: tol
+         real(c_double), intent(out) :: resnorm(*)
+         integer(c_int), intent(out) :: nsigma, converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_response_function(ctx, nfreq, omega, res) bind(C, name='afesp_ccsd_so_response_function') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nfreq
+         real(c_double), intent(in) :: omega(*)
+         real(c_double), intent(out) :: res(*)
          integer(c_int) :: rc
       end function
       ! EOM-IP-CCSD / EOM-EA-CCSD: the same calls with a sector (AFESP_EOM_IP, AFESP_EOM_EA) behind the context (include/afesp.h)

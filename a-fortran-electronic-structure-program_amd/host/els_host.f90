@@ -65,6 +65,11 @@ module host_config
       logical :: eom_left = .false.
       ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
       integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
+      ! after a converged spin-orbital CCSD: the EOM-CCSD polarisability alpha(omega) of the operators in dipx.dat / dipy.dat / dipz.dat
+      ! (AO basis, the format of t.dat) at the n_polar_omega real frequencies polar_omega (default: the static one)
+      logical :: cc_polar = .false.
+      real(dp) :: polar_omega(8) = 0.0_dp
+      integer :: n_polar_omega = 1
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -76,11 +81,14 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left, cc_rdm2, cc_relaxed
+      logical :: eom_left, cc_rdm2, cc_relaxed, cc_polar
+      real(dp) :: polar_omega(8)
+      real(dp), parameter :: omega_unset = huge(1.0_dp)
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2, cc_relaxed
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2, cc_relaxed, &
+         cc_polar, polar_omega
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -92,6 +100,7 @@ contains
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
       cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
+      cc_polar = d%cc_polar; polar_omega = omega_unset
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -175,6 +184,26 @@ contains
       cfg%eom_left = eom_left
       if (eom_left .and. eom_nroots == 0) call fail('system::read_system_in', &
          'eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!')
+      cfg%cc_polar = cc_polar
+      if (cc_polar .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
+         trim(calc_type)//' takes no cc_polar: the response equations run on the spin-orbital CCSD types!')
+      if (cc_polar .and. fcidump_in) call fail('system::read_system_in', &
+         'cc_polar with fcidump_in: the operator files dipx.dat / dipy.dat / dipz.dat are in the AO basis, which a FCIDUMP run does not have!')
+      if (cc_polar) then   ! (an input error before anything runs; polarizability_report reads them after CCSD)
+         inquire (file='dipx.dat', exist=there)
+         if (.not. there) call fail('system::read_system_in', 'cc_polar: the operator file dipx.dat does not exist!')
+         inquire (file='dipy.dat', exist=there)
+         if (.not. there) call fail('system::read_system_in', 'cc_polar: the operator file dipy.dat does not exist!')
+         inquire (file='dipz.dat', exist=there)
+         if (.not. there) call fail('system::read_system_in', 'cc_polar: the operator file dipz.dat does not exist!')
+      end if
+      cfg%n_polar_omega = count(polar_omega /= omega_unset)   ! (the values given, from the front)
+      if (cfg%n_polar_omega > 0) then
+         if (any(polar_omega(:cfg%n_polar_omega) == omega_unset)) call fail('system::read_system_in', 'invalid input file format!')
+         cfg%polar_omega(:cfg%n_polar_omega) = polar_omega(:cfg%n_polar_omega)
+      else
+         cfg%n_polar_omega = 1
+      end if
       cfg%eom_ip_nroots = eom_ip_nroots; cfg%eom_ea_nroots = eom_ea_nroots
       if (eom_ip_nroots < 0) call fail('system::read_system_in', 'eom_ip_nroots must be a non-negative integer!')
       if (eom_ea_nroots < 0) call fail('system::read_system_in', 'eom_ea_nroots must be a non-negative integer!')
@@ -973,6 +1002,7 @@ program els_amd
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
+         if (cfg%cc_polar .and. cc_ok) call polarizability_report(n_act, na_act, nb_act, .false.)
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             t0 = seconds()
             write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'CCSD(T)'; write (out, '(1X, 10("-"))')
@@ -1081,6 +1111,7 @@ program els_amd
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, nel_act, 2*n_act - nel_act)
+         if (cfg%cc_polar .and. cc_ok) call polarizability_report(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%level == LEVEL_CCSD_T .and. cc_ok) then
             ! ---------------- spin-orbital (T) (reference do_ccsd_t_spinorb, src/ccsd.f90:1812-1922)
             t0 = seconds()
@@ -1609,6 +1640,95 @@ contains
          write (out, '(1X, A, 1X, F16.8)') '<V_ne> (relaxed CCSD density, Hartree):', ex(2, 2)
       end if
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the relaxed CCSD density:', seconds() - tl, 's'
+   end subroutine
+   !> cc_polar: the EOM-CCSD polarisability alpha(omega) = -<<mu;mu>>_omega of the converged state (DESIGN.md 4.19).  The three operators
+   !> are read from dipx.dat / dipy.dat / dipz.dat (AO basis, the format of t.dat) and transformed with the SCF coefficients as
+   !> cc_relaxed transforms T and V_ne; Lambda is the one solve shared with cc_density, cc_lambda_t and the EOM sectors; all right-hand
+   !> sides (3 operators x +-omega, every frequency) share one basis.  Prints one 3 x 3 table per frequency with the isotropic mean and the
+   !> anisotropy, the sigma builds and the largest residual.
+   subroutine polarizability_report(n, nalpha, nbeta, interleaved)
+      integer, intent(in) :: n, nalpha, nbeta
+      logical, intent(in) :: interleaved
+      character(8), parameter :: files(3) = ['dipx.dat', 'dipy.dat', 'dipz.dat']
+      real(dp), parameter :: polar_tol = 1.0e-8_dp
+      real(dp), allocatable :: ao(:, :), ma(:, :), mb(:, :), xso(:, :, :), signed(:), res(:), rf(:, :, :, :)
+      integer, allocatable :: orb(:), spin(:)
+      integer(c_int) :: nsig, pconv
+      integer(c_int64_t) :: o8, v8, nunique
+      real(dp) :: tp, alpha(3, 3), sym(3, 3), mean, aniso
+      integer :: c, x, y, f, ns, nb_ao, ms, it, nsys
+      logical :: there, ok
+      tp = seconds()
+      write (out, '(1X, 10("-"))'); write (out, '(1X, A)') 'EOM-CCSD polarisability'; write (out, '(1X, 10("-"))')
+      allocate (orb(2*n), spin(2*n), xso(2*n, 2*n, 3))
+      call spin_orbital_map(n, nalpha, nbeta, interleaved, orb, spin)
+      do c = 1, 3
+         inquire (file=files(c), exist=there)
+         if (.not. there) call fail('polar::read_operators', 'operator file '//files(c)//' does not exist')
+         nb_ao = mol%nbasis
+         if (allocated(ao)) deallocate (ao)
+         call read_two_index(files(c), ao, nb_ao)
+         ma = matmul(coeff, matmul(ao, transpose(coeff)))
+         if (cfg%uhf) then
+            mb = matmul(cb, matmul(ao, transpose(cb)))
+         else
+            mb = ma
+         end if
+         do y = 1, 2*n
+            do x = 1, 2*n
+               if (spin(x) /= spin(y)) then
+                  xso(x, y, c) = 0.0_dp
+               else if (spin(x) == 0) then
+                  xso(x, y, c) = 0.5_dp*(ma(orb(x), orb(y)) + ma(orb(y), orb(x)))
+               else
+                  xso(x, y, c) = 0.5_dp*(mb(orb(x), orb(y)) + mb(orb(y), orb(x)))
+               end if
+            end do
+         end do
+      end do
+      if (.not. lambda_live) call lambda_solve()
+      ! the signed list: +omega and -omega of every frequency, each value once
+      allocate (signed(2*cfg%n_polar_omega)); ns = 0
+      do f = 1, cfg%n_polar_omega
+         do c = 1, -1, -2
+            if (.not. any(signed(:ns) == c*cfg%polar_omega(f))) then
+               ns = ns + 1; signed(ns) = c*cfg%polar_omega(f) + 0.0_dp
+            end if
+         end do
+      end do
+      nsys = 3*ns
+      o8 = int(nalpha + nbeta, c_int64_t); v8 = int(2*n - nalpha - nbeta, c_int64_t)
+      nunique = o8*v8 + (o8*(o8 - 1)/2)*(v8*(v8 - 1)/2)
+      ms = min(4096, max(2*nsys, int(min(nunique, int(8*nsys, c_int64_t)))))
+      rc = afesp_ccsd_so_response_init(ctx, 3_c_int, xso, int(ns, c_int), signed, int(ms, c_int))
+      if (rc /= 0) call fail('polar::init_response', afesp_error_text(ctx))
+      allocate (res(nsys), rf(3, 3, cfg%n_polar_omega, 1))
+      ok = .false.
+      do it = 1, 100
+         rc = afesp_ccsd_so_response_iterate(ctx, polar_tol, res, nsig, pconv)
+         if (rc /= 0) call fail('polar::iterate', afesp_error_text(ctx))
+         if (pconv /= 0) then
+            ok = .true.
+            exit
+         end if
+      end do
+      if (.not. ok) call fail('polar::do_response', 'the response equations did not converge!')
+      rc = afesp_ccsd_so_response_function(ctx, int(cfg%n_polar_omega, c_int), cfg%polar_omega, rf)
+      if (rc /= 0) call fail('polar::response_function', afesp_error_text(ctx))
+      do f = 1, cfg%n_polar_omega
+         alpha = -transpose(rf(:, :, f, 1))   ! (the library's rows are the first operator: out[(f nop + a) nop + b])
+         sym = 0.5_dp*(alpha + transpose(alpha))
+         mean = (sym(1, 1) + sym(2, 2) + sym(3, 3))/3.0_dp
+         aniso = sqrt(0.5_dp*((sym(1, 1) - sym(2, 2))**2 + (sym(2, 2) - sym(3, 3))**2 + (sym(3, 3) - sym(1, 1))**2) &
+                      + 3.0_dp*(sym(1, 2)**2 + sym(2, 3)**2 + sym(3, 1)**2))
+         write (out, '(2X, A, F14.8, A)') 'omega = ', cfg%polar_omega(f), ' Eh'
+         do c = 1, 3
+            write (out, '(4X, A1, 2X, 3F18.10)') 'xyz'(c:c), alpha(c, :)
+         end do
+         write (out, '(4X, A, F18.10, 3X, A, F18.10)') 'mean ', mean, 'anisotropy ', aniso
+      end do
+      write (out, '(2X, A, I0, 3X, A, ES11.3)') 'response sigma builds: ', nsig, 'largest residual: ', maxval(res)
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the EOM-CCSD polarisability:', seconds() - tp, 's'
    end subroutine
    !> sum over p, r beta and q, s alpha of (x_pr y_qs - x_ps y_qr) S_ps S_rq, S the non-zero (beta, alpha) block of a
    function flip_pair(xm, ym, a) result(val)

@@ -378,6 +378,60 @@ int afesp_ccsd_so_eom_ref_coupling(afesp_ctx* ctx, int nvec, const double* r1, c
 int afesp_ccsd_so_eom_density(afesp_ctx* ctx, double l0, const double* l1, const double* l2, double r0, const double* r1, const double* r2,
                               double* d, int64_t capacity);
 
+/* EOM-CCSD linear response: static and dynamic polarisabilities (afesp_version 4).  X is a real symmetric one-body
+ * operator over the nocc + nvirt spin orbitals in the state's order, (nocc+nvirt)^2 column-major; X_N its normal-ordered part and
+ * X-bar = exp(-T) X_N exp(T).  Vectors are laid out as t1 / t2 with the metric <x, y> = sum x1 y1 + 1/4 sum x2 y2, as above.
+ *   xi^X_mu            = <mu| X-bar |0> = residual(f + X) - residual(f) at fixed t (the residual is linear in f):
+ *                          X~_kj = X_kj + sum_c X_kc t_jc,   X~_bc = X_bc - sum_k t_kb X_kc
+ *                          xi_ia = X_ai + sum_b X_ab t_ib - sum_j t_ja X_ji + sum_jb X_jb (t_ijab - t_ib t_ja)
+ *                          xi_ijab = P(ab) sum_c X~_bc t_ijac - P(ij) sum_k X~_kj t_ikab
+ *   R^X(omega)         : (A - omega) R^X(omega) = -xi^X with A the matrix of afesp_ccsd_so_eom_sigma
+ *   <<X;Y>>_omega      = Phi[X, R^Y(omega)] + Phi[Y, R^X(-omega)]
+ *   Phi[X, R]          = <0| (1 + Lambda) (X-bar - <X-bar>) R |0> = Tr(X gamma(1, lambda; 0, R)) - Tr(X D) <lambda, R>
+ *                        with gamma afesp_ccsd_so_eom_density (it holds the disconnected E <l, r> piece) and D afesp_ccsd_so_density
+ *   alpha_XY(omega)    = -<<X;Y>>_omega
+ * This is the EOM-CC response function (Stanton and Bartlett 1993), not the LR-CC one: the term quadratic in the perturbed amplitudes is
+ * absent by definition, <<X;Y>>_omega = <<Y;X>>_-omega holds but alpha_XY(omega) != alpha_YX(omega) in general off omega = 0; for two
+ * electrons it is exact.  Real frequencies only.
+ *   afesp_ccsd_so_response_xi         = xi1 [nop * o*v], xi2 [nop * o*o*v*v] of nop operators x [nop * (o+v)^2] at the current t1 / t2, one
+ *                                       after the other (host in / out; needs neither a Lambda nor a response state).  An operator's
+ *                                       vector has the same bits whatever else is in the batch; xi2 is antisymmetric to the bit.
+ *   afesp_ccsd_so_response_init       = the response state: the operators, the nfreq_signed signed frequencies omega to solve for each
+ *                                       (a polarisability at omega needs +omega and -omega in the list; 0 once), and a basis of at most
+ *                                       max_space vectors SHARED by all nop * nfreq_signed systems (at most 64 systems,
+ *                                       2 nop nfreq_signed <= max_space <= 4096; status 1 otherwise, or if it does not fit).  Owned by
+ *                                       the Lambda state beside the EOM states and released with them; it has a basis of its own and
+ *                                       writes nothing of t1 / t2, lambda, the epochs, the H-bar elements, a (T) plan or an EOM Davidson state
+ *                                       (_function rebuilds G_vv / G_oo of the current lambda, as afesp_ccsd_so_density does).
+ *   afesp_ccsd_so_response_iterate    = one step: the pending vectors (at first the preconditioned right-hand sides xi / (omega + D))
+ *                                       are orthonormalised against the basis, ONE sigma build each serves every system, the projected
+ *                                       matrix G and right-hand sides are extended, (G - omega_j) y_j = -B^T xi_j is solved on the host
+ *                                       by LU with partial pivoting, then x_j = B y_j, rho_j = xi_j + (A - omega_j) x_j and the
+ *                                       corrections rho_j / (omega_j + D) / |rho_j| of the systems with |rho_j| >= tol; a full space collapses onto
+ *                                       the current x_j.  resnorm: nop * nfreq_signed entries, system iop + nop * ifreq (NULL: not
+ *                                       wanted); *nsigma = sigma builds since _init; *converged = every system has |rho_j| < tol.
+ *   afesp_ccsd_so_response_get_vector = R^X_iop(omega[ifreq]) of the last step.
+ *   afesp_ccsd_so_response_function   = out[(f * nop + a) * nop + b] = <<X_a;X_b>>_omega[f] for nfreq frequencies, from the resident
+ *                                       solutions at +omega[f] and -omega[f].
+ *   afesp_lu_solve                    = TEST ENTRY, not part of the supported interface and free to disappear: the host LU solve of the
+ *                                       projected systems (csrc/small_eig.h; no context, no GPU) for the CPU tests: a x = b in place,
+ *                                       a [n*n] and b [n*nrhs] column-major; 0, 1 (bad argument) or 2 (a pivot not above `floor`).
+ * Statuses: 1 no spin-orbital state, a NULL or bad argument, a non-symmetric operator (beyond 1e-12 of its largest element), nop < 1, a
+ * frequency asked of _function that is not in the state's list at both signs, or a recording context; AFESP_LAMBDA_STALE (21) without a
+ * live Lambda state or response state, or after anything wrote t1 / t2 or l1 / l2 (20 is afesp_ccsd_so_lambda_init's refusal);
+ * AFESP_RESPONSE_POLE from _iterate: a pivot of a projected system is below 1e-10 max(|G|, |omega|) -- the frequency is at a root of the
+ * projected EOM matrix, an excitation energy, where no response is defined; by then the step has extended the basis and counted its sigma builds and no pending
+ * vector is left, so a repeated _iterate only solves the same projected systems and returns 26 again (start over with _init);
+ * AFESP_RESPONSE_NOT_CONVERGED from _function: a solution it needs has not reached the tol of the last _iterate (or no step was made). */
+#define AFESP_RESPONSE_POLE 26
+#define AFESP_RESPONSE_NOT_CONVERGED 27
+int afesp_ccsd_so_response_xi(afesp_ctx* ctx, int nop, const double* x, double* xi1, double* xi2);
+int afesp_ccsd_so_response_init(afesp_ctx* ctx, int nop, const double* x, int nfreq_signed, const double* omega, int max_space);
+int afesp_ccsd_so_response_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* nsigma, int* converged);
+int afesp_ccsd_so_response_get_vector(afesp_ctx* ctx, int iop, int ifreq, double* r1, double* r2);
+int afesp_ccsd_so_response_function(afesp_ctx* ctx, int nfreq, const double* omega, double* out /* [nfreq*nop*nop] */);
+int afesp_lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor);
+
 /* EOM-IP-CCSD and EOM-EA-CCSD on the same state: ionisation potentials omega = E(N-1) - E(N) in the 1h + 2h1p sector,
  * r1(nocc), r2(nocc,nocc,nvirt) antisymmetric in its first two indices, and electron affinities omega = E(N+1) - E(N) in the 1p + 2p1h
  * sector, r1(nvirt), r2(nocc,nvirt,nvirt) antisymmetric in its last two.  <x, y> = sum x1 y1 + 1/2 sum x2 y2; the unique amplitudes are
