@@ -50,6 +50,8 @@ EXPORTS = [
     "afesp_fcidump_scan", "afesp_read_fcidump", "afesp_read_fcidump_uhf",
     "afesp_mo_fock_ro", "afesp_read_fcidump_rohf", "afesp_mo_rotate_uhf", "afesp_ccsd_uso_init_fock",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
+    "afesp_test_davidson_create", "afesp_test_davidson_destroy", "afesp_test_davidson_set_guess", "afesp_test_davidson_iterate",
+    "afesp_test_davidson_linear_start", "afesp_test_davidson_linear_iterate", "afesp_test_davidson_get_vector", "afesp_test_davidson_fetch",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
 
@@ -207,6 +209,15 @@ def load_library():
     L.afesp_first_use_count.argtypes = []
     L.afesp_first_use_count.restype = C.c_uint64
     L.afesp_test_ring_path.argtypes = [C.c_int64, C.c_int64]
+    _ip = C.POINTER(C.c_int)
+    L.afesp_test_davidson_create.argtypes = [C.c_void_p, i64, i64, dbl, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+    L.afesp_test_davidson_destroy.argtypes = [C.c_void_p]
+    L.afesp_test_davidson_set_guess.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_test_davidson_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, _ip, _ip, _ip]
+    L.afesp_test_davidson_linear_start.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_test_davidson_linear_iterate.argtypes = [C.c_void_p, dbl, _dp, _ip, _ip, _ip]
+    L.afesp_test_davidson_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_test_davidson_fetch.argtypes = [C.c_void_p, C.c_char_p, _dp, i64, C.POINTER(i64)]
     _lib = L
     return L
 
@@ -467,6 +478,85 @@ class Engine:
 
     def test_inject(self, what):
         self._chk(self.L.afesp_test_inject(self.h, what))
+
+    # ---- test hook: the block Davidson unit on A = diag(d) + U V^T given as data (include/afesp.h; tests/test_gpu_davidson.py).
+    # Vectors are whole (nvec,) arrays here; the metric's split at n1 is made in these wrappers.
+    davidson_test_shape = (0, 1, 1, 2)                                     # (n1, nvec, nroots, max_space) of the last create
+
+    def davidson_test_create(self, n1, nvec, w2, follow, nroots, max_space, d, U, V, diag):
+        """U, V: (nvec, r) or None (r = 0)"""
+        r = 0 if U is None else np.asarray(U).shape[1]
+        Uf, Vf = (_f(U), _f(V)) if r else (np.zeros(1), np.zeros(1))
+        self._chk(self.L.afesp_test_davidson_create(self.h, n1, nvec, w2, 1 if follow else 0, nroots, max_space, r, _f(d), Uf, Vf, _f(diag)))
+        self.davidson_test_shape = (int(n1), int(nvec), int(nroots), int(max_space))
+
+    def davidson_test_destroy(self):
+        self._chk(self.L.afesp_test_davidson_destroy(self.h))   # (the shape stays: a later call gets the library's own refusal)
+
+    def _davidson_halves(self, x):
+        n1, nvec = self.davidson_test_shape[:2]
+        x = _f(x)
+        if x.size != nvec:
+            raise ValueError("davidson_test: a vector has nvec elements")
+        return (x[:n1].copy() if n1 else np.zeros(1)), (x[n1:].copy() if n1 < nvec else np.zeros(1))
+
+    def davidson_test_set_guess(self, k, x):
+        self._chk(self.L.afesp_test_davidson_set_guess(self.h, k, *self._davidson_halves(x)))
+
+    def davidson_test_iterate(self, tol=1e-8):
+        """One step -> (omega, resnorm, flags, dict(nsigma, ncollapse, nb, npend), converged)"""
+        nroots = self.davidson_test_shape[2]
+        om, rs = np.zeros(nroots), np.zeros(nroots)
+        fl, cnt, cv = (C.c_int * nroots)(), (C.c_int * 4)(), C.c_int()
+        self._chk(self.L.afesp_test_davidson_iterate(self.h, tol, om, rs, fl, cnt, C.byref(cv)))
+        return om, rs, np.array(fl[:], dtype=int), dict(zip(("nsigma", "ncollapse", "nb", "npend"), cnt[:])), bool(cv.value)
+
+    def davidson_test_linear_start(self, rhs, shifts):
+        """rhs: (nvec, nrhs); shifts: nroots of them"""
+        rhs = np.asarray(rhs, dtype=np.float64)
+        self._chk(self.L.afesp_test_davidson_linear_start(self.h, rhs.shape[1], _f(rhs), _f(shifts)))
+
+    def davidson_test_linear_iterate(self, tol=1e-8):
+        """One step -> (resnorm, flags, dict(nsigma, ncollapse, nb, npend), converged)"""
+        nroots = self.davidson_test_shape[2]
+        rs = np.zeros(nroots)
+        fl, cnt, cv = (C.c_int * nroots)(), (C.c_int * 4)(), C.c_int()
+        self._chk(self.L.afesp_test_davidson_linear_iterate(self.h, tol, rs, fl, cnt, C.byref(cv)))
+        return rs, np.array(fl[:], dtype=int), dict(zip(("nsigma", "ncollapse", "nb", "npend"), cnt[:])), bool(cv.value)
+
+    def davidson_test_get_vector(self, k):
+        n1, nvec = self.davidson_test_shape[:2]
+        x1, x2 = np.zeros(max(n1, 1)), np.zeros(max(nvec - n1, 1))
+        self._chk(self.L.afesp_test_davidson_get_vector(self.h, k, x1, x2))
+        return np.concatenate([x1[:n1], x2[:nvec - n1]])
+
+    def davidson_test_fetch(self, what):
+        """What the state holds (include/afesp.h): vectors as the columns of an (nvec, k) array, G (nb, nb), prhs (nb, nrhs), y ->
+        (coefficients (nb, nr), omega (nr,)), counts -> dict, diag / target flat"""
+        n1, nvec, nroots, ms = self.davidson_test_shape
+        cap = {"G": ms * ms, "prhs": ms * nroots, "y": (ms + 1) * nroots, "target": nroots, "counts": 4, "diag": nvec,
+               "B": nvec * ms, "S": nvec * ms}.get(what, nvec * nroots)
+        if what in ("B", "S", "pend"):
+            c = self.davidson_test_fetch("counts")
+            cap = nvec * (c["npend"] if what == "pend" else c["nb"])
+        out, n = np.zeros(max(cap, 1)), i64()
+        self._chk(self.L.afesp_test_davidson_fetch(self.h, what.encode(), out, cap, C.byref(n)))
+        out = out[:n.value]
+        if what == "counts":
+            return dict(zip(("nsigma", "ncollapse", "nb", "npend"), (int(v) for v in out)))
+        if what in ("B", "S", "pend", "x", "sx", "corr"):
+            return out.reshape(nvec, -1, order="F")
+        if what == "G":
+            nb = int(round(np.sqrt(out.size)))
+            return out.reshape(nb, nb, order="F")
+        if what == "prhs":
+            nb = self.davidson_test_fetch("counts")["nb"]
+            return out.reshape(nb, -1, order="F") if nb else out.reshape(0, 0)
+        if what == "y":
+            nb = self.davidson_test_fetch("counts")["nb"]
+            nr = out.size // (nb + 1)
+            return out[:nb * nr].reshape(nb, nr, order="F"), out[nb * nr:]
+        return out
 
     # ---- input / output side: src/integrals.f90:146-161, src/mp2.f90:451-487
     def read_eri_text(self, path, nbasis, want_host_copy=True):

@@ -56,6 +56,7 @@ struct Plan {
 
 struct Comm;
 struct Recorder;   // fused.h
+struct DavidsonTest;   // davidson_test.h
 
 // Device arena owned by the context.  On this runtime a hipMalloc of a GB or more is normally 0.3 ms but now and then takes
 // 0.1-5 s, and a calculation frees and re-allocates tens of GB between its stages (AO->MO temporaries,
@@ -78,6 +79,7 @@ struct Context {
     Comm* comm = nullptr;                 // rank-to-rank sums (comm.h); null = single rank
     int cc_split_mode = -1;               // afesp_ccsd_set_split: 1 split the CCSD iteration over the ranks, 0 replicas, -1 environment (default off)
     int test_throw = 0;                   // test hook (afesp_test_inject): the next laned amplitude update throws
+    DavidsonTest* dav_test = nullptr;     // test hook (afesp_test_davidson_*, davidson_test.h): a Davidson state on a matrix given as data
     int fused_mode = -1;                  // afesp_ccsd_set_fused: 1 launch-fused small-system path on, 0 off, -1 environment (default on)
     // Recording (fused.h): the offset tables of the plans made meanwhile are not uploaded one by one -- their host images wait here
     // (destination, image) and go to the device in as few copies as their destinations are contiguous (plan_alloc hands out

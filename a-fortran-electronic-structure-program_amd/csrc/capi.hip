@@ -16,6 +16,7 @@
 #include "eom_so.h"
 #include "eom_ipea_so.h"
 #include "response_so.h"
+#include "davidson_test.h"
 #include "small_eig.h"
 #include "comm.h"
 #include "tall.h"
@@ -211,6 +212,7 @@ void afesp_ctx_destroy(afesp_ctx* ctx)
     first_use_tls_device() = ctx->cx.device;   // (no guard here: the thread would otherwise keep its previous call's device)
     (void)hipSetDevice(ctx->cx.device);
     if (ctx->cx.startup.joinable()) ctx->cx.startup.join();
+    davidson_test_destroy(ctx->cx);
     ctx->sv.destroy(ctx->cx);
     comm_destroy(ctx->cx.comm);
     ctx->cx.comm = nullptr;
@@ -1291,6 +1293,58 @@ int afesp_arena_stats(afesp_ctx* ctx, double out[4])
 int afesp_test_inject(afesp_ctx* ctx, int what)
 {
     return entry(ctx, [&](Context& cx) { cx.test_throw = what; });
+}
+
+// ---- the test entry to the block Davidson unit (davidson_test.h)
+int afesp_test_davidson_create(afesp_ctx* ctx, int64_t n1, int64_t nvec, double w2, int follow, int nroots, int max_space, int r, const double* d,
+                               const double* U, const double* V, const double* diag)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_create(cx, n1, nvec, w2, follow, nroots, max_space, r, d, U, V, diag); });
+}
+
+int afesp_test_davidson_destroy(afesp_ctx* ctx)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_destroy(cx); });
+}
+
+int afesp_test_davidson_set_guess(afesp_ctx* ctx, int k, const double* x1, const double* x2)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_set_guess(cx, k, x1, x2); });
+}
+
+static void davidson_test_report(Context& cx, const char* who, int conv, double* omega, double* resnorm, int* flags, int counts[4], int* converged)
+{
+    const Davidson& E = davidson_test_need(cx, who).d;
+    davidson_report(E, conv, omega, resnorm, flags, nullptr, converged);
+    if (counts) counts[0] = E.nsigma, counts[1] = E.ncollapse, counts[2] = E.nb, counts[3] = E.npend;
+}
+
+int afesp_test_davidson_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int counts[4], int* converged)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_report(cx, "afesp_test_davidson_iterate", davidson_test_iterate(cx, tol), omega, resnorm, flags, counts, converged); });
+}
+
+int afesp_test_davidson_linear_start(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shifts)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_linear_start(cx, nrhs, rhs, shifts); });
+}
+
+int afesp_test_davidson_linear_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* flags, int counts[4], int* converged)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_report(cx, "afesp_test_davidson_linear_iterate", davidson_test_linear_iterate(cx, tol), nullptr, resnorm, flags, counts, converged); });
+}
+
+int afesp_test_davidson_get_vector(afesp_ctx* ctx, int k, double* x1, double* x2)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_get_vector(cx, k, x1, x2); });
+}
+
+int afesp_test_davidson_fetch(afesp_ctx* ctx, const char* what, double* out, int64_t capacity, int64_t* count)
+{
+    return entry(ctx, [&](Context& cx) {
+        const int64_t n = davidson_test_fetch(cx, what, out, capacity);
+        if (count) *count = n;
+    });
 }
 
 }  // extern "C"

@@ -681,6 +681,27 @@ int afesp_arena_stats(afesp_ctx* ctx, double out[4]);
 /* Test hook: what = 1 makes the next laned (small-system) amplitude update throw once, from a lane other than the main one
  * -- the failure mode of a capture that dies half-way (tests/test_gpu_cc.py). */
 int afesp_test_inject(afesp_ctx* ctx, int what);
+/* Test / diagnostic hook, per context: the block Davidson unit of the EOM and response solvers (csrc/davidson_so.h) on a matrix given as
+ * data, A = diag(d) + U V^T with U, V of nvec x r column-major (r <= 64; a dense m x m matrix is d = 0, U = A, V = 1), in the metric of n1
+ * elements of weight 1 and nvec - n1 of weight w2.  One state per context, beside the EOM and response states and freed with the context
+ * (tests/test_gpu_davidson.py).  create: 1 <= nroots <= nvec, 2 nroots <= max_space <= 4096, status 1 otherwise; `diag` is the
+ * preconditioner diagonal, given apart from d; follow != 0 keeps the roots nearest to the guess step's.  set_guess / iterate /
+ * get_vector are the unit's eigenvalue calls (x1: the first n1 elements, x2: the rest), linear_start / linear_iterate its linear mode for
+ * (A - shifts[j]) x_j = -rhs[j % nrhs], j < nroots, with status 26 at a pole as afesp_ccsd_so_response_iterate has it.  counts =
+ * {sigma builds, collapses, basis vectors, pending vectors}.  fetch copies what the state holds: what = "B", "S" (basis vectors), "pend"
+ * (pending vectors), "x", "sx", "corr" (nroots columns), "diag", "G" (basis x basis, column-major), "prhs" (basis x nrhs), "y" (the
+ * coefficients of the last step, basis x roots, then the values of omega given to the Ritz pass; status 1 when no step has finished on the
+ * present basis, as after a step that ended at a pole), "target", "counts"; *count = doubles
+ * written, status 1 when capacity is smaller. */
+int afesp_test_davidson_create(afesp_ctx* ctx, int64_t n1, int64_t nvec, double w2, int follow, int nroots, int max_space, int r, const double* d,
+                               const double* U, const double* V, const double* diag);
+int afesp_test_davidson_destroy(afesp_ctx* ctx);
+int afesp_test_davidson_set_guess(afesp_ctx* ctx, int k, const double* x1, const double* x2);
+int afesp_test_davidson_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int counts[4], int* converged);
+int afesp_test_davidson_linear_start(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shifts);
+int afesp_test_davidson_linear_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* flags, int counts[4], int* converged);
+int afesp_test_davidson_get_vector(afesp_ctx* ctx, int k, double* x1, double* x2);
+int afesp_test_davidson_fetch(afesp_ctx* ctx, const char* what, double* out, int64_t capacity, int64_t* count);
 /* Test / diagnostic hook, per context: launches so far of {the streamed tall x skinny kernel, the gather kernel through the operator
  * layer's planner, the LDS-DMA GEMM with 128-row tiles, the LDS-DMA GEMM with 96-row tiles where the rows end} -- tests check with it
  * that a product took the kernel meant for its shape (tests/test_gpu_operators.py, tests/test_gpu_cc.py). */
