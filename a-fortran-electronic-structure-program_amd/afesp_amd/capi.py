@@ -41,6 +41,8 @@ EXPORTS = [
     "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
     "afesp_ccsd_so_response_xi", "afesp_ccsd_so_response_init", "afesp_ccsd_so_response_iterate", "afesp_ccsd_so_response_get_vector",
     "afesp_ccsd_so_response_function", "afesp_lu_solve",
+    "afesp_ccsd_so_response_init_complex", "afesp_ccsd_so_response_get_vector_complex", "afesp_ccsd_so_response_function_complex",
+    "afesp_lu_solve_complex",
     "afesp_read_eri_text", "afesp_write_fcidump", "afesp_set_eri", "afesp_build_fock", "afesp_ccsd_t_plain",
     "afesp_synthetic_ao", "afesp_ccsd_pp_ladder_flop", "afesp_ccsd_iteration_flop",
     "afesp_device_count", "afesp_comm_unique_id", "afesp_comm_init", "afesp_comm_destroy", "afesp_allreduce_sum",
@@ -51,7 +53,7 @@ EXPORTS = [
     "afesp_mo_fock_ro", "afesp_read_fcidump_rohf", "afesp_mo_rotate_uhf", "afesp_ccsd_uso_init_fock",
     "afesp_ccsd_t_block_size", "afesp_test_inject", "afesp_ccsd_is_split", "afesp_ccsd_set_split", "afesp_ccsd_set_fused", "afesp_ccsd_iteration_launches", "afesp_debug_stamps", "afesp_launch_counts", "afesp_first_use_count", "afesp_test_ring_path", "afesp_arena_stats",
     "afesp_test_davidson_create", "afesp_test_davidson_destroy", "afesp_test_davidson_set_guess", "afesp_test_davidson_iterate",
-    "afesp_test_davidson_linear_start", "afesp_test_davidson_linear_iterate", "afesp_test_davidson_get_vector", "afesp_test_davidson_fetch",
+    "afesp_test_davidson_linear_start", "afesp_test_davidson_linear_start_complex", "afesp_test_davidson_linear_iterate", "afesp_test_davidson_get_vector", "afesp_test_davidson_fetch",
 ]
 COMM_RCCL, COMM_HOST = 0, 1
 
@@ -160,6 +162,10 @@ def load_library():
     L.afesp_ccsd_so_response_get_vector.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
     L.afesp_ccsd_so_response_function.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     L.afesp_lu_solve.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, dbl]
+    L.afesp_ccsd_so_response_init_complex.argtypes = [C.c_void_p, C.c_int, _dp, C.c_int, _dp, C.c_int]
+    L.afesp_ccsd_so_response_get_vector_complex.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
+    L.afesp_ccsd_so_response_function_complex.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_lu_solve_complex.argtypes = [C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, dbl]
     L.afesp_ccsd_so_eom_ipea_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.afesp_ccsd_so_eom_ipea_sigma.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]
     L.afesp_ccsd_so_eom_ipea_guess.argtypes = [C.c_void_p, C.c_int]
@@ -215,6 +221,7 @@ def load_library():
     L.afesp_test_davidson_set_guess.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     L.afesp_test_davidson_iterate.argtypes = [C.c_void_p, dbl, _dp, _dp, _ip, _ip, _ip]
     L.afesp_test_davidson_linear_start.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
+    L.afesp_test_davidson_linear_start_complex.argtypes = [C.c_void_p, C.c_int, _dp, _dp, _dp]
     L.afesp_test_davidson_linear_iterate.argtypes = [C.c_void_p, dbl, _dp, _ip, _ip, _ip]
     L.afesp_test_davidson_get_vector.argtypes = [C.c_void_p, C.c_int, _dp, _dp]
     L.afesp_test_davidson_fetch.argtypes = [C.c_void_p, C.c_char_p, _dp, i64, C.POINTER(i64)]
@@ -482,6 +489,7 @@ class Engine:
     # ---- test hook: the block Davidson unit on A = diag(d) + U V^T given as data (include/afesp.h; tests/test_gpu_davidson.py).
     # Vectors are whole (nvec,) arrays here; the metric's split at n1 is made in these wrappers.
     davidson_test_shape = (0, 1, 1, 2)                                     # (n1, nvec, nroots, max_space) of the last create
+    davidson_test_complex = False                                          # the last start was davidson_test_linear_start_complex
 
     def davidson_test_create(self, n1, nvec, w2, follow, nroots, max_space, d, U, V, diag):
         """U, V: (nvec, r) or None (r = 0)"""
@@ -489,6 +497,7 @@ class Engine:
         Uf, Vf = (_f(U), _f(V)) if r else (np.zeros(1), np.zeros(1))
         self._chk(self.L.afesp_test_davidson_create(self.h, n1, nvec, w2, 1 if follow else 0, nroots, max_space, r, _f(d), Uf, Vf, _f(diag)))
         self.davidson_test_shape = (int(n1), int(nvec), int(nroots), int(max_space))
+        self.davidson_test_complex = False
 
     def davidson_test_destroy(self):
         self._chk(self.L.afesp_test_davidson_destroy(self.h))   # (the shape stays: a later call gets the library's own refusal)
@@ -502,6 +511,7 @@ class Engine:
 
     def davidson_test_set_guess(self, k, x):
         self._chk(self.L.afesp_test_davidson_set_guess(self.h, k, *self._davidson_halves(x)))
+        self.davidson_test_complex = False
 
     def davidson_test_iterate(self, tol=1e-8):
         """One step -> (omega, resnorm, flags, dict(nsigma, ncollapse, nb, npend), converged)"""
@@ -515,6 +525,16 @@ class Engine:
         """rhs: (nvec, nrhs); shifts: nroots of them"""
         rhs = np.asarray(rhs, dtype=np.float64)
         self._chk(self.L.afesp_test_davidson_linear_start(self.h, rhs.shape[1], _f(rhs), _f(shifts)))
+        self.davidson_test_complex = False
+
+    def davidson_test_linear_start_complex(self, rhs, shifts):
+        """rhs: (nvec, nrhs); shifts: nroots complex numbers.  davidson_test_linear_iterate then makes the complex steps, and
+        davidson_test_fetch gives x, sx, corr as complex (nvec, nroots) arrays and y as (complex coefficients (nb, nroots), shifts)"""
+        rhs = np.asarray(rhs, dtype=np.float64)
+        z = np.asarray(shifts, dtype=np.complex128)
+        self._chk(self.L.afesp_test_davidson_linear_start_complex(self.h, rhs.shape[1], _f(rhs), np.ascontiguousarray(z.real),
+                                                                  np.ascontiguousarray(z.imag)))
+        self.davidson_test_complex = True
 
     def davidson_test_linear_iterate(self, tol=1e-8):
         """One step -> (resnorm, flags, dict(nsigma, ncollapse, nb, npend), converged)"""
@@ -534,8 +554,10 @@ class Engine:
         """What the state holds (include/afesp.h): vectors as the columns of an (nvec, k) array, G (nb, nb), prhs (nb, nrhs), y ->
         (coefficients (nb, nr), omega (nr,)), counts -> dict, diag / target flat"""
         n1, nvec, nroots, ms = self.davidson_test_shape
-        cap = {"G": ms * ms, "prhs": ms * nroots, "y": (ms + 1) * nroots, "target": nroots, "counts": 4, "diag": nvec,
-               "B": nvec * ms, "S": nvec * ms}.get(what, nvec * nroots)
+        cz = self.davidson_test_complex
+        ncol = 2 if cz else 1
+        cap = {"G": ms * ms, "prhs": ms * nroots, "y": (ms + 1) * nroots * ncol, "target": nroots, "counts": 4, "diag": nvec,
+               "B": nvec * ms, "S": nvec * ms}.get(what, nvec * nroots * ncol)
         if what in ("B", "S", "pend"):
             c = self.davidson_test_fetch("counts")
             cap = nvec * (c["npend"] if what == "pend" else c["nb"])
@@ -544,6 +566,9 @@ class Engine:
         out = out[:n.value]
         if what == "counts":
             return dict(zip(("nsigma", "ncollapse", "nb", "npend"), (int(v) for v in out)))
+        if cz and what in ("x", "sx", "corr"):
+            cols = out.reshape(nvec, -1, order="F")
+            return cols[:, 0::2] + 1j * cols[:, 1::2]
         if what in ("B", "S", "pend", "x", "sx", "corr"):
             return out.reshape(nvec, -1, order="F")
         if what == "G":
@@ -554,6 +579,10 @@ class Engine:
             return out.reshape(nb, -1, order="F") if nb else out.reshape(0, 0)
         if what == "y":
             nb = self.davidson_test_fetch("counts")["nb"]
+            if cz:
+                nr = out.size // (2 * (nb + 1))
+                y = out[:nb * nr].reshape(nb, nr, order="F") + 1j * out[nb * nr:2 * nb * nr].reshape(nb, nr, order="F")
+                return y, out[2 * nb * nr:2 * nb * nr + nr] + 1j * out[2 * nb * nr + nr:]
             nr = out.size // (nb + 1)
             return out[:nb * nr].reshape(nb, nr, order="F"), out[nb * nr:]
         return out
@@ -1195,6 +1224,32 @@ class Engine:
         out = np.zeros(max(om.size * nop * nop, 1))
         self._chk(self.L.afesp_ccsd_so_response_function(self.h, om.size, om if om.size else np.zeros(1), out))
         return out[:om.size * nop * nop].reshape(om.size, nop, nop)
+
+    # ---- the same at complex frequencies z = omega + i gamma; so_response_iterate steps either kind of state
+    def so_response_init_complex(self, x, z_signed, max_space):
+        """The response state of the operators x (k, o+v, o+v) for the complex frequencies z_signed, on one real basis of max_space vectors"""
+        k, flat, _ = self._so_operators(x, "so_response_init_complex")
+        z = np.atleast_1d(np.asarray(z_signed, dtype=np.complex128))
+        pairs = np.ascontiguousarray(np.stack([z.real, z.imag], axis=1).ravel()) if z.size else np.zeros(2)
+        self._chk(self.L.afesp_ccsd_so_response_init_complex(self.h, k, flat if k else np.zeros(1), z.size, pairs, max_space))
+        self.response_shape = (k, z.size)
+
+    def so_response_vector_complex(self, iop, ifreq):
+        """R^X_iop(z_signed[ifreq]) of the last step -> (r1, r2), complex"""
+        o, v = self.so_o, self.so_v
+        a1, a2, b1, b2 = np.zeros(o * v), np.zeros(o * o * v * v), np.zeros(o * v), np.zeros(o * o * v * v)
+        self._chk(self.L.afesp_ccsd_so_response_get_vector_complex(self.h, iop, ifreq, a1, a2, b1, b2))
+        return (a1 + 1j * b1).reshape((o, v), order="F"), (a2 + 1j * b2).reshape((o, o, v, v), order="F")
+
+    def so_response_function_complex(self, zs):
+        """<<X_a;X_b>>_z for every z of zs whose solutions at z and -z (or -conj z) are converged in the state -> complex (nfreq, nop, nop)"""
+        nop = self.response_shape[0]
+        z = np.atleast_1d(np.asarray(zs, dtype=np.complex128))
+        pairs = np.ascontiguousarray(np.stack([z.real, z.imag], axis=1).ravel()) if z.size else np.zeros(2)
+        out = np.zeros(max(2 * z.size * nop * nop, 2))
+        self._chk(self.L.afesp_ccsd_so_response_function_complex(self.h, z.size, pairs, out))
+        out = out[:2 * z.size * nop * nop]
+        return (out[0::2] + 1j * out[1::2]).reshape(z.size, nop, nop)
 
     # ---- EOM-IP-CCSD / EOM-EA-CCSD of the same state (include/afesp.h; afesp_amd.eom drives them).  sector: EOM_IP (1h + 2h1p:
     # r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)); the rules and statuses are those of the EE calls above

@@ -50,6 +50,8 @@ class SystemIn:
     eom_nroots: int = 0             # after a converged spin-orbital CCSD: this many EOM-EE-CCSD excitation energies (afesp_amd/eom.py); 0 = off
     cc_polar: bool = False          # ... the EOM-CCSD polarisability alpha(omega) from dipx.dat / dipy.dat / dipz.dat (afesp_amd/response.py)
     polar_omega: list = dataclasses.field(default_factory=lambda: [0.0])   # ... at these real frequencies / Eh (up to 8)
+    polar_gamma: float = 0.0        # ... > 0: every polar_omega is solved at omega + i gamma (damped response: Re / Im alpha-bar and sigma(omega))
+    polar_c6_npts: int = 0          # ... > 0: alpha-bar(iu) on this many Casimir-Polder grid points and the homo-dimer C6 (response.casimir_polder_grid)
     eom_left: bool = False          # ... and their left eigenvectors, from the right ones as guess (eom.so_eom_left_solve); needs eom_nroots > 0
     eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
@@ -201,6 +203,11 @@ def read_els_in(path: str) -> SystemIn:
                          "run does not have!")
     if not 1 <= len(sysin.polar_omega) <= 8:
         raise ValueError("polar_omega takes at most 8 frequencies!")
+    if isinstance(sysin.polar_gamma, bool) or not isinstance(sysin.polar_gamma, (int, float)) or not sysin.polar_gamma >= 0.0:
+        raise ValueError("polar_gamma is a damping in Eh, zero (real frequencies) or positive!")
+    sysin.polar_gamma = float(sysin.polar_gamma)
+    if not isinstance(sysin.polar_c6_npts, int) or isinstance(sysin.polar_c6_npts, bool) or not 0 <= sysin.polar_c6_npts <= 21:
+        raise ValueError("polar_c6_npts is the number of Casimir-Polder grid points, 0 (off) to 21 (three operators each, 64 systems in one response state)!")
     for key in ("eom_ip_nroots", "eom_ea_nroots"):
         val = getattr(sysin, key)
         if not isinstance(val, int) or isinstance(val, bool) or val < 0:

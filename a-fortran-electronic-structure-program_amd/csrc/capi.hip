@@ -125,7 +125,7 @@ void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
 
 extern "C" {
 
-int afesp_version(void) { return 4; }
+int afesp_version(void) { return 5; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -845,6 +845,34 @@ int afesp_ccsd_so_response_function(afesp_ctx* ctx, int nfreq, const double* ome
 
 int afesp_lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor) { return lu_solve(n, a, lda, nrhs, b, ldb, floor); }
 
+// ---- the same at complex frequencies (response_so.h)
+int afesp_ccsd_so_response_init_complex(afesp_ctx* ctx, int nop, const double* x, int nfreq_signed, const double* z, int max_space)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_init_complex(cx, ctx->sv.need_so("afesp_ccsd_so_response_init_complex: no spin-orbital CCSD state").so, nop, x, nfreq_signed, z, max_space);
+    });
+}
+
+int afesp_ccsd_so_response_get_vector_complex(afesp_ctx* ctx, int iop, int ifreq, double* r1_re, double* r2_re, double* r1_im, double* r2_im)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_get_vector_complex(cx, ctx->sv.need_so("afesp_ccsd_so_response_get_vector_complex: no spin-orbital CCSD state").so, iop, ifreq, r1_re,
+                                       r2_re, r1_im, r2_im);
+    });
+}
+
+int afesp_ccsd_so_response_function_complex(afesp_ctx* ctx, int nfreq, const double* z, double* out)
+{
+    return entry(ctx, [&](Context& cx) {
+        so_response_function_complex(cx, ctx->sv.need_so("afesp_ccsd_so_response_function_complex: no spin-orbital CCSD state").so, nfreq, z, out);
+    });
+}
+
+int afesp_lu_solve_complex(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor)
+{
+    return lu_solve_complex(n, a, lda, nrhs, b, ldb, floor);
+}
+
 // ---- EOM-IP-CCSD and EOM-EA-CCSD (eom_ipea_so.h)
 static SOState& ipea_state(afesp_ctx* ctx, int sector, const char* who)
 {
@@ -1327,6 +1355,11 @@ int afesp_test_davidson_iterate(afesp_ctx* ctx, double tol, double* omega, doubl
 int afesp_test_davidson_linear_start(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shifts)
 {
     return entry(ctx, [&](Context& cx) { davidson_test_linear_start(cx, nrhs, rhs, shifts); });
+}
+
+int afesp_test_davidson_linear_start_complex(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shift_re, const double* shift_im)
+{
+    return entry(ctx, [&](Context& cx) { davidson_test_linear_start_complex(cx, nrhs, rhs, shift_re, shift_im); });
 }
 
 int afesp_test_davidson_linear_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* flags, int counts[4], int* converged)

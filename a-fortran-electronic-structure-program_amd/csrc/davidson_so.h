@@ -6,6 +6,11 @@
 // Linear mode (davidson_linear_*; its user is response_so.h): the same basis, sigma storage, orthonormalisation, Gram panel
 // collapse and fused pass solve (A - shift_j) x_j = -rhs_j for `nroots` systems at once on ONE basis -- every pending correction costs one sigma build
 // that serves every system.  The eigenvalue entry points above are untouched by it.
+//
+// Complex linear mode (davidson_linear_start_complex): the shifts are complex, z_j = omega_j + i gamma_j, the matrix and the
+// right-hand sides stay real.  The basis, sigma storage, G and prhs are the real ones; a solution x_j = P_j + i Q_j takes two columns
+// (2 j: real part, 2 j + 1: imaginary part) of x, sx, corr and pend, the projected solve is a complex LU on the host, and one fused pass of
+// its own (davidson_cfused_kernel) forms both columns of every system from one sweep over B and S.
 #pragma once
 #include "afesp_internal.h"
 
@@ -47,6 +52,10 @@ struct Davidson {
     const double* rhs = nullptr;
     int nrhs = 0;
     std::vector<double> shift, prhs;
+    // complex linear mode: `wide` -- pend, x, sx, corr have 2 nroots columns and coef room for complex coefficients (davidson_alloc);
+    // `cplx` -- the last start was davidson_linear_start_complex; shift_im[j] = gamma_j beside shift[j] = omega_j
+    bool wide = false, cplx = false;
+    std::vector<double> shift_im;
 };
 
 constexpr int DAVIDSON_ERR_POLE = 26;   // davidson_linear_iterate: a shift is at a root of the projected matrix
@@ -55,9 +64,12 @@ using DavidsonSigma = std::function<void(const double* r, double* sigma)>;   // 
 
 // device bytes of a state
 double davidson_bytes(double nvec, int nroots, int max_space);
+double davidson_bytes_complex(double nvec, int nsys, int max_space);   // the same of a state allocated with wide = true
 // fill_diag writes `diag` once (launches on cx.stream).  A failed allocation leaves what was allocated to the caller's davidson_free.
+// wide: two columns per system in pend, x, sx and corr -- what davidson_linear_start_complex needs; every other entry point runs on a
+// wide state as on a plain one.
 void davidson_alloc(Context& cx, Davidson& D, int64_t n1, int64_t nvec, double w2, bool follow, int nroots, int max_space,
-                    const std::function<void(double* diag)>& fill_diag);
+                    const std::function<void(double* diag)>& fill_diag, bool wide = false);
 void davidson_free(Context& cx, Davidson& D);
 void davidson_restart(Davidson& D);   // no basis, no pending vectors, no targets
 // Messages carry the caller's names: prefix + "iterate", "guess", "set_guess", "get_vector".
@@ -77,7 +89,19 @@ void davidson_linear_start(Context& cx, Davidson& D, const double* rhs, int nrhs
 // D.x holds the solutions, D.resnorm their residual norms, D.flags bit 0 |rho_j| < tol.  -> 1 when every system has converged.
 // Throws DAVIDSON_ERR_POLE when a pivot of a projected system is below 1e-10 max(|G|_max, |shift_j|): the basis has been extended and
 // the sigma builds counted by then, no pending vector is left, and a repeated call only solves the same systems and throws again.
+// On a state started by davidson_linear_start_complex it makes the complex step below instead (D.cplx).
 int davidson_linear_iterate(Context& cx, Davidson& D, const std::string& prefix, double tol, const DavidsonSigma& sigma);
+// ---- complex linear mode: (A - z_j) x_j = -rhs_j with z_j = shift_re[j] + i shift_im[j], x_j = P_j + i Q_j, on a wide state with
+// 4 nroots <= max_space and nroots <= 64.  Start: no basis; the pending vectors are Re and Im of rhs_j / (z_j - diag), in that order per
+// system (where |z_j - diag| < 1e-4 the denominator is the real +-1e-4 with the sign of its real part, + for zero) -- a system with
+// gamma_j = 0 gives an exactly zero imaginary vector, which the orthonormalisation drops.
+// Step (davidson_linear_iterate): collapse onto Re x_j, Im x_j of every system in column order if the pending vectors do not fit; the
+// pending vectors as in the real mode; (G - z_j) y_j = -B^T rhs_j by complex LU with partial pivoting on |pivot| on the host
+// (DAVIDSON_ERR_POLE for |pivot| <= 1e-10 max(|G|_max, |z_j|)); one fused pass: P_j = B Re y_j, Q_j = B Im y_j, S P_j, S Q_j,
+//   rho_re = rhs_j + S P_j - omega_j P_j + gamma_j Q_j,   rho_im = S Q_j - omega_j Q_j - gamma_j P_j,
+// |rho_j|^2 = |rho_re|^2 + |rho_im|^2 in the unit's metric, and the corrections rho_j / (z_j - diag) (complex division, guarded as above);
+// Re and Im of corr_j / |rho_j| of the systems with |rho_j| >= tol are the next pending vectors.  D.omega holds Re z_j.
+void davidson_linear_start_complex(Context& cx, Davidson& D, const double* rhs, int nrhs, const double* shift_re, const double* shift_im);
 // the fixed-order reduction of this unit for others: blocks of a partial-sum grid over nvec elements, and out[b] = the ordered sum of
 // partial[b nblk .. (b + 1) nblk)
 int davidson_reduce_blocks(int64_t nvec);

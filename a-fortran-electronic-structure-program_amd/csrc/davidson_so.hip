@@ -144,6 +144,93 @@ __global__ void davidson_precondition_kernel(double* pend, const double* rhs, in
     }
 }
 
+// the guarded denominator z - diag of the complex linear mode: inside DAV_CLAMP of zero it is the real +-DAV_CLAMP, with the sign of its
+// real part (+ for zero)
+__device__ inline void davidson_cden(double om, double ga, double D, double& dr, double& di)
+{
+    dr = om - D;
+    di = ga;
+    if (dr * dr + di * di < DAV_CLAMP * DAV_CLAMP) {
+        dr = dr < 0.0 ? -DAV_CLAMP : DAV_CLAMP;
+        di = 0.0;
+    }
+}
+
+// The fused pass of the complex linear mode for the systems k0 .. k0 + nr (nr <= DAV_CCHUNK): every stored b_p and sigma_p is read once
+// and gives, with y_k = yre_k + i yim_k, z_k = om_k + i ga_k,
+//   P_k = sum_p yre(p,k) b_p,  Q_k = sum_p yim(p,k) b_p,  SP_k, SQ_k the same of sigma_p      -> columns 2 k and 2 k + 1 of X and SX
+//   rho_re = rhs_(k % nrhs) + SP_k - om_k P_k + ga_k Q_k,   rho_im = SQ_k - om_k Q_k - ga_k P_k
+//   corr_k = rho_k / (z_k - diag)                                                              -> columns 2 k and 2 k + 1 of corr
+// and the block partials of <rho_re, rho_re> + <rho_im, rho_im> at partial[(k0 + k) nblk + blk].  yre, yim: nb x nsys column-major.
+constexpr int DAV_CCHUNK = DAV_RCHUNK;   // complex systems of one launch: B and S are read as often per system as the real pass reads them
+__global__ void davidson_cfused_kernel(double* X, double* SX, double* corr, double* partial, const double* B, const double* S, int64_t stride,
+                                       int nb, const double* yre, const double* yim, const double* om, const double* ga, const double* diag,
+                                       int64_t n1, double w2, int64_t nvec, int k0, int nr, const double* rhs, int nrhs)
+{
+    __shared__ double sm[DAV_CCHUNK * 4];
+    double nrm[DAV_CCHUNK];
+#pragma unroll
+    for (int k = 0; k < DAV_CCHUNK; ++k) nrm[k] = 0.0;
+    GRID_STRIDE(e, nvec)
+    {
+        double pr[DAV_CCHUNK], qi[DAV_CCHUNK], spr[DAV_CCHUNK], sqi[DAV_CCHUNK];
+#pragma unroll
+        for (int k = 0; k < DAV_CCHUNK; ++k) pr[k] = qi[k] = spr[k] = sqi[k] = 0.0;
+        for (int p = 0; p < nb; ++p) {
+            const double b = B[stride * p + e], s = S[stride * p + e];
+#pragma unroll
+            for (int k = 0; k < DAV_CCHUNK; ++k)
+                if (k < nr) {
+                    const double cr = yre[p + (int64_t)nb * (k0 + k)], ci = yim[p + (int64_t)nb * (k0 + k)];
+                    pr[k] = __fma_rn(cr, b, pr[k]);
+                    qi[k] = __fma_rn(ci, b, qi[k]);
+                    spr[k] = __fma_rn(cr, s, spr[k]);
+                    sqi[k] = __fma_rn(ci, s, sqi[k]);
+                }
+        }
+        const double D = diag[e], w = e < n1 ? 1.0 : w2;
+#pragma unroll
+        for (int k = 0; k < DAV_CCHUNK; ++k)
+            if (k < nr) {
+                const double o = om[k0 + k], g = ga[k0 + k];
+                double rre = __fma_rn(g, qi[k], __fma_rn(-o, pr[k], spr[k]));
+                rre = __dadd_rn(rhs[stride * ((k0 + k) % nrhs) + e], rre);
+                const double rim = __fma_rn(-g, pr[k], __fma_rn(-o, qi[k], sqi[k]));
+                double dr, di;
+                davidson_cden(o, g, D, dr, di);
+                const double m2 = dr * dr + di * di;
+                const int64_t c0 = stride * 2 * (k0 + k) + e, c1 = c0 + stride;
+                X[c0] = pr[k];
+                X[c1] = qi[k];
+                SX[c0] = spr[k];
+                SX[c1] = sqi[k];
+                corr[c0] = (rre * dr + rim * di) / m2;
+                corr[c1] = (rim * dr - rre * di) / m2;
+                nrm[k] += w * (rre * rre + rim * rim);
+            }
+    }
+    block_sum<DAV_CCHUNK>(nrm, sm);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < nr; ++k) partial[(int64_t)(k0 + k) * gridDim.x + blockIdx.x] = nrm[k];
+}
+
+// pend_(2 j), pend_(2 j + 1) = Re, Im of rhs_(j % nrhs) / (z_j - diag), j < nsys: the first pending vectors of the complex linear mode
+__global__ void davidson_cprecondition_kernel(double* pend, const double* rhs, int nrhs, const double* om, const double* ga, const double* diag,
+                                              int64_t stride, int nsys, int64_t nvec)
+{
+    GRID_STRIDE(e, nvec)
+    {
+        const double D = diag[e];
+        for (int j = 0; j < nsys; ++j) {
+            double dr, di;
+            davidson_cden(om[j], ga[j], D, dr, di);
+            const double m2 = dr * dr + di * di, r = rhs[stride * (j % nrhs) + e];
+            pend[stride * 2 * j + e] = r * dr / m2;
+            pend[stride * (2 * j + 1) + e] = -(r * di) / m2;
+        }
+    }
+}
+
 void preload_once()
 {
     static const bool loaded = [] {
@@ -153,6 +240,8 @@ void preload_once()
         first_use_touch(reinterpret_cast<const void*>(davidson_scale_kernel));
         first_use_touch(reinterpret_cast<const void*>(davidson_ritz_kernel));
         first_use_touch(reinterpret_cast<const void*>(davidson_precondition_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_cfused_kernel));
+        first_use_touch(reinterpret_cast<const void*>(davidson_cprecondition_kernel));
         (void)hipGetLastError();
         return true;
     }();
@@ -235,25 +324,34 @@ double davidson_bytes(double nvec, int nroots, int max_space)
                   (double)nroots * (DAV_MAXBLK + 2.0) + (double)max_space * nroots);
 }
 
+double davidson_bytes_complex(double nvec, int nsys, int max_space)
+{
+    // four more columns per system, and the imaginary parts of the coefficients and shifts
+    return davidson_bytes(nvec, nsys, max_space) + 8.0 * (4.0 * nsys * nvec + (double)max_space * nsys + nsys);
+}
+
 void davidson_alloc(Context& cx, Davidson& E, int64_t n1, int64_t nvec, double w2, bool follow, int nroots, int max_space,
-                    const std::function<void(double* diag)>& fill_diag)
+                    const std::function<void(double* diag)>& fill_diag, bool wide)
 {
     preload_once();
+    const int64_t ncol = wide ? 2 * nroots : nroots;
     E.nroots = nroots;
     E.max_space = max_space;
     E.n1 = n1;
     E.nvec = nvec;
     E.w2 = w2;
     E.follow = follow;
+    E.wide = wide;
+    E.cplx = false;
     E.B = cx.alloc(nvec * max_space);
     E.S = cx.alloc(nvec * max_space);
-    E.pend = cx.alloc(nvec * nroots);
-    E.x = cx.alloc(nvec * nroots);
-    E.sx = cx.alloc(nvec * nroots);
-    E.corr = cx.alloc(nvec * nroots);
+    E.pend = cx.alloc(nvec * ncol);
+    E.x = cx.alloc(nvec * ncol);
+    E.sx = cx.alloc(nvec * ncol);
+    E.corr = cx.alloc(nvec * ncol);
     E.partial = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots) * DAV_MAXBLK);
     E.sums = cx.alloc(std::max<int64_t>(3 * (max_space + 1), nroots));
-    E.coef = cx.alloc((int64_t)max_space * nroots + nroots);
+    E.coef = cx.alloc((int64_t)max_space * ncol + ncol);
     E.diag = cx.alloc(nvec);
     fill_diag(E.diag);
     E.G.assign((size_t)max_space * max_space, 0.0);
@@ -274,6 +372,7 @@ void davidson_restart(Davidson& E)
     E.npend = 0;
     E.ritz = false;
     E.user_guess = false;
+    E.cplx = false;
     E.target.clear();
     E.nsigma = E.ncollapse = 0;
     std::fill(E.flags.begin(), E.flags.end(), 0);
@@ -401,8 +500,113 @@ void davidson_linear_start(Context& cx, Davidson& E, const double* rhs, int nrhs
     E.npend = E.nroots;
 }
 
+void davidson_linear_start_complex(Context& cx, Davidson& E, const double* rhs, int nrhs, const double* shift_re, const double* shift_im)
+{
+    const char* who = "davidson_linear_start_complex";
+    if (!rhs || nrhs < 1 || nrhs > E.nroots || !shift_re || !shift_im) throw Error(1, std::string(who) + ": no right-hand sides or shifts");
+    if (!E.wide || E.max_space < 4 * E.nroots || E.nroots > 64)
+        throw Error(1, std::string(who) + ": needs a state with two columns per system, 4 nsys <= max_space and nsys <= 64");
+    const int ns = E.nroots;
+    davidson_restart(E);
+    E.cplx = true;
+    E.rhs = rhs;
+    E.nrhs = nrhs;
+    E.shift.assign(shift_re, shift_re + ns);
+    E.shift_im.assign(shift_im, shift_im + ns);
+    E.prhs.assign((size_t)E.max_space * nrhs, 0.0);
+    std::fill(E.resnorm.begin(), E.resnorm.end(), HUGE_VAL);
+    AFESP_HIP(hipMemcpyAsync(E.coef, E.shift.data(), sizeof(double) * ns, hipMemcpyHostToDevice, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(E.coef + ns, E.shift_im.data(), sizeof(double) * ns, hipMemcpyHostToDevice, cx.stream));
+    LAUNCH(davidson_cprecondition_kernel, grid_for(E.nvec), E.pend, rhs, nrhs, E.coef, E.coef + ns, E.diag, E.nvec, ns, E.nvec);
+    cx.sync();   // (E.coef is written again by the first step)
+    E.npend = 2 * ns;
+}
+
+namespace {
+
+// davidson_linear_iterate of a state in the complex mode (davidson_so.h)
+int linear_iterate_complex(Context& cx, Davidson& E, const std::string& prefix, double tol, const DavidsonSigma& sigma)
+{
+    const std::string who = prefix + "iterate";
+    const int64_t nvec = E.nvec;
+    const int ms = E.max_space, ns = E.nroots;
+    if (!E.rhs || (E.nb == 0 && E.npend == 0)) throw Error(1, who + ": no right-hand sides (call " + prefix + "init first)");
+    // ---- collapse onto Re x_j, Im x_j of every system, in column order (no new sigma builds)
+    if (E.nb + E.npend > ms) {
+        E.nb = 0;
+        for (int k = 0; k < 2 * ns; ++k)
+            if (orthonormalise(cx, E, E.x + nvec * k, E.sx + nvec * k)) extend_linear(cx, E);
+        ++E.ncollapse;
+    }
+    // ---- the pending vectors, as in the real mode
+    for (int k = 0; k < E.npend && E.nb < ms; ++k) {
+        if (!orthonormalise(cx, E, E.pend + nvec * k, nullptr)) continue;
+        sigma(E.B + nvec * E.nb, E.S + nvec * E.nb);
+        ++E.nsigma;
+        extend_linear(cx, E);
+    }
+    E.npend = 0;
+    if (E.nb == 0) throw Error(1, who + ": every right-hand side vanished");
+    // ---- (G - z_j) y_j = -B^T rhs_j on the host; up: Re y (nb x ns), Im y (nb x ns), omega (ns), gamma (ns)
+    const int nb = E.nb;
+    double gmax = 0.0;
+    for (int q = 0; q < nb; ++q)
+        for (int p = 0; p < nb; ++p) gmax = std::max(gmax, std::fabs(E.G[p + (size_t)ms * q]));
+    std::vector<double> m(2 * (size_t)nb * nb), y(2 * (size_t)nb), up(2 * ((size_t)nb * ns + ns));
+    double *yre = up.data(), *yim = yre + (size_t)nb * ns, *uom = yim + (size_t)nb * ns, *uga = uom + ns;
+    for (int j = 0; j < ns; ++j) {
+        const double om = E.shift[j], ga = E.shift_im[j];
+        for (int q = 0; q < nb; ++q)
+            for (int p = 0; p < nb; ++p) {
+                m[2 * (p + (size_t)nb * q)] = E.G[p + (size_t)ms * q] - (p == q ? om : 0.0);
+                m[2 * (p + (size_t)nb * q) + 1] = p == q ? -ga : 0.0;
+            }
+        for (int p = 0; p < nb; ++p) {
+            y[2 * p] = -E.prhs[p + (size_t)ms * (j % E.nrhs)];
+            y[2 * p + 1] = 0.0;
+        }
+        const int rc = lu_solve_complex(nb, m.data(), nb, 1, y.data(), nb, DAV_POLE * std::max(gmax, std::hypot(om, ga)));
+        if (rc == 2)
+            throw Error(DAVIDSON_ERR_POLE, who + ": frequency at a pole: system " + std::to_string(j) + " (shift " + std::to_string(om) + " + " +
+                                               std::to_string(ga) + " i) is singular in the projected space of " + std::to_string(nb) + " vectors");
+        if (rc) throw Error(1, who + ": the projected system was not solved (status " + std::to_string(rc) + ")");
+        for (int p = 0; p < nb; ++p) {
+            yre[p + (size_t)nb * j] = y[2 * p];
+            yim[p + (size_t)nb * j] = y[2 * p + 1];
+        }
+        uom[j] = om;
+        uga[j] = ga;
+    }
+    AFESP_HIP(hipMemcpyAsync(E.coef, up.data(), sizeof(double) * up.size(), hipMemcpyHostToDevice, cx.stream));
+    // ---- the fused pass
+    const int nblk = davidson_reduce_blocks(nvec);
+    const double* dco = E.coef;
+    for (int k0 = 0; k0 < ns; k0 += DAV_CCHUNK)
+        LAUNCH(davidson_cfused_kernel, dim3(nblk), E.x, E.sx, E.corr, E.partial, E.B, E.S, nvec, nb, dco, dco + (size_t)nb * ns,
+               dco + 2 * (size_t)nb * ns, dco + 2 * (size_t)nb * ns + ns, E.diag, E.n1, E.w2, nvec, k0, std::min(DAV_CCHUNK, ns - k0), E.rhs, E.nrhs);
+    LAUNCH(davidson_final_kernel, dim3(ns), E.sums, E.partial, nblk);
+    std::vector<double> nrm(ns);
+    read_back(cx, nrm.data(), E.sums, ns);   // (also: `up` is no longer read)
+    E.ritz = true;
+    int all = 1;
+    for (int j = 0; j < ns; ++j) {
+        E.omega[j] = E.shift[j];
+        E.resnorm[j] = std::sqrt(nrm[j]);
+        E.flags[j] = E.resnorm[j] < tol ? EOM_FLAG_CONVERGED : 0;
+        if (E.flags[j]) continue;
+        all = 0;
+        LAUNCH(davidson_scale_kernel, grid_for(nvec), E.pend + nvec * E.npend, E.corr + nvec * 2 * j, E.pend + nvec * (E.npend + 1),
+               E.corr + nvec * (2 * j + 1), 1.0 / E.resnorm[j], nvec);
+        E.npend += 2;
+    }
+    return all;
+}
+
+}  // namespace
+
 int davidson_linear_iterate(Context& cx, Davidson& E, const std::string& prefix, double tol, const DavidsonSigma& sigma)
 {
+    if (E.cplx) return linear_iterate_complex(cx, E, prefix, tol, sigma);
     const std::string who = prefix + "iterate";
     const int64_t nvec = E.nvec;
     const int ms = E.max_space, ns = E.nroots;

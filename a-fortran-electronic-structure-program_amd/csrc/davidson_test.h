@@ -26,12 +26,17 @@ void davidson_test_sigma(Context& cx, DavidsonTest& T, const double* x, double* 
 void davidson_test_set_guess(Context& cx, int k, const double* x1, const double* x2);
 int davidson_test_iterate(Context& cx, double tol);          // -> 1 when every root has converged
 void davidson_test_linear_start(Context& cx, int nrhs, const double* rhs_host, const double* shifts);
-int davidson_test_linear_iterate(Context& cx, double tol);
+// the complex linear mode (davidson_linear_start_complex): nroots shifts shift_re + i shift_im; status 1 unless 4 nroots <= max_space and
+// nroots <= 64.  A state created for the real modes is allocated again with two columns per system, its diagonal carried over.
+void davidson_test_linear_start_complex(Context& cx, int nrhs, const double* rhs_host, const double* shift_re, const double* shift_im);
+int davidson_test_linear_iterate(Context& cx, double tol);   // (the real or the complex step, whichever start came last)
 void davidson_test_get_vector(Context& cx, int k, double* x1, double* x2);
 // what: B, S, pend (the first nb, nb, npend columns), x, sx, corr (nroots columns), diag, G (nb x nb column-major), prhs (nb x nrhs), y (the
 // coefficients of the last step, nb x nr, and behind them the nr values of omega the Ritz pass was given; status 1 when no step has finished
 // on the present basis -- before the first step, after a restart, after a step that threw at a pole --), target, counts ({nsigma,
-// ncollapse, nb, npend}) -> the number of doubles written; status 1 when `capacity` is smaller
+// ncollapse, nb, npend}) -> the number of doubles written; status 1 when `capacity` is smaller.  After a complex start x, sx and corr hold
+// 2 nroots columns (2 j: real part of system j, 2 j + 1: imaginary part) and y is Re y (nb x nroots), Im y (nb x nroots), then the nroots
+// values of omega and of gamma; on a real state every string answers as it always did.
 int64_t davidson_test_fetch(Context& cx, const char* what, double* out, int64_t capacity);
 
 }  // namespace afesp

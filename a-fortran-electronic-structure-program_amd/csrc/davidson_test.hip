@@ -135,6 +135,34 @@ void davidson_test_linear_start(Context& cx, int nrhs, const double* rhs_host, c
     T.linear = true;
 }
 
+void davidson_test_linear_start_complex(Context& cx, int nrhs, const double* rhs_host, const double* shift_re, const double* shift_im)
+{
+    const char* who = "afesp_test_davidson_linear_start_complex";
+    DavidsonTest& T = davidson_test_need(cx, who);
+    if (nrhs < 1 || nrhs > T.d.nroots || !rhs_host || !shift_re || !shift_im)
+        throw Error(1, std::string(who) + ": needs 1 <= nrhs <= nroots right-hand sides and nroots complex shifts");
+    if (T.d.max_space < 4 * T.d.nroots || T.d.nroots > 64) throw Error(1, std::string(who) + ": needs 4 nroots <= max_space and nroots <= 64");
+    if (!T.d.wide) {   // the state again with two columns per system, the diagonal carried over
+        Davidson wide;
+        try {
+            davidson_alloc(cx, wide, T.d.n1, T.d.nvec, T.d.w2, T.d.follow, T.d.nroots, T.d.max_space, [&](double* dg) { k_copy(cx, dg, T.d.diag, T.d.nvec); }, true);
+            cx.sync();
+        } catch (...) {
+            davidson_free(cx, wide);
+            throw;
+        }
+        davidson_free(cx, T.d);
+        T.d = wide;
+    }
+    cx.release(T.rhs);
+    T.rhs = nullptr;
+    T.d.rhs = nullptr;
+    T.rhs = cx.alloc(T.d.nvec * nrhs);
+    upload(cx, T.rhs, rhs_host, T.d.nvec * nrhs);
+    davidson_linear_start_complex(cx, T.d, T.rhs, nrhs, shift_re, shift_im);
+    T.linear = true;
+}
+
 int davidson_test_linear_iterate(Context& cx, double tol)
 {
     DavidsonTest& T = davidson_test_need(cx, "afesp_test_davidson_linear_iterate");
@@ -160,18 +188,19 @@ int64_t davidson_test_fetch(Context& cx, const char* what, double* out, int64_t 
     const std::string w = what;
     const int nb = E.nb, ms = E.max_space;
     const int nr = T.linear ? E.nroots : std::min(E.nroots, nb);
+    const int ncol = E.cplx ? 2 : 1;   // complex linear mode: real and imaginary columns
     const double* dev = nullptr;
     int64_t n = 0;
     if (w == "B") dev = E.B, n = E.nvec * nb;
     else if (w == "S") dev = E.S, n = E.nvec * nb;
     else if (w == "pend") dev = E.pend, n = E.nvec * E.npend;
-    else if (w == "x") dev = E.x, n = E.nvec * E.nroots;
-    else if (w == "sx") dev = E.sx, n = E.nvec * E.nroots;
-    else if (w == "corr") dev = E.corr, n = E.nvec * E.nroots;
+    else if (w == "x") dev = E.x, n = E.nvec * E.nroots * ncol;
+    else if (w == "sx") dev = E.sx, n = E.nvec * E.nroots * ncol;
+    else if (w == "corr") dev = E.corr, n = E.nvec * E.nroots * ncol;
     else if (w == "diag") dev = E.diag, n = E.nvec;
     else if (w == "y") {
         if (!E.ritz || T.y_nb != nb) throw Error(1, "afesp_test_davidson_fetch: no coefficients: no step has finished on the present basis");
-        dev = E.coef, n = (int64_t)nb * nr + nr;
+        dev = E.coef, n = ((int64_t)nb * nr + nr) * ncol;
     }
     if (dev) {
         if (n > capacity) throw Error(1, "afesp_test_davidson_fetch: capacity is below the " + std::to_string(n) + " doubles of " + w);

@@ -170,12 +170,13 @@ void preload_response_so()
     (void)hipGetLastError();
 }
 
-double so_response_bytes(int64_t o, int64_t v, int nop, int nsys, int max_space)
+double so_response_bytes(int64_t o, int64_t v, int nop, int nsys, int max_space, bool cplx)
 {
     const double O = (double)o, V = (double)v, nvec = O * V + O * O * V * V;
     // the Davidson state and the scratch of a sigma build and of a density call as the left EOM state counts them; the xi vectors, the
-    // operators and their dressed blocks
-    return so_eom_left_bytes(o, v, nsys, max_space) + 8.0 * nop * (nvec + (O + V) * (O + V) + O * O + V * V);
+    // operators and their dressed blocks; complex frequencies: what the second column of every system adds to the Davidson state
+    return so_eom_left_bytes(o, v, nsys, max_space) + 8.0 * nop * (nvec + (O + V) * (O + V) + O * O + V * V) +
+           (cplx ? davidson_bytes_complex(nvec, nsys, max_space) - davidson_bytes(nvec, nsys, max_space) : 0.0);
 }
 
 // so_response_xi behind its argument check
@@ -244,21 +245,24 @@ SOResponse& so_response_need(SOState& s, const char* who)
     return *r;
 }
 
-void so_response_init(Context& cx, SOState& s, int nop, const double* x, int nfreq, const double* omega, int max_space)
+// so_response_init (gamma null: real frequencies omega[f]) and so_response_init_complex (omega[f] + i gamma[f], both with stride `inc`)
+static void response_init(Context& cx, SOState& s, const char* who, int nop, const double* x, int nfreq, const double* omega, const double* gamma,
+                          int inc, int max_space)
 {
     need_plain(cx);
-    const char* who = "afesp_ccsd_so_response_init";
+    const bool cplx = gamma != nullptr;
     SOLambda& L = so_lambda_need(s, who);
     const int64_t O = s.o, V = s.v, N = O + V, nvec = vec_len(s);
     check_operators(who, nop, x, N);
     if (nfreq < 1 || !omega || (int64_t)nop * nfreq > RESPONSE_MAX_SYSTEMS)
         throw Error(1, std::string(who) + ": nfreq_signed must be at least 1 and nop nfreq_signed at most " + std::to_string(RESPONSE_MAX_SYSTEMS));
     for (int f = 0; f < nfreq; ++f)
-        if (!std::isfinite(omega[f])) throw Error(1, std::string(who) + ": a frequency is not finite");
+        if (!std::isfinite(omega[inc * f]) || (cplx && !std::isfinite(gamma[inc * f]))) throw Error(1, std::string(who) + ": a frequency is not finite");
     const int nsys = nop * nfreq;
-    if (max_space < 2 * nsys || max_space > 4096) throw Error(1, std::string(who) + ": max_space must be in 2 nop nfreq_signed .. 4096");
+    if (max_space < (cplx ? 4 : 2) * nsys || max_space > 4096)
+        throw Error(1, std::string(who) + ": max_space must be in " + (cplx ? "4" : "2") + " nop nfreq_signed .. 4096");
     so_response_free(cx, s);
-    if (!cx.fits(so_response_bytes(O, V, nop, nsys, max_space)))
+    if (!cx.fits(so_response_bytes(O, V, nop, nsys, max_space, cplx)))
         throw Error(1, std::string(who) + ": the response state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
     static const bool loaded = (preload_eom_so(), true);   // (the diagonal is the EE state's)
     (void)loaded;
@@ -269,15 +273,23 @@ void so_response_init(Context& cx, SOState& s, int nop, const double* x, int nfr
         R.nop = nop;
         R.nfreq = nfreq;
         R.x.assign(x, x + (int64_t)nop * N * N);
-        R.omega.assign(omega, omega + nfreq);
+        R.cplx = cplx;
+        R.omega.resize(nfreq);
+        R.gamma.assign(nfreq, 0.0);
+        for (int f = 0; f < nfreq; ++f) {
+            R.omega[f] = omega[inc * f];
+            if (cplx) R.gamma[f] = gamma[inc * f];
+        }
         R.phi.assign((size_t)nop * nsys, 0.0);
+        R.phi_im.assign(cplx ? (size_t)nop * nsys : 0, 0.0);
         R.have_phi.assign(nsys, 0);
         R.xi = cx.alloc(nvec * nop);
         xi_build(cx, s, nop, x, R.xi);   // (checked above)
-        davidson_alloc(cx, R.d, O * V, nvec, 0.25, false, nsys, max_space, [&](double* diag) { so_eom_fill_diag(cx, s, diag); });
-        std::vector<double> shifts(nsys);
-        for (int j = 0; j < nsys; ++j) shifts[j] = omega[j / nop];
-        davidson_linear_start(cx, R.d, R.xi, nop, shifts.data());
+        davidson_alloc(cx, R.d, O * V, nvec, 0.25, false, nsys, max_space, [&](double* diag) { so_eom_fill_diag(cx, s, diag); }, cplx);
+        std::vector<double> shifts(nsys), shifts_im(nsys);
+        for (int j = 0; j < nsys; ++j) shifts[j] = R.omega[j / nop], shifts_im[j] = R.gamma[j / nop];
+        if (cplx) davidson_linear_start_complex(cx, R.d, R.xi, nop, shifts.data(), shifts_im.data());
+        else davidson_linear_start(cx, R.d, R.xi, nop, shifts.data());
         R.d.epoch = L.epoch;
         R.lam_stamp = L.stamp;
         cx.sync();
@@ -285,6 +297,24 @@ void so_response_init(Context& cx, SOState& s, int nop, const double* x, int nfr
         try { cx.quiesce(); so_response_free(cx, s); } catch (...) {}
         throw;
     }
+}
+
+void so_response_init(Context& cx, SOState& s, int nop, const double* x, int nfreq, const double* omega, int max_space)
+{
+    response_init(cx, s, "afesp_ccsd_so_response_init", nop, x, nfreq, omega, nullptr, 1, max_space);
+}
+
+void so_response_init_complex(Context& cx, SOState& s, int nop, const double* x, int nfreq, const double* z, int max_space)
+{
+    response_init(cx, s, "afesp_ccsd_so_response_init_complex", nop, x, nfreq, z, z ? z + 1 : nullptr, 2, max_space);
+}
+
+// status 1 where the state is not of the kind the entry point `who` works on
+static void need_mode(const SOResponse& R, bool cplx, const char* who)
+{
+    if (R.cplx != cplx)
+        throw Error(1, std::string(who) + ": the response state was made for " + (R.cplx ? "complex" : "real") + " frequencies (use the " +
+                           (R.cplx ? "_complex entry points" : "entry points without _complex") + ", or initialise it again)");
 }
 
 int so_response_iterate(Context& cx, SOState& s, double tol)
@@ -301,6 +331,7 @@ void so_response_get_vector(Context& cx, SOState& s, int iop, int ifreq, double*
 {
     need_plain(cx);
     SOResponse& R = so_response_need(s, "afesp_ccsd_so_response_get_vector");
+    need_mode(R, false, "afesp_ccsd_so_response_get_vector");
     if (!R.stepped || iop < 0 || iop >= R.nop || ifreq < 0 || ifreq >= R.nfreq || !r1 || !r2)
         throw Error(1, "afesp_ccsd_so_response_get_vector: no solution (iop, ifreq) (iterate first; iop in 0 .. nop - 1, ifreq in 0 .. nfreq_signed - 1), or a NULL vector");
     const Davidson& E = R.d;
@@ -310,15 +341,138 @@ void so_response_get_vector(Context& cx, SOState& s, int iop, int ifreq, double*
     cx.sync();
 }
 
+void so_response_get_vector_complex(Context& cx, SOState& s, int iop, int ifreq, double* r1_re, double* r2_re, double* r1_im, double* r2_im)
+{
+    need_plain(cx);
+    const char* who = "afesp_ccsd_so_response_get_vector_complex";
+    SOResponse& R = so_response_need(s, who);
+    need_mode(R, true, who);
+    if (!R.stepped || iop < 0 || iop >= R.nop || ifreq < 0 || ifreq >= R.nfreq || !r1_re || !r2_re || !r1_im || !r2_im)
+        throw Error(1, std::string(who) + ": no solution (iop, ifreq) (iterate first; iop in 0 .. nop - 1, ifreq in 0 .. nfreq_signed - 1), or a NULL vector");
+    const Davidson& E = R.d;
+    const double* p = E.x + E.nvec * 2 * (iop + R.nop * ifreq);
+    const double* q = p + E.nvec;
+    AFESP_HIP(hipMemcpyAsync(r1_re, p, sizeof(double) * E.n1, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(r2_re, p + E.n1, sizeof(double) * (E.nvec - E.n1), hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(r1_im, q, sizeof(double) * E.n1, hipMemcpyDeviceToHost, cx.stream));
+    AFESP_HIP(hipMemcpyAsync(r2_im, q + E.n1, sizeof(double) * (E.nvec - E.n1), hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+}
+
+namespace {
+
+// Phi[X_a, r] of one device vector r for every operator of the state: one density call, the traces on the host in a fixed order.  The
+// host copy of lambda, D and Tr(X_a D) are made at the first call and kept for the later ones of one response function.
+struct PhiWork {
+    std::vector<double> lam, r, D, gam, trD;
+
+    void column(Context& cx, SOState& s, SOResponse& R, const double* xj, double* phi /* nop, stride 1 */)
+    {
+        SOLambda& L = *s.lam;
+        const int nop = R.nop;
+        const int64_t O = s.o, V = s.v, N = O + V, ov = O * V, o2v2 = O * O * V * V, nvec = ov + o2v2;
+        const int nblk = davidson_reduce_blocks(nvec);
+        if (lam.empty()) {
+            lam.resize(nvec);
+            r.resize(nvec);
+            D.resize(N * N);
+            gam.resize(N * N);
+            trD.resize(nop);
+            AFESP_HIP(hipMemcpyAsync(lam.data(), L.l1.d, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
+            AFESP_HIP(hipMemcpyAsync(lam.data() + ov, L.l2.d, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
+            cx.sync();
+            so_density(cx, s, D.data(), N * N);
+            for (int a = 0; a < nop; ++a) {
+                double t = 0.0;
+                for (int64_t e = 0; e < N * N; ++e) t += R.x[(int64_t)a * N * N + e] * D[e];
+                trD[a] = t;
+            }
+        }
+        double* partial = cx.scratch("rsp_partial", nblk + 1);
+        LAUNCH(response_dot_kernel, dim3(nblk), partial, L.l1.d, L.l2.d, xj, ov, o2v2);
+        davidson_reduce_final(cx, partial + nblk, partial, 1, nblk);
+        double lr = 0.0;
+        AFESP_HIP(hipMemcpyAsync(&lr, partial + nblk, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(r.data(), xj, sizeof(double) * nvec, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+        so_eom_density(cx, s, 1.0, lam.data(), lam.data() + ov, 0.0, r.data(), r.data() + ov, gam.data(), N * N);
+        for (int a = 0; a < nop; ++a) {
+            double t = 0.0;
+            for (int64_t e = 0; e < N * N; ++e) t += R.x[(int64_t)a * N * N + e] * gam[e];
+            phi[a] = t - trD[a] * lr;
+        }
+    }
+};
+
+void need_converged(const SOResponse& R, const char* who, int g)
+{
+    for (int a = 0; a < R.nop; ++a)
+        if (!R.stepped || !(R.d.flags[a + R.nop * g] & EOM_FLAG_CONVERGED))
+            throw Error(RESPONSE_ERR_NOT_CONVERGED, std::string(who) + ": the solution of operator " + std::to_string(a) + " at frequency " +
+                                                        std::to_string(R.omega[g]) + (R.cplx ? " + " + std::to_string(R.gamma[g]) + " i" : "") +
+                                                        " has not converged (residual " +
+                                                        std::to_string(R.stepped ? R.d.resnorm[a + R.nop * g] : HUGE_VAL) + ")");
+}
+
+}  // namespace
+
+void so_response_function_complex(Context& cx, SOState& s, int nfreq, const double* z, double* out)
+{
+    need_plain(cx);
+    const char* who = "afesp_ccsd_so_response_function_complex";
+    SOResponse& R = so_response_need(s, who);
+    need_mode(R, true, who);
+    if (nfreq < 1 || !z || !out) throw Error(1, std::string(who) + ": nfreq < 1 or a NULL argument");
+    const int nop = R.nop;
+    const int64_t nvec = vec_len(s);
+    // ---- which stored frequency serves z and -z of every request: -z itself, or the conjugate of the solution at -conj(z)
+    std::vector<int> plus(nfreq, -1), minus(nfreq, -1);
+    std::vector<char> conj(nfreq, 0);
+    for (int f = 0; f < nfreq; ++f) {
+        const double re = z[2 * f], im = z[2 * f + 1];
+        int partner = -1;
+        for (int g = R.nfreq - 1; g >= 0; --g) {
+            if (R.omega[g] == re && R.gamma[g] == im) plus[f] = g;
+            if (R.omega[g] == -re && R.gamma[g] == -im) minus[f] = g;
+            if (R.omega[g] == -re && R.gamma[g] == im) partner = g;
+        }
+        if (minus[f] < 0 && partner >= 0) minus[f] = partner, conj[f] = 1;
+        if (plus[f] < 0 || minus[f] < 0)
+            throw Error(1, std::string(who) + ": the frequency " + std::to_string(re) + " + " + std::to_string(im) +
+                               " i was not solved at z and at -z (or -conj z) by this response state");
+    }
+    for (int f = 0; f < nfreq; ++f)
+        for (int g : {plus[f], minus[f]}) need_converged(R, who, g);
+    // ---- Phi[X_a, P_j] and Phi[X_a, Q_j] of the systems that lack them: two density calls per solution
+    PhiWork work;
+    for (int f = 0; f < nfreq; ++f)
+        for (int g : {plus[f], minus[f]})
+            for (int b = 0; b < nop; ++b) {
+                const int j = b + nop * g;
+                if (R.have_phi[j]) continue;
+                work.column(cx, s, R, R.d.x + nvec * 2 * j, R.phi.data() + (size_t)nop * j);
+                work.column(cx, s, R, R.d.x + nvec * (2 * j + 1), R.phi_im.data() + (size_t)nop * j);
+                R.have_phi[j] = 1;
+            }
+    for (int f = 0; f < nfreq; ++f)
+        for (int a = 0; a < nop; ++a)
+            for (int b = 0; b < nop; ++b) {
+                const size_t jp = a + (size_t)nop * (b + nop * plus[f]), jm = b + (size_t)nop * (a + nop * minus[f]);
+                double* o2 = out + 2 * (((size_t)f * nop + a) * nop + b);
+                o2[0] = R.phi[jp] + R.phi[jm];
+                o2[1] = R.phi_im[jp] + (conj[f] ? -R.phi_im[jm] : R.phi_im[jm]);
+            }
+}
+
 void so_response_function(Context& cx, SOState& s, int nfreq, const double* omega, double* out)
 {
     need_plain(cx);
     const char* who = "afesp_ccsd_so_response_function";
     SOResponse& R = so_response_need(s, who);
-    SOLambda& L = *s.lam;
+    need_mode(R, false, who);
     if (nfreq < 1 || !omega || !out) throw Error(1, std::string(who) + ": nfreq < 1 or a NULL argument");
     const int nop = R.nop;
-    const int64_t O = s.o, V = s.v, N = O + V, ov = O * V, o2v2 = O * O * V * V, nvec = ov + o2v2;
+    const int64_t nvec = vec_len(s);
     // ---- which stored frequency serves +omega and -omega of every request; all of them solved and converged?
     std::vector<int> plus(nfreq, -1), minus(nfreq, -1);
     for (int f = 0; f < nfreq; ++f) {
@@ -330,47 +484,15 @@ void so_response_function(Context& cx, SOState& s, int nfreq, const double* omeg
             throw Error(1, std::string(who) + ": the frequency " + std::to_string(omega[f]) + " was not solved at both signs by this response state");
     }
     for (int f = 0; f < nfreq; ++f)
-        for (int g : {plus[f], minus[f]})
-            for (int a = 0; a < nop; ++a)
-                if (!R.stepped || !(R.d.flags[a + nop * g] & EOM_FLAG_CONVERGED))
-                    throw Error(RESPONSE_ERR_NOT_CONVERGED, std::string(who) + ": the solution of operator " + std::to_string(a) + " at frequency " +
-                                                                std::to_string(R.omega[g]) + " has not converged (residual " +
-                                                                std::to_string(R.stepped ? R.d.resnorm[a + nop * g] : HUGE_VAL) + ")");
+        for (int g : {plus[f], minus[f]}) need_converged(R, who, g);
     // ---- Phi[X_a, R_j] of the systems that lack it: one density per solution, the traces on the host in a fixed order
-    std::vector<double> lam, r(nvec), D, gam(N * N), trD(nop);
-    const int nblk = davidson_reduce_blocks(nvec);
+    PhiWork work;
     for (int f = 0; f < nfreq; ++f)
         for (int g : {plus[f], minus[f]})
             for (int b = 0; b < nop; ++b) {
                 const int j = b + nop * g;
                 if (R.have_phi[j]) continue;
-                if (lam.empty()) {
-                    lam.resize(nvec);
-                    D.resize(N * N);
-                    AFESP_HIP(hipMemcpyAsync(lam.data(), L.l1.d, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
-                    AFESP_HIP(hipMemcpyAsync(lam.data() + ov, L.l2.d, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
-                    cx.sync();
-                    so_density(cx, s, D.data(), N * N);
-                    for (int a = 0; a < nop; ++a) {
-                        double t = 0.0;
-                        for (int64_t e = 0; e < N * N; ++e) t += R.x[(int64_t)a * N * N + e] * D[e];
-                        trD[a] = t;
-                    }
-                }
-                const double* xj = R.d.x + nvec * j;
-                double* partial = cx.scratch("rsp_partial", nblk + 1);
-                LAUNCH(response_dot_kernel, dim3(nblk), partial, L.l1.d, L.l2.d, xj, ov, o2v2);
-                davidson_reduce_final(cx, partial + nblk, partial, 1, nblk);
-                double lr = 0.0;
-                AFESP_HIP(hipMemcpyAsync(&lr, partial + nblk, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
-                AFESP_HIP(hipMemcpyAsync(r.data(), xj, sizeof(double) * nvec, hipMemcpyDeviceToHost, cx.stream));
-                cx.sync();
-                so_eom_density(cx, s, 1.0, lam.data(), lam.data() + ov, 0.0, r.data(), r.data() + ov, gam.data(), N * N);
-                for (int a = 0; a < nop; ++a) {
-                    double t = 0.0;
-                    for (int64_t e = 0; e < N * N; ++e) t += R.x[(int64_t)a * N * N + e] * gam[e];
-                    R.phi[a + (size_t)nop * j] = t - trD[a] * lr;
-                }
+                work.column(cx, s, R, R.d.x + nvec * j, R.phi.data() + (size_t)nop * j);
                 R.have_phi[j] = 1;
             }
     for (int f = 0; f < nfreq; ++f)

@@ -437,4 +437,59 @@ inline int lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, dou
     return 0;
 }
 
+// lu_solve for a complex matrix and complex right-hand sides: a and b hold (re, im) pairs, element (i, j) of a at a[2 (i + lda j)] and
+// a[2 (i + lda j) + 1], b likewise with ldb.  Pivoting is on |pivot| (hypot); -> 2 when |pivot| is not above `floor`.  The products and
+// quotients are written out on the parts -- (a + ib)(c + id) = (ac - bd) + i(ad + bc), (a + ib) / (c + id) = [(ac + bd) + i(bc - ad)] /
+// (c^2 + d^2) -- so that a system whose imaginary parts are all zero is solved with imaginary parts that are exactly zero.
+inline int lu_solve_complex(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor)
+{
+    if (n < 1 || nrhs < 0 || !a || lda < n || (nrhs > 0 && (!b || ldb < n)) || !(floor >= 0.0)) return 1;
+    auto A = [&](int i, int j) { return a + 2 * (i + (size_t)lda * j); };
+    auto Bv = [&](int i, int j) { return b + 2 * (i + (size_t)ldb * j); };
+    auto mag = [](const double* z) { return std::hypot(z[0], z[1]); };
+    // z -= l w
+    auto submul = [](double* z, const double* l, const double* w) {
+        z[0] -= l[0] * w[0] - l[1] * w[1];
+        z[1] -= l[0] * w[1] + l[1] * w[0];
+    };
+    auto div = [](const double* x, const double* y, double* q) {
+        const double m2 = y[0] * y[0] + y[1] * y[1];
+        const double re = (x[0] * y[0] + x[1] * y[1]) / m2, im = (x[1] * y[0] - x[0] * y[1]) / m2;
+        q[0] = re;
+        q[1] = im;
+    };
+    for (int k = 0; k < n; ++k) {
+        int p = k;
+        for (int i = k + 1; i < n; ++i)
+            if (mag(A(i, k)) > mag(A(p, k))) p = i;
+        if (!(mag(A(p, k)) > floor)) return 2;
+        if (p != k) {
+            for (int j = 0; j < n; ++j) {
+                std::swap(A(k, j)[0], A(p, j)[0]);
+                std::swap(A(k, j)[1], A(p, j)[1]);
+            }
+            for (int j = 0; j < nrhs; ++j) {
+                std::swap(Bv(k, j)[0], Bv(p, j)[0]);
+                std::swap(Bv(k, j)[1], Bv(p, j)[1]);
+            }
+        }
+        for (int i = k + 1; i < n; ++i) {
+            double l[2];
+            div(A(i, k), A(k, k), l);
+            if (l[0] == 0.0 && l[1] == 0.0) continue;
+            A(i, k)[0] = l[0];
+            A(i, k)[1] = l[1];
+            for (int j = k + 1; j < n; ++j) submul(A(i, j), l, A(k, j));
+            for (int j = 0; j < nrhs; ++j) submul(Bv(i, j), l, Bv(k, j));
+        }
+    }
+    for (int j = 0; j < nrhs; ++j)
+        for (int k = n - 1; k >= 0; --k) {
+            double x[2] = {Bv(k, j)[0], Bv(k, j)[1]};
+            for (int i = k + 1; i < n; ++i) submul(x, A(k, i), Bv(i, j));
+            div(x, A(k, k), Bv(k, j));
+        }
+    return 0;
+}
+
 }  // namespace afesp

@@ -27,6 +27,7 @@ module afesp_capi
              afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
              afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
              afesp_ccsd_so_response_init, afesp_ccsd_so_response_iterate, afesp_ccsd_so_response_function, &
+             afesp_ccsd_so_response_init_complex, afesp_ccsd_so_response_function_complex, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
 
    integer(c_int), parameter :: AFESP_COMM_RCCL = 0, AFESP_COMM_HOST = 1
@@ -609,6 +610,23 @@ module afesp_capi
          type(c_ptr), value :: ctx
          integer(c_int), value :: nfreq
          real(c_double), intent(in) :: omega(*)
+         real(c_double), intent(out) :: res(*)
+         integer(c_int) :: rc
+      end function
+      ! the same at complex frequencies: z holds (re, im) pairs, res (re, im) pairs of <<X_a;X_b>>_z; _iterate steps either kind of state
+      function afesp_ccsd_so_response_init_complex(ctx, nop, x, nfreq_signed, z, max_space) &
+         bind(C, name='afesp_ccsd_so_response_init_complex') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nop, nfreq_signed, max_space
+         real(c_double), intent(in) :: x(*), z(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_response_function_complex(ctx, nfreq, z, res) bind(C, name='afesp_ccsd_so_response_function_complex') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nfreq
+         real(c_double), intent(in) :: z(*)
          real(c_double), intent(out) :: res(*)
          integer(c_int) :: rc
       end function

@@ -70,6 +70,11 @@ module host_config
       logical :: cc_polar = .false.
       real(dp) :: polar_omega(8) = 0.0_dp
       integer :: n_polar_omega = 1
+      ! ... polar_gamma > 0: every polar_omega is solved at omega + i polar_gamma (DESIGN.md 4.20) and the table gains Re / Im of the mean
+      ! and the absorption cross-section; polar_c6_npts > 0: the mean at i u_k on that many Casimir-Polder grid points and the
+      ! homo-dimer C6.  Both at their defaults: the path above, untouched.
+      real(dp) :: polar_gamma = 0.0_dp
+      integer :: polar_c6_npts = 0
    end type
 contains
    !> &elsinput namelist; keys that are absent keep the defaults above (the reference leaves them undefined).
@@ -82,13 +87,14 @@ contains
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
       logical :: eom_left, cc_rdm2, cc_relaxed, cc_polar
-      real(dp) :: polar_omega(8)
+      real(dp) :: polar_omega(8), polar_gamma
+      integer :: polar_c6_npts
       real(dp), parameter :: omega_unset = huge(1.0_dp)
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
          cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2, cc_relaxed, &
-         cc_polar, polar_omega
+         cc_polar, polar_omega, polar_gamma, polar_c6_npts
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
       ccsd_t_tol = d%ccsd_t_tol; scf_diis_n_errmat = d%scf_diis_n_errmat; ccsd_diis_n_errmat = d%ccsd_diis_n_errmat
@@ -101,6 +107,7 @@ contains
       cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
       cc_polar = d%cc_polar; polar_omega = omega_unset
+      polar_gamma = d%polar_gamma; polar_c6_npts = d%polar_c6_npts
       inquire (file='els.in', exist=there)
       if (.not. there) call fail('system::read_system_in', 'input file els.in does not exist')
       open (newunit=unit, file='els.in', action='read', status='old')
@@ -204,6 +211,10 @@ contains
       else
          cfg%n_polar_omega = 1
       end if
+      if (.not. polar_gamma >= 0.0_dp) call fail('system::read_system_in', 'polar_gamma is a damping in Eh, zero (real frequencies) or positive!')
+      if (polar_c6_npts < 0 .or. polar_c6_npts > 21) call fail('system::read_system_in', &
+         'polar_c6_npts is the number of Casimir-Polder grid points, 0 (off) to 21 (three operators each, 64 systems in one response state)!')
+      cfg%polar_gamma = polar_gamma; cfg%polar_c6_npts = polar_c6_npts
       cfg%eom_ip_nroots = eom_ip_nroots; cfg%eom_ea_nroots = eom_ea_nroots
       if (eom_ip_nroots < 0) call fail('system::read_system_in', 'eom_ip_nroots must be a non-negative integer!')
       if (eom_ea_nroots < 0) call fail('system::read_system_in', 'eom_ea_nroots must be a non-negative integer!')
@@ -1687,6 +1698,12 @@ contains
          end do
       end do
       if (.not. lambda_live) call lambda_solve()
+      if (cfg%polar_gamma > 0.0_dp) then   ! damped response: every frequency at omega + i gamma (DESIGN.md 4.20)
+         call polar_damped_table(xso, nalpha + nbeta, 2*n - nalpha - nbeta)
+         if (cfg%polar_c6_npts > 0) call polar_c6_table(xso, nalpha + nbeta, 2*n - nalpha - nbeta)
+         write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the EOM-CCSD polarisability:', seconds() - tp, 's'
+         return
+      end if
       ! the signed list: +omega and -omega of every frequency, each value once
       allocate (signed(2*cfg%n_polar_omega)); ns = 0
       do f = 1, cfg%n_polar_omega
@@ -1728,7 +1745,151 @@ contains
          write (out, '(4X, A, F18.10, 3X, A, F18.10)') 'mean ', mean, 'anisotropy ', aniso
       end do
       write (out, '(2X, A, I0, 3X, A, ES11.3)') 'response sigma builds: ', nsig, 'largest residual: ', maxval(res)
+      if (cfg%polar_c6_npts > 0) call polar_c6_table(xso, nalpha + nbeta, 2*n - nalpha - nbeta)
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the EOM-CCSD polarisability:', seconds() - tp, 's'
+   end subroutine
+   !> alpha(z) = -<<mu;mu>>_z of the three operators xso at the nz complex frequencies z(1:2, :) = (re, im): the signed list (z, and -z
+   !> where Re z /= 0 -- for an imaginary z its partner is its own conjugate --, each value once), one response state on one real basis,
+   !> the steps, the function.  alpha(a, b, f) = (re, im) in alpha(1:2, a, b, f).
+   subroutine polar_complex_solve(xso, o, v, nz, z, alpha, nsig, maxres)
+      real(dp), intent(in) :: xso(:, :, :), z(:, :)
+      integer, intent(in) :: o, v, nz
+      real(dp), intent(out) :: alpha(:, :, :, :), maxres
+      integer(c_int), intent(out) :: nsig
+      real(dp), parameter :: polar_tol = 1.0e-8_dp
+      real(dp), allocatable :: signed(:, :), res(:), rf(:, :, :, :)
+      integer(c_int) :: pconv
+      integer(c_int64_t) :: o8, v8, nunique
+      integer :: f, c, g, ns, nsys, ms, it, a, b
+      logical :: ok, seen
+      real(dp) :: cand(2)
+      allocate (signed(2, 2*nz)); ns = 0
+      do f = 1, nz
+         do c = 1, -1, -2
+            if (c == -1 .and. z(1, f) == 0.0_dp) cycle
+            cand = c*z(:, f) + 0.0_dp
+            seen = .false.
+            do g = 1, ns
+               if (signed(1, g) == cand(1) .and. signed(2, g) == cand(2)) seen = .true.
+            end do
+            if (.not. seen) then
+               ns = ns + 1; signed(:, ns) = cand
+            end if
+         end do
+      end do
+      nsys = 3*ns
+      if (nsys > 64) call fail('polar::init_response', 'more than 64 response systems: fewer frequencies or grid points!')
+      o8 = int(o, c_int64_t); v8 = int(v, c_int64_t)
+      nunique = o8*v8 + (o8*(o8 - 1)/2)*(v8*(v8 - 1)/2)
+      ms = min(4096, max(4*nsys, int(min(nunique + int(2*nsys, c_int64_t), int(16*nsys, c_int64_t)))))
+      rc = afesp_ccsd_so_response_init_complex(ctx, 3_c_int, xso, int(ns, c_int), signed, int(ms, c_int))
+      if (rc /= 0) call fail('polar::init_response', afesp_error_text(ctx))
+      allocate (res(nsys), rf(2, 3, 3, nz))
+      ok = .false.
+      do it = 1, 100
+         rc = afesp_ccsd_so_response_iterate(ctx, polar_tol, res, nsig, pconv)
+         if (rc /= 0) call fail('polar::iterate', afesp_error_text(ctx))
+         if (pconv /= 0) then
+            ok = .true.
+            exit
+         end if
+      end do
+      if (.not. ok) call fail('polar::do_response', 'the response equations did not converge!')
+      rc = afesp_ccsd_so_response_function_complex(ctx, int(nz, c_int), z, rf)
+      if (rc /= 0) call fail('polar::response_function', afesp_error_text(ctx))
+      do f = 1, nz
+         do b = 1, 3
+            do a = 1, 3
+               alpha(:, a, b, f) = -rf(:, b, a, f)   ! (the library's rows are the first operator: out[2 ((f nop + a) nop + b)])
+            end do
+         end do
+      end do
+      maxres = maxval(res)
+   end subroutine
+   !> polar_gamma > 0: per frequency the real and the imaginary 3 x 3 table of alpha(omega + i gamma), Re and Im of the isotropic mean and
+   !> the absorption cross-section sigma(omega) = 4 pi omega / c Im mean (atomic units)
+   subroutine polar_damped_table(xso, o, v)
+      real(dp), intent(in) :: xso(:, :, :)
+      integer, intent(in) :: o, v
+      real(dp), parameter :: light_speed = 137.035999084_dp, pi = 3.14159265358979323846_dp
+      real(dp), allocatable :: z(:, :), alpha(:, :, :, :)
+      integer(c_int) :: nsig
+      real(dp) :: maxres, mean(2)
+      integer :: f, c, part, nf
+      nf = cfg%n_polar_omega
+      allocate (z(2, nf), alpha(2, 3, 3, nf))
+      z(1, :) = cfg%polar_omega(:nf); z(2, :) = cfg%polar_gamma
+      call polar_complex_solve(xso, o, v, nf, z, alpha, nsig, maxres)
+      do f = 1, nf
+         write (out, '(2X, A, F14.8, A, F14.8, A)') 'omega = ', z(1, f), ' Eh   gamma = ', z(2, f), ' Eh'
+         do part = 1, 2
+            do c = 1, 3
+               write (out, '(4X, A2, 1X, A1, 2X, 3F18.10)') merge('Re', 'Im', part == 1), 'xyz'(c:c), alpha(part, c, :, f)
+            end do
+         end do
+         mean = (alpha(:, 1, 1, f) + alpha(:, 2, 2, f) + alpha(:, 3, 3, f))/3.0_dp
+         write (out, '(4X, A, F18.10, 3X, A, F18.10, 3X, A, F18.10)') 'Re mean ', mean(1), 'Im mean ', mean(2), &
+            'sigma ', 4.0_dp*pi*z(1, f)/light_speed*mean(2)
+      end do
+      write (out, '(2X, A, I0, 3X, A, ES11.3)') 'response sigma builds: ', nsig, 'largest residual: ', maxres
+   end subroutine
+   !> polar_c6_npts > 0: the isotropic mean at i u_k on the Gauss-Legendre grid t_k in (-1, 1) mapped by u = u0 (1 + t) / (1 - t), weights
+   !> w_k 2 u0 / (1 - t_k)^2, u0 = 0.3, and the homo-dimer C6 = (3 / pi) sum_k weight_k mean(i u_k)^2.  One solve per grid point (the
+   !> partner of an imaginary frequency is its own conjugate), all points in one response state.
+   subroutine polar_c6_table(xso, o, v)
+      real(dp), intent(in) :: xso(:, :, :)
+      integer, intent(in) :: o, v
+      real(dp), parameter :: u0 = 0.3_dp, pi = 3.14159265358979323846_dp
+      real(dp), allocatable :: t(:), w(:), z(:, :), alpha(:, :, :, :), mean(:)
+      integer(c_int) :: nsig
+      real(dp) :: maxres, c6
+      integer :: k, np
+      np = cfg%polar_c6_npts
+      allocate (t(np), w(np), z(2, np), alpha(2, 3, 3, np), mean(np))
+      call gauss_legendre(np, t, w)
+      z(1, :) = 0.0_dp; z(2, :) = u0*(1.0_dp + t)/(1.0_dp - t)
+      w = w*2.0_dp*u0/(1.0_dp - t)**2
+      call polar_complex_solve(xso, o, v, np, z, alpha, nsig, maxres)
+      write (out, '(2X, A, I0, A, F10.6)') 'Casimir-Polder grid: ', np, ' points, u0 = ', u0
+      c6 = 0.0_dp
+      do k = 1, np
+         mean(k) = (alpha(1, 1, 1, k) + alpha(1, 2, 2, k) + alpha(1, 3, 3, k))/3.0_dp
+         write (out, '(4X, A, I3, 3X, A, F18.10, 3X, A, F18.10, 3X, A, F18.10)') 'point', k, 'u ', z(2, k), 'weight ', w(k), 'mean(iu) ', mean(k)
+         c6 = c6 + w(k)*mean(k)**2
+      end do
+      c6 = 3.0_dp/pi*c6
+      write (out, '(2X, A, F18.10)') 'C6 (homo-dimer) = ', c6
+      write (out, '(2X, A, I0, 3X, A, ES11.3)') 'C6 response sigma builds: ', nsig, 'largest residual: ', maxres
+   end subroutine
+   !> nodes (ascending) and weights of the n-point Gauss-Legendre rule on (-1, 1): Newton's iteration on P_n from the Chebyshev guess
+   subroutine gauss_legendre(n, t, w)
+      integer, intent(in) :: n
+      real(dp), intent(out) :: t(n), w(n)
+      real(dp), parameter :: pi = 3.14159265358979323846_dp
+      real(dp) :: x, p0, p1, p2, dp1, dx
+      integer :: i, j, it
+      do i = 1, n
+         x = -cos(pi*(real(i, dp) - 0.25_dp)/(real(n, dp) + 0.5_dp))
+         do it = 1, 100
+            p0 = 1.0_dp; p1 = x
+            do j = 2, n
+               p2 = (real(2*j - 1, dp)*x*p1 - real(j - 1, dp)*p0)/real(j, dp)
+               p0 = p1; p1 = p2
+            end do
+            dp1 = real(n, dp)*(x*p1 - p0)/(x*x - 1.0_dp)
+            dx = p1/dp1
+            x = x - dx
+            if (abs(dx) < 1.0e-15_dp) exit
+         end do
+         p0 = 1.0_dp; p1 = x
+         do j = 2, n
+            p2 = (real(2*j - 1, dp)*x*p1 - real(j - 1, dp)*p0)/real(j, dp)
+            p0 = p1; p1 = p2
+         end do
+         dp1 = real(n, dp)*(x*p1 - p0)/(x*x - 1.0_dp)
+         t(i) = x
+         w(i) = 2.0_dp/((1.0_dp - x*x)*dp1*dp1)
+      end do
    end subroutine
    !> sum over p, r beta and q, s alpha of (x_pr y_qs - x_ps y_qr) S_ps S_rq, S the non-zero (beta, alpha) block of a
    function flip_pair(xm, ym, a) result(val)

@@ -392,7 +392,7 @@ int afesp_ccsd_so_eom_density(afesp_ctx* ctx, double l0, const double* l1, const
  *   alpha_XY(omega)    = -<<X;Y>>_omega
  * This is the EOM-CC response function (Stanton and Bartlett 1993), not the LR-CC one: the term quadratic in the perturbed amplitudes is
  * absent by definition, <<X;Y>>_omega = <<Y;X>>_-omega holds but alpha_XY(omega) != alpha_YX(omega) in general off omega = 0; for two
- * electrons it is exact.  Real frequencies only.
+ * electrons it is exact.  Real frequencies here; complex ones: the _complex entry points below.
  *   afesp_ccsd_so_response_xi         = xi1 [nop * o*v], xi2 [nop * o*o*v*v] of nop operators x [nop * (o+v)^2] at the current t1 / t2, one
  *                                       after the other (host in / out; needs neither a Lambda nor a response state).  An operator's
  *                                       vector has the same bits whatever else is in the batch; xi2 is antisymmetric to the bit.
@@ -431,6 +431,31 @@ int afesp_ccsd_so_response_iterate(afesp_ctx* ctx, double tol, double* resnorm, 
 int afesp_ccsd_so_response_get_vector(afesp_ctx* ctx, int iop, int ifreq, double* r1, double* r2);
 int afesp_ccsd_so_response_function(afesp_ctx* ctx, int nfreq, const double* omega, double* out /* [nfreq*nop*nop] */);
 int afesp_lu_solve(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor);
+
+/* The same response function at complex frequencies z = omega + i gamma (afesp_version 5): damped spectra, alpha(i omega)
+ * and C6.  A and xi^X are real, R = P + i Q:
+ *   (A - z) R^X(z) = -xi^X      <=>      (A - omega) P + gamma Q = -xi,   (A - omega) Q - gamma P = 0
+ *   <<X;Y>>_z          = Phi[X, R^Y(z)] + Phi[Y, R^X(-z)],   Phi[X, P + i Q] = Phi[X, P] + i Phi[X, Q],   alpha_XY(z) = -<<X;Y>>_z
+ *   R(conj z)          = conj R(z)
+ * the analytic continuation of the function above: with gamma > 0 nothing is singular at an excitation energy, Im alpha(omega + i gamma)
+ * is the absorption profile, alpha(i u) the integrand of the Casimir-Polder integral.  The basis of the solver stays real and every sigma
+ * build serves every system; a solution takes two vectors.
+ *   afesp_ccsd_so_response_init_complex       = as _init with nfreq_signed complex frequencies z [2 * nfreq_signed: re, im]; at most 64
+ *                                               systems, 4 nop nfreq_signed <= max_space <= 4096.  Releases an earlier response state of
+ *                                               either kind.  afesp_ccsd_so_response_iterate steps a state of either kind.
+ *   afesp_ccsd_so_response_get_vector_complex = Re and Im of R^X_iop(z[ifreq]) of the last step.
+ *   afesp_ccsd_so_response_function_complex   = out[2 * ((f * nop + a) * nop + b) + {0, 1}] = Re, Im of <<X_a;X_b>>_z[f].  R^X(-z) is the
+ *                                               resident solution at -z where the list has it, otherwise the conjugate of the one at
+ *                                               -conj(z) -- for an imaginary z that is z itself: one solve per imaginary frequency.
+ *   afesp_lu_solve_complex                    = TEST ENTRY, as afesp_lu_solve: the host LU of the projected complex systems; a and b hold
+ *                                               (re, im) pairs, element (i, j) at a[2 * (i + lda * j)]; pivoting on |pivot|; 0, 1 or 2.
+ * Statuses as above; in addition 1 when a real entry point (_get_vector, _function) is called on a state made by _init_complex or a
+ * _complex one on a state made by _init -- no silent reinterpretation --, and 1 from _function_complex for a z whose -z and -conj(z) are
+ * both missing from the list.  With gamma != 0 a pole (26) cannot occur; it remains for gamma = 0. */
+int afesp_ccsd_so_response_init_complex(afesp_ctx* ctx, int nop, const double* x, int nfreq_signed, const double* z, int max_space);
+int afesp_ccsd_so_response_get_vector_complex(afesp_ctx* ctx, int iop, int ifreq, double* r1_re, double* r2_re, double* r1_im, double* r2_im);
+int afesp_ccsd_so_response_function_complex(afesp_ctx* ctx, int nfreq, const double* z, double* out /* [2*nfreq*nop*nop] */);
+int afesp_lu_solve_complex(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor);
 
 /* EOM-IP-CCSD and EOM-EA-CCSD on the same state: ionisation potentials omega = E(N-1) - E(N) in the 1h + 2h1p sector,
  * r1(nocc), r2(nocc,nocc,nvirt) antisymmetric in its first two indices, and electron affinities omega = E(N+1) - E(N) in the 1p + 2p1h
@@ -692,13 +717,17 @@ int afesp_test_inject(afesp_ctx* ctx, int what);
  * (pending vectors), "x", "sx", "corr" (nroots columns), "diag", "G" (basis x basis, column-major), "prhs" (basis x nrhs), "y" (the
  * coefficients of the last step, basis x roots, then the values of omega given to the Ritz pass; status 1 when no step has finished on the
  * present basis, as after a step that ended at a pole), "target", "counts"; *count = doubles
- * written, status 1 when capacity is smaller. */
+ * written, status 1 when capacity is smaller.  linear_start_complex starts the complex linear mode (A - (shift_re[j] + i shift_im[j])) x_j =
+ * -rhs[j % nrhs] (4 nroots <= max_space and nroots <= 64, status 1 otherwise); linear_iterate then makes its steps, and "x", "sx", "corr"
+ * hold 2 nroots columns (2 j: real part of system j, 2 j + 1: imaginary part), "y" Re y and Im y (basis x roots each), then omega and gamma.
+ * On a state in a real mode every string answers as before. */
 int afesp_test_davidson_create(afesp_ctx* ctx, int64_t n1, int64_t nvec, double w2, int follow, int nroots, int max_space, int r, const double* d,
                                const double* U, const double* V, const double* diag);
 int afesp_test_davidson_destroy(afesp_ctx* ctx);
 int afesp_test_davidson_set_guess(afesp_ctx* ctx, int k, const double* x1, const double* x2);
 int afesp_test_davidson_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int counts[4], int* converged);
 int afesp_test_davidson_linear_start(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shifts);
+int afesp_test_davidson_linear_start_complex(afesp_ctx* ctx, int nrhs, const double* rhs, const double* shift_re, const double* shift_im);
 int afesp_test_davidson_linear_iterate(afesp_ctx* ctx, double tol, double* resnorm, int* flags, int counts[4], int* converged);
 int afesp_test_davidson_get_vector(afesp_ctx* ctx, int k, double* x1, double* x2);
 int afesp_test_davidson_fetch(afesp_ctx* ctx, const char* what, double* out, int64_t capacity, int64_t* count);
