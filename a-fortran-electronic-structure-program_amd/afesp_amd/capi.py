@@ -1049,108 +1049,152 @@ class Engine:
         self._chk(self.L.afesp_ccsd_so_relax_pair_row(self.h, which, out.ctypes.data_as(C.c_void_p), reps, C.byref(ms)))
         return out[:o * v].reshape((o, v), order="F"), ms.value
 
-    # ---- EOM-EE-CCSD excitation energies of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them).  All need a live Lambda
-    # state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes t1 / t2 or lambda
-    eom_nroots = 0
+    # ---- The EOM-CCSD eigenproblems of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them): EE, its left-hand side, and
+    # the IP and EA sectors.  All need a live Lambda state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes
+    # t1 / t2 or lambda, and no call for one problem touches the state of another.  One set of helpers serves them, keyed by kind:
+    # "ee", "left", or the sector of the ipea calls -- EOM_IP (1h + 2h1p: r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v))
+    EOM_IP, EOM_EA = 1, 2
+    _eom_nroots = {}                                                        # kind -> nroots of its last init
 
+    def _eom_shapes(self, kind):
+        o, v = self.so_o, self.so_v
+        if kind in ("ee", "left"):
+            return (o, v), (o, o, v, v)
+        return ((o,), (o, o, v)) if kind == self.EOM_IP else ((v,), (o, v, v))
+
+    def _eom_fn(self, kind, call):
+        """the library's entry `call` of the kind -> (function, its arguments between the context and the call's own)"""
+        if kind == "ee":
+            return getattr(self.L, "afesp_ccsd_so_eom_" + call), ()
+        if kind == "left":
+            return getattr(self.L, "afesp_ccsd_so_eom_" + ("lsigma" if call == "sigma" else "left_" + call)), ()
+        return getattr(self.L, "afesp_ccsd_so_eom_ipea_" + call), (kind,)
+
+    def _eom_stack(self, kind, x1, x2, who):
+        """k vectors with a leading axis, or one vector -> (k, flat x1, flat x2, single)"""
+        sh1, sh2 = self._eom_shapes(kind)
+        x1, x2 = np.asarray(x1, dtype=np.float64), np.asarray(x2, dtype=np.float64)
+        single = x1.ndim == len(sh1)
+        if single:
+            x1, x2 = x1[None], x2[None]
+        k = x1.shape[0]
+        if x1.shape != (k, *sh1) or x2.shape != (k, *sh2):
+            raise ValueError(f"{who}: the vectors do not have the shapes (k,) {sh1} / (k,) {sh2} of this state")
+        return k, np.concatenate([_f(x) for x in x1]), np.concatenate([_f(x) for x in x2]), single
+
+    def _eom_init(self, kind, nroots, max_space):
+        fn, lead = self._eom_fn(kind, "init")
+        self._chk(fn(self.h, *lead, nroots, max_space))
+        self._eom_nroots = {**self._eom_nroots, kind: int(nroots)}
+
+    def _eom_sigma(self, kind, x1, x2, who):
+        sh1, sh2 = self._eom_shapes(kind)
+        k, a1, a2, single = self._eom_stack(kind, x1, x2, who)
+        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
+        fn, lead = self._eom_fn(kind, "sigma")
+        self._chk(fn(self.h, *lead, k, a1, a2, s1, s2))
+        s1 = np.stack([x.reshape(sh1, order="F") for x in s1.reshape(k, -1)])
+        s2 = np.stack([x.reshape(sh2, order="F") for x in s2.reshape(k, -1)])
+        return (s1[0], s2[0]) if single else (s1, s2)
+
+    def _eom_guess(self, kind):
+        fn, lead = self._eom_fn(kind, "guess")
+        self._chk(fn(self.h, *lead))
+
+    def _eom_set_guess(self, kind, k, x1, x2):
+        fn, lead = self._eom_fn(kind, "set_guess")
+        self._chk(fn(self.h, *lead, k, _f(x1), _f(x2)))
+
+    def _eom_iterate(self, kind, tol):
+        n = self._eom_nroots.get(kind, 1)
+        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
+        ns, cv = C.c_int(), C.c_int()
+        fn, lead = self._eom_fn(kind, "iterate")
+        self._chk(fn(self.h, *lead, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
+        return om, rs, fl, ns.value, bool(cv.value)
+
+    def _eom_vector(self, kind, k):
+        sh1, sh2 = self._eom_shapes(kind)
+        x1, x2 = np.zeros(int(np.prod(sh1))), np.zeros(int(np.prod(sh2)))
+        fn, lead = self._eom_fn(kind, "get_vector")
+        self._chk(fn(self.h, *lead, k, x1, x2))
+        return x1.reshape(sh1, order="F"), x2.reshape(sh2, order="F")
+
+    # EOM-EE-CCSD excitation energies
     def so_eom_init(self, nroots, max_space):
-        self._chk(self.L.afesp_ccsd_so_eom_init(self.h, nroots, max_space))
-        self.eom_nroots = int(nroots)
+        self._eom_init("ee", nroots, max_space)
 
     def so_eom_sigma(self, r1, r2):
         """sigma = A r.  r1 (o,v) and r2 (o,o,v,v) for one vector -> (s1, s2); with a leading axis, (k,o,v) and (k,o,o,v,v), k vectors in one
         call -> the same with that axis."""
-        o, v = self.so_o, self.so_v
-        r1, r2 = np.asarray(r1, dtype=np.float64), np.asarray(r2, dtype=np.float64)
-        single = r1.ndim == 2
-        if single:
-            r1, r2 = r1[None], r2[None]
-        k = r1.shape[0]
-        if r1.shape != (k, o, v) or r2.shape != (k, o, o, v, v):
-            raise ValueError("so_eom_sigma: r1 / r2 do not have the shapes (k,) o v / (k,) o o v v of this state")
-        a1, a2 = np.concatenate([_f(x) for x in r1]), np.concatenate([_f(x) for x in r2])
-        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
-        self._chk(self.L.afesp_ccsd_so_eom_sigma(self.h, k, a1, a2, s1, s2))
-        s1 = np.stack([x.reshape((o, v), order="F") for x in s1.reshape(k, o * v)])
-        s2 = np.stack([x.reshape((o, o, v, v), order="F") for x in s2.reshape(k, o * o * v * v)])
-        return (s1[0], s2[0]) if single else (s1, s2)
+        return self._eom_sigma("ee", r1, r2, "so_eom_sigma")
 
     def so_eom_guess(self):
-        self._chk(self.L.afesp_ccsd_so_eom_guess(self.h))
+        self._eom_guess("ee")
 
     def so_eom_set_guess(self, k, r1, r2):
-        self._chk(self.L.afesp_ccsd_so_eom_set_guess(self.h, k, _f(r1), _f(r2)))
+        self._eom_set_guess("ee", k, r1, r2)
 
     def so_eom_iterate(self, tol=1e-8):
         """One Davidson step -> (omega, resnorm, flags, sigma builds so far, converged); flags: bit 0 converged, bit 1 complex"""
-        n = self.eom_nroots
-        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        ns, cv = C.c_int(), C.c_int()
-        self._chk(self.L.afesp_ccsd_so_eom_iterate(self.h, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
-        return om, rs, fl, ns.value, bool(cv.value)
+        return self._eom_iterate("ee", tol)
 
     def so_eom_vector(self, k):
         """Ritz vector k of the last step, <x, x> = sum x1^2 + 1/4 sum x2^2 = 1"""
-        o, v = self.so_o, self.so_v
-        r1, r2 = np.zeros(o * v), np.zeros(o * o * v * v)
-        self._chk(self.L.afesp_ccsd_so_eom_get_vector(self.h, k, r1, r2))
-        return r1.reshape((o, v), order="F"), r2.reshape((o, o, v, v), order="F")
+        return self._eom_vector("ee", k)
 
-    # ---- EOM-EE-CCSD left eigenvectors, reference coupling and the bilinear density (include/afesp.h; afesp_amd.eom drives them).  The
-    # left Davidson state stands beside the right-hand one: no call here touches that, t1 / t2 or lambda
-    eom_left_nroots = 0
-
-    def _so_stack(self, x1, x2, who):
-        """(k,o,v) / (k,o,o,v,v) or one vector -> (k, flat x1, flat x2, single)"""
-        o, v = self.so_o, self.so_v
-        x1, x2 = np.asarray(x1, dtype=np.float64), np.asarray(x2, dtype=np.float64)
-        single = x1.ndim == 2
-        if single:
-            x1, x2 = x1[None], x2[None]
-        k = x1.shape[0]
-        if x1.shape != (k, o, v) or x2.shape != (k, o, o, v, v):
-            raise ValueError(f"{who}: the vectors do not have the shapes (k,) o v / (k,) o o v v of this state")
-        return k, np.concatenate([_f(x) for x in x1]), np.concatenate([_f(x) for x in x2]), single
-
+    # EOM-EE-CCSD left eigenvectors: the left Davidson state stands beside the right-hand one
     def so_eom_lsigma(self, l1, l2):
         """sigma_L = A^T l.  l1 (o,v) and l2 (o,o,v,v) for one vector -> (s1, s2); with a leading axis, k vectors in one call -> the same
         with that axis."""
-        o, v = self.so_o, self.so_v
-        k, a1, a2, single = self._so_stack(l1, l2, "so_eom_lsigma")
-        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
-        self._chk(self.L.afesp_ccsd_so_eom_lsigma(self.h, k, a1, a2, s1, s2))
-        s1 = np.stack([x.reshape((o, v), order="F") for x in s1.reshape(k, o * v)])
-        s2 = np.stack([x.reshape((o, o, v, v), order="F") for x in s2.reshape(k, o * o * v * v)])
-        return (s1[0], s2[0]) if single else (s1, s2)
+        return self._eom_sigma("left", l1, l2, "so_eom_lsigma")
 
     def so_eom_left_init(self, nroots, max_space):
-        self._chk(self.L.afesp_ccsd_so_eom_left_init(self.h, nroots, max_space))
-        self.eom_left_nroots = int(nroots)
+        self._eom_init("left", nroots, max_space)
 
     def so_eom_left_guess(self):
-        self._chk(self.L.afesp_ccsd_so_eom_left_guess(self.h))
+        self._eom_guess("left")
 
     def so_eom_left_set_guess(self, k, l1, l2):
-        self._chk(self.L.afesp_ccsd_so_eom_left_set_guess(self.h, k, _f(l1), _f(l2)))
+        self._eom_set_guess("left", k, l1, l2)
 
     def so_eom_left_iterate(self, tol=1e-8):
         """One Davidson step of the left state -> (omega, resnorm, flags, sigma builds so far, converged)"""
-        n = self.eom_left_nroots
-        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        ns, cv = C.c_int(), C.c_int()
-        self._chk(self.L.afesp_ccsd_so_eom_left_iterate(self.h, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
-        return om, rs, fl, ns.value, bool(cv.value)
+        return self._eom_iterate("left", tol)
 
     def so_eom_left_vector(self, k):
         """Left Ritz vector k of the last step, <x, x> = 1 (biorthonormalise it against the right vectors: afesp_amd.eom)"""
-        o, v = self.so_o, self.so_v
-        l1, l2 = np.zeros(o * v), np.zeros(o * o * v * v)
-        self._chk(self.L.afesp_ccsd_so_eom_left_get_vector(self.h, k, l1, l2))
-        return l1.reshape((o, v), order="F"), l2.reshape((o, o, v, v), order="F")
+        return self._eom_vector("left", k)
 
+    # EOM-IP-CCSD / EOM-EA-CCSD: sector is EOM_IP or EOM_EA; the rules and statuses are those of the EE calls
+    def so_eom_ipea_shapes(self, sector):
+        return self._eom_shapes(sector)
+
+    def so_eom_ipea_init(self, sector, nroots, max_space):
+        self._eom_init(sector, nroots, max_space)
+
+    def so_eom_ipea_sigma(self, sector, r1, r2):
+        """sigma = A r of the sector for one vector -> (s1, s2); with a leading axis, k vectors in one call -> the same with that axis."""
+        return self._eom_sigma(sector, r1, r2, "so_eom_ipea_sigma")
+
+    def so_eom_ipea_guess(self, sector):
+        self._eom_guess(sector)
+
+    def so_eom_ipea_set_guess(self, sector, k, r1, r2):
+        self._eom_set_guess(sector, k, r1, r2)
+
+    def so_eom_ipea_iterate(self, sector, tol=1e-8):
+        """One Davidson step of the sector -> (omega, resnorm, flags, sigma builds so far, converged)"""
+        return self._eom_iterate(sector, tol)
+
+    def so_eom_ipea_vector(self, sector, k):
+        """Ritz vector k of the sector's last step, <x, x> = sum x1^2 + 1/2 sum x2^2 = 1"""
+        return self._eom_vector(sector, k)
+
+    # the reference coupling of right EE vectors and the bilinear density of a left and a right pair: they need the Lambda state only
     def so_eom_ref_coupling(self, r1, r2):
         """c = sum H_ia r_ia + 1/4 sum <ij||ab> r_ijab of one right vector (-> float) or of k vectors (-> array); r0 = c / omega"""
-        k, a1, a2, single = self._so_stack(r1, r2, "so_eom_ref_coupling")
+        k, a1, a2, single = self._eom_stack("ee", r1, r2, "so_eom_ref_coupling")
         c = np.zeros(k)
         self._chk(self.L.afesp_ccsd_so_eom_ref_coupling(self.h, k, a1, a2, c))
         return float(c[0]) if single else c
@@ -1250,57 +1294,6 @@ class Engine:
         self._chk(self.L.afesp_ccsd_so_response_function_complex(self.h, z.size, pairs, out))
         out = out[:2 * z.size * nop * nop]
         return (out[0::2] + 1j * out[1::2]).reshape(z.size, nop, nop)
-
-    # ---- EOM-IP-CCSD / EOM-EA-CCSD of the same state (include/afesp.h; afesp_amd.eom drives them).  sector: EOM_IP (1h + 2h1p:
-    # r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)); the rules and statuses are those of the EE calls above
-    EOM_IP, EOM_EA = 1, 2
-    eom_ipea_nroots = {}                                                    # sector -> nroots of its last so_eom_ipea_init
-
-    def so_eom_ipea_shapes(self, sector):
-        o, v = self.so_o, self.so_v
-        return ((o,), (o, o, v)) if sector == self.EOM_IP else ((v,), (o, v, v))
-
-    def so_eom_ipea_init(self, sector, nroots, max_space):
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_init(self.h, sector, nroots, max_space))
-        self.eom_ipea_nroots = {**self.eom_ipea_nroots, sector: int(nroots)}
-
-    def so_eom_ipea_sigma(self, sector, r1, r2):
-        """sigma = A r of the sector for one vector -> (s1, s2); with a leading axis, k vectors in one call -> the same with that axis."""
-        sh1, sh2 = self.so_eom_ipea_shapes(sector)
-        r1, r2 = np.asarray(r1, dtype=np.float64), np.asarray(r2, dtype=np.float64)
-        single = r1.ndim == 1
-        if single:
-            r1, r2 = r1[None], r2[None]
-        k = r1.shape[0]
-        if r1.shape != (k, *sh1) or r2.shape != (k, *sh2):
-            raise ValueError("so_eom_ipea_sigma: r1 / r2 do not have the shapes of this sector and state")
-        a1, a2 = np.concatenate([_f(x) for x in r1]), np.concatenate([_f(x) for x in r2])
-        s1, s2 = np.zeros_like(a1), np.zeros_like(a2)
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_sigma(self.h, sector, k, a1, a2, s1, s2))
-        s1 = s1.reshape(k, *sh1)
-        s2 = np.stack([x.reshape(sh2, order="F") for x in s2.reshape(k, -1)])
-        return (s1[0], s2[0]) if single else (s1, s2)
-
-    def so_eom_ipea_guess(self, sector):
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_guess(self.h, sector))
-
-    def so_eom_ipea_set_guess(self, sector, k, r1, r2):
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_set_guess(self.h, sector, k, _f(r1), _f(r2)))
-
-    def so_eom_ipea_iterate(self, sector, tol=1e-8):
-        """One Davidson step of the sector -> (omega, resnorm, flags, sigma builds so far, converged)"""
-        n = self.eom_ipea_nroots.get(sector, 1)
-        om, rs, fl = np.zeros(n), np.zeros(n), np.zeros(n, dtype=np.int32)
-        ns, cv = C.c_int(), C.c_int()
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_iterate(self.h, sector, tol, om, rs, fl, C.byref(ns), C.byref(cv)))
-        return om, rs, fl, ns.value, bool(cv.value)
-
-    def so_eom_ipea_vector(self, sector, k):
-        """Ritz vector k of the sector's last step, <x, x> = sum x1^2 + 1/2 sum x2^2 = 1"""
-        sh1, sh2 = self.so_eom_ipea_shapes(sector)
-        r1, r2 = np.zeros(int(np.prod(sh1))), np.zeros(int(np.prod(sh2)))
-        self._chk(self.L.afesp_ccsd_so_eom_ipea_get_vector(self.h, sector, k, r1, r2))
-        return r1, r2.reshape(sh2, order="F")
 
     def do_ccsd_t_spatial_plain(self, t_begin=0, t_end=None):
         """E[T], E(T) only: what plain CCSD(T)_spatial / CCSD[T]_spatial need (no y, no D sums)."""

@@ -14,7 +14,6 @@
 #include "density2_so.h"
 #include "relax_so.h"
 #include "eom_so.h"
-#include "eom_ipea_so.h"
 #include "response_so.h"
 #include "davidson_test.h"
 #include "small_eig.h"
@@ -119,6 +118,47 @@ void report(const StepResult& r, double* energy, double* rms_sq, int* converged)
     if (energy) *energy = r.energy;
     if (rms_sq) *rms_sq = r.rms;
     if (converged) *converged = r.converged;
+}
+
+// what a Davidson step reports, for the iterate entry points
+void davidson_report(const Davidson& E, int conv, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    for (int k = 0; k < E.nroots; ++k) {
+        if (omega) omega[k] = E.omega[k];
+        if (resnorm) resnorm[k] = E.resnorm[k];
+        if (flags) flags[k] = E.flags[k];
+    }
+    if (nsigma) *nsigma = E.nsigma;
+    if (converged) *converged = conv;
+}
+
+// ---- the EOM-CCSD eigenproblems: EE, EE left, IP and EA on one driver (eom_so.h).  An entry point is its name and its kind; those of the
+// ipea family give their sector instead (and EOM_KINDS for the kind), which is checked first, as ever, and chooses the kind.
+// call(cx, state, kind) does the work: the driver's function with the entry point's own arguments, or the step and its report.
+template <class Call>
+int eom_call(afesp_ctx* ctx, const char* who, EomKind kind, const int* sector, Call&& call)
+{
+    return entry(ctx, [&](Context& cx) {
+        if (sector && !so_eom_sector_ok(*sector)) throw Error(1, std::string(who) + ": sector must be AFESP_EOM_IP (1) or AFESP_EOM_EA (2)");
+        if (sector) kind = so_eom_kind_of_sector(*sector);
+        call(cx, ctx->sv.need_so((std::string(who) + ": no spin-orbital CCSD state").c_str()).so, kind);
+    });
+}
+
+template <class... A, class... B>
+int eom_entry(afesp_ctx* ctx, const char* who, EomKind kind, const int* sector, void (*driver)(Context&, SOState&, EomKind, A...), B... args)
+{
+    return eom_call(ctx, who, kind, sector, [&](Context& cx, SOState& so, EomKind k) { driver(cx, so, k, args...); });
+}
+
+int eom_iterate_entry(afesp_ctx* ctx, const char* who, EomKind kind, const int* sector, double tol, double* omega, double* resnorm,
+                      int* flags, int* nsigma, int* converged)
+{
+    return eom_call(ctx, who, kind, sector, [&](Context& cx, SOState& so, EomKind k) {
+        if (!(tol > 0.0)) throw Error(1, std::string(who) + ": tol must be positive");
+        const int conv = so_eom_iterate(cx, so, k, tol);
+        davidson_report(so.eom[k]->d, conv, omega, resnorm, flags, nsigma, converged);
+    });
 }
 
 }  // namespace
@@ -631,54 +671,80 @@ int afesp_ccsd_so_density(afesp_ctx* ctx, double* d, int64_t capacity)
     return entry(ctx, [&](Context& cx) { so_density(cx, ctx->sv.need_so("afesp_ccsd_so_density: no spin-orbital CCSD state").so, d, capacity); });
 }
 
-// ---- EOM-EE-CCSD excitation energies (eom_so.h)
+// ---- the EOM-CCSD eigenproblems (eom_so.h): one-liners over eom_entry / eom_iterate_entry
 int afesp_ccsd_so_eom_init(afesp_ctx* ctx, int nroots, int max_space)
 {
-    return entry(ctx, [&](Context& cx) { so_eom_init(cx, ctx->sv.need_so("afesp_ccsd_so_eom_init: no spin-orbital CCSD state").so, nroots, max_space); });
+    return eom_entry(ctx, "afesp_ccsd_so_eom_init", EOM_KIND_EE, nullptr, so_eom_init, nroots, max_space);
 }
-
 int afesp_ccsd_so_eom_sigma(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* s1, double* s2)
 {
-    return entry(ctx, [&](Context& cx) {
-        so_eom_sigma_host(cx, ctx->sv.need_so("afesp_ccsd_so_eom_sigma: no spin-orbital CCSD state").so, nvec, r1, r2, s1, s2);
-    });
+    return eom_entry(ctx, "afesp_ccsd_so_eom_sigma", EOM_KIND_EE, nullptr, so_eom_sigma_host, nvec, r1, r2, s1, s2);
 }
-
 int afesp_ccsd_so_eom_guess(afesp_ctx* ctx)
 {
-    return entry(ctx, [&](Context& cx) { so_eom_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_guess: no spin-orbital CCSD state").so); });
+    return eom_entry(ctx, "afesp_ccsd_so_eom_guess", EOM_KIND_EE, nullptr, so_eom_guess);
 }
-
 int afesp_ccsd_so_eom_set_guess(afesp_ctx* ctx, int k, const double* r1, const double* r2)
 {
-    return entry(ctx, [&](Context& cx) { so_eom_set_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_set_guess: no spin-orbital CCSD state").so, k, r1, r2); });
+    return eom_entry(ctx, "afesp_ccsd_so_eom_set_guess", EOM_KIND_EE, nullptr, so_eom_set_guess, k, r1, r2);
 }
-
-// what a Davidson step reports, for the three iterate entry points
-static void davidson_report(const Davidson& E, int conv, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
-{
-    for (int k = 0; k < E.nroots; ++k) {
-        if (omega) omega[k] = E.omega[k];
-        if (resnorm) resnorm[k] = E.resnorm[k];
-        if (flags) flags[k] = E.flags[k];
-    }
-    if (nsigma) *nsigma = E.nsigma;
-    if (converged) *converged = conv;
-}
-
 int afesp_ccsd_so_eom_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
 {
-    return entry(ctx, [&](Context& cx) {
-        SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_iterate: no spin-orbital CCSD state").so;
-        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_iterate: tol must be positive");
-        const int conv = so_eom_iterate(cx, so, tol);
-        davidson_report(so.eom->d, conv, omega, resnorm, flags, nsigma, converged);
-    });
+    return eom_iterate_entry(ctx, "afesp_ccsd_so_eom_iterate", EOM_KIND_EE, nullptr, tol, omega, resnorm, flags, nsigma, converged);
 }
-
 int afesp_ccsd_so_eom_get_vector(afesp_ctx* ctx, int k, double* r1, double* r2)
 {
-    return entry(ctx, [&](Context& cx) { so_eom_get_vector(cx, ctx->sv.need_so("afesp_ccsd_so_eom_get_vector: no spin-orbital CCSD state").so, k, r1, r2); });
+    return eom_entry(ctx, "afesp_ccsd_so_eom_get_vector", EOM_KIND_EE, nullptr, so_eom_get_vector, k, r1, r2);
+}
+
+int afesp_ccsd_so_eom_left_init(afesp_ctx* ctx, int nroots, int max_space)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_left_init", EOM_KIND_EE_LEFT, nullptr, so_eom_init, nroots, max_space);
+}
+int afesp_ccsd_so_eom_lsigma(afesp_ctx* ctx, int nvec, const double* l1, const double* l2, double* s1, double* s2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_lsigma", EOM_KIND_EE_LEFT, nullptr, so_eom_sigma_host, nvec, l1, l2, s1, s2);
+}
+int afesp_ccsd_so_eom_left_guess(afesp_ctx* ctx)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_left_guess", EOM_KIND_EE_LEFT, nullptr, so_eom_guess);
+}
+int afesp_ccsd_so_eom_left_set_guess(afesp_ctx* ctx, int k, const double* l1, const double* l2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_left_set_guess", EOM_KIND_EE_LEFT, nullptr, so_eom_set_guess, k, l1, l2);
+}
+int afesp_ccsd_so_eom_left_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    return eom_iterate_entry(ctx, "afesp_ccsd_so_eom_left_iterate", EOM_KIND_EE_LEFT, nullptr, tol, omega, resnorm, flags, nsigma, converged);
+}
+int afesp_ccsd_so_eom_left_get_vector(afesp_ctx* ctx, int k, double* l1, double* l2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_left_get_vector", EOM_KIND_EE_LEFT, nullptr, so_eom_get_vector, k, l1, l2);
+}
+
+int afesp_ccsd_so_eom_ipea_init(afesp_ctx* ctx, int sector, int nroots, int max_space)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_init", EOM_KINDS, &sector, so_eom_init, nroots, max_space);
+}
+int afesp_ccsd_so_eom_ipea_sigma(afesp_ctx* ctx, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_sigma", EOM_KINDS, &sector, so_eom_sigma_host, nvec, r1, r2, s1, s2);
+}
+int afesp_ccsd_so_eom_ipea_guess(afesp_ctx* ctx, int sector)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_guess", EOM_KINDS, &sector, so_eom_guess);
+}
+int afesp_ccsd_so_eom_ipea_set_guess(afesp_ctx* ctx, int sector, int k, const double* r1, const double* r2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_set_guess", EOM_KINDS, &sector, so_eom_set_guess, k, r1, r2);
+}
+int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
+{
+    return eom_iterate_entry(ctx, "afesp_ccsd_so_eom_ipea_iterate", EOM_KINDS, &sector, tol, omega, resnorm, flags, nsigma, converged);
+}
+int afesp_ccsd_so_eom_ipea_get_vector(afesp_ctx* ctx, int sector, int k, double* r1, double* r2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_get_vector", EOM_KINDS, &sector, so_eom_get_vector, k, r1, r2);
 }
 
 int afesp_eig_general(int n, const double* a, int lda, double* wr, double* wi, double* vr) { return eig_general(n, a, lda, wr, wi, vr); }
@@ -745,50 +811,7 @@ int afesp_ccsd_so_relax_pair_row(afesp_ctx* ctx, int which, double* out, int rep
     });
 }
 
-// ---- EOM-EE-CCSD left eigenvectors, reference coupling and the bilinear density (eom_so.h, eom_left_so.hip)
-int afesp_ccsd_so_eom_lsigma(afesp_ctx* ctx, int nvec, const double* l1, const double* l2, double* s1, double* s2)
-{
-    return entry(ctx, [&](Context& cx) {
-        so_eom_lsigma_host(cx, ctx->sv.need_so("afesp_ccsd_so_eom_lsigma: no spin-orbital CCSD state").so, nvec, l1, l2, s1, s2);
-    });
-}
-
-int afesp_ccsd_so_eom_left_init(afesp_ctx* ctx, int nroots, int max_space)
-{
-    return entry(ctx, [&](Context& cx) {
-        so_eom_init(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_init: no spin-orbital CCSD state").so, nroots, max_space, true);
-    });
-}
-
-int afesp_ccsd_so_eom_left_guess(afesp_ctx* ctx)
-{
-    return entry(ctx, [&](Context& cx) { so_eom_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_guess: no spin-orbital CCSD state").so, true); });
-}
-
-int afesp_ccsd_so_eom_left_set_guess(afesp_ctx* ctx, int k, const double* l1, const double* l2)
-{
-    return entry(ctx, [&](Context& cx) {
-        so_eom_set_guess(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_set_guess: no spin-orbital CCSD state").so, k, l1, l2, true);
-    });
-}
-
-int afesp_ccsd_so_eom_left_iterate(afesp_ctx* ctx, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
-{
-    return entry(ctx, [&](Context& cx) {
-        SOState& so = ctx->sv.need_so("afesp_ccsd_so_eom_left_iterate: no spin-orbital CCSD state").so;
-        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_left_iterate: tol must be positive");
-        const int conv = so_eom_iterate(cx, so, tol, true);
-        davidson_report(so.eom_left->d, conv, omega, resnorm, flags, nsigma, converged);
-    });
-}
-
-int afesp_ccsd_so_eom_left_get_vector(afesp_ctx* ctx, int k, double* l1, double* l2)
-{
-    return entry(ctx, [&](Context& cx) {
-        so_eom_get_vector(cx, ctx->sv.need_so("afesp_ccsd_so_eom_left_get_vector: no spin-orbital CCSD state").so, k, l1, l2, true);
-    });
-}
-
+// ---- EOM-EE-CCSD reference coupling and the bilinear density (eom_so.h, eom_left_so.hip)
 int afesp_ccsd_so_eom_ref_coupling(afesp_ctx* ctx, int nvec, const double* r1, const double* r2, double* c)
 {
     return entry(ctx, [&](Context& cx) {
@@ -871,50 +894,6 @@ int afesp_ccsd_so_response_function_complex(afesp_ctx* ctx, int nfreq, const dou
 int afesp_lu_solve_complex(int n, double* a, int lda, int nrhs, double* b, int ldb, double floor)
 {
     return lu_solve_complex(n, a, lda, nrhs, b, ldb, floor);
-}
-
-// ---- EOM-IP-CCSD and EOM-EA-CCSD (eom_ipea_so.h)
-static SOState& ipea_state(afesp_ctx* ctx, int sector, const char* who)
-{
-    if (!so_eom_sector_ok(sector)) throw Error(1, std::string(who) + ": sector must be AFESP_EOM_IP (1) or AFESP_EOM_EA (2)");
-    return ctx->sv.need_so((std::string(who) + ": no spin-orbital CCSD state").c_str()).so;
-}
-
-int afesp_ccsd_so_eom_ipea_init(afesp_ctx* ctx, int sector, int nroots, int max_space)
-{
-    return entry(ctx, [&](Context& cx) { so_eom_ipea_init(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_init"), sector, nroots, max_space); });
-}
-
-int afesp_ccsd_so_eom_ipea_sigma(afesp_ctx* ctx, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2)
-{
-    return entry(ctx, [&](Context& cx) {
-        so_eom_ipea_sigma_host(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_sigma"), sector, nvec, r1, r2, s1, s2);
-    });
-}
-
-int afesp_ccsd_so_eom_ipea_guess(afesp_ctx* ctx, int sector)
-{
-    return entry(ctx, [&](Context& cx) { so_eom_ipea_guess(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_guess"), sector); });
-}
-
-int afesp_ccsd_so_eom_ipea_set_guess(afesp_ctx* ctx, int sector, int k, const double* r1, const double* r2)
-{
-    return entry(ctx, [&](Context& cx) { so_eom_ipea_set_guess(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_set_guess"), sector, k, r1, r2); });
-}
-
-int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma, int* converged)
-{
-    return entry(ctx, [&](Context& cx) {
-        SOState& so = ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_iterate");
-        if (!(tol > 0.0)) throw Error(1, "afesp_ccsd_so_eom_ipea_iterate: tol must be positive");
-        const int conv = so_eom_ipea_iterate(cx, so, sector, tol);
-        davidson_report(so.ipea[sector - 1]->d, conv, omega, resnorm, flags, nsigma, converged);
-    });
-}
-
-int afesp_ccsd_so_eom_ipea_get_vector(afesp_ctx* ctx, int sector, int k, double* r1, double* r2)
-{
-    return entry(ctx, [&](Context& cx) { so_eom_ipea_get_vector(cx, ipea_state(ctx, sector, "afesp_ccsd_so_eom_ipea_get_vector"), sector, k, r1, r2); });
 }
 
 int64_t afesp_ccsd_so_t_ntriples(int64_t nocc) { return so_triples_count((int)nocc); }

@@ -9,7 +9,7 @@ namespace afesp {
 
 struct SOLambda;   // lambda_so.h
 struct SOEom;      // eom_so.h
-struct SOEomX;     // eom_ipea_so.h
+enum EomKind { EOM_KIND_EE = 0, EOM_KIND_EE_LEFT, EOM_KIND_IP, EOM_KIND_EA, EOM_KINDS };   // the EOM eigenproblems and their slots below
 struct SOResponse; // response_so.h
 
 struct SOState : DiisRing {
@@ -38,9 +38,7 @@ struct SOState : DiisRing {
     Tensor f_ov, f_oo, f_vv;
     double f_offdiag = 0.0;          // largest |f_oo|, |f_vv| off-diagonal element: (T) is defined for (semi)canonical orbitals only
     SOLambda* lam = nullptr;         // the Lambda state made by so_lambda_init for one amp_epoch (lambda_so.h); released by so_free
-    SOEom* eom = nullptr;            // the EOM state that borrows lam's H-bar elements (eom_so.h); released wherever lam is
-    SOEom* eom_left = nullptr;       // the left-hand Davidson state beside it (eigenvectors of A^T); released with it
-    SOEomX* ipea[2] = {nullptr, nullptr};   // ... and those of the EOM-IP and EOM-EA sectors (eom_ipea_so.h), released with it
+    SOEom* eom[EOM_KINDS] = {};      // the EOM states that borrow lam's H-bar elements, one per kind (eom_so.h); released wherever lam is
     SOResponse* resp = nullptr;      // the linear-response state beside them (response_so.h), released with it
 };
 
@@ -70,8 +68,7 @@ void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out)
 // xa(ij, ef) = x(i,j,e,f) for i < j, e < f with leading dimension lad_na: so_ladder_bare's packer, into a buffer of the caller's
 void so_pair_pack(Context& cx, SOState& s, const Tensor& x, double* xa);
 void so_lambda_free(Context& cx, SOState& s);     // lambda_so.hip (releases the EOM state too: it borrows from the Lambda state)
-void so_eom_free(Context& cx, SOState& s);        // eom_so.hip
-void so_eom_ipea_free(Context& cx, SOState& s);   // eom_ipea_so.hip
+void so_eom_free(Context& cx, SOState& s);        // eom_so.hip (every kind)
 void so_response_free(Context& cx, SOState& s);   // response_so.hip
 // (T): contribution of the triples i<j<k with flat index in [t_begin, t_end) to E_T (ccsd.f90:1910)
 int64_t so_triples_count(int o);

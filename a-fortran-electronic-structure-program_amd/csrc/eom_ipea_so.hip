@@ -136,29 +136,6 @@ __global__ void ipea_unit_kernel(double* x, int64_t nvec, int64_t ip, int64_t im
     }
 }
 
-const char* sector_name(int sector) { return sector == EOM_SECTOR_IP ? "EOM-IP" : "EOM-EA"; }
-
-void need_plain(Context& cx)
-{
-    if (cx.rec) throw Error(1, "so_eom_ipea: the EOM equations are not part of a recorded (launch-fused) sequence");
-}
-
-void sector_sizes(const SOState& s, int sector, int64_t* n1, int64_t* n2, int64_t* nunique)
-{
-    const int64_t O = s.o, V = s.v;
-    if (sector == EOM_SECTOR_IP) { *n1 = O; *n2 = O * O * V; *nunique = O + (O * (O - 1) / 2) * V; }
-    else { *n1 = V; *n2 = O * V * V; *nunique = V + O * (V * (V - 1) / 2); }
-}
-
-void free_one(Context& cx, SOState& s, int sector)
-{
-    SOEomX*& E = s.ipea[sector - 1];
-    if (!E) return;
-    davidson_free(cx, E->d);
-    delete E;
-    E = nullptr;
-}
-
 // W(i,a,b) = sum_{e<f} <ab||ef> r(i,e,f) = 1/2 sum_ef: the bare ladder over the antisymmetric pair (e,f) against the pair-form va the T
 // iteration built at init, in that iteration's own pair buffers ta / pa and with its offset table -- r is packed as ra(i, ef) on ta's
 // leading dimension, a tall x skinny product M = K = v (v - 1) / 2, N = o.  That needs o <= o (o - 1) / 2, so that r fills rows of ta the T
@@ -198,17 +175,15 @@ void ea_ladder_bare(Context& cx, SOState& s, const Tensor& r2, const Tensor& W)
 
 void preload_eom_ipea_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(ipea_diag_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
-    first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
-    (void)hipGetLastError();
-}
-
-static void preload_once()
-{
-    static const bool loaded = (preload_eom_ipea_so(), true);
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(ipea_diag_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
     (void)loaded;
 }
 
@@ -223,58 +198,11 @@ double so_eom_ipea_bytes(int64_t o, int64_t v, int sector, int nroots, int max_s
     return davidson_bytes(nvec, nroots, max_space) + 8.0 * (scratch + 2.0 * nvec);
 }
 
-void so_eom_ipea_free(Context& cx, SOState& s)
-{
-    free_one(cx, s, EOM_SECTOR_IP);
-    free_one(cx, s, EOM_SECTOR_EA);
-}
-
-SOEomX& so_eom_ipea_need(SOState& s, int sector, const char* who)
-{
-    so_lambda_need(s, who);
-    SOEomX* E = s.ipea[sector - 1];
-    if (!E || E->d.epoch != s.amp_epoch)
-        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no " + sector_name(sector) +
-                                          " state for the live Lambda state (call afesp_ccsd_so_eom_ipea_init first)");
-    return *E;
-}
-
-void so_eom_ipea_init(Context& cx, SOState& s, int sector, int nroots, int max_space)
-{
-    need_plain(cx);
-    SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ipea_init");
-    int64_t n1, n2, nunique;
-    sector_sizes(s, sector, &n1, &n2, &nunique);
-    const int64_t nvec = n1 + n2;
-    if (nroots < 1 || (int64_t)nroots > nunique)
-        throw Error(1, "afesp_ccsd_so_eom_ipea_init: nroots must be in 1 .. " + std::to_string(nunique) + " (the unique amplitudes of the " +
-                           sector_name(sector) + " sector)");
-    if ((int64_t)max_space < 2 * (int64_t)nroots || max_space > 4096)
-        throw Error(1, "afesp_ccsd_so_eom_ipea_init: max_space must be in 2 nroots .. 4096");
-    free_one(cx, s, sector);
-    if (!cx.fits(so_eom_ipea_bytes(s.o, s.v, sector, nroots, max_space)))
-        throw Error(1, std::string("afesp_ccsd_so_eom_ipea_init: the ") + sector_name(sector) + " state of this system (" + std::to_string(max_space) +
-                           " basis vectors) does not fit the free device memory");
-    preload_once();
-    s.ipea[sector - 1] = new SOEomX();
-    SOEomX& E = *s.ipea[sector - 1];
-    try {
-        E.sector = sector;
-        davidson_alloc(cx, E.d, n1, nvec, 0.5, false, nroots, max_space,
-                       [&](double* diag) { LAUNCH(ipea_diag_kernel, grid_for(nvec), diag, sector, s.e, s.lev, s.o, s.v, nvec); });
-        E.d.epoch = L.epoch;
-        cx.sync();
-    } catch (...) {
-        try { cx.quiesce(); free_one(cx, s, sector); } catch (...) {}
-        throw;
-    }
-}
-
 void so_eom_ipea_sigma(Context& cx, SOState& s, int sector, const double* r, double* sigma)
 {
-    need_plain(cx);
+    so_eom_need_plain(cx);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ipea_sigma");
-    preload_once();
+    preload_eom_ipea_so();
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
                  const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
     const int o = s.o, v = s.v;
@@ -328,81 +256,37 @@ void so_eom_ipea_sigma(Context& cx, SOState& s, int sector, const double* r, dou
     }
 }
 
-void so_eom_ipea_sigma_host(Context& cx, SOState& s, int sector, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+void so_eom_ipea_fill_diag(Context& cx, SOState& s, int sector, double* diag)
 {
-    need_plain(cx);
-    so_lambda_need(s, "afesp_ccsd_so_eom_ipea_sigma");
-    if (nvec < 1 || !r1 || !r2 || !s1 || !s2) throw Error(1, "afesp_ccsd_so_eom_ipea_sigma: nvec < 1 or a NULL vector");
-    int64_t n1, n2, nunique;
-    sector_sizes(s, sector, &n1, &n2, &nunique);
-    double* r = cx.scratch("ipea_r_stage", n1 + n2);
-    double* sg = cx.scratch("ipea_s_stage", n1 + n2);
-    for (int k = 0; k < nvec; ++k) {
-        AFESP_HIP(hipMemcpyAsync(r, r1 + n1 * k, sizeof(double) * n1, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(r + n1, r2 + n2 * k, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
-        so_eom_ipea_sigma(cx, s, sector, r, sg);
-        AFESP_HIP(hipMemcpyAsync(s1 + n1 * k, sg, sizeof(double) * n1, hipMemcpyDeviceToHost, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(s2 + n2 * k, sg + n1, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
-    }
+    const int64_t O = s.o, V = s.v, nvec = sector == EOM_SECTOR_IP ? O + O * O * V : V + O * V * V;
+    LAUNCH(ipea_diag_kernel, grid_for(nvec), diag, sector, s.e, s.lev, s.o, s.v, nvec);
 }
 
-void so_eom_ipea_guess(Context& cx, SOState& s, int sector)
+void so_eom_ipea_unique(const SOState& s, int sector, std::vector<int64_t>& idx)
 {
-    need_plain(cx);
-    Davidson& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_guess").d;
-    const int64_t O = s.o, V = s.v, n1 = E.n1;
-    std::vector<double> D(E.nvec);
-    AFESP_HIP(hipMemcpyAsync(D.data(), E.diag, sizeof(double) * E.nvec, hipMemcpyDeviceToHost, cx.stream));
-    cx.sync();
-    // the unique amplitudes by ascending diagonal, ties by flat index
-    std::vector<int64_t> idx;
-    for (int64_t x = 0; x < n1; ++x) idx.push_back(x);
+    const int64_t O = s.o, V = s.v;
     if (sector == EOM_SECTOR_IP) {
         for (int64_t a = 0; a < V; ++a)
             for (int64_t j = 0; j < O; ++j)
-                for (int64_t i = 0; i < j; ++i) idx.push_back(n1 + i + O * (j + O * a));
+                for (int64_t i = 0; i < j; ++i) idx.push_back(O + i + O * (j + O * a));
     } else {
         for (int64_t b = 0; b < V; ++b)
             for (int64_t a = 0; a < b; ++a)
-                for (int64_t i = 0; i < O; ++i) idx.push_back(n1 + i + O * (a + V * b));
+                for (int64_t i = 0; i < O; ++i) idx.push_back(V + i + O * (a + V * b));
     }
-    const int nr = E.nroots;
-    std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return D[p] != D[q] ? D[p] < D[q] : p < q; });
-    davidson_restart(E);
-    for (int k = 0; k < nr; ++k) {
-        const int64_t ip = idx[k];
-        int64_t im = -1;
-        if (ip >= n1) {
-            const int64_t y = ip - n1;
-            if (sector == EOM_SECTOR_IP) im = n1 + (y / O) % O + O * (y % O + O * (y / (O * O)));
-            else im = n1 + y % O + O * (y / (O * V) + V * ((y / O) % V));
-        }
-        LAUNCH(ipea_unit_kernel, grid_for(E.nvec), E.pend + E.nvec * k, E.nvec, ip, im, sector, s.o, s.v);
+}
+
+void so_eom_ipea_unit(Context& cx, SOState& s, int sector, double* x, int64_t p)
+{
+    const bool ip = sector == EOM_SECTOR_IP;
+    const int64_t O = s.o, V = s.v, n1 = ip ? O : V, nvec = n1 + (ip ? O * O * V : O * V * V);
+    int64_t im = -1;   // the image with the pair exchanged
+    if (p >= n1) {
+        const int64_t y = p - n1;
+        if (ip) im = n1 + (y / O) % O + O * (y % O + O * (y / (O * O)));
+        else im = n1 + y % O + O * (y / (O * V) + V * ((y / O) % V));
     }
-    E.npend = nr;
-    cx.sync();
-}
-
-static const char* const ipea_prefix ="afesp_ccsd_so_eom_ipea_";
-
-void so_eom_ipea_set_guess(Context& cx, SOState& s, int sector, int k, const double* r1, const double* r2)
-{
-    need_plain(cx);
-    davidson_set_pending_from_host(cx, so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_set_guess").d, ipea_prefix, k, r1, r2);
-}
-
-int so_eom_ipea_iterate(Context& cx, SOState& s, int sector, double tol)
-{
-    need_plain(cx);
-    Davidson& E = so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_iterate").d;
-    return davidson_iterate(cx, E, ipea_prefix, tol, [&](const double* r, double* sigma) { so_eom_ipea_sigma(cx, s, sector, r, sigma); });
-}
-
-void so_eom_ipea_get_vector(Context& cx, SOState& s, int sector, int k, double* r1, double* r2)
-{
-    need_plain(cx);
-    davidson_get_vector(cx, so_eom_ipea_need(s, sector, "afesp_ccsd_so_eom_ipea_get_vector").d, ipea_prefix, k, r1, r2);
+    LAUNCH(ipea_unit_kernel, grid_for(nvec), x, nvec, p, im, sector, s.o, s.v);
 }
 
 }  // namespace afesp

@@ -74,17 +74,6 @@ __global__ void eom_density_assemble_kernel(double* D, const double* doo, const 
     }
 }
 
-void need_plain(Context& cx)
-{
-    if (cx.rec) throw Error(1, "so_eom: the EOM equations are not part of a recorded (launch-fused) sequence");
-}
-
-void preload_once()
-{
-    static const bool loaded = (preload_eom_left_so(), true);
-    (void)loaded;
-}
-
 // G_vv / G_oo of (x2, l2) into buffers of the caller: G_ae = -1/2 x_mnef l_mnaf, G_mi = 1/2 x_mnef l_inef
 void build_G(Context& cx, const Tensor& x2, const Tensor& l2, const Tensor& Gvv, const Tensor& Goo)
 {
@@ -105,10 +94,14 @@ void wdot(Context& cx, double* out, const double* a1, const double* a2, const do
 
 void preload_eom_left_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(eom_lsigma_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_wdot_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_density_assemble_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(eom_lsigma_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(eom_wdot_kernel));
+        first_use_touch(reinterpret_cast<const void*>(eom_density_assemble_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
 }
 
 double so_eom_left_bytes(int64_t o, int64_t v, int nroots, int max_space)
@@ -121,9 +114,9 @@ double so_eom_left_bytes(int64_t o, int64_t v, int nroots, int max_space)
 
 void so_eom_lsigma(Context& cx, SOState& s, const double* l, double* sigma)
 {
-    need_plain(cx);
+    so_eom_need_plain(cx);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_lsigma");
-    preload_once();
+    preload_eom_left_so();
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
                  const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
     const int o = s.o, v = s.v;
@@ -169,30 +162,12 @@ void so_eom_lsigma(Context& cx, SOState& s, const double* l, double* sigma)
     LAUNCH(eom_lsigma_assemble_kernel, grid_for(o2v2), sigma + ov, sigma, lad.d, AB.d, A.d, Bm.d, l2.d, l1.d, L.Hov.d, s.D2.d, s.D1.d, o, v);
 }
 
-void so_eom_lsigma_host(Context& cx, SOState& s, int nvec, const double* l1, const double* l2, double* s1, double* s2)
-{
-    need_plain(cx);
-    so_lambda_need(s, "afesp_ccsd_so_eom_lsigma");
-    if (nvec < 1 || !l1 || !l2 || !s1 || !s2) throw Error(1, "afesp_ccsd_so_eom_lsigma: nvec < 1 or a NULL vector");
-    const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
-    double* l = cx.scratch("eom_r_stage", ov + o2v2);
-    double* sg = cx.scratch("eom_s_stage", ov + o2v2);
-    for (int k = 0; k < nvec; ++k) {
-        AFESP_HIP(hipMemcpyAsync(l, l1 + ov * k, sizeof(double) * ov, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(l + ov, l2 + o2v2 * k, sizeof(double) * o2v2, hipMemcpyHostToDevice, cx.stream));
-        so_eom_lsigma(cx, s, l, sg);
-        AFESP_HIP(hipMemcpyAsync(s1 + ov * k, sg, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(s2 + o2v2 * k, sg + ov, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
-    }
-}
-
 void so_eom_ref_coupling(Context& cx, SOState& s, int nvec, const double* r1, const double* r2, double* c)
 {
-    need_plain(cx);
+    so_eom_need_plain(cx);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ref_coupling");
     if (nvec < 1 || !r1 || !r2 || !c) throw Error(1, "afesp_ccsd_so_eom_ref_coupling: nvec < 1 or a NULL vector");
-    preload_once();
+    preload_eom_left_so();
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
     double* r = cx.scratch("eom_r_stage", ov + o2v2);
     double* out = cx.scratch("eoml_sum", 1);
@@ -208,7 +183,7 @@ void so_eom_ref_coupling(Context& cx, SOState& s, int nvec, const double* r1, co
 void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const double* l2h, double r0, const double* r1h, const double* r2h,
                     double* d_host, int64_t capacity)
 {
-    need_plain(cx);
+    so_eom_need_plain(cx);
     so_lambda_need(s, "afesp_ccsd_so_eom_density");
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V, ov = O * V, o2v2 = O * O * V * V;
@@ -217,7 +192,7 @@ void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const
     if (!d_host || capacity < N * N)
         throw Error(LAMBDA_ERR_CAPACITY, "afesp_ccsd_so_eom_density: the buffer holds " + std::to_string(d_host ? capacity : 0) +
                                              " doubles, the density needs (o + v)^2 = " + std::to_string(N * N));
-    preload_once();
+    preload_eom_left_so();
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
                  const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
     const bool hasl = l1h != nullptr, hasr = r1h != nullptr;

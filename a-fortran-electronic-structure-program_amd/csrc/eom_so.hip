@@ -1,8 +1,11 @@
 // eom_so.hip -- EOM-EE-CCSD on the spin-orbital CCSD state (eom_so.h): the sigma build sigma(r) = A r, term by term in
 // the letters of tests/np_eom.py (sigma_explicit) over the H-bar elements of the live Lambda state, the diagonal and the guesses, for the
-// block Davidson iteration of davidson_so.h on the non-symmetric A.  Launches are plain call-by-call ones, as Lambda's.
+// block Davidson iteration of davidson_so.h on the non-symmetric A; and the one driver of the four EOM eigenproblems (EE, EE left, IP, EA)
+// over a descriptor per kind.  Launches are plain call-by-call ones, as Lambda's.
 #include "device_util.h"
-#include "eom_so.h"
+#include "eom_ipea_so.h"
+
+#include <algorithm>
 
 namespace afesp {
 namespace {
@@ -59,19 +62,23 @@ __global__ void eom_diag_kernel(double* diag, const double* D1, const double* D2
     }
 }
 
-void need_plain(Context& cx)
+}  // namespace
+
+void so_eom_need_plain(Context& cx)
 {
     if (cx.rec) throw Error(1, "so_eom: the EOM equations are not part of a recorded (launch-fused) sequence");
 }
 
-}  // namespace
-
 void preload_eom_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(eom_sigma_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_unit_kernel));
-    first_use_touch(reinterpret_cast<const void*>(eom_diag_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(eom_sigma_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(eom_unit_kernel));
+        first_use_touch(reinterpret_cast<const void*>(eom_diag_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
 }
 
 double so_eom_bytes(int64_t o, int64_t v, int nroots, int max_space)
@@ -82,77 +89,15 @@ double so_eom_bytes(int64_t o, int64_t v, int nroots, int max_space)
     return davidson_bytes(nvec, nroots, max_space) + 8.0 * (4.0 * o2v2 + O * O * O * V + O * O * O * O + V * V + O * O + 2.0 * nvec);
 }
 
-// the right-hand and the left-hand Davidson state are one type and one code: `left` chooses the slot, the sigma build and the names
-static SOEom*& eom_slot(SOState& s, bool left) { return left ? s.eom_left : s.eom; }
-static std::string eom_name(bool left, const char* call = "") { return std::string(left ? "afesp_ccsd_so_eom_left_" : "afesp_ccsd_so_eom_") + call; }
-
-static void eom_free_one(Context& cx, SOState& s, bool left)
-{
-    SOEom*& e = eom_slot(s, left);
-    if (!e) return;
-    davidson_free(cx, e->d);
-    delete e;
-    e = nullptr;
-}
-
-void so_eom_free(Context& cx, SOState& s)
-{
-    eom_free_one(cx, s, false);
-    eom_free_one(cx, s, true);
-}
-
 void so_eom_fill_diag(Context& cx, SOState& s, double* diag)
 {
     const int64_t nvec = (int64_t)s.o * s.v + (int64_t)s.o * s.o * s.v * s.v;
     LAUNCH(eom_diag_kernel, grid_for(nvec), diag, s.D1.d, s.D2.d, s.o, s.v, nvec);
 }
 
-SOEom& so_eom_need(SOState& s, const char* who, bool left)
-{
-    so_lambda_need(s, who);
-    SOEom* e = eom_slot(s, left);
-    if (!e || e->d.epoch != s.amp_epoch)
-        throw Error(LAMBDA_ERR_STALE, std::string(who) + (left ? ": no left EOM state for the live Lambda state (call afesp_ccsd_so_eom_left_init first)"
-                                                               : ": no EOM state for the live Lambda state (call afesp_ccsd_so_eom_init first)"));
-    return *e;
-}
-
-void so_eom_init(Context& cx, SOState& s, int nroots, int max_space, bool left)
-{
-    need_plain(cx);
-    const std::string who = eom_name(left, "init");
-    SOLambda& L = so_lambda_need(s, who.c_str());
-    const int64_t O = s.o, V = s.v, nvec = O * V + O * O * V * V, nunique = O * V + (O * (O - 1) / 2) * (V * (V - 1) / 2);
-    if (nroots < 1 || (int64_t)nroots > nunique)
-        throw Error(1, who + ": nroots must be in 1 .. " + std::to_string(nunique) + " (the unique singles and doubles)");
-    if ((int64_t)max_space < 2 * (int64_t)nroots || max_space > 4096)
-        throw Error(1, who + ": max_space must be in 2 nroots .. 4096");
-    eom_free_one(cx, s, left);
-    if (!cx.fits(left ? so_eom_left_bytes(O, V, nroots, max_space) : so_eom_bytes(O, V, nroots, max_space)))
-        throw Error(1, who + ": the EOM state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
-    static const bool loaded = (preload_eom_so(), true);
-    (void)loaded;
-    if (left) {
-        static const bool loaded_left = (preload_eom_left_so(), true);
-        (void)loaded_left;
-    }
-    eom_slot(s, left) = new SOEom();
-    SOEom& E = *eom_slot(s, left);
-    try {
-        E.left = left;
-        davidson_alloc(cx, E.d, O * V, nvec, 0.25, left, nroots, max_space,
-                       [&](double* diag) { so_eom_fill_diag(cx, s, diag); });
-        E.d.epoch = L.epoch;
-        cx.sync();
-    } catch (...) {
-        try { cx.quiesce(); eom_free_one(cx, s, left); } catch (...) {}
-        throw;
-    }
-}
-
 void so_eom_sigma(Context& cx, SOState& s, const double* r, double* sigma)
 {
-    need_plain(cx);
+    so_eom_need_plain(cx);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_sigma");
     auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
                  const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
@@ -202,79 +147,225 @@ void so_eom_sigma(Context& cx, SOState& s, const double* r, double* sigma)
     LAUNCH(eom_sigma_assemble_kernel, grid_for(o2v2), sigma + ov, sigma, lad.d, AB.d, A.d, Bm.d, r2.d, r1.d, s.D2.d, s.D1.d, o, v);
 }
 
-void so_eom_sigma_host(Context& cx, SOState& s, int nvec, const double* r1, const double* r2, double* s1, double* s2)
-{
-    need_plain(cx);
-    so_lambda_need(s, "afesp_ccsd_so_eom_sigma");
-    if (nvec < 1 || !r1 || !r2 || !s1 || !s2) throw Error(1, "afesp_ccsd_so_eom_sigma: nvec < 1 or a NULL vector");
-    const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
-    double* r = cx.scratch("eom_r_stage", ov + o2v2);
-    double* sg = cx.scratch("eom_s_stage", ov + o2v2);
-    for (int k = 0; k < nvec; ++k) {
-        AFESP_HIP(hipMemcpyAsync(r, r1 + ov * k, sizeof(double) * ov, hipMemcpyHostToDevice, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(r + ov, r2 + o2v2 * k, sizeof(double) * o2v2, hipMemcpyHostToDevice, cx.stream));
-        so_eom_sigma(cx, s, r, sg);
-        AFESP_HIP(hipMemcpyAsync(s1 + ov * k, sg, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
-        AFESP_HIP(hipMemcpyAsync(s2 + o2v2 * k, sg + ov, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
-        cx.sync();
-    }
-}
+// ---- the driver of the four eigenproblems (eom_so.h).  What differs per kind, and nothing else:
+namespace {
 
-void so_eom_guess(Context& cx, SOState& s, bool left)
+struct EomProblem {
+    std::string prefix;              // of the kind's C entry points: messages name prefix + "init", "guess", "iterate", ...
+    const char* state;               // "no <state> state for the live Lambda state"
+    const char* space;               // what bounds nroots
+    const char* sigma_entry;         // the host sigma entry
+    const char *r_stage, *s_stage;   // ... and its staging buffers (Context::scratch caches by name: kinds of different lengths keep their own)
+    int64_t n1, n2, nunique;
+    double w2;                       // weight of the n2 elements in the metric
+    bool follow;                     // the state follows the states of the caller's guesses
+    std::function<double(int nroots, int max_space)> bytes;
+    void (*preload)();
+    std::function<void(Context&, SOState&, double* diag)> fill_diag;
+    std::function<void(Context&, SOState&, const double* r, double* sigma)> sigma;
+    // the guess: the host sort key of every element, the unique elements behind the first n1 in flat-index order, the unit vector on one
+    std::function<std::vector<double>(Context&, SOState&, const Davidson&)> sort_key;
+    std::function<void(const SOState&, std::vector<int64_t>&)> unique;
+    std::function<void(Context&, SOState&, double* x, int64_t p)> unit;
+};
+
+// EE, both sides: -D from the raw D1 / D2, not the unit's symmetrised diagonal -- the two can differ in the last bit, and a tie broken
+// differently is another guess set (-D is the diagonal of A^T too: the same unit vectors)
+std::vector<double> ee_sort_key(Context& cx, SOState& s, const Davidson&)
 {
-    need_plain(cx);
-    Davidson& E = so_eom_need(s, eom_name(left, "guess").c_str(), left).d;
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
-    // (the raw D1 / D2, not the unit's symmetrised diagonal: the two can differ in the last bit, and a tie broken differently is another guess set)
     std::vector<double> D(ov + o2v2);
     AFESP_HIP(hipMemcpyAsync(D.data(), s.D1.d, sizeof(double) * ov, hipMemcpyDeviceToHost, cx.stream));
     AFESP_HIP(hipMemcpyAsync(D.data() + ov, s.D2.d, sizeof(double) * o2v2, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
-    // the unique amplitudes by ascending -D, ties by flat index
-    std::vector<int64_t> idx;
-    idx.reserve(ov + (O * (O - 1) / 2) * (V * (V - 1) / 2));
-    for (int64_t x = 0; x < ov; ++x) idx.push_back(x);
+    for (double& d : D) d = -d;
+    return D;
+}
+
+void ee_unique(const SOState& s, std::vector<int64_t>& idx)
+{
+    const int64_t O = s.o, V = s.v;
     for (int64_t b = 0; b < V; ++b)
         for (int64_t a = 0; a < b; ++a)
             for (int64_t j = 0; j < O; ++j)
-                for (int64_t i = 0; i < j; ++i) idx.push_back(ov + i + O * (j + O * (a + V * b)));
-    const int nr = E.nroots;
-    std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return -D[p] != -D[q] ? -D[p] < -D[q] : p < q; });
-    davidson_restart(E);
-    for (int k = 0; k < nr; ++k) {
-        int64_t i0 = idx[k], i1 = -1, i2 = -1, i3 = -1;
-        if (i0 >= ov) {
-            const int64_t x = i0 - ov, i = x % O, j = (x / O) % O, a = (x / (O * O)) % V, b = x / (O * O * V);
-            i1 = ov + j + O * (i + O * (b + V * a));
-            i2 = ov + j + O * (i + O * (a + V * b));
-            i3 = ov + i + O * (j + O * (b + V * a));
-        }
-        LAUNCH(eom_unit_kernel, grid_for(E.nvec), E.pend + E.nvec * k, E.nvec, i0, i1, i2, i3);
+                for (int64_t i = 0; i < j; ++i) idx.push_back(O * V + i + O * (j + O * (a + V * b)));
+}
+
+void ee_unit(Context& cx, SOState& s, double* x, int64_t i0)
+{
+    const int64_t O = s.o, V = s.v, ov = O * V, nvec = ov + O * O * V * V;
+    int64_t i1 = -1, i2 = -1, i3 = -1;
+    if (i0 >= ov) {
+        const int64_t y = i0 - ov, i = y % O, j = (y / O) % O, a = (y / (O * O)) % V, b = y / (O * O * V);
+        i1 = ov + j + O * (i + O * (b + V * a));
+        i2 = ov + j + O * (i + O * (a + V * b));
+        i3 = ov + i + O * (j + O * (b + V * a));
     }
+    LAUNCH(eom_unit_kernel, grid_for(nvec), x, nvec, i0, i1, i2, i3);
+}
+
+// IP / EA: the unit's own diagonal
+std::vector<double> diag_sort_key(Context& cx, SOState&, const Davidson& E)
+{
+    std::vector<double> D(E.nvec);
+    AFESP_HIP(hipMemcpyAsync(D.data(), E.diag, sizeof(double) * E.nvec, hipMemcpyDeviceToHost, cx.stream));
+    cx.sync();
+    return D;
+}
+
+void preload_eom_both_sides() { preload_eom_so(); preload_eom_left_so(); }
+
+EomProblem eom_problem(const SOState& s, EomKind kind)
+{
+    const int64_t O = s.o, V = s.v;
+    EomProblem P;
+    if (kind == EOM_KIND_EE || kind == EOM_KIND_EE_LEFT) {
+        const bool left = kind == EOM_KIND_EE_LEFT;
+        P.prefix = left ? "afesp_ccsd_so_eom_left_" : "afesp_ccsd_so_eom_";
+        P.state = left ? "left EOM" : "EOM";
+        P.space = "the unique singles and doubles";
+        P.sigma_entry = left ? "afesp_ccsd_so_eom_lsigma" : "afesp_ccsd_so_eom_sigma";
+        P.r_stage = "eom_r_stage"; P.s_stage = "eom_s_stage";
+        P.n1 = O * V; P.n2 = O * O * V * V; P.nunique = O * V + (O * (O - 1) / 2) * (V * (V - 1) / 2);
+        P.w2 = 0.25; P.follow = left;
+        P.bytes = [=](int nroots, int max_space) { return (left ? so_eom_left_bytes : so_eom_bytes)(O, V, nroots, max_space); };
+        P.preload = left ? preload_eom_both_sides : preload_eom_so;
+        P.fill_diag = so_eom_fill_diag;
+        P.sigma = left ? so_eom_lsigma : so_eom_sigma;   // (left: the projected matrix is then <b_p, sigma_L(b_q)>)
+        P.sort_key = ee_sort_key; P.unique = ee_unique; P.unit = ee_unit;
+    } else {
+        const bool ip = kind == EOM_KIND_IP;
+        const int sector = ip ? EOM_SECTOR_IP : EOM_SECTOR_EA;
+        P.prefix = "afesp_ccsd_so_eom_ipea_";
+        P.state = ip ? "EOM-IP" : "EOM-EA";
+        P.space = ip ? "the unique amplitudes of the EOM-IP sector" : "the unique amplitudes of the EOM-EA sector";
+        P.sigma_entry = "afesp_ccsd_so_eom_ipea_sigma";
+        P.r_stage = "ipea_r_stage"; P.s_stage = "ipea_s_stage";
+        P.n1 = ip ? O : V; P.n2 = ip ? O * O * V : O * V * V; P.nunique = ip ? O + (O * (O - 1) / 2) * V : V + O * (V * (V - 1) / 2);
+        P.w2 = 0.5; P.follow = false;
+        P.bytes = [=](int nroots, int max_space) { return so_eom_ipea_bytes(O, V, sector, nroots, max_space); };
+        P.preload = preload_eom_ipea_so;
+        P.fill_diag = [=](Context& cx, SOState& st, double* diag) { so_eom_ipea_fill_diag(cx, st, sector, diag); };
+        P.sigma = [=](Context& cx, SOState& st, const double* r, double* sigma) { so_eom_ipea_sigma(cx, st, sector, r, sigma); };
+        P.sort_key = diag_sort_key;
+        P.unique = [=](const SOState& st, std::vector<int64_t>& idx) { so_eom_ipea_unique(st, sector, idx); };
+        P.unit = [=](Context& cx, SOState& st, double* x, int64_t p) { so_eom_ipea_unit(cx, st, sector, x, p); };
+    }
+    return P;
+}
+
+void eom_free_one(Context& cx, SOState& s, EomKind kind)
+{
+    SOEom*& e = s.eom[kind];
+    if (!e) return;
+    davidson_free(cx, e->d);
+    delete e;
+    e = nullptr;
+}
+
+}  // namespace
+
+void so_eom_free(Context& cx, SOState& s)
+{
+    for (int kind = 0; kind < EOM_KINDS; ++kind) eom_free_one(cx, s, (EomKind)kind);
+}
+
+SOEom& so_eom_need(SOState& s, EomKind kind, const char* who)
+{
+    so_lambda_need(s, who);
+    SOEom* e = s.eom[kind];
+    if (!e || e->d.epoch != s.amp_epoch) {
+        const EomProblem P = eom_problem(s, kind);
+        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no " + P.state + " state for the live Lambda state (call " + P.prefix + "init first)");
+    }
+    return *e;
+}
+
+void so_eom_init(Context& cx, SOState& s, EomKind kind, int nroots, int max_space)
+{
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    const std::string who = P.prefix + "init";
+    SOLambda& L = so_lambda_need(s, who.c_str());
+    if (nroots < 1 || (int64_t)nroots > P.nunique)
+        throw Error(1, who + ": nroots must be in 1 .. " + std::to_string(P.nunique) + " (" + P.space + ")");
+    if ((int64_t)max_space < 2 * (int64_t)nroots || max_space > 4096)
+        throw Error(1, who + ": max_space must be in 2 nroots .. 4096");
+    eom_free_one(cx, s, kind);
+    if (!cx.fits(P.bytes(nroots, max_space)))
+        throw Error(1, who + ": the " + P.state + " state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
+    P.preload();
+    s.eom[kind] = new SOEom();
+    SOEom& E = *s.eom[kind];
+    try {
+        E.kind = kind;
+        davidson_alloc(cx, E.d, P.n1, P.n1 + P.n2, P.w2, P.follow, nroots, max_space, [&](double* diag) { P.fill_diag(cx, s, diag); });
+        E.d.epoch = L.epoch;
+        cx.sync();
+    } catch (...) {
+        try { cx.quiesce(); eom_free_one(cx, s, kind); } catch (...) {}
+        throw;
+    }
+}
+
+void so_eom_sigma_host(Context& cx, SOState& s, EomKind kind, int nvec, const double* r1, const double* r2, double* s1, double* s2)
+{
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    so_lambda_need(s, P.sigma_entry);
+    if (nvec < 1 || !r1 || !r2 || !s1 || !s2) throw Error(1, std::string(P.sigma_entry) + ": nvec < 1 or a NULL vector");
+    const int64_t n1 = P.n1, n2 = P.n2;
+    double* r = cx.scratch(P.r_stage, n1 + n2);
+    double* sg = cx.scratch(P.s_stage, n1 + n2);
+    for (int k = 0; k < nvec; ++k) {
+        AFESP_HIP(hipMemcpyAsync(r, r1 + n1 * k, sizeof(double) * n1, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(r + n1, r2 + n2 * k, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        P.sigma(cx, s, r, sg);
+        AFESP_HIP(hipMemcpyAsync(s1 + n1 * k, sg, sizeof(double) * n1, hipMemcpyDeviceToHost, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(s2 + n2 * k, sg + n1, sizeof(double) * n2, hipMemcpyDeviceToHost, cx.stream));
+        cx.sync();
+    }
+}
+
+void so_eom_guess(Context& cx, SOState& s, EomKind kind)
+{
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    Davidson& E = so_eom_need(s, kind, (P.prefix + "guess").c_str()).d;
+    const std::vector<double> key = P.sort_key(cx, s, E);
+    // the unique amplitudes by ascending key, ties by flat index
+    std::vector<int64_t> idx;
+    idx.reserve(P.nunique);
+    for (int64_t x = 0; x < P.n1; ++x) idx.push_back(x);
+    P.unique(s, idx);
+    const int nr = E.nroots;
+    std::partial_sort(idx.begin(), idx.begin() + nr, idx.end(), [&](int64_t p, int64_t q) { return key[p] != key[q] ? key[p] < key[q] : p < q; });
+    davidson_restart(E);
+    for (int k = 0; k < nr; ++k) P.unit(cx, s, E.pend + E.nvec * k, idx[k]);
     E.npend = nr;
     cx.sync();
 }
 
-void so_eom_set_guess(Context& cx, SOState& s, int k, const double* r1, const double* r2, bool left)
+void so_eom_set_guess(Context& cx, SOState& s, EomKind kind, int k, const double* r1, const double* r2)
 {
-    need_plain(cx);
-    davidson_set_pending_from_host(cx, so_eom_need(s, eom_name(left, "set_guess").c_str(), left).d, eom_name(left), k, r1, r2);
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    davidson_set_pending_from_host(cx, so_eom_need(s, kind, (P.prefix + "set_guess").c_str()).d, P.prefix, k, r1, r2);
 }
 
-int so_eom_iterate(Context& cx, SOState& s, double tol, bool left)
+int so_eom_iterate(Context& cx, SOState& s, EomKind kind, double tol)
 {
-    need_plain(cx);
-    Davidson& E = so_eom_need(s, eom_name(left, "iterate").c_str(), left).d;
-    return davidson_iterate(cx, E, eom_name(left), tol, [&](const double* r, double* sigma) {
-        if (left) so_eom_lsigma(cx, s, r, sigma);   // the projected matrix is then <b_p, sigma_L(b_q)>
-        else so_eom_sigma(cx, s, r, sigma);
-    });
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    Davidson& E = so_eom_need(s, kind, (P.prefix + "iterate").c_str()).d;
+    return davidson_iterate(cx, E, P.prefix, tol, [&](const double* r, double* sigma) { P.sigma(cx, s, r, sigma); });
 }
 
-void so_eom_get_vector(Context& cx, SOState& s, int k, double* r1, double* r2, bool left)
+void so_eom_get_vector(Context& cx, SOState& s, EomKind kind, int k, double* r1, double* r2)
 {
-    need_plain(cx);
-    davidson_get_vector(cx, so_eom_need(s, eom_name(left, "get_vector").c_str(), left).d, eom_name(left), k, r1, r2);
+    so_eom_need_plain(cx);
+    const EomProblem P = eom_problem(s, kind);
+    davidson_get_vector(cx, so_eom_need(s, kind, (P.prefix + "get_vector").c_str()).d, P.prefix, k, r1, r2);
 }
 
 }  // namespace afesp

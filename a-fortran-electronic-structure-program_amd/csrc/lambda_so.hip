@@ -196,8 +196,7 @@ double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr)
 
 void so_lambda_free(Context& cx, SOState& s)
 {
-    so_eom_free(cx, s);   // (it borrows this state's H-bar elements)
-    so_eom_ipea_free(cx, s);
+    so_eom_free(cx, s);   // (they borrow this state's H-bar elements)
     so_response_free(cx, s);
     if (!s.lam) return;
     so_density2_free(cx, *s.lam);

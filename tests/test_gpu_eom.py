@@ -206,7 +206,7 @@ def test_statuses_and_release(eng):
     for nroots, max_space in ((0, 8), (-1, 8), (nunique + 1, 4 * nunique), (3, 5), (2, 5000)):
         with pytest.raises(AfespError, match="status 1: .*(nroots|max_space) must be"):
             eng.so_eom_init(nroots, max_space)
-    eng.eom_nroots = 2
+    eng._eom_nroots = {"ee": 2}
     for call in (lambda: eng.so_eom_guess(), lambda: eng.so_eom_iterate(), lambda: eng.so_eom_vector(0)):
         with pytest.raises(AfespError, match="status 21: .*no EOM state"):
             call()

@@ -216,7 +216,7 @@ def test_statuses_and_release(eng):
         for nroots, max_space in ((0, 8), (-1, 8), (nunique + 1, 4096), (3, 5), (2, 5000)):
             with pytest.raises(AfespError, match="status 1: .*(nroots|max_space) must be"):
                 eng.so_eom_ipea_init(sec, nroots, max_space)
-        eng.eom_ipea_nroots = {sec: 2}
+        eng._eom_nroots = {sec: 2}
         for call in (lambda: eng.so_eom_ipea_guess(sec), lambda: eng.so_eom_ipea_iterate(sec), lambda: eng.so_eom_ipea_vector(sec, 0),
                      lambda: eng.so_eom_ipea_set_guess(sec, 0, *vec[sec])):
             with pytest.raises(AfespError, match="status 21: .*no EOM-(IP|EA) state"):

@@ -239,7 +239,7 @@ def test_statuses_and_release(eng):
         with pytest.raises(AfespError, match="status 1: afesp_ccsd_so_eom_left_init: (nroots|max_space) must be"):
             eng.so_eom_left_init(nroots, max_space)
     eng.so_eom_init(2, 8)                                                   # a right-hand state is no left one
-    eng.eom_left_nroots = 2
+    eng._eom_nroots = {"left": 2}
     for call in (lambda: eng.so_eom_left_guess(), lambda: eng.so_eom_left_iterate(), lambda: eng.so_eom_left_vector(0),
                  lambda: eng.so_eom_left_set_guess(0, *x)):
         with pytest.raises(AfespError, match="status 21: .*no left EOM state"):
