@@ -63,6 +63,10 @@ void so_intermediates(Context& cx, SOState& s);   // build_tau, build_F, build_W
 void so_amplitudes(Context& cx, SOState& s);      // update_amplitudes
 void so_build_W_vvvv(Context& cx, SOState& s);    // W_abef itself (ccsd.f90:852-861), on request: the iteration never forms it
 int so_energy(Context& cx, SOState& s, double e_tol, double t_tol);
+// out[b] = the sum of partial[b nblk .. (b + 1) nblk), b < nout, in a fixed order (device; the final sum of the CCSD and Lambda energy
+// partials); f_ov given: block 0 adds sum_{x < n1} f_ov(x) l1(x) before its tree
+void so_sum2(Context& cx, double* out, const double* partial, int nout, int nblk, const double* f_ov = nullptr, const double* l1 = nullptr,
+             int64_t n1 = 0);
 // out(ijab) = sum_{e<f} x(ijef) <ab||ef> over antisymmetric pairs against va (the bare part of so_amplitudes' ladder; x: tau or lambda_2)
 void so_ladder_bare(Context& cx, SOState& s, const Tensor& x, const Tensor& out);
 // xa(ij, ef) = x(i,j,e,f) for i < j, e < f with leading dimension lad_na: so_ladder_bare's packer, into a buffer of the caller's

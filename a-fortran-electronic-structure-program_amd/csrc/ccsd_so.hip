@@ -1,24 +1,21 @@
 // ccsd_so.hip -- spin-orbital CCSD (Stanton, Gauss, Watts, Bartlett 1991 as coded in the reference's src/ccsd.f90).
 // Every contraction the reference writes as reshape + dgemm or as a loop nest is one label-driven contract() here;
 // the index letters are the reference's.
-#include "ccsd_so.h"
 #include "device_util.h"
 #include "fused.h"
+#include "lambda_so.h"   // (ccsd_so.h, and the contractor() of the spin-orbital units)
 
 #include <cmath>
 
 namespace afesp {
 namespace {
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::min<int64_t>((n + TB - 1) / TB, 65536); }
-#define SO_STRIDE(X_, N_) for (int64_t X_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; X_ < (N_); X_ += (int64_t)gridDim.x * blockDim.x)
-
 // ccsd.f90:108-143,193-207: out(p,q,r,s) = <p+b0 q+b1 || r+b2 s+b3> over spin orbitals x = 2 X + spin, from the packed
 // chemist MO integrals: <pq|rs> = (PR|QS) [sp = sr][sq = ss]
 __global__ void slice_asym_kernel(double* out, const double* packed, int d0, int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {
     const int64_t n = (int64_t)d0 * d1 * d2 * d3;
-    SO_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int p = (int)(x % d0) + b0;
         int64_t y = x / d0;
@@ -46,7 +43,7 @@ __global__ void slice_asym_uhf_kernel(double* out, const double* aa, const doubl
                                       int d1, int d2, int d3, int b0, int b1, int b2, int b3)
 {
     const int64_t n = (int64_t)d0 * d1 * d2 * d3;
-    SO_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int p = tab[(int)(x % d0) + b0];
         int64_t y = x / d0;
@@ -64,9 +61,9 @@ __global__ void slice_asym_uhf_kernel(double* out, const double* aa, const doubl
 __global__ void so_denominators_lev_kernel(double* D1, double* D2, const double* lev, int o, int v)
 {
     const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         D2[x] = lev[i] + lev[j] - lev[o + a] - lev[o + b];
         if (x < n1) D1[x] = lev[(int)(x % o)] - lev[o + (int)(x / o)];
     }
@@ -88,9 +85,9 @@ __global__ void so_denominators_kernel(double* D1, double* D2, const double* e, 
 {
     const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
     const int os = o / 2;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         D2[x] = e[i / 2] + e[j / 2] - e[a / 2 + os] - e[b / 2 + os];
         if (x < n1) D1[x] = e[(int)(x % o) / 2] - e[(int)(x / o) / 2 + os];
     }
@@ -100,10 +97,10 @@ __global__ void so_denominators_kernel(double* D1, double* D2, const double* e, 
 __global__ void so_tau_kernel(double* tau, double* tau_t, const double* t1, const double* t2, int o, int v, double* t1_w)
 {
     const int64_t n2 = (int64_t)o * o * v * v;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
         if (x < (int64_t)o * v) t1_w[x] = t1[x];   // the t1 these intermediates belong to (so_build_W_vvvv forms W_abef from it on request)
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         const double y = t1[i + o * a] * t1[j + o * b] - t1[i + o * b] * t1[j + o * a];
         const double tt = t2[x] + 0.5 * y;
         tau_t[x] = tt;
@@ -115,7 +112,7 @@ __global__ void so_tau_kernel(double* tau, double* tau_t, const double* t1, cons
 __global__ void so_ring_operand_kernel(double* out, const double* t1, const double* t2, int o, int v)
 {
     const int64_t n2 = (int64_t)o * v * o * v;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
         const int n = (int)(x % o), f = (int)((x / o) % v), j = (int)((x / ((int64_t)o * v)) % o), b = (int)(x / ((int64_t)o * v * o));
         out[x] = 0.5 * t2[j + (int64_t)o * (n + (int64_t)o * (f + (int64_t)v * b))] + t1[j + o * f] * t1[n + o * b];
@@ -123,53 +120,39 @@ __global__ void so_ring_operand_kernel(double* out, const double* t1, const doub
 }
 
 // ccsd.f90:1783-1806 (unrestricted branch): out[0] = 1/4 sum <ij||ab> (t2 + 2 t1 t1), out[1] = sum (t2 - t2_old)^2;
-// t2_old <- t2.  One block-partial per block, summed by the caller's k_final_sum.
+// t2_old <- t2.  One block-partial per block, summed by so_sum2.
 __global__ void so_energy_kernel(double* partial, const double* oovv, const double* t1, const double* t2, double* t2_old, int o, int v)
 {
-    __shared__ double red[2][TB / 64];
+    __shared__ double red[2 * 4];
     const int64_t n2 = (int64_t)o * o * v * v;
     double e = 0.0, r = 0.0;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         const double t = t2[x];
         e += 0.25 * oovv[x] * (t + 2.0 * t1[i + o * a] * t1[j + o * b]);
         const double d = t - t2_old[x];
         r += d * d;
         t2_old[x] = t;
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        e += __shfl_down(e, off, 64);
-        r += __shfl_down(r, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = e;
-        red[1][threadIdx.x >> 6] = r;
-    }
-    __syncthreads();
+    double s[2] = {e, r};
+    block_sum_down<2>(s, red);
     if (threadIdx.x == 0) {
-        double se = 0.0, sr = 0.0;
-        for (int w = 0; w < TB / 64; ++w) {
-            se += red[0][w];
-            sr += red[1][w];
-        }
-        partial[blockIdx.x] = se;
-        partial[gridDim.x + blockIdx.x] = sr;
+        partial[blockIdx.x] = s[0];
+        partial[gridDim.x + blockIdx.x] = s[1];
     }
 }
 
-__global__ void so_sum2_kernel(double* out, const double* partial, int nblk)
+// out[b] = sum of partial[b nblk .. (b + 1) nblk) in a fixed order; block 0 adds sum f(x) l1(x) where f is given (the Lambda pseudo energy)
+__global__ void so_sum2_kernel(double* out, const double* partial, int nblk, const double* f_ov, const double* l1, int64_t n1)
 {
     __shared__ double red[TB];
     const double* p = partial + (int64_t)blockIdx.x * nblk;
     double s = 0.0;
     for (int x = threadIdx.x; x < nblk; x += TB) s += p[x];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    if (blockIdx.x == 0 && f_ov)
+        for (int64_t x = threadIdx.x; x < n1; x += TB) s += f_ov[x] * l1[x];
+    block_tree_sum(s, red);
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
@@ -179,12 +162,10 @@ __global__ void so_t2_assemble_kernel(double* t2, const double* r2, const double
                                       const double* D2, int o, int v)
 {
     const int64_t n2 = (int64_t)o * o * v * v;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
-        const int64_t ji = j + (int64_t)o * (i + (int64_t)o * (a + (int64_t)v * b));
-        const int64_t ba = i + (int64_t)o * (j + (int64_t)o * (b + (int64_t)v * a));
-        const int64_t jiba = j + (int64_t)o * (i + (int64_t)o * (b + (int64_t)v * a));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
+        const auto [ji, ba, jiba] = oovv_images(i, j, a, b, o, v);
         const double val = oovv[x] + r2[x] + (AB[x] - AB[ji] - AB[ba] + AB[jiba]) + (A[x] - A[ji]) + (Bm[x] - Bm[ba]);
         t2[x] = val / D2[x];
     }
@@ -193,7 +174,7 @@ __global__ void so_t2_assemble_kernel(double* t2, const double* r2, const double
 // F_oo helper: G(m,i) = F_oo(m,i) + 1/2 Y(i,m)
 __global__ void so_g_kernel(double* G, const double* F_oo, const double* Y, int o)
 {
-    SO_STRIDE(x, (int64_t)o * o)
+    GRID_STRIDE(x, (int64_t)o * o)
     {
         const int m = (int)(x % o), i = (int)(x / o);
         G[x] = F_oo[x] + 0.5 * Y[i + o * m];
@@ -205,7 +186,7 @@ __global__ void so_g_kernel(double* G, const double* F_oo, const double* Y, int 
 __global__ void so_fock_f_kernel(double* F_vv, double* F_oo, double* F_ov, const double* f_vv, const double* f_oo, const double* f_ov, int o, int v)
 {
     const int64_t nvv = (int64_t)v * v, noo = (int64_t)o * o, nov = (int64_t)o * v;
-    SO_STRIDE(x, nvv + noo + nov)
+    GRID_STRIDE(x, nvv + noo + nov)
     {
         if (x < nvv) F_vv[x] += f_vv[x];
         else if (x < nvv + noo) F_oo[x - nvv] += f_oo[x - nvv];
@@ -215,20 +196,16 @@ __global__ void so_fock_f_kernel(double* F_vv, double* F_oo, double* F_ov, const
 // y += x (the f_ia of the T1 residual, Eq. 1)
 __global__ void so_add_kernel(double* y, const double* x, int64_t n)
 {
-    SO_STRIDE(i, n) y[i] += x[i];
+    GRID_STRIDE(i, n) y[i] += x[i];
 }
-// out[0] += sum f_ia t_ia behind so_energy_kernel / so_sum2_kernel: one block, a fixed order
+// out[0] += sum f_ia t_ia behind so_energy_kernel / so_sum2_kernel: one block, a fixed order (a launch of its own: inside so_sum2_kernel
+// the terms would join the partials before the tree, another order of the published energy)
 __global__ void so_energy_fock_kernel(double* out, const double* f_ov, const double* t1, int64_t n)
 {
     __shared__ double red[TB];
     double s = 0.0;
     for (int64_t x = threadIdx.x; x < n; x += TB) s += f_ov[x] * t1[x];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum(s, red);
     if (threadIdx.x == 0) out[0] += red[0];
 }
 // partial[block] = sum f_ia^2 / D_ia (x < o v) + 1/4 sum <ij||ab>^2 / D_ijab over the block's elements; summed by so_sum2_kernel
@@ -237,34 +214,20 @@ __global__ void so_mp2_fock_kernel(double* partial, const double* oovv, const do
     __shared__ double red[TB];
     const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
     double e = 0.0;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
         e += 0.25 * oovv[x] * oovv[x] / D2[x];
         if (x < n1) e += f_ov[x] * f_ov[x] / D1[x];
     }
-    red[threadIdx.x] = e;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum(e, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
-// pairs x < y are numbered y(y-1)/2 + x
-__device__ __forceinline__ void unpair_lt(int64_t p, int& lo, int& hi)
-{
-    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-    while (h * (h - 1) / 2 > p) --h;
-    while ((h + 1) * h / 2 <= p) ++h;
-    hi = (int)h;
-    lo = (int)(p - h * (h - 1) / 2);
-}
 // va(ef, ab) = <ab||ef>, e < f, a < b, leading dimension ka
 __global__ void so_vvvv_asympack_kernel(double* va, const double* vvvv, int v, int64_t ka)
 {
     const int64_t V = v, np = V * (V - 1) / 2;
-    SO_STRIDE(x, np * np)
+    GRID_STRIDE(x, np * np)
     {
         int e, f, a, b;
         unpair_lt(x % np, e, f);
@@ -276,7 +239,7 @@ __global__ void so_vvvv_asympack_kernel(double* va, const double* vvvv, int v, i
 __global__ void so_tau_asympack_kernel(double* ta, const double* tau, int o, int v, int64_t na)
 {
     const int64_t O = o, V = v, npo = O * (O - 1) / 2, npv = V * (V - 1) / 2;
-    SO_STRIDE(x, npo * npv)
+    GRID_STRIDE(x, npo * npv)
     {
         int i, j, e, f;
         unpair_lt(x % npo, i, j);
@@ -288,9 +251,9 @@ __global__ void so_tau_asympack_kernel(double* ta, const double* tau, int o, int
 __global__ void so_ladder_expand_kernel(double* r2, const double* pa, int o, int v, int64_t na)
 {
     const int64_t n2 = (int64_t)o * o * v * v;
-    SO_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         double val = 0.0;
         if (i != j && a != b) {
             const int il = min(i, j), ih = max(i, j), al = min(a, b), ah = max(a, b);
@@ -312,26 +275,22 @@ static void preload_ccsd_so_fock()
     (void)hipGetLastError();
 }
 namespace {
-#define SO_LAUNCH(kernel, n, ...)                                                         \
-    do {                                                                                  \
-        if ((n) > 0) {                                                                    \
-            AFESP_KLAUNCH(kernel, dim3(blocks_for(n)), dim3(TB), 0, cx.stream, __VA_ARGS__); \
-            AFESP_HIP(hipGetLastError());                                                 \
-        }                                                                                 \
+// an element-wise kernel over n elements; nothing where there are none (a state without an occupied or a virtual pair)
+#define SO_LAUNCH(kernel, n, ...)                                                \
+    do {                                                                         \
+        if ((n) > 0) LAUNCH(kernel, grid_for(n, SO_GRID_CAP), __VA_ARGS__);      \
     } while (0)
 
-// ... or, while a call sequence is being recorded for the levelled path (fused.h), noted with the memory it reads and writes
-#define SO_KERNEL(READS, WRITES, kernel, n, ...)                                                                         \
-    do {                                                                                                                 \
-        if (cx.rec) {                                                                                                    \
-            if ((n) > 0)                                                                                                 \
-                cx.rec->opaque(READS, WRITES, [=](Context& c_) {                                                         \
-                    AFESP_KLAUNCH(kernel, dim3(blocks_for(n)), dim3(TB), 0, c_.stream, __VA_ARGS__);                \
-                    AFESP_HIP(hipGetLastError());                                                                        \
-                });                                                                                                      \
-        } else {                                                                                                         \
-            SO_LAUNCH(kernel, n, __VA_ARGS__);                                                                           \
-        }                                                                                                                \
+// ... or, while a call sequence is being recorded for the levelled path (fused.h), noted with the memory it reads and writes (replayed on
+// the context it is given, which LAUNCH reads as `cx`)
+#define SO_KERNEL(READS, WRITES, kernel, n, ...)                                                                                     \
+    do {                                                                                                                             \
+        if (cx.rec) {                                                                                                                \
+            if ((n) > 0)                                                                                                             \
+                cx.rec->opaque(READS, WRITES, [=](Context& cx) { LAUNCH(kernel, grid_for(n, SO_GRID_CAP), __VA_ARGS__); });          \
+        } else {                                                                                                                     \
+            SO_LAUNCH(kernel, n, __VA_ARGS__);                                                                                       \
+        }                                                                                                                            \
     } while (0)
 #define FR(p, n) frange(p, n)
 typedef std::vector<FusedRange> Ranges;
@@ -516,10 +475,8 @@ static double so_init_fock_terms(Context& cx, SOState& s, int n, int na, int nb,
     double e2 = 0.0;
     if (o2v2 > 0) {
         double* partial = cx.scratch("so_energy_partial", 2 * 1024);
-        AFESP_KLAUNCH(so_mp2_fock_kernel, dim3(nblk), dim3(TB), 0, cx.stream, partial, s.oovv.d, s.D2.d, s.f_ov.d, s.D1.d, o, v);
-        AFESP_HIP(hipGetLastError());
-        AFESP_KLAUNCH(so_sum2_kernel, dim3(1), dim3(TB), 0, cx.stream, cx.scal, partial, nblk);
-        AFESP_HIP(hipGetLastError());
+        LAUNCH(so_mp2_fock_kernel, nblk, partial, s.oovv.d, s.D2.d, s.f_ov.d, s.D1.d, o, v);
+        so_sum2(cx, cx.scal, partial, 1, nblk);
         e2 = host_scalars(cx, 1)[0];
     }
     cx.sync();   // (the host images of the Fock blocks)
@@ -553,8 +510,7 @@ void so_free(Context& cx, SOState& s)
 
 void so_intermediates(Context& cx, SOState& s)
 {
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     auto P = [&](double al, const Tensor& in, const char* li, double be, const Tensor& out, const char* lo) {
         permute_add(cx, al, in, li, be, out, lo);
     };
@@ -661,8 +617,7 @@ static void so_ladder(Context& cx, SOState& s)
 
 void so_amplitudes(Context& cx, SOState& s)
 {
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, o2v2 = O * O * V * V;
     // ---- T1, ccsd.f90:931-957
@@ -703,19 +658,20 @@ void so_amplitudes(Context& cx, SOState& s)
               so_t2_assemble_kernel, o2v2, s.t2.d, s.r2.d, s.oovv.d, AB.d, A.d, Bm.d, s.D2.d, o, v);
 }
 
+void so_sum2(Context& cx, double* out, const double* partial, int nout, int nblk, const double* f_ov, const double* l1, int64_t n1)
+{
+    LAUNCH(so_sum2_kernel, nout, out, partial, nblk, f_ov, l1, n1);
+}
+
 int so_energy(Context& cx, SOState& s, double e_tol, double t_tol)
 {
     const int64_t n2 = s.t2.size();
     const int nblk = (int)std::min<int64_t>((n2 + TB - 1) / TB, 1024);
     double* partial = cx.scratch("so_energy_partial", 2 * 1024);
-    AFESP_KLAUNCH(so_energy_kernel, dim3(nblk), dim3(TB), 0, cx.stream, partial, s.oovv.d, s.t1.d, s.t2.d, s.t2_old.d, s.o, s.v);
-    AFESP_HIP(hipGetLastError());
-    AFESP_KLAUNCH(so_sum2_kernel, dim3(2), dim3(TB), 0, cx.stream, cx.scal, partial, nblk);
-    AFESP_HIP(hipGetLastError());
-    if (s.fock) {   // + sum f_ia t_ia
-        AFESP_KLAUNCH(so_energy_fock_kernel, dim3(1), dim3(TB), 0, cx.stream, cx.scal, s.f_ov.d, s.t1.d, (int64_t)s.o * s.v);
-        AFESP_HIP(hipGetLastError());
-    }
+    LAUNCH(so_energy_kernel, nblk, partial, s.oovv.d, s.t1.d, s.t2.d, s.t2_old.d, s.o, s.v);
+    so_sum2(cx, cx.scal, partial, 2, nblk);
+    if (s.fock)   // + sum f_ia t_ia
+        LAUNCH(so_energy_fock_kernel, 1, cx.scal, s.f_ov.d, s.t1.d, (int64_t)s.o * s.v);
     double* h = host_scalars(cx, DIIS_FLAG_SLOT + 1);
     diis_check_flag(cx, h);
     s.energy_old = s.energy;

@@ -46,12 +46,7 @@ __global__ void davidson_panel_kernel(double* partial, const double* B, const do
 __global__ void davidson_final_kernel(double* out, const double* partial, int nblk)
 {
     __shared__ double red[TB];
-    red[threadIdx.x] = (int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum((int)threadIdx.x < nblk ? partial[(int64_t)blockIdx.x * nblk + threadIdx.x] : 0.0, red);
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
@@ -231,7 +226,7 @@ __global__ void davidson_cprecondition_kernel(double* pend, const double* rhs, i
     }
 }
 
-void preload_once()
+void preload_davidson_so()
 {
     static const bool loaded = [] {
         first_use_touch(reinterpret_cast<const void*>(davidson_panel_kernel));
@@ -333,7 +328,7 @@ double davidson_bytes_complex(double nvec, int nsys, int max_space)
 void davidson_alloc(Context& cx, Davidson& E, int64_t n1, int64_t nvec, double w2, bool follow, int nroots, int max_space,
                     const std::function<void(double* diag)>& fill_diag, bool wide)
 {
-    preload_once();
+    preload_davidson_so();
     const int64_t ncol = wide ? 2 * nroots : nroots;
     E.nroots = nroots;
     E.max_space = max_space;

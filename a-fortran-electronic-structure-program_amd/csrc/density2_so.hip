@@ -13,23 +13,12 @@ namespace {
 
 constexpr int D2_MAXBLK = 1024;
 constexpr int D2_NFAM = 6;
-inline unsigned d2_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + TB - 1) / TB, 65536)); }
-#define D2_STRIDE(X_, N_) for (int64_t X_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; X_ < (N_); X_ += (int64_t)gridDim.x * blockDim.x)
-
-__device__ __forceinline__ void d2_unpair_lt(int64_t p, int& lo, int& hi)
-{
-    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-    while (h * (h - 1) / 2 > p) --h;
-    while ((h + 1) * h / 2 <= p) ++h;
-    hi = (int)h;
-    lo = (int)(p - h * (h - 1) / 2);
-}
 
 // oooo(i,j,k,l) = 1/16 [images of Y],  Y(i,j,k,l) = tau_ijef l_klef: the antisymmetriser in each pair and the (ij)<->(kl) symmetriser
 __global__ void d2_oooo_kernel(double* G, const double* Y, int o)
 {
     const int64_t O = o, n = O * O * O * O;
-    D2_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int64_t i = x % O, j = (x / O) % O, k = (x / (O * O)) % O, l = x / (O * O * O);
 #define D2_Y(P_, Q_, R_, S_) Y[(P_) + O * ((Q_) + O * ((R_) + O * (S_)))]
@@ -44,7 +33,7 @@ __global__ void d2_oooo_kernel(double* G, const double* Y, int o)
 __global__ void d2_ooov_kernel(double* G, const double* Cr, const double* Goo, const double* t1, int o, int v)
 {
     const int64_t O = o, n = O * O * O * v;
-    D2_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int64_t i = x % O, j = (x / O) % O, k = (x / (O * O)) % O, a = x / (O * O * O);
         const double c1 = __dsub_rn(Cr[x], 4.0 * __dmul_rn(Goo[i + O * k], t1[j + O * a]));
@@ -57,7 +46,7 @@ __global__ void d2_ooov_kernel(double* G, const double* Cr, const double* Goo, c
 __global__ void d2_oovv_kernel(double* G, const double* Cr, const double* tau, const double* l2, const double* s1, const double* t1, int o, int v)
 {
     const int64_t O = o, V = v, n = O * O * V * V;
-    D2_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int64_t i = x % O, j = (x / O) % O, a = (x / (O * O)) % V, b = x / (O * O * V);
         auto c = [&](int64_t p, int64_t q, int64_t e, int64_t f) {
@@ -72,7 +61,7 @@ __global__ void d2_oovv_kernel(double* G, const double* Cr, const double* tau, c
 __global__ void d2_ovov_kernel(double* G, const double* Cr, const double* l1, const double* t1, int o, int v)
 {
     const int64_t O = o, V = v, n = O * V * O * V;
-    D2_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int64_t i = x % O, a = (x / O) % V, j = (x / (O * V)) % O, b = x / (O * V * O);
         const double c1 = __dsub_rn(Cr[x], 4.0 * __dmul_rn(l1[j + O * a], t1[i + O * b]));
@@ -85,7 +74,7 @@ __global__ void d2_ovov_kernel(double* G, const double* Cr, const double* l1, co
 __global__ void d2_ovvv_kernel(double* G, const double* Cr, const double* Gvv, const double* t1, int o, int v)
 {
     const int64_t O = o, V = v, n = O * V * V * V;
-    D2_STRIDE(x, n)
+    GRID_STRIDE(x, n)
     {
         const int64_t i = x % O, a = (x / O) % V, b = (x / (O * V)) % V, c = x / (O * V * V);
         const double c1 = __dsub_rn(Cr[x], 4.0 * __dmul_rn(Gvv[a + V * c], t1[i + O * b]));
@@ -97,7 +86,7 @@ __global__ void d2_ovvv_kernel(double* G, const double* Cr, const double* Gvv, c
 // ga(p, q) = ga(q, p) = 1/2 (w(p, q) + w(q, p)) in place, one thread per unordered pair of pair indices
 __global__ void d2_pair_symmetrise_kernel(double* ga, int64_t npv, int64_t ka)
 {
-    D2_STRIDE(y, npv * npv)
+    GRID_STRIDE(y, npv * npv)
     {
         const int64_t p = y % npv, q = y / npv;
         if (p > q) continue;
@@ -127,15 +116,15 @@ __global__ void d2_walk_kernel(double* partial, D2Walk w)
 {
     const int64_t O = w.o, V = w.v, N = O + V;
     double sum = 0.0;
-    D2_STRIDE(x, w.n)
+    GRID_STRIDE(x, w.n)
     {
         double val, wt;
         int64_t p, q, r, s;
         if (w.fam == 5) {
             const int64_t npv = V * (V - 1) / 2;
             int a, b, c, d;
-            d2_unpair_lt(x % npv, a, b);
-            d2_unpair_lt(x / npv, c, d);
+            unpair_lt(x % npv, a, b);
+            unpair_lt(x / npv, c, d);
             val = w.G[x % npv + w.ld * (x / npv)];
             wt = w.A ? 0.0 : w.g[x % npv + w.ld * (x / npv)];
             p = O + a; q = O + b; r = O + c; s = O + d;
@@ -166,15 +155,10 @@ __global__ void d2_walk_kernel(double* partial, D2Walk w)
         }
         sum += val * wt;
     }
-    __shared__ double red[TB / 64];
-    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int q = 0; q < TB / 64; ++q) t += red[q];
-        partial[blockIdx.x] = w.weight * t;
-    }
+    __shared__ double red[4];
+    double t[1] = {sum};
+    block_sum_down<1>(t, red);   // (the order of the CCSD and Lambda energies)
+    if (threadIdx.x == 0) partial[blockIdx.x] = w.weight * t[0];
 }
 
 // out[f] = the ordered sum of family f's block partials partial[f D2_MAXBLK .. + nblk[f])
@@ -186,36 +170,11 @@ __global__ void d2_final_sum_kernel(double* out, const double* partial, D2Counts
     const int nblk = cnt.nblk[blockIdx.x];
     double s = 0.0;
     for (int x = threadIdx.x; x < nblk; x += TB) s += p[x];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
+    block_tree_sum(s, red);
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
-#define D2_LAUNCH(kernel, nblocks, ...)                                                     \
-    do {                                                                                    \
-        AFESP_KLAUNCH(kernel, dim3(nblocks), dim3(TB), 0, cx.stream, __VA_ARGS__);          \
-        AFESP_HIP(hipGetLastError());                                                       \
-    } while (0)
-
-void need_plain(Context& cx, const char* who)
-{
-    if (cx.rec) throw Error(1, std::string(who) + ": the two-particle density is not part of a recorded (launch-fused) sequence");
-}
-
-SODensity2& need_built(SOState& s, const char* who)
-{
-    SOLambda& L = so_lambda_need(s, who);
-    if (!L.d2 || L.d2->epoch != s.amp_epoch || L.d2->stamp != L.stamp)
-        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no two-particle density of the current t and lambda (call afesp_ccsd_so_density2_build; "
-                                                         "whatever writes t1 / t2 or l1 / l2 makes an earlier build stale)");
-    return *L.d2;
-}
-
-int64_t pair_count(int64_t n) { return n * (n - 1) / 2; }
+constexpr const char* D2_PLAIN = "the two-particle density is";   // (so_need_plain)
 
 // the six family sums of one walk each, on the host in family order
 void walk_all(Context& cx, SOState& s, SODensity2& G, const double* A, const double* B, double* out)
@@ -234,9 +193,9 @@ void walk_all(Context& cx, SOState& s, SODensity2& G, const double* A, const dou
         cnt.nblk[f] = empty ? 0 : (int)std::min<int64_t>((counts[f] + TB - 1) / TB, D2_MAXBLK);
         if (empty) continue;
         D2Walk w{blocks[f], slices[f], A, B, A ? 1.0 : 0.25 * images[f], counts[f], s.lad_ka, f, o, v};
-        D2_LAUNCH(d2_walk_kernel, cnt.nblk[f], partial + (int64_t)f * D2_MAXBLK, w);
+        LAUNCH(d2_walk_kernel, cnt.nblk[f], partial + (int64_t)f * D2_MAXBLK, w);
     }
-    D2_LAUNCH(d2_final_sum_kernel, D2_NFAM, cx.scal, partial, cnt);
+    LAUNCH(d2_final_sum_kernel, D2_NFAM, cx.scal, partial, cnt);
     const double* h = host_scalars(cx, D2_NFAM);
     for (int f = 0; f < D2_NFAM; ++f) out[f] = h[f];
 }
@@ -245,15 +204,28 @@ void walk_all(Context& cx, SOState& s, SODensity2& G, const double* A, const dou
 
 void preload_density2_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(d2_oooo_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_ooov_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_oovv_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_ovov_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_ovvv_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_pair_symmetrise_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_walk_kernel));
-    first_use_touch(reinterpret_cast<const void*>(d2_final_sum_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(d2_oooo_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_ooov_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_oovv_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_ovov_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_ovvv_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_pair_symmetrise_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_walk_kernel));
+        first_use_touch(reinterpret_cast<const void*>(d2_final_sum_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
+}
+
+SODensity2& so_density2_need(SOState& s, const char* who)
+{
+    SOLambda& L = so_lambda_need(s, who);
+    if (!L.d2 || L.d2->epoch != s.amp_epoch || L.d2->stamp != L.stamp)
+        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no two-particle density of the current t and lambda (call afesp_ccsd_so_density2_build; "
+                                                         "whatever writes t1 / t2 or l1 / l2 makes an earlier build stale)");
+    return *L.d2;
 }
 
 double so_density2_bytes(int64_t o, int64_t v)
@@ -279,7 +251,7 @@ void so_density2_free(Context& cx, SOLambda& L)
 
 void so_density2_build(Context& cx, SOState& s)
 {
-    need_plain(cx, "afesp_ccsd_so_density2_build");
+    so_need_plain(cx, "afesp_ccsd_so_density2_build", D2_PLAIN);
     if (!s.foo_as_published)
         throw Error(LAMBDA_ERR_FOO, "afesp_ccsd_so_density2_build: this state keeps the reference's transposed F_mi term, whose equations have no consistent "
                                     "Lagrangian (initialise it with AFESP_SO_FOO_AS_PUBLISHED=1)");
@@ -300,12 +272,10 @@ void so_density2_build(Context& cx, SOState& s)
             throw;
         }
     }
-    static const bool loaded = (preload_density2_so(), true);
-    (void)loaded;
+    preload_density2_so();
     SODensity2& G = *L.d2;
     G.epoch = G.stamp = -1;   // (stale until the last launch is queued)
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const Tensor &t1 = s.t1, &t2 = s.t2, &l1 = L.l1, &l2 = L.l2, &tau = L.tau;
     // G_vv / G_oo of the current l2 (as so_density)
     C(-0.5, t2, "mnef", l2, "mnaf", 0.0, L.Gvv, "ae");
@@ -321,14 +291,14 @@ void so_density2_build(Context& cx, SOState& s)
     C(1.0, l1, "me", t1, "mb", 0.0, Xvv, "eb");
     C(1.0, l1, "me", t2, "imae", 0.0, s1, "ia");
     // ---- oooo
-    D2_LAUNCH(d2_oooo_kernel, d2_blocks(G.oooo.size()), G.oooo.d, Y.d, o);
+    LAUNCH(d2_oooo_kernel, grid_for(G.oooo.size(), SO_GRID_CAP), G.oooo.d, Y.d, o);
     // ---- ooov: -2 l_ke tau_ijea + Y_ijkm t_ma + 4 M_iakf t_jf + 2 l_ijae t_ke  (- 4 G_ik t_ja in the kernel)
     Tensor c1 = view(cx.scratch("d2_c_ooov", O * O * O * V), {O, O, O, V});
     C(-2.0, l1, "ke", tau, "ijea", 0.0, c1, "ijka");
     C(1.0, Y, "ijkm", t1, "ma", 1.0, c1, "ijka");
     C(4.0, M, "iakf", t1, "jf", 1.0, c1, "ijka");
     C(2.0, l2, "ijae", t1, "ke", 1.0, c1, "ijka");
-    D2_LAUNCH(d2_ooov_kernel, d2_blocks(G.ooov.size()), G.ooov.d, c1.d, L.Goo.d, t1.d, o, v);
+    LAUNCH(d2_ooov_kernel, grid_for(G.ooov.size(), SO_GRID_CAP), G.ooov.d, c1.d, L.Goo.d, t1.d, o, v);
     // ---- ovvv: 2 l_ma tau_imbc + Lt_mnia tau_mnbc - 4 M_icna t_nb + 2 l_imbc t_ma  (- 4 G_ac t_ib in the kernel).  Lt first: the product
     // l_mnae tau_mnbc itself would be the v^4 array times t1
     Tensor c4 = view(cx.scratch("d2_c_ovvv", O * V * V * V), {O, V, V, V});
@@ -336,12 +306,12 @@ void so_density2_build(Context& cx, SOState& s)
     C(1.0, Lt, "mnia", tau, "mnbc", 1.0, c4, "iabc");
     C(-4.0, M, "icna", t1, "nb", 1.0, c4, "iabc");
     C(2.0, l2, "imbc", t1, "ma", 1.0, c4, "iabc");
-    D2_LAUNCH(d2_ovvv_kernel, d2_blocks(G.ovvv.size()), G.ovvv.d, c4.d, L.Gvv.d, t1.d, o, v);
+    LAUNCH(d2_ovvv_kernel, grid_for(G.ovvv.size(), SO_GRID_CAP), G.ovvv.d, c4.d, L.Gvv.d, t1.d, o, v);
     // ---- ovov: -4 M_ibja + 4 Lt_jmia t_mb  (- 4 l_ja t_ib in the kernel)
     Tensor c3 = view(cx.scratch("d2_c_ovov", O * V * O * V), {O, V, O, V});
     permute_add(cx, -4.0, M, "ibja", 0.0, c3, "iajb");
     C(4.0, Lt, "jmia", t1, "mb", 1.0, c3, "iajb");
-    D2_LAUNCH(d2_ovov_kernel, d2_blocks(G.ovov.size()), G.ovov.d, c3.d, l1.d, t1.d, o, v);
+    LAUNCH(d2_ovov_kernel, grid_for(G.ovov.size(), SO_GRID_CAP), G.ovov.d, c3.d, l1.d, t1.d, o, v);
     // ---- oovv: -2 X_mj t_imab + 2 X_eb tau_ijea - 2 G_in tau_njab + 2 G_fb tau_ijaf + 1/4 Y_ijmn tau_mnab + 2 M_ibnf t_njaf + 4 (M_ibnf t_jf) t_na
     // (+ tau + l2 + 4 s_ia t_jb in the kernel)
     Tensor c2 = view(cx.scratch("d2_c_oovv", O * O * V * V), {O, O, V, V});
@@ -353,7 +323,7 @@ void so_density2_build(Context& cx, SOState& s)
     C(0.25, Y, "ijmn", tau, "mnab", 1.0, c2, "ijab");
     C(2.0, M, "ibnf", t2, "njaf", 1.0, c2, "ijab");
     C(4.0, Mt, "ibnj", t1, "na", 1.0, c2, "ijab");
-    D2_LAUNCH(d2_oovv_kernel, d2_blocks(G.oovv.size()), G.oovv.d, c2.d, tau.d, l2.d, s1.d, t1.d, o, v);
+    LAUNCH(d2_oovv_kernel, grid_for(G.oovv.size(), SO_GRID_CAP), G.oovv.d, c2.d, tau.d, l2.d, s1.d, t1.d, o, v);
     // ---- vvvv, pair form only: w(ab, cd) = sum_{i<j} l_ijab tau_ijcd, one product with K = o (o - 1) / 2 on the packed operands, then
     // ga = 1/2 (w + w^T) in place
     if (npv > 0) {
@@ -368,7 +338,7 @@ void so_density2_build(Context& cx, SOState& s)
             LA.stride[1] = TA.stride[1] = na;
             GA.stride[1] = ka;
             C(1.0, LA, "kp", TA, "kq", 0.0, GA, "pq");
-            D2_LAUNCH(d2_pair_symmetrise_kernel, d2_blocks(npv * npv), G.ga, npv, ka);
+            LAUNCH(d2_pair_symmetrise_kernel, grid_for(npv * npv, SO_GRID_CAP), G.ga, npv, ka);
         }
     }
     cx.sync();
@@ -378,9 +348,9 @@ void so_density2_build(Context& cx, SOState& s)
 
 void so_density2_get(Context& cx, SOState& s, const char* name, double* out, int64_t capacity)
 {
-    need_plain(cx, "afesp_ccsd_so_density2_get");
+    so_need_plain(cx, "afesp_ccsd_so_density2_get", D2_PLAIN);
     if (!name || !out) throw Error(1, "afesp_ccsd_so_density2_get: NULL argument");
-    SODensity2& G = need_built(s, "afesp_ccsd_so_density2_get");
+    SODensity2& G = so_density2_need(s, "afesp_ccsd_so_density2_get");
     const int64_t O = s.o, V = s.v, N = O + V, npv = pair_count(V), ka = s.lad_ka;
     auto need = [&](int64_t n) {
         if (capacity < n)
@@ -462,9 +432,9 @@ void so_density2_get(Context& cx, SOState& s, const char* name, double* out, int
 
 void so_density2_energy(Context& cx, SOState& s, double* e)
 {
-    need_plain(cx, "afesp_ccsd_so_density2_energy");
+    so_need_plain(cx, "afesp_ccsd_so_density2_energy", D2_PLAIN);
     if (!e) throw Error(1, "afesp_ccsd_so_density2_energy: NULL argument");
-    SODensity2& G = need_built(s, "afesp_ccsd_so_density2_energy");
+    SODensity2& G = so_density2_need(s, "afesp_ccsd_so_density2_energy");
     const int64_t O = s.o, V = s.v, N = O + V;
     // sum f D with the state's f: the levels on the diagonal, f_ov / f_oo / f_vv where the state has them (one-body algebra, on the host)
     std::vector<double> D((size_t)(N * N)), lev((size_t)N), fov, foo, fvv;
@@ -502,9 +472,9 @@ void so_density2_energy(Context& cx, SOState& s, double* e)
 
 double so_density2_expect(Context& cx, SOState& s, const double* A, const double* B)
 {
-    need_plain(cx, "afesp_ccsd_so_density2_expect");
+    so_need_plain(cx, "afesp_ccsd_so_density2_expect", D2_PLAIN);
     if (!A || !B) throw Error(1, "afesp_ccsd_so_density2_expect: NULL argument");
-    SODensity2& G = need_built(s, "afesp_ccsd_so_density2_expect");
+    SODensity2& G = so_density2_need(s, "afesp_ccsd_so_density2_expect");
     const int64_t N = (int64_t)s.o + s.v;
     double* ab = cx.scratch("d2_AB", 2 * N * N);
     AFESP_HIP(hipMemcpyAsync(ab, A, sizeof(double) * N * N, hipMemcpyHostToDevice, cx.stream));

@@ -1,6 +1,8 @@
-// device_util.h -- the device helpers every kernel unit shares, written once: the block size and grid-stride loop of the element-wise
-// kernels, the fixed-order wave / block sums, the triangular pair indices and their inverse, the reduction partials of a context and
-// the LAUNCH macro.  Everything has internal linkage (an unnamed namespace per unit); no __global__ function lives here.
+// device_util.h -- the device helpers every kernel unit shares, written once: the block size, grid size and grid-stride loop of the
+// element-wise kernels; the fixed-order block sums (block_sum over wave_sum, block_sum_down, block_tree_sum: two orders of the wave sum, see
+// block_sum_down); the triangular pair indices and their inverses (tri / unpair for x <= y, pair_count / unpair_lt for x < y); the decode of
+// an (o, o, v, v) element with its three images; the reduction partials of a context and the LAUNCH macro.  Everything has internal linkage
+// (an unnamed namespace per unit); no __global__ function lives here.
 #pragma once
 #include <algorithm>
 
@@ -10,6 +12,9 @@ namespace afesp {
 
 namespace {
 constexpr int TB = 256;
+// the grid cap of the spin-orbital CCSD, Lambda, two-particle-density and relaxation maps (beside grid_for's own 4096): where a kernel
+// leaves block partials, the cap decides how they are grouped
+constexpr int SO_GRID_CAP = 65536;
 inline unsigned grid_for(int64_t n, int cap = 4096) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + TB - 1) / TB, cap)); }
 #define GRID_STRIDE(IDX_, n) for (int64_t IDX_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; IDX_ < (n); IDX_ += (int64_t)gridDim.x * blockDim.x)
 
@@ -53,6 +58,42 @@ __device__ __forceinline__ void block_sum(double (&v)[NV], double* sm /* [NV*4] 
     }
 }
 
+// The same block-wide sum in the order of the CCSD, Lambda and two-particle-density energies: a __shfl_down tree over each wave, then the
+// four wave values added 0, 1, 2, 3 by thread 0.  The two trees pair the lanes differently, so the last bit of a sum differs between
+// them: a kernel stays with the order its published numbers were made in (block_sum: the Davidson, EOM, response and Z-vector
+// reductions).  Result valid in thread 0.
+template <int NV>
+__device__ __forceinline__ void block_sum_down(double (&v)[NV], double* sm /* [NV*4] */)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] += __shfl_down(v[q], off, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) sm[q * 4 + (threadIdx.x >> 6)] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) v[q] = 0.0;
+        for (int w = 0; w < TB / 64; ++w) {
+#pragma unroll
+            for (int q = 0; q < NV; ++q) v[q] += sm[q * 4 + w];
+        }
+    }
+}
+// the sum of one value per thread through a halving tree in LDS (the ordered final sum of block partials) -> red[0], for every thread
+__device__ __forceinline__ void block_tree_sum(double s, double (&red)[TB])
+{
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+}
+
 __device__ __forceinline__ int64_t tri(int64_t i, int64_t j) { return i >= j ? i * (i + 1) / 2 + j : j * (j + 1) / 2 + i; }
 // where (pq|rs) lies in the 8-fold packed array, for the four indices in any order (the one place that canonicalises them)
 __device__ __forceinline__ int64_t packed_index(int64_t p, int64_t q, int64_t r, int64_t s) { return tri(tri(p, q), tri(r, s)); }
@@ -71,6 +112,30 @@ __device__ __forceinline__ void unpair(int64_t p, int& lo, int& hi)
     unpair(p, l, h);
     hi = (int)h;
     lo = (int)l;
+}
+// pairs x < y are numbered y(y-1)/2 + x: how many of n indices, and the inverse
+__host__ __device__ inline int64_t pair_count(int64_t n) { return n * (n - 1) / 2; }
+__device__ __forceinline__ void unpair_lt(int64_t p, int& lo, int& hi)
+{
+    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
+    while (h * (h - 1) / 2 > p) --h;
+    while ((h + 1) * h / 2 <= p) ++h;
+    hi = (int)h;
+    lo = (int)(p - h * (h - 1) / 2);
+}
+
+// element x = i + o (j + o (a + v b)) of an (o, o, v, v) array: `const auto [i, j, a, b] = oovv_decode(x, o, v);` ...
+struct OOVV { int i, j, a, b; };
+__device__ __forceinline__ OOVV oovv_decode(int64_t x, int o, int v)
+{
+    return {(int)(x % o), (int)((x / o) % o), (int)((x / ((int64_t)o * o)) % v), (int)(x / ((int64_t)o * o * v))};
+}
+// ... and where its images under i <-> j, under a <-> b and under both lie: `const auto [ji, ba, jiba] = oovv_images(i, j, a, b, o, v);`
+struct OOVVImages { int64_t ji, ba, jiba; };
+__device__ __forceinline__ OOVVImages oovv_images(int i, int j, int a, int b, int o, int v)
+{
+    return {j + (int64_t)o * (i + (int64_t)o * (a + (int64_t)v * b)), i + (int64_t)o * (j + (int64_t)o * (b + (int64_t)v * a)),
+            j + (int64_t)o * (i + (int64_t)o * (b + (int64_t)v * a))};
 }
 
 // the fixed grid of the deterministic reductions: per-block partials, ordered final sum (k_final_sum)

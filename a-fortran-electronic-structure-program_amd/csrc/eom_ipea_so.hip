@@ -69,15 +69,6 @@ __global__ void ipea_assemble_kernel(double* s, const double* W, const double* A
     }
 }
 
-// pair index p = f (f - 1) / 2 + e of e < f, inverted
-__device__ __forceinline__ void ipea_unpair_lt(int64_t p, int& lo, int& hi)
-{
-    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-    while (h * (h - 1) / 2 > p) --h;
-    while ((h + 1) * h / 2 <= p) ++h;
-    hi = (int)h;
-    lo = (int)(p - h * (h - 1) / 2);
-}
 // ra(i, ef) = r(i,e,f) for e < f, leading dimension na; rows o .. oa and pairs npv .. ka are written as zero (the product reads them)
 __global__ void ipea_ea_pack_kernel(double* ra, const double* r2, int o, int v, int64_t na, int64_t oa, int64_t ka)
 {
@@ -88,7 +79,7 @@ __global__ void ipea_ea_pack_kernel(double* ra, const double* r2, int o, int v, 
         double val = 0.0;
         if (i < o && p < npv) {
             int e, f;
-            ipea_unpair_lt(p, e, f);
+            unpair_lt(p, e, f);
             val = r2[i + (int64_t)o * (e + (int64_t)v * f)];
         }
         ra[i + na * p] = val;
@@ -200,11 +191,10 @@ double so_eom_ipea_bytes(int64_t o, int64_t v, int sector, int nroots, int max_s
 
 void so_eom_ipea_sigma(Context& cx, SOState& s, int sector, const double* r, double* sigma)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ipea_sigma");
     preload_eom_ipea_so();
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v;
     const Tensor &t1 = s.t1, &t2 = s.t2;

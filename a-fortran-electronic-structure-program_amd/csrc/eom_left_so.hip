@@ -27,10 +27,8 @@ __global__ void eom_lsigma_assemble_kernel(double* s2, double* s1, const double*
     const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
     GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
-        const int64_t ji = j + (int64_t)o * (i + (int64_t)o * (a + (int64_t)v * b));
-        const int64_t ba = i + (int64_t)o * (j + (int64_t)o * (b + (int64_t)v * a));
-        const int64_t jiba = j + (int64_t)o * (i + (int64_t)o * (b + (int64_t)v * a));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
+        const auto [ji, ba, jiba] = oovv_images(i, j, a, b, o, v);
         const double same = __dadd_rn(eom_lcarrier(lad, AB, A, Bm, l1, Hov, x, i, j, a, b, o), eom_lcarrier(lad, AB, A, Bm, l1, Hov, jiba, j, i, b, a, o));
         const double swapped = __dadd_rn(eom_lcarrier(lad, AB, A, Bm, l1, Hov, ji, j, i, a, b, o), eom_lcarrier(lad, AB, A, Bm, l1, Hov, ba, i, j, b, a, o));
         const double d = __dmul_rn(0.25, __dadd_rn(__dadd_rn(D2[x], D2[jiba]), __dadd_rn(D2[ji], D2[ba])));
@@ -39,8 +37,7 @@ __global__ void eom_lsigma_assemble_kernel(double* s2, double* s1, const double*
     }
 }
 
-// block partials of sum_{x < n1} a1[x] y[x] + 1/4 sum_{x < n2} a2[x] y[n1 + x]: the reference coupling (a1 = H_ov, a2 = <ij||ab>) and the
-// metric <l, r> (a1 = l1, a2 = l2)
+// block partials of so_eom_wdot (eom_so.h)
 __global__ void eom_wdot_kernel(double* partial, const double* a1, const double* a2, const double* y, int64_t n1, int64_t n2)
 {
     __shared__ double sm[4];
@@ -50,30 +47,6 @@ __global__ void eom_wdot_kernel(double* partial, const double* a1, const double*
     if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
 }
 
-// The density blocks into the symmetric (o+v)^2 matrix, column-major, one element per thread and every sum in a fixed order:
-//   oo: 1/2 (doo(m,i) + doo(i,m)),  vv: 1/2 (dvv(a,e) + dvv(e,a)),  ov and vo: 1/2 (dov(m,e) + w t1(m,e) + l0 r1(m,e) + L1(m,e))
-// (r1, L1 null: absent)
-__global__ void eom_density_assemble_kernel(double* D, const double* doo, const double* dvv, const double* dov, const double* t1,
-                                            const double* r1, const double* L1, double w, double l0, int o, int v)
-{
-    const int n = o + v;
-    GRID_STRIDE(x, (int64_t)n * n)
-    {
-        const int p = (int)(x % n), q = (int)(x / n);
-        double val;
-        if (p < o && q < o) val = 0.5 * (doo[p + o * q] + doo[q + o * p]);
-        else if (p >= o && q >= o) val = 0.5 * (dvv[(p - o) + v * (q - o)] + dvv[(q - o) + v * (p - o)]);
-        else {
-            const int m = p < o ? p : q, e = (p < o ? q : p) - o;
-            double sum = __fma_rn(w, t1[m + o * e], dov[m + o * e]);
-            if (r1) sum = __fma_rn(l0, r1[m + o * e], sum);
-            if (L1) sum += L1[m + o * e];
-            val = 0.5 * sum;
-        }
-        D[x] = val;
-    }
-}
-
 // G_vv / G_oo of (x2, l2) into buffers of the caller: G_ae = -1/2 x_mnef l_mnaf, G_mi = 1/2 x_mnef l_inef
 void build_G(Context& cx, const Tensor& x2, const Tensor& l2, const Tensor& Gvv, const Tensor& Goo)
 {
@@ -81,23 +54,23 @@ void build_G(Context& cx, const Tensor& x2, const Tensor& l2, const Tensor& Gvv,
     contract(cx, 0.5, x2, "mnef", l2, "inef", 0.0, Goo, "mi");
 }
 
-// the ordered sum of eom_wdot_kernel's partials into out[0] (device)
-void wdot(Context& cx, double* out, const double* a1, const double* a2, const double* y, int64_t n1, int64_t n2)
-{
-    const int nblk = davidson_reduce_blocks(n1 + n2);
-    double* partial = cx.scratch("eoml_partial", nblk);
-    LAUNCH(eom_wdot_kernel, dim3(nblk), partial, a1, a2, y, n1, n2);
-    davidson_reduce_final(cx, out, partial, 1, nblk);
-}
-
 }  // namespace
+
+const double* so_eom_wdot(Context& cx, const double* a1, const double* a2, const double* y, int64_t n1, int64_t n2)
+{
+    preload_eom_left_so();
+    const int nblk = davidson_reduce_blocks(n1 + n2);
+    double* partial = cx.scratch("eoml_partial", nblk + 1);   // (the sum behind the partials)
+    LAUNCH(eom_wdot_kernel, dim3(nblk), partial, a1, a2, y, n1, n2);
+    davidson_reduce_final(cx, partial + nblk, partial, 1, nblk);
+    return partial + nblk;
+}
 
 void preload_eom_left_so()
 {
     static const bool loaded = [] {
         first_use_touch(reinterpret_cast<const void*>(eom_lsigma_assemble_kernel));
         first_use_touch(reinterpret_cast<const void*>(eom_wdot_kernel));
-        first_use_touch(reinterpret_cast<const void*>(eom_density_assemble_kernel));
         (void)hipGetLastError();
         return true;
     }();
@@ -114,11 +87,10 @@ double so_eom_left_bytes(int64_t o, int64_t v, int nroots, int max_space)
 
 void so_eom_lsigma(Context& cx, SOState& s, const double* l, double* sigma)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_lsigma");
     preload_eom_left_so();
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
     const Tensor l1 = view(const_cast<double*>(l), {O, V}), l2 = view(const_cast<double*>(l) + ov, {O, O, V, V});
@@ -164,17 +136,16 @@ void so_eom_lsigma(Context& cx, SOState& s, const double* l, double* sigma)
 
 void so_eom_ref_coupling(Context& cx, SOState& s, int nvec, const double* r1, const double* r2, double* c)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_ref_coupling");
     if (nvec < 1 || !r1 || !r2 || !c) throw Error(1, "afesp_ccsd_so_eom_ref_coupling: nvec < 1 or a NULL vector");
     preload_eom_left_so();
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V;
     double* r = cx.scratch("eom_r_stage", ov + o2v2);
-    double* out = cx.scratch("eoml_sum", 1);
     for (int k = 0; k < nvec; ++k) {
         AFESP_HIP(hipMemcpyAsync(r, r1 + ov * k, sizeof(double) * ov, hipMemcpyHostToDevice, cx.stream));
         AFESP_HIP(hipMemcpyAsync(r + ov, r2 + o2v2 * k, sizeof(double) * o2v2, hipMemcpyHostToDevice, cx.stream));
-        wdot(cx, out, L.Hov.d, s.oovv.d, r, ov, o2v2);
+        const double* out = so_eom_wdot(cx, L.Hov.d, s.oovv.d, r, ov, o2v2);
         AFESP_HIP(hipMemcpyAsync(c + k, out, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
         cx.sync();
     }
@@ -183,7 +154,7 @@ void so_eom_ref_coupling(Context& cx, SOState& s, int nvec, const double* r1, co
 void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const double* l2h, double r0, const double* r1h, const double* r2h,
                     double* d_host, int64_t capacity)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     so_lambda_need(s, "afesp_ccsd_so_eom_density");
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V, ov = O * V, o2v2 = O * O * V * V;
@@ -193,8 +164,7 @@ void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const
         throw Error(LAMBDA_ERR_CAPACITY, "afesp_ccsd_so_eom_density: the buffer holds " + std::to_string(d_host ? capacity : 0) +
                                              " doubles, the density needs (o + v)^2 = " + std::to_string(N * N));
     preload_eom_left_so();
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const bool hasl = l1h != nullptr, hasr = r1h != nullptr;
     Tensor l1, l2, r1, r2;
     if (hasl) {
@@ -212,9 +182,8 @@ void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const
     // ---- w = l0 r0 + <l, r>: the weight of the lone t_me term
     double w = l0 * r0;
     if (hasl && hasr) {
-        double* out = cx.scratch("eoml_sum", 1);
         double lr = 0.0;
-        wdot(cx, out, l1.d, l2.d, r1.d, ov, o2v2);
+        const double* out = so_eom_wdot(cx, l1.d, l2.d, r1.d, ov, o2v2);
         AFESP_HIP(hipMemcpyAsync(&lr, out, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
         cx.sync();
         w += lr;
@@ -261,8 +230,7 @@ void so_eom_density(Context& cx, SOState& s, double l0, const double* l1h, const
         }
         C(-1.0, t1, "mb", dvv, "be", 1.0, dov, "me");   // (the whole vv block, both parts: -t_mb d_be)
     }
-    LAUNCH(eom_density_assemble_kernel, grid_for(N * N), D, doo.d, dvv.d, dov.d, t1.d, hasr ? r1.d : (const double*)nullptr,
-           hasl ? L1.d : (const double*)nullptr, w, l0, o, v);
+    so_density_assemble(cx, s, D, doo.d, dvv.d, dov.d, hasr ? r1.d : (const double*)nullptr, hasl ? L1.d : (const double*)nullptr, w, l0);
     AFESP_HIP(hipMemcpyAsync(d_host, D, sizeof(double) * N * N, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
 }

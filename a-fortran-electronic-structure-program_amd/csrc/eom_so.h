@@ -36,7 +36,7 @@ void so_eom_set_guess(Context& cx, SOState& s, EomKind kind, int k, const double
 int so_eom_iterate(Context& cx, SOState& s, EomKind kind, double tol);
 void so_eom_get_vector(Context& cx, SOState& s, EomKind kind, int k, double* r1, double* r2);
 SOEom& so_eom_need(SOState& s, EomKind kind, const char* who);
-void so_eom_need_plain(Context& cx);   // a recording context (cx.rec) is refused by every EOM entry
+constexpr const char *EOM_WHO = "so_eom", *EOM_PLAIN = "the EOM equations are";   // every EOM entry: so_need_plain(cx, EOM_WHO, EOM_PLAIN)
 
 // ---- EE, right-hand side (eom_so.hip)
 // sigma = A r on device vectors [r1; r2] / [s1; s2] of length o v + o^2 v^2 (r2 antisymmetric in i,j and in a,b)
@@ -51,6 +51,10 @@ double so_eom_left_bytes(int64_t o, int64_t v, int nroots, int max_space);
 // sigma_L = A^T l on device vectors [l1; l2] / [s1; s2]: the X of so_lambda_iterate without its two inhomogeneous terms, minus D l, not
 // divided.  G_vv / G_oo of l2 go to buffers of its own: nothing of the live Lambda state, of t1 / t2 or of any EOM state is written.
 void so_eom_lsigma(Context& cx, SOState& s, const double* l, double* sigma);
+// sum_{x < n1} a1[x] y[x] + 1/4 sum_{x < n2} a2[x] y[n1 + x] of device vectors, block partials and the Davidson unit's ordered final sum:
+// the metric <l, r> (a1 = l1, a2 = l2) and the reference coupling (a1 = H_ov, a2 = <ij||ab>).  -> the sum on the device, in a cached buffer
+// that holds until the next call
+const double* so_eom_wdot(Context& cx, const double* a1, const double* a2, const double* y, int64_t n1, int64_t n2);
 // c[k] = sum H_ia r_ia + 1/4 sum <ij||ab> r_ijab of nvec host vectors (r0 = c / omega is the caller's)
 void so_eom_ref_coupling(Context& cx, SOState& s, int nvec, const double* r1, const double* r2, double* c);
 // The symmetrised one-particle matrix of <0| (l0 + L) H-bar (r0 + R) |0> differentiated by f, (o+v)^2 column-major in the state's order;

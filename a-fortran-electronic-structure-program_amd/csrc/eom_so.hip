@@ -25,10 +25,8 @@ __global__ void eom_sigma_assemble_kernel(double* s2, double* s1, const double* 
     const int64_t n2 = (int64_t)o * o * v * v, n1 = (int64_t)o * v;
     GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
-        const int64_t ji = j + (int64_t)o * (i + (int64_t)o * (a + (int64_t)v * b));
-        const int64_t ba = i + (int64_t)o * (j + (int64_t)o * (b + (int64_t)v * a));
-        const int64_t jiba = j + (int64_t)o * (i + (int64_t)o * (b + (int64_t)v * a));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
+        const auto [ji, ba, jiba] = oovv_images(i, j, a, b, o, v);
         const double same = __dadd_rn(eom_carrier(lad, AB, A, Bm, x), eom_carrier(lad, AB, A, Bm, jiba));
         const double swapped = __dadd_rn(eom_carrier(lad, AB, A, Bm, ji), eom_carrier(lad, AB, A, Bm, ba));
         const double d = __dmul_rn(0.25, __dadd_rn(__dadd_rn(D2[x], D2[jiba]), __dadd_rn(D2[ji], D2[ba])));
@@ -64,11 +62,6 @@ __global__ void eom_diag_kernel(double* diag, const double* D1, const double* D2
 
 }  // namespace
 
-void so_eom_need_plain(Context& cx)
-{
-    if (cx.rec) throw Error(1, "so_eom: the EOM equations are not part of a recorded (launch-fused) sequence");
-}
-
 void preload_eom_so()
 {
     static const bool loaded = [] {
@@ -97,10 +90,9 @@ void so_eom_fill_diag(Context& cx, SOState& s, double* diag)
 
 void so_eom_sigma(Context& cx, SOState& s, const double* r, double* sigma)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_eom_sigma");
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
     const Tensor r1 = view(const_cast<double*>(r), {O, V}), r2 = view(const_cast<double*>(r) + ov, {O, O, V, V});
@@ -283,7 +275,7 @@ SOEom& so_eom_need(SOState& s, EomKind kind, const char* who)
 
 void so_eom_init(Context& cx, SOState& s, EomKind kind, int nroots, int max_space)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     const std::string who = P.prefix + "init";
     SOLambda& L = so_lambda_need(s, who.c_str());
@@ -310,7 +302,7 @@ void so_eom_init(Context& cx, SOState& s, EomKind kind, int nroots, int max_spac
 
 void so_eom_sigma_host(Context& cx, SOState& s, EomKind kind, int nvec, const double* r1, const double* r2, double* s1, double* s2)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     so_lambda_need(s, P.sigma_entry);
     if (nvec < 1 || !r1 || !r2 || !s1 || !s2) throw Error(1, std::string(P.sigma_entry) + ": nvec < 1 or a NULL vector");
@@ -329,7 +321,7 @@ void so_eom_sigma_host(Context& cx, SOState& s, EomKind kind, int nvec, const do
 
 void so_eom_guess(Context& cx, SOState& s, EomKind kind)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     Davidson& E = so_eom_need(s, kind, (P.prefix + "guess").c_str()).d;
     const std::vector<double> key = P.sort_key(cx, s, E);
@@ -348,14 +340,14 @@ void so_eom_guess(Context& cx, SOState& s, EomKind kind)
 
 void so_eom_set_guess(Context& cx, SOState& s, EomKind kind, int k, const double* r1, const double* r2)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     davidson_set_pending_from_host(cx, so_eom_need(s, kind, (P.prefix + "set_guess").c_str()).d, P.prefix, k, r1, r2);
 }
 
 int so_eom_iterate(Context& cx, SOState& s, EomKind kind, double tol)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     Davidson& E = so_eom_need(s, kind, (P.prefix + "iterate").c_str()).d;
     return davidson_iterate(cx, E, P.prefix, tol, [&](const double* r, double* sigma) { P.sigma(cx, s, r, sigma); });
@@ -363,7 +355,7 @@ int so_eom_iterate(Context& cx, SOState& s, EomKind kind, double tol)
 
 void so_eom_get_vector(Context& cx, SOState& s, EomKind kind, int k, double* r1, double* r2)
 {
-    so_eom_need_plain(cx);
+    so_need_plain(cx, EOM_WHO, EOM_PLAIN);
     const EomProblem P = eom_problem(s, kind);
     davidson_get_vector(cx, so_eom_need(s, kind, (P.prefix + "get_vector").c_str()).d, P.prefix, k, r1, r2);
 }

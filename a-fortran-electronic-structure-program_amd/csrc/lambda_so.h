@@ -33,6 +33,23 @@ struct SOLambda : DiisRing {   // amp = [l1 ; l2]
     SORelax* rx = nullptr;     // the orbital gradient and Z-vector beside it (relax_so.h); released wherever d2 is
 };
 
+// ---- host helpers of every spin-orbital unit, written once
+// A recording context (cx.rec) is refused by every entry above the T iteration: "<who>: <what> not part of a recorded ... sequence", e.g.
+// ("so_lambda", "the Lambda equations are")
+inline void so_need_plain(Context& cx, const char* who, const char* what)
+{
+    if (cx.rec) throw Error(1, std::string(who) + ": " + what + " not part of a recorded (launch-fused) sequence");
+}
+// the two-particle density built for the current t and lambda (density2_so.hip), or LAMBDA_ERR_STALE in the caller's name
+SODensity2& so_density2_need(SOState& s, const char* who);
+// C(alpha, A, "labels", B, "labels", beta, C, "labels"): contract() on one context, the form every term of these units is written in
+inline auto contractor(Context& cx)
+{
+    return [&cx](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc, const char* lc) {
+        contract(cx, al, A, la, B, lb, be, Cc, lc);
+    };
+}
+
 // device bytes of the Lambda state and its working set (beside so_state_bytes)
 double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr);
 // Builds the intermediates from the state's current t1 / t2 (converged or not) and sets l = t.  Throws LAMBDA_ERR_FOO on a state whose
@@ -48,6 +65,11 @@ int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol);   // th
 void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity);
 // the same matrix left on the device (the cached buffer lam_density, valid until the next call of either)
 double* so_density_device(Context& cx, SOState& s, const char* who);
+// The density blocks into the symmetric (o+v)^2 matrix D (device, column-major), every sum in a fixed order:
+//   oo: 1/2 (doo(m,i) + doo(i,m)),  vv: 1/2 (dvv(a,e) + dvv(e,a)),  ov and vo: 1/2 (dov(m,e) + w t1(m,e) + l0 r1(m,e) + L1(m,e))
+// (r1, L1 null: absent).  The ground state's is w = 1, no r1, L1 = l1; the EOM states': eom_left_so.hip.
+void so_density_assemble(Context& cx, SOState& s, double* D, const double* doo, const double* dvv, const double* dov, const double* r1,
+                         const double* L1, double w, double l0);
 void so_relax_free(Context& cx, SOLambda& L);   // relax_so.hip
 // Lambda-CCSD(T): the triples [t_begin, t_end) of so_triples' own list with l1 / l2 in the left factor (triples.hip)
 double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);

@@ -12,16 +12,15 @@ namespace afesp {
 namespace {
 
 constexpr int MAXBLK = 1024;
-inline unsigned blocks_for(int64_t n) { return (unsigned)std::min<int64_t>((n + TB - 1) / TB, 65536); }
-#define LAM_STRIDE(X_, N_) for (int64_t X_ = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; X_ < (N_); X_ += (int64_t)gridDim.x * blockDim.x)
+constexpr const char *LAM_WHO = "so_lambda", *LAM_PLAIN = "the Lambda equations are";   // (so_need_plain)
 
 // tau(i,j,a,b) = t2 + t1(i,a) t1(j,b) - t1(i,b) t1(j,a)
 __global__ void lam_tau_kernel(double* tau, const double* t1, const double* t2, int o, int v)
 {
     const int64_t n2 = (int64_t)o * o * v * v;
-    LAM_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
         tau[x] = t2[x] + t1[i + o * a] * t1[j + o * b] - t1[i + o * b] * t1[j + o * a];
     }
 }
@@ -30,34 +29,22 @@ __global__ void lam_tau_kernel(double* tau, const double* t1, const double* t2, 
 __global__ void lam_ring_operand_kernel(double* out, const double* t1, const double* t2, int o, int v)
 {
     const int64_t n2 = (int64_t)o * v * o * v;
-    LAM_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
         const int n = (int)(x % o), f = (int)((x / o) % v), j = (int)((x / ((int64_t)o * v)) % o), b = (int)(x / ((int64_t)o * v * o));
         out[x] = t2[j + (int64_t)o * (n + (int64_t)o * (f + (int64_t)v * b))] + t1[j + o * f] * t1[n + o * b];
     }
 }
 
-// block sums of a pair of per-thread values: partial[block] and partial[gridDim.x + block]
+// block sums of a pair of per-thread values, in the order of so_energy_kernel: partial[block] and partial[gridDim.x + block]
 __device__ __forceinline__ void lam_block_sums(double* partial, double e, double r)
 {
-    __shared__ double red[2][TB / 64];
-    for (int off = 32; off > 0; off >>= 1) {
-        e += __shfl_down(e, off, 64);
-        r += __shfl_down(r, off, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = e;
-        red[1][threadIdx.x >> 6] = r;
-    }
-    __syncthreads();
+    __shared__ double red[2 * 4];
+    double s[2] = {e, r};
+    block_sum_down<2>(s, red);
     if (threadIdx.x == 0) {
-        double se = 0.0, sr = 0.0;
-        for (int w = 0; w < TB / 64; ++w) {
-            se += red[0][w];
-            sr += red[1][w];
-        }
-        partial[blockIdx.x] = se;
-        partial[gridDim.x + blockIdx.x] = sr;
+        partial[blockIdx.x] = s[0];
+        partial[gridDim.x + blockIdx.x] = s[1];
     }
 }
 
@@ -71,12 +58,10 @@ __global__ void lam_l2_assemble_kernel(double* l2, double* l2_old, double* parti
 {
     const int64_t n2 = (int64_t)o * o * v * v;
     double e = 0.0, r = 0.0;
-    LAM_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
-        const int i = (int)(x % o), j = (int)((x / o) % o), a = (int)((x / ((int64_t)o * o)) % v), b = (int)(x / ((int64_t)o * o * v));
-        const int64_t ji = j + (int64_t)o * (i + (int64_t)o * (a + (int64_t)v * b));
-        const int64_t ba = i + (int64_t)o * (j + (int64_t)o * (b + (int64_t)v * a));
-        const int64_t jiba = j + (int64_t)o * (i + (int64_t)o * (b + (int64_t)v * a));
+        const auto [i, j, a, b] = oovv_decode(x, o, v);
+        const auto [ji, ba, jiba] = oovv_images(i, j, a, b, o, v);
         // (rounded products, grouped so that exchanging i and j or a and b negates the term to the bit: it vanishes on the diagonals)
         const double disc = (__dmul_rn(l1[i + o * a], Hov[j + o * b]) + __dmul_rn(l1[j + o * b], Hov[i + o * a])) -
                             (__dmul_rn(l1[j + o * a], Hov[i + o * b]) + __dmul_rn(l1[i + o * b], Hov[j + o * a]));
@@ -95,7 +80,7 @@ __global__ void lam_l2_assemble_kernel(double* l2, double* l2_old, double* parti
 __global__ void lam_energy_kernel(double* partial, const double* oovv, const double* l2, double* l2_old, int64_t n2)
 {
     double e = 0.0, r = 0.0;
-    LAM_STRIDE(x, n2)
+    GRID_STRIDE(x, n2)
     {
         const double l = l2[x];
         e += 0.25 * oovv[x] * l;
@@ -106,31 +91,12 @@ __global__ void lam_energy_kernel(double* partial, const double* oovv, const dou
     lam_block_sums(partial, e, r);
 }
 
-// out[b] = sum of partial[b nblk .. (b + 1) nblk) in a fixed order (as so_sum2_kernel); block 0 adds sum f(x) l1(x) where f is given
-__global__ void lam_sum2_kernel(double* out, const double* partial, int nblk, const double* f_ov, const double* l1, int64_t n1)
-{
-    __shared__ double red[TB];
-    const double* p = partial + (int64_t)blockIdx.x * nblk;
-    double s = 0.0;
-    for (int x = threadIdx.x; x < nblk; x += TB) s += p[x];
-    if (blockIdx.x == 0 && f_ov)
-        for (int64_t x = threadIdx.x; x < n1; x += TB) s += f_ov[x] * l1[x];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
-}
-
-// The density blocks into the symmetric (o+v)^2 matrix, column-major, one element per thread and every sum in a fixed order:
-//   oo: 1/2 (doo(m,i) + doo(i,m)),  vv: 1/2 (dvv(a,e) + dvv(e,a)),  ov and vo: 1/2 (dov(m,e) + t1(m,e) + l1(m,e))
-__global__ void lam_density_assemble_kernel(double* D, const double* doo, const double* dvv, const double* dov, const double* t1,
-                                            const double* l1, int o, int v)
+// so_density_assemble (lambda_so.h), one element per thread.  (The ground state's w = 1: __fma_rn(1, t1, dov) is the once-rounded dov + t1.)
+__global__ void so_density_assemble_kernel(double* D, const double* doo, const double* dvv, const double* dov, const double* t1,
+                                           const double* r1, const double* L1, double w, double l0, int o, int v)
 {
     const int n = o + v;
-    LAM_STRIDE(x, (int64_t)n * n)
+    GRID_STRIDE(x, (int64_t)n * n)
     {
         const int p = (int)(x % n), q = (int)(x / n);
         double val;
@@ -138,21 +104,13 @@ __global__ void lam_density_assemble_kernel(double* D, const double* doo, const 
         else if (p >= o && q >= o) val = 0.5 * (dvv[(p - o) + v * (q - o)] + dvv[(q - o) + v * (p - o)]);
         else {
             const int m = p < o ? p : q, e = (p < o ? q : p) - o;
-            val = 0.5 * (dov[m + o * e] + t1[m + o * e] + l1[m + o * e]);
+            double sum = __fma_rn(w, t1[m + o * e], dov[m + o * e]);
+            if (r1) sum = __fma_rn(l0, r1[m + o * e], sum);
+            if (L1) sum += L1[m + o * e];
+            val = 0.5 * sum;
         }
         D[x] = val;
     }
-}
-
-#define LAM_LAUNCH(kernel, nblocks, ...)                                                    \
-    do {                                                                                    \
-        AFESP_KLAUNCH(kernel, dim3(nblocks), dim3(TB), 0, cx.stream, __VA_ARGS__);          \
-        AFESP_HIP(hipGetLastError());                                                       \
-    } while (0)
-
-void need_plain(Context& cx)
-{
-    if (cx.rec) throw Error(1, "so_lambda: the Lambda equations are not part of a recorded (launch-fused) sequence");
 }
 
 // G_vv / G_oo of the current l2
@@ -173,13 +131,16 @@ void free_buffers(Context& cx, SOLambda& L)
 
 void preload_lambda_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(lam_tau_kernel));
-    first_use_touch(reinterpret_cast<const void*>(lam_ring_operand_kernel));
-    first_use_touch(reinterpret_cast<const void*>(lam_l2_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(lam_energy_kernel));
-    first_use_touch(reinterpret_cast<const void*>(lam_sum2_kernel));
-    first_use_touch(reinterpret_cast<const void*>(lam_density_assemble_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(lam_tau_kernel));
+        first_use_touch(reinterpret_cast<const void*>(lam_ring_operand_kernel));
+        first_use_touch(reinterpret_cast<const void*>(lam_l2_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(lam_energy_kernel));
+        first_use_touch(reinterpret_cast<const void*>(so_density_assemble_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
 }
 
 double so_lambda_bytes(int64_t o, int64_t v, int diis_nerr)
@@ -216,7 +177,7 @@ SOLambda& so_lambda_need(SOState& s, const char* who)
 
 void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
 {
-    need_plain(cx);
+    so_need_plain(cx, LAM_WHO, LAM_PLAIN);
     if (!s.foo_as_published)
         throw Error(LAMBDA_ERR_FOO,
                     "afesp_ccsd_so_lambda_init: this state keeps the reference's transposed F_mi term, whose equations have no consistent "
@@ -225,10 +186,8 @@ void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
     so_lambda_free(cx, s);
     if (!cx.fits(so_lambda_bytes(s.o, s.v, diis_nerr)))
         throw Error(1, "afesp_ccsd_so_lambda_init: the Lambda state of this system does not fit the free device memory");
-    static const bool loaded = (preload_lambda_so(), true);
-    (void)loaded;
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    preload_lambda_so();
+    const auto C = contractor(cx);
     auto P = [&](double al, const Tensor& in, const char* li, double be, const Tensor& out, const char* lo) {
         permute_add(cx, al, in, li, be, out, lo);
     };
@@ -254,7 +213,8 @@ void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
         diis_alloc(cx, L, diis_nerr);
 
         const Tensor &t1 = s.t1, &t2 = s.t2, &tau = L.tau;
-        LAM_LAUNCH(lam_tau_kernel, blocks_for(o2v2), L.tau.d, t1.d, t2.d, o, v);
+        // (every state has o, v >= 1 -- so_init, so_init_uhf -- so no element-wise launch of this unit is empty)
+        LAUNCH(lam_tau_kernel, grid_for(o2v2, SO_GRID_CAP), L.tau.d, t1.d, t2.d, o, v);
         // ---- one-body elements
         C(1.0, s.oovv, "mnef", t1, "nf", 0.0, L.Hov, "me");
         C(1.0, s.ooov, "mnie", t1, "ne", 0.0, L.Hoo, "mi");
@@ -285,7 +245,7 @@ void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
         k_copy(cx, L.Hovvo.d, s.ovvo.d, s.ovvo.size());
         C(1.0, s.ovvv, "mbef", t1, "jf", 1.0, L.Hovvo, "mbej");
         C(1.0, t1, "nb", s.oovo, "nmej", 1.0, L.Hovvo, "mbej");
-        LAM_LAUNCH(lam_ring_operand_kernel, blocks_for(o2v2), ro.d, t1.d, t2.d, o, v);
+        LAUNCH(lam_ring_operand_kernel, grid_for(o2v2, SO_GRID_CAP), ro.d, t1.d, t2.d, o, v);
         C(-1.0, s.oovv, "mnef", ro, "nfjb", 1.0, L.Hovvo, "mbej");
         // ---- what H_abei and H_mbij share: q(m,b,e,i) = <mb||ei> - t_nibf <mn||ef>
         Tensor q = view(cx.scratch("lam_q", o2v2), {O, V, V, O});
@@ -330,10 +290,9 @@ void so_lambda_init(Context& cx, SOState& s, int diis_nerr)
 
 void so_lambda_iterate(Context& cx, SOState& s)
 {
-    need_plain(cx);
+    so_need_plain(cx, LAM_WHO, LAM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_lambda_iterate");
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, ov = O * V, o2v2 = O * O * V * V;
     const Tensor &l1 = L.l1, &l2 = L.l2;
@@ -375,20 +334,20 @@ void so_lambda_iterate(Context& cx, SOState& s)
     // l2 first (it reads the l1 the iteration started from), then l1 = x1 / D, then the fixed-order sums
     const int nblk = (int)std::min<int64_t>((o2v2 + TB - 1) / TB, MAXBLK);
     double* partial = cx.scratch("lam_partial", 2 * MAXBLK);
-    LAM_LAUNCH(lam_l2_assemble_kernel, nblk, L.l2.d, L.l2_old.d, partial, L.x2.d, s.oovv.d, AB.d, A.d, Bm.d, L.l1.d, L.Hov.d, s.D2.d, o, v);
+    LAUNCH(lam_l2_assemble_kernel, nblk, L.l2.d, L.l2_old.d, partial, L.x2.d, s.oovv.d, AB.d, A.d, Bm.d, L.l1.d, L.Hov.d, s.D2.d, o, v);
     k_div(cx, L.l1.d, L.x1.d, s.D1.d, ov);
-    LAM_LAUNCH(lam_sum2_kernel, 2, cx.scal, partial, nblk, s.fock ? s.f_ov.d : (const double*)nullptr, L.l1.d, ov);
+    so_sum2(cx, cx.scal, partial, 2, nblk, s.fock ? s.f_ov.d : (const double*)nullptr, L.l1.d, ov);
 }
 
 void so_lambda_energy(Context& cx, SOState& s)
 {
-    need_plain(cx);
+    so_need_plain(cx, LAM_WHO, LAM_PLAIN);
     SOLambda& L = so_lambda_need(s, "afesp_ccsd_so_lambda_energy");
     const int64_t n2 = L.l2.size();
     const int nblk = (int)std::min<int64_t>((n2 + TB - 1) / TB, MAXBLK);
     double* partial = cx.scratch("lam_partial", 2 * MAXBLK);
-    LAM_LAUNCH(lam_energy_kernel, nblk, partial, s.oovv.d, L.l2.d, L.l2_old.d, n2);
-    LAM_LAUNCH(lam_sum2_kernel, 2, cx.scal, partial, nblk, s.fock ? s.f_ov.d : (const double*)nullptr, L.l1.d, (int64_t)s.o * s.v);
+    LAUNCH(lam_energy_kernel, nblk, partial, s.oovv.d, L.l2.d, L.l2_old.d, n2);
+    so_sum2(cx, cx.scal, partial, 2, nblk, s.fock ? s.f_ov.d : (const double*)nullptr, L.l1.d, (int64_t)s.o * s.v);
 }
 
 int so_lambda_read(Context& cx, SOState& s, double e_tol, double l_tol)
@@ -407,8 +366,7 @@ double* so_density_device(Context& cx, SOState& s, const char* who)
     SOLambda& L = so_lambda_need(s, who);
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V;
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     Tensor doo = view(cx.scratch("lam_doo", O * O), {O, O}), dvv = view(cx.scratch("lam_dvv", V * V), {V, V});
     Tensor dov = view(cx.scratch("lam_dov", O * V), {O, V});
     double* D = cx.scratch("lam_density", N * N);
@@ -422,13 +380,21 @@ double* so_density_device(Context& cx, SOState& s, const char* who)
     C(1.0, L.l1, "ia", s.t2, "imae", 0.0, dov, "me");
     C(-1.0, s.t1, "mb", dvv, "be", 1.0, dov, "me");
     C(-1.0, L.Goo, "mj", s.t1, "je", 1.0, dov, "me");
-    LAM_LAUNCH(lam_density_assemble_kernel, blocks_for(N * N), D, doo.d, dvv.d, dov.d, s.t1.d, L.l1.d, o, v);
+    so_density_assemble(cx, s, D, doo.d, dvv.d, dov.d, nullptr, L.l1.d, 1.0, 0.0);
     return D;
+}
+
+void so_density_assemble(Context& cx, SOState& s, double* D, const double* doo, const double* dvv, const double* dov, const double* r1,
+                         const double* L1, double w, double l0)
+{
+    const int64_t N = (int64_t)s.o + s.v;
+    // (a state holds v^4 integrals, so N^2 elements stay far below either cap of grid_for: one block per TB elements, whoever calls)
+    LAUNCH(so_density_assemble_kernel, grid_for(N * N, SO_GRID_CAP), D, doo, dvv, dov, s.t1.d, r1, L1, w, l0, s.o, s.v);
 }
 
 void so_density(Context& cx, SOState& s, double* d_host, int64_t capacity)
 {
-    need_plain(cx);
+    so_need_plain(cx, LAM_WHO, LAM_PLAIN);
     so_lambda_need(s, "afesp_ccsd_so_density");
     const int64_t N = (int64_t)s.o + s.v;
     if (!d_host || capacity < N * N)

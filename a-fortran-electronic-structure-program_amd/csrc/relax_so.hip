@@ -15,16 +15,7 @@ constexpr int RX_MCAP = 6016;    // doubles of one pair column (or a segment of 
 constexpr int RX_QCAP = 2048;    // doubles of one (i,b) slice of Q in LDS, i padded to a multiple of RX_IT; larger slices are read through the caches
 constexpr int RX_IT = 8;         // occupied indices per work item
 constexpr int RX_SPLIT = 512;    // blocks over the pair columns (c<d): two per compute unit
-inline unsigned rx_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + TB - 1) / TB, 65536)); }
-
-__device__ __forceinline__ void rx_unpair_lt(int64_t p, int& lo, int& hi)
-{
-    int64_t h = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)p)) * 0.5);
-    while (h * (h - 1) / 2 > p) --h;
-    while ((h + 1) * h / 2 <= p) ++h;
-    hi = (int)h;
-    lo = (int)(p - h * (h - 1) / 2);
-}
+constexpr const char* RX_PLAIN = "orbital relaxation is";   // (so_need_plain)
 
 // partial[blockIdx.x][i + o a] = sum over the block's pair columns (c<d) of sum_b P(ab; cd) Q(i,b,c,d).  P(., cd) is one column of the
 // pair matrix (a<b at a + b(b-1)/2, leading dimension ld), read from memory once into LDS and used there for both of its images
@@ -52,7 +43,7 @@ __global__ __launch_bounds__(TB) void relax_pair_row_kernel(double* __restrict__
     for (int k = 0; k < RX_IT; ++k) acc[k] = 0.0;
     const int64_t cd0 = (int64_t)blockIdx.x * chunk, cd1 = min(npv, cd0 + chunk);
     int c = 0, d = 1;
-    if (cd0 < cd1) rx_unpair_lt(cd0, c, d);
+    if (cd0 < cd1) unpair_lt(cd0, c, d);
     const int rb = r * (r - 1) / 2;   // (v <= RX_MCAP + 1: every pair index fits 32 bits)
     for (int64_t cd = cd0; cd < cd1; ++cd) {
         const double* col = P + ld * cd;
@@ -235,28 +226,6 @@ __global__ void relax_density_kernel(double* out, const double* D, const double*
     }
 }
 
-#define RX_LAUNCH(kernel, nblocks, ...)                                                     \
-    do {                                                                                    \
-        AFESP_KLAUNCH(kernel, dim3(nblocks), dim3(TB), 0, cx.stream, __VA_ARGS__);          \
-        AFESP_HIP(hipGetLastError());                                                       \
-    } while (0)
-
-void need_plain(Context& cx, const char* who)
-{
-    if (cx.rec) throw Error(1, std::string(who) + ": orbital relaxation is not part of a recorded (launch-fused) sequence");
-}
-
-SODensity2& need_built(SOState& s, const char* who)
-{
-    SOLambda& L = so_lambda_need(s, who);
-    if (!L.d2 || L.d2->epoch != s.amp_epoch || L.d2->stamp != L.stamp)
-        throw Error(LAMBDA_ERR_STALE, std::string(who) + ": no two-particle density of the current t and lambda (call afesp_ccsd_so_density2_build; "
-                                                         "whatever writes t1 / t2 or l1 / l2 makes an earlier build stale)");
-    return *L.d2;
-}
-
-int64_t pair_count(int64_t n) { return n * (n - 1) / 2; }
-
 struct Split { int64_t chunk; int nsplit; };
 Split split_of(int64_t npv)
 {
@@ -276,8 +245,8 @@ int pair_row(Context& cx, SOState& s, const double* P, const double* Q, double* 
     const int nitems = v * ((o + RX_IT - 1) / RX_IT);
     const bool staged = (int64_t)((o + RX_IT - 1) / RX_IT * RX_IT) * v <= std::min(knobs().relax_qcap, RX_QCAP);
     for (int item0 = 0; item0 < nitems; item0 += TB) {
-        if (staged) RX_LAUNCH(relax_pair_row_kernel<true>, sp.nsplit, partial, P, s.lad_ka, Q, o, v, npv, sp.chunk, item0, nitems, mcap);
-        else RX_LAUNCH(relax_pair_row_kernel<false>, sp.nsplit, partial, P, s.lad_ka, Q, o, v, npv, sp.chunk, item0, nitems, mcap);
+        if (staged) LAUNCH(relax_pair_row_kernel<true>, sp.nsplit, partial, P, s.lad_ka, Q, o, v, npv, sp.chunk, item0, nitems, mcap);
+        else LAUNCH(relax_pair_row_kernel<false>, sp.nsplit, partial, P, s.lad_ka, Q, o, v, npv, sp.chunk, item0, nitems, mcap);
     }
     return sp.nsplit;
 }
@@ -287,8 +256,7 @@ SORelax& relax_of(Context& cx, SOState& s, SOLambda& L, const char* who)
     if (L.rx) return *L.rx;
     if (!cx.fits(so_relax_bytes(s.o, s.v)))
         throw Error(LAMBDA_ERR_CAPACITY, std::string(who) + ": the orbital gradient of this system does not fit the free device memory");
-    static const bool loaded = (preload_relax_so(), true);
-    (void)loaded;
+    preload_relax_so();
     L.rx = new SORelax();
     try {
         L.rx->vec = cx.alloc(6 * (int64_t)s.o * s.v);
@@ -305,12 +273,11 @@ void gradient(Context& cx, SOState& s, SODensity2& G, int fock_response, double*
 {
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V, npv = pair_count(V);
-    auto C = [&](double al, const Tensor& A, const char* la, const Tensor& B, const char* lb, double be, const Tensor& Cc,
-                 const char* lc) { contract(cx, al, A, la, B, lb, be, Cc, lc); };
+    const auto C = contractor(cx);
     double* D = so_density_device(cx, s, who);
     double* F = cx.scratch("rx_F", N * N);
     Tensor FD = view(cx.scratch("rx_FD", N * N), {N, N}), X = view(cx.scratch("rx_X", O * V), {O, V});
-    RX_LAUNCH(relax_fock_kernel, rx_blocks(N * N), F, (const double*)s.lev, (const double*)s.e, s.fock ? (const double*)s.f_ov.d : nullptr,
+    LAUNCH(relax_fock_kernel, grid_for(N * N, SO_GRID_CAP), F, (const double*)s.lev, (const double*)s.e, s.fock ? (const double*)s.f_ov.d : nullptr,
               s.fock ? (const double*)s.f_oo.d : nullptr, s.fock ? (const double*)s.f_vv.d : nullptr, o, v);
     C(1.0, view(F, {N, N}), "pr", view(D, {N, N}), "rq", 0.0, FD, "pq");
     // ---- the dense terms of X_ai - X_ia over the stored blocks of Gamma (np_relax.gradient_blocks, in its order)
@@ -344,7 +311,7 @@ void gradient(Context& cx, SOState& s, SODensity2& G, int fock_response, double*
         if (!n1) k_fill(cx, p1, (int64_t)n2 * O * V, 0.0);
         if (!n2) k_fill(cx, p2, (int64_t)n1 * O * V, 0.0);
     }
-    RX_LAUNCH(relax_assemble_kernel, rx_blocks(O * V), w, X.d, FD.d, p1, p2, std::max(n1, n2), o, v);
+    LAUNCH(relax_assemble_kernel, grid_for(O * V, SO_GRID_CAP), w, X.d, FD.d, p1, p2, std::max(n1, n2), o, v);
 }
 
 // y = A x on the device, (i,a) arrays
@@ -354,26 +321,30 @@ void apply(Context& cx, SOState& s, const double* x, double* y)
     Tensor Xt = view(const_cast<double*>(x), {O, V}), Yt = view(y, {O, V});
     contract(cx, 1.0, s.oovv, "ijab", Xt, "jb", 0.0, Yt, "ia");
     contract(cx, 1.0, s.ovvo, "jabi", Xt, "jb", 1.0, Yt, "ia");
-    RX_LAUNCH(relax_diag_kernel, rx_blocks(O * V), y, s.D1.d, x, O * V);
+    LAUNCH(relax_diag_kernel, grid_for(O * V, SO_GRID_CAP), y, s.D1.d, x, O * V);
 }
 
 }  // namespace
 
 void preload_relax_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(relax_pair_row_kernel<true>));
-    first_use_touch(reinterpret_cast<const void*>(relax_pair_row_kernel<false>));
-    first_use_touch(reinterpret_cast<const void*>(relax_fock_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_assemble_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_split_sum_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_diag_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_dot2_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_spin_part_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_cg_start_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_cg_step_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_cg_dir_kernel));
-    first_use_touch(reinterpret_cast<const void*>(relax_density_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(relax_pair_row_kernel<true>));
+        first_use_touch(reinterpret_cast<const void*>(relax_pair_row_kernel<false>));
+        first_use_touch(reinterpret_cast<const void*>(relax_fock_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_split_sum_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_diag_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_dot2_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_spin_part_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_cg_start_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_cg_step_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_cg_dir_kernel));
+        first_use_touch(reinterpret_cast<const void*>(relax_density_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
 }
 
 double so_relax_bytes(int64_t o, int64_t v)
@@ -394,9 +365,9 @@ void so_relax_free(Context& cx, SOLambda& L)
 void so_orbital_gradient(Context& cx, SOState& s, int fock_response, double* w_host, int64_t capacity)
 {
     const char* who = "afesp_ccsd_so_orbital_gradient";
-    need_plain(cx, who);
+    so_need_plain(cx, who, RX_PLAIN);
     if (fock_response != 0 && fock_response != 1) throw Error(1, std::string(who) + ": fock_response must be 0 or 1");
-    SODensity2& G = need_built(s, who);
+    SODensity2& G = so_density2_need(s, who);
     const int64_t n = (int64_t)s.o * s.v;
     if (!w_host || capacity < n)
         throw Error(LAMBDA_ERR_CAPACITY, std::string(who) + ": the buffer holds " + std::to_string(w_host ? capacity : 0) + " doubles, the gradient needs o v = " +
@@ -412,9 +383,9 @@ void so_orbital_gradient(Context& cx, SOState& s, int fock_response, double* w_h
 void so_zvector_apply(Context& cx, SOState& s, const double* x_host, double* y_host)
 {
     const char* who = "afesp_ccsd_so_zvector_apply";
-    need_plain(cx, who);
+    so_need_plain(cx, who, RX_PLAIN);
     if (!x_host || !y_host) throw Error(1, std::string(who) + ": NULL argument");
-    need_built(s, who);
+    so_density2_need(s, who);
     const int64_t n = (int64_t)s.o * s.v;
     relax_of(cx, s, *s.lam, who);
     double* xy = cx.scratch("rx_xy", 2 * n);
@@ -427,9 +398,9 @@ void so_zvector_apply(Context& cx, SOState& s, const double* x_host, double* y_h
 void so_zvector_solve(Context& cx, SOState& s, double tol, int maxiter, double* z_host, int* iters, double* resid)
 {
     const char* who = "afesp_ccsd_so_zvector_solve";
-    need_plain(cx, who);
+    so_need_plain(cx, who, RX_PLAIN);
     if (!(tol > 0.0) || maxiter < 1) throw Error(1, std::string(who) + ": tol must be positive and maxiter at least 1");
-    SODensity2& G = need_built(s, who);
+    SODensity2& G = so_density2_need(s, who);
     if (s.fock)
         throw Error(RELAX_ERR_NOT_HF, std::string(who) + ": the reference of a state made by afesp_ccsd_uso_init_fock is not stationary in the spin-orbital "
                                                          "rotations (a restricted open-shell Z-vector is not built)");
@@ -455,16 +426,16 @@ void so_zvector_solve(Context& cx, SOState& s, double tol, int maxiter, double* 
     char num[64];
     for (int part = 0; part < nparts && trouble.empty(); ++part) {
         const int sgn = nparts == 1 ? 0 : (part == 0 ? 1 : -1);
-        RX_LAUNCH(relax_spin_part_kernel, rx_blocks(n), Ap, w, sgn, s.o, n);
-        RX_LAUNCH(relax_cg_start_kernel, rx_blocks(n), r, p, zz, Ap, s.D1.d, n);
-        RX_LAUNCH(relax_dot2_kernel, 1, cx.scal, r, zz, r, r, n);
+        LAUNCH(relax_spin_part_kernel, grid_for(n, SO_GRID_CAP), Ap, w, sgn, s.o, n);
+        LAUNCH(relax_cg_start_kernel, grid_for(n, SO_GRID_CAP), r, p, zz, Ap, s.D1.d, n);
+        LAUNCH(relax_dot2_kernel, 1, cx.scal, r, zz, r, r, n);
         const double* h = host_scalars(cx, 2);
         double rz = h[0], rr = h[1];
         bool done = std::sqrt(rr) < part_tol;
         while (!done && R.iters < maxiter) {
             apply(cx, s, p, zz);   // (zz is free between the direction update and the next step)
-            RX_LAUNCH(relax_spin_part_kernel, rx_blocks(n), Ap, zz, sgn, s.o, n);
-            RX_LAUNCH(relax_dot2_kernel, 1, cx.scal, p, Ap, p, Ap, n);
+            LAUNCH(relax_spin_part_kernel, grid_for(n, SO_GRID_CAP), Ap, zz, sgn, s.o, n);
+            LAUNCH(relax_dot2_kernel, 1, cx.scal, p, Ap, p, Ap, n);
             const double pAp = host_scalars(cx, 1)[0];
             // Negative curvature alone does not stop the iteration: at a saddle point of the SCF energy (an unstable but stationary
             // reference) A is indefinite and the equations still have their solution.  A breakdown does: p A p = 0 is a singular A
@@ -476,15 +447,15 @@ void so_zvector_solve(Context& cx, SOState& s, double tol, int maxiter, double* 
             }
             if (pAp < 0.0) ++R.negative;
             const double alpha = rz / pAp;
-            RX_LAUNCH(relax_cg_step_kernel, rx_blocks(n), z, r, zz, p, Ap, s.D1.d, alpha, n);
-            RX_LAUNCH(relax_dot2_kernel, 1, cx.scal, r, zz, r, r, n);
+            LAUNCH(relax_cg_step_kernel, grid_for(n, SO_GRID_CAP), z, r, zz, p, Ap, s.D1.d, alpha, n);
+            LAUNCH(relax_dot2_kernel, 1, cx.scal, r, zz, r, r, n);
             h = host_scalars(cx, 2);
             const double rz_new = h[0];
             rr = h[1];
             ++R.iters;
             done = std::sqrt(rr) < part_tol;
             if (done) break;
-            RX_LAUNCH(relax_cg_dir_kernel, rx_blocks(n), p, zz, rz_new / rz, n);
+            LAUNCH(relax_cg_dir_kernel, grid_for(n, SO_GRID_CAP), p, zz, rz_new / rz, n);
             rz = rz_new;
         }
         rr_sum += rr;
@@ -508,8 +479,8 @@ void so_zvector_solve(Context& cx, SOState& s, double tol, int maxiter, double* 
 void so_relaxed_density(Context& cx, SOState& s, double* d_host, int64_t capacity)
 {
     const char* who = "afesp_ccsd_so_relaxed_density";
-    need_plain(cx, who);
-    need_built(s, who);
+    so_need_plain(cx, who, RX_PLAIN);
+    so_density2_need(s, who);
     if (s.fock)
         throw Error(RELAX_ERR_NOT_HF, std::string(who) + ": the reference of a state made by afesp_ccsd_uso_init_fock is not stationary in the spin-orbital "
                                                          "rotations (a restricted open-shell Z-vector is not built)");
@@ -522,7 +493,7 @@ void so_relaxed_density(Context& cx, SOState& s, double* d_host, int64_t capacit
                                              std::to_string(N * N));
     const double* D = so_density_device(cx, s, who);
     double* out = cx.scratch("rx_Drel", N * N);
-    RX_LAUNCH(relax_density_kernel, rx_blocks(N * N), out, D, L.rx->vec + O * V, s.o, s.v);
+    LAUNCH(relax_density_kernel, grid_for(N * N, SO_GRID_CAP), out, D, L.rx->vec + O * V, s.o, s.v);
     AFESP_HIP(hipMemcpyAsync(d_host, out, sizeof(double) * N * N, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
 }
@@ -530,9 +501,9 @@ void so_relaxed_density(Context& cx, SOState& s, double* d_host, int64_t capacit
 double so_relax_pair_row(Context& cx, SOState& s, int which, double* out_host, int reps)
 {
     const char* who = "afesp_ccsd_so_relax_pair_row";
-    need_plain(cx, who);
+    so_need_plain(cx, who, RX_PLAIN);
     if (which != 0 && which != 1) throw Error(1, std::string(who) + ": which must be 0 or 1");
-    SODensity2& G = need_built(s, who);
+    SODensity2& G = so_density2_need(s, who);
     relax_of(cx, s, *s.lam, who);
     const int64_t n = (int64_t)s.o * s.v;
     const Split sp = split_of(std::max<int64_t>(pair_count(s.v), 1));
@@ -547,7 +518,7 @@ double so_relax_pair_row(Context& cx, SOState& s, int which, double* out_host, i
     AFESP_HIP(hipEventRecord(a.e, cx.stream));
     for (int k = 0; k < reps; ++k) ns = pair_row(cx, s, P, Q, p1);
     AFESP_HIP(hipEventRecord(b.e, cx.stream));
-    RX_LAUNCH(relax_split_sum_kernel, rx_blocks(n), out, p1, ns, n);
+    LAUNCH(relax_split_sum_kernel, grid_for(n, SO_GRID_CAP), out, p1, ns, n);
     if (out_host) AFESP_HIP(hipMemcpyAsync(out_host, out, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
     cx.sync();
     float ms = 0.f;

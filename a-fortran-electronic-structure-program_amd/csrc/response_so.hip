@@ -15,6 +15,7 @@ constexpr int RSP_CT = 32;      // virtual indices of one staged piece of a row 
 constexpr int RSP_KT = 8;       // rows k of X~_oo staged at a time, fewer where o rows of RSP_KT exceed ...
 constexpr int RSP_OO = 2048;    // ... the doubles of the staging buffer: kt = min(o, RSP_KT, RSP_OO / o)
 constexpr int RSP_PAB = TB / 64;   // virtual pairs of a block: one per wave, 64 occupied pairs each
+constexpr const char *RSP_WHO = "so_response", *RSP_PLAIN = "the response equations are";   // (so_need_plain)
 
 // The dressed operators and xi1 of every operator of the batch (blockIdx.y), one element per thread and every sum in a fixed order:
 //   X~_kj = X_kj + sum_c X_kc t_jc                  -> Xoo[k + o j]
@@ -113,27 +114,6 @@ __global__ void response_xi2_kernel(double* xi, const double* Xoo, const double*
     }
 }
 
-// block partials of <x, y> = sum_{e < n1} x y + 1/4 sum behind them
-__global__ void response_dot_kernel(double* partial, const double* x1, const double* x2, const double* y, int64_t n1, int64_t n2)
-{
-    __shared__ double sm[4];
-    double acc[1] = {0.0};
-    GRID_STRIDE(e, n1 + n2) acc[0] += e < n1 ? x1[e] * y[e] : 0.25 * x2[e - n1] * y[e];
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) partial[blockIdx.x] = acc[0];
-}
-
-void need_plain(Context& cx)
-{
-    if (cx.rec) throw Error(1, "so_response: the response equations are not part of a recorded (launch-fused) sequence");
-}
-
-void preload_once()
-{
-    static const bool loaded = (preload_response_so(), true);
-    (void)loaded;
-}
-
 void check_count(const char* who, int nop, const double* x)
 {
     if (nop < 1 || nop > RESPONSE_MAX_SYSTEMS || !x)
@@ -164,10 +144,13 @@ int64_t vec_len(const SOState& s) { return (int64_t)s.o * s.v + (int64_t)s.o * s
 
 void preload_response_so()
 {
-    first_use_touch(reinterpret_cast<const void*>(response_dress_kernel));
-    first_use_touch(reinterpret_cast<const void*>(response_xi2_kernel));
-    first_use_touch(reinterpret_cast<const void*>(response_dot_kernel));
-    (void)hipGetLastError();
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(response_dress_kernel));
+        first_use_touch(reinterpret_cast<const void*>(response_xi2_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
 }
 
 double so_response_bytes(int64_t o, int64_t v, int nop, int nsys, int max_space, bool cplx)
@@ -182,7 +165,7 @@ double so_response_bytes(int64_t o, int64_t v, int nop, int nsys, int max_space,
 // so_response_xi behind its argument check
 static void xi_build(Context& cx, SOState& s, int nop, const double* x_host, double* xi)
 {
-    preload_once();
+    preload_response_so();
     const int o = s.o, v = s.v;
     const int64_t O = o, V = v, N = O + V, nvec = vec_len(s);
     if (O > RSP_OO) throw Error(1, "afesp_ccsd_so_response_xi: more occupied spin orbitals than the assemble kernel stages");
@@ -204,14 +187,14 @@ static void xi_build(Context& cx, SOState& s, int nop, const double* x_host, dou
 
 void so_response_xi(Context& cx, SOState& s, int nop, const double* x_host, double* xi)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     check_operators("afesp_ccsd_so_response_xi", nop, x_host, (int64_t)s.o + s.v);
     xi_build(cx, s, nop, x_host, xi);
 }
 
 void so_response_xi_host(Context& cx, SOState& s, int nop, const double* x, double* xi1, double* xi2)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     if (!xi1 || !xi2) throw Error(1, "afesp_ccsd_so_response_xi: a NULL vector");
     const int64_t O = s.o, V = s.v, ov = O * V, o2v2 = O * O * V * V, nvec = ov + o2v2;
     check_count("afesp_ccsd_so_response_xi", nop, x);   // (it sizes the staging buffer; the matrices themselves: so_response_xi)
@@ -249,7 +232,7 @@ SOResponse& so_response_need(SOState& s, const char* who)
 static void response_init(Context& cx, SOState& s, const char* who, int nop, const double* x, int nfreq, const double* omega, const double* gamma,
                           int inc, int max_space)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     const bool cplx = gamma != nullptr;
     SOLambda& L = so_lambda_need(s, who);
     const int64_t O = s.o, V = s.v, N = O + V, nvec = vec_len(s);
@@ -264,9 +247,8 @@ static void response_init(Context& cx, SOState& s, const char* who, int nop, con
     so_response_free(cx, s);
     if (!cx.fits(so_response_bytes(O, V, nop, nsys, max_space, cplx)))
         throw Error(1, std::string(who) + ": the response state of this system (" + std::to_string(max_space) + " basis vectors) does not fit the free device memory");
-    static const bool loaded = (preload_eom_so(), true);   // (the diagonal is the EE state's)
-    (void)loaded;
-    preload_once();
+    preload_eom_so();   // (the diagonal is the EE state's)
+    preload_response_so();
     s.resp = new SOResponse();
     SOResponse& R = *s.resp;
     try {
@@ -319,7 +301,7 @@ static void need_mode(const SOResponse& R, bool cplx, const char* who)
 
 int so_response_iterate(Context& cx, SOState& s, double tol)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     SOResponse& R = so_response_need(s, "afesp_ccsd_so_response_iterate");
     std::fill(R.have_phi.begin(), R.have_phi.end(), 0);   // (the solutions move with every step)
     const int conv = davidson_linear_iterate(cx, R.d, "afesp_ccsd_so_response_", tol, [&](const double* r, double* sigma) { so_eom_sigma(cx, s, r, sigma); });
@@ -329,7 +311,7 @@ int so_response_iterate(Context& cx, SOState& s, double tol)
 
 void so_response_get_vector(Context& cx, SOState& s, int iop, int ifreq, double* r1, double* r2)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     SOResponse& R = so_response_need(s, "afesp_ccsd_so_response_get_vector");
     need_mode(R, false, "afesp_ccsd_so_response_get_vector");
     if (!R.stepped || iop < 0 || iop >= R.nop || ifreq < 0 || ifreq >= R.nfreq || !r1 || !r2)
@@ -343,7 +325,7 @@ void so_response_get_vector(Context& cx, SOState& s, int iop, int ifreq, double*
 
 void so_response_get_vector_complex(Context& cx, SOState& s, int iop, int ifreq, double* r1_re, double* r2_re, double* r1_im, double* r2_im)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     const char* who = "afesp_ccsd_so_response_get_vector_complex";
     SOResponse& R = so_response_need(s, who);
     need_mode(R, true, who);
@@ -371,7 +353,6 @@ struct PhiWork {
         SOLambda& L = *s.lam;
         const int nop = R.nop;
         const int64_t O = s.o, V = s.v, N = O + V, ov = O * V, o2v2 = O * O * V * V, nvec = ov + o2v2;
-        const int nblk = davidson_reduce_blocks(nvec);
         if (lam.empty()) {
             lam.resize(nvec);
             r.resize(nvec);
@@ -388,11 +369,8 @@ struct PhiWork {
                 trD[a] = t;
             }
         }
-        double* partial = cx.scratch("rsp_partial", nblk + 1);
-        LAUNCH(response_dot_kernel, dim3(nblk), partial, L.l1.d, L.l2.d, xj, ov, o2v2);
-        davidson_reduce_final(cx, partial + nblk, partial, 1, nblk);
-        double lr = 0.0;
-        AFESP_HIP(hipMemcpyAsync(&lr, partial + nblk, sizeof(double), hipMemcpyDeviceToHost, cx.stream));
+        double lr = 0.0;   // <lambda, x_j>
+        AFESP_HIP(hipMemcpyAsync(&lr, so_eom_wdot(cx, L.l1.d, L.l2.d, xj, ov, o2v2), sizeof(double), hipMemcpyDeviceToHost, cx.stream));
         AFESP_HIP(hipMemcpyAsync(r.data(), xj, sizeof(double) * nvec, hipMemcpyDeviceToHost, cx.stream));
         cx.sync();
         so_eom_density(cx, s, 1.0, lam.data(), lam.data() + ov, 0.0, r.data(), r.data() + ov, gam.data(), N * N);
@@ -418,7 +396,7 @@ void need_converged(const SOResponse& R, const char* who, int g)
 
 void so_response_function_complex(Context& cx, SOState& s, int nfreq, const double* z, double* out)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     const char* who = "afesp_ccsd_so_response_function_complex";
     SOResponse& R = so_response_need(s, who);
     need_mode(R, true, who);
@@ -466,7 +444,7 @@ void so_response_function_complex(Context& cx, SOState& s, int nfreq, const doub
 
 void so_response_function(Context& cx, SOState& s, int nfreq, const double* omega, double* out)
 {
-    need_plain(cx);
+    so_need_plain(cx, RSP_WHO, RSP_PLAIN);
     const char* who = "afesp_ccsd_so_response_function";
     SOResponse& R = so_response_need(s, who);
     need_mode(R, false, who);

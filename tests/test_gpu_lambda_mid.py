@@ -7,7 +7,7 @@ complex-step definition at small extents and within 1e-13 of its own np.longdoub
 Shapes (o, v spin orbitals), each the smallest that crosses the thresholds named:
   rhf_mid   RHF-fed      n = 14, 5 + 5   o = 10, v = 18   even extents (16-byte staging), o v = 180 and v^2 = 324 rows (64- and 128-row
                                                            tiles), operands above 4096 elements, o v^2 = 3240 rows for the tall kernel
-  fock_odd  Fock-rotated n = 11, 5 + 4   o =  9, v = 13   odd extents (8-byte staging only), every f_ov / f_oo / f_vv term, lam_sum2_kernel's
+  fock_odd  Fock-rotated n = 11, 5 + 4   o =  9, v = 13   odd extents (8-byte staging only), every f_ov / f_oo / f_vv term, so_sum2_kernel's
                                                            f . l1 sum over 117 elements
   rhf_cap   RHF-fed      n = 29, 6 + 6   o = 12, v = 46   o^2 v^2 = 304704 > 262144: the 1024-block cap and a second grid-stride pass of
                                                            lam_l2_assemble_kernel / lam_energy_kernel; v^2 = 2116 >= 2048: the tile-scoring
