@@ -30,6 +30,7 @@ EXPORTS = [
     "afesp_ccsd_so_set_amplitudes", "afesp_ccsd_so_get_tensor", "afesp_ccsd_so_t_ntriples", "afesp_ccsd_so_t",
     "afesp_ccsd_so_lambda_init", "afesp_ccsd_so_lambda_iterate", "afesp_ccsd_so_lambda_energy", "afesp_ccsd_so_lambda_diis",
     "afesp_ccsd_so_get_lambda", "afesp_ccsd_so_set_lambda", "afesp_ccsd_so_density", "afesp_ccsd_so_lambda_t",
+    "afesp_ccsd_so_eom_t",
     "afesp_ccsd_so_density2_build", "afesp_ccsd_so_density2_get", "afesp_ccsd_so_density2_energy", "afesp_ccsd_so_density2_expect",
     "afesp_ccsd_so_orbital_gradient", "afesp_ccsd_so_zvector_apply", "afesp_ccsd_so_zvector_solve", "afesp_ccsd_so_relaxed_density",
     "afesp_ccsd_so_relax_pair_row",
@@ -131,6 +132,7 @@ def load_library():
     L.afesp_ccsd_so_set_lambda.argtypes = [C.c_void_p, _dp, _dp]
     L.afesp_ccsd_so_density.argtypes = [C.c_void_p, _dp, i64]
     L.afesp_ccsd_so_lambda_t.argtypes = [C.c_void_p, i64, i64, C.POINTER(dbl)]
+    L.afesp_ccsd_so_eom_t.argtypes = [C.c_void_p, C.c_int, _opt, _opt, _opt, _opt, _opt, i64, i64, _opt]
     L.afesp_ccsd_so_density2_build.argtypes = [C.c_void_p]
     L.afesp_ccsd_so_density2_get.argtypes = [C.c_void_p, C.c_char_p, _opt, i64]
     L.afesp_ccsd_so_density2_energy.argtypes = [C.c_void_p, _opt]
@@ -855,6 +857,7 @@ class Engine:
     # ---- spin-orbital path: do_ccsd_spinorb (src/ccsd.f90:71-277), do_ccsd_t_spinorb (:1812-1922)
     SO_SHAPES = {"F_vv": "vv", "F_oo": "oo", "F_ov": "ov", "W_oooo": "oooo", "W_vvvv": "vvvv", "W_ovvo": "ovvo", "tau": "oovv",
                  "tau_tilde": "oovv", "oovv": "oovv", "vvvv": "vvvv", "t1": "ov", "t2": "oovv", "f_ov": "ov", "f_oo": "oo", "f_vv": "vv",
+                 "D1": "ov",      # the singles denominators e_i - e_a
                  # of a live Lambda state (status 21 otherwise): H_vvvo is H_abei stored (i,e,a,b), H_ovoo is H_mbij stored (m,b,i,j)
                  "H_ov": "ov", "H_oo": "oo", "H_vv": "vv", "H_oooo": "oooo", "H_vovv": "vovv", "H_ooov": "ooov", "H_ovvo": "ovvo",
                  "H_vvvo": "ovvv", "H_ovoo": "ovoo", "lam_tau": "oovv", "G_vv": "vv", "G_oo": "oo"}
@@ -911,6 +914,12 @@ class Engine:
         self._chk(self.L.afesp_ccsd_so_get_tensor(self.h, name.encode(), buf, buf.size))
         return buf.reshape(dims, order="F")
 
+    def so_levels(self):
+        """The levels of the state's o + v spin orbitals relative to the first virtual one (from the singles denominators e_i - e_a):
+        every difference of levels is that of the state"""
+        d1 = self.so_tensor("D1")
+        return np.concatenate([d1[:, 0], d1[0, 0] - d1[0, :]])
+
     def so_ntriples(self):
         return self.L.afesp_ccsd_so_t_ntriples(self.so_o)
 
@@ -962,6 +971,26 @@ class Engine:
         e = dbl()
         self._chk(self.L.afesp_ccsd_so_lambda_t(self.h, t_begin, t_end, C.byref(e)))
         return e.value
+
+    def so_eom_t(self, omega, L, R, t_begin=0, t_end=None):
+        """The non-iterative triples correction to EOM-EE-CCSD excitation energies: omega[ns], L = [(l1, l2)] and
+        R = [(r1, r2)] per state, laid out as t1 / t2 and biorthonormal (afesp_amd.eom.biorthonormalise) -> delta[ns] over the triples
+        [t_begin, t_end) of do_ccsd_t_spinorb's list.  All states in one call; writes nothing of the state."""
+        if t_end is None:
+            t_end = self.so_ntriples()
+        omega = np.ascontiguousarray(np.atleast_1d(np.asarray(omega, dtype=np.float64)))
+        ns = omega.size
+        if len(L) != ns or len(R) != ns:
+            raise ValueError("so_eom_t: one left and one right vector per excitation energy")
+        cat = lambda vecs, part: np.ascontiguousarray(np.concatenate([_f(x[part]) for x in vecs])) if ns else np.zeros(0)
+        l1, l2, r1, r2 = cat(L, 0), cat(L, 1), cat(R, 0), cat(R, 1)
+        n1, n2 = self.so_o * self.so_v, (self.so_o * self.so_v) ** 2
+        if ns and (l1.size != ns * n1 or r1.size != ns * n1 or l2.size != ns * n2 or r2.size != ns * n2):
+            raise ValueError("so_eom_t: vectors are not laid out as t1 / t2 of this state")
+        out = np.zeros(max(ns, 1))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.afesp_ccsd_so_eom_t(self.h, ns, ptr(omega), ptr(l1), ptr(l2), ptr(r1), ptr(r2), t_begin, t_end, ptr(out)))
+        return out[:ns]
 
     # ---- the two-particle density of the spin-orbital state (include/afesp.h, DESIGN.md 4.17; afesp_amd.density drives them).  All need a
     # live Lambda state; get / energy / expect need a build of the current t and lambda (status 21 otherwise)

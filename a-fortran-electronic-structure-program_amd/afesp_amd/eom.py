@@ -179,6 +179,53 @@ def left_table(omega_left, omega_right, info):
     return "\n".join(lines)
 
 
+# ---------------------------------------------------------------------------------------------------------------- triples correction
+INTRUDER_GAP = 0.05    # Eh.  A diagnostic constant, not a tolerance: a state whose omega comes this close to a triples denominator is flagged
+
+
+def triples_min_gap(omega, levels, o):
+    """|omega - (e_a + e_b + e_c - e_i - e_j - e_k)| per root at the smallest such difference, that of the three highest occupied and the
+    three lowest virtual levels: the denominator an excitation energy from below meets first"""
+    lev = np.asarray(levels, dtype=np.float64)
+    eo, ev = np.sort(lev[:o]), np.sort(lev[o:])
+    omega = np.atleast_1d(np.asarray(omega, dtype=np.float64))
+    if eo.size < 3 or ev.size < 3:
+        return np.full(omega.size, np.inf)
+    return np.abs(omega - float(ev[:3].sum() - eo[-3:].sum()))
+
+
+def so_eom_triples_correction(eng, omega, L, R, t_begin=0, t_end=None, levels=None):
+    """The non-iterative triples correction to the EOM-EE-CCSD excitation energies omega from biorthonormal left vectors L
+    (biorthonormalise) and right vectors R, all states in one library call -> (delta, omega + delta, info).  Refuses vectors with
+    |<L_k, R_k> - 1| > 1e-8.  info["min_gap"]: the smallest |omega_k - (e_a + e_b + e_c - e_i - e_j - e_k)| from the levels (the state's
+    Fock diagonal, fetched unless given); info["intruder"]: the roots whose gap is below INTRUDER_GAP.  A sub-range [t_begin, t_end) of
+    the triples gives that shard's part of delta (ranks add theirs up)."""
+    omega = np.atleast_1d(np.asarray(omega, dtype=np.float64))
+    if not (len(omega) == len(L) == len(R)):
+        raise ValueError("so_eom_triples_correction: omega, L and R differ in length")
+    for k in range(len(omega)):
+        ov = dot(L[k], R[k])
+        if abs(ov - 1.0) > 1e-8:
+            raise ValueError(f"so_eom_triples_correction: <L, R> of root {k + 1} is {ov:.12f}, not 1: biorthonormalise the vectors first")
+    delta = eng.so_eom_t(omega, L, R, t_begin, t_end)
+    if levels is None:
+        levels = eng.so_levels()
+    gap = triples_min_gap(omega, levels, eng.so_o)
+    info = dict(min_gap=gap, intruder=[k for k in range(len(omega)) if gap[k] < INTRUDER_GAP])
+    return delta, omega + delta, info
+
+
+def triples_table(omega, delta, info):
+    """The lines the Fortran host prints for eom_triples: root, omega, delta, omega + delta in Eh and eV, one line per flagged state"""
+    lines = ["  root        omega / Eh   delta omega / Eh   omega+delta / Eh   omega+delta / eV"]
+    for k, w in enumerate(omega):
+        lines.append(f"  {k + 1:4d}  {w:16.10f}  {delta[k]:16.10f}  {w + delta[k]:16.10f}  {(w + delta[k]) * HARTREE_EV:16.8f}")
+    for k in info["intruder"]:
+        lines.append(f"  root {k + 1}: omega is within {info['min_gap'][k]:.4f} Eh of a triples denominator (below {INTRUDER_GAP} Eh): "
+                     "the correction is not reliable")
+    return "\n".join(lines)
+
+
 # ---------------------------------------------------------------------------------------------------------------- EOM-IP / EOM-EA
 SECTOR_IP, SECTOR_EA = 1, 2
 

@@ -53,6 +53,7 @@ class SystemIn:
     polar_gamma: float = 0.0        # ... > 0: every polar_omega is solved at omega + i gamma (damped response: Re / Im alpha-bar and sigma(omega))
     polar_c6_npts: int = 0          # ... > 0: alpha-bar(iu) on this many Casimir-Polder grid points and the homo-dimer C6 (response.casimir_polder_grid)
     eom_left: bool = False          # ... and their left eigenvectors, from the right ones as guess (eom.so_eom_left_solve); needs eom_nroots > 0
+    eom_triples: bool = False       # ... and the non-iterative triples correction to every root (eom.so_eom_triples_correction); needs eom_left
     eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
     # derived by the calc_type switch (src/system.f90:116-165)
@@ -194,6 +195,11 @@ def read_els_in(path: str) -> SystemIn:
         raise ValueError("invalid input file format!")
     if sysin.eom_left and sysin.eom_nroots == 0:
         raise ValueError("eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!")
+    if not isinstance(sysin.eom_triples, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.eom_triples and not (sysin.eom_nroots > 0 and sysin.eom_left):
+        raise ValueError("eom_triples needs eom_nroots > 0 and eom_left: the triples correction contracts the left and right vectors of "
+                         "the EOM-EE-CCSD roots!")
     if not isinstance(sysin.cc_polar, bool):
         raise ValueError("invalid input file format!")
     if sysin.cc_polar and sysin.calc_type not in CC_DENSITY_TYPES:

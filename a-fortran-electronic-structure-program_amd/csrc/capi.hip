@@ -165,7 +165,7 @@ int eom_iterate_entry(afesp_ctx* ctx, const char* who, EomKind kind, const int* 
 
 extern "C" {
 
-int afesp_version(void) { return 5; }
+int afesp_version(void) { return 6; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -912,6 +912,12 @@ int afesp_ccsd_so_lambda_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, doubl
         const double e = so_lambda_triples(cx, ctx->sv.so, t_begin, t_end);
         if (e_lt) *e_lt = e;
     });
+}
+
+int afesp_ccsd_so_eom_t(afesp_ctx* ctx, int nstates, const double* omega, const double* l1, const double* l2, const double* r1,
+                        const double* r2, int64_t t_begin, int64_t t_end, double* delta)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_triples(cx, ctx->sv.so, nstates, omega, l1, l2, r1, r2, t_begin, t_end, delta); });
 }
 
 // ---------------------------------------------------------------- open-shell (UHF-based) path

@@ -73,6 +73,10 @@ void so_density_assemble(Context& cx, SOState& s, double* D, const double* doo, 
 void so_relax_free(Context& cx, SOLambda& L);   // relax_so.hip
 // Lambda-CCSD(T): the triples [t_begin, t_end) of so_triples' own list with l1 / l2 in the left factor (triples.hip)
 double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end);
+// The triples correction to EOM-EE-CCSD excitation energies (triples.hip): nstates left / right vectors laid out as t1 / t2,
+// one after the other (host); delta[nstates].  Needs no Lambda state.
+void so_eom_triples(Context& cx, SOState& s, int nstates, const double* omega, const double* l1, const double* l2, const double* r1,
+                    const double* r2, int64_t t_begin, int64_t t_end, double* delta);
 void preload_lambda_so();
 
 }  // namespace afesp

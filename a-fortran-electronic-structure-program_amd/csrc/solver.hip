@@ -429,7 +429,7 @@ void Solver::so_fetch_tensor(Context& cx, const char* name, double* out, int64_t
     struct { const char* n; const Tensor* t; } tab[] = {
         {"F_vv", &s.F_vv}, {"F_oo", &s.F_oo}, {"F_ov", &s.F_ov}, {"W_oooo", &s.W_oooo}, {"W_vvvv", &s.W_vvvv},
         {"W_ovvo", &s.W_ovvo}, {"tau", &s.tau}, {"tau_tilde", &s.tau_t}, {"oovv", &s.oovv}, {"vvvv", &s.vvvv},
-        {"t1", &s.t1}, {"t2", &s.t2}, {"f_ov", &s.f_ov}, {"f_oo", &s.f_oo}, {"f_vv", &s.f_vv}};
+        {"t1", &s.t1}, {"t2", &s.t2}, {"f_ov", &s.f_ov}, {"f_oo", &s.f_oo}, {"f_vv", &s.f_vv}, {"D1", &s.D1}};
     // the intermediates of a live Lambda state (lambda_so.h), in its storage; G_vv / G_oo as of the last iteration or density
     static const char* const lam_names[] = {"H_ov", "H_oo", "H_vv", "H_oooo", "H_vovv", "H_ooov", "H_ovvo", "H_vvvo", "H_ovoo", "lam_tau", "G_vv", "G_oo"};
     for (size_t q = 0; q < sizeof(lam_names) / sizeof(lam_names[0]); ++q)

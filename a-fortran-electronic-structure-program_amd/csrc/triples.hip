@@ -214,6 +214,47 @@ __global__ __launch_bounds__(256) void triples_build_tt_kernel(double* tt, const
     }
 }
 
+// The right operand pair of the EOM-CCSD triples correction (so_eom_triples) in one pass: two runs of the padded summation index, one
+// behind the other, in so_triples' layout (kappa; b,c,p) / (kappa; a,r,q) --
+//   rvt, run 0:  kappa<v: <fp||bc>;         kappa=v+m: r2(m,p,c,b)      rtt, run 0:  kappa<v: r2(q,r,a,f);   kappa=v+m: -<ma||qr>
+//   rvt, run 1:  kappa<v: gR(f,p,b,c);      kappa=v+m: t2(m,p,c,b)      rtt, run 1:  kappa<v: t2(q,r,a,f);   kappa=v+m: -gR(m,a,q,r)
+// and zero in the padding rows v+o <= kappa < Kc of every run.
+__global__ __launch_bounds__(256) void eom_t_build_right_kernel(double* __restrict__ rvt, double* __restrict__ rtt, const double* __restrict__ vovv,
+                                                              const double* __restrict__ ovoo, const double* __restrict__ r2,
+                                                              const double* __restrict__ t2, const double* __restrict__ gv,
+                                                              const double* __restrict__ go, int o, int v, int Kc)
+{
+    const int64_t O = o, V = v;
+    const int64_t nvt = 2 * (int64_t)Kc * V * V * O, ntt = 2 * (int64_t)Kc * V * O * O;
+    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < nvt + ntt; x += (int64_t)gridDim.x * blockDim.x) {
+        double val = 0.0;
+        if (x < nvt) {
+            const int kap = (int)(x % Kc);
+            int64_t r = x / Kc;
+            const int64_t b = r % V;
+            r /= V;
+            const int64_t c = r % V;
+            r /= V;
+            const int64_t p = r % O, run = r / O;
+            if (kap < v) val = (run ? gv : vovv)[kap + V * (p + O * (b + V * c))];
+            else if (kap < v + o) val = (run ? t2 : r2)[(kap - v) + O * (p + O * (c + V * b))];
+            rvt[x] = val;
+        } else {
+            const int64_t y = x - nvt;
+            const int kap = (int)(y % Kc);
+            int64_t r = y / Kc;
+            const int64_t a = r % V;
+            r /= V;
+            const int64_t rr = r % O;
+            r /= O;
+            const int64_t q = r % O, run = r / O;
+            if (kap < v) val = (run ? t2 : r2)[q + O * (rr + O * (a + V * (int64_t)kap))];
+            else if (kap < v + o) val = -(run ? go : ovoo)[(kap - v) + O * (a + V * (q + O * rr))];
+            rtt[y] = val;
+        }
+    }
+}
+
 // Everything about a (T) evaluation that depends only on (o, v, triple range): chunking, per-chunk GEMM column tables,
 // per-triple metadata, the cube-orbit list.  Built once, kept in device memory, reused by every later call.
 struct TriplesPlan {
@@ -241,6 +282,7 @@ struct TriplesPlan {
     GettGroup* gdesc = nullptr;    // fused scheme: group descriptors of all chunks
     bool use_tg = false;           // fused scheme: the products run on tgemm_kernel (tgemm.h) instead of the grouped gett_kernel
     TgGroup* tgdesc = nullptr;
+    std::vector<TgGroup> tg_host;  // spin-orbital plan: the descriptors as uploaded (so_eom_triples derives its two-run copies from them)
     uint32_t* tables32 = nullptr;  // [rowA (v^2) | per chunk: colB]  byte offsets
     bool c_pairs = false;          // columns (x, x + 1), x even, of a block are adjacent in the cube-blocked layout: v even (tgemm.h)
     // fused scheme: the tuning knobs the plan was shaped by (knobs.h: every knob follows the environment per C-ABI call).  The block size
@@ -452,6 +494,7 @@ static TriplesPlan* plan_for(Context& cx, void*& slot, int o, int v, int64_t t_b
             ch.tg_max_ntiles = mx;
         }
         p->tgdesc = (TgGroup*)cx.scratch("so_tgdesc", (int64_t)(tg.size() * sizeof(TgGroup) / sizeof(double) + 1));
+        p->tg_host = tg;
         AFESP_HIP(hipMemcpyAsync(p->tgdesc, tg.data(), tg.size() * sizeof(TgGroup), hipMemcpyHostToDevice, cx.stream));
     }
     AFESP_HIP(hipMemcpyAsync(p->meta, metas.data(), metas.size() * sizeof(TripleMeta), hipMemcpyHostToDevice, cx.stream));
@@ -1332,6 +1375,156 @@ double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end
     return h[0];
 }
 
+// The non-iterative triples correction to EOM-EE-CCSD excitation energies: per state
+//   delta = sum_{i<j<k} sum_abc P(l) P(m) / (D + omega) / 6,   l = wc_l[g] + wd_l,   m = wc_r2[g] + wc_t2[gR]
+// on so_triples' plan and chunking with two pools as Lambda-(T).  The left operand pair is Lambda-(T)'s with the state's l2; the right pair
+// carries both products of m under one summation index of two runs (eom_t_build_right_kernel), which the LDS-DMA kernel walks through the
+// two-run form of its descriptors and the gather kernel through its K tables: one GEMM family fills the right pool.  gR, the one-index
+// transform of g by r1, is formed per state by six contractions.  Every buffer carries a name of its own (et_*): nothing of the state,
+// of Lambda, of an EOM or response state or of the operand copies of (T) and Lambda-(T) is written.
+void so_eom_triples(Context& cx, SOState& s, int nstates, const double* omega, const double* l1, const double* l2, const double* r1,
+                    const double* r2, int64_t t_begin, int64_t t_end, double* delta)
+{
+    if (cx.rec) throw Error(1, "afesp_ccsd_so_eom_t: the EOM triples correction is not part of a recorded (launch-fused) sequence");
+    if (!s.ready) throw Error(1, "afesp_ccsd_so_eom_t: no converged spin-orbital CCSD state in this context");
+    if (nstates < 1 || !omega || !l1 || !l2 || !r1 || !r2 || !delta)
+        throw Error(1, "afesp_ccsd_so_eom_t: nstates < 1 or a NULL argument");
+    so_triples_guard(s, "afesp_ccsd_so_eom_t");
+    const int o = s.o, v = s.v;
+    const int64_t O = o, V = v, v2 = V * V, n1 = O * V, n2 = O * O * V * V;
+    const int64_t nt8 = (V + TT - 1) / TT, vp3 = nt8 * nt8 * nt8 * CUBE;
+    const int64_t Kc = (V + O + 15) / 16 * 16;
+    for (int st = 0; st < nstates; ++st) delta[st] = 0.0;
+    t_begin = std::max<int64_t>(0, t_begin);
+    t_end = std::min<int64_t>(so_triples_count(o), t_end);
+    if (o < 3 || v < 3 || t_end <= t_begin) return;
+    TriplesPlan* p = plan_for(cx, s.tplan, o, v, t_begin, t_end);
+    if (knobs().t_debug)
+        fprintf(stderr, "afesp EOM-(T): o %d v %d states %d triples %lld per chunk %lld chunks %zu kernel %s\n", o, v, nstates,
+                (long long)(t_end - t_begin), (long long)p->nb, p->chunks.size(), p->use_tg ? "tgemm" : "gett");
+    {
+        auto it = cx.cache.find("lt_xpool");
+        const size_t want = (size_t)(3 * p->nb * vp3) * sizeof(double);
+        if ((it == cx.cache.end() || it->second.second < want) && !cx.fits((double)want))
+            throw Error(1, "afesp_ccsd_so_eom_t: the second block pool does not fit the free device memory (lower AFESP_T_POOL_GIB)");
+    }
+    // every cached buffer first (a buffer that grows bumps the scratch epoch the plan and the (T) operand record are compared with)
+    double* Mpool = cx.scratch("t_xpool", 3 * p->nb * vp3);
+    double* Lpool = cx.scratch("lt_xpool", 3 * p->nb * vp3);
+    double* partial = cx.scratch("t_partial", std::max<int64_t>((int64_t)p->norb * p->nb, 512));
+    double* sum_tmp = cx.scratch("t_sum_tmp", 6 * 128);
+    Tensor lvt = view(cx.scratch("et_lvt", Kc * v2 * O), {Kc, V, V, O}), ltt = view(cx.scratch("et_ltt", Kc * V * O * O), {Kc, V, O, O});
+    double* rvt = cx.scratch("et_rvt", 2 * Kc * v2 * O);
+    double* rtt = cx.scratch("et_rtt", 2 * Kc * V * O * O);
+    Tensor dl1 = view(cx.scratch("et_l1", n1), {O, V}), dl2 = view(cx.scratch("et_l2", n2), {O, O, V, V});
+    Tensor dr1 = view(cx.scratch("et_r1", n1), {O, V}), dr2 = view(cx.scratch("et_r2", n2), {O, O, V, V});
+    Tensor gv = view(cx.scratch("et_gv", V * O * v2), {V, O, V, V}), go = view(cx.scratch("et_go", O * V * O * O), {O, V, O, O});
+    int64_t* ktab = (int64_t*)cx.scratch("et_ktab", 4 * Kc);
+    int64_t ndesc = 0;
+    for (const TriplesPlan::Chunk& ch : p->chunks) ndesc += ch.tg_ngroups + 1;
+    TgGroup* tgd = (TgGroup*)cx.scratch("et_tgdesc", (int64_t)((ndesc + 1) * sizeof(TgGroup) / sizeof(double) + 1));
+    p = plan_for(cx, s.tplan, o, v, t_begin, t_end);   // (its tables live in cached buffers too)
+    const SOTOperands ops = so_t_operands(cx, s);      // <pq||xy> patches and the levels: (T)'s own copies, rebuilt only if stale
+    // the two runs of the right pair as the kernels address them: second A panel / second K half Kc v^2 o (Kc v o^2) elements behind the first
+    std::vector<int64_t> hk((size_t)(4 * Kc));
+    std::vector<TgGroup> htg;
+    if (p->use_tg) {
+        htg = p->tg_host;
+        for (const TriplesPlan::Chunk& ch : p->chunks)
+            for (int gi = 0; gi < ch.tg_ngroups; ++gi) {
+                TgGroup& d = htg[(size_t)(ch.tg_off + gi)];
+                d.a2 = d.a1 + Kc * v2 * O;
+                d.b1 = 0;
+                d.b2 = Kc * V * O * O;
+                d.nk = 2 * d.nk1;
+            }
+        if ((int64_t)htg.size() > ndesc + 1) throw Error(2, "afesp_ccsd_so_eom_t: descriptor count of the plan");
+        AFESP_HIP(hipMemcpyAsync(tgd, htg.data(), htg.size() * sizeof(TgGroup), hipMemcpyHostToDevice, cx.stream));
+    } else {
+        for (int64_t x = 0; x < Kc; ++x) {
+            hk[(size_t)x] = x;
+            hk[(size_t)(Kc + x)] = Kc * v2 * O + x;
+            hk[(size_t)(2 * Kc + x)] = x;
+            hk[(size_t)(3 * Kc + x)] = Kc * V * O * O + x;
+        }
+        AFESP_HIP(hipMemcpyAsync(ktab, hk.data(), hk.size() * sizeof(int64_t), hipMemcpyHostToDevice, cx.stream));
+    }
+    cx.sync();   // the host vectors may die with an exception below
+    auto products = [&](const TriplesPlan::Chunk& ch) {
+        if (p->use_tg) {
+            TgProblem tp{rvt, rtt, Mpool, p->tables32, p->tables + p->off_Cm, (int)v2, p->c_pairs, (int)((V + O - (Kc - TG_BK) + 3) / 4)};
+            AFESP_HIP(tgemm_launch(tp, tgd + ch.tg_off, ch.tg_ngroups, ch.tg_tiles, ch.tg_max_ntiles, cx.stream, cx.tg));
+            return;
+        }
+        const int64_t* tabs = p->tables + ch.tab_off;
+        for (const TriplesPlan::Group& g : ch.groups) {
+            GettProblem gp;
+            gp.A = rvt + Kc * v2 * g.r;
+            gp.B = rtt;
+            gp.C = Mpool;
+            gp.offAm = p->tables + p->off_Am; gp.offAk = ktab; gp.offBk = ktab + 2 * Kc;
+            gp.offBn = tabs + g.start;
+            gp.offCm = p->tables + p->off_Cm; gp.offCn = tabs + ch.ntab + g.start;
+            gp.M = (int)v2; gp.N = (int)g.N; gp.K = (int)(2 * Kc);
+            gp.alpha = 1.0; gp.beta = 0.0;
+            gp.nbatch = 1; gp.batchA = gp.batchB = gp.batchC = nullptr;
+            gp.a_kcontig = gp.b_kcontig = true;
+            gp.wide = true;   // (as so_chunk_products: K-contiguous runs, Kc a multiple of 16, the second run an even shift)
+            AFESP_HIP(gett_launch(gp, cx.ws, cx.stream));
+        }
+    };
+    const auto C = contractor(cx);
+    // the halves of the left pair that no state changes
+    if (Kc != V + O) {
+        AFESP_HIP(hipMemsetAsync(lvt.d, 0, sizeof(double) * Kc * v2 * O, cx.stream));
+        AFESP_HIP(hipMemsetAsync(ltt.d, 0, sizeof(double) * Kc * V * O * O, cx.stream));
+    }
+    permute_add(cx, 1.0, s.vovv, "fpbc", 0.0, rows_of(lvt, 0, V), "fbcp");
+    permute_add(cx, -1.0, s.ovoo, "maqr", 0.0, rows_of(ltt, V, O), "marq");
+    SOStamps prof(cx);
+    for (int st = 0; st < nstates; ++st) {
+        AFESP_HIP(hipMemcpyAsync(dl1.d, l1 + st * n1, sizeof(double) * n1, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(dl2.d, l2 + st * n2, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(dr1.d, r1 + st * n1, sizeof(double) * n1, hipMemcpyHostToDevice, cx.stream));
+        AFESP_HIP(hipMemcpyAsync(dr2.d, r2 + st * n2, sizeof(double) * n2, hipMemcpyHostToDevice, cx.stream));
+        permute_add(cx, 1.0, dl2, "mpcb", 0.0, rows_of(lvt, V, O), "mbcp");
+        permute_add(cx, 1.0, dl2, "qraf", 0.0, rows_of(ltt, 0, V), "farq");
+        // gR(f,p,b,c) = sum_d <fd||bc> r(p,d) - sum_l r(l,b) <fp||lc> - sum_l r(l,c) <fp||bl>,   <fp||lc> = <pf||cl>
+        C(1.0, s.vvvv, "fdbc", dr1, "pd", 0.0, gv, "fpbc");
+        C(-1.0, dr1, "lb", s.ovvo, "pfcl", 1.0, gv, "fpbc");
+        C(1.0, dr1, "lc", s.ovvo, "pfbl", 1.0, gv, "fpbc");
+        // gR(m,a,q,r) = sum_d <ma||dr> r(q,d) + sum_d <ma||qd> r(r,d) - sum_l r(l,a) <ml||qr>
+        C(1.0, s.ovvo, "madr", dr1, "qd", 0.0, go, "maqr");
+        C(-1.0, s.ovvo, "madq", dr1, "rd", 1.0, go, "maqr");
+        C(-1.0, dr1, "la", s.oooo, "mlqr", 1.0, go, "maqr");
+        {
+            const int64_t n = 2 * Kc * V * O * (V + O);
+            AFESP_KLAUNCH(eom_t_build_right_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, cx.stream, rvt, rtt,
+                          s.vovv.d, s.ovoo.d, dr2.d, s.t2.d, gv.d, go.d, o, v, (int)Kc);
+            AFESP_HIP(hipGetLastError());
+        }
+        TriplesIn in{s.lev ? s.lev : ops.e_so, dl1.d, ops.vs.d, s.fock ? s.f_ov.d : nullptr, dl2.d, o, v};
+        k_fill(cx, cx.scal, 1, 0.0);
+        for (const TriplesPlan::Chunk& ch : p->chunks) {
+            prof.stamp();
+            products(ch);
+            so_chunk_products(cx, p, ch, lvt, ltt, Lpool);
+            prof.stamp();
+            if (s.fock)
+                AFESP_KLAUNCH((triples_so_eom_orbit_kernel<true>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Mpool, Lpool,
+                              p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt, omega[st]);
+            else
+                AFESP_KLAUNCH((triples_so_eom_orbit_kernel<false>), dim3(p->norb, ch.nt), dim3(256), 0, cx.stream, partial, Mpool, Lpool,
+                              p->meta + ch.meta_off, p->orbits, in, p->norb * ch.nt, omega[st]);
+            AFESP_HIP(hipGetLastError());
+            prof.stamp();
+            sum_partials(cx, cx.scal, partial, 1, p->norb * ch.nt, sum_tmp);
+        }
+        delta[st] = host_scalars(cx, 1)[0];   // (synchronises: the next state's uploads overwrite et_l* / et_r* after this state's readers)
+    }
+    prof.read();
+}
+
 void preload_triples()
 {
     first_use_touch(reinterpret_cast<const void*>(triples_sum_kernel));
@@ -1345,6 +1538,9 @@ void preload_triples()
     first_use_touch(reinterpret_cast<const void*>(triples_so_orbit_kernel<true>));
     first_use_touch(reinterpret_cast<const void*>(triples_so_lambda_orbit_kernel<true>));
     first_use_touch(reinterpret_cast<const void*>(triples_so_lambda_orbit_kernel<false>));
+    first_use_touch(reinterpret_cast<const void*>(triples_so_eom_orbit_kernel<true>));
+    first_use_touch(reinterpret_cast<const void*>(triples_so_eom_orbit_kernel<false>));
+    first_use_touch(reinterpret_cast<const void*>(eom_t_build_right_kernel));
     (void)hipGetLastError();
     preload_tgemm();
 }

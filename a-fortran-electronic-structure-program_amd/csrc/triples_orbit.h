@@ -515,11 +515,12 @@ __global__ __launch_bounds__(256, 3) void triples_so_orbit_kernel(double* __rest
 // The LDS of the (T) kernel serves both pools in turn: R_t is staged, every thread keeps P(R_t) at its twelve elements in registers,
 // and after a barrier the same cubes are restaged with R_l (whose loads were issued before the first barrier's readers started).
 // `in` carries l1 and l2 where the (T) kernel has t1 and t2 -- the right factor is the connected part alone and needs neither.
-template <bool FOCK>
-__global__ __launch_bounds__(256, 3) void triples_so_lambda_orbit_kernel(double* __restrict__ partial, const double* __restrict__ Xpool,
-                                                                        const double* __restrict__ Lpool,
-                                                                        const TripleMeta* __restrict__ meta,
-                                                                        const int* __restrict__ orbits, TriplesIn in, int nblk_total)
+// SHIFT = true (the EOM-CCSD triples correction): the right pool holds the excited state's numerator m instead of R_t, `in`
+// carries the left vector's l1 / l2, and the excitation energy omega is added once to the D formed below:  P(L) P(m) / (D + omega) / 6.
+template <bool FOCK, bool SHIFT>
+__device__ __forceinline__ void so_lambda_orbit_body(double* __restrict__ partial, const double* __restrict__ Xpool,
+                                                     const double* __restrict__ Lpool, const TripleMeta* __restrict__ meta,
+                                                     const int* __restrict__ orbits, const TriplesIn in, int nblk_total, const double omega)
 {
     __shared__ __attribute__((aligned(16))) double wl[6 * CUBE];   // R_t, then R_l, on the six cubes of the orbit
     __shared__ double vp[27 * PATCH];                              // <pq||xy> patches for pairs (j,k), (i,k), (i,j)
@@ -614,7 +615,8 @@ __global__ __launch_bounds__(256, 3) void triples_so_lambda_orbit_kernel(double*
         if (h == 1) asm volatile("" : "+v"(l2v) : "v"(acc));   // the second orbit's reads stay behind the first orbit's arithmetic
         const int l[3] = {l0, l1, l2v};
         const bool live = tile[0] * TT + l[0] < v && tile[1] * TT + l[1] < v && tile[2] * TT + l[2] < v;
-        const double D = eo - evl[l[0]] - evl[TT + l[1]] - evl[2 * TT + l[2]];
+        const double D0 = eo - evl[l[0]] - evl[TT + l[1]] - evl[2 * TT + l[2]];
+        const double D = SHIFT ? D0 + omega : D0;
         const double rD = rcp_nr(D);
         double L[6], l1v[3][3], V[3][3][3];
 #pragma unroll
@@ -668,6 +670,26 @@ __global__ __launch_bounds__(256, 3) void triples_so_lambda_orbit_kernel(double*
     __syncthreads();
     // 3 (the identity above) / 6 (i<j<k of the 36 ordered terms) / |H|
     if (t == 0) partial[blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) / (2.0 * nH);
+}
+
+template <bool FOCK>
+__global__ __launch_bounds__(256, 3) void triples_so_lambda_orbit_kernel(double* __restrict__ partial, const double* __restrict__ Xpool,
+                                                                        const double* __restrict__ Lpool,
+                                                                        const TripleMeta* __restrict__ meta,
+                                                                        const int* __restrict__ orbits, TriplesIn in, int nblk_total)
+{
+    so_lambda_orbit_body<FOCK, false>(partial, Xpool, Lpool, meta, orbits, in, nblk_total, 0.0);
+}
+
+// The EOM-CCSD triples correction (triples.hip, so_eom_triples): Mpool holds m = wc_r2[g] + wc_t2[gR] (no disconnected part on the right),
+// Lpool the left vector's connected numerator; in.t1 / in.t2 are its l1 / l2.
+template <bool FOCK>
+__global__ __launch_bounds__(256, 3) void triples_so_eom_orbit_kernel(double* __restrict__ partial, const double* __restrict__ Mpool,
+                                                                     const double* __restrict__ Lpool,
+                                                                     const TripleMeta* __restrict__ meta,
+                                                                     const int* __restrict__ orbits, TriplesIn in, int nblk_total, double omega)
+{
+    so_lambda_orbit_body<FOCK, true>(partial, Mpool, Lpool, meta, orbits, in, nblk_total, omega);
 }
 
 }  // namespace afesp

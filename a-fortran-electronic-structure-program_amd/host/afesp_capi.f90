@@ -16,7 +16,7 @@ module afesp_capi
              afesp_fcidump_scan, afesp_read_fcidump, afesp_read_fcidump_uhf, &
              afesp_mo_fock_ro, afesp_read_fcidump_rohf, afesp_mo_rotate_uhf, afesp_ccsd_uso_init_fock, &
              afesp_ccsd_so_lambda_init, afesp_ccsd_so_lambda_energy, afesp_ccsd_so_lambda_iterate, afesp_ccsd_so_lambda_diis, &
-             afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, &
+             afesp_ccsd_so_density, afesp_ccsd_so_lambda_t, afesp_ccsd_so_eom_t, afesp_ccsd_so_get_tensor, &
              afesp_ccsd_so_density2_build, afesp_ccsd_so_density2_get, afesp_ccsd_so_density2_energy, afesp_ccsd_so_density2_expect, &
              afesp_ccsd_so_zvector_solve, afesp_ccsd_so_relaxed_density, &
              afesp_ccsd_so_eom_init, afesp_ccsd_so_eom_sigma, afesp_ccsd_so_eom_guess, afesp_ccsd_so_eom_set_guess, &
@@ -702,6 +702,26 @@ module afesp_capi
          type(c_ptr), value :: ctx
          integer(c_int64_t), value :: t_begin, t_end
          real(c_double), intent(out) :: e_lt
+         integer(c_int) :: rc
+      end function
+      !> The non-iterative triples correction to nstates EOM-EE-CCSD excitation energies from biorthonormal left and right vectors (laid out
+      !> as t1 / t2, one state after the other) over the triples [t_begin, t_end) of afesp_ccsd_so_t's list; delta(nstates)
+      function afesp_ccsd_so_eom_t(ctx, nstates, omega, l1, l2, r1, r2, t_begin, t_end, delta) bind(C, name='afesp_ccsd_so_eom_t') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: nstates
+         real(c_double), intent(in) :: omega(*), l1(*), l2(*), r1(*), r2(*)
+         integer(c_int64_t), value :: t_begin, t_end
+         real(c_double), intent(out) :: delta(*)
+         integer(c_int) :: rc
+      end function
+      !> a named tensor of the spin-orbital state (name NUL-terminated; 'D1': the singles denominators e_i - e_a, (o, v))
+      function afesp_ccsd_so_get_tensor(ctx, name, buf, capacity) bind(C, name='afesp_ccsd_so_get_tensor') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr, c_char
+         type(c_ptr), value :: ctx
+         character(kind=c_char), intent(in) :: name(*)
+         real(c_double), intent(out) :: buf(*)
+         integer(c_int64_t), value :: capacity
          integer(c_int) :: rc
       end function
       !> ---- multi-GPU: one process per GPU; the OpenMP reduction of the reference's (T) loop (src/ccsd.f90:2091) becomes a

@@ -63,6 +63,8 @@ module host_config
       integer :: eom_nroots = 0
       ! ... and their left eigenvectors, from the right ones as guess (needs eom_nroots > 0)
       logical :: eom_left = .false.
+      ! ... and the non-iterative triples correction to every root from its left and right vector (needs eom_left)
+      logical :: eom_triples = .false.
       ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
       integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
       ! after a converged spin-orbital CCSD: the EOM-CCSD polarisability alpha(omega) of the operators in dipx.dat / dipy.dat / dipz.dat
@@ -86,14 +88,14 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left, cc_rdm2, cc_relaxed, cc_polar
+      logical :: eom_left, eom_triples, cc_rdm2, cc_relaxed, cc_polar
       real(dp) :: polar_omega(8), polar_gamma
       integer :: polar_c6_npts
       real(dp), parameter :: omega_unset = huge(1.0_dp)
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, cc_rdm2, cc_relaxed, &
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, eom_triples, cc_rdm2, cc_relaxed, &
          cc_polar, polar_omega, polar_gamma, polar_c6_npts
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
@@ -105,7 +107,7 @@ contains
       fno_n_virt = d%fno_n_virt; fno_occ_tol = d%fno_occ_tol; fcidump_active = d%fcidump_active
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
       cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
-      eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left
+      eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left; eom_triples = d%eom_triples
       cc_polar = d%cc_polar; polar_omega = omega_unset
       polar_gamma = d%polar_gamma; polar_c6_npts = d%polar_c6_npts
       inquire (file='els.in', exist=there)
@@ -191,6 +193,10 @@ contains
       cfg%eom_left = eom_left
       if (eom_left .and. eom_nroots == 0) call fail('system::read_system_in', &
          'eom_left needs eom_nroots > 0: the left eigenvectors are those of the EOM-EE-CCSD roots it asks for!')
+      cfg%eom_triples = eom_triples
+      if (eom_triples .and. .not. (eom_nroots > 0 .and. eom_left)) call fail('system::read_system_in', &
+         'eom_triples needs eom_nroots > 0 and eom_left: the triples correction contracts the left and right vectors of '// &
+         'the EOM-EE-CCSD roots!')
       cfg%cc_polar = cc_polar
       if (cc_polar .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
          trim(calc_type)//' takes no cc_polar: the response equations run on the spin-orbital CCSD types!')
@@ -1989,8 +1995,135 @@ contains
                abs(omega_l(k) - omega(k)), res_l(k)
          end do
          write (out, '(75("-"))')
+         if (cfg%eom_triples) call eom_triples_report(o, v, nr, omega)
       end if
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for EOM-CCSD:', seconds() - te, 's'
+   end subroutine
+   !> eom_triples: the non-iterative triples correction to the nr roots just solved.  The left vectors are biorthonormalised against the
+   !> right ones inside every cluster of degenerate roots (S^-1 L, S_jk = <L_j, R_k> = sum l1 r1 + 1/4 sum l2 r2), all roots go to the
+   !> library in one call on this rank's shard of the i<j<k list, and the shards are summed as in the (T) branches.  A root whose omega
+   !> comes within 0.05 Eh (a diagnostic constant) of the smallest triples denominator is flagged.
+   subroutine eom_triples_report(o, v, nr, omega)
+      integer, intent(in) :: o, v, nr
+      real(dp), intent(in) :: omega(:)
+      real(dp), parameter :: hartree_ev = 27.211386245988_dp, intruder_gap = 0.05_dp, degeneracy_tol = 1.0e-6_dp
+      real(dp), allocatable :: r1(:, :), r2(:, :), l1(:, :), l2(:, :), b1(:, :), b2(:, :), s(:, :), si(:, :), red(:), d1(:, :), eo(:), ev(:)
+      integer, allocatable :: order(:)
+      integer :: k, j, a, b, c0, c1, nc, piv
+      integer(c_int64_t) :: n1, n2, t_lo, t_hi
+      integer(c_int) :: rc_mine
+      character(512) :: my_error
+      real(dp) :: tt, lowest, f, gap
+      tt = seconds()
+      n1 = int(o, c_int64_t)*v; n2 = n1*n1
+      allocate (r1(n1, nr), r2(n2, nr), l1(n1, nr), l2(n2, nr), b1(n1, nr), b2(n2, nr), order(nr), red(nr + 1))
+      do k = 1, nr
+         rc = afesp_ccsd_so_eom_get_vector(ctx, int(k - 1, c_int), r1(:, k), r2(:, k))
+         if (rc /= 0) call fail('eom::get_vector', afesp_error_text(ctx))
+         rc = afesp_ccsd_so_eom_left_get_vector(ctx, int(k - 1, c_int), l1(:, k), l2(:, k))
+         if (rc /= 0) call fail('eom::left_get_vector', afesp_error_text(ctx))
+      end do
+      ! roots in ascending order, clusters of neighbours within degeneracy_tol
+      do k = 1, nr
+         order(k) = k
+      end do
+      do k = 2, nr
+         j = k
+         do while (j > 1)
+            if (omega(order(j - 1)) <= omega(order(j))) exit
+            a = order(j); order(j) = order(j - 1); order(j - 1) = a
+            j = j - 1
+         end do
+      end do
+      c0 = 1
+      do while (c0 <= nr)
+         c1 = c0
+         do while (c1 < nr)
+            if (abs(omega(order(c1 + 1)) - omega(order(c1))) >= degeneracy_tol) exit
+            c1 = c1 + 1
+         end do
+         nc = c1 - c0 + 1
+         allocate (s(nc, nc), si(nc, nc))
+         do a = 1, nc
+            do b = 1, nc
+               s(a, b) = sum(l1(:, order(c0 + a - 1))*r1(:, order(c0 + b - 1))) + 0.25_dp*sum(l2(:, order(c0 + a - 1))*r2(:, order(c0 + b - 1)))
+            end do
+         end do
+         ! si = s^-1 by Gauss-Jordan elimination with row pivoting
+         si = 0.0_dp
+         do a = 1, nc
+            si(a, a) = 1.0_dp
+         end do
+         do a = 1, nc
+            piv = a
+            do b = a + 1, nc
+               if (abs(s(b, a)) > abs(s(piv, a))) piv = b
+            end do
+            if (abs(s(piv, a)) < 1.0e-8_dp) call fail('eom::biorthonormalise', &
+               'the overlap of the left and right vectors of a cluster of roots is singular: the two solves found different states!')
+            if (piv /= a) then
+               s([a, piv], :) = s([piv, a], :); si([a, piv], :) = si([piv, a], :)
+            end if
+            f = 1.0_dp/s(a, a)
+            s(a, :) = s(a, :)*f; si(a, :) = si(a, :)*f
+            do b = 1, nc
+               if (b /= a) then
+                  f = s(b, a)
+                  s(b, :) = s(b, :) - f*s(a, :); si(b, :) = si(b, :) - f*si(a, :)
+               end if
+            end do
+         end do
+         do a = 1, nc
+            b1(:, order(c0 + a - 1)) = 0.0_dp; b2(:, order(c0 + a - 1)) = 0.0_dp
+            do b = 1, nc
+               b1(:, order(c0 + a - 1)) = b1(:, order(c0 + a - 1)) + si(a, b)*l1(:, order(c0 + b - 1))
+               b2(:, order(c0 + a - 1)) = b2(:, order(c0 + a - 1)) + si(a, b)*l2(:, order(c0 + b - 1))
+            end do
+         end do
+         deallocate (s, si)
+         c0 = c1 + 1
+      end do
+      ! one call for all roots on this rank's shard, then the flagged sum over the ranks
+      t_hi = afesp_ccsd_so_t_ntriples(int(o, c_int64_t))
+      t_lo = (int(rank, c_int64_t)*t_hi)/world; t_hi = (int(rank + 1, c_int64_t)*t_hi)/world
+      red = 0.0_dp
+      rc = afesp_ccsd_so_eom_t(ctx, int(nr, c_int), omega, b1, b2, r1, r2, t_lo, t_hi, red)
+      if (world > 1) then
+         rc_mine = rc; my_error = ''
+         if (rc_mine /= 0) then; my_error = afesp_error_text(ctx); red = 0.0_dp; end if
+         red(nr + 1) = merge(1.0_dp, 0.0_dp, rc_mine /= 0)
+         rc = afesp_allreduce_sum(ctx, red, int(nr + 1, c_int64_t))
+         if (rc_mine /= 0) call fail('eom::do_eom_triples', trim(my_error))
+         if (rc == 0 .and. red(nr + 1) > 0.5_dp) call fail('eom::do_eom_triples', 'the triples shard of another rank failed')
+      end if
+      if (rc /= 0) call fail('eom::do_eom_triples', afesp_error_text(ctx))
+      ! the smallest triples denominator from the levels: the three highest occupied and the three lowest virtual ones
+      lowest = huge(1.0_dp)
+      if (o >= 3 .and. v >= 3) then
+         allocate (d1(o, v), eo(o), ev(v))
+         rc = afesp_ccsd_so_get_tensor(ctx, 'D1'//c_null_char, d1, n1)
+         if (rc /= 0) call fail('eom::levels', afesp_error_text(ctx))
+         eo = d1(:, 1); ev = d1(1, 1) - d1(1, :)      ! the levels relative to the first virtual one
+         lowest = 0.0_dp
+         do k = 1, 3
+            a = maxloc(eo, 1); lowest = lowest - eo(a); eo(a) = -huge(1.0_dp)
+            a = minloc(ev, 1); lowest = lowest + ev(a); ev(a) = huge(1.0_dp)
+         end do
+      end if
+      write (out, '(1X, A)') 'Non-iterative triples correction to the EOM-CCSD excitation energies'
+      write (out, '(100("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Root', '   omega (Eh)     ', 'delta omega (Eh)  ', ' omega+delta (Eh) ', ' omega+delta (eV) '
+      write (out, '(100("-"))')
+      do k = 1, nr
+         write (out, '(1X, I4, 3X, F18.12, 3X, F18.12, 3X, F18.12, 3X, F18.10)') k, omega(k), red(k), omega(k) + red(k), (omega(k) + red(k))*hartree_ev
+      end do
+      write (out, '(100("-"))')
+      do k = 1, nr
+         gap = abs(omega(k) - lowest)
+         if (gap < intruder_gap) write (out, '(1X, A, I0, A, F8.4, A)') 'Root ', k, ': omega is within ', gap, &
+            ' Eh of a triples denominator: the correction is not reliable'
+      end do
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the EOM-CCSD triples correction:', seconds() - tt, 's'
    end subroutine
    !> eom_ip_nroots / eom_ea_nroots: the lowest EOM-IP-CCSD ionisation potentials (1h + 2h1p) or EOM-EA-CCSD electron affinities (1p + 2p1h) of the
    !> converged spin-orbital CCSD state, after Lambda and EOM-EE where those were asked for.  The H-bar elements are those of the Lambda

@@ -310,6 +310,21 @@ int afesp_ccsd_so_relax_pair_row(afesp_ctx* ctx, int which, double* out, int rep
  * second pool that does not fit; AFESP_LAMBDA_STALE no Lambda state or a stale one.  An empty range gives 0. */
 int afesp_ccsd_so_lambda_t(afesp_ctx* ctx, int64_t t_begin, int64_t t_end, double* e_lt);
 
+/* Non-iterative triples correction to EOM-EE-CCSD excitation energies (afesp_version 6).  For an excitation energy w, a left
+ * vector (l1, l2) and a right vector (r1, r2), laid out as t1 / t2, with |mu3> the triply excited determinants and H the bare Hamiltonian,
+ *   m(mu3) = <mu3| [H, R2] + [[H, R1], T2] |0>,   l(mu3) = <0| (L1 + L2) H |mu3>,   delta = sum_mu3 l m / (w - (e_a + e_b + e_c - e_i - e_j - e_k)).
+ * In the notation of afesp_ccsd_so_lambda_t:  l = wc_l + wd_l,  m = wc_r2[g] + wc_t2[gR]  with gR the one-index transform of g by r1, and
+ *   delta[s] = sum over the triples i<j<k numbered [t_begin, t_end), and over a, b, c, of  P(l) P(m) / (D + w[s]) / 6.
+ * With w = 0, l = lambda, r = (0, t2) it is afesp_ccsd_so_lambda_t term for term; it is bilinear in (l, r).  The caller passes biorthonormal
+ * vectors (<l, r> = 1) and watches small |D + w| itself.  nstates vectors follow one another in l1 / l2 / r1 / r2 (host).  The enumeration
+ * is afesp_ccsd_so_t's, so shards add up.  Uses g, f, the levels and t2 only: no Lambda state is needed, and nothing of t, lambda, the
+ * epochs, the Lambda, EOM or response states or the operand copies of (T) / Lambda-(T) is written.  Device memory: two block pools as
+ * afesp_ccsd_so_lambda_t, a left operand pair and a right one of twice its size.  Statuses: 1 no spin-orbital state, a NULL argument,
+ * nstates < 1, a recording context, a Fock state whose oo / vv blocks are not diagonal, or a second pool that does not fit.  An empty
+ * range, o < 3 or v < 3 give zeros. */
+int afesp_ccsd_so_eom_t(afesp_ctx* ctx, int nstates, const double* omega, const double* l1, const double* l2, const double* r1,
+                        const double* r2, int64_t t_begin, int64_t t_end, double* delta /* [nstates] */);
+
 /* EOM-EE-CCSD excitation energies of the spin-orbital state.  The right-hand EOM matrix in the singles and doubles space
  * is the Jacobian A = dR/dt of the residuals above over the unique amplitudes; sigma(r) = A r for r = [r1 [o*v]; r2 [o*o*v*v]] laid out as
  * t1 / t2, r2 antisymmetric in i,j and in a,b.  On that storage <x, y> = sum x1 y1 + 1/4 sum x2 y2.  The excitation energies are the lowest
