@@ -241,6 +241,8 @@ TENSOR_SHAPES = {
     "I_vo": "vo", "I_vv": "vv", "I_oo_p": "oo", "I_oo": "oo", "c_oovv": "oovv", "asym_t2": "oovv", "x_voov": "voov",
     "I_oooo": "oooo", "I_ovov": "ovov", "I_voov": "voov", "I_vovv_p": "vovv", "I_ooov_p": "ooov", "r1": "ov",
     "r2": "oovv", "D1": "ov", "D2": "oovv", "t1": "ov", "t2": "oovv",
+    # what a split update leaves (include/afesp.h); "p": the v (v + 1) / 2 column pairs a <= b of the packed ladder, p = a + b (b + 1) / 2
+    "r1_sh": "ov", "ooov_sh": "ooov", "pp": "oop",
 }
 
 
@@ -407,7 +409,8 @@ class Engine:
         self._chk(self.L.afesp_ccsd_set_amplitudes(self.h, _f(t1), _f(t2)))
 
     def tensor(self, name):
-        dims = tuple(self.o if ch == "o" else self.v for ch in TENSOR_SHAPES[name])
+        ext = {"o": self.o, "v": self.v, "p": self.v * (self.v + 1) // 2}
+        dims = tuple(ext[ch] for ch in TENSOR_SHAPES[name])
         buf = np.zeros(int(np.prod(dims)))
         self._chk(self.L.afesp_ccsd_get_tensor(self.h, name.encode(), buf, buf.size))
         return buf.reshape(dims, order="F")

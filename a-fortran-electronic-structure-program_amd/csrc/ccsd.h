@@ -38,6 +38,9 @@ struct CCState : DiisRing {
     // rank split of the iteration's large products (afesp_comm_init with world > 1; ccsd_refresh_sharding)
     bool sharded = false;
     int sh_rank = 0, sh_world = 1;
+    // whether the last ccsd_intermediates / ccsd_amplitudes ran split: afesp_ccsd_get_tensor serves "ooov_sh" resp. "r1_sh" / "pp" only
+    // as a split call left them (Solver::fetch_tensor)
+    bool int_split = false, amp_split = false;
     int64_t* pp_tab = nullptr;     // offset tables of the pp-ladder GEMM: [Am | k | Bk | n]
     // symmetric / antisymmetric form (large systems): V+-(ef,ab) built at init, c+-(ij,ef) and the two products per iteration
     bool pp_sym = false;

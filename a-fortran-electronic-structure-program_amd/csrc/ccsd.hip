@@ -39,6 +39,7 @@ void ccsd_init(Context& cx, CCState& s, int o, int v, const double* eri_mo_dev, 
         if (s.eri_own) { cx.release(s.eri_own); s.eri_own = nullptr; }
         ring_reinit(s);
         s.cs_packed = s.partials_live = false;
+        s.int_split = s.amp_split = false;
         s.tail_pending = false;
         s.nact = 0; s.it = 0;
         s.hist_plain = 0;
@@ -258,8 +259,9 @@ void ccsd_refresh_sharding(Context& cx, CCState& s)
     s.sh_rank = cx.comm ? cx.comm->rank : 0;
     const bool on = cx.cc_split_mode >= 0 ? cx.cc_split_mode == 1 : env == 1;
     s.sharded = world > 1 && on && env != 0;
-    // measurement only (tools/split_slice_time.py): AFESP_CC_TIME_SLICE="rank,world" without a communicator -- the iteration does a
-    // rank's share of the split form and skips the exchange; the amplitudes that come out are NOT the iteration's
+    // AFESP_CC_TIME_SLICE="rank,world" without a communicator -- the iteration does a rank's share of the split form and skips the
+    // exchange; the amplitudes that come out are NOT the iteration's.  tests/test_gpu_cc_split.py relies on it (one engine plays every
+    // rank in turn and sums the partial residuals itself); tools/split_slice_time.py times a rank's share with it
     if (!cx.comm)
         if (knobs().cc_time_slice) { s.sharded = true; s.sh_rank = knobs().cc_time_rank; s.sh_world = knobs().cc_time_world; }
 }
@@ -291,6 +293,7 @@ void ccsd_intermediates(Context& cx, CCState& s, bool save_for_diis)
     // this rank's slice [v0, v1) of the last (virtual) index of I_ovov / I_voov: the whole range unless the iteration is split
     int64_t v0, v1;
     slice_bounds(s, &v0, &v1);
+    s.int_split = s.sharded;
     auto sl = [&](const Tensor& t, int axis) { return slice_axis(t, axis, v0, v1); };
     // asym_t2, c_oovv                                                    ccsd.f90:1063-1079
     // (large systems: together with the copies of the amplitudes that the ring products read, ring.hip)
@@ -635,6 +638,7 @@ void ccsd_amplitudes(Context& cx, CCState& s, bool defer_update)
     const bool par = lanes_pay(s) && !cx.rec, sh = s.sharded;
     const bool ring = !par && !cx.rec && !sh && ring_live(s);   // the ring terms through the buffers ccsd_intermediates left (ring.hip)
     s.partials_live = par;
+    s.amp_split = sh;
     ring_res_clear(s);
     int64_t v0, v1;
     slice_bounds(s, &v0, &v1);

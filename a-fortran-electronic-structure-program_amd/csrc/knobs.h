@@ -45,7 +45,7 @@ struct Knobs {
     bool t_one_pool = false;                // AFESP_T_ONE_POOL  the (T) block pool as one allocation
     bool cc_reinit = true;                  // AFESP_CC_REINIT=0 afesp_ccsd_init always builds a fresh state
     int cc_shard = -1;                      // AFESP_CC_SHARD=0/1  rank split of the iteration off / on (default: afesp_ccsd_set_split)
-    bool cc_time_slice = false;             // AFESP_CC_TIME_SLICE="rank,world"  measurement: one rank's share without a communicator
+    bool cc_time_slice = false;             // AFESP_CC_TIME_SLICE="rank,world"  one rank's share without a communicator: tests/test_gpu_cc_split.py relies on it; also measurement
     int cc_time_rank = 0, cc_time_world = 1;
     int ao2mo_tg = -1;                      // AFESP_AO2MO_TG=0/1   quarter transforms never / always on the LDS-DMA GEMM (default: even n >= 96)
     bool ao2mo_pair = true;                 // AFESP_AO2MO_PAIR=0   n <= 64: gather-GEMM form instead of the LDS-resident pair transform

@@ -175,6 +175,7 @@ void Solver::init(Context& cx, int o, int v, const double* host, double* dev, bo
 void Solver::update_intermediates(Context& cx)
 {
     ccsd_refresh_sharding(cx, cc);
+    cc.int_split = false;   // (ccsd_intermediates says so again when it runs split; a launch-fused program never does, and does not pass there)
     fused_or_direct(cx, ccsd_uses_lanes(cc), fused_int, [&] { ccsd_intermediates(cx, cc); });
     cx.sync();
 }
@@ -184,6 +185,9 @@ void Solver::update_amplitudes(Context& cx)
     cc.amp_epoch = ++cx.amp_clock;
     ccsd_refresh_sharding(cx, cc);
     cc.tail_pending = false;
+    // (what the LAST update left is said by ccsd_amplitudes when it runs; a launch-fused program does not pass there, is never split and
+    // leaves no laned partial residuals -- the getter added a laned update's stale ones to the residual of a launch-fused update after it)
+    cc.amp_split = cc.partials_live = false;
     fused_or_direct(cx, ccsd_uses_lanes(cc), fused_amp, [&] { ccsd_amplitudes(cx, cc); });
     cx.sync();
 }
@@ -197,7 +201,10 @@ bool Solver::iteration_body(Context& cx)
         ccsd_amplitudes(cx, cc, true);
         ccsd_tail_launch(cx, cc);
     };
-    if (ccsd_uses_lanes(cc) && fused_exec(cx, fused_iter, with_tail)) return true;
+    if (ccsd_uses_lanes(cc) && fused_exec(cx, fused_iter, with_tail)) {
+        cc.partials_live = false;   // (the whole residual lies in r2 / r1, whatever a laned iteration before this one left: update_amplitudes)
+        return true;
+    }
     // Large systems (one stream, whole-tensor products): the same two-kernel tail -- P(ia/jb) + division, the energy / rms sums and the
     // DIIS history push in ONE pass over the residual instead of three (update, energy, push: 26 against 23 passes over o^2 v^2 elements at
     // eight history vectors, and no host wait between the energy and the push); the <= 17 x 17 system is then solved on the host.
@@ -212,12 +219,14 @@ bool Solver::iteration_body(Context& cx)
         ccsd_amplitudes(cx, cc);
         ccsd_energy_launch(cx, cc);
     });
+    if (graph_cc.exec) cc.partials_live = true;   // (a replayed iteration is a laned one: its partial residuals lie where the captured call left them)
     return false;
 }
 
 StepResult Solver::step(Context& cx, double e_tol, double t_tol)
 {
     ccsd_refresh_sharding(cx, cc);
+    cc.int_split = cc.amp_split = false;   // (a replayed or launch-fused iteration is never split; one that runs split says so itself)
     const bool tail = iteration_body(cx);
     const int conv = tail ? ccsd_tail_read(cx, cc, e_tol, t_tol) : ccsd_energy_read(cx, cc, e_tol, t_tol);
     return {cc.energy, cc.rms, conv};
@@ -283,6 +292,20 @@ void Solver::fetch_tensor(Context& cx, const char* name, double* out, int64_t ca
     const Tensor* t = is("I_vovv_p") ? &vovv : nullptr;
     for (auto& e : tab)
         if (is(e.n)) t = e.t;
+    // What only a split call leaves behind (tests/test_gpu_cc_split.py): the rank-partial T1 residual and the packed ladder PP(i,j,p) of the
+    // last ccsd_amplitudes, and the buffer into which the last ccsd_intermediates put the slice of t2 <ef|ia> + t1 x_voov that it took out of
+    // I_ooov_p -- the buffer as it lies: outside the slice it holds what earlier calls left.  After an unsplit call they hold something else.
+    Tensor split_only;
+    if (is("r1_sh") || is("pp") || is("ooov_sh")) {
+        const bool amp = !is("ooov_sh");
+        auto osh = cx.cache.find("ooov_sh");
+        if (!(amp ? s.amp_split : (s.int_split && osh != cx.cache.end())))
+            throw Error(1, std::string("afesp_ccsd_get_tensor: ") + name + " is served only when the last " +
+                               (amp ? "update of the amplitudes" : "update of the intermediates") +
+                               " of this state ran split (afesp_ccsd_set_split): it did not");
+        split_only = is("r1_sh") ? view(s.r1_sh, {O, V}) : is("pp") ? view(s.pp, {O, O, V * (V + 1) / 2}) : view((double*)osh->second.first, {O, O, O, V});
+        t = &split_only;
+    }
     if (!t) throw Error(1, std::string("afesp_ccsd_get_tensor: unknown tensor ") + name);
     if (t->size() > capacity) throw Error(1, std::string("afesp_ccsd_get_tensor: buffer too small for ") + name);
     const double* src = t->d;

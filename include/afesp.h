@@ -105,7 +105,16 @@ int afesp_ccsd_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2
  * (v_vvvv and I_vovv_p are not kept by a large system's iteration and are formed by this call; v_vvvv needs the packed MO
  * integrals the solver was initialised from: status 1 if afesp_ao2mo_mp2 has replaced them since afesp_ccsd_init;
  * r2 is the T2 residual before P(ia/jb) up to terms held as their images under (i <-> j, a <-> b): r2(ijab) + r2(jiba) is what
- * equals the same sum of the reference's tmp_t2, src/ccsd.f90:1720-1728) */
+ * equals the same sum of the reference's tmp_t2, src/ccsd.f90:1720-1728)
+ * Three more names are served only as a rank-split call left them (afesp_ccsd_set_split, or AFESP_CC_TIME_SLICE; read-only, for
+ * tests/test_gpu_cc_split.py); otherwise status 1, with a message that says so, and the context stays usable:
+ *   r1_sh   (o, v)        the rank-partial part of the T1 residual, as the last update of the amplitudes ran split: r1 - r1_sh is the
+ *                         replicated part (with a communicator r1_sh is the sum over ranks and r1 the whole residual);
+ *   pp      (o, o, v (v + 1) / 2)   the packed ladder PP(i,j,p), p = a + b (b + 1) / 2 over a <= b, same condition: this rank's rows,
+ *                         zero elsewhere (with a communicator: the sum);
+ *   ooov_sh (o, o, o, v)  the t2 <ef|ia> + t1 x_voov terms that the last update of the intermediates, run split, took out of
+ *                         I_ooov_p(j,k,i,a) for this rank's slice of a; the buffer as it lies: outside the slice it holds what
+ *                         earlier calls left there (at first: nothing defined). */
 int afesp_ccsd_get_tensor(afesp_ctx* ctx, const char* name, double* out, int64_t capacity);
 /* intermediates / amplitude equations separately (src/ccsd.f90:350,357), for term-by-term parity tests.  The two calls are ONE update
  * of one set of amplitudes, as in the reference's loop: terms are regrouped between them (the t1-dressed parts of I_vovv_p, the bare

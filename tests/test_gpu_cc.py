@@ -282,6 +282,50 @@ def test_one_iteration_term_by_term(eng, o, v, fused, monkeypatch):
     assert np.max(np.abs(g1 - cc.t1)) < tol and np.max(np.abs(g2 - cc.t2)) < tol
 
 
+def test_residuals_fetched_after_a_launch_fused_update_that_follows_a_laned_one(eng):
+    """afesp_ccsd_get_tensor "r1" / "r2" add up what the last update left: a call-by-call (laned) update leaves terms of both residuals in
+    lane buffers, a launch-fused one (and a replayed graph is a laned one again) the whole residual in one place.  The compiled program does
+    not pass through ccsd_amplitudes, where the state used to learn which of the two had run: after a laned update the getter added the
+    stale lane partials to every later launch-fused residual -- errors of the size of the residual itself.  Both entry points, the two
+    evaluation orders alternating on one state, other amplitudes every time."""
+    o, v = 4, 9
+    n, e, eri = molecules.synthetic_system(o, v, scale=0.05)
+    cc = orc.OracleCC(o, v, eri, e, 8)
+
+    def oracle_residuals(t1, t2):
+        cc.t1[...] = t1
+        cc.t2[...] = t2
+        cc.L.orc_cc_intermediates(cc.h)
+        cc.L.orc_cc_amplitudes(cc.h)
+        return np.array(cc.field("r1")), np.array(cc.field("r2"))
+
+    try:
+        eng.ccsd_init(o, v, e, eri, 8)
+        for seed, fused in enumerate((0, 1, 0, 1, 1, 0)):
+            rng = np.random.default_rng(40 + seed)
+            t1 = 0.05 * rng.standard_normal((o, v))
+            t2 = 0.05 * rng.standard_normal((o, o, v, v))
+            t2 = 0.5 * (t2 + t2.transpose(1, 0, 3, 2))
+            r1, r2 = oracle_residuals(t1, t2)
+            eng.ccsd_set_fused(fused)
+            eng.set_amplitudes(t1, t2)
+            eng.update_intermediates()
+            eng.update_amplitudes()
+            assert np.max(np.abs(eng.tensor("r1") - r1)) < 1e-12, (seed, fused)
+            assert np.max(np.abs(_p(eng.tensor("r2")) - _p(r2))) < 1e-12, (seed, fused)
+        # afesp_ccsd_iterate: call by call, captured (the second such call, AFESP_GRAPH_AFTER=1), launch-fused, replayed, launch-fused
+        eng.ccsd_init(o, v, e, eri, 8)
+        for it, fused in enumerate((0, 0, 1, 0, 1)):
+            r1, r2 = oracle_residuals(*eng.amplitudes())
+            eng.ccsd_set_fused(fused)
+            eng.ccsd_iterate(1e-14, 1e-14)
+            assert np.max(np.abs(eng.tensor("r1") - r1)) < 1e-12, (it, fused)
+            assert np.max(np.abs(_p(eng.tensor("r2")) - _p(r2))) < 1e-12, (it, fused)
+    finally:
+        eng.ccsd_set_fused(-1)
+        cc.close()
+
+
 @pytest.mark.parametrize("pp_sym", ["0", "1"])
 @pytest.mark.parametrize("o,v", [(5, 53), (7, 21), (9, 19), (4, 10), (1, 3), (2, 2), (9, 1), (1, 9), (6, 4)])
 def test_launch_fused_iteration_equals_the_call_by_call_iteration(o, v, pp_sym, monkeypatch):

@@ -75,7 +75,8 @@ def test_engine_ranks_shard_triples_and_reduce(tmp_path, name, world):
 def test_ccsd_iteration_split_over_ranks(tmp_path, name, world, pp_sym):
     """the iteration's o^3 v^3 ring products and the pp-ladder (both of its forms) evaluated slice by
     slice on the ranks, one all-reduce of [PP | partial residual] per iteration -- every rank must walk the reference's own
-    iteration table (els.out, 12 decimals) and land on the replica path's energies."""
+    iteration table (els.out, 12 decimals) and land on the replica path's energies.  (Each rank's share term by term, at narrow and
+    empty slices: tests/test_gpu_cc_split.py; this is the test of the exchange itself.)"""
     res = _run_ranks(tmp_path, world, name, env={"AFESP_CC_SHARD": "1", "AFESP_PP_SYM": pp_sym})
     g = molecules.SURVEY_GOLD[name]
     _, _, _, gold = molecules.load(name)
