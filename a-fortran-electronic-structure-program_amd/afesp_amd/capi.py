@@ -40,6 +40,9 @@ EXPORTS = [
     "afesp_ccsd_so_eom_left_iterate", "afesp_ccsd_so_eom_left_get_vector", "afesp_ccsd_so_eom_ref_coupling", "afesp_ccsd_so_eom_density",
     "afesp_ccsd_so_eom_ipea_init", "afesp_ccsd_so_eom_ipea_sigma", "afesp_ccsd_so_eom_ipea_guess", "afesp_ccsd_so_eom_ipea_set_guess",
     "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
+    "afesp_ccsd_so_eom_ipea_lsigma", "afesp_ccsd_so_eom_ipea_left_init", "afesp_ccsd_so_eom_ipea_left_guess",
+    "afesp_ccsd_so_eom_ipea_left_set_guess", "afesp_ccsd_so_eom_ipea_left_iterate", "afesp_ccsd_so_eom_ipea_left_get_vector",
+    "afesp_ccsd_so_eom_ipea_dyson",
     "afesp_ccsd_so_response_xi", "afesp_ccsd_so_response_init", "afesp_ccsd_so_response_iterate", "afesp_ccsd_so_response_get_vector",
     "afesp_ccsd_so_response_function", "afesp_lu_solve",
     "afesp_ccsd_so_response_init_complex", "afesp_ccsd_so_response_get_vector_complex", "afesp_ccsd_so_response_function_complex",
@@ -175,6 +178,13 @@ def load_library():
     L.afesp_ccsd_so_eom_ipea_iterate.argtypes = [C.c_void_p, C.c_int, dbl, _dp, _dp, np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS"),
                                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.afesp_ccsd_so_eom_ipea_get_vector.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp, _dp]
+    L.afesp_ccsd_so_eom_ipea_lsigma.argtypes = L.afesp_ccsd_so_eom_ipea_sigma.argtypes
+    L.afesp_ccsd_so_eom_ipea_left_init.argtypes = L.afesp_ccsd_so_eom_ipea_init.argtypes
+    L.afesp_ccsd_so_eom_ipea_left_guess.argtypes = L.afesp_ccsd_so_eom_ipea_guess.argtypes
+    L.afesp_ccsd_so_eom_ipea_left_set_guess.argtypes = L.afesp_ccsd_so_eom_ipea_set_guess.argtypes
+    L.afesp_ccsd_so_eom_ipea_left_iterate.argtypes = L.afesp_ccsd_so_eom_ipea_iterate.argtypes
+    L.afesp_ccsd_so_eom_ipea_left_get_vector.argtypes = L.afesp_ccsd_so_eom_ipea_get_vector.argtypes
+    L.afesp_ccsd_so_eom_ipea_dyson.argtypes = [C.c_void_p, C.c_int, C.c_int, _opt, _opt, _opt, _opt, _opt, _opt]
     L.afesp_eig_general.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp]
     L.afesp_read_eri_text.argtypes = [C.c_void_p, C.c_char_p, i64, _opt, C.POINTER(i64)]
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
@@ -1084,7 +1094,8 @@ class Engine:
     # ---- The EOM-CCSD eigenproblems of the spin-orbital state (include/afesp.h; afesp_amd.eom drives them): EE, its left-hand side, and
     # the IP and EA sectors.  All need a live Lambda state (so_lambda_init for the current t1 / t2; status 21 otherwise); none writes
     # t1 / t2 or lambda, and no call for one problem touches the state of another.  One set of helpers serves them, keyed by kind:
-    # "ee", "left", or the sector of the ipea calls -- EOM_IP (1h + 2h1p: r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v))
+    # "ee", "left", the sector of the ipea calls -- EOM_IP (1h + 2h1p: r1 (o,), r2 (o,o,v)) or EOM_EA (1p + 2p1h: r1 (v,), r2 (o,v,v)) -- or
+    # ("left", sector) for the sector's left-hand side
     EOM_IP, EOM_EA = 1, 2
     _eom_nroots = {}                                                        # kind -> nroots of its last init
 
@@ -1092,7 +1103,8 @@ class Engine:
         o, v = self.so_o, self.so_v
         if kind in ("ee", "left"):
             return (o, v), (o, o, v, v)
-        return ((o,), (o, o, v)) if kind == self.EOM_IP else ((v,), (o, v, v))
+        sector = kind[1] if isinstance(kind, tuple) else kind
+        return ((o,), (o, o, v)) if sector == self.EOM_IP else ((v,), (o, v, v))
 
     def _eom_fn(self, kind, call):
         """the library's entry `call` of the kind -> (function, its arguments between the context and the call's own)"""
@@ -1100,6 +1112,8 @@ class Engine:
             return getattr(self.L, "afesp_ccsd_so_eom_" + call), ()
         if kind == "left":
             return getattr(self.L, "afesp_ccsd_so_eom_" + ("lsigma" if call == "sigma" else "left_" + call)), ()
+        if isinstance(kind, tuple):
+            return getattr(self.L, "afesp_ccsd_so_eom_ipea_" + ("lsigma" if call == "sigma" else "left_" + call)), (kind[1],)
         return getattr(self.L, "afesp_ccsd_so_eom_ipea_" + call), (kind,)
 
     def _eom_stack(self, kind, x1, x2, who):
@@ -1222,6 +1236,58 @@ class Engine:
     def so_eom_ipea_vector(self, sector, k):
         """Ritz vector k of the sector's last step, <x, x> = sum x1^2 + 1/2 sum x2^2 = 1"""
         return self._eom_vector(sector, k)
+
+    # the left-hand side of the sectors: one more Davidson state per sector, for A^T, beside the right-hand one
+    def so_eom_ipea_lsigma(self, sector, l1, l2):
+        """sigma_L = A^T l of the sector (the transpose in its metric) for one vector -> (s1, s2); with a leading axis, k vectors in one
+        call -> the same with that axis."""
+        return self._eom_sigma(("left", sector), l1, l2, "so_eom_ipea_lsigma")
+
+    def so_eom_ipea_left_init(self, sector, nroots, max_space):
+        self._eom_init(("left", sector), nroots, max_space)
+
+    def so_eom_ipea_left_guess(self, sector):
+        self._eom_guess(("left", sector))
+
+    def so_eom_ipea_left_set_guess(self, sector, k, l1, l2):
+        self._eom_set_guess(("left", sector), k, l1, l2)
+
+    def so_eom_ipea_left_iterate(self, sector, tol=1e-8):
+        """One Davidson step of the sector's left state -> (omega, resnorm, flags, sigma builds so far, converged)"""
+        return self._eom_iterate(("left", sector), tol)
+
+    def so_eom_ipea_left_vector(self, sector, k):
+        """Left Ritz vector k of the sector's last step, <x, x> = 1 (biorthonormalise it against the right vectors: afesp_amd.eom)"""
+        return self._eom_vector(("left", sector), k)
+
+    def so_eom_ipea_dyson(self, sector, l=None, r=None):
+        """The Dyson vectors over the o + v spin orbitals of the state (its order) of left vectors l = (l1, l2) and / or right vectors
+        r = (r1, r2) of the sector -> (gamma_L, gamma_R), None for an absent side; one vector -> (o+v,), with a leading axis (k, o+v).
+        A half-given pair -- (l1, None) -- is passed on and refused by the library."""
+        n = self.so_o + self.so_v
+        ptrs, outs, keep, k, single = [], [], [], None, True
+        for x in (l, r):
+            if x is None:
+                ptrs += [None, None]
+                outs.append(None)
+                continue
+            if x[0] is None or x[1] is None:                                # half a pair: the library's refusal
+                k = k or 1
+                a = [None if y is None else _f(y) for y in x]
+            else:
+                kk, a1, a2, single = self._eom_stack(sector, x[0], x[1], "so_eom_ipea_dyson")
+                if k is not None and kk != k and all(p is not None for p in ptrs):
+                    raise ValueError("so_eom_ipea_dyson: as many left as right vectors")
+                k, a = kk, [a1, a2]
+            keep += a
+            ptrs += [None if y is None else y.ctypes.data_as(C.c_void_p) for y in a]
+            outs.append(np.zeros(n * k))
+        if k is None:
+            k = 1
+        d = [None if y is None else y.ctypes.data_as(C.c_void_p) for y in outs]
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_dyson(self.h, sector, k, *ptrs, *d))
+        shape = lambda y: None if y is None else (y.copy() if single else y.reshape(k, n))
+        return shape(outs[0]), shape(outs[1])
 
     # the reference coupling of right EE vectors and the bilinear density of a left and a right pair: they need the Lambda state only
     def so_eom_ref_coupling(self, r1, r2):

@@ -2,7 +2,9 @@
 (host code); EOM-IP-CCSD ionisation potentials and EOM-EA-CCSD electron affinities of the same state over
 Engine.so_eom_ipea_* (so_eom_ip_solve, so_eom_ea_solve, label_ipea_root); the left eigenvectors of the EE roots, their
 biorthonormalisation against the right ones, excited-state and transition densities and oscillator strengths over Engine.so_eom_left_*,
-so_eom_ref_coupling and so_eom_density (so_eom_left_solve, biorthonormalise, so_eom_properties, oscillator_strengths).
+so_eom_ref_coupling and so_eom_density (so_eom_left_solve, biorthonormalise, so_eom_properties, oscillator_strengths); the
+left eigenvectors of the IP / EA roots, Dyson orbitals and pole strengths over Engine.so_eom_ipea_left_* and so_eom_ipea_dyson
+(so_eom_ip_left_solve, so_eom_ea_left_solve, biorthonormalise_ipea, so_eom_ipea_properties).
 
 The spin-orbital space holds every Ms component: a triplet appears threefold (Ms = 0 and the two spin-flip components Ms = +-1), a singlet
 once.  The driver reports the degeneracies and filters nothing."""
@@ -279,6 +281,109 @@ def label_ipea_root(sector, x1, x2, nbasis, nalpha, nbeta, interleaved):
     return dict(kind=kind, occ=tuple(int(orb[p]) for p in occ), virt=tuple(int(orb[p]) for p in virt),
                 spins_occ=tuple(int(spin[p]) for p in occ), spins_virt=tuple(int(spin[p]) for p in virt),
                 delta_ms=float(sum(ms(spin[p]) for p in virt) - sum(ms(spin[p]) for p in occ)), weight=weight)
+
+
+# ---------------------------------------------------------------------------------------------------------------- IP / EA: left vectors, Dyson orbitals
+def dot_ipea(x, y):
+    """<x, y> = sum x1 y1 + 1/2 sum x2 y2 of two vectors of a sector on full storage"""
+    return float(np.sum(x[0] * y[0]) + 0.5 * np.sum(x[1] * y[1]))
+
+
+def _so_eom_ipea_left_solve(eng, sector, right_vectors, nroots, tol, max_space, maxiter):
+    if maxiter < 1:
+        raise ValueError("so_eom_ip_left_solve / so_eom_ea_left_solve: maxiter must be at least 1")
+    if nroots is None:
+        if right_vectors is None:
+            raise ValueError("so_eom_ip_left_solve / so_eom_ea_left_solve: give nroots or right_vectors")
+        nroots = len(right_vectors)
+    def init():
+        ms = max_space if max_space is not None else default_max_space(nroots, ipea_nunique(sector, eng.so_o, eng.so_v))
+        eng.so_eom_ipea_left_init(sector, nroots, ms)
+        return ms
+    return _davidson(init, lambda: eng.so_eom_ipea_left_guess(sector), lambda k, l1, l2: eng.so_eom_ipea_left_set_guess(sector, k, l1, l2),
+                     lambda t: eng.so_eom_ipea_left_iterate(sector, t), lambda k: eng.so_eom_ipea_left_vector(sector, k), nroots,
+                     None if right_vectors is None else right_vectors[:nroots], tol, maxiter, "left EOM-CCSD")
+
+
+def so_eom_ip_left_solve(eng, right_vectors=None, nroots=None, tol=1e-8, max_space=None, maxiter=100):
+    """The left eigenvectors l A = omega l of EOM-IP-CCSD roots, on a Davidson state of its own beside the sector's
+    right-hand one, which is not touched.  right_vectors: the converged right vectors [(r1, r2)] as the left guess (nroots defaults to
+    their number) -- the library then follows the states of the guesses, as so_eom_left_solve; without them the library's guesses and the
+    lowest roots.  -> (omega, [(l1, l2)] with <l, l> = 1, info) like so_eom_ip_solve; not yet biorthonormal: biorthonormalise_ipea."""
+    return _so_eom_ipea_left_solve(eng, SECTOR_IP, right_vectors, nroots, tol, max_space, maxiter)
+
+
+def so_eom_ea_left_solve(eng, right_vectors=None, nroots=None, tol=1e-8, max_space=None, maxiter=100):
+    """The left eigenvectors of EOM-EA-CCSD roots.  See so_eom_ip_left_solve."""
+    return _so_eom_ipea_left_solve(eng, SECTOR_EA, right_vectors, nroots, tol, max_space, maxiter)
+
+
+def biorthonormalise_ipea(omega, L, R, degeneracy_tol=1e-6):
+    """biorthonormalise with the sectors' metric <x, y> = sum x1 y1 + 1/2 sum x2 y2: -> new left vectors with <L_j, R_k> = delta_jk inside
+    every cluster of degenerate roots.  Every doublet of a closed-shell reference is a twofold cluster whose two Davidson iterations end
+    in two different bases, so S^-1 L with S_jk = <L_j, R_k> is the normal path here.  Raises ValueError where a cluster's S is singular
+    (condition number above 1e8 with every vector scaled to unit norm): the left and the right solve did not find the same states.
+    Roots of a cluster whose right vectors are equal to the bit are one state: the library gives both members of a pair of roots that
+    rounding split into omega +- i epsilon the pair's one real vector (flag FLAG_COMPLEX).  S is formed over the distinct states, with the
+    left vector of each state's first root, and the other roots of the state receive the same left vector -- a vector of the doublet's
+    space like any other, whose pole strength is the doublet's."""
+    if not (len(omega) == len(L) == len(R)):
+        raise ValueError("biorthonormalise_ipea: omega, L and R differ in length")
+    out = [None] * len(L)
+    for members in clusters(np.asarray(omega), degeneracy_tol):
+        cl, first = [], {}
+        for j in members:
+            same = [k for k in cl if np.array_equal(R[j][0], R[k][0]) and np.array_equal(R[j][1], R[k][1])]
+            first[j] = same[0] if same else j
+            if not same:
+                cl.append(j)
+        S = np.array([[dot_ipea(L[j], R[k]) for k in cl] for j in cl])
+        nl, nr = [np.sqrt(dot_ipea(L[j], L[j])) for j in cl], [np.sqrt(dot_ipea(R[k], R[k])) for k in cl]
+        sv = np.linalg.svd(S / np.outer(nl, nr), compute_uv=False) if min(nl + nr) > 0.0 else np.zeros(1)
+        if not sv[-1] * 1e8 >= max(1.0, sv[0]):
+            raise ValueError(f"biorthonormalise_ipea: the overlap of the left and right vectors of the roots {cl} is singular "
+                             f"(singular values {sv}): the two solves found different states")
+        Si = np.linalg.inv(S)
+        for a, j in enumerate(cl):
+            out[j] = (sum(Si[a, b] * L[m][0] for b, m in enumerate(cl)), sum(Si[a, b] * L[m][1] for b, m in enumerate(cl)))
+        for j in members:
+            out[j] = out[first[j]]
+    return out
+
+
+def so_eom_ipea_properties(eng, sector, L, R):
+    """Per root k, from biorthonormal left vectors L (biorthonormalise_ipea) and right vectors R of the sector, all roots in one library
+    call: -> [dict(dyson_left, dyson_right, pole_strength)].  The Dyson vectors run over the o + v spin orbitals in the state's order,
+    dyson_left[p] = <0| L_k e^-T a_p e^T |0>, dyson_right[p] = <0| (1 + Lambda) e^-T a_p^+ e^T R_k |0> for IP (a_p^+ / a_p for EA), with the
+    converged lambda of the engine's live Lambda state; pole_strength = sum_p dyson_left[p] dyson_right[p].  Inside a degenerate cluster
+    only the sum of the pole strengths is independent of the basis the cluster's vectors came out in."""
+    if len(L) != len(R):
+        raise ValueError("so_eom_ipea_properties: L and R differ in length")
+    gl, gr = eng.so_eom_ipea_dyson(sector, (np.stack([x[0] for x in L]), np.stack([x[1] for x in L])),
+                                   (np.stack([x[0] for x in R]), np.stack([x[1] for x in R])))
+    return [dict(dyson_left=gl[k], dyson_right=gr[k], pole_strength=float(np.dot(gl[k], gr[k]))) for k in range(len(L))]
+
+
+def dyson_spin_parts(gamma, nbasis, nalpha, nbeta, interleaved):
+    """A Dyson vector over the state's spin orbitals (afesp_amd.density.so_spin_order) -> (alpha, beta) parts over the nbasis spatial
+    orbitals: an ionisation or attachment of definite Ms has one of them zero"""
+    orb, spin = so_spin_order(nbasis, nalpha, nbeta, interleaved)
+    gamma = np.asarray(gamma, dtype=np.float64)
+    if gamma.shape != (len(orb),):
+        raise ValueError(f"dyson_spin_parts: the vector has shape {gamma.shape}, the state {len(orb)} spin orbitals")
+    parts = np.zeros((2, nbasis))
+    parts[spin, orb] = gamma
+    return parts[0], parts[1]
+
+
+def ipea_left_table(omega_left, omega_right, info, pole):
+    """The lines the Fortran host prints for eom_ipea_left: root, omega_left in Eh and eV, |omega_left - omega_right|, residual, pole
+    strength, and the sigma builds"""
+    lines = ["  root   omega(left) / Eh   omega(left) / eV   |left-right|     residual   pole strength"]
+    for k, w in enumerate(omega_left):
+        lines.append(f"  {k + 1:4d}  {w:16.10f}  {w * HARTREE_EV:16.8f}  {abs(w - omega_right[k]):11.3e}  {info['resnorm'][k]:11.3e}  {pole[k]:14.10f}")
+    lines.append(f"  left sigma builds: {info['nsigma']}")
+    return "\n".join(lines)
 
 
 def table(omega, info):

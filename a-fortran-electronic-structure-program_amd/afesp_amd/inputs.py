@@ -56,6 +56,7 @@ class SystemIn:
     eom_triples: bool = False       # ... and the non-iterative triples correction to every root (eom.so_eom_triples_correction); needs eom_left
     eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
+    eom_ipea_left: bool = False     # ... and the left eigenvectors and pole strengths of those roots (eom.so_eom_ipea_properties); needs one of the two > 0
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -220,6 +221,11 @@ def read_els_in(path: str) -> SystemIn:
             raise ValueError(f"{key} must be a non-negative integer!")
         if val > 0 and sysin.calc_type not in CC_DENSITY_TYPES:
             raise ValueError(f"{sysin.calc_type} takes no {key}: the EOM-CCSD equations run on the spin-orbital CCSD types!")
+    if not isinstance(sysin.eom_ipea_left, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.eom_ipea_left and sysin.eom_ip_nroots == 0 and sysin.eom_ea_nroots == 0:
+        raise ValueError("eom_ipea_left needs eom_ip_nroots > 0 or eom_ea_nroots > 0: the left eigenvectors and pole strengths are those of "
+                         "the EOM-IP-CCSD / EOM-EA-CCSD roots they ask for!")
     return sysin
 
 

@@ -13,7 +13,7 @@
 #include "solver.h"
 #include "density2_so.h"
 #include "relax_so.h"
-#include "eom_so.h"
+#include "eom_ipea_so.h"
 #include "response_so.h"
 #include "davidson_test.h"
 #include "small_eig.h"
@@ -133,14 +133,15 @@ void davidson_report(const Davidson& E, int conv, double* omega, double* resnorm
 }
 
 // ---- the EOM-CCSD eigenproblems: EE, EE left, IP and EA on one driver (eom_so.h).  An entry point is its name and its kind; those of the
-// ipea family give their sector instead (and EOM_KINDS for the kind), which is checked first, as ever, and chooses the kind.
+// ipea family give their sector instead (and EOM_KINDS for the kind, EOM_KIND_IP_LEFT for the left side of either sector), which is checked
+// first, as ever, and chooses the kind.
 // call(cx, state, kind) does the work: the driver's function with the entry point's own arguments, or the step and its report.
 template <class Call>
 int eom_call(afesp_ctx* ctx, const char* who, EomKind kind, const int* sector, Call&& call)
 {
     return entry(ctx, [&](Context& cx) {
         if (sector && !so_eom_sector_ok(*sector)) throw Error(1, std::string(who) + ": sector must be AFESP_EOM_IP (1) or AFESP_EOM_EA (2)");
-        if (sector) kind = so_eom_kind_of_sector(*sector);
+        if (sector) kind = so_eom_kind_of_sector(*sector, kind == EOM_KIND_IP_LEFT);
         call(cx, ctx->sv.need_so((std::string(who) + ": no spin-orbital CCSD state").c_str()).so, kind);
     });
 }
@@ -165,7 +166,7 @@ int eom_iterate_entry(afesp_ctx* ctx, const char* who, EomKind kind, const int* 
 
 extern "C" {
 
-int afesp_version(void) { return 6; }
+int afesp_version(void) { return 7; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -808,6 +809,40 @@ int afesp_ccsd_so_relax_pair_row(afesp_ctx* ctx, int which, double* out, int rep
     return entry(ctx, [&](Context& cx) {
         const double t = so_relax_pair_row(cx, ctx->sv.need_so("afesp_ccsd_so_relax_pair_row: no spin-orbital CCSD state").so, which, out, reps);
         if (ms) *ms = t;
+    });
+}
+
+// ---- the left-hand side of the EOM-IP / EOM-EA sectors and their Dyson orbitals (eom_ipea_so.h, eom_ipea_left_so.hip)
+int afesp_ccsd_so_eom_ipea_lsigma(afesp_ctx* ctx, int sector, int nvec, const double* l1, const double* l2, double* s1, double* s2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_lsigma", EOM_KIND_IP_LEFT, &sector, so_eom_sigma_host, nvec, l1, l2, s1, s2);
+}
+int afesp_ccsd_so_eom_ipea_left_init(afesp_ctx* ctx, int sector, int nroots, int max_space)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_left_init", EOM_KIND_IP_LEFT, &sector, so_eom_init, nroots, max_space);
+}
+int afesp_ccsd_so_eom_ipea_left_guess(afesp_ctx* ctx, int sector)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_left_guess", EOM_KIND_IP_LEFT, &sector, so_eom_guess);
+}
+int afesp_ccsd_so_eom_ipea_left_set_guess(afesp_ctx* ctx, int sector, int k, const double* l1, const double* l2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_left_set_guess", EOM_KIND_IP_LEFT, &sector, so_eom_set_guess, k, l1, l2);
+}
+int afesp_ccsd_so_eom_ipea_left_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma,
+                                        int* converged)
+{
+    return eom_iterate_entry(ctx, "afesp_ccsd_so_eom_ipea_left_iterate", EOM_KIND_IP_LEFT, &sector, tol, omega, resnorm, flags, nsigma, converged);
+}
+int afesp_ccsd_so_eom_ipea_left_get_vector(afesp_ctx* ctx, int sector, int k, double* l1, double* l2)
+{
+    return eom_entry(ctx, "afesp_ccsd_so_eom_ipea_left_get_vector", EOM_KIND_IP_LEFT, &sector, so_eom_get_vector, k, l1, l2);
+}
+int afesp_ccsd_so_eom_ipea_dyson(afesp_ctx* ctx, int sector, int nvec, const double* l1, const double* l2, const double* r1, const double* r2,
+                                 double* dl, double* dr)
+{
+    return eom_call(ctx, "afesp_ccsd_so_eom_ipea_dyson", EOM_KINDS, &sector, [&](Context& cx, SOState& so, EomKind) {
+        so_eom_ipea_dyson(cx, so, sector, nvec, l1, l2, r1, r2, dl, dr);
     });
 }
 

@@ -9,7 +9,7 @@ namespace afesp {
 
 struct SOLambda;   // lambda_so.h
 struct SOEom;      // eom_so.h
-enum EomKind { EOM_KIND_EE = 0, EOM_KIND_EE_LEFT, EOM_KIND_IP, EOM_KIND_EA, EOM_KINDS };   // the EOM eigenproblems and their slots below
+enum EomKind { EOM_KIND_EE = 0, EOM_KIND_EE_LEFT, EOM_KIND_IP, EOM_KIND_EA, EOM_KIND_IP_LEFT, EOM_KIND_EA_LEFT, EOM_KINDS };   // the EOM eigenproblems and their slots below
 struct SOResponse; // response_so.h
 
 struct SOState : DiisRing {

@@ -11,29 +11,6 @@ namespace {
 
 constexpr double IPEA_SEED = 1e-3;   // weight of the guesses' admixture of every unique amplitude (ipea_unit_kernel)
 
-// the level of spin orbital p (occupied first) of either kind of state: lev of a UHF- or Fock-fed one, the spatial e of an RHF-fed one
-// (interleaved spins: so_denominators_kernel)
-__device__ __forceinline__ double ipea_level(const double* e, const double* lev, int o, int p)
-{
-    return lev ? lev[p] : (p < o ? e[p / 2] : e[(p - o) / 2 + o / 2]);
-}
-
-// The diagonal of a sector's matrix on full storage.  IP: -e_i, then -((e_i + e_j) - e_a); EA: e_a, then (e_a + e_b) - e_i.  The bracketed
-// sum is symmetric in the antisymmetric pair to the bit, so a product with an antisymmetric vector stays antisymmetric to the bit.
-__device__ __forceinline__ double ipea_diag(int sector, const double* e, const double* lev, int o, int v, int64_t x)
-{
-    if (sector == EOM_SECTOR_IP) {
-        if (x < o) return -ipea_level(e, lev, o, (int)x);
-        const int64_t y = x - o;
-        const int i = (int)(y % o), j = (int)((y / o) % o), a = (int)(y / ((int64_t)o * o));
-        return -__dadd_rn(__dadd_rn(ipea_level(e, lev, o, i), ipea_level(e, lev, o, j)), -ipea_level(e, lev, o, o + a));
-    }
-    if (x < v) return ipea_level(e, lev, o, o + (int)x);
-    const int64_t y = x - v;
-    const int i = (int)(y % o), a = (int)((y / o) % v), b = (int)(y / ((int64_t)o * v));
-    return __dadd_rn(__dadd_rn(ipea_level(e, lev, o, o + a), ipea_level(e, lev, o, o + b)), -ipea_level(e, lev, o, i));
-}
-
 __global__ void ipea_diag_kernel(double* diag, int sector, const double* e, const double* lev, int o, int v, int64_t nvec)
 {
     GRID_STRIDE(x, nvec) diag[x] = ipea_diag(sector, e, lev, o, v, x);
@@ -127,13 +104,30 @@ __global__ void ipea_unit_kernel(double* x, int64_t nvec, int64_t ip, int64_t im
     }
 }
 
+}  // namespace
+
+void preload_eom_ipea_so()
+{
+    static const bool loaded = [] {
+        first_use_touch(reinterpret_cast<const void*>(ipea_diag_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
+        first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
+        (void)hipGetLastError();
+        return true;
+    }();
+    (void)loaded;
+}
+
 // W(i,a,b) = sum_{e<f} <ab||ef> r(i,e,f) = 1/2 sum_ef: the bare ladder over the antisymmetric pair (e,f) against the pair-form va the T
 // iteration built at init, in that iteration's own pair buffers ta / pa and with its offset table -- r is packed as ra(i, ef) on ta's
 // leading dimension, a tall x skinny product M = K = v (v - 1) / 2, N = o.  That needs o <= o (o - 1) / 2, so that r fills rows of ta the T
 // iteration fills too and its zero padding stays zero: o >= 3.  A state with o = 2, or without va (o = 1: the T iteration has no pair of
 // occupied orbitals), contracts against <ab||ef> itself.
-void ea_ladder_bare(Context& cx, SOState& s, const Tensor& r2, const Tensor& W)
+void so_eom_ea_ladder_bare(Context& cx, SOState& s, const Tensor& r2, const Tensor& W)
 {
+    preload_eom_ipea_so();
     const int o = s.o, v = s.v;
     const int64_t V = v, npv = V * (V - 1) / 2, ka = s.lad_ka, na = s.lad_na, oa = (o + 1) & ~1;
     if (npv == 0) {
@@ -160,22 +154,6 @@ void ea_ladder_bare(Context& cx, SOState& s, const Tensor& r2, const Tensor& W)
     ++(tall ? cx.n_tall : cx.n_gett);
     AFESP_HIP(tall ? tall_launch(gp, cx.stream) : gett_launch(gp, cx.ws, cx.stream));
     LAUNCH(ipea_ea_expand_kernel, grid_for(W.size()), W.d, s.pa, o, v, na);
-}
-
-}  // namespace
-
-void preload_eom_ipea_so()
-{
-    static const bool loaded = [] {
-        first_use_touch(reinterpret_cast<const void*>(ipea_diag_kernel));
-        first_use_touch(reinterpret_cast<const void*>(ipea_assemble_kernel));
-        first_use_touch(reinterpret_cast<const void*>(ipea_ea_pack_kernel));
-        first_use_touch(reinterpret_cast<const void*>(ipea_ea_expand_kernel));
-        first_use_touch(reinterpret_cast<const void*>(ipea_unit_kernel));
-        (void)hipGetLastError();
-        return true;
-    }();
-    (void)loaded;
 }
 
 double so_eom_ipea_bytes(int64_t o, int64_t v, int sector, int nroots, int max_space)
@@ -234,7 +212,7 @@ void so_eom_ipea_sigma(Context& cx, SOState& s, int sector, const double* r, dou
         // ---- sigma2: W = bare ladder + 1/4 Q_imn tau_mnab + y_m t_imab - H_mi r_mab - H_abei r_e  (H_abei stored (i,e,a,b));
         //      P(ab) [ -t_mb Z_iam + H_mbei r_mae + H_be r_iae ]
         Tensor W = view(cx.scratch("ipea_W", n2), {O, V, V}), A = view(cx.scratch("ipea_A", n2), {O, V, V});
-        ea_ladder_bare(cx, s, r2, W);
+        so_eom_ea_ladder_bare(cx, s, r2, W);
         C(0.25, Q, "imn", L.tau, "mnab", 1.0, W, "iab");
         C(1.0, t2, "imab", y, "m", 1.0, W, "iab");
         C(-1.0, L.Hoo, "mi", r2, "mab", 1.0, W, "iab");

@@ -2,7 +2,8 @@
 // the Jacobian A = dR/dt of the residuals so_amplitudes evaluates before its division: sigma(r) = A r is contracted from the
 // lambda-independent H-bar elements a live SOLambda keeps resident (borrowed, not copied), and the lowest eigenvalues of A come from a
 // block Davidson iteration whose vectors never leave the device.  On full (i,j,a,b) storage <x, y> = sum x1 y1 + 1/4 sum x2 y2.
-// The same driver serves the four eigenproblems -- EE, EE left (A^T), IP and EA (eom_ipea_so.h): one state
+// The same driver serves the six eigenproblems -- EE, EE left (A^T), IP and EA (eom_ipea_so.h) and their left
+// sides: one state
 // type, one slot per kind in SOState::eom, and what differs per kind in one descriptor (eom_problem in eom_so.hip).
 #pragma once
 #include "davidson_so.h"
@@ -10,10 +11,13 @@
 
 namespace afesp {
 
-// EomKind (ccsd_so.h): EOM_KIND_EE, EOM_KIND_EE_LEFT, EOM_KIND_IP, EOM_KIND_EA.  The sectors of the C interface (AFESP_EOM_IP / AFESP_EOM_EA):
+// EomKind (ccsd_so.h): EOM_KIND_EE, EOM_KIND_EE_LEFT, EOM_KIND_IP, EOM_KIND_EA, EOM_KIND_IP_LEFT, EOM_KIND_EA_LEFT.  The sectors of the C interface (AFESP_EOM_IP / AFESP_EOM_EA):
 constexpr int EOM_SECTOR_IP = 1, EOM_SECTOR_EA = 2;
 inline bool so_eom_sector_ok(int sector) { return sector == EOM_SECTOR_IP || sector == EOM_SECTOR_EA; }
-inline EomKind so_eom_kind_of_sector(int sector) { return sector == EOM_SECTOR_IP ? EOM_KIND_IP : EOM_KIND_EA; }
+inline EomKind so_eom_kind_of_sector(int sector, bool left = false)
+{
+    return sector == EOM_SECTOR_IP ? (left ? EOM_KIND_IP_LEFT : EOM_KIND_IP) : (left ? EOM_KIND_EA_LEFT : EOM_KIND_EA);
+}
 
 struct SOEom {
     Davidson d;                 // EE: n1 = o v, n2 = o^2 v^2, w2 = 1/4, diag = -D; IP: n1 = o, n2 = o^2 v; EA: n1 = v, n2 = o v^2; w2 = 1/2

@@ -1,6 +1,6 @@
 // eom_so.hip -- EOM-EE-CCSD on the spin-orbital CCSD state (eom_so.h): the sigma build sigma(r) = A r, term by term in
 // the letters of tests/np_eom.py (sigma_explicit) over the H-bar elements of the live Lambda state, the diagonal and the guesses, for the
-// block Davidson iteration of davidson_so.h on the non-symmetric A; and the one driver of the four EOM eigenproblems (EE, EE left, IP, EA)
+// block Davidson iteration of davidson_so.h on the non-symmetric A; and the one driver of the six EOM eigenproblems (EE, IP, EA, their left sides)
 // over a descriptor per kind.  Launches are plain call-by-call ones, as Lambda's.
 #include "device_util.h"
 #include "eom_ipea_so.h"
@@ -139,7 +139,7 @@ void so_eom_sigma(Context& cx, SOState& s, const double* r, double* sigma)
     LAUNCH(eom_sigma_assemble_kernel, grid_for(o2v2), sigma + ov, sigma, lad.d, AB.d, A.d, Bm.d, r2.d, r1.d, s.D2.d, s.D1.d, o, v);
 }
 
-// ---- the driver of the four eigenproblems (eom_so.h).  What differs per kind, and nothing else:
+// ---- the driver of the six eigenproblems (eom_so.h).  What differs per kind, and nothing else:
 namespace {
 
 struct EomProblem {
@@ -206,6 +206,7 @@ std::vector<double> diag_sort_key(Context& cx, SOState&, const Davidson& E)
 }
 
 void preload_eom_both_sides() { preload_eom_so(); preload_eom_left_so(); }
+void preload_eom_ipea_both_sides() { preload_eom_ipea_so(); preload_eom_ipea_left_so(); }
 
 EomProblem eom_problem(const SOState& s, EomKind kind)
 {
@@ -226,19 +227,22 @@ EomProblem eom_problem(const SOState& s, EomKind kind)
         P.sigma = left ? so_eom_lsigma : so_eom_sigma;   // (left: the projected matrix is then <b_p, sigma_L(b_q)>)
         P.sort_key = ee_sort_key; P.unique = ee_unique; P.unit = ee_unit;
     } else {
-        const bool ip = kind == EOM_KIND_IP;
+        const bool ip = kind == EOM_KIND_IP || kind == EOM_KIND_IP_LEFT, left = kind == EOM_KIND_IP_LEFT || kind == EOM_KIND_EA_LEFT;
         const int sector = ip ? EOM_SECTOR_IP : EOM_SECTOR_EA;
-        P.prefix = "afesp_ccsd_so_eom_ipea_";
-        P.state = ip ? "EOM-IP" : "EOM-EA";
+        P.prefix = left ? "afesp_ccsd_so_eom_ipea_left_" : "afesp_ccsd_so_eom_ipea_";
+        P.state = left ? (ip ? "left EOM-IP" : "left EOM-EA") : (ip ? "EOM-IP" : "EOM-EA");
         P.space = ip ? "the unique amplitudes of the EOM-IP sector" : "the unique amplitudes of the EOM-EA sector";
-        P.sigma_entry = "afesp_ccsd_so_eom_ipea_sigma";
-        P.r_stage = "ipea_r_stage"; P.s_stage = "ipea_s_stage";
+        P.sigma_entry = left ? "afesp_ccsd_so_eom_ipea_lsigma" : "afesp_ccsd_so_eom_ipea_sigma";
+        P.r_stage = left ? "ipeal_r_stage" : "ipea_r_stage"; P.s_stage = left ? "ipeal_s_stage" : "ipea_s_stage";
         P.n1 = ip ? O : V; P.n2 = ip ? O * O * V : O * V * V; P.nunique = ip ? O + (O * (O - 1) / 2) * V : V + O * (V * (V - 1) / 2);
-        P.w2 = 0.5; P.follow = false;
-        P.bytes = [=](int nroots, int max_space) { return so_eom_ipea_bytes(O, V, sector, nroots, max_space); };
-        P.preload = preload_eom_ipea_so;
+        P.w2 = 0.5; P.follow = left;
+        P.bytes = [=](int nroots, int max_space) { return (left ? so_eom_ipea_left_bytes : so_eom_ipea_bytes)(O, V, sector, nroots, max_space); };
+        P.preload = left ? preload_eom_ipea_both_sides : preload_eom_ipea_so;
         P.fill_diag = [=](Context& cx, SOState& st, double* diag) { so_eom_ipea_fill_diag(cx, st, sector, diag); };
-        P.sigma = [=](Context& cx, SOState& st, const double* r, double* sigma) { so_eom_ipea_sigma(cx, st, sector, r, sigma); };
+        // (left: -D is the diagonal of A^T too -- the same diagonal, unique amplitudes and unit vectors with the admixture)
+        P.sigma = [=](Context& cx, SOState& st, const double* r, double* sigma) {
+            (left ? so_eom_ipea_lsigma : so_eom_ipea_sigma)(cx, st, sector, r, sigma);
+        };
         P.sort_key = diag_sort_key;
         P.unique = [=](const SOState& st, std::vector<int64_t>& idx) { so_eom_ipea_unique(st, sector, idx); };
         P.unit = [=](Context& cx, SOState& st, double* x, int64_t p) { so_eom_ipea_unit(cx, st, sector, x, p); };

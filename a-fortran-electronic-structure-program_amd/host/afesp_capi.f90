@@ -26,6 +26,9 @@ module afesp_capi
              afesp_ccsd_so_eom_density, &
              afesp_ccsd_so_eom_ipea_init, afesp_ccsd_so_eom_ipea_sigma, afesp_ccsd_so_eom_ipea_guess, afesp_ccsd_so_eom_ipea_set_guess, &
              afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
+             afesp_ccsd_so_eom_ipea_lsigma, afesp_ccsd_so_eom_ipea_left_init, afesp_ccsd_so_eom_ipea_left_guess, &
+             afesp_ccsd_so_eom_ipea_left_set_guess, afesp_ccsd_so_eom_ipea_left_iterate, afesp_ccsd_so_eom_ipea_left_get_vector, &
+             afesp_ccsd_so_eom_ipea_dyson, &
              afesp_ccsd_so_response_init, afesp_ccsd_so_response_iterate, afesp_ccsd_so_response_function, &
              afesp_ccsd_so_response_init_complex, afesp_ccsd_so_response_function_complex, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
@@ -673,6 +676,63 @@ module afesp_capi
          type(c_ptr), value :: ctx
          integer(c_int), value :: sector, k
          real(c_double), intent(out) :: r1(*), r2(*)
+         integer(c_int) :: rc
+      end function
+      ! the left-hand side of both sectors and the Dyson orbitals (include/afesp.h).  _dyson takes c_ptr arguments: c_loc of the
+      ! vectors, or c_null_ptr for an absent side
+      function afesp_ccsd_so_eom_ipea_lsigma(ctx, sector, nvec, l1, l2, s1, s2) bind(C, name='afesp_ccsd_so_eom_ipea_lsigma') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nvec
+         real(c_double), intent(in) :: l1(*), l2(*)
+         real(c_double), intent(out) :: s1(*), s2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_left_init(ctx, sector, nroots, max_space) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_left_init') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nroots, max_space
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_left_guess(ctx, sector) bind(C, name='afesp_ccsd_so_eom_ipea_left_guess') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_left_set_guess(ctx, sector, k, l1, l2) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_left_set_guess') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, k
+         real(c_double), intent(in) :: l1(*), l2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_left_iterate(ctx, sector, tol, omega, resnorm, flags, nsigma, converged) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_left_iterate') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector
+         real(c_double), value :: tol
+         real(c_double), intent(out) :: omega(*), resnorm(*)
+         integer(c_int), intent(out) :: flags(*), nsigma, converged
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_left_get_vector(ctx, sector, k, l1, l2) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_left_get_vector') result(rc)
+         import :: c_int, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, k
+         real(c_double), intent(out) :: l1(*), l2(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_dyson(ctx, sector, nvec, l1, l2, r1, r2, dl, dr) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_dyson') result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nvec
+         type(c_ptr), value :: l1, l2, r1, r2, dl, dr
          integer(c_int) :: rc
       end function
       function afesp_eig_general(n, a, lda, wr, wi, vr) bind(C, name='afesp_eig_general') result(rc)

@@ -67,6 +67,8 @@ module host_config
       logical :: eom_triples = .false.
       ! ... this many EOM-IP-CCSD ionisation potentials / EOM-EA-CCSD electron affinities (0: off)
       integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
+      ! ... and the left eigenvectors and pole strengths of those roots (needs one of the two > 0)
+      logical :: eom_ipea_left = .false.
       ! after a converged spin-orbital CCSD: the EOM-CCSD polarisability alpha(omega) of the operators in dipx.dat / dipy.dat / dipz.dat
       ! (AO basis, the format of t.dat) at the n_polar_omega real frequencies polar_omega (default: the static one)
       logical :: cc_polar = .false.
@@ -88,14 +90,14 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left, eom_triples, cc_rdm2, cc_relaxed, cc_polar
+      logical :: eom_left, eom_triples, cc_rdm2, cc_relaxed, cc_polar, eom_ipea_left
       real(dp) :: polar_omega(8), polar_gamma
       integer :: polar_c6_npts
       real(dp), parameter :: omega_unset = huge(1.0_dp)
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, eom_triples, cc_rdm2, cc_relaxed, &
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, eom_triples, eom_ipea_left, cc_rdm2, cc_relaxed, &
          cc_polar, polar_omega, polar_gamma, polar_c6_npts
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
@@ -108,6 +110,7 @@ contains
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
       cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left; eom_triples = d%eom_triples
+      eom_ipea_left = d%eom_ipea_left
       cc_polar = d%cc_polar; polar_omega = omega_unset
       polar_gamma = d%polar_gamma; polar_c6_npts = d%polar_c6_npts
       inquire (file='els.in', exist=there)
@@ -228,6 +231,10 @@ contains
          trim(calc_type)//' takes no eom_ip_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
       if (eom_ea_nroots > 0 .and. .not. (cfg%level >= LEVEL_CCSD .and. (cfg%spinorb .or. cfg%uhf))) call fail('system::read_system_in', &
          trim(calc_type)//' takes no eom_ea_nroots: the EOM-CCSD equations run on the spin-orbital CCSD types!')
+      cfg%eom_ipea_left = eom_ipea_left
+      if (eom_ipea_left .and. eom_ip_nroots == 0 .and. eom_ea_nroots == 0) call fail('system::read_system_in', &
+         'eom_ipea_left needs eom_ip_nroots > 0 or eom_ea_nroots > 0: the left eigenvectors and pole strengths are those of '// &
+         'the EOM-IP-CCSD / EOM-EA-CCSD roots they ask for!')
       if (cfg%rohf) then   ! no ROHF SCF here: the orbitals come from a file, and a frozen core reaches this path as an active-space file
          if (.not. fcidump_in) call fail('system::read_system_in', trim(calc_type)// &
             ' needs fcidump_in = .true.: there is no ROHF SCF, the restricted open-shell orbitals come from a FCIDUMP!')
@@ -1015,7 +1022,7 @@ program els_amd
             if (.not. allocated(ab_overlap)) ab_overlap = matmul(cb, matmul(mol%ovlp, transpose(coeff)))
             call relaxed_density_report(n_act, na_act, nb_act, .false.)
          end if
-         if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
+         if ((cfg%cc_lambda_t .or. cfg%eom_ipea_left) .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, na_act + nb_act, 2*n_act - na_act - nb_act)
@@ -1124,7 +1131,7 @@ program els_amd
          if (cfg%cc_density .and. cc_ok) call lambda_and_occupations(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%cc_rdm2 .and. cc_ok) call rdm2_energy_and_spin(n_act, nel_act/2, nel_act/2, .true.)
          if (cfg%cc_relaxed .and. cc_ok) call relaxed_density_report(n_act, nel_act/2, nel_act/2, .true.)
-         if (cfg%cc_lambda_t .and. cc_ok .and. .not. lambda_live) call lambda_solve()
+         if ((cfg%cc_lambda_t .or. cfg%eom_ipea_left) .and. cc_ok .and. .not. lambda_live) call lambda_solve()
          if (cfg%eom_nroots > 0 .and. cc_ok) call eom_excitations(nel_act, 2*n_act - nel_act)
          if (cfg%eom_ip_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_IP, cfg%eom_ip_nroots, nel_act, 2*n_act - nel_act)
          if (cfg%eom_ea_nroots > 0 .and. cc_ok) call eom_ipea(AFESP_EOM_EA, cfg%eom_ea_nroots, nel_act, 2*n_act - nel_act)
@@ -2186,7 +2193,141 @@ contains
          end if
       end do
       write (out, '(75("-"))')
+      if (cfg%eom_ipea_left) call eom_ipea_left_report(sector, what, nr, ms, int(o + v), n1, n2, omega)
       write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for '//what//'-CCSD:', seconds() - te, 's'
+   end subroutine
+   !> eom_ipea_left: the left eigenvectors of the nr roots just solved, on a Davidson state of its own from the right vectors as guess,
+   !> biorthonormalised against the right ones inside every cluster of degenerate roots (S^-1 L, S_jk = <L_j, R_k> = sum l1 r1 +
+   !> 1/2 sum l2 r2: every doublet of a closed-shell reference is a twofold cluster; roots with one and the same right vector are one state),
+   !> and the pole strengths sum_p gamma_L(p) gamma_R(p) of
+   !> the Dyson vectors, with the converged Lambda the main program solved before the sector.
+   subroutine eom_ipea_left_report(sector, what, nr, ms, nso, n1, n2, omega)
+      integer(c_int), intent(in) :: sector
+      character(6), intent(in) :: what
+      integer, intent(in) :: nr, ms, nso
+      integer(c_int64_t), intent(in) :: n1, n2
+      real(dp), intent(in) :: omega(:)
+      real(dp), parameter :: hartree_ev = 27.211386245988_dp, eom_tol = 1.0e-8_dp, degeneracy_tol = 1.0e-6_dp
+      real(dp), allocatable, target :: r1(:, :), r2(:, :), b1(:, :), b2(:, :), dl(:, :), dr(:, :)
+      real(dp), allocatable :: l1(:, :), l2(:, :), omega_l(:), res_l(:), s(:, :), si(:, :)
+      integer(c_int), allocatable :: flags_l(:)
+      integer, allocatable :: order(:), owner(:), st(:)
+      integer(c_int) :: nsig, econv
+      integer :: it, k, j, a, b, c0, c1, nc, piv
+      real(dp) :: f
+      logical :: ok
+      allocate (r1(n1, nr), r2(n2, nr), l1(n1, nr), l2(n2, nr), b1(n1, nr), b2(n2, nr), dl(nso, nr), dr(nso, nr), order(nr), owner(nr), st(nr))
+      allocate (omega_l(nr), res_l(nr), flags_l(nr))
+      rc = afesp_ccsd_so_eom_ipea_left_init(ctx, sector, int(nr, c_int), int(ms, c_int))
+      if (rc /= 0) call fail('eom_ipea::init_left', afesp_error_text(ctx))
+      do k = 1, nr
+         rc = afesp_ccsd_so_eom_ipea_get_vector(ctx, sector, int(k - 1, c_int), r1(:, k), r2(:, k))
+         if (rc /= 0) call fail('eom_ipea::get_vector', afesp_error_text(ctx))
+         rc = afesp_ccsd_so_eom_ipea_left_set_guess(ctx, sector, int(k - 1, c_int), r1(:, k), r2(:, k))
+         if (rc /= 0) call fail('eom_ipea::left_guess', afesp_error_text(ctx))
+      end do
+      ok = .false.
+      do it = 1, 100
+         rc = afesp_ccsd_so_eom_ipea_left_iterate(ctx, sector, eom_tol, omega_l, res_l, flags_l, nsig, econv)
+         if (rc /= 0) call fail('eom_ipea::left_davidson_step', afesp_error_text(ctx))
+         if (econv /= 0) then
+            ok = .true.
+            exit
+         end if
+      end do
+      if (.not. ok) call fail('eom_ipea::do_eom_left', 'the left '//what//'-CCSD Davidson iteration did not converge!')
+      do k = 1, nr
+         rc = afesp_ccsd_so_eom_ipea_left_get_vector(ctx, sector, int(k - 1, c_int), l1(:, k), l2(:, k))
+         if (rc /= 0) call fail('eom_ipea::left_get_vector', afesp_error_text(ctx))
+      end do
+      ! roots in ascending order, clusters of neighbours within degeneracy_tol
+      do k = 1, nr
+         order(k) = k
+      end do
+      do k = 2, nr
+         j = k
+         do while (j > 1)
+            if (omega(order(j - 1)) <= omega(order(j))) exit
+            a = order(j); order(j) = order(j - 1); order(j - 1) = a
+            j = j - 1
+         end do
+      end do
+      c0 = 1
+      do while (c0 <= nr)
+         c1 = c0
+         do while (c1 < nr)
+            if (abs(omega(order(c1 + 1)) - omega(order(c1))) >= degeneracy_tol) exit
+            c1 = c1 + 1
+         end do
+         ! the distinct states of the cluster: roots whose right vectors are equal to the bit are one state (the library gives both members
+         ! of a pair that rounding split into omega +- i epsilon the pair's one real vector); st(1 .. nc) are the states' first roots
+         nc = 0
+         do k = c0, c1
+            owner(order(k)) = order(k)
+            do a = 1, nc
+               if (all(r1(:, order(k)) == r1(:, st(a))) .and. all(r2(:, order(k)) == r2(:, st(a)))) owner(order(k)) = st(a)
+            end do
+            if (owner(order(k)) == order(k)) then
+               nc = nc + 1; st(nc) = order(k)
+            end if
+         end do
+         allocate (s(nc, nc), si(nc, nc))
+         do a = 1, nc
+            do b = 1, nc
+               s(a, b) = sum(l1(:, st(a))*r1(:, st(b))) + 0.5_dp*sum(l2(:, st(a))*r2(:, st(b)))
+            end do
+         end do
+         ! si = s^-1 by Gauss-Jordan elimination with partial pivoting (clusters are multiplets: a few roots)
+         si = 0.0_dp
+         do a = 1, nc
+            si(a, a) = 1.0_dp
+         end do
+         do a = 1, nc
+            piv = a
+            do b = a + 1, nc
+               if (abs(s(b, a)) > abs(s(piv, a))) piv = b
+            end do
+            if (abs(s(piv, a)) < 1.0e-8_dp) call fail('eom_ipea::biorthonormalise', &
+               'the overlap of the left and right vectors of a cluster of degenerate roots is singular: the two solves found different states!')
+            if (piv /= a) then
+               s([a, piv], :) = s([piv, a], :); si([a, piv], :) = si([piv, a], :)
+            end if
+            f = 1.0_dp/s(a, a)
+            s(a, :) = f*s(a, :); si(a, :) = f*si(a, :)
+            do b = 1, nc
+               if (b /= a) then
+                  f = s(b, a)
+                  s(b, :) = s(b, :) - f*s(a, :); si(b, :) = si(b, :) - f*si(a, :)
+               end if
+            end do
+         end do
+         do a = 1, nc
+            b1(:, st(a)) = 0.0_dp; b2(:, st(a)) = 0.0_dp
+            do b = 1, nc
+               b1(:, st(a)) = b1(:, st(a)) + si(a, b)*l1(:, st(b))
+               b2(:, st(a)) = b2(:, st(a)) + si(a, b)*l2(:, st(b))
+            end do
+         end do
+         do k = c0, c1
+            if (owner(order(k)) /= order(k)) then
+               b1(:, order(k)) = b1(:, owner(order(k))); b2(:, order(k)) = b2(:, owner(order(k)))
+            end if
+         end do
+         deallocate (s, si)
+         c0 = c1 + 1
+      end do
+      rc = afesp_ccsd_so_eom_ipea_dyson(ctx, sector, int(nr, c_int), c_loc(b1), c_loc(b2), c_loc(r1), c_loc(r2), c_loc(dl), c_loc(dr))
+      if (rc /= 0) call fail('eom_ipea::dyson', afesp_error_text(ctx))
+      write (out, '(1X, A, 1X, I0, A, I0)') 'Left eigenvectors: Davidson steps:', it, ', sigma builds: ', nsig
+      write (out, '(96("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Root', 'omega left (Eh)   ', ' omega left (eV)  ', '|left-right|', ' Residual ', &
+         '  Pole strength   '
+      write (out, '(96("-"))')
+      do k = 1, nr
+         write (out, '(1X, I4, 3X, F18.12, 3X, F18.10, 3X, ES12.3, 3X, ES10.3, 3X, F18.14)') k, omega_l(k), omega_l(k)*hartree_ev, &
+            abs(omega_l(k) - omega(k)), res_l(k), sum(dl(:, k)*dr(:, k))
+      end do
+      write (out, '(96("-"))')
    end subroutine
    subroutine print_fno_cut(asked, kept_occ, dropped_occ, any_dropped)
       integer, intent(in) :: asked

@@ -501,6 +501,31 @@ int afesp_ccsd_so_eom_ipea_iterate(afesp_ctx* ctx, int sector, double tol, doubl
                                    int* converged);
 int afesp_ccsd_so_eom_ipea_get_vector(afesp_ctx* ctx, int sector, int k, double* r1, double* r2);
 
+/* The left-hand side of both sectors, Dyson orbitals and pole strengths (afesp_version 7).  sigma_L = A^T l, the transpose
+ * in the sector's metric: <l, sigma(r)> = <sigma_L(l), r>; the vectors are laid out as the right-hand ones.
+ *   afesp_ccsd_so_eom_ipea_lsigma   = s = A^T l for nvec vectors stored one after the other; needs the Lambda state only.
+ *   afesp_ccsd_so_eom_ipea_left_*   = one more block Davidson state per sector, for A^T, beside the right-hand one and with its rules
+ *                                     (arguments, statuses, the guesses of _left_guess with their admixture).  From the caller's guesses
+ *                                     (_left_set_guess with the converged right vectors) the state follows the states of the guesses, as
+ *                                     afesp_ccsd_so_eom_left_* does: root k of the left state is root k of the right one.
+ *   afesp_ccsd_so_eom_ipea_dyson    = the Dyson vectors of nvec left and / or right vectors over all nocc + nvirt spin orbitals in the
+ *                                     state's order, (nocc + nvirt) x nvec column-major:
+ *                                       dl[p] = <0| L e^-T a_p e^T |0>,  dr[p] = <0| (1 + Lambda) e^-T a_p^+ e^T R |0>     (IP; a_p^+ / a_p: EA)
+ *                                     with the phases of the ghost-orbital construction that defines the sectors.  For a biorthonormal
+ *                                     pair <L_k, R_k> = 1 the pole strength is sum_p dl[p] dr[p].  l1 / l2 both NULL (dl is not written)
+ *                                     or both given, and r1 / r2 / dr likewise; a half-given pair is status 1.  Needs the live Lambda
+ *                                     state (status 21 otherwise: it reads lambda) and no Davidson state.
+ * None writes t1 / t2, lambda, the epoch or the state of another kind. */
+int afesp_ccsd_so_eom_ipea_lsigma(afesp_ctx* ctx, int sector, int nvec, const double* l1, const double* l2, double* s1, double* s2);
+int afesp_ccsd_so_eom_ipea_left_init(afesp_ctx* ctx, int sector, int nroots, int max_space);
+int afesp_ccsd_so_eom_ipea_left_guess(afesp_ctx* ctx, int sector);
+int afesp_ccsd_so_eom_ipea_left_set_guess(afesp_ctx* ctx, int sector, int k, const double* l1, const double* l2);
+int afesp_ccsd_so_eom_ipea_left_iterate(afesp_ctx* ctx, int sector, double tol, double* omega, double* resnorm, int* flags, int* nsigma,
+                                        int* converged);
+int afesp_ccsd_so_eom_ipea_left_get_vector(afesp_ctx* ctx, int sector, int k, double* l1, double* l2);
+int afesp_ccsd_so_eom_ipea_dyson(afesp_ctx* ctx, int sector, int nvec, const double* l1, const double* l2, const double* r1, const double* r2,
+                                 double* dl, double* dr);
+
 /* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
  * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
  *   afesp_build_fock_uhf = fock_s = core_hamil + J[dens_a + dens_b] - K[dens_s] for s = a, b on the resident packed AO integrals

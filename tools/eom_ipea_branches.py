@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Prints the per-product tables of tests/test_gpu_eom_ipea_mid.py: every product of one EOM-IP and one EOM-EA sigma build at the three
 mid-size shapes with its kernel extents, tile code, K slices and staging width, from the launcher's own lines (AFESP_GETT_DEBUG,
-AFESP_CONTRACT_TRACE), and which of them the tall kernel takes once AFESP_TALL_MIN is o^2 v (tools/eom_branches.py, for the two sectors)."""
+AFESP_CONTRACT_TRACE), and which of them the tall kernel takes once AFESP_TALL_MIN is o^2 v (tools/eom_branches.py, for the two sectors).
+With --left: the same tables for the left sigma builds, for tests/test_gpu_eom_ipea_left_mid.py."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "a-fortran-electronic-structure-program_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -26,7 +27,7 @@ with Engine(0) as eng:
     eng.so_set_amplitudes(*t)
     eng.so_lambda_init(0)
     sys.stderr.write("SIGMA BEGINS\\n"); sys.stderr.flush()
-    eng.so_eom_ipea_sigma(sector, *r)
+    (eng.so_eom_ipea_lsigma if {left} else eng.so_eom_ipea_sigma)(sector, *r)
 """
 LAUNCH = re.compile(r"gett_launch M (\d+) N (\d+) K (\d+) batch \d+ akc \d bkc \d wide (\d) -> tm (\d+) tn (\d+) tiles \d+ x \d+ split (\d+)")
 TRACE = re.compile(r"contract (\S+)\s*,(\S+)\s*>(\S+)\s+M\s+(\d+) N\s+(\d+) K\s+(\d+) akc \d bkc \d wide (\d)[^\n]*?(\(repacked\)|\(tall\))?$")
@@ -36,7 +37,7 @@ def run(name, sector, tall_min=None):
     env = dict(os.environ, AFESP_GETT_DEBUG="1", AFESP_CONTRACT_TRACE="1")
     if tall_min is not None:
         env["AFESP_TALL_MIN"] = str(tall_min)
-    src = CHILD.format(pkg=os.path.join(ROOT, "a-fortran-electronic-structure-program_amd"), tests=os.path.join(ROOT, "tests"))
+    src = CHILD.format(pkg=os.path.join(ROOT, "a-fortran-electronic-structure-program_amd"), tests=os.path.join(ROOT, "tests"), left="--left" in sys.argv)
     err = subprocess.run([sys.executable, "-c", src, name, str(sector)], env=env, capture_output=True, text=True, timeout=600, check=True).stderr
     rows, last = [], None
     for line in err.split("SIGMA BEGINS\n", 1)[1].splitlines():

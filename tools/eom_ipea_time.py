@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """One EOM-IP-CCSD and one EOM-EA-CCSD sigma build and one Davidson step of each with 4 roots, next to one Lambda iteration and one
-EOM-EE sigma build, on the same spin-orbital state at the H2O/cc-pVTZ shape (n = 58, 10 electrons -> o = 10, v = 106 spin orbitals;
+EOM-EE sigma build, and the left-hand side of both sectors (a left sigma build, a left Davidson step, a Dyson call of
+4 left and 4 right vectors), on the same spin-orbital state at the H2O/cc-pVTZ shape (n = 58, 10 electrons -> o = 10, v = 106 spin orbitals;
 synthetic integrals as tools/eom_time.py).  Wall times of the calls, each synchronised by its own host read; the median of the repeats
-after one warm call.  DESIGN.md 4.14 records the numbers."""
+after one warm call.  DESIGN.md 4.14 and 4.22 record the numbers."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "a-fortran-electronic-structure-program_amd")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -60,3 +61,21 @@ with Engine(0) as eng:
             t0 = time.perf_counter(); om, res, fl, ns, cv = eng.so_eom_ipea_iterate(sector, 1e-8); ts.append((time.perf_counter() - t0) * 1e3)
             print("%s Davidson step %d: %8.3f ms, %d sigma builds so far, omega[0] %.8f, residuals %s" % (title, it + 2, ts[-1], ns, om[0], np.array2string(res, precision=2)))
         print("%s Davidson step      median %8.3f ms for %d roots" % (title, float(np.median(ts)), nroots))
+        one = lambda: eng._chk(eng.L.afesp_ccsd_so_eom_ipea_lsigma(eng.h, sector, 1, c1, c2, d1, d2))
+        g0 = eng.launch_counts()
+        one()
+        g1 = eng.launch_counts()
+        print("%s left sigma, host in/out median %8.3f ms  (min %.3f, max %.3f); products: %d gather, %d tall"
+              % (title, *median_ms(one), g1["gett"] - g0["gett"], g1["tall"] - g0["tall"]))
+        eng.so_eom_ipea_left_init(sector, nroots, 8 * nroots)
+        eng.so_eom_ipea_left_guess(sector)
+        eng.so_eom_ipea_left_iterate(sector, 1e-8)
+        ts = []
+        for it in range(5):
+            t0 = time.perf_counter(); om, res, fl, ns, cv = eng.so_eom_ipea_left_iterate(sector, 1e-8); ts.append((time.perf_counter() - t0) * 1e3)
+        print("%s left Davidson step median %8.3f ms for %d roots" % (title, float(np.median(ts)), nroots))
+        X = [eng.so_eom_ipea_vector(sector, k) for k in range(nroots)]
+        Y = [eng.so_eom_ipea_left_vector(sector, k) for k in range(nroots)]
+        pair = lambda V: (np.stack([x[0] for x in V]), np.stack([x[1] for x in V]))
+        print("%s Dyson call, %d left and %d right vectors, host in/out median %8.3f ms  (min %.3f, max %.3f)"
+              % (title, nroots, nroots, *median_ms(lambda: eng.so_eom_ipea_dyson(sector, pair(Y), pair(X)))))
