@@ -42,7 +42,7 @@ EXPORTS = [
     "afesp_ccsd_so_eom_ipea_iterate", "afesp_ccsd_so_eom_ipea_get_vector",
     "afesp_ccsd_so_eom_ipea_lsigma", "afesp_ccsd_so_eom_ipea_left_init", "afesp_ccsd_so_eom_ipea_left_guess",
     "afesp_ccsd_so_eom_ipea_left_set_guess", "afesp_ccsd_so_eom_ipea_left_iterate", "afesp_ccsd_so_eom_ipea_left_get_vector",
-    "afesp_ccsd_so_eom_ipea_dyson",
+    "afesp_ccsd_so_eom_ipea_dyson", "afesp_ccsd_so_eom_ipea_t", "afesp_ccsd_so_eom_ipea_t_nitems",
     "afesp_ccsd_so_response_xi", "afesp_ccsd_so_response_init", "afesp_ccsd_so_response_iterate", "afesp_ccsd_so_response_get_vector",
     "afesp_ccsd_so_response_function", "afesp_lu_solve",
     "afesp_ccsd_so_response_init_complex", "afesp_ccsd_so_response_get_vector_complex", "afesp_ccsd_so_response_function_complex",
@@ -185,6 +185,9 @@ def load_library():
     L.afesp_ccsd_so_eom_ipea_left_iterate.argtypes = L.afesp_ccsd_so_eom_ipea_iterate.argtypes
     L.afesp_ccsd_so_eom_ipea_left_get_vector.argtypes = L.afesp_ccsd_so_eom_ipea_get_vector.argtypes
     L.afesp_ccsd_so_eom_ipea_dyson.argtypes = [C.c_void_p, C.c_int, C.c_int, _opt, _opt, _opt, _opt, _opt, _opt]
+    L.afesp_ccsd_so_eom_ipea_t.argtypes = [C.c_void_p, C.c_int, C.c_int, _opt, _opt, _opt, _opt, _opt, i64, i64, _opt]
+    L.afesp_ccsd_so_eom_ipea_t_nitems.argtypes = [C.c_int, C.c_int]
+    L.afesp_ccsd_so_eom_ipea_t_nitems.restype = i64
     L.afesp_eig_general.argtypes = [C.c_int, _dp, C.c_int, _dp, _dp, _dp]
     L.afesp_read_eri_text.argtypes = [C.c_void_p, C.c_char_p, i64, _opt, C.POINTER(i64)]
     L.afesp_write_fcidump.argtypes = [C.c_void_p, C.c_char_p, i64, C.POINTER(i64)]
@@ -933,6 +936,13 @@ class Engine:
         d1 = self.so_tensor("D1")
         return np.concatenate([d1[:, 0], d1[0, 0] - d1[0, :]])
 
+    def so_abs_levels(self):
+        """The levels of the state's o + v spin orbitals themselves, occupied first (so_levels gives them relative to the first virtual one,
+        which serves differences of as many occupied as virtual levels only)"""
+        buf = np.zeros(self.so_o + self.so_v)
+        self._chk(self.L.afesp_ccsd_so_get_tensor(self.h, b"levels", buf, buf.size))
+        return buf
+
     def so_ntriples(self):
         return self.L.afesp_ccsd_so_t_ntriples(self.so_o)
 
@@ -1288,6 +1298,33 @@ class Engine:
         self._chk(self.L.afesp_ccsd_so_eom_ipea_dyson(self.h, sector, k, *ptrs, *d))
         shape = lambda y: None if y is None else (y.copy() if single else y.reshape(k, n))
         return shape(outs[0]), shape(outs[1])
+
+    def so_eom_ipea_t_nitems(self, sector):
+        """How many items the sector's triples correction runs over: the triples i<j<k of do_ccsd_t_spinorb's list (IP) or the pairs i<j
+        numbered j (j - 1) / 2 + i (EA)"""
+        return int(self.L.afesp_ccsd_so_eom_ipea_t_nitems(sector, self.so_o))
+
+    def so_eom_ipea_t(self, sector, omega, L, R, begin=0, end=None):
+        """The non-iterative triples correction to EOM-IP-CCSD (sector 1) or EOM-EA-CCSD (sector 2) roots: omega[ns],
+        L = [(l1, l2)] and R = [(r1, r2)] per state in the sector's layout, biorthonormal (afesp_amd.eom.biorthonormalise_ipea)
+        -> delta[ns] over the items [begin, end).  All states in one call; writes nothing of the state."""
+        if end is None:
+            end = self.so_eom_ipea_t_nitems(sector)
+        omega = np.ascontiguousarray(np.atleast_1d(np.asarray(omega, dtype=np.float64)))
+        ns = omega.size
+        if len(L) != ns or len(R) != ns:
+            raise ValueError("so_eom_ipea_t: one left and one right vector per root")
+        cat = lambda vecs, part: np.ascontiguousarray(np.concatenate([_f(x[part]) for x in vecs])) if ns else np.zeros(0)
+        l1, l2, r1, r2 = cat(L, 0), cat(L, 1), cat(R, 0), cat(R, 1)
+        if sector in (1, 2):
+            sh1, sh2 = self._eom_shapes(sector)
+            n1, n2 = int(np.prod(sh1)), int(np.prod(sh2))
+            if ns and (l1.size != ns * n1 or r1.size != ns * n1 or l2.size != ns * n2 or r2.size != ns * n2):
+                raise ValueError(f"so_eom_ipea_t: vectors are not laid out as {sh1} / {sh2} of this state's sector")
+        out = np.zeros(max(ns, 1))
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+        self._chk(self.L.afesp_ccsd_so_eom_ipea_t(self.h, sector, ns, ptr(omega), ptr(l1), ptr(l2), ptr(r1), ptr(r2), begin, end, ptr(out)))
+        return out[:ns]
 
     # the reference coupling of right EE vectors and the bilinear density of a left and a right pair: they need the Lambda state only
     def so_eom_ref_coupling(self, r1, r2):

@@ -393,3 +393,49 @@ def table(omega, info):
         lines.append(f"  {k + 1:4d}  {w:16.10f}  {w * HARTREE_EV:16.8f}  {info['r1_norm2'][k]:9.6f}  {info['resnorm'][k]:11.3e}")
     lines.append(f"  sigma builds: {info['nsigma']}")
     return "\n".join(lines)
+
+
+# ---------------------------------------------------------------------------------------------------------------- triples correction, IP / EA
+def ipea_triples_min_gap(sector, omega, levels, o):
+    """|omega - D_eps| per root at the smallest D_eps of the sector's 3h2p / 3p2h determinants: e_a + e_b - e_i - e_j - e_k from the three
+    highest occupied and the two lowest virtual levels (IP), e_a + e_b + e_c - e_i - e_j from the two highest occupied and the three lowest
+    virtual ones (EA) -- the denominator a root from below meets first"""
+    lev = np.asarray(levels, dtype=np.float64)
+    eo, ev = np.sort(lev[:o]), np.sort(lev[o:])
+    omega = np.atleast_1d(np.asarray(omega, dtype=np.float64))
+    no, nv = (3, 2) if sector == SECTOR_IP else (2, 3)
+    if eo.size < no or ev.size < nv:
+        return np.full(omega.size, np.inf)
+    return np.abs(omega - float(ev[:nv].sum() - eo[-no:].sum()))
+
+
+def _so_eom_ipea_triples_correction(eng, sector, omega, L, R, begin, end, levels):
+    who = "so_eom_ip_triples_correction" if sector == SECTOR_IP else "so_eom_ea_triples_correction"
+    omega = np.atleast_1d(np.asarray(omega, dtype=np.float64))
+    if not (len(omega) == len(L) == len(R)):
+        raise ValueError(f"{who}: omega, L and R differ in length")
+    for k in range(len(omega)):
+        ov = dot_ipea(L[k], R[k])
+        if abs(ov - 1.0) > 1e-8:
+            raise ValueError(f"{who}: <L, R> of root {k + 1} is {ov:.12f}, not 1: biorthonormalise_ipea the vectors first")
+    delta = eng.so_eom_ipea_t(sector, omega, L, R, begin, end)
+    if levels is None:
+        levels = eng.so_abs_levels()      # (2 - 3 or 3 - 2 levels: a common shift does not cancel)
+    gap = ipea_triples_min_gap(sector, omega, levels, eng.so_o)
+    info = dict(min_gap=gap, intruder=[k for k in range(len(omega)) if gap[k] < INTRUDER_GAP])
+    return delta, omega + delta, info
+
+
+def so_eom_ip_triples_correction(eng, omega, L, R, begin=0, end=None, levels=None):
+    """The non-iterative 3h2p correction to the EOM-IP-CCSD ionisation potentials omega from biorthonormal left vectors L
+    (biorthonormalise_ipea) and right vectors R, all roots in one library call -> (delta, omega + delta, info).  Refuses vectors with
+    |<L_k, R_k> - 1| > 1e-8 in the sector's metric.  info["min_gap"]: the smallest |omega_k - (e_a + e_b - e_i - e_j - e_k)| from the
+    levels (the state's Fock diagonal, fetched unless given); info["intruder"]: the roots whose gap is below INTRUDER_GAP.  A sub-range
+    [begin, end) of the triples i<j<k gives that shard's part of delta (ranks add theirs up).  triples_table prints the result."""
+    return _so_eom_ipea_triples_correction(eng, SECTOR_IP, omega, L, R, begin, end, levels)
+
+
+def so_eom_ea_triples_correction(eng, omega, L, R, begin=0, end=None, levels=None):
+    """The same for the EOM-EA-CCSD electron affinities: the 3p2h correction, the gap |omega_k - (e_a + e_b + e_c - e_i - e_j)|, shards over
+    the pairs i<j"""
+    return _so_eom_ipea_triples_correction(eng, SECTOR_EA, omega, L, R, begin, end, levels)

@@ -57,6 +57,7 @@ class SystemIn:
     eom_ip_nroots: int = 0         # ... this many EOM-IP-CCSD ionisation potentials; 0 = off
     eom_ea_nroots: int = 0          # ... this many EOM-EA-CCSD electron affinities; 0 = off
     eom_ipea_left: bool = False     # ... and the left eigenvectors and pole strengths of those roots (eom.so_eom_ipea_properties); needs one of the two > 0
+    eom_ipea_triples: bool = False  # ... and the non-iterative triples correction to those roots (eom.so_eom_ip_triples_correction / _ea_); needs eom_ipea_left
     # derived by the calc_type switch (src/system.f90:116-165)
     level: str = "CCSD(T)"        # one of RHF, MP2, CCSD, CCSD(T)
     restricted: bool = True
@@ -226,6 +227,11 @@ def read_els_in(path: str) -> SystemIn:
     if sysin.eom_ipea_left and sysin.eom_ip_nroots == 0 and sysin.eom_ea_nroots == 0:
         raise ValueError("eom_ipea_left needs eom_ip_nroots > 0 or eom_ea_nroots > 0: the left eigenvectors and pole strengths are those of "
                          "the EOM-IP-CCSD / EOM-EA-CCSD roots they ask for!")
+    if not isinstance(sysin.eom_ipea_triples, bool):
+        raise ValueError("invalid input file format!")
+    if sysin.eom_ipea_triples and not (sysin.eom_ipea_left and (sysin.eom_ip_nroots > 0 or sysin.eom_ea_nroots > 0)):
+        raise ValueError("eom_ipea_triples needs eom_ipea_left and eom_ip_nroots > 0 or eom_ea_nroots > 0: the triples correction contracts "
+                         "the left and right vectors of the EOM-IP-CCSD / EOM-EA-CCSD roots!")
     return sysin
 
 

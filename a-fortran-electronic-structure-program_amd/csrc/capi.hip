@@ -14,6 +14,7 @@
 #include "density2_so.h"
 #include "relax_so.h"
 #include "eom_ipea_so.h"
+#include "eom_ipea_t_so.h"
 #include "response_so.h"
 #include "davidson_test.h"
 #include "small_eig.h"
@@ -166,7 +167,7 @@ int eom_iterate_entry(afesp_ctx* ctx, const char* who, EomKind kind, const int* 
 
 extern "C" {
 
-int afesp_version(void) { return 7; }
+int afesp_version(void) { return 8; }
 int64_t afesp_neri(int64_t nbasis) { return neri_of(nbasis); }
 
 int afesp_ctx_create(int device, afesp_ctx** out)
@@ -953,6 +954,14 @@ int afesp_ccsd_so_eom_t(afesp_ctx* ctx, int nstates, const double* omega, const 
                         const double* r2, int64_t t_begin, int64_t t_end, double* delta)
 {
     return entry(ctx, [&](Context& cx) { so_eom_triples(cx, ctx->sv.so, nstates, omega, l1, l2, r1, r2, t_begin, t_end, delta); });
+}
+
+// ---- the triples correction to EOM-IP / EOM-EA roots (eom_ipea_t_so.h)
+int64_t afesp_ccsd_so_eom_ipea_t_nitems(int sector, int nocc) { return so_eom_sector_ok(sector) ? so_eom_ipea_t_items(sector, nocc) : 0; }
+int afesp_ccsd_so_eom_ipea_t(afesp_ctx* ctx, int sector, int nstates, const double* omega, const double* l1, const double* l2,
+                             const double* r1, const double* r2, int64_t begin, int64_t end, double* delta)
+{
+    return entry(ctx, [&](Context& cx) { so_eom_ipea_triples(cx, ctx->sv.so, sector, nstates, omega, l1, l2, r1, r2, begin, end, delta); });
 }
 
 // ---------------------------------------------------------------- open-shell (UHF-based) path

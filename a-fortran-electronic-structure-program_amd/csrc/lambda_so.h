@@ -3,6 +3,7 @@
 // division and L(t, l) = E(t) + sum l1 R1 + 1/4 sum l2 R2, the Lambda residual is G = dL/dt = X - D l; one iteration is the Jacobi step
 // l <- l + G / D = X / D.  Everything in X that depends on t alone is built once (so_lambda_init) for one amp_epoch of the state.
 #pragma once
+#include <vector>
 #include "ccsd_so.h"
 
 namespace afesp {
@@ -78,5 +79,35 @@ double so_lambda_triples(Context& cx, SOState& s, int64_t t_begin, int64_t t_end
 void so_eom_triples(Context& cx, SOState& s, int nstates, const double* omega, const double* l1, const double* l2, const double* r1,
                     const double* r2, int64_t t_begin, int64_t t_end, double* delta);
 void preload_lambda_so();
+
+// afesp_profile on the spin-orbital drivers: three events per chunk (before the products, between them and the orbit pass, after it), read
+// once the call's result is on the host; adds to Context::prof_gemm_ms / prof_orbit_ms as the spin-free driver does.  Nothing without it.
+struct SOStamps {
+    Context& cx;
+    std::vector<hipEvent_t> evs;
+    explicit SOStamps(Context& c) : cx(c) {}
+    void stamp()
+    {
+        if (!cx.prof) return;
+        hipEvent_t e;
+        AFESP_HIP(hipEventCreate(&e));
+        AFESP_HIP(hipEventRecord(e, cx.stream));
+        evs.push_back(e);
+    }
+    void read()
+    {
+        if (!evs.empty()) AFESP_HIP(hipEventSynchronize(evs.back()));
+        for (size_t q = 0; q + 2 < evs.size(); q += 3) {
+            float a = 0.f, b = 0.f;
+            AFESP_HIP(hipEventElapsedTime(&a, evs[q], evs[q + 1]));
+            AFESP_HIP(hipEventElapsedTime(&b, evs[q + 1], evs[q + 2]));
+            cx.prof_gemm_ms += a;
+            cx.prof_orbit_ms += b;
+            cx.prof_gemm_launches += 1;
+            cx.prof_orbit_launches += 1;
+        }
+    }
+    ~SOStamps() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); }
+};
 
 }  // namespace afesp

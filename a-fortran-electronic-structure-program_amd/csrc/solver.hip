@@ -464,6 +464,21 @@ void Solver::so_fetch_tensor(Context& cx, const char* name, double* out, int64_t
             cx.sync();
             return;
         }
+    if (!strcmp(name, "levels")) {   // the level of every spin orbital, occupied first: lev of a UHF- or Fock-fed state, the spatial e of an RHF-fed one
+        const int64_t o = s.o, n = (int64_t)s.o + s.v;
+        if (!s.ready || (!s.lev && !s.e)) throw Error(1, "afesp_ccsd_so_get_tensor: no spin-orbital state holds levels");
+        if (n > capacity) throw Error(1, "afesp_ccsd_so_get_tensor: buffer too small for levels");
+        if (s.lev) {
+            AFESP_HIP(hipMemcpyAsync(out, s.lev, sizeof(double) * n, hipMemcpyDeviceToHost, cx.stream));
+            cx.sync();
+        } else {
+            std::vector<double> e((size_t)(n / 2));
+            AFESP_HIP(hipMemcpyAsync(e.data(), s.e, sizeof(double) * e.size(), hipMemcpyDeviceToHost, cx.stream));
+            cx.sync();
+            for (int64_t p = 0; p < n; ++p) out[p] = e[(size_t)(p < o ? p / 2 : (p - o) / 2 + o / 2)];   // (interleaved spins: ipea_level)
+        }
+        return;
+    }
     for (auto& e : tab)
         if (!strcmp(e.n, name)) {
             if (!e.t->d) throw Error(1, std::string("afesp_ccsd_so_get_tensor: this state holds no ") + name + " (afesp_ccsd_uso_init_fock makes one that does)");

@@ -100,7 +100,7 @@ hipError_t triples_read_orbit_stamps(unsigned long long* out, int n)
 
 
 // out[q] += sum of partial[q][0..nblk) for q < nq, two stages when there are many partials; `tmp` holds nq * 128 doubles
-static void sum_partials(Context& cx, double* out, const double* partial, int nq, int nblk, double* tmp)
+void sum_partials(Context& cx, double* out, const double* partial, int nq, int nblk, double* tmp)
 {
     if (nblk > 8192) {
         AFESP_KLAUNCH(triples_sum_kernel, dim3(nq, 128), dim3(256), 0, cx.stream, tmp, partial, nblk);
@@ -343,7 +343,7 @@ static std::vector<int64_t> assemble_pool(Context& cx, int64_t nblocks, int64_t 
 }
 
 static bool fused_use_tg(int o, int v);
-static int64_t device_pool_budget();
+int64_t device_pool_budget();
 
 // Plan of the spin-orbital (T): i<j<k, three blocks per triple; one tgemm_kernel launch per chunk (or, under AFESP_T_GEMM=gett, one
 // gather-GEMM launch per integral slab and chunk).
@@ -537,7 +537,7 @@ static int fused_block_size(int o, int v, bool cr, int64_t budget_bytes)
     return best;
 }
 
-static int64_t device_pool_budget()
+int64_t device_pool_budget()
 {
     size_t mem_free = 0, mem_total = 0;
     AFESP_HIP(hipMemGetInfo(&mem_free, &mem_total));
@@ -1153,36 +1153,6 @@ __global__ void so_levels_kernel(double* e_so, const double* e, int n2)
     if (x < n2) e_so[x] = e[x / 2];
 }
 
-// afesp_profile on the spin-orbital drivers: three events per chunk (before the products, between them and the orbit pass, after it), read
-// once the call's result is on the host; adds to Context::prof_gemm_ms / prof_orbit_ms as the spin-free driver does.  Nothing without it.
-struct SOStamps {
-    Context& cx;
-    std::vector<hipEvent_t> evs;
-    explicit SOStamps(Context& c) : cx(c) {}
-    void stamp()
-    {
-        if (!cx.prof) return;
-        hipEvent_t e;
-        AFESP_HIP(hipEventCreate(&e));
-        AFESP_HIP(hipEventRecord(e, cx.stream));
-        evs.push_back(e);
-    }
-    void read()
-    {
-        if (!evs.empty()) AFESP_HIP(hipEventSynchronize(evs.back()));
-        for (size_t q = 0; q + 2 < evs.size(); q += 3) {
-            float a = 0.f, b = 0.f;
-            AFESP_HIP(hipEventElapsedTime(&a, evs[q], evs[q + 1]));
-            AFESP_HIP(hipEventElapsedTime(&b, evs[q + 1], evs[q + 2]));
-            cx.prof_gemm_ms += a;
-            cx.prof_orbit_ms += b;
-            cx.prof_gemm_launches += 1;
-            cx.prof_orbit_launches += 1;
-        }
-    }
-    ~SOStamps() { for (hipEvent_t e : evs) (void)hipEventDestroy(e); }
-};
-
 // The t-side operand copies of the spin-orbital (T) in the cached buffers t_vt / t_tt / t_vs / t_eso, rebuilt only when the record
 // Context::t_ops_* does not name this state, its amplitude epoch and the scratch epoch (shared by so_triples and so_lambda_triples).
 struct SOTOperands { Tensor vt, tt, vs; double* e_so; };
@@ -1254,7 +1224,7 @@ static void so_chunk_products(Context& cx, const TriplesPlan* p, const TriplesPl
     }
 }
 
-static void so_triples_guard(const SOState& s, const char* who)
+void so_triples_guard(const SOState& s, const char* who)
 {
     if (!s.ready) throw Error(1, std::string(who) + ": no converged spin-orbital CCSD state in this context");
     // (T) is defined in (semi)canonical orbitals only: a guard, not a tolerance

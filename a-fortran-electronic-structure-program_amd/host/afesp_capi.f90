@@ -28,7 +28,7 @@ module afesp_capi
              afesp_ccsd_so_eom_ipea_iterate, afesp_ccsd_so_eom_ipea_get_vector, AFESP_EOM_IP, AFESP_EOM_EA, &
              afesp_ccsd_so_eom_ipea_lsigma, afesp_ccsd_so_eom_ipea_left_init, afesp_ccsd_so_eom_ipea_left_guess, &
              afesp_ccsd_so_eom_ipea_left_set_guess, afesp_ccsd_so_eom_ipea_left_iterate, afesp_ccsd_so_eom_ipea_left_get_vector, &
-             afesp_ccsd_so_eom_ipea_dyson, &
+             afesp_ccsd_so_eom_ipea_dyson, afesp_ccsd_so_eom_ipea_t, afesp_ccsd_so_eom_ipea_t_nitems, &
              afesp_ccsd_so_response_init, afesp_ccsd_so_response_iterate, afesp_ccsd_so_response_function, &
              afesp_ccsd_so_response_init_complex, afesp_ccsd_so_response_function_complex, &
              AFESP_COMM_RCCL, AFESP_COMM_HOST
@@ -775,7 +775,25 @@ module afesp_capi
          real(c_double), intent(out) :: delta(*)
          integer(c_int) :: rc
       end function
-      !> a named tensor of the spin-orbital state (name NUL-terminated; 'D1': the singles denominators e_i - e_a, (o, v))
+      !> the non-iterative triples correction to EOM-IP (sector 1) / EOM-EA (sector 2) roots over the items [begin, end): IP the triples
+      !> i<j<k of afesp_ccsd_so_t's list, EA the pairs i<j numbered j (j - 1) / 2 + i; nstates vectors in the sector's layout one after the other
+      function afesp_ccsd_so_eom_ipea_t(ctx, sector, nstates, omega, l1, l2, r1, r2, t_begin, t_end, delta) &
+         bind(C, name='afesp_ccsd_so_eom_ipea_t') result(rc)
+         import :: c_int, c_int64_t, c_double, c_ptr
+         type(c_ptr), value :: ctx
+         integer(c_int), value :: sector, nstates
+         real(c_double), intent(in) :: omega(*), l1(*), l2(*), r1(*), r2(*)
+         integer(c_int64_t), value :: t_begin, t_end
+         real(c_double), intent(out) :: delta(*)
+         integer(c_int) :: rc
+      end function
+      function afesp_ccsd_so_eom_ipea_t_nitems(sector, nocc) bind(C, name='afesp_ccsd_so_eom_ipea_t_nitems') result(n)
+         import :: c_int, c_int64_t
+         integer(c_int), value :: sector, nocc
+         integer(c_int64_t) :: n
+      end function
+      !> a named tensor of the spin-orbital state (name NUL-terminated; 'D1': the singles denominators e_i - e_a, (o, v);
+      !> 'levels': the levels of the o + v spin orbitals themselves, occupied first)
       function afesp_ccsd_so_get_tensor(ctx, name, buf, capacity) bind(C, name='afesp_ccsd_so_get_tensor') result(rc)
          import :: c_int, c_int64_t, c_double, c_ptr, c_char
          type(c_ptr), value :: ctx

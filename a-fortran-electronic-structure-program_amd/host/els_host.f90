@@ -69,6 +69,8 @@ module host_config
       integer :: eom_ip_nroots = 0, eom_ea_nroots = 0
       ! ... and the left eigenvectors and pole strengths of those roots (needs one of the two > 0)
       logical :: eom_ipea_left = .false.
+      ! ... and the non-iterative triples correction to those roots from their left and right vectors (needs eom_ipea_left)
+      logical :: eom_ipea_triples = .false.
       ! after a converged spin-orbital CCSD: the EOM-CCSD polarisability alpha(omega) of the operators in dipx.dat / dipy.dat / dipz.dat
       ! (AO basis, the format of t.dat) at the n_polar_omega real frequencies polar_omega (default: the static one)
       logical :: cc_polar = .false.
@@ -90,14 +92,14 @@ contains
       integer :: n_frozen_core, n_frozen_virt, fno_n_virt, eom_nroots, eom_ip_nroots, eom_ea_nroots
       real(dp) :: fno_occ_tol
       logical :: write_fcidump, scf_read_guess, scf_write_guess, there, frozen_core, fcidump_active, fcidump_in, cc_density, cc_lambda_t
-      logical :: eom_left, eom_triples, cc_rdm2, cc_relaxed, cc_polar, eom_ipea_left
+      logical :: eom_left, eom_triples, cc_rdm2, cc_relaxed, cc_polar, eom_ipea_left, eom_ipea_triples
       real(dp) :: polar_omega(8), polar_gamma
       integer :: polar_c6_npts
       real(dp), parameter :: omega_unset = huge(1.0_dp)
       namelist /elsinput/ calc_type, scf_e_tol, scf_d_tol, scf_diis_n_errmat, ccsd_e_tol, ccsd_t_tol, &
          ccsd_diis_n_errmat, scf_maxiter, ccsd_maxiter, write_fcidump, scf_read_guess, scf_write_guess, charge, multiplicity, &
          frozen_core, n_frozen_core, n_frozen_virt, fno_n_virt, fno_occ_tol, fcidump_active, fcidump_in, &
-         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, eom_triples, eom_ipea_left, cc_rdm2, cc_relaxed, &
+         cc_density, cc_lambda_t, eom_nroots, eom_ip_nroots, eom_ea_nroots, eom_left, eom_triples, eom_ipea_left, eom_ipea_triples, cc_rdm2, cc_relaxed, &
          cc_polar, polar_omega, polar_gamma, polar_c6_npts
       type(run_config) :: d
       calc_type = d%calc_type; scf_e_tol = d%scf_e_tol; scf_d_tol = d%scf_d_tol; ccsd_e_tol = d%ccsd_e_tol
@@ -110,7 +112,7 @@ contains
       fcidump_in = d%fcidump_in; cc_density = d%cc_density; eom_nroots = d%eom_nroots
       cc_lambda_t = d%cc_lambda_t; cc_rdm2 = d%cc_rdm2; cc_relaxed = d%cc_relaxed
       eom_ip_nroots = d%eom_ip_nroots; eom_ea_nroots = d%eom_ea_nroots; eom_left = d%eom_left; eom_triples = d%eom_triples
-      eom_ipea_left = d%eom_ipea_left
+      eom_ipea_left = d%eom_ipea_left; eom_ipea_triples = d%eom_ipea_triples
       cc_polar = d%cc_polar; polar_omega = omega_unset
       polar_gamma = d%polar_gamma; polar_c6_npts = d%polar_c6_npts
       inquire (file='els.in', exist=there)
@@ -235,6 +237,10 @@ contains
       if (eom_ipea_left .and. eom_ip_nroots == 0 .and. eom_ea_nroots == 0) call fail('system::read_system_in', &
          'eom_ipea_left needs eom_ip_nroots > 0 or eom_ea_nroots > 0: the left eigenvectors and pole strengths are those of '// &
          'the EOM-IP-CCSD / EOM-EA-CCSD roots they ask for!')
+      cfg%eom_ipea_triples = eom_ipea_triples
+      if (eom_ipea_triples .and. .not. (eom_ipea_left .and. (eom_ip_nroots > 0 .or. eom_ea_nroots > 0))) call fail('system::read_system_in', &
+         'eom_ipea_triples needs eom_ipea_left and eom_ip_nroots > 0 or eom_ea_nroots > 0: the triples correction contracts '// &
+         'the left and right vectors of the EOM-IP-CCSD / EOM-EA-CCSD roots!')
       if (cfg%rohf) then   ! no ROHF SCF here: the orbitals come from a file, and a frozen core reaches this path as an active-space file
          if (.not. fcidump_in) call fail('system::read_system_in', trim(calc_type)// &
             ' needs fcidump_in = .true.: there is no ROHF SCF, the restricted open-shell orbitals come from a FCIDUMP!')
@@ -2328,6 +2334,76 @@ contains
             abs(omega_l(k) - omega(k)), res_l(k), sum(dl(:, k)*dr(:, k))
       end do
       write (out, '(96("-"))')
+      if (cfg%eom_ipea_triples) then
+         if (sector == AFESP_EOM_IP) then
+            call eom_ipea_triples_report(sector, what, nr, int(n1), nso - int(n1), omega, b1, b2, r1, r2)
+         else
+            call eom_ipea_triples_report(sector, what, nr, nso - int(n1), int(n1), omega, b1, b2, r1, r2)
+         end if
+      end if
+   end subroutine
+   !> eom_ipea_triples: the non-iterative triples correction to the nr roots of a sector from the biorthonormal left vectors b1 / b2 and the
+   !> right vectors r1 / r2 of eom_ipea_left_report.  All roots go to the library in one call on this rank's shard of the sector's items
+   !> (IP: the triples i<j<k; EA: the pairs i<j), and the shards are summed as in the (T) branches.  A root whose omega comes within 0.05 Eh
+   !> (a diagnostic constant) of the smallest 3h2p / 3p2h denominator is flagged.
+   subroutine eom_ipea_triples_report(sector, what, nr, o, v, omega, b1, b2, r1, r2)
+      integer(c_int), intent(in) :: sector
+      character(6), intent(in) :: what
+      integer, intent(in) :: nr, o, v
+      real(dp), intent(in) :: omega(:), b1(:, :), b2(:, :), r1(:, :), r2(:, :)
+      real(dp), parameter :: hartree_ev = 27.211386245988_dp, intruder_gap = 0.05_dp
+      real(dp), allocatable :: red(:), d1(:, :), eo(:), ev(:)
+      integer :: k, a, no, nv
+      integer(c_int64_t) :: t_lo, t_hi
+      integer(c_int) :: rc_mine
+      character(512) :: my_error
+      real(dp) :: tt, lowest, gap
+      tt = seconds()
+      allocate (red(nr + 1))
+      ! one call for all roots on this rank's shard, then the flagged sum over the ranks
+      t_hi = afesp_ccsd_so_eom_ipea_t_nitems(sector, int(o, c_int))
+      t_lo = (int(rank, c_int64_t)*t_hi)/world; t_hi = (int(rank + 1, c_int64_t)*t_hi)/world
+      red = 0.0_dp
+      rc = afesp_ccsd_so_eom_ipea_t(ctx, sector, int(nr, c_int), omega, b1, b2, r1, r2, t_lo, t_hi, red)
+      if (world > 1) then
+         rc_mine = rc; my_error = ''
+         if (rc_mine /= 0) then; my_error = afesp_error_text(ctx); red = 0.0_dp; end if
+         red(nr + 1) = merge(1.0_dp, 0.0_dp, rc_mine /= 0)
+         rc = afesp_allreduce_sum(ctx, red, int(nr + 1, c_int64_t))
+         if (rc_mine /= 0) call fail('eom_ipea::do_triples', trim(my_error))
+         if (rc == 0 .and. red(nr + 1) > 0.5_dp) call fail('eom_ipea::do_triples', 'the triples shard of another rank failed')
+      end if
+      if (rc /= 0) call fail('eom_ipea::do_triples', afesp_error_text(ctx))
+      ! the smallest denominator from the levels: the three (two) highest occupied and the two (three) lowest virtual ones for IP (EA)
+      no = merge(3, 2, sector == AFESP_EOM_IP); nv = merge(2, 3, sector == AFESP_EOM_IP)
+      lowest = huge(1.0_dp)
+      if (o >= no .and. v >= nv) then
+         allocate (d1(o + v, 1), eo(o), ev(v))
+         rc = afesp_ccsd_so_get_tensor(ctx, 'levels'//c_null_char, d1, int(o + v, c_int64_t))
+         if (rc /= 0) call fail('eom_ipea::levels', afesp_error_text(ctx))
+         eo = d1(1:o, 1); ev = d1(o + 1:o + v, 1)      ! the levels themselves: 2 - 3 (3 - 2) of them, a common shift does not cancel
+         lowest = 0.0_dp
+         do k = 1, no
+            a = maxloc(eo, 1); lowest = lowest - eo(a); eo(a) = -huge(1.0_dp)
+         end do
+         do k = 1, nv
+            a = minloc(ev, 1); lowest = lowest + ev(a); ev(a) = huge(1.0_dp)
+         end do
+      end if
+      write (out, '(1X, A)') 'Non-iterative triples correction to the '//what//'-CCSD roots'
+      write (out, '(100("-"))')
+      write (out, '(1X, A, 3X, A, 3X, A, 3X, A, 3X, A)') 'Root', '   omega (Eh)     ', 'delta omega (Eh)  ', ' omega+delta (Eh) ', ' omega+delta (eV) '
+      write (out, '(100("-"))')
+      do k = 1, nr
+         write (out, '(1X, I4, 3X, F18.12, 3X, F18.12, 3X, F18.12, 3X, F18.10)') k, omega(k), red(k), omega(k) + red(k), (omega(k) + red(k))*hartree_ev
+      end do
+      write (out, '(100("-"))')
+      do k = 1, nr
+         gap = abs(omega(k) - lowest)
+         if (gap < intruder_gap) write (out, '(1X, A, I0, A, F8.4, A)') 'Root ', k, ': omega is within ', gap, &
+            ' Eh of a triples denominator: the correction is not reliable'
+      end do
+      write (out, '(1X, A, 1X, F16.8, A)') 'Time taken for the '//what//'-CCSD triples correction:', seconds() - tt, 's'
    end subroutine
    subroutine print_fno_cut(asked, kept_occ, dropped_occ, any_dropped)
       integer, intent(in) :: asked

@@ -187,7 +187,8 @@ int afesp_ccsd_so_iterate(afesp_ctx* ctx, double e_tol, double t_tol, double* en
 int afesp_ccsd_so_diis(afesp_ctx* ctx);
 int afesp_ccsd_so_get_amplitudes(afesp_ctx* ctx, double* t1, double* t2);
 int afesp_ccsd_so_set_amplitudes(afesp_ctx* ctx, const double* t1, const double* t2);
-/* name: F_vv F_oo F_ov W_oooo (stored i,j,m,n) W_vvvv (stored e,f,a,b) W_ovvo tau tau_tilde oovv vvvv t1 t2.
+/* name: F_vv F_oo F_ov W_oooo (stored i,j,m,n) W_vvvv (stored e,f,a,b) W_ovvo tau tau_tilde oovv vvvv t1 t2, D1 (the singles denominators
+ * e_i - e_a), levels (the level of every spin orbital, nocc + nvirt of them, occupied first).
  * With a live Lambda state (afesp_ccsd_so_lambda_init; status 21 without one or with a stale one) also its t-fixed intermediates:
  * H_ov (m,e) H_oo (m,i) H_vv (a,e) H_oooo (m,n,i,j) H_vovv (a,m,e,f) H_ooov (m,n,i,e) H_ovvo (m,b,e,j) H_vvvo (H_abei stored i,e,a,b)
  * H_ovoo (m,b,i,j) lam_tau (i,j,a,b), and G_vv (a,e) G_oo (m,i) as of the last afesp_ccsd_so_lambda_iterate / afesp_ccsd_so_density */
@@ -525,6 +526,26 @@ int afesp_ccsd_so_eom_ipea_left_iterate(afesp_ctx* ctx, int sector, double tol, 
 int afesp_ccsd_so_eom_ipea_left_get_vector(afesp_ctx* ctx, int sector, int k, double* l1, double* l2);
 int afesp_ccsd_so_eom_ipea_dyson(afesp_ctx* ctx, int sector, int nvec, const double* l1, const double* l2, const double* r1, const double* r2,
                                  double* dl, double* dr);
+
+/* Non-iterative triples correction to EOM-IP-CCSD and EOM-EA-CCSD roots (afesp_version 8): afesp_ccsd_so_eom_t's correction
+ * in the ghost-orbital embedding that defines the sectors.  For a root w of sector 1 (IP) or 2 (EA), a left vector (l1, l2) and a right
+ * vector (r1, r2) in the sector's layout (IP x1[nocc], x2[nocc,nocc,nvirt]; EA x1[nvirt], x2[nocc,nvirt,nvirt]), H the bare Hamiltonian,
+ *   m(mu) = <mu| [H, R2] + [[H, R1], T2] |0>,   l(mu) = <0| (L1 + L2) H |mu>,   delta = sum_mu l(mu) m(mu) / (w - D_eps(mu))
+ * over the 3h2p determinants (IP: i<j<k, a<b, D_eps = e_a + e_b - e_i - e_j - e_k) or the 3p2h determinants (EA: i<j, a<b<c,
+ * D_eps = e_a + e_b + e_c - e_i - e_j).  This is the bare-H, lowest-order member of the EOM-IP/EA-CCSD* family.
+ * Items: for IP the triples i<j<k in afesp_ccsd_so_t's numbering (afesp_ccsd_so_t_ntriples of them); for EA the pairs i<j numbered
+ * j (j - 1) / 2 + i, the library's triangular pair numbering (nocc (nocc - 1) / 2 of them).  afesp_ccsd_so_eom_ipea_t_nitems returns
+ * the count (0 for a bad sector).  delta[s] is the sum over the items [begin, end), clipped to the list, so shards add up.
+ * The caller passes biorthonormal vectors (<l, r> = 1 in the sector's metric) and watches small |w - D_eps| itself.  nstates vectors follow
+ * one another in l1 / l2 / r1 / r2 (host).  Uses g, f, the levels and t2 only: no Lambda state and no Davidson state is needed, and nothing of
+ * t, lambda, the epochs, the Lambda, EOM or response states or the operand copies of (T) / Lambda-(T) / EOM-(T) is written.  Device memory:
+ * the images of a chunk of items, bounded by AFESP_T_POOL_GIB (at least one item: 6 nvirt^2 doubles for IP, 6 nvirt^3 for EA), beside
+ * copies of <vo||vv> and t2.  Statuses: 1 no spin-orbital state, a bad sector, a NULL argument, nstates < 1, a recording context, a Fock
+ * state whose oo / vv blocks are not diagonal, or a chunk that does not fit the free device memory.  An empty range gives zeros, and so
+ * do IP with nocc < 3 or nvirt < 2 and EA with nocc < 2 or nvirt < 3. */
+int afesp_ccsd_so_eom_ipea_t(afesp_ctx* ctx, int sector, int nstates, const double* omega, const double* l1, const double* l2,
+                             const double* r1, const double* r2, int64_t begin, int64_t end, double* delta /* [nstates] */);
+int64_t afesp_ccsd_so_eom_ipea_t_nitems(int sector, int nocc);
 
 /* Open-shell (UHF-based) path.  The reference accepts calc_type = "UHF" but runs its spin-orbital CCSD/(T) on doubled RHF
  * orbitals only (src/main.F90:48-52); these calls feed the same spin-orbital solver with canonical UHF orbitals.
