@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import orc
+from np_integrals import _hash_uniform, _packed, _tri, hashed_mp2, scalar_bound
 
 pytestmark = pytest.mark.gpu
 O, V = 20, 200
@@ -128,31 +129,13 @@ def test_one_amplitude_update_at_config_5_against_the_pinned_restatement(capsys)
     assert rc == 0, capsys.readouterr().out[-2000:]
 
 
-def _hash_uniform(k, seed):
-    """numpy twin of the device generator (csrc/capi.hip, splitmix64) used by afesp_synthetic_ao / afesp_synthetic_init"""
-    with np.errstate(over="ignore"):
-        x = (k.astype(np.uint64) + np.uint64(seed)) + np.uint64(0x9E3779B97F4A7C15)
-        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        x ^= x >> np.uint64(31)
-    return (x >> np.uint64(11)).astype(np.float64) / 9007199254740992.0
-
-
-def _tri(i, j):
-    hi, lo = np.maximum(i, j), np.minimum(i, j)
-    return hi * (hi + 1) // 2 + lo
-
-
-def _packed(i, j, k, l):
-    return _tri(_tri(i, j), _tri(k, l))          # integrals.f90:196-210, 0-based
-
-
 @pytest.mark.parametrize("blocked", [None, "1"])
 def test_ao2mo_full_size_with_a_signed_permutation(blocked, monkeypatch):
     """n = 220 (config 5), the whole tensor at once (what this size runs) and slab by slab (what n >= 256 runs; forced):
     with C a signed permutation matrix every MO integral is one AO integral with a sign,
     (pq|rs) = s_p s_q s_r s_s (P(p)P(q)|P(r)P(s)) -- exact in floating point, so the pair-squaring, the four quarter transforms over
-    unique pairs and the repack are checked element by element (200 000 sampled index quadruples) at the full size."""
+    unique pairs and the repack are checked element by element (200 000 sampled index quadruples) at the full size.  E(MP2), here
+    through the slice / denominator / sum launches of the large form, is held to np_integrals.hashed_mp2 at 1e-10 max(1, |E|)."""
     from afesp_amd.capi import Engine
     if blocked:
         monkeypatch.setenv("AFESP_AO2MO_BLOCKED", blocked)
@@ -166,7 +149,11 @@ def test_ao2mo_full_size_with_a_signed_permutation(blocked, monkeypatch):
     with Engine(0) as eng:
         eng.synthetic_ao(n, scale, seed)
         e_mp2, mo = eng.do_mp2_spatial(n, o, c, e, None)
-    assert np.isfinite(e_mp2)
+    # E(MP2) of the five-launch form (o^2 v^2 = 1.6e7 > 2^22) against the same sum formed on the host from the hash alone
+    ref, major = hashed_mp2(n, o, perm, sign, e, scale, seed)
+    print(f"E(MP2) {e_mp2:.15g} reference {ref:.15g} error / bound {abs(e_mp2 - ref) / scalar_bound(ref):.3g} |ref| / majorant {abs(ref) / major:.3g}")
+    assert 0.1 < abs(ref) < 1e4
+    assert abs(e_mp2 - ref) <= scalar_bound(ref)
     p, q, r, s = (rng.integers(0, n, 200_000) for _ in range(4))
     ao_index = _packed(perm[p], perm[q], perm[r], perm[s]).astype(np.uint64)
     expect = sign[p] * sign[q] * sign[r] * sign[s] * scale * (2.0 * _hash_uniform(ao_index, seed) - 1.0)
